@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the IBL-precompute hot path on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|ref]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c4|c2|ref] [--full] [--dump-outputs DIR]
   N > 1: either the launcher form (python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
          or plain `python bench.py --gpus N`: without WORLD_SIZE in the environment the script starts its N workers itself
          (a child `torch.distributed.run`, decided before anything touches the GPU) and exits with their code.
@@ -13,8 +13,11 @@ HotreloadShaders does (render.cpp:505-589).  With N ranks the (mip, face, row-ti
 cost-partitioned over the ranks (strong scaling: the job is fixed) and the output tiles are gathered
 to rank 0 with one grouped RCCL send/recv batch per step.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel,
-HIP-event timed on the stream it runs on) and `cpu_baseline` (the scalar C oracle timed on the host).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times
+the K steps and prints the headline (`value`, `ms_per_step`); `--full` adds `kernels` and `roofline`
+(dominant kernel, HIP-event timed on the stream it runs on), the shade / post / frame-loop / sweep / LUT
+extras and `cpu_baseline` (the scalar C oracle timed on the host).  `--dump-outputs DIR` writes the maps
+of the last timed step as .npy files (inputs are seeded: two builds compare output for output).
 """
 import argparse
 import ctypes as C
@@ -183,6 +186,31 @@ def cpu_baseline(env, W, spec_size, irr_size, budget_s=15.0):
     }
 
 
+DUMP_WHOLE_TEXELS = 1 << 20    # --dump-outputs: levels up to this many texels are written whole (16 MB) ...
+DUMP_SAMPLE_TEXELS = 1 << 19   # ... larger ones as this many seeded draws (duplicates dropped, ~8 MB)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, torch, spec_mem, irr_mem, level_offsets, spec_size, irr_size):
+    """What a caller of the timed path receives -- the prefiltered specular cube (every level) and the irradiance cube -- as float32
+    .npy files under d.  The texels sampled from a large level depend only on its size and index, so runs and builds compare file by file."""
+    os.makedirs(d, exist_ok=True)
+    files = {"irradiance": irr_mem.view(6, irr_size, irr_size, 4).cpu().numpy()}
+    for m, off in enumerate(level_offsets):
+        size = max(1, spec_size >> m)
+        n = 6 * size * size
+        level = spec_mem[off: off + n * 4].view(n, 4)
+        if n <= DUMP_WHOLE_TEXELS:
+            files[f"specular_mip{m}"] = level.view(6, size, size, 4).cpu().numpy()
+        else:
+            idx = np.unique(np.random.default_rng([0x5EED0D, size, m]).integers(0, n, DUMP_SAMPLE_TEXELS))
+            files[f"specular_mip{m}_sample"] = level.index_select(0, torch.from_numpy(idx).to(level.device)).cpu().numpy()
+    total = sum(a.nbytes for a in files.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs would write {total} bytes"
+    for name, a in files.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -209,7 +237,17 @@ def main():
                          "emissive.npy (uint8 [H][W][4], the RGBA8 attachments of render.cpp:680-687), depth.npy (float32 [H][W]) and "
                          "optionally camera.json {\"pos\": [x,y,z], \"ori_xyzw\": [..], \"fov\": deg}")
     ap.add_argument("--dry-launch", action="store_true", help="print the worker command `--gpus N` would start and exit 0 (no GPU, no torch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: per-kernel times and roofline, the shade / post / frame-loop / sweep / LUT "
+                         "extras (--no-shade, --no-c5 drop some) and the CPU baseline (--no-cpu-baseline drops it); off: set up, warm up, time "
+                         "the steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the maps the last step computed as DIR/<name>.npy (float32): irradiance.npy and "
+                         "specular_mip<m>.npy [6][s][s][4] for every level of at most 2^20 texels, specular_mip<m>_sample.npy [n][4] (a fixed, "
+                         "seeded set of texels) for the larger ones")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     # ---- N > 1 without a launcher: become the launcher.  Decided here, before torch / HIP are touched: the workers are CHILD
     # processes (never an exec from a process that has initialised the GPU), rank 0 of them prints the one JSON line.
@@ -247,7 +285,7 @@ def main():
         env = load_env(W, seed, workers=max(1, min(6, (os.cpu_count() or 8) // max(1, world))))
     gb_file = load_gbuffer_dir(args.gbuffer) if args.gbuffer else None
     c5_gbd = None
-    if not args.no_shade and not args.no_c5:                      # this rank's band of the 7680x4320 G-buffer (worker processes: before the GPU is touched)
+    if args.full and not args.no_shade and not args.no_c5:        # this rank's band of the 7680x4320 G-buffer (worker processes: before the GPU is touched)
         from pbrhip import synth
         c5_gbd = synth.synth_gbuffer_temple(7680, 4320, rows=(4320 * rank // world, 4320 * (rank + 1) // world),
                                             workers=max(1, min(16, (os.cpu_count() or 8) // max(1, world))))
@@ -429,7 +467,7 @@ def main():
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
-        for g_ in ((graph, graph2) if overlap else (graph,)):
+        for g_ in (((graph, graph2) if overlap else (graph,)) if args.full else ()):     # per-kernel times: --full only
             for i in range(L.GPUX_GraphTimedOpCount(g_)):
                 nm = L.GPUX_GraphTimedOpName(g_, i).decode()
                 op_ms.setdefault(nm, []).append(L.GPUX_GraphTimedOpMs(g_, i))
@@ -439,6 +477,8 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:                 # the maps of the last timed step (gathered on rank 0), before anything reruns the job
+        dump_outputs(args.dump_outputs, torch, spec_mem, irr_mem, [L.pbrk_level_offset(spec_size, m) * 4 for m in range(n_mips)], spec_size, irr_size)
 
     step_split = None
     if world > 1:       # per-rank compute time and (on rank 0: waiting for the slowest sender + the transfer itself) exchange time
@@ -543,7 +583,7 @@ def main():
                      "frac": k["frac"], "avg_ms": k["avg_ms"]} for k in kernels if k.get("bound") == "hbm"]
 
     extra = {}
-    if rank == 0 and not args.no_shade:
+    if rank == 0 and args.full and not args.no_shade:
         try:
             extra["shade"] = shade_bench(L, pbrhip, env_tex, world, gb_file=gb_file)
         except Exception as e:      # the headline number must not depend on the extra
@@ -569,7 +609,7 @@ def main():
         except Exception as e:
             extra["lut_c1_error"] = repr(e)
 
-    if not args.no_shade and not args.no_c5:                      # every rank takes part (screen bands + gather)
+    if args.full and not args.no_shade and not args.no_c5:        # every rank takes part (screen bands + gather)
         c5 = shade_c5_bench(L, pbrhip, env_tex, rank, world, backend, torch, dist, c5_gbd, frames=args.c5_frames, comm=comm)
         if rank == 0:
             extra["shade_c5"] = c5
@@ -606,7 +646,7 @@ def main():
             extra["mc_region_recomputed_wave_slices"] = [int(st[0]), int(st[1])]
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(env, W, spec_size, irr_size)
 
     if args.check and rank == 0:
@@ -675,8 +715,8 @@ def main():
                                                  f"procedural HDR cube {W}^2 x6 RGBA32F (seed {seed:#x}, RGBE round-tripped)"),
                        "texels_per_step": total_texels, "sample_evaluations_per_step": sample_evals,
                        "overlap": overlap, "parallelism": "single GPU" if world == 1 else f"{world} ranks, weighted linear partition of output rows (3-8 dispatches per rank), 1 grouped RCCL send/recv gather per step"},
-            "roofline": roofline, "roofline_hbm": roofline_hbm, "rates": rates, "step_split": step_split, "rccl": rccl_report, "kernels": kernels[:12],
-            "cpu_baseline": cpu, "extra": extra,
+            "roofline": roofline, "roofline_hbm": roofline_hbm if args.full else None, "rates": rates, "step_split": step_split, "rccl": rccl_report,
+            "kernels": kernels[:12] if args.full else None, "cpu_baseline": cpu, "extra": extra, "full": args.full,
         }
         print(json.dumps(out))
 

@@ -328,7 +328,7 @@ def test_bench_accepts_real_files_by_path(gpu, tmp_path):
     (gdir / "camera.json").write_text(json.dumps({"pos": [float(v) for v in gbd["cam_pos"]], "fov": 75.0}))
     env_vars = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     for hdr, layout, cube in ((strip, "cube strip", 96), (eq, "equirectangular", 256)):
-        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "ref", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-c5",
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--workload", "ref", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-c5",
                             "--check", "--hdr", str(hdr), "--gbuffer", str(gdir)], capture_output=True, text=True, timeout=900, env=env_vars, cwd=root)
         assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
         out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -338,6 +338,40 @@ def test_bench_accepts_real_files_by_path(gpu, tmp_path):
         assert out["inputs"]["gbuffer"]["width"] == 320 and out["extra"]["shade"]["mpixels_per_s_kernel"] > 0, out["extra"].get("shade_error")
         assert "320x180" in out["extra"]["shade"]["workload"]
         assert out["extra"]["check_max_rel_err_vs_oracle"] < 1e-4
+
+
+def test_bench_plain_run_dumps_the_maps_of_its_last_step(gpu, tmp_path):
+    """A plain `bench.py` run (no --full) times its steps and prints the headline without the per-kernel, extra and CPU-baseline
+    legs; `--dump-outputs DIR` writes the maps of the last timed step as float32 .npy files (64 MB at most), which match the oracle
+    on spot rows of the same seeded environment."""
+    import json, os, subprocess, sys
+    import pbr_oracle as O
+    from pbrhip import synth
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "dump"
+    env_vars = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "ref", "--steps", "2", "--warmup", "1", "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=900, env=env_vars, cwd=root)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0 and out["unit"] == "Mtexels/s" and out["higher_is_better"] is True
+    assert out["dtype"] == "f32" and out["full"] is False
+    assert out["kernels"] is None and out["roofline"] is None and out["cpu_baseline"] is None and "shade" not in out["extra"]
+    files = {f[:-4]: np.load(dump / f) for f in os.listdir(dump)}
+    assert set(files) == {"irradiance"} | {f"specular_mip{m}" for m in range(9)}
+    assert all(a.dtype == np.float32 for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+    pyr = O.build_pyramid(synth.synth_env(256, seed=0x5EED00AB))            # the `ref` workload's environment
+    for m in (0, 1, 2, 4):
+        size = 256 >> m
+        got = files[f"specular_mip{m}"]
+        assert got.shape == (6, size, size, 4)
+        for (f, y) in ((0, 0), (3, size // 2), (5, size - 1)):
+            want = O.prefilter_mip(pyr, 256, 256, m, faces=(f, f + 1), rows=(y, y + 1))[f, y]
+            err = np.abs(got[f, y].astype(np.float64) - want) / np.maximum(np.abs(want), 1e-3)
+            assert err.max() < REL, (m, f, y, err.max())
+    want = O.irradiance(pyr, 256, 32, faces=(2, 3), rows=(5, 6))[2, 5, :, :3]
+    got = files["irradiance"][2, 5, :, :3].astype(np.float64)
+    assert (np.abs(got - want) / np.maximum(np.abs(want), 1e-3)).max() < REL
 
 
 def test_soak_random_environments_and_rows(gpu):

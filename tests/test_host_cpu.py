@@ -45,12 +45,12 @@ def test_library_exports_every_declared_symbol(L):
     assert declared <= exported
 
 
-def test_header_enums_keep_reference_numbering():
+def test_header_enums_keep_reference_numbering(tmp_path):
     """Enum values are ABI (callers pass them by value)."""
     src = "#include \"gpux.h\"\n#include <stdio.h>\nint main(){printf(\"%d %d %d %d %d %d %d %d %zu %zu %zu\\n\", GPU_Format_RGBA8UN, GPU_Format_RG16F," \
           " GPU_Format_RGBA16F, GPU_Format_RGBA32F, GPU_Format_D32F_Or_X8D24UN, GPU_Format_BC5_UN, GPU_TextureFlag_Cubemap, GPU_BufferFlag_StorageBuffer," \
           " sizeof(GPU_Texture), sizeof(GPU_Buffer), sizeof(GPU_ShaderDesc)); return 0;}\n"
-    exe = "/tmp/pbr_enum_check"
+    exe = str(tmp_path / "pbr_enum_check")
     subprocess.run(["gcc", "-std=c11", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src, text=True, check=True)
     vals = subprocess.check_output([exe], text=True).split()
     assert vals == ["3", "6", "8", "12", "23", "29", "8", "4", "28", "16", "80"]

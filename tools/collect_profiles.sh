@@ -13,19 +13,19 @@ export TMPDIR=/tmp
 cd /tmp                                        # rocprofv3 scratch files go to the working directory
 B=$REPO/bench.py
 
-python3 $B --bounded-cut > "$OUT/${TAG}_bench.json"
+python3 $B --full --bounded-cut > "$OUT/${TAG}_bench.json"
 echo "[1/6] bench done"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$SCR/kt" -- python3 $B --no-cpu-baseline > "$OUT/${TAG}_bench_under_rocprof.json"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$SCR/kt" -- python3 $B --full --no-cpu-baseline > "$OUT/${TAG}_bench_under_rocprof.json"
 echo "[2/6] kernel trace done"
-rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$SCR/fetch" -- python3 $B --no-cpu-baseline --steps 1 --warmup 0 --no-shade > /dev/null
+rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d "$SCR/fetch" -- python3 $B --full --no-cpu-baseline --steps 1 --warmup 0 --no-shade > /dev/null
 echo "[3/6] FETCH_SIZE done"
-rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$SCR/write" -- python3 $B --no-cpu-baseline --steps 1 --warmup 0 --no-shade > /dev/null
+rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d "$SCR/write" -- python3 $B --full --no-cpu-baseline --steps 1 --warmup 0 --no-shade > /dev/null
 echo "[4/6] WRITE_SIZE done"
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES \
-    --output-format csv -d "$SCR/sq1" -- python3 $B --no-cpu-baseline --steps 1 --warmup 0 --c5-frames 2 > /dev/null
+    --output-format csv -d "$SCR/sq1" -- python3 $B --full --no-cpu-baseline --steps 1 --warmup 0 --c5-frames 2 > /dev/null
 echo "[5/6] SQ pass 1 done"
 rocprofv3 --kernel-trace --pmc SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE \
-    --output-format csv -d "$SCR/sq2" -- python3 $B --no-cpu-baseline --steps 1 --warmup 0 --c5-frames 2 > /dev/null
+    --output-format csv -d "$SCR/sq2" -- python3 $B --full --no-cpu-baseline --steps 1 --warmup 0 --c5-frames 2 > /dev/null
 echo "[6/6] SQ pass 2 done"
 python3 $REPO/tools/summarize_prof.py "$TAG" "$SCR/kt" "$SCR/fetch" "$SCR/write"
 python3 $REPO/tools/summarize_sq.py "$TAG" "$SCR/sq1" "$SCR/sq2"
