@@ -259,7 +259,7 @@ static inline GPU_Access GPU_Read(uint32_t binding) { GPU_Access x = { GPU_Acces
 static inline GPU_Access GPU_Write(uint32_t binding) { GPU_Access x = { GPU_AccessFlag_Write, binding }; return x; }                          /* [gpu.h:435] */
 static inline GPU_Access GPU_ReadWrite(uint32_t binding) { GPU_Access x = { GPU_AccessFlag_Read | GPU_AccessFlag_Write, binding }; return x; } /* [gpu.h:436] */
 
-GPU_API GPU_GraphicsPipeline* GPU_MakeGraphicsPipeline(const GPU_GraphicsPipelineDesc* desc);  /* [gpu.h:438] lighting_pass.glsl only */
+GPU_API GPU_GraphicsPipeline* GPU_MakeGraphicsPipeline(const GPU_GraphicsPipelineDesc* desc);  /* [gpu.h:438] full-screen passes + sun_depth_pass.glsl */
 GPU_API void GPU_DestroyGraphicsPipeline(GPU_GraphicsPipeline* pipeline);            /* [gpu.h:441] NULL ok */
 GPU_API GPU_ComputePipeline* GPU_MakeComputePipeline(GPU_PipelineLayout* layout, const GPU_ShaderDesc* cs);   /* [gpu.h:443] */
 GPU_API void GPU_DestroyComputePipeline(GPU_ComputePipeline* pipeline);              /* [gpu.h:446] NULL ok */
@@ -292,9 +292,11 @@ GPU_API void GPU_OpBeginRenderPass(GPU_Graph* graph);
 GPU_API void GPU_OpEndRenderPass(GPU_Graph* graph);
 GPU_API void GPU_OpBindDrawParams(GPU_Graph* graph, uint32_t draw_params);
 GPU_API void GPU_OpDraw(GPU_Graph* graph, uint32_t vertex_count, uint32_t instance_count, uint32_t first_vertex, uint32_t first_instance);
-GPU_API void GPU_OpDrawIndexed(GPU_Graph* graph, uint32_t index_count, uint32_t instance_count, uint32_t first_index, uint32_t vertex_offset, uint32_t first_instance);   /* unsupported (raster) */
-GPU_API void GPU_OpBindVertexBuffer(GPU_Graph* graph, GPU_Buffer* buffer);           /* [gpu.h:464] unsupported (raster) */
-GPU_API void GPU_OpBindIndexBuffer(GPU_Graph* graph, GPU_Buffer* buffer);            /* [gpu.h:465] unsupported (raster) */
+/* Indexed draws exist for the sun depth pass only (sun_depth_pass.glsl, depth-only render pass, render.cpp:993-1020): 32-bit indices,
+ * every draw of one pass instance rasterised as one K12 job at GPU_GraphSubmit; anywhere else: unsupported (raster). */
+GPU_API void GPU_OpDrawIndexed(GPU_Graph* graph, uint32_t index_count, uint32_t instance_count, uint32_t first_index, uint32_t vertex_offset, uint32_t first_instance);
+GPU_API void GPU_OpBindVertexBuffer(GPU_Graph* graph, GPU_Buffer* buffer);           /* [gpu.h:464] */
+GPU_API void GPU_OpBindIndexBuffer(GPU_Graph* graph, GPU_Buffer* buffer);            /* [gpu.h:465] uint32 indices */
 
 /* ================================ transfers =============================== */
 /* Texture<->buffer copies are tightly packed, row major, layers consecutive (gpu_vulkan.c:2925-2932). */

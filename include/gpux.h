@@ -108,4 +108,9 @@ GPU_API uint64_t GPUX_FoldedBlitCount(void);
 GPU_API void GPUX_SetGraphOverlap(int on);
 GPU_API uint64_t GPUX_OverlappedSubmitCount(void);
 
+/* ---- K12: the sun depth pass (sun_depth_pass.glsl through GPU_OpDrawIndexed).  Triangles the rasteriser skipped since
+ * the library was loaded: a vertex index past the bound vertex buffer, a non-finite transformed vertex, or a vertex outside the
+ * +-2^21-pixel guard band (where Vulkan would clip).  Counted on the device; the value includes every submission waited for. ---- */
+GPU_API uint64_t GPUX_RasterRejectedTriangles(void);
+
 #endif

@@ -206,6 +206,30 @@ GPU_Texture* PBR_PostBloomDownscale(PBR_PostProcess* pp);
 GPU_Texture* PBR_PostBloomUpscale(PBR_PostProcess* pp);
 uint32_t PBR_PostBloomPassCount(const PBR_PostProcess* pp);
 
+/* ---- sun shadow depth pass (N5 / K12): render.cpp:88-111 (pipeline), :677 + :725-729 (2048^2 D32F target and its depth-only
+ *      render pass), :995-1020 (per-frame clear + one indexed draw per part); asset_import.cpp:172-173 (merged buffers) ---- */
+typedef struct PBR_MeshPart { uint32_t first_index, index_count; } PBR_MeshPart;     /* RenderObjectPart's draw range */
+typedef struct PBR_Mesh PBR_Mesh;
+/* vertices: vertex_count x 11 floats (render.h:31-36 Vertex: position, normal, tangent, tex_coord); 32-bit indices */
+PBR_Mesh* PBR_MakeMesh(const float* vertices_11f, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count,
+                       const PBR_MeshPart* parts, uint32_t part_count);
+void PBR_DestroyMesh(PBR_Mesh* mesh);
+GPU_Buffer* PBR_MeshVertexBuffer(PBR_Mesh* mesh);
+GPU_Buffer* PBR_MeshIndexBuffer(PBR_Mesh* mesh);
+uint32_t PBR_MeshPartCount(const PBR_Mesh* mesh);
+
+typedef struct PBR_SunDepthPass PBR_SunDepthPass;
+PBR_SunDepthPass* PBR_MakeSunDepthPass(uint32_t size);                 /* reference: 2048 */
+void PBR_DestroySunDepthPass(PBR_SunDepthPass* pass);
+GPU_Texture* PBR_SunDepthTexture(PBR_SunDepthPass* pass);              /* D32F size^2: bind it as SUN_DEPTH_MAP (PBR_MakeLightingPassLive) */
+GPU_Buffer* PBR_SunDepthGlobalsBuffer(PBR_SunDepthPass* pass);         /* persistently mapped PBR_Globals */
+GPU_GraphicsPipeline* PBR_SunDepthPipeline(PBR_SunDepthPass* pass);
+GPU_RenderPass* PBR_SunDepthRenderPass(PBR_SunDepthPass* pass);
+GPU_PipelineLayout* PBR_SunDepthLayout(PBR_SunDepthPass* pass);        /* one buffer binding, "GLOBALS" */
+GPU_DescriptorSet* PBR_SunDepthDescriptorSet(PBR_SunDepthPass* pass);
+/* render.cpp:991 + 995-1020: copies globals (if not NULL) into the mapped buffer, clears the map to 1 and draws every part */
+void PBR_RecordSunDepthPass(PBR_SunDepthPass* pass, GPU_Graph* graph, const PBR_Mesh* mesh, const PBR_Globals* globals);
+
 #ifdef __cplusplus
 }
 #endif

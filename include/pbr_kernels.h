@@ -234,6 +234,33 @@ int pbrk_bloom_pass(const PbrkBloomArgs* args, void* stream);
  * passes of at most small_max_pixels target pixels; default 40000, env PBR_BLOOM_SMALL_MAX_PIXELS).  Negative = default. */
 void pbrk_bloom_set_thresholds(long long quad_min_pixels, long long small_max_pixels);
 
+/* ---- K12 (N5): the sun depth pass (sun_depth_pass.glsl: gl_Position = sun_space_from_world * vec4(p, 1), no fragment output, LESS
+ *      depth test + write into a D32F target) as a compute rasteriser.  The draws of one render-pass instance are one job: draw d
+ *      covers job triangles [first_tri, next draw's first_tri) and reads indices first_index + 3 t' + k (32-bit) of the index buffer,
+ *      vertex = index + vertex_offset.  Contract (coverage, tie rule, depth arithmetic, guard band): DESIGN.md K12.
+ *      Setup (one thread per triangle: transform, snap, reject, bin into 32 x 32-pixel tiles) then one workgroup per tile keeping the
+ *      per-pixel minimum in registers; no global atomics on the depth map, no read-back.  `scratch` holds pbrk_raster_scratch_bytes;
+ *      `draws` is device memory (PbrkRasterDraw[draw_count], first_tri ascending, every draw at least one triangle). ---- */
+typedef struct PbrkRasterDraw {
+    float m[16];                  /* sun_space_from_world, column-major, as snapshotted at submit */
+    uint32_t first_tri, first_index, vertex_offset, pad;
+} PbrkRasterDraw;
+typedef struct PbrkRasterArgs {
+    const void* vertices;         /* position = first 3 floats of each vertex */
+    uint32_t vertex_stride;       /* bytes, multiple of 4 */
+    uint32_t vertex_count;        /* vertices in the bound buffer: a larger vertex index skips its triangle (counted) */
+    const uint32_t* indices;
+    const PbrkRasterDraw* draws;
+    uint32_t draw_count, tri_count;
+    float* depth;                 /* width x height fp32, tight rows */
+    int width, height;            /* at most 16384 each */
+    void* scratch;
+    unsigned long long* rejected; /* device counter: += triangles skipped for an index, a non-finite value or the guard band */
+} PbrkRasterArgs;
+size_t pbrk_raster_scratch_bytes(uint32_t tri_count, int width, int height);
+int pbrk_raster_setup(const PbrkRasterArgs* args, void* stream);    /* K12.setup: clear bins, transform + bin, scan, fill */
+int pbrk_raster_tiles(const PbrkRasterArgs* args, void* stream);    /* K12.tiles: per-tile depth minimum, one store per pixel */
+
 /* ---- diagnostics: the device samplers of the widened passes evaluated at caller-supplied coordinates, so that tests can feed them
  *      NaN / inf / 1e30 / boundary values directly (a ray that has marched far away must never become an out-of-bounds read).
  *      which: 0 = LIGHTGRID (RGBA16F n^3, coords xyz), 1 = sampler2DShadow (R32F w x h, coords u, v, ref; result in out[0]),

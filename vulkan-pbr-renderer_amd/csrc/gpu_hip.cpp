@@ -48,7 +48,7 @@ static void gpu_fail(const char* fmt, ...) {
 // object model
 // ------------------------------------------------------------------------------------------
 enum BindKind { Bind_Texture, Bind_Sampler, Bind_Buffer, Bind_StorageImage };
-enum KernelId { Kernel_None = 0, Kernel_BrdfLut, Kernel_Irradiance, Kernel_Prefilter, Kernel_Lighting, Kernel_LightgridSweep, Kernel_TaaResolve, Kernel_FinalPost, Kernel_BloomDown, Kernel_BloomUp };
+enum KernelId { Kernel_None = 0, Kernel_BrdfLut, Kernel_Irradiance, Kernel_Prefilter, Kernel_Lighting, Kernel_LightgridSweep, Kernel_TaaResolve, Kernel_FinalPost, Kernel_BloomDown, Kernel_BloomUp, Kernel_SunDepth };
 
 struct GPU_Sampler { GPU_SamplerDesc desc; bool shared; };
 
@@ -85,9 +85,12 @@ struct GPU_DescriptorArena { std::vector<GPU_DescriptorSet*> sets; };
 
 struct GPU_ComputePipeline { GPU_PipelineLayout* layout; KernelId kernel; };
 struct GPU_RenderPass { GPU_RenderPassDesc desc; std::vector<GPU_TextureView> targets; };
-struct GPU_GraphicsPipeline { GPU_PipelineLayout* layout; GPU_RenderPass* pass; KernelId kernel; int shade_flags; bool blend_additive = false; };
+struct GPU_GraphicsPipeline { GPU_PipelineLayout* layout; GPU_RenderPass* pass; KernelId kernel; int shade_flags; bool blend_additive = false;
+                              uint32_t vertex_stride = 0; /* sun depth pass: bytes per vertex (gpu_vulkan.c:1745-1762) */ };
 
-enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear };
+enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster };
+// one GPU_OpDrawIndexed of the sun depth pass: job triangles [first_tri, first_tri + index_count / 3), matrix from the set's GLOBALS
+struct RasterDraw { GPU_DescriptorSet* set; uint32_t first_tri, first_index, vertex_offset; };
 struct Op {
     OpKind kind;
     std::string name;
@@ -112,8 +115,14 @@ struct Op {
     bool folded = false;
     TextureImpl* blend_tex = nullptr; uint32_t blend_mip = 0;
     bool skip_level0 = false;                      // Op_Clear of all levels whose level 0 the next op overwrites entirely
+    // sun depth raster job (Op_Raster): every indexed draw of one render-pass instance; buf = vertices, buf2 = indices, tex = target
+    std::vector<RasterDraw> draws;
+    uint32_t tri_count = 0, vertex_stride = 0;
+    int raster_slot = -1;                          // GPU_Graph::raster scratch of this job
 };
 struct DrawParams { GPU_GraphicsPipeline* pipeline; GPU_DescriptorSet* set; };
+// per raster job of a graph, kept across submissions: bins / records (device), the draw table (device + pinned staging)
+struct RasterScratch { void* dev = nullptr; size_t dev_bytes = 0; void* draws_dev = nullptr; PbrkRasterDraw* draws_host = nullptr; size_t draws_cap = 0; };
 struct GPU_Graph {
     hipStream_t stream = nullptr;
     hipStream_t cur = nullptr;                     // stream the op being executed launches on (stream, or a side stream)
@@ -134,6 +143,9 @@ struct GPU_Graph {
     GPU_RenderPass* preparing = nullptr; GPU_RenderPass* in_pass = nullptr;
     std::vector<DrawParams> draw_params;
     int bound_draw = -1;
+    BufferImpl* vertex_buffer = nullptr; BufferImpl* index_buffer = nullptr;     // GPU_OpBindVertexBuffer / GPU_OpBindIndexBuffer
+    int raster_op = -1;                            // index in ops of the raster job of the open render pass (-1: none yet)
+    std::vector<RasterScratch> raster; size_t raster_used = 0;
     // hipGraph replay (GPUX_SetGraphReplay): the executable graph of the previous submission, updated in place when the
     // next one has the same shape
     hipGraphExec_t exec = nullptr;
@@ -172,6 +184,8 @@ static struct {
     float prefilter_tol = 0.0f;                     // GPUX_SetPrefilterTolerance: 0 = exact sums (default)
     int kept_samples[32] = {0};                     // per output mip: samples kept by the last prefilter dispatch
     int replay = -1;                                // GPUX_SetGraphReplay: submissions go through an instantiated hipGraph (-1: PBR_GRAPH_REPLAY or 0)
+    unsigned long long* raster_rejected = nullptr;  // device counter of K12 (GPUX_RasterRejectedTriangles)
+    uint64_t raster_rejected_base = 0;              // what earlier GPU_Init .. GPU_Deinit spans counted
 } G;
 
 static const char kTokenLut[] = "HIPK1:gen_brdf_integration_map";
@@ -183,6 +197,7 @@ static const char kTokenTaa[] = "HIPK8:taa_resolve";
 static const char kTokenFinal[] = "HIPK9:final_post_process";
 static const char kTokenBloomDown[] = "HIPK10:bloom_downsample";
 static const char kTokenBloomUp[] = "HIPK11:bloom_upsample";
+static const char kTokenSun[] = "HIPK12:sun_depth_pass";
 
 // ------------------------------------------------------------------------------------------
 // formats  [gpu.h:99-144]
@@ -254,6 +269,11 @@ GPU_API void GPU_Deinit(void) {
     (void)hipDeviceSynchronize();
     for (auto& kv : G.tables) (void)hipFree(kv.second.dev);
     G.tables.clear();
+    if (G.raster_rejected) {
+        unsigned long long d = 0;
+        if (hipMemcpy(&d, G.raster_rejected, 8, hipMemcpyDeviceToHost) == hipSuccess) G.raster_rejected_base += d;
+        (void)hipFree(G.raster_rejected); G.raster_rejected = nullptr;
+    }
     G.init = false;
 }
 
@@ -543,6 +563,7 @@ static KernelId identify_shader(const GPU_ShaderDesc* d) {
         if (t == kTokenFinal) return Kernel_FinalPost;
         if (t == kTokenBloomDown) return Kernel_BloomDown;
         if (t == kTokenBloomUp) return Kernel_BloomUp;
+        if (t == kTokenSun) return Kernel_SunDepth;
         return Kernel_None;
     }
     std::string b = basename_of(d->glsl_debug_filepath);
@@ -556,6 +577,7 @@ static KernelId identify_shader(const GPU_ShaderDesc* d) {
     if (b == "bloom_downsample.glsl" && glsl_contains(d->glsl, "BLOOM_INPUT") && glsl_contains(d->glsl, "dst_mip_level")) return Kernel_BloomDown;
     if (b == "bloom_upsample.glsl" && glsl_contains(d->glsl, "BLOOM_INPUT") && glsl_contains(d->glsl, "radius")) return Kernel_BloomUp;
     if (b == "lightgrid_sweep.glsl" && glsl_contains(d->glsl, "LIGHTMAP_IMG") && glsl_contains(d->glsl, "X_direction")) return Kernel_LightgridSweep;
+    if (b == "sun_depth_pass.glsl" && glsl_contains(d->glsl, "sun_space_from_world") && glsl_contains(d->glsl, "vs_position")) return Kernel_SunDepth;
     return Kernel_None;
 }
 static GPU_String token_for(KernelId k) {
@@ -569,6 +591,7 @@ static GPU_String token_for(KernelId k) {
     case Kernel_FinalPost: return GPU_String{kTokenFinal, sizeof kTokenFinal - 1};
     case Kernel_BloomDown: return GPU_String{kTokenBloomDown, sizeof kTokenBloomDown - 1};
     case Kernel_BloomUp: return GPU_String{kTokenBloomUp, sizeof kTokenBloomUp - 1};
+    case Kernel_SunDepth: return GPU_String{kTokenSun, sizeof kTokenSun - 1};
     default: return GPU_String{nullptr, 0};
     }
 }
@@ -583,7 +606,7 @@ GPU_API GPU_String GPU_SPIRVFromGLSL(DS_Arena* arena, GPU_ShaderStage stage, GPU
     GPU_ShaderDesc probe = *desc;
     probe.spirv = empty;
     KernelId k = identify_shader(&probe);
-    bool stage_ok = (k == Kernel_Lighting || k == Kernel_TaaResolve || k == Kernel_FinalPost || k == Kernel_BloomDown || k == Kernel_BloomUp) ? (stage == GPU_ShaderStage_Vertex || stage == GPU_ShaderStage_Fragment)
+    bool stage_ok = (k == Kernel_Lighting || k == Kernel_TaaResolve || k == Kernel_FinalPost || k == Kernel_BloomDown || k == Kernel_BloomUp || k == Kernel_SunDepth) ? (stage == GPU_ShaderStage_Vertex || stage == GPU_ShaderStage_Fragment)
                                            : (stage == GPU_ShaderStage_Compute);
     if (k != Kernel_None && stage_ok) {
         if (out_errors) { out_errors->data = nullptr; out_errors->length = 0; }
@@ -591,7 +614,7 @@ GPU_API GPU_String GPU_SPIRVFromGLSL(DS_Arena* arena, GPU_ShaderStage stage, GPU
     }
     snprintf(g_last_error_text, sizeof g_last_error_text,
              "the HIP backend has no built-in kernel for shader \"%s\" (stage %d); supported: gen_brdf_integration_map.glsl, "
-             "gen_irradiance_map.glsl, gen_prefiltered_env_map.glsl, lightgrid_sweep.glsl (compute), lighting_pass.glsl, taa_resolve.glsl, bloom_downsample.glsl, bloom_upsample.glsl, final_post_process.glsl (full-screen)",
+             "gen_irradiance_map.glsl, gen_prefiltered_env_map.glsl, lightgrid_sweep.glsl (compute), lighting_pass.glsl, taa_resolve.glsl, bloom_downsample.glsl, bloom_upsample.glsl, final_post_process.glsl (full-screen), sun_depth_pass.glsl (depth-only raster)",
              basename_of(desc->glsl_debug_filepath).c_str(), (int)stage);
     if (!out_errors) { gpu_fail("GPU_SPIRVFromGLSL: %s", g_last_error_text); return empty; }
     g_last_error.shader_stage = stage; g_last_error.line = 0;
@@ -647,6 +670,10 @@ GPU_API GPU_RenderPass* GPU_MakeRenderPass(const GPU_RenderPassDesc* desc) {
         rp->desc.width = mip_dim(rp->targets[0].texture->width, rp->targets[0].mip_level);
         rp->desc.height = mip_dim(rp->targets[0].texture->height, rp->targets[0].mip_level);
     }
+    if ((rp->desc.width == 0 || rp->desc.height == 0) && rp->targets.empty() && desc->depth_stencil_target) {   // depth-only pass (render.cpp:725-729)
+        rp->desc.width = desc->depth_stencil_target->width;
+        rp->desc.height = desc->depth_stencil_target->height;
+    }
     return rp;
 }
 GPU_API void GPU_DestroyRenderPass(GPU_RenderPass* rp) { delete rp; }
@@ -654,6 +681,33 @@ GPU_API void GPU_DestroyRenderPass(GPU_RenderPass* rp) { delete rp; }
 GPU_API GPU_GraphicsPipeline* GPU_MakeGraphicsPipeline(const GPU_GraphicsPipelineDesc* desc) {
     GPU_REQUIRE(desc && desc->layout && desc->render_pass, nullptr, "GPU_MakeGraphicsPipeline: NULL argument");
     KernelId k = identify_shader(&desc->fs);
+    if (k == Kernel_None && identify_shader(&desc->vs) == Kernel_SunDepth) k = Kernel_SunDepth;      // the pass has a vertex stage only
+    if (k == Kernel_SunDepth) {
+        // K12: depth test + write, two-sided, position first; anything else would need a raster feature this backend does not have
+        const GPU_RenderPassDesc& rd = desc->render_pass->desc;
+        const GPU_Texture* dt = rd.depth_stencil_target;
+        GPU_REQUIRE(dt && dt->format == GPU_Format_D32F_Or_X8D24UN && rd.color_targets_count == 0, nullptr,
+                    "GPU_MakeGraphicsPipeline: sun_depth_pass.glsl needs a render pass with a D32F depth target and no colour targets (render.cpp:725-729)");
+        GPU_REQUIRE(dt->layer_count == 1 && dt->depth == 1 && rd.width == dt->width && rd.height == dt->height && dt->width <= 16384 && dt->height <= 16384, nullptr,
+                    "GPU_MakeGraphicsPipeline: the sun depth pass must cover its whole 2-D depth target (at most 16384^2)");
+        GPU_REQUIRE(desc->enable_depth_test && desc->enable_depth_write, nullptr,
+                    "GPU_MakeGraphicsPipeline: sun_depth_pass.glsl is implemented with depth test + depth write only");
+        GPU_REQUIRE(desc->cull_mode == GPU_CullMode_TwoSided, nullptr, "GPU_MakeGraphicsPipeline: sun_depth_pass.glsl is implemented for GPU_CullMode_TwoSided only");
+        GPU_REQUIRE(!desc->enable_blending && !desc->enable_conservative_rasterization, nullptr,
+                    "GPU_MakeGraphicsPipeline: blending and conservative rasterisation are not implemented for sun_depth_pass.glsl");
+        GPU_REQUIRE(desc->vertex_input_formats && desc->vertex_input_formats_count > 0 && desc->vertex_input_formats[0] == GPU_Format_RGB32F, nullptr,
+                    "GPU_MakeGraphicsPipeline: sun_depth_pass.glsl reads an RGB32F position as its first vertex attribute");
+        uint32_t stride = 0;
+        for (uint32_t i = 0; i < desc->vertex_input_formats_count; ++i) {                   // gpu_vulkan.c:1745-1762
+            GPU_FormatInfo fi = GPUX_GetFormatInfo(desc->vertex_input_formats[i]);
+            GPU_REQUIRE(fi.vertex_input, nullptr, "GPU_MakeGraphicsPipeline: vertex attribute %u has a format that is not a vertex input", i);
+            stride += fi.block_size;
+        }
+        GPU_REQUIRE((stride & 3) == 0, nullptr, "GPU_MakeGraphicsPipeline: vertex stride %u is not a multiple of 4 bytes", stride);
+        GPU_GraphicsPipeline* p = new GPU_GraphicsPipeline();
+        p->layout = desc->layout; p->pass = desc->render_pass; p->kernel = k; p->shade_flags = 0; p->vertex_stride = stride;
+        return p;
+    }
     GPU_REQUIRE(k == Kernel_Lighting || k == Kernel_TaaResolve || k == Kernel_FinalPost || k == Kernel_BloomDown || k == Kernel_BloomUp, nullptr,
                 "GPU_MakeGraphicsPipeline: unsupported (raster): only the full-screen lighting_pass / taa_resolve / final_post_process pipelines have HIP kernels (got \"%s\")",
                 basename_of(desc->fs.glsl_debug_filepath).c_str());
@@ -736,6 +790,7 @@ static void reset_graph(GPU_Graph* g) {
     g->submitted = false;
     g->bound_cpipe = nullptr; g->bound_cset = nullptr; g->push_size = 0;
     g->preparing = nullptr; g->in_pass = nullptr; g->draw_params.clear(); g->bound_draw = -1;
+    g->vertex_buffer = nullptr; g->index_buffer = nullptr; g->raster_op = -1; g->raster_used = 0;
 }
 GPU_API void GPU_DestroyGraph(GPU_Graph* g) {
     GPU_REQUIRE_V(g, "GPU_DestroyGraph: NULL graph");            // the reference does not accept NULL here (gpu_vulkan.c:2393-2404)
@@ -748,6 +803,7 @@ GPU_API void GPU_DestroyGraph(GPU_Graph* g) {
     if (g->span_a) (void)hipEventDestroy(g->span_a);
     if (g->span_b) (void)hipEventDestroy(g->span_b);
     if (g->exec) (void)hipGraphExecDestroy(g->exec);
+    for (RasterScratch& r : g->raster) { (void)hipFree(r.dev); (void)hipFree(r.draws_dev); (void)hipHostFree(r.draws_host); }
     if (G.last_submitted == g) G.last_submitted = nullptr;        // idle by contract (gpu.h:453): nothing left to order against
     (void)hipStreamDestroy(g->stream);
     delete g;
@@ -891,11 +947,13 @@ GPU_API uint32_t GPU_OpPrepareDrawParams(GPU_Graph* g, GPU_GraphicsPipeline* p, 
 GPU_API void GPU_OpBeginRenderPass(GPU_Graph* g) {
     REC_GUARD(g);
     GPU_REQUIRE_V(g->preparing, "GPU_OpBeginRenderPass: GPU_OpPrepareRenderPass was not called");
-    g->in_pass = g->preparing; g->preparing = nullptr; g->bound_draw = -1;
+    g->in_pass = g->preparing; g->preparing = nullptr; g->bound_draw = -1; g->raster_op = -1;
 }
+static void close_raster_job(GPU_Graph* g);
 GPU_API void GPU_OpEndRenderPass(GPU_Graph* g) {
     REC_GUARD(g);
     GPU_REQUIRE_V(g->in_pass, "GPU_OpEndRenderPass: not inside a render pass");
+    close_raster_job(g);
     g->in_pass = nullptr; g->bound_draw = -1;
 }
 GPU_API void GPU_OpBindDrawParams(GPU_Graph* g, uint32_t idx) {
@@ -1035,9 +1093,86 @@ GPU_API void GPU_OpDraw(GPU_Graph* g, uint32_t vertex_count, uint32_t instance_c
     record_shade(g, 0, 0, false, __func__);
 }
 GPU_API void GPUX_OpDrawRows(GPU_Graph* g, uint32_t row0, uint32_t row1) { REC_GUARD(g); record_shade(g, row0, row1, true, __func__); }
-GPU_API void GPU_OpDrawIndexed(GPU_Graph* g, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t) { (void)g; gpu_fail("GPU_OpDrawIndexed: unsupported (raster)"); }
-GPU_API void GPU_OpBindVertexBuffer(GPU_Graph* g, GPU_Buffer* b) { (void)g; (void)b; gpu_fail("GPU_OpBindVertexBuffer: unsupported (raster)"); }
-GPU_API void GPU_OpBindIndexBuffer(GPU_Graph* g, GPU_Buffer* b) { (void)g; (void)b; gpu_fail("GPU_OpBindIndexBuffer: unsupported (raster)"); }
+// ---- K12: indexed draws of the sun depth pass (render.cpp:993-1020) ----
+// The draws of one render-pass instance are ONE raster job (one Op_Raster): the result is a per-pixel minimum, so merging them is
+// exact, and one setup + one tile launch replace hundreds of per-part launches.  A job is closed (its scratch sized from the known
+// triangle count, no read-back) at GPU_OpEndRenderPass, or when the pass binds another vertex / index buffer pair.
+static void close_raster_job(GPU_Graph* g) {
+    if (g->raster_op < 0) return;
+    Op& op = g->ops[(size_t)g->raster_op];
+    g->raster_op = -1;
+    if ((size_t)op.raster_slot >= g->raster.size()) g->raster.resize((size_t)op.raster_slot + 1);
+    RasterScratch& rs = g->raster[(size_t)op.raster_slot];
+    const int W = (int)op.tex->base.width, H = (int)op.tex->base.height;
+    const size_t need = pbrk_raster_scratch_bytes(op.tri_count, W, H);
+    bool ok = true;
+    if (rs.dev_bytes < need) {
+        (void)hipFree(rs.dev); rs.dev = nullptr; rs.dev_bytes = 0;
+        if (hipMalloc(&rs.dev, need) == hipSuccess) rs.dev_bytes = need; else { rs.dev = nullptr; ok = false; }
+    }
+    if (ok && rs.draws_cap < op.draws.size()) {
+        (void)hipFree(rs.draws_dev); (void)hipHostFree(rs.draws_host); rs.draws_dev = nullptr; rs.draws_host = nullptr; rs.draws_cap = 0;
+        const size_t bytes = op.draws.size() * sizeof(PbrkRasterDraw);
+        if (hipMalloc(&rs.draws_dev, bytes) == hipSuccess && hipHostMalloc((void**)&rs.draws_host, bytes, hipHostMallocDefault) == hipSuccess) rs.draws_cap = op.draws.size();
+        else ok = false;
+    }
+    if (ok && !G.raster_rejected) {
+        if (hipMalloc((void**)&G.raster_rejected, 8) != hipSuccess || hipMemset(G.raster_rejected, 0, 8) != hipSuccess) { G.raster_rejected = nullptr; ok = false; }
+    }
+    if (!ok) { (void)hipGetLastError(); op.tri_count = 0; op.draws.clear(); gpu_fail("GPU_OpEndRenderPass: allocation of the sun depth raster scratch (%zu bytes) failed", need); }
+}
+
+GPU_API void GPU_OpDrawIndexed(GPU_Graph* g, uint32_t index_count, uint32_t instance_count, uint32_t first_index, uint32_t vertex_offset, uint32_t first_instance) {
+    (void)first_instance;                                                     // the shader never reads gl_InstanceIndex
+    REC_GUARD(g);
+    GPU_REQUIRE_V(g->in_pass && g->bound_draw >= 0 && g->draw_params[(size_t)g->bound_draw].pipeline->kernel == Kernel_SunDepth,
+                  "GPU_OpDrawIndexed: unsupported (raster): only the sun depth pass (sun_depth_pass.glsl) draws indexed triangles");
+    const DrawParams dp = g->draw_params[(size_t)g->bound_draw];
+    GPU_REQUIRE_V(dp.pipeline->pass == g->in_pass, "GPU_OpDrawIndexed: pipeline was created for a different render pass");
+    GPU_REQUIRE_V(dp.set->layout == dp.pipeline->layout, "GPU_OpDrawIndexed: descriptor set and pipeline use different layouts");
+    Slot* gl = named_slot(dp.set, "GLOBALS");
+    GPU_REQUIRE_V(gl && gl->buf && gl->buf->base.size >= 448, "GPU_OpDrawIndexed: \"GLOBALS\" must be a buffer that holds sun_space_from_world (render.h:122-136)");
+    GPU_REQUIRE_V(g->vertex_buffer, "GPU_OpDrawIndexed: no vertex buffer bound (GPU_OpBindVertexBuffer)");
+    GPU_REQUIRE_V(g->index_buffer, "GPU_OpDrawIndexed: no index buffer bound (GPU_OpBindIndexBuffer)");
+    const uint64_t n_idx = g->index_buffer->base.size / 4;                    // 32-bit indices (gpu_vulkan.c:2591-2593)
+    GPU_REQUIRE_V((uint64_t)first_index + index_count <= n_idx, "GPU_OpDrawIndexed: indices [%u, %llu) lie outside the bound index buffer (%llu indices)",
+                  first_index, (unsigned long long)first_index + index_count, (unsigned long long)n_idx);
+    const uint32_t tris = index_count / 3;                                    // whole triangles only
+    if (tris == 0 || instance_count == 0) return;                             // any instance count > 0 draws the same triangles once
+    if (g->raster_op >= 0) {
+        const Op& cur = g->ops[(size_t)g->raster_op];
+        if (cur.buf != g->vertex_buffer || cur.buf2 != g->index_buffer || cur.vertex_stride != dp.pipeline->vertex_stride) close_raster_job(g);
+    }
+    if (g->raster_op < 0) {
+        Op op; op.kind = Op_Raster; op.name = "K12.sun_depth";
+        op.pass = g->in_pass; op.gpipe = dp.pipeline;
+        op.tex = (TextureImpl*)g->in_pass->desc.depth_stencil_target;
+        op.buf = g->vertex_buffer; op.buf2 = g->index_buffer; op.vertex_stride = dp.pipeline->vertex_stride;
+        op.raster_slot = (int)g->raster_used++;
+        g->ops.push_back(op);
+        g->raster_op = (int)g->ops.size() - 1;
+    }
+    Op& op = g->ops[(size_t)g->raster_op];
+    GPU_REQUIRE_V((uint64_t)op.tri_count + tris <= (1u << 26), "GPU_OpDrawIndexed: more than 2^26 triangles in one sun depth pass");
+    op.draws.push_back({dp.set, op.tri_count, first_index, vertex_offset});
+    op.tri_count += tris;
+}
+GPU_API void GPU_OpBindVertexBuffer(GPU_Graph* g, GPU_Buffer* b) {
+    REC_GUARD(g);
+    GPU_REQUIRE_V(b, "GPU_OpBindVertexBuffer: NULL buffer");
+    g->vertex_buffer = (BufferImpl*)b;
+}
+GPU_API void GPU_OpBindIndexBuffer(GPU_Graph* g, GPU_Buffer* b) {
+    REC_GUARD(g);
+    GPU_REQUIRE_V(b, "GPU_OpBindIndexBuffer: NULL buffer");
+    g->index_buffer = (BufferImpl*)b;
+}
+GPU_API uint64_t GPUX_RasterRejectedTriangles(void) {
+    uint64_t v = G.raster_rejected_base;
+    unsigned long long d = 0;
+    if (G.init && G.raster_rejected && hipMemcpy(&d, G.raster_rejected, 8, hipMemcpyDeviceToHost) == hipSuccess) v += d;
+    return v;
+}
 
 // ---- transfers ----
 GPU_API void GPU_OpCopyBufferToBuffer(GPU_Graph* g, GPU_Buffer* src, GPU_Buffer* dst, uint32_t dst_offset, uint32_t src_offset, uint32_t size) {
@@ -1486,6 +1621,27 @@ static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
         target->bordered_valid = false;
         return;
     }
+    case Op_Raster: {
+        if (!op.tri_count) return;
+        RasterScratch& rs = g->raster[(size_t)op.raster_slot];             // draw table snapshotted by GPU_GraphSubmit
+        PbrkRasterArgs a;
+        a.vertices = op.buf->dev; a.vertex_stride = op.vertex_stride; a.vertex_count = op.buf->base.size / op.vertex_stride;
+        a.indices = (const uint32_t*)op.buf2->dev;
+        a.draws = (const PbrkRasterDraw*)rs.draws_dev; a.draw_count = (uint32_t)op.draws.size(); a.tri_count = op.tri_count;
+        a.depth = (float*)op.tex->dev; a.width = (int)op.tex->base.width; a.height = (int)op.tex->base.height;
+        a.scratch = rs.dev; a.rejected = G.raster_rejected;
+        timed(g, "K12.setup", ev_used, [&] {
+            HIP_OK(hipMemcpyAsync(rs.draws_dev, rs.draws_host, op.draws.size() * sizeof(PbrkRasterDraw), hipMemcpyHostToDevice, st));
+            int rc = pbrk_raster_setup(&a, st);
+            if (rc != PBRK_OK) gpu_fail("K12 setup launch failed (%d)", rc);
+        });
+        timed(g, "K12.tiles", ev_used, [&] {
+            int rc = pbrk_raster_tiles(&a, st);
+            if (rc != PBRK_OK) gpu_fail("K12 tile launch failed (%d)", rc);
+        });
+        op.tex->bordered_valid = false;
+        return;
+    }
     case Op_MipGen: {
         timed(g, op.name, ev_used, [&] {
             int rc = pbrk_mip_chain(op.tex->dev, (int)op.tex->base.width, (int)op.tex->base.mip_level_count, st);
@@ -1606,6 +1762,7 @@ static bool op_replayable(const Op& op) {
     case Op_MipGen: return true;
     case Op_Blit: return true;
     case Op_CopyB2B: case Op_CopyB2T: case Op_CopyT2B: return false;          // host pointers may be involved: keep them out of captures
+    case Op_Raster: return false;                                             // its draw table is uploaded from pinned staging at submit
     case Op_Clear: {
         const uint32_t tb = op.tex->texel_bytes;                              // one fill launch; the staged form of other texel sizes synchronises
         return tb == 1 || tb == 2 || tb == 4 || tb == 8 || tb == 16;
@@ -1739,6 +1896,22 @@ static bool contains(const std::vector<TextureImpl*>& v, const TextureImpl* t) {
 GPU_API void GPU_GraphSubmit(GPU_Graph* g) {
     GPU_REQUIRE_V(g && !g->submitted, "GPU_GraphSubmit: graph is NULL or already submitted");
     GPU_REQUIRE_V(g->in_pass == nullptr && g->preparing == nullptr, "GPU_GraphSubmit: render pass still open");
+    // K12: snapshot every sun depth draw's sun_space_from_world (the caller fills the mapped Globals before submitting, render.cpp:991)
+    // into the job's draw table, before anything is launched: an orthographic matrix (last row (0, 0, 0, c > 0)) needs no near-plane clip
+    for (const Op& op : g->ops) {
+        if (op.kind != Op_Raster || !op.tri_count) continue;
+        RasterScratch& rs = g->raster[(size_t)op.raster_slot];
+        for (size_t i = 0; i < op.draws.size(); ++i) {
+            const RasterDraw& d = op.draws[i];
+            BufferImpl* gb = named_slot(d.set, "GLOBALS")->buf;
+            PbrkRasterDraw& o = rs.draws_host[i];
+            if (gb->pinned_host) memcpy(o.m, (const char*)gb->dev + 384, 64);        // render.h:129: sun_space_from_world
+            else HIP_OK(hipMemcpy(o.m, (const char*)gb->dev + 384, 64, hipMemcpyDeviceToHost));
+            GPU_REQUIRE_V(o.m[3] == 0.0f && o.m[7] == 0.0f && o.m[11] == 0.0f && o.m[15] > 0.0f,
+                          "GPU_GraphSubmit: perspective sun projection not implemented (sun_space_from_world's last row must be (0, 0, 0, c > 0))");
+            o.first_tri = d.first_tri; o.first_index = d.first_index; o.vertex_offset = d.vertex_offset; o.pad = 0;
+        }
+    }
     g->timed_names.clear(); g->timed_ms.clear();
     size_t ev_used = 0;
     g->sync_used = 0;

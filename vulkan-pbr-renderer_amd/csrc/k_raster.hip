@@ -1,0 +1,349 @@
+// k_raster.hip -- K12 (N5): the sun depth pass, shaders/sun_depth_pass.glsl (render.cpp:993-1020), as a compute rasteriser.
+//
+// The pass has one matrix product per vertex, no fragment output, no culling, no blending: a LESS depth test and a depth write
+// into a 2048^2 D32F target.  The result is a per-pixel minimum over every covered fragment, which does not depend on triangle
+// order, so all draws of one render-pass instance are ONE job and the rules of DESIGN.md K12 are met bit for bit:
+//   * setup (one thread per triangle): fetch the three indices, skip the triangle when a vertex index is past the vertex buffer,
+//     transform in fp32 (m0 x + m1 y + m2 z + m3, no FMA: -ffp-contract=off), divide by w, viewport, reject what is not finite
+//     or outside +-2^21 px (counted), snap to 1/256 px, write a 64-B record (snapped vertices, z0, z1-z0, z2-z0 and 1/area in
+//     fp64, clamped pixel box) and count the record into every 32 x 32-pixel tile its box touches -- or, when that is more than
+//     kMaxTiles tiles, append it to one "large" list;
+//   * scan: exclusive prefix of the per-tile counts (one workgroup); fill: each binned triangle writes its index into its tiles'
+//     bins (slot order depends on scheduling, the minimum does not);
+//   * tiles (one workgroup per tile, 256 lanes x 4 adjacent pixels of one row): load the current depth, walk the tile's bin and the
+//     large list 256 entries at a time -- the lanes first drop the records that cannot touch the tile (box, and an edge function
+//     negative over the whole tile), the rest go through LDS --, evaluate the exact int64 edge functions at the pixel centres with the
+//     top-left rule, interpolate z in fp64, keep the minimum in registers and store once.  No atomics touch the depth map.
+// Scratch sizes follow from the triangle count and the target size alone (pbrk_raster_scratch_bytes): no read-back.
+#include "pbr_kernels.h"
+
+#include <hip/hip_runtime.h>
+
+#include <float.h>
+#include <math.h>
+
+namespace {
+constexpr int kTile = 32;                 // tile edge in pixels
+constexpr int kMaxTiles = 16;             // a triangle whose pixel box touches more tiles goes to the large list
+constexpr int kThreads = 256;
+
+struct TriRec {                           // 64 B; bx0 > bx1 marks a record that covers nothing
+    int x0, y0, x1, y1, x2, y2;           // snapped framebuffer coordinates, 1/256 px
+    short bx0, by0, bx1, by1;             // pixel box, clamped to the target
+    float z0, pad;
+    double inv, dz1, dz2;                 // 1 / (E0 + E1 + E2), z1 - z0, z2 - z0
+};
+static_assert(sizeof(TriRec) == 64, "TriRec is four 16-B words");
+
+struct Layout {
+    size_t rec, cnt, off, cur, bins, large, total;
+    int tx, ty, ntiles;
+};
+
+Layout raster_layout(uint32_t n, int W, int H) {
+    Layout L;
+    L.tx = (W + kTile - 1) / kTile; L.ty = (H + kTile - 1) / kTile; L.ntiles = L.tx * L.ty;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~(size_t)255; return r; };
+    L.rec = take((size_t)n * sizeof(TriRec));
+    L.cnt = take(((size_t)L.ntiles + 1) * 4);           // per-tile counts, then the large-list count
+    L.off = take(((size_t)L.ntiles + 1) * 4);           // exclusive prefix of the counts
+    L.cur = take((size_t)L.ntiles * 4);                 // fill cursors
+    L.bins = take((size_t)kMaxTiles * n * 4);
+    L.large = take((size_t)n * 4);
+    L.total = o > 256 ? o : 256;
+    return L;
+}
+
+__device__ inline bool top_left(long long a, long long b) { return a > 0 || (a == 0 && b > 0); }
+
+__global__ __launch_bounds__(kThreads) void k_raster_setup(PbrkRasterArgs a, Layout L) {
+    const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
+    bool rejected = false;
+    unsigned key = 0xFFFFFFFFu;                                     // the one tile of a single-tile triangle
+    char* scratch = (char*)a.scratch;
+    if (t < a.tri_count) {
+        int lo = 0, hi = (int)a.draw_count - 1;                   // last draw with first_tri <= t
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (a.draws[mid].first_tri <= t) lo = mid; else hi = mid - 1;
+        }
+        const PbrkRasterDraw* d = &a.draws[lo];
+        const uint32_t* ix = a.indices + (size_t)d->first_index + 3 * (size_t)(t - d->first_tri);   // in range: checked at record time
+        const float hw = (float)a.width * 0.5f, hh = (float)a.height * 0.5f;
+        int X[3] = {0, 0, 0}, Y[3] = {0, 0, 0};
+        float Z[3] = {0.0f, 0.0f, 0.0f};
+        bool ok = true;
+        for (int k = 0; k < 3 && ok; ++k) {
+            const unsigned long long v = (unsigned long long)ix[k] + d->vertex_offset;
+            if (v >= a.vertex_count) { ok = false; break; }
+            const float* p = (const float*)((const char*)a.vertices + v * a.vertex_stride);
+            const float x = p[0], y = p[1], z = p[2];
+            const float cx = ((d->m[0] * x + d->m[4] * y) + d->m[8] * z) + d->m[12];
+            const float cy = ((d->m[1] * x + d->m[5] * y) + d->m[9] * z) + d->m[13];
+            const float cz = ((d->m[2] * x + d->m[6] * y) + d->m[10] * z) + d->m[14];
+            const float cw = ((d->m[3] * x + d->m[7] * y) + d->m[11] * z) + d->m[15];
+            const float xd = cx / cw, yd = cy / cw, zd = cz / cw;
+            const float xf = hw * xd + hw, yf = hh * yd + hh;
+            if (!(fabsf(xf) <= 2097152.0f) || !(fabsf(yf) <= 2097152.0f) || !(fabsf(zd) <= FLT_MAX)) { ok = false; break; }
+            X[k] = (int)rintf(xf * 256.0f); Y[k] = (int)rintf(yf * 256.0f); Z[k] = zd;
+        }
+        rejected = !ok;
+        TriRec r;
+        r.x0 = X[0]; r.y0 = Y[0]; r.x1 = X[1]; r.y1 = Y[1]; r.x2 = X[2]; r.y2 = Y[2];
+        r.bx0 = 1; r.by0 = 1; r.bx1 = 0; r.by1 = 0;
+        r.z0 = Z[0]; r.pad = 0.0f;
+        r.inv = 0.0; r.dz1 = 0.0; r.dz2 = 0.0;
+        long long i0 = 1, i1 = 0, j0 = 1, j1 = 0;
+        if (ok) {
+            const long long x0 = X[0], y0 = Y[0], x1 = X[1], y1 = Y[1], x2 = X[2], y2 = Y[2];
+            const long long area = (x1 - x0) * (y2 - y0) - (y1 - y0) * (x2 - x0);
+            if (area != 0) {
+                const long long mnx = x0 < x1 ? (x0 < x2 ? x0 : x2) : (x1 < x2 ? x1 : x2);
+                const long long mxx = x0 > x1 ? (x0 > x2 ? x0 : x2) : (x1 > x2 ? x1 : x2);
+                const long long mny = y0 < y1 ? (y0 < y2 ? y0 : y2) : (y1 < y2 ? y1 : y2);
+                const long long mxy = y0 > y1 ? (y0 > y2 ? y0 : y2) : (y1 > y2 ? y1 : y2);
+                i0 = (mnx + 127) >> 8; i1 = (mxx - 128) >> 8;          // pixel centres 256 i + 128 inside [mnx, mxx]
+                j0 = (mny + 127) >> 8; j1 = (mxy - 128) >> 8;
+                if (i0 < 0) i0 = 0;
+                if (j0 < 0) j0 = 0;
+                if (i1 > a.width - 1) i1 = a.width - 1;
+                if (j1 > a.height - 1) j1 = a.height - 1;
+                if (i0 <= i1 && j0 <= j1) {
+                    r.bx0 = (short)i0; r.bx1 = (short)i1; r.by0 = (short)j0; r.by1 = (short)j1;
+                    r.inv = 1.0 / (double)area;
+                    r.dz1 = (double)Z[1] - (double)Z[0];
+                    r.dz2 = (double)Z[2] - (double)Z[0];
+                } else {
+                    i0 = 1; i1 = 0;
+                }
+            }
+        }
+        const int4* src = (const int4*)&r;
+        int4* dst = (int4*)(scratch + L.rec) + 4 * (size_t)t;
+        dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; dst[3] = src[3];
+        if (i0 <= i1 && j0 <= j1) {
+            const int tx0 = (int)(i0 >> 5), tx1 = (int)(i1 >> 5), ty0 = (int)(j0 >> 5), ty1 = (int)(j1 >> 5);
+            unsigned* cnt = (unsigned*)(scratch + L.cnt);
+            if (tx0 == tx1 && ty0 == ty1) {
+                key = (unsigned)(ty0 * L.tx + tx0);                 // counted below, one atomic per distinct tile of the wave
+            } else if ((tx1 - tx0 + 1) * (ty1 - ty0 + 1) <= kMaxTiles) {
+                for (int ty = ty0; ty <= ty1; ++ty)
+                    for (int tx = tx0; tx <= tx1; ++tx) atomicAdd(&cnt[ty * L.tx + tx], 1u);
+            } else {
+                const unsigned slot = atomicAdd(&cnt[L.ntiles], 1u);          // < tri_count
+                ((unsigned*)(scratch + L.large))[slot] = t;
+            }
+        }
+    }
+    const unsigned long long m = __ballot(rejected);
+    const int lane = threadIdx.x & 63;
+    if (lane == 0 && m) atomicAdd(a.rejected, (unsigned long long)__popcll(m));
+    // consecutive triangles of a part mostly fall into the same tile: one atomic per distinct tile of the wave
+    unsigned long long todo = __ballot(key != 0xFFFFFFFFu);
+    while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const unsigned k = __shfl(key, leader);
+        const unsigned long long grp = __ballot(key == k);
+        if (lane == leader) atomicAdd((unsigned*)(scratch + L.cnt) + k, (unsigned)__popcll(grp));
+        todo &= ~grp;
+    }
+}
+
+// exclusive prefix of the tile counts: 1024 threads, each a contiguous chunk
+__global__ __launch_bounds__(1024) void k_raster_scan(char* scratch, Layout L) {
+    __shared__ unsigned part[1024];
+    const unsigned* cnt = (const unsigned*)(scratch + L.cnt);
+    unsigned* off = (unsigned*)(scratch + L.off);
+    unsigned* cur = (unsigned*)(scratch + L.cur);
+    const int n = L.ntiles, chunk = (n + 1023) / 1024;
+    const int b = threadIdx.x * chunk, e = b + chunk < n ? b + chunk : n;
+    unsigned s = 0;
+    for (int i = b; i < e; ++i) s += cnt[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {                                  // inclusive Hillis-Steele
+        const unsigned v = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0u;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    unsigned run = part[threadIdx.x] - s;
+    for (int i = b; i < e; ++i) { off[i] = run; cur[i] = run; run += cnt[i]; }
+    if (threadIdx.x == 1023) off[n] = part[1023];
+}
+
+__global__ __launch_bounds__(kThreads) void k_raster_fill(PbrkRasterArgs a, Layout L) {
+    const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
+    char* scratch = (char*)a.scratch;
+    unsigned* cur = (unsigned*)(scratch + L.cur);
+    unsigned* bins = (unsigned*)(scratch + L.bins);
+    unsigned key = 0xFFFFFFFFu;
+    if (t < a.tri_count) {
+        const TriRec* r = (const TriRec*)(scratch + L.rec) + t;
+        const int bx0 = r->bx0, bx1 = r->bx1, by0 = r->by0, by1 = r->by1;
+        if (bx0 <= bx1 && by0 <= by1) {
+            const int tx0 = bx0 >> 5, tx1 = bx1 >> 5, ty0 = by0 >> 5, ty1 = by1 >> 5;
+            if (tx0 == tx1 && ty0 == ty1) {
+                key = (unsigned)(ty0 * L.tx + tx0);
+            } else if ((tx1 - tx0 + 1) * (ty1 - ty0 + 1) <= kMaxTiles) {
+                for (int ty = ty0; ty <= ty1; ++ty)
+                    for (int tx = tx0; tx <= tx1; ++tx) bins[atomicAdd(&cur[ty * L.tx + tx], 1u)] = t;   // slots stay inside the tile's range
+            }
+        }
+    }
+    // single-tile triangles: the wave's lanes of one tile take consecutive slots from one atomic (the counts of the setup match)
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(key != 0xFFFFFFFFu);
+    while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const unsigned k = __shfl(key, leader);
+        const unsigned long long grp = __ballot(key == k);
+        unsigned base = 0;
+        if (lane == leader) base = atomicAdd(&cur[k], (unsigned)__popcll(grp));
+        base = __shfl(base, leader);
+        if (key == k) bins[base + (unsigned)__popcll(grp & ((1ull << lane) - 1ull))] = t;
+        todo &= ~grp;
+    }
+}
+
+// Can a triangle cover a pixel centre of the tile [px0, px0 + 31] x [py0, py0 + 31]?  Its pixel box must meet the tile, and no edge
+// function may be negative at every centre of it (an affine function's maximum over the tile is at the corner its gradient points to).
+__device__ inline bool meets_tile(const int4* rec, int px0, int py0) {
+    const int4 w0 = rec[0], w1 = rec[1];                                    // x0 y0 x1 y1 | x2 y2 (bx0, by0) (bx1, by1)
+    const int bx0 = (short)(w1.z & 0xFFFF), by0 = w1.z >> 16, bx1 = (short)(w1.w & 0xFFFF), by1 = w1.w >> 16;
+    if (bx0 > bx1 || by0 > by1 || bx1 < px0 || bx0 > px0 + kTile - 1 || by1 < py0 || by0 > py0 + kTile - 1) return false;
+    const long long x0 = w0.x, y0 = w0.y, x1 = w0.z, y1 = w0.w, x2 = w1.x, y2 = w1.y;
+    const long long sg = ((x1 - x0) * (y2 - y0) - (y1 - y0) * (x2 - x0)) > 0 ? 1 : -1;
+    const long long lo_x = 256LL * px0 + 128, hi_x = lo_x + 256LL * (kTile - 1), lo_y = 256LL * py0 + 128, hi_y = lo_y + 256LL * (kTile - 1);
+    const long long ex[3][4] = {{x1, y1, x2, y2}, {x2, y2, x0, y0}, {x0, y0, x1, y1}};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const long long ax = ex[k][0], ay = ex[k][1], bxx = ex[k][2], byy = ex[k][3];
+        const long long A = -(byy - ay) * sg, B = (bxx - ax) * sg;           // oriented gradient
+        const long long Px = A > 0 ? hi_x : lo_x, Py = B > 0 ? hi_y : lo_y;
+        if (sg * ((bxx - ax) * (Py - ay) - (byy - ay) * (Px - ax)) < 0) return false;
+    }
+    return true;
+}
+
+// one list (a tile's bin or the large list) against the four pixels (px .. px+3, py) of this lane: 256 entries at a time, the lanes
+// first keep the entries that can touch the tile (meets_tile), the kept records are staged in LDS, then every lane walks them
+__device__ inline void raster_list(const unsigned* list, unsigned n, const int4* recs, int4* lds, unsigned* kept, unsigned* nkept,
+                                   int tx0, int ty0, int px, int py, float cur[4]) {
+    const TriRec* sr = (const TriRec*)lds;
+    for (unsigned base = 0; base < n; base += kThreads) {
+        __syncthreads();                                                    // the previous batch is consumed
+        if (threadIdx.x == 0) *nkept = 0;
+        __syncthreads();
+        const unsigned j = base + threadIdx.x;
+        if (j < n) {
+            const unsigned t = list[j];
+            if (meets_tile(recs + 4 * (size_t)t, tx0, ty0)) kept[atomicAdd(nkept, 1u)] = t;     // LDS counter; order is irrelevant
+        }
+        __syncthreads();
+        const unsigned m = *nkept;
+        if (threadIdx.x < m) {
+            const int4* src = recs + 4 * (size_t)kept[threadIdx.x];
+            int4* d = lds + 4 * threadIdx.x;
+            d[0] = src[0]; d[1] = src[1]; d[2] = src[2]; d[3] = src[3];
+        }
+        __syncthreads();
+        for (unsigned k = 0; k < m; ++k) {
+            const TriRec& r = sr[k];
+            if (py < r.by0 || py > r.by1 || px + 3 < r.bx0 || px > r.bx1) continue;
+            const long long x0 = r.x0, y0 = r.y0, x1 = r.x1, y1 = r.y1, x2 = r.x2, y2 = r.y2;
+            const bool pos = r.inv > 0.0;                                   // orientation: both windings are drawn
+            // E0 = edge(v1 -> v2), E1 = edge(v2 -> v0), E2 = edge(v0 -> v1); edge(a -> b, p) = (b.x - a.x)(p.y - a.y) - (b.y - a.y)(p.x - a.x)
+            const long long Px = 256LL * px + 128, Py = 256LL * py + 128;
+            long long e0 = (x2 - x1) * (Py - y1) - (y2 - y1) * (Px - x1);
+            long long e1 = (x0 - x2) * (Py - y2) - (y0 - y2) * (Px - x2);
+            long long e2 = (x1 - x0) * (Py - y0) - (y1 - y0) * (Px - x0);
+            const long long d0 = -(y2 - y1) * 256, d1 = -(y0 - y2) * 256, d2 = -(y1 - y0) * 256;
+            // top-left rule (y down): with the edge functions oriented positive inside, a centre ON an edge is covered when the
+            // inward normal (A, B) has A > 0 (left edge) or A == 0 and B > 0 (top edge)
+            const long long sg = pos ? 1 : -1;
+            const long long b0 = top_left(-(y2 - y1) * sg, (x2 - x1) * sg) ? 0 : 1;
+            const long long b1 = top_left(-(y0 - y2) * sg, (x0 - x2) * sg) ? 0 : 1;
+            const long long b2 = top_left(-(y1 - y0) * sg, (x1 - x0) * sg) ? 0 : 1;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const long long n0 = pos ? e0 : -e0, n1 = pos ? e1 : -e1, n2 = pos ? e2 : -e2;
+                const int x = px + q;
+                if (n0 >= b0 && n1 >= b1 && n2 >= b2 && x >= r.bx0 && x <= r.bx1) {
+                    const double z = (double)r.z0 + ((double)e1 * r.dz1 + (double)e2 * r.dz2) * r.inv;
+                    float zf = (float)z;
+                    if (zf >= 0.0f && zf <= 1.0f) {
+                        if (zf == 0.0f) zf = 0.0f;                          // -0 -> +0
+                        if (zf < cur[q]) cur[q] = zf;                       // LESS
+                    }
+                }
+                e0 += d0; e1 += d1; e2 += d2;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_raster_tiles(PbrkRasterArgs a, Layout L) {
+    __shared__ int4 lds[kThreads * 4];                                      // 256 records, 16 KB
+    __shared__ unsigned kept[kThreads];
+    __shared__ unsigned nkept;
+    const char* scratch = (const char*)a.scratch;
+    const int tile = blockIdx.y * L.tx + blockIdx.x;
+    const int py = blockIdx.y * kTile + (threadIdx.x >> 3);
+    const int px = blockIdx.x * kTile + (threadIdx.x & 7) * 4;
+    const int W = a.width, H = a.height;
+    const bool row_in = py < H;
+    const bool vec = row_in && (W & 3) == 0 && px + 3 < W;
+    float cur[4] = {1.0f, 1.0f, 1.0f, 1.0f};
+    float* row = a.depth + (size_t)(row_in ? py : 0) * W;
+    if (vec) {
+        const float4 v = *(const float4*)(row + px);
+        cur[0] = v.x; cur[1] = v.y; cur[2] = v.z; cur[3] = v.w;
+    } else if (row_in) {
+        for (int q = 0; q < 4; ++q) if (px + q < W) cur[q] = row[px + q];
+    }
+    const unsigned* cnt = (const unsigned*)(scratch + L.cnt);
+    const unsigned* off = (const unsigned*)(scratch + L.off);
+    const int4* recs = (const int4*)(scratch + L.rec);
+    const int tx0 = blockIdx.x * kTile, ty0 = blockIdx.y * kTile;
+    raster_list((const unsigned*)(scratch + L.bins) + off[tile], off[tile + 1] - off[tile], recs, lds, kept, &nkept, tx0, ty0, px, py, cur);
+    raster_list((const unsigned*)(scratch + L.large), cnt[L.ntiles], recs, lds, kept, &nkept, tx0, ty0, px, py, cur);
+    if (vec) {
+        *(float4*)(row + px) = make_float4(cur[0], cur[1], cur[2], cur[3]);
+    } else if (row_in) {
+        for (int q = 0; q < 4; ++q) if (px + q < W) row[px + q] = cur[q];
+    }
+}
+
+bool args_ok(const PbrkRasterArgs* a) {
+    return a && a->vertices && a->indices && a->draws && a->depth && a->scratch && a->rejected && a->draw_count > 0 &&
+           a->width > 0 && a->height > 0 && a->width <= 16384 && a->height <= 16384 && a->vertex_stride >= 12 && (a->vertex_stride & 3) == 0;
+}
+}  // namespace
+
+extern "C" size_t pbrk_raster_scratch_bytes(uint32_t tri_count, int width, int height) {
+    if (width <= 0 || height <= 0) return 0;
+    return raster_layout(tri_count, width, height).total;
+}
+
+extern "C" int pbrk_raster_setup(const PbrkRasterArgs* a, void* stream) {
+    if (!args_ok(a)) return PBRK_E_ARG;
+    if (a->tri_count == 0) return PBRK_OK;
+    const Layout L = raster_layout(a->tri_count, a->width, a->height);
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync((char*)a->scratch + L.cnt, 0, ((size_t)L.ntiles + 1) * 4, st) != hipSuccess) return PBRK_E_LAUNCH;
+    const unsigned blocks = (a->tri_count + kThreads - 1) / kThreads;
+    hipLaunchKernelGGL(k_raster_setup, dim3(blocks), dim3(kThreads), 0, st, *a, L);
+    hipLaunchKernelGGL(k_raster_scan, dim3(1), dim3(1024), 0, st, (char*)a->scratch, L);
+    hipLaunchKernelGGL(k_raster_fill, dim3(blocks), dim3(kThreads), 0, st, *a, L);
+    return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
+}
+
+extern "C" int pbrk_raster_tiles(const PbrkRasterArgs* a, void* stream) {
+    if (!args_ok(a)) return PBRK_E_ARG;
+    if (a->tri_count == 0) return PBRK_OK;
+    const Layout L = raster_layout(a->tri_count, a->width, a->height);
+    hipLaunchKernelGGL(k_raster_tiles, dim3(L.tx, L.ty), dim3(kThreads), 0, (hipStream_t)stream, *a, L);
+    return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
+}

@@ -116,6 +116,30 @@ class PbrkShadeArgs(C.Structure):
                 ("globals", C.c_float * 138)]
 
 
+class GPU_TextureView(C.Structure):
+    _fields_ = [("texture", C.POINTER(GPU_Texture)), ("mip_level", C.c_uint32)]
+
+
+class GPU_RenderPassDesc(C.Structure):
+    _fields_ = [("color_targets_count", C.c_uint32), ("color_targets", C.POINTER(GPU_TextureView)),
+                ("msaa_color_resolve_targets", C.POINTER(GPU_TextureView)), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("depth_stencil_target", C.POINTER(GPU_Texture))]
+
+
+class GPU_GraphicsPipelineDesc(C.Structure):
+    _fields_ = [("layout", C.c_void_p), ("render_pass", C.c_void_p), ("vs", GPU_ShaderDesc), ("fs", GPU_ShaderDesc),
+                ("vertex_input_formats", C.POINTER(C.c_int)), ("vertex_input_formats_count", C.c_uint32),
+                ("enable_depth_test", C.c_bool), ("enable_depth_write", C.c_bool), ("enable_blending", C.c_bool),
+                ("blending_mode_additive", C.c_bool), ("enable_conservative_rasterization", C.c_bool), ("cull_mode", C.c_int)]
+
+
+class PBR_MeshPart(C.Structure):
+    _fields_ = [("first_index", C.c_uint32), ("index_count", C.c_uint32)]
+
+
+CullMode_TwoSided, CullMode_DrawCW, CullMode_DrawCCW = 0, 1, 2
+ShaderStage_Vertex, ShaderStage_Fragment, ShaderStage_Compute = 0, 1, 2
+
 TexP = C.POINTER(GPU_Texture)
 BufP = C.POINTER(GPU_Buffer)
 VP = C.c_void_p
@@ -169,6 +193,7 @@ PROTOTYPES = {
     "GPUX_InvalidateTexture": (None, [TexP]),
     "GPUX_TextureTotalBytes": (C.c_uint64, [TexP]), "GPUX_TextureMipOffset": (C.c_uint64, [TexP, U32]),
     "GPUX_MakeCubemapFromEquirect": (TexP, [VP, U32, U32, U32, C.c_int]),
+    "GPUX_RasterRejectedTriangles": (C.c_uint64, []),
     "GPUX_GraphStream": (VP, [VP]), "GPUX_EnableOpTiming": (None, [C.c_int]), "GPUX_SetTileStreams": (None, [C.c_int]), "GPUX_GraphTimedOpCount": (U32, [VP]),
     "GPUX_GraphTimedOpName": (C.c_char_p, [VP, U32]), "GPUX_GraphTimedOpMs": (C.c_float, [VP, U32]), "GPUX_GraphSpanMs": (C.c_float, [VP]),
     # --- host layer (include/pbr_host.h) ---
@@ -209,6 +234,12 @@ PROTOTYPES = {
     "PBR_RecordBloom": (None, [VP, VP, U32]), "PBR_RecordFinalPostProcessBloom": (None, [VP, VP, U32]),
     "PBR_PostBloomDownscale": (TexP, [VP]), "PBR_PostBloomUpscale": (TexP, [VP]), "PBR_PostBloomPassCount": (U32, [VP]),
     "PBR_RecordTaaResolve": (None, [VP, VP, U32]), "PBR_RecordTaaResolveRows": (None, [VP, VP, U32, U32, U32]), "PBR_RecordFinalPostProcess": (None, [VP, VP, U32]),
+    "PBR_MakeMesh": (VP, [VP, U32, VP, U32, C.POINTER(PBR_MeshPart), U32]), "PBR_DestroyMesh": (None, [VP]),
+    "PBR_MeshVertexBuffer": (BufP, [VP]), "PBR_MeshIndexBuffer": (BufP, [VP]), "PBR_MeshPartCount": (U32, [VP]),
+    "PBR_MakeSunDepthPass": (VP, [U32]), "PBR_DestroySunDepthPass": (None, [VP]), "PBR_SunDepthTexture": (TexP, [VP]),
+    "PBR_SunDepthGlobalsBuffer": (BufP, [VP]), "PBR_SunDepthPipeline": (VP, [VP]), "PBR_SunDepthRenderPass": (VP, [VP]),
+    "PBR_SunDepthLayout": (VP, [VP]), "PBR_SunDepthDescriptorSet": (VP, [VP]),
+    "PBR_RecordSunDepthPass": (None, [VP, VP, VP, C.POINTER(PBR_Globals)]),
     "PBR_MakeLightgrid": (VP, [U32]), "PBR_DestroyLightgrid": (None, [VP]), "PBR_LightgridTexture": (TexP, [VP]),
     "PBR_LightgridSweepDirection": (U32, [VP]), "PBR_RecordLightgridClear": (None, [VP, VP]),
     "PBR_RecordLightgridSweep": (None, [VP, VP]), "PBR_RecordLightgridSweepLines": (None, [VP, VP, U32, U32, U32, U32, U32]),
@@ -243,6 +274,8 @@ PROTOTYPES = {
     "pbrk_mc_region_flag_stats": (C.c_int, [C.POINTER(C.c_uint64)]), "pbrk_mc_region_window_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
     "pbrk_lut_cells_build": (C.c_int, [VP, C.c_int, VP, VP]),
     "pbrk_equirect_to_cube": (C.c_int, [VP, C.c_int, C.c_int, VP, C.c_int, VP]),
+    "pbrk_raster_scratch_bytes": (C.c_size_t, [U32, C.c_int, C.c_int]),
+    "pbrk_raster_setup": (C.c_int, [VP, VP]), "pbrk_raster_tiles": (C.c_int, [VP, VP]),
 }
 
 _LIB = None
@@ -333,6 +366,22 @@ def fill_globals(pos, ori=None, fov=75.0, aspect=16.0 / 9.0, near=0.02, far=1.0e
     o = None if ori is None else (C.c_float * 4)(*[float(v) for v in ori])
     lib().PBR_FillGlobals(C.byref(g), p, o, fov, aspect, near, far, sun_angle[0], sun_angle[1], frame_idx)
     return g
+
+
+def make_mesh(vertices, indices, parts):
+    """vertices float32 [n][11] (or [n][3]: padded to the reference's 44-B Vertex), indices uint32, parts [(first_index, index_count)]
+    -> PBR_Mesh* (GPU vertex + index buffers, asset_import.cpp:172-173)."""
+    v = np.asarray(vertices, np.float32)
+    if v.ndim == 2 and v.shape[1] == 3:
+        v = np.concatenate([v, np.zeros((len(v), 8), np.float32)], 1)
+    v = np.ascontiguousarray(v)
+    assert v.ndim == 2 and v.shape[1] == 11, v.shape
+    ix = np.ascontiguousarray(indices, np.uint32)
+    pa = (PBR_MeshPart * max(1, len(parts)))(*[PBR_MeshPart(int(a), int(b)) for a, b in parts])
+    m = lib().PBR_MakeMesh(v.ctypes.data_as(VP), len(v), ix.ctypes.data_as(VP), len(ix), pa, len(parts))
+    if not m:
+        raise RuntimeError("PBR_MakeMesh failed")
+    return m
 
 
 def partition(specular_size, min_size, irradiance_size, env_size, world, rank):

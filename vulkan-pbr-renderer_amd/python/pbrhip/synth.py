@@ -514,3 +514,123 @@ def synth_gi_scene(width, height, seed=0x5EED00F0, grid_size=128):
     v, u = np.mgrid[0:512, 0:512] / 512.0
     sun = (0.5 + 0.08 * np.sin(2 * np.pi * 40 * u) * np.cos(2 * np.pi * 36 * v)).astype(np.float32)
     return gbd, grid, levels, sun
+
+
+def _param_grid(nu, nv, fn, closed_u=False):
+    """Triangulated parametric patch: fn(u, v) -> xyz over an (nu + 1) x (nv + 1) lattice of [0,1]^2 -> (positions, uv, triangles)."""
+    u, v = np.meshgrid(np.linspace(0.0, 1.0, nu + 1), np.linspace(0.0, 1.0, nv + 1), indexing="ij")
+    p = fn(u, v).reshape(-1, 3)
+    a = (np.arange(nu)[:, None] * (nv + 1) + np.arange(nv)[None, :]).ravel()
+    b, c, d = a + (nv + 1), a + 1, a + nv + 2
+    tri = np.stack([np.stack([a, b, d], 1), np.stack([a, d, c], 1)], 1).reshape(-1, 3)
+    return p, np.stack([u.ravel(), v.ravel()], 1), tri
+
+
+def _sun_rotation(sun_angle):
+    """render.cpp:959-971 in float64: the rotation whose inverse, times a +-40 ortho box, is sun_space_from_world."""
+    ax, ay = np.radians(sun_angle[0]), np.radians(sun_angle[1])
+    k = np.array([np.cos(ay), np.sin(ay), 0.0])
+    k = k / np.linalg.norm(k)
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(ax) * K + (1 - np.cos(ax)) * (K @ K)
+
+
+def synth_mesh_temple(n_triangles=200000, seed=0x5EED0012, sun_angle=(56.5, 97.0), map_size=2048):
+    """A temple for the sun depth pass (render.cpp:993-1020), about n_triangles triangles in ~100 parts of one merged mesh (the layout
+    of asset_import.cpp:172-173): a floor grid reaching past the +-40 sun volume, a ring of columns, boxes, spheres, an arch, and one
+    part of hostile cases -- slivers, degenerate triangles (repeated index, collinear), geometry beyond +-40 in x / y and in z (outside
+    the depth range), a quad larger than the map, and vertices placed on the exact pixel centres of a map_size^2 map at sun_angle.
+    Returns (vertices float32 [n][11] = position, normal, tangent, uv; indices uint32; parts [(first_index, index_count)])."""
+    rng = np.random.default_rng(seed)
+    P, UV, T, parts = [], [], [], []
+    nv_total = [0]
+    ni_total = [0]
+
+    def add(p, uv, tri):
+        tri = np.asarray(tri, np.int64) + nv_total[0]
+        P.append(np.asarray(p, np.float64)); UV.append(np.asarray(uv, np.float64)); T.append(tri)
+        parts.append((ni_total[0], 3 * len(tri)))
+        nv_total[0] += len(p); ni_total[0] += 3 * len(tri)
+
+    def grid_for(budget, aspect=1.0):
+        nu = max(3, int(np.sqrt(max(budget, 8) / 2.0 * aspect)))
+        return nu, max(2, int(max(budget, 8) / 2.0 / nu))
+
+    n = max(int(1.15 * n_triangles), 2000)             # the grids round their budgets down
+    # floor: one grid over [-48, 48]^2 at z = 0 (past the sun volume in x and y)
+    nu, nv = grid_for(0.12 * n)
+    add(*_param_grid(nu, nv, lambda u, v: np.stack([96 * u - 48, 96 * v - 48, np.zeros_like(u)], -1)))
+    # columns: 30 cylinders on two rings
+    for k in range(30):
+        ang = 2 * np.pi * k / 15 + (0.1 if k >= 15 else 0.0)
+        rad = 14.0 if k < 15 else 24.0
+        cx, cy, r, h = rad * np.cos(ang), rad * np.sin(ang), 0.9 + 0.3 * rng.random(), 8.0 + 6.0 * rng.random()
+        nu, nv = grid_for(0.25 * n / 30, aspect=4.0)
+        add(*_param_grid(nu, nv, lambda u, v, cx=cx, cy=cy, r=r, h=h: np.stack(
+            [cx + r * np.cos(2 * np.pi * u), cy + r * np.sin(2 * np.pi * u), h * v], -1)))
+    # boxes: 24, each face a grid (one part per box)
+    for k in range(24):
+        c = np.array([rng.uniform(-30, 30), rng.uniform(-30, 30), 0.0])
+        s = np.array([rng.uniform(0.8, 4.0), rng.uniform(0.8, 4.0), rng.uniform(0.8, 5.0)])
+        nu, nv = grid_for(0.10 * n / 24 / 6)
+        ps, uvs, ts, off = [], [], [], 0
+        for axis in range(3):
+            for sign in (0.0, 1.0):
+                def face(u, v, axis=axis, sign=sign, c=c, s=s):
+                    q = np.zeros(u.shape + (3,))
+                    o = [i for i in range(3) if i != axis]
+                    q[..., axis] = sign
+                    q[..., o[0]], q[..., o[1]] = u, v
+                    return c + (q - np.array([0.5, 0.5, 0.0])) * s
+                p, uv, t = _param_grid(nu, nv, face)
+                ps.append(p); uvs.append(uv); ts.append(t + off); off += len(p)
+        add(np.concatenate(ps), np.concatenate(uvs), np.concatenate(ts))
+    # spheres: 40
+    for k in range(40):
+        c = np.array([rng.uniform(-35, 35), rng.uniform(-35, 35), rng.uniform(1, 12)])
+        r = rng.uniform(0.4, 3.0)
+        nu, nv = grid_for(0.33 * n / 40, aspect=2.0)
+        add(*_param_grid(nu, nv, lambda u, v, c=c, r=r: c + r * np.stack(
+            [np.sin(np.pi * v) * np.cos(2 * np.pi * u), np.sin(np.pi * v) * np.sin(2 * np.pi * u), np.cos(np.pi * v)], -1)))
+    # arch: half torus over the centre, in 4 parts
+    for k in range(4):
+        nu, nv = grid_for(0.08 * n / 4, aspect=3.0)
+        add(*_param_grid(nu, nv, lambda u, v, k=k: np.stack(
+            [(10 + 1.5 * np.cos(2 * np.pi * v)) * np.cos(np.pi * (k + u) / 4),
+             np.full_like(u, -6.0) + 1.5 * np.sin(2 * np.pi * v),
+             (10 + 1.5 * np.cos(2 * np.pi * v)) * np.sin(np.pi * (k + u) / 4)], -1)))
+    # hostile cases, one part
+    m = max(64, n // 200)
+    ps, ts = [], []
+    base = rng.uniform(-30, 30, (m, 3)); base[:, 2] = rng.uniform(0, 10, m)
+    d = rng.normal(size=(m, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
+    e = rng.normal(size=(m, 3)) * 1e-3                                          # slivers: 10-30 units long, 1e-3 wide
+    ps.append(np.stack([base, base + d * rng.uniform(10, 30, (m, 1)), base + d * 0.5 + e], 1).reshape(-1, 3))
+    ts.append(np.arange(3 * m).reshape(m, 3))
+    off = 3 * m
+    q = rng.uniform(-20, 20, (m, 3))                                           # degenerate: collinear, and a repeated index
+    ps.append(np.stack([q, q + 1.0, q + 2.0], 1).reshape(-1, 3)); ts.append(off + np.arange(3 * m).reshape(m, 3)); off += 3 * m
+    ts.append(off - 3 * m + np.stack([np.arange(m) * 3, np.arange(m) * 3, np.arange(m) * 3 + 1], 1))
+    far = np.array([[-60, -60, 50], [60, -60, 50], [60, 60, 50], [-60, 60, 50],     # above the volume (z > 40) and beyond it in x / y
+                    [-500, -500, -45], [500, -500, -45], [500, 500, -45], [-500, 500, -45],   # below, far larger than the map
+                    [30, 30, -60], [70, 30, 60], [30, 70, 0]], np.float64)                 # straddles the depth range
+    ps.append(far); ts.append(off + np.array([[0, 1, 2], [0, 2, 3], [4, 5, 6], [4, 6, 7], [8, 9, 10]])); off += len(far)
+    R = _sun_rotation(sun_angle)                                                # vertices on pixel centres of the map at sun_angle
+    k = max(16, m // 4)
+    ij = rng.integers(100, map_size - 100, (k, 2))
+    steps = rng.integers(1, 12, (k, 2))
+    cen = []
+    for (i, j), (a, b) in zip(ij, steps):
+        for (ii, jj) in ((i, j), (i + a, j), (i, j + b)):
+            xd, yd = (ii + 0.5) / (map_size / 2) - 1, (jj + 0.5) / (map_size / 2) - 1
+            zd = 0.3 + 0.4 * rng.random()
+            cen.append(R @ np.array([40 * xd, 40 * yd, (0.5 - zd) * 80]))
+    ps.append(np.array(cen)); ts.append(off + np.arange(3 * k).reshape(k, 3)); off += 3 * k
+    p = np.concatenate(ps)
+    add(p, np.zeros((len(p), 2)), np.concatenate(ts))
+    pos = np.concatenate(P).astype(np.float32)
+    verts = np.zeros((len(pos), 11), np.float32)
+    verts[:, 0:3] = pos
+    verts[:, 5] = 1.0                                                          # normal +z (not read by the pass)
+    verts[:, 9:11] = np.concatenate(UV).astype(np.float32)
+    return verts, np.concatenate(T).astype(np.uint32).ravel(), parts
