@@ -137,6 +137,12 @@ void pbrk_mc_set_kernels(int region, int lds);
 int pbrk_mc_region_flag_stats(unsigned long long* out3);
 /* samples that binning proved to tap one region from every texel of their tile (they run the body without tests), summed over tiles */
 int pbrk_mc_region_window_stats(unsigned long long* out1);
+/* absorbed words of the region kernel (PBR_MC_STATS=1), since the last reset: {wave-words skipped, their wave-samples, of those the
+ * samples run through the count-only body}.  A tile's region passes visit 4 x (its region flags) wave-samples in all. */
+int pbrk_mc_region_skip_stats(unsigned long long* out3);
+/* skipping of mask words whose samples provably cannot change any lane's fp32 sums (default 1; tests and A-B runs): the outputs are
+ * the same bit for bit either way */
+void pbrk_mc_set_absorb(int on);
 
 /* ---- K5: deferred shade pass (shaders/lighting_pass.glsl:432-716, in-scope sub-blocks). */
 typedef struct PbrkShadeArgs {

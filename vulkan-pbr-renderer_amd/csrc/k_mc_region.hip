@@ -24,6 +24,9 @@
 //      Measured (one box, A/B): C4 mip 1 36.7 -> 35.1 ms.  The same on the whole-face levels (39 -> 37 instructions) LOSES
 //      3-5 % -- the wave-uniform choice of body per sample costs more than two comparisons -- so it is compiled for SUB only;
 //      two separate loops (proved samples, then the rest) were slower on every level.
+//   2c. (round 4, absorbed words) a mask word whose samples provably cannot change any lane's fp32 sums is not accumulated
+//      (the lemma at absorb_threshold); its samples only run the count-only body, so the check of step 3 still sees every pair.
+//      Compiled for the 66^2 region shapes only (ABS).
 // Each (texel, sample) pair is accumulated exactly once, in an order (region, then sample index) that depends on the texel
 // only, not on the tile: a row-sharded dispatch equals a full one bit for bit.
 #include "pbr_device.h"
@@ -54,7 +57,10 @@ struct RegArgs {
     int expect[REG_MAX_S];      // samples per slice
     int tile_y0;                // MFMA variant: first tile row (multiple of 16) covering a.y0
     int pole_row[2];            // faces +X / -X: tile row (relative to the dispatch's first row, clamped) nearest to the pole of the tangent frame
-    unsigned long long* stats;  // optional: [0] += healed wave-slices, [1] += all wave-slices, [2] += (region, sample) flags, [3] += samples per tile, [4] += regions visited
+    int absorb;                 // skip mask words whose samples are absorbed by every lane's sums (pbrk_mc_set_absorb; bit-identical)
+    unsigned long long* stats;  // optional: [0] += healed wave-slices, [1] += all wave-slices, [2] += (region, sample) flags, [3] += samples per tile, [4] += regions visited,
+                                // [5] += proved samples (SUB), [6] += absorbed wave-words, [7] += their wave-samples, [8] += of those run through the
+                                // count-only body (a tile's region passes run 4 x [2] wave-samples in all)
 };
 
 // direction -> (sc, tc, ma) of face f: the table of v_cubesc / v_cubetc / v_cubema (gen_prefiltered_env_map.glsl:12-23)
@@ -71,7 +77,8 @@ __device__ __forceinline__ void face_coords(int f, float x, float y, float z, fl
 
 // One sample of a pass: accumulate it in the lanes whose direction falls into the staged region.
 // CLS = major axis of the region's face (0: x, 1: y, 2: z): the hardware's tie rule (z >= y >= x) in two comparisons.
-template <int RS, bool SUB, int CLS>
+// ACC = false: the count-only body of an absorbed word -- the same frame transform, predicates, ballots and pair count, no taps.
+template <int RS, bool SUB, int CLS, bool ACC = true>
 __device__ __forceinline__ void region_sample(const v4f e, unsigned lds_base, f3 Pb, f3 Pt, f3 Pr, float half_n, float off,
                                               float ulo, float uhi, float vlo, float vhi,
                                               float& ar, float& ag, float& ab, unsigned& cnt) {
@@ -90,6 +97,7 @@ __device__ __forceinline__ void region_sample(const v4f e, unsigned lds_base, f3
     // mask; a wave none of whose lanes is on the face skips the rest.  The (lane, sample) pairs taken are counted per wave
     // with scalar instructions.
     if (inm == 0) return;
+    if (!ACC && !SUB) { cnt += (unsigned)__builtin_popcountll(inm); return; }
     bool in = c1 && c2;
     const float h = __builtin_amdgcn_rcpf(ma) * half_n;
     const float u = fmaf(sc, h, off), v = fmaf(tc, h, off);                   // bordered tap coordinates, [0.5, n + 0.5]
@@ -101,7 +109,7 @@ __device__ __forceinline__ void region_sample(const v4f e, unsigned lds_base, f3
         in = in && c3 && c4 && c5 && c6;
     }
     cnt += (unsigned)__builtin_popcountll(inm);
-    if (in) {
+    if (ACC && in) {
         const float a = __builtin_amdgcn_fractf(u), b = __builtin_amdgcn_fractf(v);
         // whole 16-byte texels: ds_read_b128 runs at 256 B/clk/CU, the 12-byte form the compiler would pick at 96 (the
         // empty asm keeps the fourth component alive); LDS byte address = jl * row + (il << 4) + base (the region's origin
@@ -156,11 +164,33 @@ __device__ __forceinline__ void certain_sample(const v4f e, unsigned lds_base, f
     ab = fmaf(w11, q11.z, fmaf(w01, q01.z, fmaf(w10, q10.z, fmaf(w00, q00.z, ab))));
 }
 
+// ---- absorbed words (round 4) ----
+// Lemma.  acc' = fma(x, y, acc) is rounded once, to nearest even.  If acc is a normal positive float and 0 <= x y <= acc 2^-25, then
+// acc' == acc: with 2^e <= acc < 2^(e+1), acc 2^-25 < 2^(e-24) = ulp(acc) / 2, so the exact sum acc + x y lies less than half an ulp
+// above acc and rounds back to it.  acc being unchanged, the same bound covers the next FMA of the chain.
+// A sample's tap weights (wa, w11, w10, wt, w01, w00 of region_sample / certain_sample) are formed from its weight w >= 0 and
+// a, b in [0, 1) by monotone roundings: each lies in [0, w].  Its taps are texels of the staged region, so with M = the largest
+// R, G, B component staged for the region (border included; all finite and >= +0) every product of the sample's twelve FMAs is <= w M.
+// A mask word whose largest weight is W is therefore a no-op for a lane when W M <= acc 2^-25 holds for each of its three sums; a
+// wave skips the word only when that holds for all 64 lanes, so what it still accumulates keeps the order (region, sample index).
+// In fp32: T = fl(fl(W M) (1 + 2^-20)) 2^25 (the scaling is exact; an overflow gives +inf) and the test acc >= max(T, 2^-100).  For
+// acc >= 2^-100, acc 2^-25 >= 2^-125 is normal and exact; if W M > acc 2^-25 (normal range), fl(W M) >= W M (1 - 2^-24) and the
+// inflation keeps T > acc: a passing test implies the bound.  A NaN T fails every comparison, and so does a NaN sum.  A weight or
+// texel whose bit pattern is not below that of +inf (negative, -0, inf, NaN) switches the word / the region off.
+__device__ __forceinline__ float absorb_threshold(float wmax, float m) {
+    const float t = wmax * m * 1.00000095367431640625f * 0x1p25f;        // (W M) (1 + 2^-20) 2^25, left to right
+    return t < 0x1p-100f ? 0x1p-100f : t;                               // NaN stays NaN
+}
+
 // One pass over the flagged samples of this wave's slice for the staged region.  Samples are taken two at a time so that the
 // second table entry's scalar load is in flight while the first sample computes.
-// CERT: cwords holds, per mask word, the samples proved to be in this region for the whole tile (certain_sample).
+// cwords holds, per mask word, the samples proved to be in this region for the whole tile.  CERT: they run certain_sample; else
+// they are only credited in absorbed words.  cwords + NW: per mask word, the bit pattern of its largest weight.  rbits: the bit
+// pattern of the staged region's largest component, not below +inf's where absorbed words must not be skipped.  skc (stats only):
+// the workgroup's LDS counters {absorbed wave-words, their wave-samples, of those run through the count-only body}.
 template <int RS, bool SUB, int CLS, int REG_S, bool CERT>
-__device__ __forceinline__ void region_pass(unsigned lds_base, const unsigned* __restrict__ mwords, const unsigned* __restrict__ cwords, int NW, int s,
+__device__ __forceinline__ void region_pass(unsigned lds_base, const unsigned* __restrict__ mwords, const unsigned* __restrict__ cwords,
+                                            unsigned rbits, unsigned* skc, int NW, int s,
                                             ctab_t tab, f3 Pb, f3 Pt, f3 Pr, float half_n, float off,
                                             float ulo, float uhi, float vlo, float vhi,
                                             float& ar, float& ag, float& ab, unsigned& cnt) {
@@ -168,13 +198,36 @@ __device__ __forceinline__ void region_pass(unsigned lds_base, const unsigned* _
     unsigned cnext = (CERT && s < NW) ? (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[s]) : 0u;
     for (int w = s; w < NW; w += REG_S) {
         unsigned m = mnext;
-        const unsigned c = cnext;
+        unsigned c = cnext;
         mnext = w + REG_S < NW ? (unsigned)__builtin_amdgcn_readfirstlane((int)mwords[w + REG_S]) : 0u;
         if (CERT) {
             cnext = w + REG_S < NW ? (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[w + REG_S]) : 0u;
             cnt += 64u * (unsigned)__builtin_popcount(m & c);              // every lane takes every proved sample
         }
         ctab_t tw = tab + (w << 5);
+        const unsigned wb = (rbits < 0x7f800000u && m != 0u) ? (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[NW + w]) : 0x7f800000u;
+        if (wb < 0x7f800000u) {
+            const float T = absorb_threshold(__uint_as_float(wb), __uint_as_float(rbits));
+            if (__builtin_amdgcn_ballot_w64(!(ar >= T && ag >= T && ab >= T)) == 0ull) {
+                // absorbed for all 64 lanes: proved samples are credited, the rest run the count-only body (the net of step 3)
+                if (!CERT) {
+                    c = (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[w]);
+                    cnt += 64u * (unsigned)__builtin_popcount(m & c);
+                }
+                if (skc && (threadIdx.x & 63) == 0) {
+                    atomicAdd(&skc[0], 1u);
+                    atomicAdd(&skc[1], (unsigned)__builtin_popcount(m));
+                    atomicAdd(&skc[2], (unsigned)__builtin_popcount(m & ~c));
+                }
+                m &= ~c;
+                while (m) {
+                    const int i0 = __builtin_ctz(m);
+                    m &= m - 1u;
+                    region_sample<RS, SUB, CLS, false>(tw[i0], lds_base, Pb, Pt, Pr, half_n, off, ulo, uhi, vlo, vhi, ar, ag, ab, cnt);
+                }
+                continue;
+            }
+        }
         while (m) {
             const int i0 = __builtin_ctz(m);
             m &= m - 1u;
@@ -198,15 +251,17 @@ __device__ __forceinline__ void region_pass(unsigned lds_base, const unsigned* _
 // direction is pushed through the tile-centre frame; a rigorous bound on how far a texel's own frame can move it yields the
 // regions; one bit per (region, sample) in `masks`, any[r] != 0 when region r has a bit.  Leaves with a barrier pending: callers
 // synchronise before reading the masks.
-// cmask (optional, [NW], directly behind dmax and zeroed here with the rest): bit i set when sample i is PROVED to tap one region
-// of one face from every texel of the tile -- certainly on the face (ma' - |sc'| >= (ma - |sc|) - sqrt(2) delta > 0), its tap
-// bounds inside the face and inside one region's cells.  Such a sample has exactly one region flag.
+// cmask (optional, [NW]): bit i set when sample i is PROVED to tap one region of one face from every texel of the tile -- certainly
+// on the face (ma' - |sc'| >= (ma - |sc|) - sqrt(2) delta > 0), its tap bounds inside the face and inside one region's cells.  Such
+// a sample has exactly one region flag.  wmax (optional, [NW]): per mask word, the largest bit pattern of its samples' weights (for
+// weights >= +0 the largest weight; anything else orders above +inf).  The ntail words behind dmax are zeroed with the masks.
 __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsigned* dmax, int NR, int NW, int G, int RC, int n,
-                                           f3 R, f3 T, f3 B, f3 Rc, f3 Tc, f3 Bc, ctab_t tab, int n_tab, int tid, unsigned* cmask = nullptr) {
+                                           f3 R, f3 T, f3 B, f3 Rc, f3 Tc, f3 Bc, ctab_t tab, int n_tab, int tid,
+                                           unsigned* cmask = nullptr, unsigned* wmax = nullptr, int ntail = 0) {
     const float nf = (float)n;
     const float half_n = 0.5f * nf;
     const float off = 0.5f * nf + 0.5f;
-    for (int k = tid; k < NR * NW + NR + 1 + (cmask ? NW : 0); k += 1024) masks[k] = 0u;
+    for (int k = tid; k < NR * NW + NR + 1 + ntail; k += 1024) masks[k] = 0u;
     __syncthreads();
     {
         f3 dR = sub3(R, Rc), dT = sub3(T, Tc), dB = sub3(B, Bc);
@@ -224,6 +279,7 @@ __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsig
         const float Ly = fmaf(e.x, Bc.y, fmaf(e.y, Tc.y, e.z * Rc.y));
         const float Lz = fmaf(e.x, Bc.z, fmaf(e.y, Tc.z, e.z * Rc.z));
         const unsigned bit = 1u << (i & 31);
+        if (wmax) atomicMax(&wmax[i >> 5], __float_as_uint(e.w));
 #pragma unroll
         for (int f = 0; f < 6; ++f) {
             float sc, tc, ma;
@@ -267,11 +323,18 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_r[];
     float4* region = (float4*)smem_r;
     const unsigned lds_base = (unsigned)(unsigned long long)smem_r;      // LDS byte offset of the staged region (low half of the flat address)
-    unsigned* masks = (unsigned*)(smem_r + RS * RS * 16);
+    unsigned* skc = (unsigned*)(smem_r + RS * RS * 16);                  // [4] (absorb, stats) counters of the absorbed words: a fixed address
+    unsigned* masks = skc + 4;
     unsigned* any = masks + q.NR * q.NW;
     unsigned* dmax = any + q.NR;
     constexpr bool CERT = SUB;                                           // see the header, 2b
-    unsigned* cmask = dmax + 1;                                          // [NW] (CERT) samples proved to tap one region from the whole tile
+    // see the header, 2c: compiled for the 66^2 region shapes only.  The 34^2 / 18^2 levels of C4 (mips 3, 4: weights fall to ~e^-6)
+    // never absorb a word, and the test alone cost them 7 % (measured); without it their code is that of round 3
+    constexpr bool ABS = RS == 66;
+    const bool absorb_on = ABS && q.absorb;                              // workgroup-uniform
+    unsigned* cmask = dmax + 1;                                          // [NW] samples proved to tap one region from the whole tile
+    unsigned* wmax = cmask + q.NW;                                       // [NW] (absorb) largest weight (bit pattern) per mask word
+    unsigned* rmax = wmax + q.NW;                                        // [NR] (absorb) largest staged R, G, B bit pattern per region
     const McArgs& p = q.a;
     const int tid = threadIdx.x;
     const int s = __builtin_amdgcn_readfirstlane(tid / REG_TX);
@@ -319,7 +382,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     const int NW = q.NW, NR = q.NR, G = q.G, RC = q.RC;
 
     // ---- 1. binning ----
-    region_bin(masks, any, dmax, NR, NW, G, RC, n, R, T, B, Rc, Tc, Bc, tab, p.n_tab, tid, CERT ? cmask : nullptr);
+    if (ABS && tid < 4) skc[tid] = 0u;                                   // ordered by the barrier behind region_bin's clearing
+    region_bin(masks, any, dmax, NR, NW, G, RC, n, R, T, B, Rc, Tc, Bc, tab, p.n_tab, tid, (CERT || ABS) ? cmask : nullptr,
+               absorb_on ? wmax : nullptr, absorb_on ? 2 * NW + NR : ((CERT || ABS) ? NW : 0));
 
     // ---- 2. region passes ----
     float ar = 0.0f, ag = 0.0f, ab = 0.0f;
@@ -340,11 +405,28 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         const int ox = gx * RC, oy = gy * RC;
         const int rcx = min(RC, n + 1 - ox), rcy = min(RC, n + 1 - oy);      // cells of this region; texels: one more
         const float4* __restrict__ fsrc = p.src + ((size_t)f * nb + oy) * nb + ox;
+        unsigned vmax = 0u;                                        // largest R, G, B bit pattern: any negative / inf / NaN orders above +inf
         for (int k = tid; k < RS * RS; k += 1024) {
             const int ry = k / RS, rx = k - ry * RS;
-            if (rx <= rcx && ry <= rcy) region[k] = fsrc[ry * nb + rx];
+            if (rx <= rcx && ry <= rcy) {
+                const float4 v = fsrc[ry * nb + rx];
+                region[k] = v;
+                if (ABS) vmax = max(vmax, max(__float_as_uint(v.x), max(__float_as_uint(v.y), __float_as_uint(v.z))));
+            }
+        }
+        if (absorb_on) {                                           // wave maximum, one LDS atomic per wave, ahead of the barrier
+            // xor butterflies inside each 32-lane half (ds_swizzle: the pattern is an immediate, no lane-address registers), halves via readlane
+            vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (16 << 10) | 0x1f));
+            vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (8 << 10) | 0x1f));
+            vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (4 << 10) | 0x1f));
+            vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (2 << 10) | 0x1f));
+            vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (1 << 10) | 0x1f));
+            const unsigned wv = max((unsigned)__builtin_amdgcn_readlane((int)vmax, 0), (unsigned)__builtin_amdgcn_readlane((int)vmax, 32));
+            if ((tid & 63) == 0) atomicMax(&rmax[r], wv);
         }
         __syncthreads();
+        // wave-uniform; the pattern of +inf (never below itself) when absorbed words must not be skipped
+        const unsigned rbits = absorb_on ? (unsigned)__builtin_amdgcn_readfirstlane((int)rmax[r]) : 0x7f800000u;
         // signed permutation of the frame for this face: rows give (sc, tc, ma) directly
         f3 Pb, Pt, Pr;
         face_coords(f, B.x, B.y, B.z, Pb.x, Pb.y, Pb.z);
@@ -352,10 +434,11 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         face_coords(f, R.x, R.y, R.z, Pr.x, Pr.y, Pr.z);
         const unsigned* mw = masks + r * NW;
         const unsigned pass_base = lds_base - (unsigned)(oy * RS + ox) * 16u;      // taps are addressed with face coordinates
+        unsigned* const sc = (ABS && q.stats) ? skc : nullptr;
         switch (f >> 1) {
-        case 0: region_pass<RS, SUB, 0, REG_S, CERT>(pass_base, mw, cmask, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
-        case 1: region_pass<RS, SUB, 1, REG_S, CERT>(pass_base, mw, cmask, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
-        default: region_pass<RS, SUB, 2, REG_S, CERT>(pass_base, mw, cmask, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+        case 0: region_pass<RS, SUB, 0, REG_S, CERT>(pass_base, mw, cmask, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+        case 1: region_pass<RS, SUB, 1, REG_S, CERT>(pass_base, mw, cmask, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+        default: region_pass<RS, SUB, 2, REG_S, CERT>(pass_base, mw, cmask, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
         }
     }
 
@@ -387,6 +470,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 
     // ---- 4. combine the slices (fixed tree) and store ----
     __syncthreads();                                               // everybody is done with the staged region
+    if (absorb_on && q.stats && tid < 3 && skc[tid]) atomicAdd(&q.stats[6 + tid], (unsigned long long)skc[tid]);
     float* red = (float*)smem_r;
     red[(s * REG_TX + t) * 3 + 0] = ar;
     red[(s * REG_TX + t) * 3 + 1] = ag;
@@ -647,12 +731,17 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 }
 
 static unsigned long long* g_reg_stats = nullptr;      // device counters, enabled by PBR_MC_STATS=1
+#define REG_STATS_BYTES 128                            // 16 slots (RegArgs::stats)
 
 extern "C" int pbrk_mc_region_stats(unsigned long long* out2, int reset) {
     if (!g_reg_stats || !out2) return PBRK_E_ARG;
     if (hipMemcpy(out2, g_reg_stats, 16, hipMemcpyDeviceToHost) != hipSuccess) return PBRK_E_LAUNCH;
-    if (reset && hipMemset(g_reg_stats, 0, 64) != hipSuccess) return PBRK_E_LAUNCH;
+    if (reset && hipMemset(g_reg_stats, 0, REG_STATS_BYTES) != hipSuccess) return PBRK_E_LAUNCH;
     return PBRK_OK;
+}
+extern "C" int pbrk_mc_region_skip_stats(unsigned long long* out3) {      // absorbed words: see RegArgs::stats [6..8]
+    if (!g_reg_stats || !out3) return PBRK_E_ARG;
+    return hipMemcpy(out3, g_reg_stats + 6, 24, hipMemcpyDeviceToHost) == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
 }
 extern "C" int pbrk_mc_region_window_stats(unsigned long long* out1) {      // samples run through the test-free body (sum over tiles)
     if (!g_reg_stats || !out1) return PBRK_E_ARG;
@@ -680,6 +769,9 @@ static void launch_mfma_t(const RegArgs& q, unsigned grid, size_t lds, hipStream
 // Which kernel serves a level (tests / A-B runs; -1 = the environment variable PBR_MC_REGION / PBR_MC_LDS, else the default 1)
 int g_mc_region_mode = -1, g_mc_lds_mode = -1;
 extern "C" void pbrk_mc_set_kernels(int region, int lds) { g_mc_region_mode = region; g_mc_lds_mode = lds; }
+// Skipping of absorbed words (tests / A-B runs; the outputs are the same bit for bit either way)
+static int g_mc_absorb = 1;
+extern "C" void pbrk_mc_set_absorb(int on) { g_mc_absorb = on ? 1 : 0; }
 
 bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
     static int stats_on = -1;
@@ -696,12 +788,17 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
     else { RS = 66; q.RC = 65; q.G = (a.n_src + 1 + 64) / 65; }
     q.NR = 6 * q.G * q.G;
     q.NW = (a.n_tab + 31) / 32;
-    size_t lds = (size_t)RS * RS * 16 + ((size_t)q.NR * q.NW + q.NR + 4 + (q.G > 1 ? q.NW : 0)) * 4;      // region, flags, any[], dmax, (quarter-face levels) proved-sample flags
+    // counters, region flags, any[], dmax, proved-sample flags, (absorb) wmax[], rmax[]; where the last two do not fit, the level runs
+    // without them.  The absorbed-word skip is compiled for the 66^2 shapes only (k_mc_region, ABS).
+    q.absorb = RS == 66 ? g_mc_absorb : 0;
+    const size_t lds_fixed = (size_t)RS * RS * 16 + (4 + (size_t)q.NR * q.NW + q.NR + 1 + q.NW) * 4;
+    size_t lds = lds_fixed + (q.absorb ? (size_t)(q.NW + q.NR) * 4 : 0);
+    if (lds > 80 * 1024) { q.absorb = 0; lds = lds_fixed; }
     if (lds < (size_t)1024 * 3 * 4) lds = (size_t)1024 * 3 * 4;      // the slices' partial sums (REG_S * REG_TX = 1024 texel-slices)
     if (lds > 80 * 1024) return false;                             // two workgroups per CU or not at all
     if (stats_on < 0) {
         const char* e = getenv("PBR_MC_STATS"); stats_on = e ? atoi(e) : 0;
-        if (stats_on) { if (hipMalloc(&g_reg_stats, 64) != hipSuccess) g_reg_stats = nullptr; else (void)hipMemset(g_reg_stats, 0, 64); }
+        if (stats_on) { if (hipMalloc(&g_reg_stats, REG_STATS_BYTES) != hipSuccess) g_reg_stats = nullptr; else (void)hipMemset(g_reg_stats, 0, REG_STATS_BYTES); }
     }
     q.stats = g_reg_stats;
     // Tile size: 16 x 16 output texels x 4 slices of the sample table everywhere.  Measured and dropped: 8 x 8 tiles x 16
