@@ -143,6 +143,8 @@ int pbrk_mc_region_skip_stats(unsigned long long* out3);
 /* skipping of mask words whose samples provably cannot change any lane's fp32 sums (default 1; tests and A-B runs): the outputs are
  * the same bit for bit either way */
 void pbrk_mc_set_absorb(int on);
+/* the region kernel's round-5 loop on the 66^2 region shapes (default on; the outputs are the same bit for bit either way) */
+void pbrk_mc_set_runs(int on);
 
 /* ---- K5: deferred shade pass (shaders/lighting_pass.glsl:432-716, in-scope sub-blocks). */
 typedef struct PbrkShadeArgs {

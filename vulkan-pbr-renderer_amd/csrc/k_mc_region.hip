@@ -27,6 +27,8 @@
 //   2c. (round 4, absorbed words) a mask word whose samples provably cannot change any lane's fp32 sums is not accumulated
 //      (the lemma at absorb_threshold); its samples only run the count-only body, so the check of step 3 still sees every pair.
 //      Compiled for the 66^2 region shapes only (ABS).
+//   2d. (round 5, 66^2 shapes, RUNS) less scalar work per sample: only non-empty words, runs of proved samples without a per-sample
+//      test, counts per lane (one ballot chain), a barrier per visited region only (region_pass_runs; C4 72.2 -> 66.2 ms, same bytes).
 // Each (texel, sample) pair is accumulated exactly once, in an order (region, then sample index) that depends on the texel
 // only, not on the tile: a row-sharded dispatch equals a full one bit for bit.
 #include "pbr_device.h"
@@ -164,6 +166,66 @@ __device__ __forceinline__ void certain_sample(const v4f e, unsigned lds_base, f
     ab = fmaf(w11, q11.z, fmaf(w01, q01.z, fmaf(w10, q10.z, fmaf(w00, q00.z, ab))));
 }
 
+// ---- scalar-lean loop (round 5, 66^2 shapes) ----
+// The same sample as region_sample, counted PER LANE: cnt += 1 in the lanes that take it, under the exec mask the body runs with
+// anyway.  That drops the second ballot chain (one 4-way s_and_b64 chain for the count, another for the exec mask) and the
+// s_bcnt1; only the wave-uniform early exit of SUB keeps a ballot.  Taps, weights and FMA order are region_sample's, bit for bit.
+template <int RS, bool SUB, int CLS, bool ACC = true>
+__device__ __forceinline__ void lane_sample(const v4f e, unsigned lds_base, f3 Pb, f3 Pt, f3 Pr, float half_n, float off,
+                                            float ulo, float uhi, float vlo, float vhi,
+                                            float& ar, float& ag, float& ab, unsigned& cnt) {
+    const float sc = fmaf(e.x, Pb.x, fmaf(e.y, Pt.x, e.z * Pr.x));
+    const float tc = fmaf(e.x, Pb.y, fmaf(e.y, Pt.y, e.z * Pr.y));
+    const float ma = fmaf(e.x, Pb.z, fmaf(e.y, Pt.z, e.z * Pr.z));
+    bool c1, c2;
+    if (CLS == 0) { c1 = ma > fabsf(sc); c2 = ma > fabsf(tc); }
+    else if (CLS == 1) { c1 = ma >= fabsf(sc); c2 = ma > fabsf(tc); }
+    else { c1 = ma >= fabsf(sc); c2 = ma >= fabsf(tc); }
+    bool in = c1 && c2;
+    if (SUB && __builtin_amdgcn_ballot_w64(in) == 0ull) return;    // no lane on the face: skip the projection
+    const float h = __builtin_amdgcn_rcpf(ma) * half_n;
+    const float u = fmaf(sc, h, off), v = fmaf(tc, h, off);
+    if (SUB) in = in && u >= ulo && u < uhi && v >= vlo && v < vhi;
+    if (in) {
+        cnt += 1u;
+        if (ACC) {
+            const int il = (int)u, jl = (int)v;
+            const float a = __builtin_amdgcn_fractf(u), b = __builtin_amdgcn_fractf(v);
+            unsigned t16, addr;
+            asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(t16) : "v"(il), "s"(lds_base));
+            asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(addr) : "v"(jl), "s"(RS * 16), "v"(t16));
+            lds_v4f_p tp = (lds_v4f_p)(unsigned long long)addr;
+            v4f q00 = tp[0], q10 = tp[1], q01 = tp[RS], q11 = tp[RS + 1];
+            asm("" : "+v"(q00)); asm("" : "+v"(q10)); asm("" : "+v"(q01)); asm("" : "+v"(q11));
+            const float wgt = e.w;
+            const float wa = wgt * a;
+            const float w11 = wa * b;
+            const float w10 = wa - w11;
+            const float wt = wgt - wa;
+            const float w01 = wt * b;
+            const float w00 = wt - w01;
+            ar = fmaf(w11, q11.x, fmaf(w01, q01.x, fmaf(w10, q10.x, fmaf(w00, q00.x, ar))));
+            ag = fmaf(w11, q11.y, fmaf(w01, q01.y, fmaf(w10, q10.y, fmaf(w00, q00.y, ag))));
+            ab = fmaf(w11, q11.z, fmaf(w01, q01.z, fmaf(w10, q10.z, fmaf(w00, q00.z, ab))));
+        }
+    }
+}
+
+// f(entry) for the samples of mask m in index order; the next entry's scalar load is issued before the current sample computes
+template <typename F>
+__device__ __forceinline__ void each_sample(unsigned m, ctab_t tw, F&& f) {
+    if (m == 0u) return;
+    v4f e = tw[__builtin_ctz(m)];
+    m &= m - 1u;
+    while (m) {
+        const v4f en = tw[__builtin_ctz(m)];
+        m &= m - 1u;
+        f(e);
+        e = en;
+    }
+    f(e);
+}
+
 // ---- absorbed words (round 4) ----
 // Lemma.  acc' = fma(x, y, acc) is rounded once, to nearest even.  If acc is a normal positive float and 0 <= x y <= acc 2^-25, then
 // acc' == acc: with 2^e <= acc < 2^(e+1), acc 2^-25 < 2^(e-24) = ulp(acc) / 2, so the exact sum acc + x y lies less than half an ulp
@@ -247,6 +309,59 @@ __device__ __forceinline__ void region_pass(unsigned lds_base, const unsigned* _
     }
 }
 
+// region_pass with less scalar work per word and per sample (round 5, 66^2 shapes; RUNS in k_mc_region).  Same words, samples,
+// bodies, absorb decisions and FMA order; cnt counts per LANE (every lane of a complete wave ends at expect[s]):
+//   * only the non-empty words of the slice are visited: one LDS read per lane (lane k: word s + REG_S k; NW <= 256) and a ballot;
+//   * CERT: the proved samples below the next tested one run as a run of certain_sample (no per-sample proved-bit test, no exec
+//     join), then the tested one, in index order;
+//   * tested samples use lane_sample (one ballot chain), and every loop issues the next table entry's load ahead of the body.
+template <int RS, bool SUB, int CLS, int REG_S, bool CERT>
+__device__ __forceinline__ void region_pass_runs(unsigned lds_base, const unsigned* __restrict__ mwords, const unsigned* __restrict__ cwords,
+                                                 unsigned rbits, unsigned* skc, int NW, int s,
+                                                 ctab_t tab, f3 Pb, f3 Pt, f3 Pr, float half_n, float off,
+                                                 float ulo, float uhi, float vlo, float vhi,
+                                                 float& ar, float& ag, float& ab, unsigned& cnt) {
+    const int wl = s + REG_S * (int)(threadIdx.x & 63);
+    unsigned long long nz = __builtin_amdgcn_ballot_w64(wl < NW && mwords[wl] != 0u);
+    auto tested = [&](const v4f e) { lane_sample<RS, SUB, CLS>(e, lds_base, Pb, Pt, Pr, half_n, off, ulo, uhi, vlo, vhi, ar, ag, ab, cnt); };
+    while (nz) {
+        const int w = s + REG_S * (int)__builtin_ctzll(nz);
+        nz &= nz - 1ull;
+        const unsigned m = (unsigned)__builtin_amdgcn_readfirstlane((int)mwords[w]);
+        unsigned c = CERT ? (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[w]) : 0u;
+        ctab_t tw = tab + (w << 5);
+        const unsigned wb = rbits < 0x7f800000u ? (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[NW + w]) : 0x7f800000u;
+        if (wb < 0x7f800000u) {
+            const float T = absorb_threshold(__uint_as_float(wb), __uint_as_float(rbits));
+            if (__builtin_amdgcn_ballot_w64(!(ar >= T && ag >= T && ab >= T)) == 0ull) {
+                if (!CERT) c = (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[w]);
+                cnt += (unsigned)__builtin_popcount(m & c);                // every lane takes every proved sample
+                if (skc && (threadIdx.x & 63) == 0) {
+                    atomicAdd(&skc[0], 1u);
+                    atomicAdd(&skc[1], (unsigned)__builtin_popcount(m));
+                    atomicAdd(&skc[2], (unsigned)__builtin_popcount(m & ~c));
+                }
+                each_sample(m & ~c, tw, [&](const v4f e) {
+                    lane_sample<RS, SUB, CLS, false>(e, lds_base, Pb, Pt, Pr, half_n, off, ulo, uhi, vlo, vhi, ar, ag, ab, cnt);
+                });
+                continue;
+            }
+        }
+        if (!CERT) { each_sample(m, tw, tested); continue; }
+        cnt += (unsigned)__builtin_popcount(m & c);
+        unsigned mc = m & c, mu = m & ~c;
+        for (;;) {
+            const unsigned below = mu ? (mu & (0u - mu)) - 1u : ~0u;     // the samples before the next tested one (all: none left)
+            each_sample(mc & below, tw, [&](const v4f e) { certain_sample<RS>(e, lds_base, Pb, Pt, Pr, half_n, off, ar, ag, ab); });
+            mc &= ~below;
+            if (!mu) break;
+            const int it = __builtin_ctz(mu);
+            mu &= mu - 1u;
+            tested(tw[it]);
+        }
+    }
+}
+
 // Binning (once per tile): which regions of the source level can the samples reach from ANY texel of the tile?  Every sample
 // direction is pushed through the tile-centre frame; a rigorous bound on how far a texel's own frame can move it yields the
 // regions; one bit per (region, sample) in `masks`, any[r] != 0 when region r has a bit.  Leaves with a barrier pending: callers
@@ -317,7 +432,8 @@ __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsig
     }
 }
 
-template <int RS, bool SUB, int TILE>
+// RUNS (66^2 shapes only): the region loop visits the flagged regions only and runs region_pass_runs (round 5; cnt per lane)
+template <int RS, bool SUB, int TILE, bool RUNS = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_mc_region(const RegArgs q) {
     constexpr int REG_TX = TILE * TILE, REG_S = 1024 / REG_TX;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_r[];
@@ -397,9 +513,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         if (tid == 0) { atomicAdd(&q.stats[3], (unsigned long long)p.n_tab); unsigned v = 0; for (int r = 0; r < NR; ++r) v += any[r] != 0u; atomicAdd(&q.stats[4], (unsigned long long)v);
                         if (CERT) { unsigned c = 0; for (int k = 0; k < NW; ++k) c += __popc(cmask[k]); atomicAdd(&q.stats[5], (unsigned long long)c); } }
     }
-    for (int r = 0; r < NR; ++r) {
-        __syncthreads();                                           // binning done / readers of the previous region done
-        if (any[r] == 0u) continue;                                // workgroup-uniform
+    auto visit = [&](const int r) {                                // stage region r and run this wave's slice over it
         const int f = r / (G * G);
         const int gy = (r / G) % G, gx = r % G;
         const int ox = gx * RC, oy = gy * RC;
@@ -435,18 +549,43 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         const unsigned* mw = masks + r * NW;
         const unsigned pass_base = lds_base - (unsigned)(oy * RS + ox) * 16u;      // taps are addressed with face coordinates
         unsigned* const sc = (ABS && q.stats) ? skc : nullptr;
+        if (RUNS) {
+            switch (f >> 1) {
+            case 0: region_pass_runs<RS, SUB, 0, REG_S, CERT>(pass_base, mw, cmask, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+            case 1: region_pass_runs<RS, SUB, 1, REG_S, CERT>(pass_base, mw, cmask, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+            default: region_pass_runs<RS, SUB, 2, REG_S, CERT>(pass_base, mw, cmask, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+            }
+            return;
+        }
         switch (f >> 1) {
         case 0: region_pass<RS, SUB, 0, REG_S, CERT>(pass_base, mw, cmask, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
         case 1: region_pass<RS, SUB, 1, REG_S, CERT>(pass_base, mw, cmask, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
         default: region_pass<RS, SUB, 2, REG_S, CERT>(pass_base, mw, cmask, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+        }
+    };
+    if (RUNS) {
+        // the barrier ahead of each staging runs for the flagged regions only (once per visited region instead of once per region
+        // of the level); any[] is final after binning, so the skip needs none.  (A 64-bit mask of the visited regions kept across
+        // the passes, or a ballot search for the next one, spills VGPRs at the 64-VGPR budget of the quarter-face shape.)
+        __syncthreads();                                           // binning done
+        for (int r = 0; r < NR; ++r) {
+            if (__builtin_amdgcn_readfirstlane((int)any[r]) == 0) continue;      // workgroup-uniform
+            __syncthreads();                                       // readers of the previous region done
+            visit(r);
+        }
+    } else {
+        for (int r = 0; r < NR; ++r) {
+            __syncthreads();                                       // binning done / readers of the previous region done
+            if (any[r] == 0u) continue;                            // workgroup-uniform
+            visit(r);
         }
     }
 
     // ---- 3. completeness check; a wave that missed a sample recomputes its slice with direct loads ----
     // cnt is a wave total (scalar): no (texel, sample) pair can be taken twice -- the in-region tests partition the tap positions
     // exactly -- so the total is right exactly when no lane missed a sample
-    const unsigned expect = 64u * (unsigned)q.expect[s];
-    const bool healed = cnt != expect;
+    // RUNS: cnt per lane; a wave recomputes when any lane's count is off (a stronger test than the total)
+    const bool healed = RUNS ? __builtin_amdgcn_ballot_w64(cnt != (unsigned)q.expect[s]) != 0ull : cnt != 64u * (unsigned)q.expect[s];
     if (healed) {
         __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.src, 0, (int)p.src_bytes, 0x00020000);
         ar = 0.0f; ag = 0.0f; ab = 0.0f;
@@ -752,11 +891,11 @@ extern "C" int pbrk_mc_region_flag_stats(unsigned long long* out3) {
     return hipMemcpy(out3, g_reg_stats + 2, 24, hipMemcpyDeviceToHost) == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
 }
 
-template <int RS, bool SUB, int TILE>
+template <int RS, bool SUB, int TILE, bool RUNS = false>
 static void launch_region_t(const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
     static bool attr_set = false;
-    if (!attr_set) { (void)hipFuncSetAttribute((const void*)k_mc_region<RS, SUB, TILE>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
-    hipLaunchKernelGGL((k_mc_region<RS, SUB, TILE>), dim3(grid), dim3(1024), lds, st, q);
+    if (!attr_set) { (void)hipFuncSetAttribute((const void*)k_mc_region<RS, SUB, TILE, RUNS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
+    hipLaunchKernelGGL((k_mc_region<RS, SUB, TILE, RUNS>), dim3(grid), dim3(1024), lds, st, q);
 }
 
 template <int RS, bool SUB>
@@ -772,6 +911,9 @@ extern "C" void pbrk_mc_set_kernels(int region, int lds) { g_mc_region_mode = re
 // Skipping of absorbed words (tests / A-B runs; the outputs are the same bit for bit either way)
 static int g_mc_absorb = 1;
 extern "C" void pbrk_mc_set_absorb(int on) { g_mc_absorb = on ? 1 : 0; }
+// The round-5 loop of the 66^2 shapes (k_mc_region RUNS; tests / A-B runs; the outputs are the same bit for bit either way)
+static int g_mc_runs = 1;
+extern "C" void pbrk_mc_set_runs(int on) { g_mc_runs = on ? 1 : 0; }
 
 bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
     static int stats_on = -1;
@@ -839,7 +981,7 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
     const unsigned grid = (unsigned)(q.a.tiles_per_face * nfaces);
     if (RS == 18) launch_region_t<18, false, 16>(q, grid, lds, st);
     else if (RS == 34) launch_region_t<34, false, 16>(q, grid, lds, st);
-    else if (q.G == 1) launch_region_t<66, false, 16>(q, grid, lds, st);
-    else launch_region_t<66, true, 16>(q, grid, lds, st);
+    else if (q.G == 1) { if (g_mc_runs) launch_region_t<66, false, 16, true>(q, grid, lds, st); else launch_region_t<66, false, 16>(q, grid, lds, st); }
+    else { if (g_mc_runs) launch_region_t<66, true, 16, true>(q, grid, lds, st); else launch_region_t<66, true, 16>(q, grid, lds, st); }
     return true;
 }
