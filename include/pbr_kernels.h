@@ -145,6 +145,9 @@ int pbrk_mc_region_skip_stats(unsigned long long* out3);
 void pbrk_mc_set_absorb(int on);
 /* the region kernel's round-5 loop on the 66^2 region shapes (default on; the outputs are the same bit for bit either way) */
 void pbrk_mc_set_runs(int on);
+/* the region kernel's visiting order: the k-th region (0 .. 6 G^2 - 1) a tile of `face` stages at G regions per face edge -- its own
+ * face's regions first, then the others in index order; -1 for arguments out of range.  Host-side twin of the kernel's loop. */
+int pbrk_mc_region_order(int face, int G, int k);
 
 /* ---- K5: deferred shade pass (shaders/lighting_pass.glsl:432-716, in-scope sub-blocks). */
 typedef struct PbrkShadeArgs {

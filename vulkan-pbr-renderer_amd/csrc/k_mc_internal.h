@@ -64,6 +64,12 @@ __device__ __forceinline__ f3 sample_bordered(__amdgpu_buffer_rsrc_t rs, f3 L, f
     return r;
 }
 
+// k_mc_region.hip: the k-th region a tile visits -- the GG regions of its own face (first region: own) first, then all the
+// others in index order.  A permutation of 0 .. NR-1 that depends on the face only.
+__host__ __device__ __forceinline__ int mc_region_visit(int k, int own, int GG) {
+    return k < GG ? own + k : (k < own + GG ? k - GG : k);
+}
+
 // k_mc_region.hip: taps from LDS-staged regions of the source level.  Returns false when the kernel does not apply
 // (the caller then takes the direct kernel); the decision depends on the level's shape only, never on the dispatched range.
 bool launch_mc_region(McArgs a, int nfaces, hipStream_t st);

@@ -29,7 +29,14 @@
 //      Compiled for the 66^2 region shapes only (ABS).
 //   2d. (round 5, 66^2 shapes, RUNS) less scalar work per sample: only non-empty words, runs of proved samples without a per-sample
 //      test, counts per lane (one ballot chain), a barrier per visited region only (region_pass_runs; C4 72.2 -> 66.2 ms, same bytes).
-// Each (texel, sample) pair is accumulated exactly once, in an order (region, then sample index) that depends on the texel
+//   2e. (round 6, visiting order) a tile visits the regions of its OWN face first, then all the others in index order
+//      (mc_region_visit, k_mc_internal.h).  The own face holds a texel's big terms (small angles, large weights); met first, they
+//      make the sums every later word is tested against in 2c, so the neighbours' tail words are absorbed on every face and not
+//      only on the faces whose index happens to be the lowest (C4 mip 2: 0.439 -> 0.478 of the wave-samples absorbed, the six
+//      faces 0.47-0.49 instead of 0.40-0.47; profiles/r06_order.md).
+//      Taken by the 66^2 shapes, where words are absorbed; the 34^2 / 18^2 shapes keep index order (OWN_FIRST in k_mc_region).
+// Each (texel, sample) pair is accumulated exactly once, in an order (66^2 shapes: own face's regions, then the other regions in
+// index order; else regions in index order; sample index inside a region) that depends on the level's shape and the texel's face
 // only, not on the tile: a row-sharded dispatch equals a full one bit for bit.
 #include "pbr_device.h"
 #include "pbr_kernels.h"
@@ -234,7 +241,7 @@ __device__ __forceinline__ void each_sample(unsigned m, ctab_t tw, F&& f) {
 // a, b in [0, 1) by monotone roundings: each lies in [0, w].  Its taps are texels of the staged region, so with M = the largest
 // R, G, B component staged for the region (border included; all finite and >= +0) every product of the sample's twelve FMAs is <= w M.
 // A mask word whose largest weight is W is therefore a no-op for a lane when W M <= acc 2^-25 holds for each of its three sums; a
-// wave skips the word only when that holds for all 64 lanes, so what it still accumulates keeps the order (region, sample index).
+// wave skips the word only when that holds for all 64 lanes, so what it still accumulates keeps the order (region as visited, sample index).
 // In fp32: T = fl(fl(W M) (1 + 2^-20)) 2^25 (the scaling is exact; an overflow gives +inf) and the test acc >= max(T, 2^-100).  For
 // acc >= 2^-100, acc 2^-25 >= 2^-125 is normal and exact; if W M > acc 2^-25 (normal range), fl(W M) >= W M (1 - 2^-24) and the
 // inflation keeps T > acc: a passing test implies the bound.  A NaN T fails every comparison, and so does a NaN sum.  A weight or
@@ -298,7 +305,7 @@ __device__ __forceinline__ void region_pass(unsigned lds_base, const unsigned* _
             m &= m - 1u;                                                   // no-op when m is already 0
             const v4f e0 = tw[i0];
             const v4f e1 = tw[i1];
-            // samples in index order whichever body they take: the order of a texel's sum stays (region, sample index)
+            // samples in index order whichever body they take: the order of a texel's sum stays (region as visited, sample index)
             if (CERT && ((c >> i0) & 1u)) certain_sample<RS>(e0, lds_base, Pb, Pt, Pr, half_n, off, ar, ag, ab);
             else region_sample<RS, SUB, CLS>(e0, lds_base, Pb, Pt, Pr, half_n, off, ulo, uhi, vlo, vhi, ar, ag, ab, cnt);
             if (two) {
@@ -448,6 +455,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     // never absorb a word, and the test alone cost them 7 % (measured); without it their code is that of round 3
     constexpr bool ABS = RS == 66;
     const bool absorb_on = ABS && q.absorb;                              // workgroup-uniform
+    // see the header, 2e: the order pays through the absorbed words, so it is taken where they are compiled.  The 34^2 / 18^2 shapes keep
+    // index order and their bytes: there the reordered sums bought nothing and moved C4 mip 3 to 2.5e-5 from the direct kernel,
+    // past the 2e-5 of the every-texel cross-check (test_gpu_configs.py)
+    constexpr bool OWN_FIRST = ABS;
     unsigned* cmask = dmax + 1;                                          // [NW] samples proved to tap one region from the whole tile
     unsigned* wmax = cmask + q.NW;                                       // [NW] (absorb) largest weight (bit pattern) per mask word
     unsigned* rmax = wmax + q.NW;                                        // [NR] (absorb) largest staged R, G, B bit pattern per region
@@ -568,13 +579,15 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         // of the level); any[] is final after binning, so the skip needs none.  (A 64-bit mask of the visited regions kept across
         // the passes, or a ballot search for the next one, spills VGPRs at the 64-VGPR budget of the quarter-face shape.)
         __syncthreads();                                           // binning done
-        for (int r = 0; r < NR; ++r) {
+        for (int k = 0; k < NR; ++k) {
+            const int r = OWN_FIRST ? mc_region_visit(k, face * (G * G), G * G) : k;
             if (__builtin_amdgcn_readfirstlane((int)any[r]) == 0) continue;      // workgroup-uniform
             __syncthreads();                                       // readers of the previous region done
             visit(r);
         }
     } else {
-        for (int r = 0; r < NR; ++r) {
+        for (int k = 0; k < NR; ++k) {
+            const int r = OWN_FIRST ? mc_region_visit(k, face * (G * G), G * G) : k;
             __syncthreads();                                       // binning done / readers of the previous region done
             if (any[r] == 0u) continue;                            // workgroup-uniform
             visit(r);
@@ -867,6 +880,12 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         o.x = ar / p.divisor; o.y = ag / p.divisor; o.z = ab / p.divisor; o.w = p.alpha;
         p.out[((size_t)face * p.size + y) * p.size + x] = o;
     }
+}
+
+// the visiting order of the region loops, for host-side checks: the k-th region a tile of `face` visits at G regions per face edge
+extern "C" int pbrk_mc_region_order(int face, int G, int k) {
+    if (face < 0 || face > 5 || G < 1 || k < 0 || k >= 6 * G * G) return -1;
+    return mc_region_visit(k, face * (G * G), G * G);
 }
 
 static unsigned long long* g_reg_stats = nullptr;      // device counters, enabled by PBR_MC_STATS=1
