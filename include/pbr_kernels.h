@@ -145,6 +145,12 @@ int pbrk_mc_region_skip_stats(unsigned long long* out3);
 void pbrk_mc_set_absorb(int on);
 /* the region kernel's round-5 loop on the 66^2 region shapes (default on; the outputs are the same bit for bit either way) */
 void pbrk_mc_set_runs(int on);
+/* the region kernel's prologue (default 1: per-launch maxima from a preparation kernel, binning without run-time divisions, row-wise
+ * staging; 0: the prologue before it; tests and A-B runs): the outputs are the same bit for bit either way */
+void pbrk_mc_set_prologue(int lean);
+/* builds with PBR_MC_PHASE_STAMPS and PBR_MC_STATS=1: clocks of each workgroup's first lane, summed since the last reset, in {frames,
+ * clearing + binning, staging, region passes, reduction + store}; zeros in the product build */
+int pbrk_mc_region_phase_stats(unsigned long long* out5);
 /* the region kernel's visiting order: the k-th region (0 .. 6 G^2 - 1) a tile of `face` stages at G regions per face edge -- its own
  * face's regions first, then the others in index order; -1 for arguments out of range.  Host-side twin of the kernel's loop. */
 int pbrk_mc_region_order(int face, int G, int k);

@@ -35,6 +35,16 @@
 //      only on the faces whose index happens to be the lowest (C4 mip 2: 0.439 -> 0.478 of the wave-samples absorbed, the six
 //      faces 0.47-0.49 instead of 0.40-0.47; profiles/r06_order.md).
 //      Taken by the 66^2 shapes, where words are absorbed; the 34^2 / 18^2 shapes keep index order (OWN_FIRST in k_mc_region).
+//   2f. (round 7, prologue, LEAN) work every tile repeated for a result that is the same for the whole launch, and arithmetic the flags
+//      do not need.  (i) The two maxima of the absorbed-word test (2c) -- per mask word the largest weight, per region the largest staged
+//      R, G, B -- come from k_mc_prep, launched once on the same stream ahead of the region kernel, and are read with scalar loads; the
+//      per-sample LDS atomic of binning and the per-staging max / butterfly / atomic are gone, with their LDS arrays' clearing.  (ii) Binning
+//      knows G and RC at compile time (one region per face: r = f, no division; quarter faces: RC = 65) and takes the hardware
+//      reciprocal and square root inside the slack its bound already carries (region_bin).  (iii) The 66^2 shapes stage by rows -- a wave
+//      per row, a lane per column, all of a thread's loads ahead of its first LDS write.  The 34^2 / 18^2 shapes keep their staging (two
+//      sweeps with a constant divisor: under 1 % of their kernels).  Flags may differ from the earlier prologue's by the rounding of (ii);
+//      the samples accumulated, their order and the absorb decisions do not: same bytes (pbrk_mc_set_prologue(0) keeps the earlier
+//      prologue as the yardstick, tests/test_gpu_mc_prologue.py).
 // Each (texel, sample) pair is accumulated exactly once, in an order (66^2 shapes: own face's regions, then the other regions in
 // index order; else regions in index order; sample index inside a region) that depends on the level's shape and the texel's face
 // only, not on the tile: a row-sharded dispatch equals a full one bit for bit.
@@ -43,6 +53,7 @@
 #include "k_mc_internal.h"
 
 #include <stdlib.h>
+#include <mutex>
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 // The sample table is read-only for the whole launch: a pointer into the constant address space makes every wave-uniform
@@ -50,6 +61,8 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 // and falls back to 64-lane vector loads of one address).
 typedef const __attribute__((address_space(4))) v4f* ctab_t;
 typedef const __attribute__((address_space(3))) v4f* lds_v4f_p;
+// the launch's maxima (k_mc_prep): read-only for the region kernel, so wave-uniform reads of them are scalar loads as well
+typedef const __attribute__((address_space(4))) unsigned* cu32_t;
 
 // A 1024-thread workgroup owns a TILE x TILE block of output texels and 1024 / TILE^2 slices of the sample table:
 //   TILE 16 (the only instantiation): 256 texels x 4 slices (waves 4s .. 4s+3 own slice s).
@@ -66,10 +79,13 @@ struct RegArgs {
     int expect[REG_MAX_S];      // samples per slice
     int tile_y0;                // MFMA variant: first tile row (multiple of 16) covering a.y0
     int pole_row[2];            // faces +X / -X: tile row (relative to the dispatch's first row, clamped) nearest to the pole of the tangent frame
+    const unsigned* tabmax;     // lean prologue, absorb: [NW] largest weight bit pattern per mask word, then [NR] largest staged R, G, B bit pattern per
+                                // region (k_mc_prep, once per launch); null with the parent's prologue
     int absorb;                 // skip mask words whose samples are absorbed by every lane's sums (pbrk_mc_set_absorb; bit-identical)
     unsigned long long* stats;  // optional: [0] += healed wave-slices, [1] += all wave-slices, [2] += (region, sample) flags, [3] += samples per tile, [4] += regions visited,
                                 // [5] += proved samples (SUB), [6] += absorbed wave-words, [7] += their wave-samples, [8] += of those run through the
-                                // count-only body (a tile's region passes run 4 x [2] wave-samples in all)
+                                // count-only body (a tile's region passes run 4 x [2] wave-samples in all); PBR_MC_PHASE_STAMPS builds: [9..13] += clocks of
+                                // a workgroup's first lane in frames, clearing + binning, staging, region passes, reduction + store
 };
 
 // direction -> (sc, tc, ma) of face f: the table of v_cubesc / v_cubetc / v_cubema (gen_prefiltered_env_map.glsl:12-23)
@@ -254,11 +270,11 @@ __device__ __forceinline__ float absorb_threshold(float wmax, float m) {
 // One pass over the flagged samples of this wave's slice for the staged region.  Samples are taken two at a time so that the
 // second table entry's scalar load is in flight while the first sample computes.
 // cwords holds, per mask word, the samples proved to be in this region for the whole tile.  CERT: they run certain_sample; else
-// they are only credited in absorbed words.  cwords + NW: per mask word, the bit pattern of its largest weight.  rbits: the bit
+// they are only credited in absorbed words.  cwords + NW (LEAN: wmg, the launch's table): per mask word, the bit pattern of its largest weight.  rbits: the bit
 // pattern of the staged region's largest component, not below +inf's where absorbed words must not be skipped.  skc (stats only):
 // the workgroup's LDS counters {absorbed wave-words, their wave-samples, of those run through the count-only body}.
-template <int RS, bool SUB, int CLS, int REG_S, bool CERT>
-__device__ __forceinline__ void region_pass(unsigned lds_base, const unsigned* __restrict__ mwords, const unsigned* __restrict__ cwords,
+template <int RS, bool SUB, int CLS, int REG_S, bool CERT, bool LEAN>
+__device__ __forceinline__ void region_pass(unsigned lds_base, const unsigned* __restrict__ mwords, const unsigned* __restrict__ cwords, cu32_t wmg,
                                             unsigned rbits, unsigned* skc, int NW, int s,
                                             ctab_t tab, f3 Pb, f3 Pt, f3 Pr, float half_n, float off,
                                             float ulo, float uhi, float vlo, float vhi,
@@ -274,7 +290,7 @@ __device__ __forceinline__ void region_pass(unsigned lds_base, const unsigned* _
             cnt += 64u * (unsigned)__builtin_popcount(m & c);              // every lane takes every proved sample
         }
         ctab_t tw = tab + (w << 5);
-        const unsigned wb = (rbits < 0x7f800000u && m != 0u) ? (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[NW + w]) : 0x7f800000u;
+        const unsigned wb = (rbits < 0x7f800000u && m != 0u) ? (LEAN ? wmg[w] : (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[NW + w])) : 0x7f800000u;
         if (wb < 0x7f800000u) {
             const float T = absorb_threshold(__uint_as_float(wb), __uint_as_float(rbits));
             if (__builtin_amdgcn_ballot_w64(!(ar >= T && ag >= T && ab >= T)) == 0ull) {
@@ -322,8 +338,8 @@ __device__ __forceinline__ void region_pass(unsigned lds_base, const unsigned* _
 //   * CERT: the proved samples below the next tested one run as a run of certain_sample (no per-sample proved-bit test, no exec
 //     join), then the tested one, in index order;
 //   * tested samples use lane_sample (one ballot chain), and every loop issues the next table entry's load ahead of the body.
-template <int RS, bool SUB, int CLS, int REG_S, bool CERT>
-__device__ __forceinline__ void region_pass_runs(unsigned lds_base, const unsigned* __restrict__ mwords, const unsigned* __restrict__ cwords,
+template <int RS, bool SUB, int CLS, int REG_S, bool CERT, bool LEAN>
+__device__ __forceinline__ void region_pass_runs(unsigned lds_base, const unsigned* __restrict__ mwords, const unsigned* __restrict__ cwords, cu32_t wmg,
                                                  unsigned rbits, unsigned* skc, int NW, int s,
                                                  ctab_t tab, f3 Pb, f3 Pt, f3 Pr, float half_n, float off,
                                                  float ulo, float uhi, float vlo, float vhi,
@@ -337,7 +353,7 @@ __device__ __forceinline__ void region_pass_runs(unsigned lds_base, const unsign
         const unsigned m = (unsigned)__builtin_amdgcn_readfirstlane((int)mwords[w]);
         unsigned c = CERT ? (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[w]) : 0u;
         ctab_t tw = tab + (w << 5);
-        const unsigned wb = rbits < 0x7f800000u ? (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[NW + w]) : 0x7f800000u;
+        const unsigned wb = rbits < 0x7f800000u ? (LEAN ? wmg[w] : (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[NW + w])) : 0x7f800000u;
         if (wb < 0x7f800000u) {
             const float T = absorb_threshold(__uint_as_float(wb), __uint_as_float(rbits));
             if (__builtin_amdgcn_ballot_w64(!(ar >= T && ag >= T && ab >= T)) == 0ull) {
@@ -377,6 +393,12 @@ __device__ __forceinline__ void region_pass_runs(unsigned lds_base, const unsign
 // on the face (ma' - |sc'| >= (ma - |sc|) - sqrt(2) delta > 0), its tap bounds inside the face and inside one region's cells.  Such
 // a sample has exactly one region flag.  wmax (optional, [NW]): per mask word, the largest bit pattern of its samples' weights (for
 // weights >= +0 the largest weight; anything else orders above +inf).  The ntail words behind dmax are zeroed with the masks.
+// LEAN (header, 2f): G and RC are compile-time facts -- G1: one region per face, r = f and no division; else the quarter-face shape,
+// RC = 65 -- and the reach bound takes v_rcp_f32 / v_sqrt_f32 (1 ulp each) for the two divisions and two square roots.  That
+// moves mu, mv by less than 5e-7 relative (rl enters three times, the root once: 4 x 2^-23 and their roundings), inside the 1.0001
+// they carry, and uc, vc by less than 2^-22 (|sc / ma| + 1) half_n texel, under 1e-3 texel up to n = 1024, inside the 0.05: the flags
+// stay a superset of what any texel of the tile reaches, and "certain" is claimed under the same inequalities.
+template <bool LEAN, bool G1>
 __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsigned* dmax, int NR, int NW, int G, int RC, int n,
                                            f3 R, f3 T, f3 B, f3 Rc, f3 Tc, f3 Bc, ctab_t tab, int n_tab, int tid,
                                            unsigned* cmask = nullptr, unsigned* wmax = nullptr, int ntail = 0) {
@@ -401,7 +423,7 @@ __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsig
         const float Ly = fmaf(e.x, Bc.y, fmaf(e.y, Tc.y, e.z * Rc.y));
         const float Lz = fmaf(e.x, Bc.z, fmaf(e.y, Tc.z, e.z * Rc.z));
         const unsigned bit = 1u << (i & 31);
-        if (wmax) atomicMax(&wmax[i >> 5], __float_as_uint(e.w));
+        if (!LEAN && wmax) atomicMax(&wmax[i >> 5], __float_as_uint(e.w));
 #pragma unroll
         for (int f = 0; f < 6; ++f) {
             float sc, tc, ma;
@@ -415,11 +437,12 @@ __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsig
             if (mlo > 0.2f) {
                 // g(L) = sc / ma has |grad g| = sqrt(1 + g^2) / ma; along the segment L -> L' (ma >= ma - delta, |g| <= (|sc| + delta) /
                 // (ma - delta)) that is bounded, so |g(L') - g(L)| <= delta sqrt(1 + gmax^2) / (ma - delta); + 0.05 texel for rcp / fma rounding
-                const float rm = 1.0f / ma, rl = 1.0f / mlo;
+                const float rm = LEAN ? __builtin_amdgcn_rcpf(ma) : 1.0f / ma, rl = LEAN ? __builtin_amdgcn_rcpf(mlo) : 1.0f / mlo;
                 const float ru = sc * rm, rv = tc * rm;
                 const float gu = (fabsf(sc) + delta) * rl, gv = (fabsf(tc) + delta) * rl;
-                const float mu = delta * sqrtf(fmaf(gu, gu, 1.0f)) * rl * half_n * 1.0001f + 0.05f;
-                const float mv = delta * sqrtf(fmaf(gv, gv, 1.0f)) * rl * half_n * 1.0001f + 0.05f;
+                const float su = fmaf(gu, gu, 1.0f), sv = fmaf(gv, gv, 1.0f);
+                const float mu = delta * (LEAN ? __builtin_amdgcn_sqrtf(su) : sqrtf(su)) * rl * half_n * 1.0001f + 0.05f;
+                const float mv = delta * (LEAN ? __builtin_amdgcn_sqrtf(sv) : sqrtf(sv)) * rl * half_n * 1.0001f + 0.05f;
                 const float uc = fmaf(ru, half_n, off), vc = fmaf(rv, half_n, off);
                 const float ul = floorf(uc - mu), uh = floorf(uc + mu), vl = floorf(vc - mv), vh = floorf(vc + mv);
                 if (uh < 0.0f || ul > nf || vh < 0.0f || vl > nf) continue;      // cannot be on this face at all
@@ -427,7 +450,14 @@ __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsig
                 lo_v = (int)fmaxf(vl, 0.0f); hi_v = (int)fminf(vh, nf);
                 certain = cmask && ma - d2 > fabsf(sc) && ma - d2 > fabsf(tc) && ul >= 0.0f && uh <= nf && vl >= 0.0f && vh <= nf;
             }
-            const int gx0 = lo_u / RC, gx1 = hi_u / RC, gy0 = lo_v / RC, gy1 = hi_v / RC;
+            if (LEAN && G1) {                                              // RC = n + 1: every tap position of the face lies in region f
+                if (certain) atomicOr(&cmask[i >> 5], bit);
+                atomicOr(&masks[f * NW + (i >> 5)], bit);
+                any[f] = 1u;
+                continue;
+            }
+            const int rc = LEAN ? 65 : RC;
+            const int gx0 = lo_u / rc, gx1 = hi_u / rc, gy0 = lo_v / rc, gy1 = hi_v / rc;
             if (certain && gx0 == gx1 && gy0 == gy1) atomicOr(&cmask[i >> 5], bit);
             for (int gy = gy0; gy <= gy1; ++gy)
                 for (int gx = gx0; gx <= gx1; ++gx) {
@@ -439,8 +469,16 @@ __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsig
     }
 }
 
+// Clock of the calling lane (PBR_MC_PHASE_STAMPS builds only: where a tile's time goes; the product build has no stamp in it)
+#ifdef PBR_MC_PHASE_STAMPS
+#define STAMP() ((unsigned long long)__builtin_readcyclecounter())
+#else
+#define STAMP() 0ull
+#endif
+
 // RUNS (66^2 shapes only): the region loop visits the flagged regions only and runs region_pass_runs (round 5; cnt per lane)
-template <int RS, bool SUB, int TILE, bool RUNS = false>
+// LEAN: the prologue of header 2f (pbrk_mc_set_prologue); false: the one before it, kept as the yardstick
+template <int RS, bool SUB, int TILE, bool RUNS = false, bool LEAN = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_mc_region(const RegArgs q) {
     constexpr int REG_TX = TILE * TILE, REG_S = 1024 / REG_TX;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_r[];
@@ -460,8 +498,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     // past the 2e-5 of the every-texel cross-check (test_gpu_configs.py)
     constexpr bool OWN_FIRST = ABS;
     unsigned* cmask = dmax + 1;                                          // [NW] samples proved to tap one region from the whole tile
-    unsigned* wmax = cmask + q.NW;                                       // [NW] (absorb) largest weight (bit pattern) per mask word
-    unsigned* rmax = wmax + q.NW;                                        // [NR] (absorb) largest staged R, G, B bit pattern per region
+    unsigned* wmax = cmask + q.NW;                                       // [NW] (absorb, !LEAN) largest weight (bit pattern) per mask word
+    unsigned* rmax = wmax + q.NW;                                        // [NR] (absorb, !LEAN) largest staged R, G, B bit pattern per region
+    cu32_t wmg = (cu32_t)(unsigned long long)q.tabmax;                   // (absorb, LEAN) the same two for the whole launch: [NW], then [NR]
+    [[maybe_unused]] const unsigned long long st0 = STAMP();
     const McArgs& p = q.a;
     const int tid = threadIdx.x;
     const int s = __builtin_amdgcn_readfirstlane(tid / REG_TX);
@@ -510,8 +550,14 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 
     // ---- 1. binning ----
     if (ABS && tid < 4) skc[tid] = 0u;                                   // ordered by the barrier behind region_bin's clearing
-    region_bin(masks, any, dmax, NR, NW, G, RC, n, R, T, B, Rc, Tc, Bc, tab, p.n_tab, tid, (CERT || ABS) ? cmask : nullptr,
-               absorb_on ? wmax : nullptr, absorb_on ? 2 * NW + NR : ((CERT || ABS) ? NW : 0));
+    [[maybe_unused]] const unsigned long long st1 = STAMP();
+    region_bin<LEAN, !SUB>(masks, any, dmax, NR, NW, G, RC, n, R, T, B, Rc, Tc, Bc, tab, p.n_tab, tid, (CERT || ABS) ? cmask : nullptr,
+                           (absorb_on && !LEAN) ? wmax : nullptr, (absorb_on && !LEAN) ? 2 * NW + NR : ((CERT || ABS) ? NW : 0));
+    [[maybe_unused]] unsigned long long st_stage = 0ull;
+#ifdef PBR_MC_PHASE_STAMPS
+    __syncthreads();                                               // the wait for the slowest thread's binning is charged to binning
+#endif
+    [[maybe_unused]] const unsigned long long st2 = STAMP();       // the diagnostics below are charged to no phase
 
     // ---- 2. region passes ----
     float ar = 0.0f, ag = 0.0f, ab = 0.0f;
@@ -530,28 +576,63 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         const int ox = gx * RC, oy = gy * RC;
         const int rcx = min(RC, n + 1 - ox), rcy = min(RC, n + 1 - oy);      // cells of this region; texels: one more
         const float4* __restrict__ fsrc = p.src + ((size_t)f * nb + oy) * nb + ox;
-        unsigned vmax = 0u;                                        // largest R, G, B bit pattern: any negative / inf / NaN orders above +inf
-        for (int k = tid; k < RS * RS; k += 1024) {
-            const int ry = k / RS, rx = k - ry * RS;
-            if (rx <= rcx && ry <= rcy) {
-                const float4 v = fsrc[ry * nb + rx];
-                region[k] = v;
-                if (ABS) vmax = max(vmax, max(__float_as_uint(v.x), max(__float_as_uint(v.y), __float_as_uint(v.z))));
+        const unsigned long long sta = STAMP();
+        unsigned rbits = 0x7f800000u;                              // wave-uniform; the pattern of +inf (never below itself) when absorbed words must not be skipped
+        if (LEAN && RS == 66) {
+            // wave w takes rows w, w + 16, ..: the row is wave-uniform, a lane's column is its index -- no division per texel; columns 64
+            // and 65 go to the first 132 threads, one texel each.  Addresses are clamped into the region, so every load is
+            // unconditional and all of a thread's loads are issued before its first LDS write; the guards are on the writes.
+            // The thread index is formed again per staging (opaque to the optimiser): hoisted out of the region loop, the lane's source and
+            // LDS offsets stay alive across the passes and spill at the 64-VGPR budget.
+            int tid_s = tid;
+            asm volatile("" : "+v"(tid_s));
+            const int wv = __builtin_amdgcn_readfirstlane(tid_s >> 6), ln = tid_s & 63;
+            // row bases are wave-uniform (scalar); a lane adds its clamped column as a 32-bit byte offset
+            const unsigned cx = (unsigned)min(ln, rcx) << 4;
+            const char* const base = (const char*)fsrc;
+            const unsigned rowb = (unsigned)nb << 4;
+            const float4 v0 = *(const float4*)(base + (size_t)((unsigned)min(wv, rcy) * rowb) + cx);
+            const float4 v1 = *(const float4*)(base + (size_t)((unsigned)min(wv + 16, rcy) * rowb) + cx);
+            const float4 v2 = *(const float4*)(base + (size_t)((unsigned)min(wv + 32, rcy) * rowb) + cx);
+            const float4 v3 = *(const float4*)(base + (size_t)((unsigned)min(wv + 48, rcy) * rowb) + cx);
+            const float4 v4 = *(const float4*)(base + (size_t)((unsigned)min(wv + 64, rcy) * rowb) + cx);
+            const int ey = tid_s >> 1, ex = 64 + (tid_s & 1);      // tid < 132: rows 0 .. 65
+            const float4 ve = *(const float4*)(base + (unsigned)(min(ey, rcy) * nb + min(ex, rcx)) * 16u);
+            if (ln <= rcx) {
+                float4* const dst = region + wv * RS + ln;
+                if (wv <= rcy) dst[0] = v0;
+                if (wv + 16 <= rcy) dst[16 * RS] = v1;
+                if (wv + 32 <= rcy) dst[32 * RS] = v2;
+                if (wv + 48 <= rcy) dst[48 * RS] = v3;
+                if (wv + 64 <= rcy) dst[64 * RS] = v4;
             }
+            if (tid_s < 2 * RS && ex <= rcx && ey <= rcy) region[ey * RS + ex] = ve;
+            if (absorb_on) rbits = wmg[NW + r];                    // scalar load, in flight across the barrier
+            __syncthreads();
+        } else {
+            unsigned vmax = 0u;                                        // largest R, G, B bit pattern: any negative / inf / NaN orders above +inf
+            for (int k = tid; k < RS * RS; k += 1024) {
+                const int ry = k / RS, rx = k - ry * RS;
+                if (rx <= rcx && ry <= rcy) {
+                    const float4 v = fsrc[ry * nb + rx];
+                    region[k] = v;
+                    if (ABS && !LEAN) vmax = max(vmax, max(__float_as_uint(v.x), max(__float_as_uint(v.y), __float_as_uint(v.z))));
+                }
+            }
+            if (absorb_on && !LEAN) {                                  // wave maximum, one LDS atomic per wave, ahead of the barrier
+                // xor butterflies inside each 32-lane half (ds_swizzle: the pattern is an immediate, no lane-address registers), halves via readlane
+                vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (16 << 10) | 0x1f));
+                vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (8 << 10) | 0x1f));
+                vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (4 << 10) | 0x1f));
+                vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (2 << 10) | 0x1f));
+                vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (1 << 10) | 0x1f));
+                const unsigned wv = max((unsigned)__builtin_amdgcn_readlane((int)vmax, 0), (unsigned)__builtin_amdgcn_readlane((int)vmax, 32));
+                if ((tid & 63) == 0) atomicMax(&rmax[r], wv);
+            }
+            __syncthreads();
+            if (absorb_on) rbits = LEAN ? wmg[NW + r] : (unsigned)__builtin_amdgcn_readfirstlane((int)rmax[r]);
         }
-        if (absorb_on) {                                           // wave maximum, one LDS atomic per wave, ahead of the barrier
-            // xor butterflies inside each 32-lane half (ds_swizzle: the pattern is an immediate, no lane-address registers), halves via readlane
-            vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (16 << 10) | 0x1f));
-            vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (8 << 10) | 0x1f));
-            vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (4 << 10) | 0x1f));
-            vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (2 << 10) | 0x1f));
-            vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (1 << 10) | 0x1f));
-            const unsigned wv = max((unsigned)__builtin_amdgcn_readlane((int)vmax, 0), (unsigned)__builtin_amdgcn_readlane((int)vmax, 32));
-            if ((tid & 63) == 0) atomicMax(&rmax[r], wv);
-        }
-        __syncthreads();
-        // wave-uniform; the pattern of +inf (never below itself) when absorbed words must not be skipped
-        const unsigned rbits = absorb_on ? (unsigned)__builtin_amdgcn_readfirstlane((int)rmax[r]) : 0x7f800000u;
+        const unsigned long long stb = STAMP();
         // signed permutation of the frame for this face: rows give (sc, tc, ma) directly
         f3 Pb, Pt, Pr;
         face_coords(f, B.x, B.y, B.z, Pb.x, Pb.y, Pb.z);
@@ -562,18 +643,18 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         unsigned* const sc = (ABS && q.stats) ? skc : nullptr;
         if (RUNS) {
             switch (f >> 1) {
-            case 0: region_pass_runs<RS, SUB, 0, REG_S, CERT>(pass_base, mw, cmask, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
-            case 1: region_pass_runs<RS, SUB, 1, REG_S, CERT>(pass_base, mw, cmask, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
-            default: region_pass_runs<RS, SUB, 2, REG_S, CERT>(pass_base, mw, cmask, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+            case 0: region_pass_runs<RS, SUB, 0, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+            case 1: region_pass_runs<RS, SUB, 1, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+            default: region_pass_runs<RS, SUB, 2, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
             }
-            return;
+        } else switch (f >> 1) {
+        case 0: region_pass<RS, SUB, 0, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+        case 1: region_pass<RS, SUB, 1, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+        default: region_pass<RS, SUB, 2, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
         }
-        switch (f >> 1) {
-        case 0: region_pass<RS, SUB, 0, REG_S, CERT>(pass_base, mw, cmask, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
-        case 1: region_pass<RS, SUB, 1, REG_S, CERT>(pass_base, mw, cmask, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
-        default: region_pass<RS, SUB, 2, REG_S, CERT>(pass_base, mw, cmask, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
-        }
+        st_stage += stb - sta;
     };
+    [[maybe_unused]] const unsigned long long st2b = STAMP();
     if (RUNS) {
         // the barrier ahead of each staging runs for the flagged regions only (once per visited region instead of once per region
         // of the level); any[] is final after binning, so the skip needs none.  (A 64-bit mask of the visited regions kept across
@@ -598,6 +679,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     // cnt is a wave total (scalar): no (texel, sample) pair can be taken twice -- the in-region tests partition the tap positions
     // exactly -- so the total is right exactly when no lane missed a sample
     // RUNS: cnt per lane; a wave recomputes when any lane's count is off (a stronger test than the total)
+    [[maybe_unused]] const unsigned long long st3 = STAMP();
     const bool healed = RUNS ? __builtin_amdgcn_ballot_w64(cnt != (unsigned)q.expect[s]) != 0ull : cnt != 64u * (unsigned)q.expect[s];
     if (healed) {
         __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.src, 0, (int)p.src_bytes, 0x00020000);
@@ -650,6 +732,12 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         o.x = red[t_o * 3 + 0] / p.divisor; o.y = red[t_o * 3 + 1] / p.divisor; o.z = red[t_o * 3 + 2] / p.divisor; o.w = p.alpha;
         p.out[((size_t)face * p.size + y_o) * p.size + x_o] = o;
     }
+#ifdef PBR_MC_PHASE_STAMPS
+    if (q.stats && tid == 0) {                                     // [12]: the region loop less its stagings (passes, barriers, the skipped regions' tests)
+        atomicAdd(&q.stats[9], st1 - st0); atomicAdd(&q.stats[10], st2 - st1); atomicAdd(&q.stats[11], st_stage);
+        atomicAdd(&q.stats[12], (st3 - st2b) - st_stage); atomicAdd(&q.stats[13], STAMP() - st3);
+    }
+#endif
 }
 
 // ==========================================================================================
@@ -787,7 +875,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         const f3 Bc = cross3(Tc, Rc);
         for (int k = tid; k < NR * NW + NR + 1; k += 1024) masks[k] = 0u;
         __syncthreads();
-        region_bin(masks, any, dmax, NR, NW, G, RC, n, R, T, B, Rc, Tc, Bc, tab, p.n_tab, tid);
+        region_bin<false, false>(masks, any, dmax, NR, NW, G, RC, n, R, T, B, Rc, Tc, Bc, tab, p.n_tab, tid);
         Fg = g == 0 ? R : (g == 1 ? T : (g == 2 ? B : mk3(0.0f, 0.0f, 0.0f)));
     }
     const float bw = g == 3 ? 1.0f : 0.0f;
@@ -910,11 +998,84 @@ extern "C" int pbrk_mc_region_flag_stats(unsigned long long* out3) {
     return hipMemcpy(out3, g_reg_stats + 2, 24, hipMemcpyDeviceToHost) == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
 }
 
-template <int RS, bool SUB, int TILE, bool RUNS = false>
+extern "C" int pbrk_mc_region_phase_stats(unsigned long long* out5) {      // PBR_MC_PHASE_STAMPS builds; zeros otherwise (RegArgs::stats [9..13])
+    if (!g_reg_stats || !out5) return PBRK_E_ARG;
+    return hipMemcpy(out5, g_reg_stats + 9, 40, hipMemcpyDeviceToHost) == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
+}
+
+template <int RS, bool SUB, int TILE, bool RUNS = false, bool LEAN = false>
 static void launch_region_t(const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
     static bool attr_set = false;
-    if (!attr_set) { (void)hipFuncSetAttribute((const void*)k_mc_region<RS, SUB, TILE, RUNS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
-    hipLaunchKernelGGL((k_mc_region<RS, SUB, TILE, RUNS>), dim3(grid), dim3(1024), lds, st, q);
+    if (!attr_set) { (void)hipFuncSetAttribute((const void*)k_mc_region<RS, SUB, TILE, RUNS, LEAN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
+    hipLaunchKernelGGL((k_mc_region<RS, SUB, TILE, RUNS, LEAN>), dim3(grid), dim3(1024), lds, st, q);
+}
+
+// ---- the launch's maxima (header, 2f) ----
+// out[0 .. NW): per mask word, the largest bit pattern of its samples' weights; out[NW .. NW + NR): per region, the largest bit
+// pattern of the R, G, B of exactly the texels the region kernel stages for it (rx <= rcx, ry <= rcy: apron included).  Compared as
+// unsigned integers, as the lemma at absorb_threshold wants: a negative, -0, inf or NaN orders at or above +inf's pattern.
+// Block b < NR reduces region b; the blocks behind take 256 words each, one per thread.
+__global__ __launch_bounds__(256) void k_mc_prep(const float4* __restrict__ src, int n, int G, int RC, int NR,
+                                                 const float4* __restrict__ tab, int n_tab, int NW, unsigned* __restrict__ out) {
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= NR) {
+        const int w = ((int)blockIdx.x - NR) * 256 + tid;
+        if (w >= NW) return;
+        unsigned m = 0u;
+        for (int i = w << 5; i < min((w << 5) + 32, n_tab); ++i) m = max(m, __float_as_uint(tab[i].w));
+        out[w] = m;
+        return;
+    }
+    __shared__ unsigned red;
+    if (tid == 0) red = 0u;
+    __syncthreads();
+    const int r = (int)blockIdx.x, nb = n + 2;
+    const int f = r / (G * G), gy = (r / G) % G, gx = r % G;
+    const int ox = gx * RC, oy = gy * RC;
+    const int cols = min(RC, n + 1 - ox) + 1, rows = min(RC, n + 1 - oy) + 1;
+    const float4* __restrict__ fsrc = src + ((size_t)f * nb + oy) * nb + ox;
+    unsigned m = 0u;
+    for (int k = tid; k < rows * cols; k += 256) {
+        const int ry = k / cols, rx = k - ry * cols;
+        const float4 v = fsrc[ry * nb + rx];
+        m = max(m, max(__float_as_uint(v.x), max(__float_as_uint(v.y), __float_as_uint(v.z))));
+    }
+    atomicMax(&red, m);
+    __syncthreads();
+    if (tid == 0) out[NW + r] = red;
+}
+
+// Scratch for those tables: a ring of slots in device memory, allocated once per device.  A slot is written by k_mc_prep and read
+// by the region kernel behind it on the same stream; an event recorded behind that reader is waited for, in-stream, by the next
+// launch that takes the slot, so launches in flight on different streams (the tile streams of GPU_GraphSubmit) never share one.
+#define PREP_SLOTS 32
+#define PREP_SLOT_WORDS 4096                                    // NW <= 256; NR (NW + 1) words of masks fit 80 KB of LDS behind the region
+#define PREP_MAX_DEVICES 16
+struct PrepRing { unsigned* dev; hipEvent_t ev[PREP_SLOTS]; bool used[PREP_SLOTS]; unsigned next; };
+static PrepRing g_prep[PREP_MAX_DEVICES];
+static std::mutex g_prep_lock;
+
+// The slot for one launch on `st` (its previous reader waited for), or null: no device memory, or `st` is being captured into a
+// graph -- a replayed graph keeps the slot it was recorded with, and nothing would order its replays against later launches.
+static unsigned* prep_acquire(hipStream_t st, int* slot_out) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (cs != hipStreamCaptureStatusNone) return nullptr;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PREP_MAX_DEVICES) return nullptr;
+    PrepRing& R = g_prep[dev];
+    if (!R.dev) {
+        if (hipMalloc(&R.dev, (size_t)PREP_SLOTS * PREP_SLOT_WORDS * 4) != hipSuccess) { (void)hipGetLastError(); R.dev = nullptr; return nullptr; }
+        for (int i = 0; i < PREP_SLOTS; ++i) {
+            R.used[i] = false;
+            if (hipEventCreateWithFlags(&R.ev[i], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(R.dev); R.dev = nullptr; return nullptr; }
+        }
+        R.next = 0;
+    }
+    const int slot = (int)(R.next++ % PREP_SLOTS);
+    if (R.used[slot] && hipStreamWaitEvent(st, R.ev[slot], 0) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    *slot_out = slot;
+    return R.dev + (size_t)slot * PREP_SLOT_WORDS;
 }
 
 template <int RS, bool SUB>
@@ -933,6 +1094,17 @@ extern "C" void pbrk_mc_set_absorb(int on) { g_mc_absorb = on ? 1 : 0; }
 // The round-5 loop of the 66^2 shapes (k_mc_region RUNS; tests / A-B runs; the outputs are the same bit for bit either way)
 static int g_mc_runs = 1;
 extern "C" void pbrk_mc_set_runs(int on) { g_mc_runs = on ? 1 : 0; }
+// The prologue of header 2f (k_mc_region LEAN; tests / A-B runs; 0: the prologue before it; the outputs are the same bit for bit either way)
+static int g_mc_lean = 1;
+extern "C" void pbrk_mc_set_prologue(int lean) { g_mc_lean = lean ? 1 : 0; }
+
+template <bool LEAN>
+static void launch_shape(int RS, const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
+    if (RS == 18) launch_region_t<18, false, 16, false, LEAN>(q, grid, lds, st);
+    else if (RS == 34) launch_region_t<34, false, 16, false, LEAN>(q, grid, lds, st);
+    else if (q.G == 1) { if (g_mc_runs) launch_region_t<66, false, 16, true, LEAN>(q, grid, lds, st); else launch_region_t<66, false, 16, false, LEAN>(q, grid, lds, st); }
+    else { if (g_mc_runs) launch_region_t<66, true, 16, true, LEAN>(q, grid, lds, st); else launch_region_t<66, true, 16, false, LEAN>(q, grid, lds, st); }
+}
 
 bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
     static int stats_on = -1;
@@ -998,9 +1170,25 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
         }
     }
     const unsigned grid = (unsigned)(q.a.tiles_per_face * nfaces);
-    if (RS == 18) launch_region_t<18, false, 16>(q, grid, lds, st);
-    else if (RS == 34) launch_region_t<34, false, 16>(q, grid, lds, st);
-    else if (q.G == 1) { if (g_mc_runs) launch_region_t<66, false, 16, true>(q, grid, lds, st); else launch_region_t<66, false, 16>(q, grid, lds, st); }
-    else { if (g_mc_runs) launch_region_t<66, true, 16, true>(q, grid, lds, st); else launch_region_t<66, true, 16>(q, grid, lds, st); }
+    // Lean prologue: the maxima of the absorbed-word test come from k_mc_prep, once per launch, instead of from every tile.  Without
+    // a scratch slot (see prep_acquire) the launch takes the prologue that builds them itself: the same bytes.
+    bool lean = g_mc_lean != 0;
+    q.tabmax = nullptr;
+    if (lean && q.absorb) {
+        std::lock_guard<std::mutex> hold(g_prep_lock);
+        int slot = -1;
+        unsigned* scratch = q.NW + q.NR <= PREP_SLOT_WORDS ? prep_acquire(st, &slot) : nullptr;
+        if (!scratch) lean = false;
+        else {
+            int dev = 0; (void)hipGetDevice(&dev);
+            q.tabmax = scratch;
+            hipLaunchKernelGGL(k_mc_prep, dim3((unsigned)(q.NR + (q.NW + 255) / 256)), dim3(256), 0, st, a.src, a.n_src, q.G, q.RC, q.NR, a.tab, a.n_tab, q.NW, scratch);
+            launch_shape<true>(RS, q, grid, lds, st);
+            if (hipEventRecord(g_prep[dev].ev[slot], st) == hipSuccess) g_prep[dev].used[slot] = true;
+            return true;
+        }
+    }
+    if (lean) launch_shape<true>(RS, q, grid, lds, st);
+    else launch_shape<false>(RS, q, grid, lds, st);
     return true;
 }
