@@ -230,6 +230,32 @@ GPU_DescriptorSet* PBR_SunDepthDescriptorSet(PBR_SunDepthPass* pass);
 /* render.cpp:991 + 995-1020: copies globals (if not NULL) into the mapped buffer, clears the map to 1 and draws every part */
 void PBR_RecordSunDepthPass(PBR_SunDepthPass* pass, GPU_Graph* graph, const PBR_Mesh* mesh, const PBR_Globals* globals);
 
+/* ---- geometry pass (K13): render.cpp:190-233 (pipelines), :680-708 (targets, render passes), :993 + :1076-1115 (per-frame clear
+ *      and one indexed draw per part, then the skybox with its own buffers); a part's material = its four RGBA8UN textures ---- */
+typedef struct PBR_Material PBR_Material;
+/* four size x size RGBA8 level-0 images (base colour, normal, ORM, emissive); size a power of two; mips are generated */
+PBR_Material* PBR_MakeMaterial(uint32_t size, const void* base_color, const void* normal, const void* orm, const void* emissive);
+void PBR_DestroyMaterial(PBR_Material* material);
+GPU_Texture* PBR_MaterialTexture(PBR_Material* material, uint32_t which);    /* 0 .. 3 in the order above */
+void PBR_MeshSetPartMaterial(PBR_Mesh* mesh, uint32_t part, PBR_Material* material);   /* the material is not owned by the mesh */
+
+typedef struct PBR_GeometryPass PBR_GeometryPass;
+/* the two render passes and pipelines of the reference: pass i writes gb's four colour planes, PBR_PostVelocity(pp, i) and gb->depth */
+PBR_GeometryPass* PBR_MakeGeometryPass(const PBR_GBuffer* gb, PBR_PostProcess* pp, uint32_t width, uint32_t height);
+void PBR_DestroyGeometryPass(PBR_GeometryPass* pass);
+GPU_Buffer* PBR_GeometryGlobalsBuffer(PBR_GeometryPass* pass);              /* persistently mapped PBR_Globals */
+GPU_GraphicsPipeline* PBR_GeometryPipeline(PBR_GeometryPass* pass, uint32_t frame_idx_mod2);
+GPU_RenderPass* PBR_GeometryRenderPass(PBR_GeometryPass* pass, uint32_t frame_idx_mod2);
+GPU_PipelineLayout* PBR_GeometryLayout(PBR_GeometryPass* pass);             /* GLOBALS, TEX0, TEX1, TEX_ORM, TEX_EMISSIVE, SAMPLER_LINEAR_WRAP */
+/* the set a part with this material draws with; created on first use and kept until the pass is destroyed, so destroy the pass
+ * before any material it has seen */
+GPU_DescriptorSet* PBR_GeometryDescriptorSet(PBR_GeometryPass* pass, PBR_Material* material);
+/* render.cpp:991, :993, :1076-1115: copies globals (if not NULL), clears the depth, draws every part of `mesh` and then of `skybox`
+ * (may be NULL) with its own buffers.  A part that has no material (PBR_MeshSetPartMaterial) is not drawn.  jitter / jitter_prev: two
+ * floats each (NULL = 0, 0).  Materials must outlive the pass: it keeps one descriptor set per material it has drawn with. */
+void PBR_RecordGeometryPass(PBR_GeometryPass* pass, GPU_Graph* graph, const PBR_Mesh* mesh, const PBR_Mesh* skybox, const PBR_Globals* globals,
+                            const float* jitter, const float* jitter_prev, uint32_t frame_idx);
+
 #ifdef __cplusplus
 }
 #endif

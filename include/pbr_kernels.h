@@ -278,6 +278,35 @@ size_t pbrk_raster_scratch_bytes(uint32_t tri_count, int width, int height);
 int pbrk_raster_setup(const PbrkRasterArgs* args, void* stream);    /* K12.setup: clear bins, transform + bin, scan, fill */
 int pbrk_raster_tiles(const PbrkRasterArgs* args, void* stream);    /* K12.tiles: per-tile depth minimum, one store per pixel */
 
+/* ---- K13: the geometry pass (geometry_pass.glsl, render.cpp:1076-1115) as a compute rasteriser on K12's structure: setup (one
+ *      thread per triangle: vertex stage, clip, fan, snap, bin), then one workgroup per 32 x 32 tile (a 2 x 2 quad per lane) that
+ *      first finds each pixel's winner (depth, then triangle number; the alpha test before the depth write) and then shades it once.
+ *      Contract: DESIGN.md K13.  Vertices are the 44-B Vertex of render.h:31-36; every draw names its own buffers and textures. ---- */
+typedef struct PbrkGeoTex { const void* texels; int width, height, levels, pad; } PbrkGeoTex;    /* RGBA8UN, levels back to back */
+typedef struct PbrkGeoDraw {
+    float m[16], m_old[16];       /* clip_space_from_world, old_clip_space_from_world: column-major, as snapshotted at submit */
+    float jitter[2], jitter_prev[2];
+    PbrkGeoTex tex[4];            /* TEX0 (base colour), TEX1 (normal), TEX_ORM, TEX_EMISSIVE */
+    const void* vertices; const uint32_t* indices;
+    uint32_t vertex_count, first_tri, first_index, vertex_offset;
+} PbrkGeoDraw;
+typedef struct PbrkGeometryArgs {
+    const PbrkGeoDraw* draws;     /* device memory, first_tri ascending, every draw at least one triangle */
+    uint32_t draw_count, tri_count;
+    void* color[4];               /* base colour, normal, ORM, emissive: RGBA8UN, width x height, tight rows */
+    void* velocity;               /* RG16F */
+    float* depth;                 /* D32F */
+    int width, height;            /* at most 16384 each */
+    void* scratch;
+    unsigned long long* rejected;
+} PbrkGeometryArgs;
+size_t pbrk_geometry_scratch_bytes(uint32_t tri_count, int width, int height);
+int pbrk_geometry_setup(const PbrkGeometryArgs* args, void* stream);
+int pbrk_geometry_tiles(const PbrkGeometryArgs* args, void* stream);
+/* mip chain of a 2-D RGBA8UN texture with power-of-two extents (levels back to back): each level is the 2 x 2 box of the one above,
+ * averaged in fp32 on the decoded values, stored as rint(255 x) */
+int pbrk_mip_chain_rgba8(void* pyramid, int width, int height, int levels, void* stream);
+
 /* ---- diagnostics: the device samplers of the widened passes evaluated at caller-supplied coordinates, so that tests can feed them
  *      NaN / inf / 1e30 / boundary values directly (a ray that has marched far away must never become an out-of-bounds read).
  *      which: 0 = LIGHTGRID (RGBA16F n^3, coords xyz), 1 = sampler2DShadow (R32F w x h, coords u, v, ref; result in out[0]),

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Renders one viewable frame through the whole path (synthetic HDR cube -> IBL precompute -> metal-rough spheres G-buffer ->
-shade -> TAA x3 -> bloom -> tone map) and writes it as a PNG:   python3 tools/render_frame.py out.png [width height [live]]
+shade -> TAA x3 -> bloom -> tone map) and writes it as a PNG:   python3 tools/render_frame.py out.png [width height [live | raster]]
+With `raster` the G-buffer is not synthetic: the geometry pass (K13) rasterises synth_mesh_temple with procedural materials each frame.
 With `live` the lighting pass is the reference's complete live shader (shafts, sun shadows, voxel GI) inside the reference's
 frame loop: light-grid sweep -> lighting (reading last frame's bloom_downscale_rt) -> TAA -> bloom -> final, eight frames."""
 import ctypes as C
@@ -41,15 +42,26 @@ def main():
     L.PBR_GenPrefilteredEnvMap(env_tex, maps.tex_specular_env_map, 16)
     L.PBR_GenBRDFIntegrationMap(maps.brdf_lut)
     live = len(sys.argv) > 4 and sys.argv[4] == "live"
+    raster = len(sys.argv) > 4 and sys.argv[4] == "raster"
     if live:
         gbd, grid, _, sun = synth.synth_gi_scene(W, H)
+    elif raster:
+        gbd = {"cam_pos": (0.0, -30.0, 6.0)}
     else:
         gbd = synth.synth_gbuffer_spheres(W, H)
     gb = pbrhip.PBR_GBuffer()
     L.PBR_MakeGBuffer(C.byref(gb), W, H, pbrhip.Format_RGBA16F)
-    for name, arr in (("base_color", gbd["base"]), ("normal", gbd["normal"]), ("orm", gbd["orm"]), ("emissive", gbd["emissive"]), ("depth", gbd["depth"])):
-        pbrhip.upload_mip(getattr(gb, name), 0, arr)
+    if not raster:
+        for name, arr in (("base_color", gbd["base"]), ("normal", gbd["normal"]), ("orm", gbd["orm"]), ("emissive", gbd["emissive"]), ("depth", gbd["depth"])):
+            pbrhip.upload_mip(getattr(gb, name), 0, arr)
     pp = L.PBR_MakePostProcess(C.byref(gb), W, H, pbrhip.Format_RGBA8UN)
+    if raster:
+        verts, idx, parts, part_mat = synth.synth_mesh_temple(200000, n_materials=8)
+        materials = [pbrhip.make_material(m) for m in synth.synth_materials(8, 128)]
+        mesh = pbrhip.make_mesh(verts, idx, parts)
+        for k, m in enumerate(part_mat):
+            L.PBR_MeshSetPartMaterial(mesh, k, materials[m])
+        gp = L.PBR_MakeGeometryPass(C.byref(gb), pp, W, H)
     lg = None
     if live:
         lg = L.PBR_MakeLightgrid(grid.shape[0])
@@ -66,6 +78,10 @@ def main():
         if live:
             glob.lightgrid_scale = 1.0 / synth.GI_SCENE_EXTENT
             L.PBR_RecordLightgridSweep(lg, g)                                   # render.cpp:1061-1072
+        if raster:                                                              # render.cpp:993, 1076-1115; a still camera
+            for k in range(16):
+                glob.old_clip_space_from_world[k] = glob.clip_space_from_world[k]
+            L.PBR_RecordGeometryPass(gp, g, mesh, None, C.byref(glob), None, None, frame)
         L.PBR_RecordLightingPass(lp, g, C.byref(glob), 0, 0)
         L.PBR_RecordTaaResolve(pp, g, frame); L.PBR_RecordBloom(pp, g, frame); L.PBR_RecordFinalPostProcessBloom(pp, g, frame)
         L.GPU_GraphSubmit(g); L.GPU_GraphWait(g)

@@ -48,7 +48,7 @@ static void gpu_fail(const char* fmt, ...) {
 // object model
 // ------------------------------------------------------------------------------------------
 enum BindKind { Bind_Texture, Bind_Sampler, Bind_Buffer, Bind_StorageImage };
-enum KernelId { Kernel_None = 0, Kernel_BrdfLut, Kernel_Irradiance, Kernel_Prefilter, Kernel_Lighting, Kernel_LightgridSweep, Kernel_TaaResolve, Kernel_FinalPost, Kernel_BloomDown, Kernel_BloomUp, Kernel_SunDepth };
+enum KernelId { Kernel_None = 0, Kernel_BrdfLut, Kernel_Irradiance, Kernel_Prefilter, Kernel_Lighting, Kernel_LightgridSweep, Kernel_TaaResolve, Kernel_FinalPost, Kernel_BloomDown, Kernel_BloomUp, Kernel_SunDepth, Kernel_Geometry };
 
 struct GPU_Sampler { GPU_SamplerDesc desc; bool shared; };
 
@@ -90,7 +90,8 @@ struct GPU_GraphicsPipeline { GPU_PipelineLayout* layout; GPU_RenderPass* pass; 
 
 enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster };
 // one GPU_OpDrawIndexed of the sun depth pass: job triangles [first_tri, first_tri + index_count / 3), matrix from the set's GLOBALS
-struct RasterDraw { GPU_DescriptorSet* set; uint32_t first_tri, first_index, vertex_offset; };
+// (K13, the geometry pass: also the buffers bound at the draw and the pushed jitter pair -- the skybox rebinds both inside the pass)
+struct RasterDraw { GPU_DescriptorSet* set; uint32_t first_tri, first_index, vertex_offset; BufferImpl* vb = nullptr; BufferImpl* ib = nullptr; float push[4] = {0, 0, 0, 0}; };
 struct Op {
     OpKind kind;
     std::string name;
@@ -122,7 +123,7 @@ struct Op {
 };
 struct DrawParams { GPU_GraphicsPipeline* pipeline; GPU_DescriptorSet* set; };
 // per raster job of a graph, kept across submissions: bins / records (device), the draw table (device + pinned staging)
-struct RasterScratch { void* dev = nullptr; size_t dev_bytes = 0; void* draws_dev = nullptr; PbrkRasterDraw* draws_host = nullptr; size_t draws_cap = 0; };
+struct RasterScratch { void* dev = nullptr; size_t dev_bytes = 0; void* draws_dev = nullptr; void* draws_host = nullptr; size_t draws_cap = 0; /* bytes */ };
 struct GPU_Graph {
     hipStream_t stream = nullptr;
     hipStream_t cur = nullptr;                     // stream the op being executed launches on (stream, or a side stream)
@@ -198,6 +199,7 @@ static const char kTokenFinal[] = "HIPK9:final_post_process";
 static const char kTokenBloomDown[] = "HIPK10:bloom_downsample";
 static const char kTokenBloomUp[] = "HIPK11:bloom_upsample";
 static const char kTokenSun[] = "HIPK12:sun_depth_pass";
+static const char kTokenGeometry[] = "HIPK13:geometry_pass";
 
 // ------------------------------------------------------------------------------------------
 // formats  [gpu.h:99-144]
@@ -408,6 +410,11 @@ GPU_API uint64_t GPUX_TextureMipBytes(const GPU_Texture* t, uint32_t mip) {
     return bw * bh * d * fi.block_size * t->layer_count;
 }
 
+// 2-D RGBA8UN with power-of-two extents: the material textures of the geometry pass (K13)
+static bool is_rgba8_pow2(const TextureImpl* t) {
+    const uint32_t w = t->base.width, h = t->base.height;
+    return t->base.format == GPU_Format_RGBA8UN && t->base.layer_count == 1 && t->base.depth == 1 && (w & (w - 1)) == 0 && (h & (h - 1)) == 0;
+}
 static bool is_f4_cube(const TextureImpl* t) {
     return t->base.format == GPU_Format_RGBA32F && (t->base.flags & GPU_TextureFlag_Cubemap) && t->base.width == t->base.height && t->base.depth == 1;
 }
@@ -443,8 +450,12 @@ static GPU_Texture* make_texture_impl(GPU_Format format, uint32_t width, uint32_
     if (data) {
         HIP_OK(hipMemcpy(t->dev, data, (size_t)GPUX_TextureMipBytes(&t->base, 0), hipMemcpyHostToDevice));
         if (mips > 1) {                                                        // gpu_vulkan.c:1444-1446
-            if (!is_f4_cube(t)) {
-                gpu_fail("%s: mip generation is implemented for RGBA32F cubemaps only", fn);
+            if (is_rgba8_pow2(t)) {
+                int rc = pbrk_mip_chain_rgba8(t->dev, (int)width, (int)height, (int)mips, nullptr);
+                if (rc != PBRK_OK) gpu_fail("%s: RGBA8UN mip chain kernel failed (%d)", fn, rc);
+                HIP_OK(hipStreamSynchronize(nullptr));
+            } else if (!is_f4_cube(t)) {
+                gpu_fail("%s: mip generation is implemented for RGBA32F cubemaps and power-of-two 2-D RGBA8UN textures only", fn);
             } else {
                 int rc = pbrk_mip_chain(t->dev, (int)width, (int)mips, nullptr);
                 if (rc != PBRK_OK) gpu_fail("%s: mip chain kernel failed (%d)", fn, rc);
@@ -564,6 +575,7 @@ static KernelId identify_shader(const GPU_ShaderDesc* d) {
         if (t == kTokenBloomDown) return Kernel_BloomDown;
         if (t == kTokenBloomUp) return Kernel_BloomUp;
         if (t == kTokenSun) return Kernel_SunDepth;
+        if (t == kTokenGeometry) return Kernel_Geometry;
         return Kernel_None;
     }
     std::string b = basename_of(d->glsl_debug_filepath);
@@ -578,6 +590,7 @@ static KernelId identify_shader(const GPU_ShaderDesc* d) {
     if (b == "bloom_upsample.glsl" && glsl_contains(d->glsl, "BLOOM_INPUT") && glsl_contains(d->glsl, "radius")) return Kernel_BloomUp;
     if (b == "lightgrid_sweep.glsl" && glsl_contains(d->glsl, "LIGHTMAP_IMG") && glsl_contains(d->glsl, "X_direction")) return Kernel_LightgridSweep;
     if (b == "sun_depth_pass.glsl" && glsl_contains(d->glsl, "sun_space_from_world") && glsl_contains(d->glsl, "vs_position")) return Kernel_SunDepth;
+    if (b == "geometry_pass.glsl" && glsl_contains(d->glsl, "old_clip_space_from_world") && glsl_contains(d->glsl, "out_velocity")) return Kernel_Geometry;
     return Kernel_None;
 }
 static GPU_String token_for(KernelId k) {
@@ -592,6 +605,7 @@ static GPU_String token_for(KernelId k) {
     case Kernel_BloomDown: return GPU_String{kTokenBloomDown, sizeof kTokenBloomDown - 1};
     case Kernel_BloomUp: return GPU_String{kTokenBloomUp, sizeof kTokenBloomUp - 1};
     case Kernel_SunDepth: return GPU_String{kTokenSun, sizeof kTokenSun - 1};
+    case Kernel_Geometry: return GPU_String{kTokenGeometry, sizeof kTokenGeometry - 1};
     default: return GPU_String{nullptr, 0};
     }
 }
@@ -606,7 +620,7 @@ GPU_API GPU_String GPU_SPIRVFromGLSL(DS_Arena* arena, GPU_ShaderStage stage, GPU
     GPU_ShaderDesc probe = *desc;
     probe.spirv = empty;
     KernelId k = identify_shader(&probe);
-    bool stage_ok = (k == Kernel_Lighting || k == Kernel_TaaResolve || k == Kernel_FinalPost || k == Kernel_BloomDown || k == Kernel_BloomUp || k == Kernel_SunDepth) ? (stage == GPU_ShaderStage_Vertex || stage == GPU_ShaderStage_Fragment)
+    bool stage_ok = (k == Kernel_Lighting || k == Kernel_TaaResolve || k == Kernel_FinalPost || k == Kernel_BloomDown || k == Kernel_BloomUp || k == Kernel_SunDepth || k == Kernel_Geometry) ? (stage == GPU_ShaderStage_Vertex || stage == GPU_ShaderStage_Fragment)
                                            : (stage == GPU_ShaderStage_Compute);
     if (k != Kernel_None && stage_ok) {
         if (out_errors) { out_errors->data = nullptr; out_errors->length = 0; }
@@ -614,7 +628,7 @@ GPU_API GPU_String GPU_SPIRVFromGLSL(DS_Arena* arena, GPU_ShaderStage stage, GPU
     }
     snprintf(g_last_error_text, sizeof g_last_error_text,
              "the HIP backend has no built-in kernel for shader \"%s\" (stage %d); supported: gen_brdf_integration_map.glsl, "
-             "gen_irradiance_map.glsl, gen_prefiltered_env_map.glsl, lightgrid_sweep.glsl (compute), lighting_pass.glsl, taa_resolve.glsl, bloom_downsample.glsl, bloom_upsample.glsl, final_post_process.glsl (full-screen), sun_depth_pass.glsl (depth-only raster)",
+             "gen_irradiance_map.glsl, gen_prefiltered_env_map.glsl, lightgrid_sweep.glsl (compute), lighting_pass.glsl, taa_resolve.glsl, bloom_downsample.glsl, bloom_upsample.glsl, final_post_process.glsl (full-screen), sun_depth_pass.glsl (depth-only raster), geometry_pass.glsl (G-buffer raster)",
              basename_of(desc->glsl_debug_filepath).c_str(), (int)stage);
     if (!out_errors) { gpu_fail("GPU_SPIRVFromGLSL: %s", g_last_error_text); return empty; }
     g_last_error.shader_stage = stage; g_last_error.line = 0;
@@ -706,6 +720,33 @@ GPU_API GPU_GraphicsPipeline* GPU_MakeGraphicsPipeline(const GPU_GraphicsPipelin
         GPU_REQUIRE((stride & 3) == 0, nullptr, "GPU_MakeGraphicsPipeline: vertex stride %u is not a multiple of 4 bytes", stride);
         GPU_GraphicsPipeline* p = new GPU_GraphicsPipeline();
         p->layout = desc->layout; p->pass = desc->render_pass; p->kernel = k; p->shade_flags = 0; p->vertex_stride = stride;
+        return p;
+    }
+    if (k == Kernel_Geometry) {
+        // K13: exactly the reference's state (render.cpp:190-233, 700-708)
+        const GPU_RenderPassDesc& rd = desc->render_pass->desc;
+        const GPU_Texture* dt = rd.depth_stencil_target;
+        GPU_REQUIRE(rd.color_targets_count == 5 && dt && dt->format == GPU_Format_D32F_Or_X8D24UN, nullptr,
+                    "GPU_MakeGraphicsPipeline: geometry_pass.glsl needs a render pass with five colour targets and a D32F depth target (render.cpp:700-708)");
+        GPU_REQUIRE(rd.width > 0 && rd.height > 0 && rd.width <= 16384 && rd.height <= 16384 && dt->width == rd.width && dt->height == rd.height && dt->layer_count == 1 && dt->depth == 1, nullptr,
+                    "GPU_MakeGraphicsPipeline: the geometry pass must cover its whole 2-D depth target (at most 16384^2)");
+        for (uint32_t i = 0; i < 5; ++i) {
+            const GPU_Texture* ct = desc->render_pass->targets[i].texture;
+            GPU_REQUIRE(ct && desc->render_pass->targets[i].mip_level == 0 && ct->format == (i < 4 ? GPU_Format_RGBA8UN : GPU_Format_RG16F) &&
+                        ct->width == rd.width && ct->height == rd.height && ct->layer_count == 1 && ct->depth == 1, nullptr,
+                        "GPU_MakeGraphicsPipeline: geometry pass colour target %u must be a %ux%u 2D %s texture (render.cpp:680-691)", i, rd.width, rd.height, i < 4 ? "RGBA8UN" : "RG16F");
+        }
+        GPU_REQUIRE(desc->enable_depth_test && desc->enable_depth_write, nullptr, "GPU_MakeGraphicsPipeline: geometry_pass.glsl is implemented with depth test + depth write only");
+        GPU_REQUIRE(desc->cull_mode == GPU_CullMode_DrawCCW, nullptr, "GPU_MakeGraphicsPipeline: geometry_pass.glsl is implemented for GPU_CullMode_DrawCCW only (render.cpp:232)");
+        GPU_REQUIRE(!desc->enable_blending && !desc->enable_conservative_rasterization, nullptr,
+                    "GPU_MakeGraphicsPipeline: blending and conservative rasterisation are not implemented for geometry_pass.glsl");
+        GPU_REQUIRE(desc->vertex_input_formats && desc->vertex_input_formats_count == 4 && desc->vertex_input_formats[0] == GPU_Format_RGB32F &&
+                    desc->vertex_input_formats[1] == GPU_Format_RGB32F && desc->vertex_input_formats[2] == GPU_Format_RGB32F && desc->vertex_input_formats[3] == GPU_Format_RG32F, nullptr,
+                    "GPU_MakeGraphicsPipeline: geometry_pass.glsl reads the 44-byte Vertex (RGB32F x3, RG32F; render.cpp:227)");
+        for (const char* name : {"GLOBALS", "TEX0", "TEX1", "TEX_ORM", "TEX_EMISSIVE", "SAMPLER_LINEAR_WRAP"})
+            GPU_REQUIRE(find_binding(desc->layout, name) >= 0, nullptr, "GPU_MakeGraphicsPipeline: the geometry pass layout has no \"%s\" binding", name);
+        GPU_GraphicsPipeline* p = new GPU_GraphicsPipeline();
+        p->layout = desc->layout; p->pass = desc->render_pass; p->kernel = k; p->shade_flags = 0; p->vertex_stride = 44;
         return p;
     }
     GPU_REQUIRE(k == Kernel_Lighting || k == Kernel_TaaResolve || k == Kernel_FinalPost || k == Kernel_BloomDown || k == Kernel_BloomUp, nullptr,
@@ -1104,30 +1145,74 @@ static void close_raster_job(GPU_Graph* g) {
     if ((size_t)op.raster_slot >= g->raster.size()) g->raster.resize((size_t)op.raster_slot + 1);
     RasterScratch& rs = g->raster[(size_t)op.raster_slot];
     const int W = (int)op.tex->base.width, H = (int)op.tex->base.height;
-    const size_t need = pbrk_raster_scratch_bytes(op.tri_count, W, H);
+    const bool geo = op.gpipe->kernel == Kernel_Geometry;
+    const size_t need = geo ? pbrk_geometry_scratch_bytes(op.tri_count, W, H) : pbrk_raster_scratch_bytes(op.tri_count, W, H);
     bool ok = true;
     if (rs.dev_bytes < need) {
         (void)hipFree(rs.dev); rs.dev = nullptr; rs.dev_bytes = 0;
         if (hipMalloc(&rs.dev, need) == hipSuccess) rs.dev_bytes = need; else { rs.dev = nullptr; ok = false; }
     }
-    if (ok && rs.draws_cap < op.draws.size()) {
+    const size_t table = op.draws.size() * (geo ? sizeof(PbrkGeoDraw) : sizeof(PbrkRasterDraw));
+    if (ok && rs.draws_cap < table) {
         (void)hipFree(rs.draws_dev); (void)hipHostFree(rs.draws_host); rs.draws_dev = nullptr; rs.draws_host = nullptr; rs.draws_cap = 0;
-        const size_t bytes = op.draws.size() * sizeof(PbrkRasterDraw);
-        if (hipMalloc(&rs.draws_dev, bytes) == hipSuccess && hipHostMalloc((void**)&rs.draws_host, bytes, hipHostMallocDefault) == hipSuccess) rs.draws_cap = op.draws.size();
+        if (hipMalloc(&rs.draws_dev, table) == hipSuccess && hipHostMalloc((void**)&rs.draws_host, table, hipHostMallocDefault) == hipSuccess) rs.draws_cap = table;
         else ok = false;
     }
     if (ok && !G.raster_rejected) {
         if (hipMalloc((void**)&G.raster_rejected, 8) != hipSuccess || hipMemset(G.raster_rejected, 0, 8) != hipSuccess) { G.raster_rejected = nullptr; ok = false; }
     }
-    if (!ok) { (void)hipGetLastError(); op.tri_count = 0; op.draws.clear(); gpu_fail("GPU_OpEndRenderPass: allocation of the sun depth raster scratch (%zu bytes) failed", need); }
+    if (!ok) { (void)hipGetLastError(); op.tri_count = 0; op.draws.clear(); gpu_fail("GPU_OpEndRenderPass: allocation of the raster scratch (%zu bytes) failed", need); }
+}
+
+// K13: one indexed draw of the geometry pass.  All draws of a render-pass instance are one job whatever buffers and textures they
+// bind: each draw records its own.  Everything a launch could trip over is checked here.
+static void record_geometry_draw(GPU_Graph* g, const DrawParams& dp, uint32_t index_count, uint32_t instance_count, uint32_t first_index, uint32_t vertex_offset) {
+    const char* fn = "GPU_OpDrawIndexed";
+    GPU_REQUIRE_V(dp.pipeline->pass == g->in_pass, "%s: pipeline was created for a different render pass", fn);
+    GPU_REQUIRE_V(dp.set->layout == dp.pipeline->layout, "%s: descriptor set and pipeline use different layouts", fn);
+    Slot* gl = named_slot(dp.set, "GLOBALS");
+    GPU_REQUIRE_V(gl && gl->buf && gl->buf->base.size >= 512, "%s: \"GLOBALS\" must be a buffer that holds old_clip_space_from_world (render.h:122-136)", fn);
+    for (const char* name : {"TEX0", "TEX1", "TEX_ORM", "TEX_EMISSIVE"}) {
+        Slot* sl = named_slot(dp.set, name);
+        GPU_REQUIRE_V(sl && sl->tex, "%s: geometry pass: \"%s\" is not bound", fn, name);
+        GPU_REQUIRE_V(sl->tex->base.format == GPU_Format_RGBA8UN && sl->tex->base.layer_count == 1 && sl->tex->base.depth == 1 && sl->whole,
+                      "%s: geometry pass: \"%s\" must be a whole 2D RGBA8UN texture", fn, name);
+    }
+    Slot* sm = named_slot(dp.set, "SAMPLER_LINEAR_WRAP");
+    GPU_REQUIRE_V(sm && sm->sampler == &G.samplers[0], "%s: geometry pass: \"SAMPLER_LINEAR_WRAP\" must be GPU_SamplerLinearWrap()", fn);
+    GPU_REQUIRE_V(g->push_size == 16, "%s: the geometry pass needs its 16-byte push constants (taa_jitter, taa_jitter_prev; render.cpp:1091-1094)", fn);
+    GPU_REQUIRE_V(g->vertex_buffer, "%s: no vertex buffer bound (GPU_OpBindVertexBuffer)", fn);
+    GPU_REQUIRE_V(g->index_buffer, "%s: no index buffer bound (GPU_OpBindIndexBuffer)", fn);
+    const uint64_t n_idx = g->index_buffer->base.size / 4;
+    GPU_REQUIRE_V((uint64_t)first_index + index_count <= n_idx, "%s: indices [%u, %llu) lie outside the bound index buffer (%llu indices)", fn,
+                  first_index, (unsigned long long)first_index + index_count, (unsigned long long)n_idx);
+    const uint32_t tris = index_count / 3;
+    if (tris == 0 || instance_count == 0) return;
+    if (g->raster_op < 0) {
+        Op op; op.kind = Op_Raster; op.name = "K13.geometry";
+        op.pass = g->in_pass; op.gpipe = dp.pipeline;
+        op.tex = (TextureImpl*)g->in_pass->desc.depth_stencil_target;
+        op.vertex_stride = 44;
+        op.raster_slot = (int)g->raster_used++;
+        g->ops.push_back(op);
+        g->raster_op = (int)g->ops.size() - 1;
+    }
+    Op& op = g->ops[(size_t)g->raster_op];
+    GPU_REQUIRE_V((uint64_t)op.tri_count + tris <= (1u << 26), "%s: more than 2^26 triangles in one geometry pass", fn);
+    RasterDraw d; d.set = dp.set; d.first_tri = op.tri_count; d.first_index = first_index; d.vertex_offset = vertex_offset;
+    d.vb = g->vertex_buffer; d.ib = g->index_buffer; memcpy(d.push, g->push, 16);
+    op.draws.push_back(d);
+    op.tri_count += tris;
 }
 
 GPU_API void GPU_OpDrawIndexed(GPU_Graph* g, uint32_t index_count, uint32_t instance_count, uint32_t first_index, uint32_t vertex_offset, uint32_t first_instance) {
     (void)first_instance;                                                     // the shader never reads gl_InstanceIndex
     REC_GUARD(g);
-    GPU_REQUIRE_V(g->in_pass && g->bound_draw >= 0 && g->draw_params[(size_t)g->bound_draw].pipeline->kernel == Kernel_SunDepth,
-                  "GPU_OpDrawIndexed: unsupported (raster): only the sun depth pass (sun_depth_pass.glsl) draws indexed triangles");
+    GPU_REQUIRE_V(g->in_pass && g->bound_draw >= 0 && (g->draw_params[(size_t)g->bound_draw].pipeline->kernel == Kernel_SunDepth ||
+                                                       g->draw_params[(size_t)g->bound_draw].pipeline->kernel == Kernel_Geometry),
+                  "GPU_OpDrawIndexed: unsupported (raster): only the sun depth pass (sun_depth_pass.glsl) and the geometry pass (geometry_pass.glsl) draw indexed triangles");
     const DrawParams dp = g->draw_params[(size_t)g->bound_draw];
+    if (dp.pipeline->kernel == Kernel_Geometry) { record_geometry_draw(g, dp, index_count, instance_count, first_index, vertex_offset); return; }
     GPU_REQUIRE_V(dp.pipeline->pass == g->in_pass, "GPU_OpDrawIndexed: pipeline was created for a different render pass");
     GPU_REQUIRE_V(dp.set->layout == dp.pipeline->layout, "GPU_OpDrawIndexed: descriptor set and pipeline use different layouts");
     Slot* gl = named_slot(dp.set, "GLOBALS");
@@ -1154,7 +1239,8 @@ GPU_API void GPU_OpDrawIndexed(GPU_Graph* g, uint32_t index_count, uint32_t inst
     }
     Op& op = g->ops[(size_t)g->raster_op];
     GPU_REQUIRE_V((uint64_t)op.tri_count + tris <= (1u << 26), "GPU_OpDrawIndexed: more than 2^26 triangles in one sun depth pass");
-    op.draws.push_back({dp.set, op.tri_count, first_index, vertex_offset});
+    RasterDraw rd; rd.set = dp.set; rd.first_tri = op.tri_count; rd.first_index = first_index; rd.vertex_offset = vertex_offset;
+    op.draws.push_back(rd);
     op.tri_count += tris;
 }
 GPU_API void GPU_OpBindVertexBuffer(GPU_Graph* g, GPU_Buffer* b) {
@@ -1217,7 +1303,7 @@ GPU_API void GPU_OpGenerateMipmaps(GPU_Graph* g, GPU_Texture* tex) {
     REC_GUARD(g);
     GPU_REQUIRE_V(tex, "GPU_OpGenerateMipmaps: NULL texture");
     TextureImpl* t = (TextureImpl*)tex;
-    GPU_REQUIRE_V(is_f4_cube(t), "GPU_OpGenerateMipmaps: implemented for RGBA32F cubemaps only");
+    GPU_REQUIRE_V(is_f4_cube(t) || is_rgba8_pow2(t), "GPU_OpGenerateMipmaps: implemented for RGBA32F cubemaps and power-of-two 2-D RGBA8UN textures only");
     Op op; op.kind = Op_MipGen; op.name = "K2.mip_chain"; op.tex = t;
     g->ops.push_back(op);
 }
@@ -1624,6 +1710,26 @@ static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
     case Op_Raster: {
         if (!op.tri_count) return;
         RasterScratch& rs = g->raster[(size_t)op.raster_slot];             // draw table snapshotted by GPU_GraphSubmit
+        if (op.gpipe->kernel == Kernel_Geometry) {
+            PbrkGeometryArgs a;
+            a.draws = (const PbrkGeoDraw*)rs.draws_dev; a.draw_count = (uint32_t)op.draws.size(); a.tri_count = op.tri_count;
+            for (int k = 0; k < 4; ++k) a.color[k] = ((TextureImpl*)op.pass->targets[(size_t)k].texture)->dev;
+            a.velocity = ((TextureImpl*)op.pass->targets[4].texture)->dev;
+            a.depth = (float*)op.tex->dev; a.width = (int)op.tex->base.width; a.height = (int)op.tex->base.height;
+            a.scratch = rs.dev; a.rejected = G.raster_rejected;
+            timed(g, "K13.setup", ev_used, [&] {
+                HIP_OK(hipMemcpyAsync(rs.draws_dev, rs.draws_host, op.draws.size() * sizeof(PbrkGeoDraw), hipMemcpyHostToDevice, st));
+                int rc = pbrk_geometry_setup(&a, st);
+                if (rc != PBRK_OK) gpu_fail("K13 setup launch failed (%d)", rc);
+            });
+            timed(g, "K13.tiles", ev_used, [&] {
+                int rc = pbrk_geometry_tiles(&a, st);
+                if (rc != PBRK_OK) gpu_fail("K13 tile launch failed (%d)", rc);
+            });
+            for (const GPU_TextureView& tv : op.pass->targets) { ((TextureImpl*)tv.texture)->bordered_valid = false; ((TextureImpl*)tv.texture)->lut_cells_valid = false; }
+            op.tex->bordered_valid = false;
+            return;
+        }
         PbrkRasterArgs a;
         a.vertices = op.buf->dev; a.vertex_stride = op.vertex_stride; a.vertex_count = op.buf->base.size / op.vertex_stride;
         a.indices = (const uint32_t*)op.buf2->dev;
@@ -1644,7 +1750,8 @@ static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
     }
     case Op_MipGen: {
         timed(g, op.name, ev_used, [&] {
-            int rc = pbrk_mip_chain(op.tex->dev, (int)op.tex->base.width, (int)op.tex->base.mip_level_count, st);
+            int rc = is_rgba8_pow2(op.tex) ? pbrk_mip_chain_rgba8(op.tex->dev, (int)op.tex->base.width, (int)op.tex->base.height, (int)op.tex->base.mip_level_count, st)
+                                           : pbrk_mip_chain(op.tex->dev, (int)op.tex->base.width, (int)op.tex->base.mip_level_count, st);
             if (rc != PBRK_OK) gpu_fail("K2 launch failed (%d)", rc);
         });
         op.tex->bordered_valid = false;
@@ -1901,10 +2008,29 @@ GPU_API void GPU_GraphSubmit(GPU_Graph* g) {
     for (const Op& op : g->ops) {
         if (op.kind != Op_Raster || !op.tri_count) continue;
         RasterScratch& rs = g->raster[(size_t)op.raster_slot];
+        if (op.gpipe->kernel == Kernel_Geometry) {                           // K13: both matrices, the draw's textures and buffers
+            for (size_t i = 0; i < op.draws.size(); ++i) {
+                const RasterDraw& d = op.draws[i];
+                BufferImpl* gb = named_slot(d.set, "GLOBALS")->buf;
+                PbrkGeoDraw& o = ((PbrkGeoDraw*)rs.draws_host)[i];
+                memset(&o, 0, sizeof o);
+                if (gb->pinned_host) { memcpy(o.m, gb->dev, 64); memcpy(o.m_old, (const char*)gb->dev + 448, 64); }      // render.h:123, :130
+                else { HIP_OK(hipMemcpy(o.m, gb->dev, 64, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(o.m_old, (const char*)gb->dev + 448, 64, hipMemcpyDeviceToHost)); }
+                memcpy(o.jitter, d.push, 8); memcpy(o.jitter_prev, d.push + 2, 8);
+                static const char* const names[4] = {"TEX0", "TEX1", "TEX_ORM", "TEX_EMISSIVE"};
+                for (int k = 0; k < 4; ++k) {
+                    const TextureImpl* t = named_slot(d.set, names[k])->tex;
+                    o.tex[k].texels = t->dev; o.tex[k].width = (int)t->base.width; o.tex[k].height = (int)t->base.height; o.tex[k].levels = (int)t->base.mip_level_count;
+                }
+                o.vertices = d.vb->dev; o.indices = (const uint32_t*)d.ib->dev; o.vertex_count = d.vb->base.size / 44u;
+                o.first_tri = d.first_tri; o.first_index = d.first_index; o.vertex_offset = d.vertex_offset;
+            }
+            continue;
+        }
         for (size_t i = 0; i < op.draws.size(); ++i) {
             const RasterDraw& d = op.draws[i];
             BufferImpl* gb = named_slot(d.set, "GLOBALS")->buf;
-            PbrkRasterDraw& o = rs.draws_host[i];
+            PbrkRasterDraw& o = ((PbrkRasterDraw*)rs.draws_host)[i];
             if (gb->pinned_host) memcpy(o.m, (const char*)gb->dev + 384, 64);        // render.h:129: sun_space_from_world
             else HIP_OK(hipMemcpy(o.m, (const char*)gb->dev + 384, 64, hipMemcpyDeviceToHost));
             GPU_REQUIRE_V(o.m[3] == 0.0f && o.m[7] == 0.0f && o.m[11] == 0.0f && o.m[15] > 0.0f,

@@ -2,14 +2,16 @@
  * pbr_demo.c -- headless C driver of the hot path through the GPU_* boundary (what main.cpp:35-51 +
  * HotreloadShaders + BuildRenderCommands do for this path, without window / mesh import / raster passes).
  *
- *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm]]]
+ *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster]]]]
  *
  * Loads a vertical-strip HDR cube (asset_import.cpp:17-27), runs the IBL precompute (render.cpp:505-619),
  * shades a flat synthetic G-buffer (a metallic floor under the sky), then runs three frames of the per-frame chain
  * lighting -> TAA resolve -> bloom -> tone map (render.cpp:1119-1187) plus the light-grid sweep (render.cpp:1061-1072),
  * and prints fp64 checksums of every map / frame plus HIP-event timings per kernel, one "key value" pair per line, so
  * that a test can compare it with the same sequence driven from another language.  With a last argument the 8-bit
- * frame is written as a binary PPM.
+ * frame is written as a binary PPM.  With `raster` as the ninth argument the three frames of the chain start with the geometry pass
+ * (render.cpp:1076-1115) over a small built-in mesh (a checkered floor and a block), so the lighting pass shades a rasterised
+ * G-buffer instead of the synthetic one; every other output is unchanged.
  */
 #include "pbr_host.h"
 
@@ -35,6 +37,43 @@ static double checksum_texture_mip(GPU_Texture* tex, uint32_t mip, int channels_
     GPU_DestroyGraph(g);
     GPU_DestroyBuffer(buf);
     return sum;
+}
+
+/* opt-in `raster` mode: a two-sided floor and block, one procedural material */
+static PBR_Mesh* demo_mesh(PBR_Material** material_out) {
+    enum { S = 16 };
+    static uint8_t img[4][S * S * 4];
+    for (int y = 0; y < S; ++y)
+        for (int x = 0; x < S; ++x) {
+            const int on = ((x >> 2) + (y >> 2)) & 1;
+            uint8_t* b = img[0] + 4 * (y * S + x); b[0] = on ? 230 : 90; b[1] = on ? 200 : 80; b[2] = on ? 120 : 70; b[3] = 255;
+            uint8_t* n = img[1] + 4 * (y * S + x); n[0] = 128; n[1] = 128; n[2] = 255; n[3] = 255;
+            uint8_t* o = img[2] + 4 * (y * S + x); o[0] = 255; o[1] = on ? 60 : 160; o[2] = on ? 255 : 0; o[3] = 255;
+            uint8_t* e = img[3] + 4 * (y * S + x); e[0] = 0; e[1] = 0; e[2] = 0; e[3] = 255;
+        }
+    *material_out = PBR_MakeMaterial(S, img[0], img[1], img[2], img[3]);
+    /* quads as (corner, edge u, edge v, normal); each drawn with both windings */
+    static const float quads[3][12] = {
+        {-40.f, 2.f, 0.f, 80.f, 0.f, 0.f, 0.f, 80.f, 0.f, 0.f, 0.f, 1.f},       /* floor z = 0 */
+        {-3.f, 14.f, 0.f, 6.f, 0.f, 0.f, 0.f, 0.f, 6.f, 0.f, -1.f, 0.f},        /* block front */
+        {-3.f, 14.f, 6.f, 6.f, 0.f, 0.f, 0.f, 6.f, 0.f, 0.f, 0.f, 1.f}};        /* block top */
+    float v[3 * 4 * 11]; uint32_t ix[3 * 12]; uint32_t nv = 0, ni = 0;
+    for (int q = 0; q < 3; ++q) {
+        const float* Q = quads[q];
+        for (int c = 0; c < 4; ++c) {
+            const float a = (c == 1 || c == 2) ? 1.f : 0.f, b = c >= 2 ? 1.f : 0.f;
+            float* o = v + 11 * (nv + c);
+            for (int e = 0; e < 3; ++e) { o[e] = Q[e] + a * Q[3 + e] + b * Q[6 + e]; o[3 + e] = Q[9 + e]; o[6 + e] = e == 0 ? 1.f : 0.f; }
+            o[9] = a * (q == 0 ? 20.f : 2.f); o[10] = b * (q == 0 ? 20.f : 2.f);
+        }
+        const uint32_t t[12] = {0, 1, 2, 0, 2, 3, 0, 2, 1, 0, 3, 2};
+        for (int k = 0; k < 12; ++k) ix[ni++] = nv + t[k];
+        nv += 4;
+    }
+    PBR_MeshPart part = {0, ni};
+    PBR_Mesh* m = PBR_MakeMesh(v, nv, ix, ni, &part, 1);
+    if (m) PBR_MeshSetPartMaterial(m, 0, *material_out);
+    return m;
 }
 
 int main(int argc, char** argv) {
@@ -101,8 +140,20 @@ int main(int argc, char** argv) {
 
     /* ---- per-frame chain: lighting -> TAA -> bloom -> final, three frames (velocity buffers stay zero: a still camera) ---- */
     PBR_PostProcess* pp = PBR_MakePostProcess(&gb, width, height, GPU_Format_RGBA8UN);
+    const int raster = argc > 9 && strcmp(argv[9], "raster") == 0;
+    PBR_Material* material = NULL; PBR_Mesh* mesh = NULL; PBR_GeometryPass* gp = NULL;
+    if (raster) {
+        mesh = demo_mesh(&material);
+        gp = PBR_MakeGeometryPass(&gb, pp, width, height);
+        if (!mesh || !gp) return 1;
+        printf("gbuffer_raster 1\n");
+    }
     for (uint32_t frame = 0; frame < 3; ++frame) {
         PBR_FillGlobals(&globals, pos, NULL, 75.f, (float)width / (float)height, 0.02f, 10000.f, 56.5f, 97.f, frame);
+        if (raster) {                                                        /* render.cpp:993, 1076-1115; a still camera */
+            memcpy(globals.old_clip_space_from_world, globals.clip_space_from_world, sizeof globals.clip_space_from_world);
+            PBR_RecordGeometryPass(gp, graph, mesh, NULL, &globals, NULL, NULL, frame);
+        }
         PBR_RecordLightingPass(lp, graph, &globals, 0, 0);                   /* render.cpp:1119-1127 */
         PBR_RecordTaaResolve(pp, graph, frame);                              /* render.cpp:1131-1137 */
         PBR_RecordBloom(pp, graph, frame);                                   /* render.cpp:1139-1176 */
@@ -157,6 +208,10 @@ int main(int argc, char** argv) {
         printf("lightgrid_bits_sum %.9e\n", checksum_texture_mip(grid, 0, 0));
         GPU_DestroyGraph(g); GPU_DestroyBuffer(up); free(vox);
         PBR_DestroyLightgrid(lg);
+    }
+    if (raster) {
+        printf("gbuffer_depth_sum %.9e\n", checksum_texture_mip(gb.depth, 0, 1));
+        PBR_DestroyGeometryPass(gp); PBR_DestroyMesh(mesh); PBR_DestroyMaterial(material);
     }
     PBR_DestroyPostProcess(pp);
 

@@ -10,16 +10,10 @@
  * The backend rasterises the pass with K12; its texture is the SUN_DEPTH_MAP of the lighting pass.
  */
 #include "pbr_host.h"
+#include "pbr_mesh.h"
 
 #include <stdlib.h>
 #include <string.h>
-
-struct PBR_Mesh {
-    GPU_Buffer* vertex_buffer;
-    GPU_Buffer* index_buffer;
-    PBR_MeshPart* parts;
-    uint32_t part_count;
-};
 
 PBR_Mesh* PBR_MakeMesh(const float* vertices_11f, uint32_t vertex_count, const uint32_t* indices, uint32_t index_count,
                        const PBR_MeshPart* parts, uint32_t part_count) {
@@ -31,7 +25,8 @@ PBR_Mesh* PBR_MakeMesh(const float* vertices_11f, uint32_t vertex_count, const u
     m->vertex_buffer = GPU_MakeBuffer(vertex_count * 44u, GPU_BufferFlag_GPU | GPU_BufferFlag_StorageBuffer, vertices_11f);
     m->index_buffer = GPU_MakeBuffer(index_count * 4u, GPU_BufferFlag_GPU | GPU_BufferFlag_StorageBuffer, indices);
     m->parts = (PBR_MeshPart*)malloc((part_count ? part_count : 1) * sizeof *m->parts);
-    if (!m->vertex_buffer || !m->index_buffer || !m->parts) { PBR_DestroyMesh(m); return NULL; }
+    m->materials = (PBR_Material**)calloc(part_count ? part_count : 1, sizeof *m->materials);
+    if (!m->vertex_buffer || !m->index_buffer || !m->parts || !m->materials) { PBR_DestroyMesh(m); return NULL; }
     if (part_count) memcpy(m->parts, parts, part_count * sizeof *parts);
     m->part_count = part_count;
     return m;
@@ -42,12 +37,14 @@ void PBR_DestroyMesh(PBR_Mesh* m) {
     GPU_DestroyBuffer(m->vertex_buffer);
     GPU_DestroyBuffer(m->index_buffer);
     free(m->parts);
+    free(m->materials);
     free(m);
 }
 
 GPU_Buffer* PBR_MeshVertexBuffer(PBR_Mesh* m) { return m->vertex_buffer; }
 GPU_Buffer* PBR_MeshIndexBuffer(PBR_Mesh* m) { return m->index_buffer; }
 uint32_t PBR_MeshPartCount(const PBR_Mesh* m) { return m->part_count; }
+void PBR_MeshSetPartMaterial(PBR_Mesh* m, uint32_t part, PBR_Material* material) { if (part < m->part_count) m->materials[part] = material; }
 
 struct PBR_SunDepthPass {
     GPU_Texture* sun_depth_rt;

@@ -240,6 +240,12 @@ PROTOTYPES = {
     "PBR_SunDepthGlobalsBuffer": (BufP, [VP]), "PBR_SunDepthPipeline": (VP, [VP]), "PBR_SunDepthRenderPass": (VP, [VP]),
     "PBR_SunDepthLayout": (VP, [VP]), "PBR_SunDepthDescriptorSet": (VP, [VP]),
     "PBR_RecordSunDepthPass": (None, [VP, VP, VP, C.POINTER(PBR_Globals)]),
+    "PBR_MakeMaterial": (VP, [U32, VP, VP, VP, VP]), "PBR_DestroyMaterial": (None, [VP]), "PBR_MaterialTexture": (TexP, [VP, U32]),
+    "PBR_MeshSetPartMaterial": (None, [VP, U32, VP]),
+    "PBR_MakeGeometryPass": (VP, [C.POINTER(PBR_GBuffer), VP, U32, U32]), "PBR_DestroyGeometryPass": (None, [VP]),
+    "PBR_GeometryGlobalsBuffer": (BufP, [VP]), "PBR_GeometryPipeline": (VP, [VP, U32]), "PBR_GeometryRenderPass": (VP, [VP, U32]),
+    "PBR_GeometryLayout": (VP, [VP]), "PBR_GeometryDescriptorSet": (VP, [VP, VP]),
+    "PBR_RecordGeometryPass": (None, [VP, VP, VP, VP, C.POINTER(PBR_Globals), C.POINTER(C.c_float), C.POINTER(C.c_float), U32]),
     "PBR_MakeLightgrid": (VP, [U32]), "PBR_DestroyLightgrid": (None, [VP]), "PBR_LightgridTexture": (TexP, [VP]),
     "PBR_LightgridSweepDirection": (U32, [VP]), "PBR_RecordLightgridClear": (None, [VP, VP]),
     "PBR_RecordLightgridSweep": (None, [VP, VP]), "PBR_RecordLightgridSweepLines": (None, [VP, VP, U32, U32, U32, U32, U32]),
@@ -279,6 +285,9 @@ PROTOTYPES = {
     "pbrk_equirect_to_cube": (C.c_int, [VP, C.c_int, C.c_int, VP, C.c_int, VP]),
     "pbrk_raster_scratch_bytes": (C.c_size_t, [U32, C.c_int, C.c_int]),
     "pbrk_raster_setup": (C.c_int, [VP, VP]), "pbrk_raster_tiles": (C.c_int, [VP, VP]),
+    "pbrk_geometry_scratch_bytes": (C.c_size_t, [U32, C.c_int, C.c_int]),
+    "pbrk_geometry_setup": (C.c_int, [VP, VP]), "pbrk_geometry_tiles": (C.c_int, [VP, VP]),
+    "pbrk_mip_chain_rgba8": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, VP]),
 }
 
 _LIB = None
@@ -384,6 +393,17 @@ def make_mesh(vertices, indices, parts):
     m = lib().PBR_MakeMesh(v.ctypes.data_as(VP), len(v), ix.ctypes.data_as(VP), len(ix), pa, len(parts))
     if not m:
         raise RuntimeError("PBR_MakeMesh failed")
+    return m
+
+
+def make_material(images):
+    """images: four uint8 [size][size][4] level-0 images (base colour, normal, ORM, emissive) -> PBR_Material* with generated mips."""
+    imgs = [np.ascontiguousarray(im, np.uint8) for im in images]
+    size = imgs[0].shape[0]
+    assert len(imgs) == 4 and all(im.shape == (size, size, 4) for im in imgs)
+    m = lib().PBR_MakeMaterial(size, *[im.ctypes.data_as(VP) for im in imgs])
+    if not m:
+        raise RuntimeError("PBR_MakeMaterial failed")
     return m
 
 

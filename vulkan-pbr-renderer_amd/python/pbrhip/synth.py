@@ -535,12 +535,13 @@ def _sun_rotation(sun_angle):
     return np.eye(3) + np.sin(ax) * K + (1 - np.cos(ax)) * (K @ K)
 
 
-def synth_mesh_temple(n_triangles=200000, seed=0x5EED0012, sun_angle=(56.5, 97.0), map_size=2048):
+def synth_mesh_temple(n_triangles=200000, seed=0x5EED0012, sun_angle=(56.5, 97.0), map_size=2048, n_materials=None):
     """A temple for the sun depth pass (render.cpp:993-1020), about n_triangles triangles in ~100 parts of one merged mesh (the layout
     of asset_import.cpp:172-173): a floor grid reaching past the +-40 sun volume, a ring of columns, boxes, spheres, an arch, and one
     part of hostile cases -- slivers, degenerate triangles (repeated index, collinear), geometry beyond +-40 in x / y and in z (outside
     the depth range), a quad larger than the map, and vertices placed on the exact pixel centres of a map_size^2 map at sun_angle.
-    Returns (vertices float32 [n][11] = position, normal, tangent, uv; indices uint32; parts [(first_index, index_count)])."""
+    Returns (vertices float32 [n][11] = position, normal, tangent, uv; indices uint32; parts [(first_index, index_count)]); with
+    n_materials also a fourth value, the material index of every part (part k uses material k mod n_materials)."""
     rng = np.random.default_rng(seed)
     P, UV, T, parts = [], [], [], []
     nv_total = [0]
@@ -633,4 +634,24 @@ def synth_mesh_temple(n_triangles=200000, seed=0x5EED0012, sun_angle=(56.5, 97.0
     verts[:, 0:3] = pos
     verts[:, 5] = 1.0                                                          # normal +z (not read by the pass)
     verts[:, 9:11] = np.concatenate(UV).astype(np.float32)
+    if n_materials is not None:
+        return verts, np.concatenate(T).astype(np.uint32).ravel(), parts, [k % int(n_materials) for k in range(len(parts))]
     return verts, np.concatenate(T).astype(np.uint32).ravel(), parts
+
+
+def synth_materials(n, size, seed=0x5EED1300):
+    """n procedural materials: each four uint8 [size][size][4] images (base colour, normal, ORM, emissive).  The base colour's alpha
+    crosses 0.3 (a band of low alpha), so the geometry pass's discard is exercised; normals stay inside the unit disc."""
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:size, 0:size].astype(np.float64) / size
+    out = []
+    for k in range(n):
+        f = rng.uniform(1.0, 4.0, 6)
+        ph = rng.uniform(0.0, 2.0 * np.pi, 6)
+        w = lambda a: 0.5 + 0.5 * np.sin(2.0 * np.pi * np.round(f[a]) * (x if a % 2 == 0 else y) + ph[a])  # noqa: E731
+        base = np.stack([0.2 + 0.8 * w(0), 0.2 + 0.8 * w(1), 0.2 + 0.8 * w(2), np.clip(1.6 * w(3) * w(4) + 0.15, 0.0, 1.0)], -1)
+        nrm = np.stack([0.5 + 0.3 * (w(0) - 0.5), 0.5 + 0.3 * (w(1) - 0.5), np.ones_like(x), np.ones_like(x)], -1)
+        orm = np.stack([np.ones_like(x), 0.1 + 0.8 * w(2), w(5), np.ones_like(x)], -1)
+        emi = np.stack([0.3 * w(4), 0.2 * w(5), 0.4 * w(3), np.ones_like(x)], -1)
+        out.append([np.rint(255.0 * im).astype(np.uint8) for im in (base, nrm, orm, emi)])
+    return out
