@@ -142,3 +142,42 @@ def raster(depth, pos, indices, draws):
     out = depth.copy().ravel()
     np.minimum.at(out, lin, z)
     return out.reshape(H, W), rejected
+
+
+def crowded_triangles(W, H, seed=0x5EED12C0):
+    """Input of the K12 and K13 GPU tests that load the paths a small random scene never reaches: one triangle over the whole target
+    (its pixel box touches every tile), 260 small ones inside the tile at (64, 64) and six across the right and bottom edges.
+    Returns (tris float64 [n][3][2] in pixels, multiples of 1/8, all of negative area: counter-clockwise on a y-down screen;
+    depth float64 [n], distinct, the large triangle behind everything)."""
+    rng = np.random.default_rng(seed)
+    big = [[(-10.0, -10.0), (-10.0, 2.0 * H + 20.0), (2.0 * W + 20.0, -10.0)]]
+    c = rng.uniform(67.0, 93.0, (260, 1, 2))
+    small = c + np.array([(-2.0, -2.0), (0.0, 2.0), (2.0, -1.0)]) + rng.uniform(-0.5, 0.5, (260, 3, 2))
+    edge = [[(W - 10.0, 20.0), (W - 5.0, 50.0), (W + 15.0, 30.0)], [(W - 1.5, 60.0), (W - 0.25, 70.0), (W + 40.0, 64.0)],
+            [(50.0, H - 8.0), (60.0, H - 0.75), (90.0, H + 12.0)], [(100.0, H - 1.5), (104.0, H + 30.0), (130.0, H - 1.25)],
+            [(W - 20.0, H - 20.0), (W - 12.0, H + 9.0), (W + 9.0, H - 12.0)], [(W - 1.5, H - 1.5), (W - 1.0, H + 5.0), (W + 5.0, H - 1.0)]]
+    tris = np.rint(np.concatenate([np.array(big), small, np.array(edge)]) * 8.0) / 8.0
+    x, y = tris[..., 0], tris[..., 1]
+    area = (x[:, 1] - x[:, 0]) * (y[:, 2] - y[:, 0]) - (y[:, 1] - y[:, 0]) * (x[:, 2] - x[:, 0])
+    assert (area < 0).all()
+    m = len(tris)
+    depth = np.concatenate([[0.9], rng.permutation(np.arange(1, m)) / (m + 2.0) * 0.8])
+    return tris, depth
+
+
+def tile_load(tris, W, H, tile=32, max_tiles=16):
+    """What triangles given in pixels ask of the tile structure of DESIGN.md K12: (bin size of every tile [ty][tx], number of triangles
+    whose pixel box touches more than `max_tiles` tiles).  Boxes by the contract's rule: the pixel centres inside the bounding box."""
+    tx, ty = -(-W // tile), -(-H // tile)
+    bins, large = np.zeros((ty, tx), np.int64), 0
+    for t in np.asarray(tris, np.float64):
+        i0, i1 = max(int(np.ceil(t[:, 0].min() - 0.5)), 0), min(int(np.floor(t[:, 0].max() - 0.5)), W - 1)
+        j0, j1 = max(int(np.ceil(t[:, 1].min() - 0.5)), 0), min(int(np.floor(t[:, 1].max() - 0.5)), H - 1)
+        if i0 > i1 or j0 > j1:
+            continue
+        a0, a1, b0, b1 = i0 // tile, i1 // tile, j0 // tile, j1 // tile
+        if (a1 - a0 + 1) * (b1 - b0 + 1) > max_tiles:
+            large += 1
+        else:
+            bins[b0:b1 + 1, a0:a1 + 1] += 1
+    return bins, large

@@ -1,6 +1,6 @@
 """K13: the geometry pass (geometry_pass.glsl through GPU_OpDrawIndexed) on the GPU against the CPU reference of the contract
 (tests/geometry_raster_ref.py).  Depth, normal, ORM, emissive and velocity are compared bit for bit; base colour
-within one 8-bit code (hardware pow).  Every frame is at most 64^2 with a few hundred triangles and 32^2 textures."""
+within one 8-bit code (hardware pow).  Every frame is at most 193 x 97 with a few hundred triangles and 32^2 textures."""
 import ctypes as C
 import os
 import sys
@@ -133,6 +133,20 @@ def two_draw_scene(W=64, H=40):
         d["mesh"] = 2
     return dict(W=W, H=H, materials=a["materials"] + b["materials"], meshes=a["meshes"] + b["meshes"] + c["meshes"],
                 passes=[dict(clear=True, draws=da + db), dict(clear=False, draws=dc)])
+
+
+def crowded_scene(W, H):
+    """R.crowded_triangles under the orthographic pixel matrix: a triangle over the whole target behind everything, 260 in one tile, six
+    across the right and bottom edges; each with its own depth and its own emissive texel."""
+    tris, depth = R.crowded_triangles(W, H)
+    m = len(tris)
+    pos = np.concatenate([tris.reshape(-1, 2), np.repeat(depth, 3)[:, None]], 1)
+    k = np.arange(m)
+    uv = np.repeat(np.stack([(k % 32 + 0.5) / 32, (k // 32 + 0.5) / 32], 1), 3, 0)
+    M = R.pixel_matrix(W, H)
+    draw = dict(m=M, m_old=M, jitter=(0.0, 0.0), jitter_prev=(0.0, 0.0), material=0, vertices=vertices(pos, uv),
+                indices=np.arange(3 * m, dtype=np.uint32), index_count=3 * m, first_index=0, vertex_offset=0, mesh=0)
+    return dict(W=W, H=H, tris=tris, materials=[flat_material()], meshes=[(draw["vertices"], draw["indices"])], passes=[dict(clear=True, draws=[draw])])
 
 
 def reference(scene):
@@ -312,6 +326,21 @@ def test_geometry_odd_size_33x17(gpu):
     got, rejected = run(gpu, scene)
     assert rejected == rej
     check("odd size 33x17", got, want)
+
+
+@pytest.mark.parametrize("W,H", [(192, 96), (193, 97)])
+def test_geometry_second_batch_and_large_list(gpu, W, H):
+    """What no other frame of this file reaches (none has more than six tiles; profiles/raster_shared.md lists each frame's load): a
+    record on the large list, its box touching all 18 or 28 tiles.  Beside it a bin of more than 256 records, walked in two batches,
+    which only the end-to-end frame has otherwise; at 193 x 97 with a last tile column and row one pixel wide.  No pixel is left out
+    of the comparison."""
+    scene, want, wins, rej = ref_of(("crowded", W, H), lambda: crowded_scene(W, H))
+    bins, large = R.tile_load(scene["tris"], W, H)
+    assert bins.max() > 256 and large >= 1 and bins[:, -1].max() >= 1 and bins[-1, :].max() >= 1
+    assert rej == 0 and (wins[0] >= 0).all() and len(np.unique(wins[0])) > 200      # nothing rejected, every pixel won, most triangles seen
+    got, rejected = run(gpu, scene)
+    assert rejected == 0                                                     # the counter does not move
+    check(f"crowded {W}x{H}", got, want)
 
 
 def test_geometry_replay_overlap_and_globals_snapshot(gpu):

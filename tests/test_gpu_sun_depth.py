@@ -185,6 +185,51 @@ def test_sun_depth_random_256(gpu):
     L.PBR_DestroySunDepthPass(sp)
 
 
+def test_sun_depth_second_batch_large_list_and_cut_edge_tiles_193x97(gpu):
+    """A 193 x 97 map (7 x 4 tiles, the last column and row one pixel wide) through the raw call sequence on a depth target of its own:
+    a triangle over the whole map (large list), 260 single-tile ones in one bin (a second batch of 256) and six across the right and
+    bottom edges.  The other maps of this file are square multiples of the tile; every texel is compared."""
+    import pbrhip
+    L = gpu
+    W, H = 193, 97
+    tris, depth = R.crowded_triangles(W, H)
+    bins, large = R.tile_load(tris, W, H)
+    assert bins.max() > 256 and large >= 1 and bins[:, -1].max() >= 1 and bins[-1, :].max() >= 1
+    m = len(tris)
+    pos = np.concatenate([tris.reshape(-1, 2), np.repeat(depth, 3)[:, None]], 1).astype(np.float32)
+    idx = np.arange(3 * m, dtype=np.uint32)
+    M = R.pixel_matrix(W, H)
+    want, rej = R.raster(np.ones((H, W), np.float32), pos, idx, [(3 * m, 1, 0, 0, M)])
+    assert rej == 0 and (want < 1).all()                                    # the reference rejects nothing and covers every texel
+    sp = L.PBR_MakeSunDepthPass(64)                                         # for its layout, descriptor set and Globals buffer
+    tex = pbrhip.make_texture(pbrhip.Format_D32F_Or_X8D24UN, W, H, pbrhip.TextureFlag_RenderTarget)
+    rd = pbrhip.GPU_RenderPassDesc()
+    rd.color_targets_count = 0; rd.width = W; rd.height = H; rd.depth_stencil_target = tex
+    rp = L.GPU_MakeRenderPass(C.byref(rd))
+    d, keep = _pipeline_desc(L, sp, render_pass=rp)
+    pipe = L.GPU_MakeGraphicsPipeline(C.byref(d))
+    assert pipe
+    _write_globals(L.PBR_SunDepthGlobalsBuffer(sp), _globals(M))
+    mesh = pbrhip.make_mesh(pos, idx, [(0, 3 * m)])
+    before = L.GPUX_RasterRejectedTriangles()
+    g = L.GPU_MakeGraph()
+    L.GPU_OpClearDepthStencil(g, tex, ALL)
+    L.GPU_OpPrepareRenderPass(g, rp)
+    p = L.GPU_OpPrepareDrawParams(g, pipe, L.PBR_SunDepthDescriptorSet(sp))
+    L.GPU_OpBeginRenderPass(g)
+    L.GPU_OpBindVertexBuffer(g, L.PBR_MeshVertexBuffer(mesh))
+    L.GPU_OpBindIndexBuffer(g, L.PBR_MeshIndexBuffer(mesh))
+    L.GPU_OpBindDrawParams(g, p)
+    L.GPU_OpDrawIndexed(g, 3 * m, 1, 0, 0, 0)
+    L.GPU_OpEndRenderPass(g)
+    L.GPU_GraphSubmit(g); L.GPU_GraphWait(g)
+    got = pbrhip.read_mip(tex, 0)[..., 0].copy()
+    assert L.GPUX_RasterRejectedTriangles() == before                       # the counter does not move
+    _check("crowded 193x97", got, want)
+    L.GPU_DestroyGraph(g); L.PBR_DestroyMesh(mesh); L.GPU_DestroyGraphicsPipeline(pipe); L.GPU_DestroyRenderPass(rp)
+    L.GPU_DestroyTexture(tex); L.PBR_DestroySunDepthPass(sp)
+
+
 def test_sun_depth_reference_frame_2048(gpu):
     """PBR_RecordSunDepthPass over synth_mesh_temple (~200k triangles, ~100 parts: one draw per part) at 2048^2, at the default
     sun angle (56.5, 97) and two others."""

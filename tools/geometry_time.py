@@ -54,14 +54,14 @@ for it in range(args.timed + 2):
             name = L.GPUX_GraphTimedOpName(g, i).decode()
             if name in per_op:
                 per_op[name].append(L.GPUX_GraphTimedOpMs(g, i))
-L.GPUX_EnableOpTiming(0)
 
-spans = []
+spans = []                                                                 # the span is recorded only while op timing is on
 for rep in range(args.graphs):
     for _ in range(args.passes):
         L.PBR_RecordGeometryPass(gp, g, mesh, None, C.byref(glob), None, None, 0)
     L.GPU_GraphSubmit(g); L.GPU_GraphWait(g)
     spans.append(L.GPUX_GraphSpanMs(g) / args.passes)
+L.GPUX_EnableOpTiming(0)
 cover = float((pbrhip.read_mip(gb.depth, 0)[..., 0] < 1).mean())
 
 setup, tiles, span = float(np.median(per_op["K13.setup"])), float(np.median(per_op["K13.tiles"])), float(np.median(spans))

@@ -89,8 +89,8 @@ struct GPU_GraphicsPipeline { GPU_PipelineLayout* layout; GPU_RenderPass* pass; 
                               uint32_t vertex_stride = 0; /* sun depth pass: bytes per vertex (gpu_vulkan.c:1745-1762) */ };
 
 enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster };
-// one GPU_OpDrawIndexed of the sun depth pass: job triangles [first_tri, first_tri + index_count / 3), matrix from the set's GLOBALS
-// (K13, the geometry pass: also the buffers bound at the draw and the pushed jitter pair -- the skybox rebinds both inside the pass)
+// one GPU_OpDrawIndexed of a raster job (K12 or K13): job triangles [first_tri, first_tri + index_count / 3), matrices from the set's
+// GLOBALS, the buffers bound at the draw and the pushed constants (K13 reads them: the skybox rebinds both inside the pass; K12 does not)
 struct RasterDraw { GPU_DescriptorSet* set; uint32_t first_tri, first_index, vertex_offset; BufferImpl* vb = nullptr; BufferImpl* ib = nullptr; float push[4] = {0, 0, 0, 0}; };
 struct Op {
     OpKind kind;
@@ -116,14 +116,21 @@ struct Op {
     bool folded = false;
     TextureImpl* blend_tex = nullptr; uint32_t blend_mip = 0;
     bool skip_level0 = false;                      // Op_Clear of all levels whose level 0 the next op overwrites entirely
-    // sun depth raster job (Op_Raster): every indexed draw of one render-pass instance; buf = vertices, buf2 = indices, tex = target
+    // raster job (Op_Raster, K12 or K13): the indexed draws of one render-pass instance; tex = depth target, buf = vertices and
+    // buf2 = indices of the job's first draw (K12 has one pair per job)
     std::vector<RasterDraw> draws;
     uint32_t tri_count = 0, vertex_stride = 0;
     int raster_slot = -1;                          // GPU_Graph::raster scratch of this job
 };
 struct DrawParams { GPU_GraphicsPipeline* pipeline; GPU_DescriptorSet* set; };
-// per raster job of a graph, kept across submissions: bins / records (device), the draw table (device + pinned staging)
+// per raster job (K12 or K13) of a graph, kept across submissions: bins / records (device), the draw table (device + pinned staging)
 struct RasterScratch { void* dev = nullptr; size_t dev_bytes = 0; void* draws_dev = nullptr; void* draws_host = nullptr; size_t draws_cap = 0; /* bytes */ };
+// what the two raster jobs differ in on the host, beside the kernel-specific halves of record_raster_draw, snapshot_raster_draws and exec_raster
+struct RasterKind { const char* op_name; const char* tag; const char* shader; const char* pass_name; GPU_CullMode cull; const char* cull_name; size_t draw_bytes; size_t (*scratch_bytes)(uint32_t, int, int); };
+static const RasterKind kSunDepthJob = {"K12.sun_depth", "K12", "sun_depth_pass.glsl", "sun depth", GPU_CullMode_TwoSided, "GPU_CullMode_TwoSided only", sizeof(PbrkRasterDraw), pbrk_raster_scratch_bytes};
+static const RasterKind kGeometryJob = {"K13.geometry", "K13", "geometry_pass.glsl", "geometry", GPU_CullMode_DrawCCW, "GPU_CullMode_DrawCCW only (render.cpp:232)", sizeof(PbrkGeoDraw), pbrk_geometry_scratch_bytes};
+static const RasterKind& raster_kind(KernelId k) { return k == Kernel_Geometry ? kGeometryJob : kSunDepthJob; }
+
 struct GPU_Graph {
     hipStream_t stream = nullptr;
     hipStream_t cur = nullptr;                     // stream the op being executed launches on (stream, or a side stream)
@@ -692,6 +699,24 @@ GPU_API GPU_RenderPass* GPU_MakeRenderPass(const GPU_RenderPassDesc* desc) {
 }
 GPU_API void GPU_DestroyRenderPass(GPU_RenderPass* rp) { delete rp; }
 
+// What both raster pipelines ask, in the order the checks have always had (K13 checks its colour targets between the two): the pass
+// covers its whole depth target (a texture has no zero extent, so width > 0 adds nothing to K12); depth test and write, the pass's
+// cull mode, nothing blended.
+static bool raster_target_ok(const GPU_GraphicsPipelineDesc* desc, const RasterKind& rk) {
+    const GPU_RenderPassDesc& rd = desc->render_pass->desc;
+    const GPU_Texture* dt = rd.depth_stencil_target;
+    GPU_REQUIRE(rd.width > 0 && rd.height > 0 && rd.width <= 16384 && rd.height <= 16384 && dt->width == rd.width && dt->height == rd.height && dt->layer_count == 1 && dt->depth == 1, false,
+                "GPU_MakeGraphicsPipeline: the %s pass must cover its whole 2-D depth target (at most 16384^2)", rk.pass_name);
+    return true;
+}
+static bool raster_state_ok(const GPU_GraphicsPipelineDesc* desc, const RasterKind& rk) {
+    GPU_REQUIRE(desc->enable_depth_test && desc->enable_depth_write, false, "GPU_MakeGraphicsPipeline: %s is implemented with depth test + depth write only", rk.shader);
+    GPU_REQUIRE(desc->cull_mode == rk.cull, false, "GPU_MakeGraphicsPipeline: %s is implemented for %s", rk.shader, rk.cull_name);
+    GPU_REQUIRE(!desc->enable_blending && !desc->enable_conservative_rasterization, false,
+                "GPU_MakeGraphicsPipeline: blending and conservative rasterisation are not implemented for %s", rk.shader);
+    return true;
+}
+
 GPU_API GPU_GraphicsPipeline* GPU_MakeGraphicsPipeline(const GPU_GraphicsPipelineDesc* desc) {
     GPU_REQUIRE(desc && desc->layout && desc->render_pass, nullptr, "GPU_MakeGraphicsPipeline: NULL argument");
     KernelId k = identify_shader(&desc->fs);
@@ -702,13 +727,7 @@ GPU_API GPU_GraphicsPipeline* GPU_MakeGraphicsPipeline(const GPU_GraphicsPipelin
         const GPU_Texture* dt = rd.depth_stencil_target;
         GPU_REQUIRE(dt && dt->format == GPU_Format_D32F_Or_X8D24UN && rd.color_targets_count == 0, nullptr,
                     "GPU_MakeGraphicsPipeline: sun_depth_pass.glsl needs a render pass with a D32F depth target and no colour targets (render.cpp:725-729)");
-        GPU_REQUIRE(dt->layer_count == 1 && dt->depth == 1 && rd.width == dt->width && rd.height == dt->height && dt->width <= 16384 && dt->height <= 16384, nullptr,
-                    "GPU_MakeGraphicsPipeline: the sun depth pass must cover its whole 2-D depth target (at most 16384^2)");
-        GPU_REQUIRE(desc->enable_depth_test && desc->enable_depth_write, nullptr,
-                    "GPU_MakeGraphicsPipeline: sun_depth_pass.glsl is implemented with depth test + depth write only");
-        GPU_REQUIRE(desc->cull_mode == GPU_CullMode_TwoSided, nullptr, "GPU_MakeGraphicsPipeline: sun_depth_pass.glsl is implemented for GPU_CullMode_TwoSided only");
-        GPU_REQUIRE(!desc->enable_blending && !desc->enable_conservative_rasterization, nullptr,
-                    "GPU_MakeGraphicsPipeline: blending and conservative rasterisation are not implemented for sun_depth_pass.glsl");
+        if (!raster_target_ok(desc, kSunDepthJob) || !raster_state_ok(desc, kSunDepthJob)) return nullptr;
         GPU_REQUIRE(desc->vertex_input_formats && desc->vertex_input_formats_count > 0 && desc->vertex_input_formats[0] == GPU_Format_RGB32F, nullptr,
                     "GPU_MakeGraphicsPipeline: sun_depth_pass.glsl reads an RGB32F position as its first vertex attribute");
         uint32_t stride = 0;
@@ -728,18 +747,14 @@ GPU_API GPU_GraphicsPipeline* GPU_MakeGraphicsPipeline(const GPU_GraphicsPipelin
         const GPU_Texture* dt = rd.depth_stencil_target;
         GPU_REQUIRE(rd.color_targets_count == 5 && dt && dt->format == GPU_Format_D32F_Or_X8D24UN, nullptr,
                     "GPU_MakeGraphicsPipeline: geometry_pass.glsl needs a render pass with five colour targets and a D32F depth target (render.cpp:700-708)");
-        GPU_REQUIRE(rd.width > 0 && rd.height > 0 && rd.width <= 16384 && rd.height <= 16384 && dt->width == rd.width && dt->height == rd.height && dt->layer_count == 1 && dt->depth == 1, nullptr,
-                    "GPU_MakeGraphicsPipeline: the geometry pass must cover its whole 2-D depth target (at most 16384^2)");
+        if (!raster_target_ok(desc, kGeometryJob)) return nullptr;
         for (uint32_t i = 0; i < 5; ++i) {
             const GPU_Texture* ct = desc->render_pass->targets[i].texture;
             GPU_REQUIRE(ct && desc->render_pass->targets[i].mip_level == 0 && ct->format == (i < 4 ? GPU_Format_RGBA8UN : GPU_Format_RG16F) &&
                         ct->width == rd.width && ct->height == rd.height && ct->layer_count == 1 && ct->depth == 1, nullptr,
                         "GPU_MakeGraphicsPipeline: geometry pass colour target %u must be a %ux%u 2D %s texture (render.cpp:680-691)", i, rd.width, rd.height, i < 4 ? "RGBA8UN" : "RG16F");
         }
-        GPU_REQUIRE(desc->enable_depth_test && desc->enable_depth_write, nullptr, "GPU_MakeGraphicsPipeline: geometry_pass.glsl is implemented with depth test + depth write only");
-        GPU_REQUIRE(desc->cull_mode == GPU_CullMode_DrawCCW, nullptr, "GPU_MakeGraphicsPipeline: geometry_pass.glsl is implemented for GPU_CullMode_DrawCCW only (render.cpp:232)");
-        GPU_REQUIRE(!desc->enable_blending && !desc->enable_conservative_rasterization, nullptr,
-                    "GPU_MakeGraphicsPipeline: blending and conservative rasterisation are not implemented for geometry_pass.glsl");
+        if (!raster_state_ok(desc, kGeometryJob)) return nullptr;
         GPU_REQUIRE(desc->vertex_input_formats && desc->vertex_input_formats_count == 4 && desc->vertex_input_formats[0] == GPU_Format_RGB32F &&
                     desc->vertex_input_formats[1] == GPU_Format_RGB32F && desc->vertex_input_formats[2] == GPU_Format_RGB32F && desc->vertex_input_formats[3] == GPU_Format_RG32F, nullptr,
                     "GPU_MakeGraphicsPipeline: geometry_pass.glsl reads the 44-byte Vertex (RGB32F x3, RG32F; render.cpp:227)");
@@ -1134,25 +1149,25 @@ GPU_API void GPU_OpDraw(GPU_Graph* g, uint32_t vertex_count, uint32_t instance_c
     record_shade(g, 0, 0, false, __func__);
 }
 GPU_API void GPUX_OpDrawRows(GPU_Graph* g, uint32_t row0, uint32_t row1) { REC_GUARD(g); record_shade(g, row0, row1, true, __func__); }
-// ---- K12: indexed draws of the sun depth pass (render.cpp:993-1020) ----
-// The draws of one render-pass instance are ONE raster job (one Op_Raster): the result is a per-pixel minimum, so merging them is
-// exact, and one setup + one tile launch replace hundreds of per-part launches.  A job is closed (its scratch sized from the known
-// triangle count, no read-back) at GPU_OpEndRenderPass, or when the pass binds another vertex / index buffer pair.
+// ---- raster jobs: the indexed draws of the sun depth pass (K12, render.cpp:993-1020) and of the geometry pass (K13, :1076-1115) ----
+// The draws of one render-pass instance are ONE raster job (one Op_Raster): the result does not depend on triangle order (K12: a
+// per-pixel minimum; K13: depth, then triangle number), so merging them is exact, and one setup + one tile launch replace hundreds of
+// per-part launches.  A job is closed (its scratch sized from the known triangle count, no read-back) at GPU_OpEndRenderPass, or,
+// for K12, when the pass binds another vertex / index buffer pair: K13's draws name their own buffers, K12's share the job's.
 static void close_raster_job(GPU_Graph* g) {
     if (g->raster_op < 0) return;
     Op& op = g->ops[(size_t)g->raster_op];
     g->raster_op = -1;
     if ((size_t)op.raster_slot >= g->raster.size()) g->raster.resize((size_t)op.raster_slot + 1);
     RasterScratch& rs = g->raster[(size_t)op.raster_slot];
-    const int W = (int)op.tex->base.width, H = (int)op.tex->base.height;
-    const bool geo = op.gpipe->kernel == Kernel_Geometry;
-    const size_t need = geo ? pbrk_geometry_scratch_bytes(op.tri_count, W, H) : pbrk_raster_scratch_bytes(op.tri_count, W, H);
+    const RasterKind& rk = raster_kind(op.gpipe->kernel);
+    const size_t need = rk.scratch_bytes(op.tri_count, (int)op.tex->base.width, (int)op.tex->base.height);
     bool ok = true;
     if (rs.dev_bytes < need) {
         (void)hipFree(rs.dev); rs.dev = nullptr; rs.dev_bytes = 0;
         if (hipMalloc(&rs.dev, need) == hipSuccess) rs.dev_bytes = need; else { rs.dev = nullptr; ok = false; }
     }
-    const size_t table = op.draws.size() * (geo ? sizeof(PbrkGeoDraw) : sizeof(PbrkRasterDraw));
+    const size_t table = op.draws.size() * rk.draw_bytes;
     if (ok && rs.draws_cap < table) {
         (void)hipFree(rs.draws_dev); (void)hipHostFree(rs.draws_host); rs.draws_dev = nullptr; rs.draws_host = nullptr; rs.draws_cap = 0;
         if (hipMalloc(&rs.draws_dev, table) == hipSuccess && hipHostMalloc((void**)&rs.draws_host, table, hipHostMallocDefault) == hipSuccess) rs.draws_cap = table;
@@ -1164,43 +1179,52 @@ static void close_raster_job(GPU_Graph* g) {
     if (!ok) { (void)hipGetLastError(); op.tri_count = 0; op.draws.clear(); gpu_fail("GPU_OpEndRenderPass: allocation of the raster scratch (%zu bytes) failed", need); }
 }
 
-// K13: one indexed draw of the geometry pass.  All draws of a render-pass instance are one job whatever buffers and textures they
-// bind: each draw records its own.  Everything a launch could trip over is checked here.
-static void record_geometry_draw(GPU_Graph* g, const DrawParams& dp, uint32_t index_count, uint32_t instance_count, uint32_t first_index, uint32_t vertex_offset) {
+// One indexed draw of a raster job.  Everything a launch could trip over is checked here.
+static void record_raster_draw(GPU_Graph* g, const DrawParams& dp, uint32_t index_count, uint32_t instance_count, uint32_t first_index, uint32_t vertex_offset) {
     const char* fn = "GPU_OpDrawIndexed";
+    const bool geo = dp.pipeline->kernel == Kernel_Geometry;
+    const RasterKind& rk = raster_kind(dp.pipeline->kernel);
     GPU_REQUIRE_V(dp.pipeline->pass == g->in_pass, "%s: pipeline was created for a different render pass", fn);
     GPU_REQUIRE_V(dp.set->layout == dp.pipeline->layout, "%s: descriptor set and pipeline use different layouts", fn);
     Slot* gl = named_slot(dp.set, "GLOBALS");
-    GPU_REQUIRE_V(gl && gl->buf && gl->buf->base.size >= 512, "%s: \"GLOBALS\" must be a buffer that holds old_clip_space_from_world (render.h:122-136)", fn);
-    for (const char* name : {"TEX0", "TEX1", "TEX_ORM", "TEX_EMISSIVE"}) {
-        Slot* sl = named_slot(dp.set, name);
-        GPU_REQUIRE_V(sl && sl->tex, "%s: geometry pass: \"%s\" is not bound", fn, name);
-        GPU_REQUIRE_V(sl->tex->base.format == GPU_Format_RGBA8UN && sl->tex->base.layer_count == 1 && sl->tex->base.depth == 1 && sl->whole,
-                      "%s: geometry pass: \"%s\" must be a whole 2D RGBA8UN texture", fn, name);
+    if (geo) {
+        GPU_REQUIRE_V(gl && gl->buf && gl->buf->base.size >= 512, "%s: \"GLOBALS\" must be a buffer that holds old_clip_space_from_world (render.h:122-136)", fn);
+        for (const char* name : {"TEX0", "TEX1", "TEX_ORM", "TEX_EMISSIVE"}) {
+            Slot* sl = named_slot(dp.set, name);
+            GPU_REQUIRE_V(sl && sl->tex, "%s: geometry pass: \"%s\" is not bound", fn, name);
+            GPU_REQUIRE_V(sl->tex->base.format == GPU_Format_RGBA8UN && sl->tex->base.layer_count == 1 && sl->tex->base.depth == 1 && sl->whole,
+                          "%s: geometry pass: \"%s\" must be a whole 2D RGBA8UN texture", fn, name);
+        }
+        Slot* sm = named_slot(dp.set, "SAMPLER_LINEAR_WRAP");
+        GPU_REQUIRE_V(sm && sm->sampler == &G.samplers[0], "%s: geometry pass: \"SAMPLER_LINEAR_WRAP\" must be GPU_SamplerLinearWrap()", fn);
+        GPU_REQUIRE_V(g->push_size == 16, "%s: the geometry pass needs its 16-byte push constants (taa_jitter, taa_jitter_prev; render.cpp:1091-1094)", fn);
+    } else {
+        GPU_REQUIRE_V(gl && gl->buf && gl->buf->base.size >= 448, "%s: \"GLOBALS\" must be a buffer that holds sun_space_from_world (render.h:122-136)", fn);
     }
-    Slot* sm = named_slot(dp.set, "SAMPLER_LINEAR_WRAP");
-    GPU_REQUIRE_V(sm && sm->sampler == &G.samplers[0], "%s: geometry pass: \"SAMPLER_LINEAR_WRAP\" must be GPU_SamplerLinearWrap()", fn);
-    GPU_REQUIRE_V(g->push_size == 16, "%s: the geometry pass needs its 16-byte push constants (taa_jitter, taa_jitter_prev; render.cpp:1091-1094)", fn);
     GPU_REQUIRE_V(g->vertex_buffer, "%s: no vertex buffer bound (GPU_OpBindVertexBuffer)", fn);
     GPU_REQUIRE_V(g->index_buffer, "%s: no index buffer bound (GPU_OpBindIndexBuffer)", fn);
-    const uint64_t n_idx = g->index_buffer->base.size / 4;
+    const uint64_t n_idx = g->index_buffer->base.size / 4;                    // 32-bit indices (gpu_vulkan.c:2591-2593)
     GPU_REQUIRE_V((uint64_t)first_index + index_count <= n_idx, "%s: indices [%u, %llu) lie outside the bound index buffer (%llu indices)", fn,
                   first_index, (unsigned long long)first_index + index_count, (unsigned long long)n_idx);
-    const uint32_t tris = index_count / 3;
-    if (tris == 0 || instance_count == 0) return;
+    const uint32_t tris = index_count / 3;                                    // whole triangles only
+    if (tris == 0 || instance_count == 0) return;                             // any instance count > 0 draws the same triangles once
+    if (!geo && g->raster_op >= 0) {
+        const Op& cur = g->ops[(size_t)g->raster_op];
+        if (cur.buf != g->vertex_buffer || cur.buf2 != g->index_buffer || cur.vertex_stride != dp.pipeline->vertex_stride) close_raster_job(g);
+    }
     if (g->raster_op < 0) {
-        Op op; op.kind = Op_Raster; op.name = "K13.geometry";
+        Op op; op.kind = Op_Raster; op.name = rk.op_name;
         op.pass = g->in_pass; op.gpipe = dp.pipeline;
         op.tex = (TextureImpl*)g->in_pass->desc.depth_stencil_target;
-        op.vertex_stride = 44;
+        op.buf = g->vertex_buffer; op.buf2 = g->index_buffer; op.vertex_stride = dp.pipeline->vertex_stride;
         op.raster_slot = (int)g->raster_used++;
         g->ops.push_back(op);
         g->raster_op = (int)g->ops.size() - 1;
     }
     Op& op = g->ops[(size_t)g->raster_op];
-    GPU_REQUIRE_V((uint64_t)op.tri_count + tris <= (1u << 26), "%s: more than 2^26 triangles in one geometry pass", fn);
+    GPU_REQUIRE_V((uint64_t)op.tri_count + tris <= (1u << 26), "%s: more than 2^26 triangles in one %s pass", fn, rk.pass_name);
     RasterDraw d; d.set = dp.set; d.first_tri = op.tri_count; d.first_index = first_index; d.vertex_offset = vertex_offset;
-    d.vb = g->vertex_buffer; d.ib = g->index_buffer; memcpy(d.push, g->push, 16);
+    d.vb = g->vertex_buffer; d.ib = g->index_buffer; memcpy(d.push, g->push, sizeof d.push);
     op.draws.push_back(d);
     op.tri_count += tris;
 }
@@ -1211,37 +1235,7 @@ GPU_API void GPU_OpDrawIndexed(GPU_Graph* g, uint32_t index_count, uint32_t inst
     GPU_REQUIRE_V(g->in_pass && g->bound_draw >= 0 && (g->draw_params[(size_t)g->bound_draw].pipeline->kernel == Kernel_SunDepth ||
                                                        g->draw_params[(size_t)g->bound_draw].pipeline->kernel == Kernel_Geometry),
                   "GPU_OpDrawIndexed: unsupported (raster): only the sun depth pass (sun_depth_pass.glsl) and the geometry pass (geometry_pass.glsl) draw indexed triangles");
-    const DrawParams dp = g->draw_params[(size_t)g->bound_draw];
-    if (dp.pipeline->kernel == Kernel_Geometry) { record_geometry_draw(g, dp, index_count, instance_count, first_index, vertex_offset); return; }
-    GPU_REQUIRE_V(dp.pipeline->pass == g->in_pass, "GPU_OpDrawIndexed: pipeline was created for a different render pass");
-    GPU_REQUIRE_V(dp.set->layout == dp.pipeline->layout, "GPU_OpDrawIndexed: descriptor set and pipeline use different layouts");
-    Slot* gl = named_slot(dp.set, "GLOBALS");
-    GPU_REQUIRE_V(gl && gl->buf && gl->buf->base.size >= 448, "GPU_OpDrawIndexed: \"GLOBALS\" must be a buffer that holds sun_space_from_world (render.h:122-136)");
-    GPU_REQUIRE_V(g->vertex_buffer, "GPU_OpDrawIndexed: no vertex buffer bound (GPU_OpBindVertexBuffer)");
-    GPU_REQUIRE_V(g->index_buffer, "GPU_OpDrawIndexed: no index buffer bound (GPU_OpBindIndexBuffer)");
-    const uint64_t n_idx = g->index_buffer->base.size / 4;                    // 32-bit indices (gpu_vulkan.c:2591-2593)
-    GPU_REQUIRE_V((uint64_t)first_index + index_count <= n_idx, "GPU_OpDrawIndexed: indices [%u, %llu) lie outside the bound index buffer (%llu indices)",
-                  first_index, (unsigned long long)first_index + index_count, (unsigned long long)n_idx);
-    const uint32_t tris = index_count / 3;                                    // whole triangles only
-    if (tris == 0 || instance_count == 0) return;                             // any instance count > 0 draws the same triangles once
-    if (g->raster_op >= 0) {
-        const Op& cur = g->ops[(size_t)g->raster_op];
-        if (cur.buf != g->vertex_buffer || cur.buf2 != g->index_buffer || cur.vertex_stride != dp.pipeline->vertex_stride) close_raster_job(g);
-    }
-    if (g->raster_op < 0) {
-        Op op; op.kind = Op_Raster; op.name = "K12.sun_depth";
-        op.pass = g->in_pass; op.gpipe = dp.pipeline;
-        op.tex = (TextureImpl*)g->in_pass->desc.depth_stencil_target;
-        op.buf = g->vertex_buffer; op.buf2 = g->index_buffer; op.vertex_stride = dp.pipeline->vertex_stride;
-        op.raster_slot = (int)g->raster_used++;
-        g->ops.push_back(op);
-        g->raster_op = (int)g->ops.size() - 1;
-    }
-    Op& op = g->ops[(size_t)g->raster_op];
-    GPU_REQUIRE_V((uint64_t)op.tri_count + tris <= (1u << 26), "GPU_OpDrawIndexed: more than 2^26 triangles in one sun depth pass");
-    RasterDraw rd; rd.set = dp.set; rd.first_tri = op.tri_count; rd.first_index = first_index; rd.vertex_offset = vertex_offset;
-    op.draws.push_back(rd);
-    op.tri_count += tris;
+    record_raster_draw(g, g->draw_params[(size_t)g->bound_draw], index_count, instance_count, first_index, vertex_offset);
 }
 GPU_API void GPU_OpBindVertexBuffer(GPU_Graph* g, GPU_Buffer* b) {
     REC_GUARD(g);
@@ -1496,6 +1490,47 @@ static void publish_side_work(GPU_Graph* g) {
     for (hipStream_t s : g->side) if (s != g->cur) HIP_OK(hipStreamWaitEvent(s, e, 0));
 }
 
+// Globals as they are at submit time: the caller fills the persistently mapped buffer before GPU_GraphSubmit (render.cpp:991)
+static void read_globals(const BufferImpl* buf, size_t offset, void* dst, size_t bytes) {
+    if (buf->pinned_host) memcpy(dst, (const char*)buf->dev + offset, bytes);
+    else HIP_OK(hipMemcpy(dst, (const char*)buf->dev + offset, bytes, hipMemcpyDeviceToHost));
+}
+
+// A raster job: upload the draw table that GPU_GraphSubmit snapshotted, setup (transform, bin), tiles
+static void exec_raster(GPU_Graph* g, Op& op, size_t& ev_used) {
+    if (!op.tri_count) return;
+    hipStream_t st = g->cur;
+    RasterScratch& rs = g->raster[(size_t)op.raster_slot];
+    const RasterKind& rk = raster_kind(op.gpipe->kernel);
+    const bool geo = op.gpipe->kernel == Kernel_Geometry;
+    PbrkRasterArgs sa;
+    PbrkGeometryArgs ga;
+    if (geo) {
+        ga.draws = (const PbrkGeoDraw*)rs.draws_dev; ga.draw_count = (uint32_t)op.draws.size(); ga.tri_count = op.tri_count;
+        for (int k = 0; k < 4; ++k) ga.color[k] = ((TextureImpl*)op.pass->targets[(size_t)k].texture)->dev;
+        ga.velocity = ((TextureImpl*)op.pass->targets[4].texture)->dev;
+        ga.depth = (float*)op.tex->dev; ga.width = (int)op.tex->base.width; ga.height = (int)op.tex->base.height;
+        ga.scratch = rs.dev; ga.rejected = G.raster_rejected;
+    } else {
+        sa.vertices = op.buf->dev; sa.vertex_stride = op.vertex_stride; sa.vertex_count = op.buf->base.size / op.vertex_stride;
+        sa.indices = (const uint32_t*)op.buf2->dev;
+        sa.draws = (const PbrkRasterDraw*)rs.draws_dev; sa.draw_count = (uint32_t)op.draws.size(); sa.tri_count = op.tri_count;
+        sa.depth = (float*)op.tex->dev; sa.width = (int)op.tex->base.width; sa.height = (int)op.tex->base.height;
+        sa.scratch = rs.dev; sa.rejected = G.raster_rejected;
+    }
+    timed(g, std::string(rk.tag) + ".setup", ev_used, [&] {
+        HIP_OK(hipMemcpyAsync(rs.draws_dev, rs.draws_host, op.draws.size() * rk.draw_bytes, hipMemcpyHostToDevice, st));
+        int rc = geo ? pbrk_geometry_setup(&ga, st) : pbrk_raster_setup(&sa, st);
+        if (rc != PBRK_OK) gpu_fail("%s setup launch failed (%d)", rk.tag, rc);
+    });
+    timed(g, std::string(rk.tag) + ".tiles", ev_used, [&] {
+        int rc = geo ? pbrk_geometry_tiles(&ga, st) : pbrk_raster_tiles(&sa, st);
+        if (rc != PBRK_OK) gpu_fail("%s tile launch failed (%d)", rk.tag, rc);
+    });
+    for (const GPU_TextureView& tv : op.pass->targets) { ((TextureImpl*)tv.texture)->bordered_valid = false; ((TextureImpl*)tv.texture)->lut_cells_valid = false; }
+    op.tex->bordered_valid = false;
+}
+
 static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
     hipStream_t st = g->cur;
     switch (op.kind) {
@@ -1696,10 +1731,7 @@ static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
         }
         a.out = target->dev;
         a.out_format = target->base.format == GPU_Format_RGBA16F ? PBRK_FMT_RGBA16F : PBRK_FMT_RGBA32F;
-        BufferImpl* gb = named_slot(s, "GLOBALS")->buf;
-        // Globals snapshot at submit time: the caller fills the persistently mapped buffer before GPU_GraphSubmit (render.cpp:991)
-        if (gb->pinned_host) memcpy(a.globals, gb->dev, 552);
-        else HIP_OK(hipMemcpy(a.globals, gb->dev, 552, hipMemcpyDeviceToHost));
+        read_globals(named_slot(s, "GLOBALS")->buf, 0, a.globals, 552);
         timed(g, "K5.shade", ev_used, [&] {
             int rc = pbrk_shade(&a, st);
             if (rc != PBRK_OK) gpu_fail("K5 launch failed (%d)", rc);
@@ -1707,47 +1739,7 @@ static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
         target->bordered_valid = false;
         return;
     }
-    case Op_Raster: {
-        if (!op.tri_count) return;
-        RasterScratch& rs = g->raster[(size_t)op.raster_slot];             // draw table snapshotted by GPU_GraphSubmit
-        if (op.gpipe->kernel == Kernel_Geometry) {
-            PbrkGeometryArgs a;
-            a.draws = (const PbrkGeoDraw*)rs.draws_dev; a.draw_count = (uint32_t)op.draws.size(); a.tri_count = op.tri_count;
-            for (int k = 0; k < 4; ++k) a.color[k] = ((TextureImpl*)op.pass->targets[(size_t)k].texture)->dev;
-            a.velocity = ((TextureImpl*)op.pass->targets[4].texture)->dev;
-            a.depth = (float*)op.tex->dev; a.width = (int)op.tex->base.width; a.height = (int)op.tex->base.height;
-            a.scratch = rs.dev; a.rejected = G.raster_rejected;
-            timed(g, "K13.setup", ev_used, [&] {
-                HIP_OK(hipMemcpyAsync(rs.draws_dev, rs.draws_host, op.draws.size() * sizeof(PbrkGeoDraw), hipMemcpyHostToDevice, st));
-                int rc = pbrk_geometry_setup(&a, st);
-                if (rc != PBRK_OK) gpu_fail("K13 setup launch failed (%d)", rc);
-            });
-            timed(g, "K13.tiles", ev_used, [&] {
-                int rc = pbrk_geometry_tiles(&a, st);
-                if (rc != PBRK_OK) gpu_fail("K13 tile launch failed (%d)", rc);
-            });
-            for (const GPU_TextureView& tv : op.pass->targets) { ((TextureImpl*)tv.texture)->bordered_valid = false; ((TextureImpl*)tv.texture)->lut_cells_valid = false; }
-            op.tex->bordered_valid = false;
-            return;
-        }
-        PbrkRasterArgs a;
-        a.vertices = op.buf->dev; a.vertex_stride = op.vertex_stride; a.vertex_count = op.buf->base.size / op.vertex_stride;
-        a.indices = (const uint32_t*)op.buf2->dev;
-        a.draws = (const PbrkRasterDraw*)rs.draws_dev; a.draw_count = (uint32_t)op.draws.size(); a.tri_count = op.tri_count;
-        a.depth = (float*)op.tex->dev; a.width = (int)op.tex->base.width; a.height = (int)op.tex->base.height;
-        a.scratch = rs.dev; a.rejected = G.raster_rejected;
-        timed(g, "K12.setup", ev_used, [&] {
-            HIP_OK(hipMemcpyAsync(rs.draws_dev, rs.draws_host, op.draws.size() * sizeof(PbrkRasterDraw), hipMemcpyHostToDevice, st));
-            int rc = pbrk_raster_setup(&a, st);
-            if (rc != PBRK_OK) gpu_fail("K12 setup launch failed (%d)", rc);
-        });
-        timed(g, "K12.tiles", ev_used, [&] {
-            int rc = pbrk_raster_tiles(&a, st);
-            if (rc != PBRK_OK) gpu_fail("K12 tile launch failed (%d)", rc);
-        });
-        op.tex->bordered_valid = false;
-        return;
-    }
+    case Op_Raster: exec_raster(g, op, ev_used); return;
     case Op_MipGen: {
         timed(g, op.name, ev_used, [&] {
             int rc = is_rgba8_pow2(op.tex) ? pbrk_mip_chain_rgba8(op.tex->dev, (int)op.tex->base.width, (int)op.tex->base.height, (int)op.tex->base.mip_level_count, st)
@@ -2000,44 +1992,45 @@ GPU_API void GPUX_SetGraphOverlap(int on) { g_overlap_on = on; }
 GPU_API uint64_t GPUX_OverlappedSubmitCount(void) { return g_overlapped_submits; }
 static bool contains(const std::vector<TextureImpl*>& v, const TextureImpl* t) { for (const TextureImpl* x : v) if (x == t) return true; return false; }
 
+// The draw tables of the raster jobs, filled from what every draw's GLOBALS holds now (the caller fills the mapped Globals before
+// submitting, render.cpp:991), before anything is launched.
+static bool fill_sun_draw(const RasterDraw& d, PbrkRasterDraw& o) {
+    read_globals(named_slot(d.set, "GLOBALS")->buf, 384, o.m, 64);           // render.h:129: sun_space_from_world
+    // an orthographic matrix (last row (0, 0, 0, c > 0)) needs no near-plane clip
+    GPU_REQUIRE(o.m[3] == 0.0f && o.m[7] == 0.0f && o.m[11] == 0.0f && o.m[15] > 0.0f, false,
+                "GPU_GraphSubmit: perspective sun projection not implemented (sun_space_from_world's last row must be (0, 0, 0, c > 0))");
+    o.first_tri = d.first_tri; o.first_index = d.first_index; o.vertex_offset = d.vertex_offset; o.pad = 0;
+    return true;
+}
+static bool fill_geo_draw(const RasterDraw& d, PbrkGeoDraw& o) {          // both matrices, the draw's textures and buffers
+    memset(&o, 0, sizeof o);
+    const BufferImpl* gb = named_slot(d.set, "GLOBALS")->buf;
+    read_globals(gb, 0, o.m, 64); read_globals(gb, 448, o.m_old, 64);      // render.h:123, :130
+    memcpy(o.jitter, d.push, 8); memcpy(o.jitter_prev, d.push + 2, 8);
+    static const char* const names[4] = {"TEX0", "TEX1", "TEX_ORM", "TEX_EMISSIVE"};
+    for (int k = 0; k < 4; ++k) {
+        const TextureImpl* t = named_slot(d.set, names[k])->tex;
+        o.tex[k].texels = t->dev; o.tex[k].width = (int)t->base.width; o.tex[k].height = (int)t->base.height; o.tex[k].levels = (int)t->base.mip_level_count;
+    }
+    o.vertices = d.vb->dev; o.indices = (const uint32_t*)d.ib->dev; o.vertex_count = d.vb->base.size / 44u;
+    o.first_tri = d.first_tri; o.first_index = d.first_index; o.vertex_offset = d.vertex_offset;
+    return true;
+}
+static bool snapshot_raster_draws(GPU_Graph* g) {
+    for (const Op& op : g->ops) {
+        if (op.kind != Op_Raster || !op.tri_count) continue;
+        void* table = g->raster[(size_t)op.raster_slot].draws_host;
+        const bool geo = op.gpipe->kernel == Kernel_Geometry;
+        for (size_t i = 0; i < op.draws.size(); ++i)
+            if (!(geo ? fill_geo_draw(op.draws[i], ((PbrkGeoDraw*)table)[i]) : fill_sun_draw(op.draws[i], ((PbrkRasterDraw*)table)[i]))) return false;
+    }
+    return true;
+}
+
 GPU_API void GPU_GraphSubmit(GPU_Graph* g) {
     GPU_REQUIRE_V(g && !g->submitted, "GPU_GraphSubmit: graph is NULL or already submitted");
     GPU_REQUIRE_V(g->in_pass == nullptr && g->preparing == nullptr, "GPU_GraphSubmit: render pass still open");
-    // K12: snapshot every sun depth draw's sun_space_from_world (the caller fills the mapped Globals before submitting, render.cpp:991)
-    // into the job's draw table, before anything is launched: an orthographic matrix (last row (0, 0, 0, c > 0)) needs no near-plane clip
-    for (const Op& op : g->ops) {
-        if (op.kind != Op_Raster || !op.tri_count) continue;
-        RasterScratch& rs = g->raster[(size_t)op.raster_slot];
-        if (op.gpipe->kernel == Kernel_Geometry) {                           // K13: both matrices, the draw's textures and buffers
-            for (size_t i = 0; i < op.draws.size(); ++i) {
-                const RasterDraw& d = op.draws[i];
-                BufferImpl* gb = named_slot(d.set, "GLOBALS")->buf;
-                PbrkGeoDraw& o = ((PbrkGeoDraw*)rs.draws_host)[i];
-                memset(&o, 0, sizeof o);
-                if (gb->pinned_host) { memcpy(o.m, gb->dev, 64); memcpy(o.m_old, (const char*)gb->dev + 448, 64); }      // render.h:123, :130
-                else { HIP_OK(hipMemcpy(o.m, gb->dev, 64, hipMemcpyDeviceToHost)); HIP_OK(hipMemcpy(o.m_old, (const char*)gb->dev + 448, 64, hipMemcpyDeviceToHost)); }
-                memcpy(o.jitter, d.push, 8); memcpy(o.jitter_prev, d.push + 2, 8);
-                static const char* const names[4] = {"TEX0", "TEX1", "TEX_ORM", "TEX_EMISSIVE"};
-                for (int k = 0; k < 4; ++k) {
-                    const TextureImpl* t = named_slot(d.set, names[k])->tex;
-                    o.tex[k].texels = t->dev; o.tex[k].width = (int)t->base.width; o.tex[k].height = (int)t->base.height; o.tex[k].levels = (int)t->base.mip_level_count;
-                }
-                o.vertices = d.vb->dev; o.indices = (const uint32_t*)d.ib->dev; o.vertex_count = d.vb->base.size / 44u;
-                o.first_tri = d.first_tri; o.first_index = d.first_index; o.vertex_offset = d.vertex_offset;
-            }
-            continue;
-        }
-        for (size_t i = 0; i < op.draws.size(); ++i) {
-            const RasterDraw& d = op.draws[i];
-            BufferImpl* gb = named_slot(d.set, "GLOBALS")->buf;
-            PbrkRasterDraw& o = ((PbrkRasterDraw*)rs.draws_host)[i];
-            if (gb->pinned_host) memcpy(o.m, (const char*)gb->dev + 384, 64);        // render.h:129: sun_space_from_world
-            else HIP_OK(hipMemcpy(o.m, (const char*)gb->dev + 384, 64, hipMemcpyDeviceToHost));
-            GPU_REQUIRE_V(o.m[3] == 0.0f && o.m[7] == 0.0f && o.m[11] == 0.0f && o.m[15] > 0.0f,
-                          "GPU_GraphSubmit: perspective sun projection not implemented (sun_space_from_world's last row must be (0, 0, 0, c > 0))");
-            o.first_tri = d.first_tri; o.first_index = d.first_index; o.vertex_offset = d.vertex_offset; o.pad = 0;
-        }
-    }
+    if (!snapshot_raster_draws(g)) return;
     g->timed_names.clear(); g->timed_ms.clear();
     size_t ev_used = 0;
     g->sync_used = 0;

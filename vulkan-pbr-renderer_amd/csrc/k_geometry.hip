@@ -1,5 +1,6 @@
 // k_geometry.hip -- K13: the geometry pass, shaders/geometry_pass.glsl (render.cpp:1076-1115), as a compute rasteriser on K12's
-// structure (raster_bins.h).  The rules live in geometry_core.h; this file is the machinery around them:
+// structure.  The rules live in geometry_core.h, the raster-job machinery shared with K12 (record, pixel box, draw
+// lookup, counting, scan, fill, pre-filter, batch loop, launch sequence) in raster_bins.h; this file is what is K13's own:
 //   * setup (one thread per source triangle): vertex stage, clip, fan, snap (geo_setup) -> one attribute record and up to six
 //     coverage records (slots 6 t .. 6 t + 5; unused ones cover nothing), each counted into the tiles its pixel box touches;
 //   * scan and fill: K12's, over the 6 n coverage records;
@@ -26,12 +27,8 @@ __global__ __launch_bounds__(kThreads) void k_geo_setup(PbrkGeometryArgs a, Layo
     bool rejected = false;
     char* scratch = (char*)a.scratch;
     if (t < a.tri_count) {
-        int lo = 0, hi = (int)a.draw_count - 1;                   // last draw with first_tri <= t
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (a.draws[mid].first_tri <= t) lo = mid; else hi = mid - 1;
-        }
-        const PbrkGeoDraw& d = a.draws[lo];
+        const int di = find_draw(a.draws, a.draw_count, t);
+        const PbrkGeoDraw& d = a.draws[di];
         const uint32_t* ix = d.indices + (size_t)d.first_index + 3 * (size_t)(t - d.first_tri);   // in range: checked at record time
         const float* v[3] = {nullptr, nullptr, nullptr};
         bool ok = true;
@@ -45,98 +42,22 @@ __global__ __launch_bounds__(kThreads) void k_geo_setup(PbrkGeometryArgs a, Layo
         if (ok) {
             GeoAttr A;
             n = geo_setup(d, v[0], v[1], v[2], a.width, a.height, A, cov);
-            if (n > 0) { A.draw = (uint32_t)lo; ((GeoAttr*)(scratch + L.extra))[t] = A; }
+            if (n > 0) { A.draw = (uint32_t)di; ((GeoAttr*)(scratch + L.extra))[t] = A; }
         }
         rejected = !ok || n < 0;
-        unsigned* cnt = (unsigned*)(scratch + L.cnt);
         for (int k = 0; k < kFan; ++k) {
-            // the record as its four 16-B words (TriRec's layout): x0 y0 x1 y1 | x2 y2 (bx0, by0) (bx1, by1) | z0, source triangle, inv | dz1, dz2
-            int4 w0 = make_int4(0, 0, 0, 0), w1 = make_int4(0, 0, 1 | (1 << 16), 0);                // box (1, 1) .. (0, 0): covers nothing
-            const int4 w2 = make_int4(0, (int)t, 0, 0), w3 = make_int4(0, 0, 0, 0);
-            long long i0 = 1, i1 = 0, j0 = 1, j1 = 0;
+            TriRec r;                                                       // slots past the fan cover nothing
+            r.pad = __uint_as_float(t);
             if (k < n) {
-                const long long x0 = cov[k].x[0], y0 = cov[k].y[0], x1 = cov[k].x[1], y1 = cov[k].y[1], x2 = cov[k].x[2], y2 = cov[k].y[2];
-                w0 = make_int4((int)x0, (int)y0, (int)x1, (int)y1);
-                w1.x = (int)x2; w1.y = (int)y2;
-                const long long mnx = x0 < x1 ? (x0 < x2 ? x0 : x2) : (x1 < x2 ? x1 : x2);
-                const long long mxx = x0 > x1 ? (x0 > x2 ? x0 : x2) : (x1 > x2 ? x1 : x2);
-                const long long mny = y0 < y1 ? (y0 < y2 ? y0 : y2) : (y1 < y2 ? y1 : y2);
-                const long long mxy = y0 > y1 ? (y0 > y2 ? y0 : y2) : (y1 > y2 ? y1 : y2);
-                i0 = (mnx + 127) >> 8; i1 = (mxx - 128) >> 8;              // pixel centres 256 i + 128 inside [mnx, mxx]
-                j0 = (mny + 127) >> 8; j1 = (mxy - 128) >> 8;
-                if (i0 < 0) i0 = 0;
-                if (j0 < 0) j0 = 0;
-                if (i1 > a.width - 1) i1 = a.width - 1;
-                if (j1 > a.height - 1) j1 = a.height - 1;
-                if (i0 <= i1 && j0 <= j1) { w1.z = (int)i0 | ((int)j0 << 16); w1.w = (int)i1 | ((int)j1 << 16); }
-                else { i0 = 1; i1 = 0; }
+                r.x0 = cov[k].x[0]; r.y0 = cov[k].y[0]; r.x1 = cov[k].x[1]; r.y1 = cov[k].y[1]; r.x2 = cov[k].x[2]; r.y2 = cov[k].y[2];
+                r.set_box(pixel_box(r.x0, r.y0, r.x1, r.y1, r.x2, r.y2, a.width, a.height));
             }
-            int4* dst = (int4*)(scratch + L.rec) + 4 * ((size_t)kFan * t + k);
-            dst[0] = w0; dst[1] = w1; dst[2] = w2; dst[3] = w3;
-            if (i0 <= i1 && j0 <= j1) {
-                const int tx0 = (int)(i0 >> 5), tx1 = (int)(i1 >> 5), ty0 = (int)(j0 >> 5), ty1 = (int)(j1 >> 5);
-                if ((tx1 - tx0 + 1) * (ty1 - ty0 + 1) <= kMaxTiles) {
-                    for (int ty = ty0; ty <= ty1; ++ty)
-                        for (int tx = tx0; tx <= tx1; ++tx) atomicAdd(&cnt[ty * L.tx + tx], 1u);
-                } else {
-                    const unsigned slot = atomicAdd(&cnt[L.ntiles], 1u);     // < kFan * tri_count
-                    ((unsigned*)(scratch + L.large))[slot] = kFan * t + k;
-                }
-            }
+            store_rec(scratch, L, (size_t)kFan * t + k, r);
+            if (!r.box().empty()) count_box(scratch, L, r.box(), kFan * t + k, false);
         }
     }
     const unsigned long long m = __ballot(rejected);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(a.rejected, (unsigned long long)__popcll(m));
-}
-
-// phase A over one list (a tile's bin or the large list) for the quad (qx, qy) of this lane
-__device__ __forceinline__ void geo_list(const PbrkGeometryArgs& a, const unsigned* list, unsigned n, const int4* recs, const GeoAttr* attrs,
-                                int4* lds, unsigned* kept, unsigned* nkept, int tx0, int ty0, int qx, int qy, float* bz, unsigned* bt) {
-    const int W = a.width, H = a.height;
-    for (unsigned base = 0; base < n; base += kThreads) {
-        __syncthreads();                                                    // the previous batch is consumed
-        if (threadIdx.x == 0) *nkept = 0;
-        __syncthreads();
-        const unsigned j = base + threadIdx.x;
-        if (j < n) {
-            const unsigned t = list[j];
-            if (meets_tile(recs + 4 * (size_t)t, tx0, ty0)) kept[atomicAdd(nkept, 1u)] = t;     // LDS counter; the winner does not depend on order
-        }
-        __syncthreads();
-        const unsigned m = *nkept;
-        if (threadIdx.x < m) {
-            const int4* src = recs + 4 * (size_t)kept[threadIdx.x];
-            int4* d = lds + 4 * threadIdx.x;
-            d[0] = src[0]; d[1] = src[1]; d[2] = src[2]; d[3] = src[3];
-        }
-        __syncthreads();
-        for (unsigned k = 0; k < m; ++k) {
-            const int4 w0 = lds[4 * k], w1 = lds[4 * k + 1];
-            const int bx0 = w1.z & 0xFFFF, by0 = w1.z >> 16, bx1 = w1.w & 0xFFFF, by1 = w1.w >> 16;      // all in [0, 16383]
-            if (qy + 1 < by0 || qy > by1 || qx + 1 < bx0 || qx > bx1) continue;
-            GeoCov c;
-            c.x[0] = w0.x; c.y[0] = w0.y; c.x[1] = w0.z; c.y[1] = w0.w; c.x[2] = w1.x; c.y[2] = w1.y;
-            const unsigned src = (unsigned)lds[4 * k + 2].y;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int i = qx + (q & 1), jj = qy + (q >> 1);
-                if (i >= W || jj >= H || i < bx0 || i > bx1 || jj < by0 || jj > by1 || !geo_covers(c, i, jj)) continue;
-                const GeoAttr& A = attrs[src];
-                double lam[3];
-                float z;
-                geo_lambda(A, i, jj, W, H, lam);
-                if (!geo_depth(A, lam, &z)) continue;
-                const float cz = sel4(bz, q);
-                const unsigned ct = sel4(bt, q);
-                if (!(z < cz || (z == cz && ct != kNone && src < ct))) continue;   // LESS; among this pass's fragments the lower triangle wins a tie
-                GeoPix P;
-                geo_pix(A, i, jj, W, H, P);
-                if (geo_alpha(a.draws[A.draw], P) < 0.3f) continue;            // discard: neither wins nor writes
-                if (q == 0) { bz[0] = z; bt[0] = src; } else if (q == 1) { bz[1] = z; bt[1] = src; }
-                else if (q == 2) { bz[2] = z; bt[2] = src; } else { bz[3] = z; bt[3] = src; }
-            }
-        }
-    }
 }
 
 __global__ __launch_bounds__(kThreads) void k_geo_tiles(PbrkGeometryArgs a, Layout L) {
@@ -144,8 +65,7 @@ __global__ __launch_bounds__(kThreads) void k_geo_tiles(PbrkGeometryArgs a, Layo
     __shared__ unsigned kept[kThreads];
     __shared__ unsigned nkept;
     const char* scratch = (const char*)a.scratch;
-    const int tile = blockIdx.y * L.tx + blockIdx.x;
-    const int qx = blockIdx.x * kTile + 2 * (int)(threadIdx.x & 15);
+    const int qx = blockIdx.x * kTile + 2 * (int)(threadIdx.x & 15);        // this lane: the quad (qx .. qx + 1, qy .. qy + 1)
     const int qy = blockIdx.y * kTile + 2 * (int)(threadIdx.x >> 4);
     const int W = a.width, H = a.height;
     float bz[4];
@@ -155,13 +75,35 @@ __global__ __launch_bounds__(kThreads) void k_geo_tiles(PbrkGeometryArgs a, Layo
         const int i = qx + (q & 1), j = qy + (q >> 1);
         bz[q] = (i < W && j < H) ? a.depth[(size_t)j * W + i] : -1.0f;
     }
-    const unsigned* cnt = (const unsigned*)(scratch + L.cnt);
-    const unsigned* off = (const unsigned*)(scratch + L.off);
-    const int4* recs = (const int4*)(scratch + L.rec);
     const GeoAttr* attrs = (const GeoAttr*)(scratch + L.extra);
-    const int tx0 = blockIdx.x * kTile, ty0 = blockIdx.y * kTile;
-    geo_list(a, (const unsigned*)(scratch + L.bins) + off[tile], off[tile + 1] - off[tile], recs, attrs, lds, kept, &nkept, tx0, ty0, qx, qy, bz, bt);
-    geo_list(a, (const unsigned*)(scratch + L.large), cnt[L.ntiles], recs, attrs, lds, kept, &nkept, tx0, ty0, qx, qy, bz, bt);
+    const TriRec* sr = (const TriRec*)lds;
+    // phase A: the winner does not depend on the order of the records
+    walk_tile(scratch, L, lds, kept, &nkept, [&](unsigned k) {
+        const TriRec& r = sr[k];
+        const PixBox b = r.box();
+        if (qy + 1 < b.y0 || qy > b.y1 || qx + 1 < b.x0 || qx > b.x1) return;
+        GeoCov c;
+        c.x[0] = r.x0; c.y[0] = r.y0; c.x[1] = r.x1; c.y[1] = r.y1; c.x[2] = r.x2; c.y[2] = r.y2;
+        const unsigned src = __float_as_uint(r.pad);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int i = qx + (q & 1), jj = qy + (q >> 1);
+            if (i >= W || jj >= H || i < b.x0 || i > b.x1 || jj < b.y0 || jj > b.y1 || !geo_covers(c, i, jj)) continue;
+            const GeoAttr& A = attrs[src];
+            double lam[3];
+            float z;
+            geo_lambda(A, i, jj, W, H, lam);
+            if (!geo_depth(A, lam, &z)) continue;
+            const float cz = sel4(bz, q);
+            const unsigned ct = sel4(bt, q);
+            if (!(z < cz || (z == cz && ct != kNone && src < ct))) continue;   // LESS; among this pass's fragments the lower triangle wins a tie
+            GeoPix P;
+            geo_pix(A, i, jj, W, H, P);
+            if (geo_alpha(a.draws[A.draw], P) < 0.3f) continue;            // discard: neither wins nor writes
+            if (q == 0) { bz[0] = z; bt[0] = src; } else if (q == 1) { bz[1] = z; bt[1] = src; }
+            else if (q == 2) { bz[2] = z; bt[2] = src; } else { bz[3] = z; bt[3] = src; }
+        }
+    });
 #pragma unroll 1
     for (int q = 0; q < 4; ++q) {
         const unsigned src = sel4(bt, q);
@@ -198,7 +140,7 @@ __global__ __launch_bounds__(kThreads) void k_mip_rgba8(const uchar4* src, uchar
 
 bool args_ok(const PbrkGeometryArgs* a) {
     return a && a->draws && a->color[0] && a->color[1] && a->color[2] && a->color[3] && a->velocity && a->depth && a->scratch && a->rejected &&
-           a->draw_count > 0 && a->width > 0 && a->height > 0 && a->width <= 16384 && a->height <= 16384 && a->tri_count <= (1u << 26);
+           a->draw_count > 0 && dims_ok(a->width, a->height) && a->tri_count <= (1u << 26);
 }
 Layout geo_layout(uint32_t n, int W, int H) { return raster_layout(kFan * n, W, H, (size_t)n * sizeof(GeoAttr)); }
 }  // namespace
@@ -212,14 +154,7 @@ extern "C" int pbrk_geometry_setup(const PbrkGeometryArgs* a, void* stream) {
     if (!args_ok(a)) return PBRK_E_ARG;
     if (a->tri_count == 0) return PBRK_OK;
     const Layout L = geo_layout(a->tri_count, a->width, a->height);
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync((char*)a->scratch + L.cnt, 0, ((size_t)L.ntiles + 1) * 4, st) != hipSuccess) return PBRK_E_LAUNCH;
-    const unsigned blocks = (a->tri_count + kThreads - 1) / kThreads;
-    const unsigned nrec = kFan * a->tri_count;
-    hipLaunchKernelGGL(k_geo_setup, dim3(blocks), dim3(kThreads), 0, st, *a, L);
-    hipLaunchKernelGGL(k_raster_scan, dim3(1), dim3(1024), 0, st, (char*)a->scratch, L);
-    hipLaunchKernelGGL(k_raster_fill, dim3((nrec + kThreads - 1) / kThreads), dim3(kThreads), 0, st, (char*)a->scratch, nrec, L);
-    return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
+    return launch_binning(k_geo_setup, *a, L, kFan * a->tri_count, (hipStream_t)stream) ? PBRK_OK : PBRK_E_LAUNCH;
 }
 
 extern "C" int pbrk_geometry_tiles(const PbrkGeometryArgs* a, void* stream) {

@@ -15,6 +15,9 @@
 //     negative over the whole tile), the rest go through LDS --, evaluate the exact int64 edge functions at the pixel centres with the
 //     top-left rule, interpolate z in fp64, keep the minimum in registers and store once.  No atomics touch the depth map.
 // Scratch sizes follow from the triangle count and the target size alone (pbrk_raster_scratch_bytes): no read-back.
+// What K13 needs as well lives in raster_bins.h: record, pixel box, draw lookup, counting, scan, fill, pre-filter, the batch loop of
+// the tile kernel and the launch sequence of setup.  This file keeps the transform and guard band of setup and the depth minimum of
+// the tile body.
 #include "pbr_kernels.h"
 #include "raster_bins.h"
 
@@ -28,15 +31,10 @@ namespace {
 __global__ __launch_bounds__(kThreads) void k_raster_setup(PbrkRasterArgs a, Layout L) {
     const uint32_t t = blockIdx.x * kThreads + threadIdx.x;
     bool rejected = false;
-    unsigned key = 0xFFFFFFFFu;                                     // the one tile of a single-tile triangle
+    unsigned key = kNoKey;                                          // the one tile of a single-tile triangle
     char* scratch = (char*)a.scratch;
     if (t < a.tri_count) {
-        int lo = 0, hi = (int)a.draw_count - 1;                   // last draw with first_tri <= t
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (a.draws[mid].first_tri <= t) lo = mid; else hi = mid - 1;
-        }
-        const PbrkRasterDraw* d = &a.draws[lo];
+        const PbrkRasterDraw* d = &a.draws[find_draw(a.draws, a.draw_count, t)];
         const uint32_t* ix = a.indices + (size_t)d->first_index + 3 * (size_t)(t - d->first_tri);   // in range: checked at record time
         const float hw = (float)a.width * 0.5f, hh = (float)a.height * 0.5f;
         int X[3] = {0, 0, 0}, Y[3] = {0, 0, 0};
@@ -59,129 +57,29 @@ __global__ __launch_bounds__(kThreads) void k_raster_setup(PbrkRasterArgs a, Lay
         rejected = !ok;
         TriRec r;
         r.x0 = X[0]; r.y0 = Y[0]; r.x1 = X[1]; r.y1 = Y[1]; r.x2 = X[2]; r.y2 = Y[2];
-        r.bx0 = 1; r.by0 = 1; r.bx1 = 0; r.by1 = 0;
-        r.z0 = Z[0]; r.pad = 0.0f;
-        r.inv = 0.0; r.dz1 = 0.0; r.dz2 = 0.0;
-        long long i0 = 1, i1 = 0, j0 = 1, j1 = 0;
-        if (ok) {
-            const long long x0 = X[0], y0 = Y[0], x1 = X[1], y1 = Y[1], x2 = X[2], y2 = Y[2];
-            const long long area = (x1 - x0) * (y2 - y0) - (y1 - y0) * (x2 - x0);
-            if (area != 0) {
-                const long long mnx = x0 < x1 ? (x0 < x2 ? x0 : x2) : (x1 < x2 ? x1 : x2);
-                const long long mxx = x0 > x1 ? (x0 > x2 ? x0 : x2) : (x1 > x2 ? x1 : x2);
-                const long long mny = y0 < y1 ? (y0 < y2 ? y0 : y2) : (y1 < y2 ? y1 : y2);
-                const long long mxy = y0 > y1 ? (y0 > y2 ? y0 : y2) : (y1 > y2 ? y1 : y2);
-                i0 = (mnx + 127) >> 8; i1 = (mxx - 128) >> 8;          // pixel centres 256 i + 128 inside [mnx, mxx]
-                j0 = (mny + 127) >> 8; j1 = (mxy - 128) >> 8;
-                if (i0 < 0) i0 = 0;
-                if (j0 < 0) j0 = 0;
-                if (i1 > a.width - 1) i1 = a.width - 1;
-                if (j1 > a.height - 1) j1 = a.height - 1;
-                if (i0 <= i1 && j0 <= j1) {
-                    r.bx0 = (short)i0; r.bx1 = (short)i1; r.by0 = (short)j0; r.by1 = (short)j1;
-                    r.inv = 1.0 / (double)area;
-                    r.dz1 = (double)Z[1] - (double)Z[0];
-                    r.dz2 = (double)Z[2] - (double)Z[0];
-                } else {
-                    i0 = 1; i1 = 0;
-                }
+        r.z0 = Z[0];
+        const long long area = ((long long)X[1] - X[0]) * ((long long)Y[2] - Y[0]) - ((long long)Y[1] - Y[0]) * ((long long)X[2] - X[0]);
+        if (ok && area != 0) {
+            r.set_box(pixel_box(X[0], Y[0], X[1], Y[1], X[2], Y[2], a.width, a.height));
+            if (!r.box().empty()) {
+                r.inv = 1.0 / (double)area;
+                r.dz1 = (double)Z[1] - (double)Z[0];
+                r.dz2 = (double)Z[2] - (double)Z[0];
             }
         }
-        const int4* src = (const int4*)&r;
-        int4* dst = (int4*)(scratch + L.rec) + 4 * (size_t)t;
-        dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2]; dst[3] = src[3];
-        if (i0 <= i1 && j0 <= j1) {
-            const int tx0 = (int)(i0 >> 5), tx1 = (int)(i1 >> 5), ty0 = (int)(j0 >> 5), ty1 = (int)(j1 >> 5);
-            unsigned* cnt = (unsigned*)(scratch + L.cnt);
-            if (tx0 == tx1 && ty0 == ty1) {
-                key = (unsigned)(ty0 * L.tx + tx0);                 // counted below, one atomic per distinct tile of the wave
-            } else if ((tx1 - tx0 + 1) * (ty1 - ty0 + 1) <= kMaxTiles) {
-                for (int ty = ty0; ty <= ty1; ++ty)
-                    for (int tx = tx0; tx <= tx1; ++tx) atomicAdd(&cnt[ty * L.tx + tx], 1u);
-            } else {
-                const unsigned slot = atomicAdd(&cnt[L.ntiles], 1u);          // < tri_count
-                ((unsigned*)(scratch + L.large))[slot] = t;
-            }
-        }
+        store_rec(scratch, L, t, r);
+        if (!r.box().empty()) key = count_box(scratch, L, r.box(), t, true);
     }
     const unsigned long long m = __ballot(rejected);
-    const int lane = threadIdx.x & 63;
-    if (lane == 0 && m) atomicAdd(a.rejected, (unsigned long long)__popcll(m));
-    // consecutive triangles of a part mostly fall into the same tile: one atomic per distinct tile of the wave
-    unsigned long long todo = __ballot(key != 0xFFFFFFFFu);
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const unsigned k = __shfl(key, leader);
-        const unsigned long long grp = __ballot(key == k);
-        if (lane == leader) atomicAdd((unsigned*)(scratch + L.cnt) + k, (unsigned)__popcll(grp));
-        todo &= ~grp;
-    }
-}
-
-// one list (a tile's bin or the large list) against the four pixels (px .. px+3, py) of this lane: 256 entries at a time, the lanes
-// first keep the entries that can touch the tile (meets_tile), the kept records are staged in LDS, then every lane walks them
-__device__ inline void raster_list(const unsigned* list, unsigned n, const int4* recs, int4* lds, unsigned* kept, unsigned* nkept,
-                                   int tx0, int ty0, int px, int py, float cur[4]) {
-    const TriRec* sr = (const TriRec*)lds;
-    for (unsigned base = 0; base < n; base += kThreads) {
-        __syncthreads();                                                    // the previous batch is consumed
-        if (threadIdx.x == 0) *nkept = 0;
-        __syncthreads();
-        const unsigned j = base + threadIdx.x;
-        if (j < n) {
-            const unsigned t = list[j];
-            if (meets_tile(recs + 4 * (size_t)t, tx0, ty0)) kept[atomicAdd(nkept, 1u)] = t;     // LDS counter; order is irrelevant
-        }
-        __syncthreads();
-        const unsigned m = *nkept;
-        if (threadIdx.x < m) {
-            const int4* src = recs + 4 * (size_t)kept[threadIdx.x];
-            int4* d = lds + 4 * threadIdx.x;
-            d[0] = src[0]; d[1] = src[1]; d[2] = src[2]; d[3] = src[3];
-        }
-        __syncthreads();
-        for (unsigned k = 0; k < m; ++k) {
-            const TriRec& r = sr[k];
-            if (py < r.by0 || py > r.by1 || px + 3 < r.bx0 || px > r.bx1) continue;
-            const long long x0 = r.x0, y0 = r.y0, x1 = r.x1, y1 = r.y1, x2 = r.x2, y2 = r.y2;
-            const bool pos = r.inv > 0.0;                                   // orientation: both windings are drawn
-            // E0 = edge(v1 -> v2), E1 = edge(v2 -> v0), E2 = edge(v0 -> v1); edge(a -> b, p) = (b.x - a.x)(p.y - a.y) - (b.y - a.y)(p.x - a.x)
-            const long long Px = 256LL * px + 128, Py = 256LL * py + 128;
-            long long e0 = (x2 - x1) * (Py - y1) - (y2 - y1) * (Px - x1);
-            long long e1 = (x0 - x2) * (Py - y2) - (y0 - y2) * (Px - x2);
-            long long e2 = (x1 - x0) * (Py - y0) - (y1 - y0) * (Px - x0);
-            const long long d0 = -(y2 - y1) * 256, d1 = -(y0 - y2) * 256, d2 = -(y1 - y0) * 256;
-            // top-left rule (y down): with the edge functions oriented positive inside, a centre ON an edge is covered when the
-            // inward normal (A, B) has A > 0 (left edge) or A == 0 and B > 0 (top edge)
-            const long long sg = pos ? 1 : -1;
-            const long long b0 = top_left(-(y2 - y1) * sg, (x2 - x1) * sg) ? 0 : 1;
-            const long long b1 = top_left(-(y0 - y2) * sg, (x0 - x2) * sg) ? 0 : 1;
-            const long long b2 = top_left(-(y1 - y0) * sg, (x1 - x0) * sg) ? 0 : 1;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const long long n0 = pos ? e0 : -e0, n1 = pos ? e1 : -e1, n2 = pos ? e2 : -e2;
-                const int x = px + q;
-                if (n0 >= b0 && n1 >= b1 && n2 >= b2 && x >= r.bx0 && x <= r.bx1) {
-                    const double z = (double)r.z0 + ((double)e1 * r.dz1 + (double)e2 * r.dz2) * r.inv;
-                    float zf = (float)z;
-                    if (zf >= 0.0f && zf <= 1.0f) {
-                        if (zf == 0.0f) zf = 0.0f;                          // -0 -> +0
-                        if (zf < cur[q]) cur[q] = zf;                       // LESS
-                    }
-                }
-                e0 += d0; e1 += d1; e2 += d2;
-            }
-        }
-    }
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(a.rejected, (unsigned long long)__popcll(m));
+    wave_take((unsigned*)(scratch + L.cnt), key);                   // the single-tile triangles of the wave
 }
 
 __global__ __launch_bounds__(kThreads) void k_raster_tiles(PbrkRasterArgs a, Layout L) {
     __shared__ int4 lds[kThreads * 4];                                      // 256 records, 16 KB
     __shared__ unsigned kept[kThreads];
     __shared__ unsigned nkept;
-    const char* scratch = (const char*)a.scratch;
-    const int tile = blockIdx.y * L.tx + blockIdx.x;
-    const int py = blockIdx.y * kTile + (threadIdx.x >> 3);
+    const int py = blockIdx.y * kTile + (threadIdx.x >> 3);                 // this lane: the four pixels (px .. px + 3, py)
     const int px = blockIdx.x * kTile + (threadIdx.x & 7) * 4;
     const int W = a.width, H = a.height;
     const bool row_in = py < H;
@@ -194,12 +92,40 @@ __global__ __launch_bounds__(kThreads) void k_raster_tiles(PbrkRasterArgs a, Lay
     } else if (row_in) {
         for (int q = 0; q < 4; ++q) if (px + q < W) cur[q] = row[px + q];
     }
-    const unsigned* cnt = (const unsigned*)(scratch + L.cnt);
-    const unsigned* off = (const unsigned*)(scratch + L.off);
-    const int4* recs = (const int4*)(scratch + L.rec);
-    const int tx0 = blockIdx.x * kTile, ty0 = blockIdx.y * kTile;
-    raster_list((const unsigned*)(scratch + L.bins) + off[tile], off[tile + 1] - off[tile], recs, lds, kept, &nkept, tx0, ty0, px, py, cur);
-    raster_list((const unsigned*)(scratch + L.large), cnt[L.ntiles], recs, lds, kept, &nkept, tx0, ty0, px, py, cur);
+    const TriRec* sr = (const TriRec*)lds;
+    walk_tile((const char*)a.scratch, L, lds, kept, &nkept, [&](unsigned k) {
+        const TriRec& r = sr[k];
+        const PixBox b = r.box();
+        if (py < b.y0 || py > b.y1 || px + 3 < b.x0 || px > b.x1) return;
+        const long long x0 = r.x0, y0 = r.y0, x1 = r.x1, y1 = r.y1, x2 = r.x2, y2 = r.y2;
+        const bool pos = r.inv > 0.0;                                       // orientation: both windings are drawn
+        // E0 = edge(v1 -> v2), E1 = edge(v2 -> v0), E2 = edge(v0 -> v1); edge(a -> b, p) = (b.x - a.x)(p.y - a.y) - (b.y - a.y)(p.x - a.x)
+        const long long Px = 256LL * px + 128, Py = 256LL * py + 128;
+        long long e0 = (x2 - x1) * (Py - y1) - (y2 - y1) * (Px - x1);
+        long long e1 = (x0 - x2) * (Py - y2) - (y0 - y2) * (Px - x2);
+        long long e2 = (x1 - x0) * (Py - y0) - (y1 - y0) * (Px - x0);
+        const long long d0 = -(y2 - y1) * 256, d1 = -(y0 - y2) * 256, d2 = -(y1 - y0) * 256;
+        // top-left rule (y down): with the edge functions oriented positive inside, a centre ON an edge is covered when the
+        // inward normal (A, B) has A > 0 (left edge) or A == 0 and B > 0 (top edge)
+        const long long sg = pos ? 1 : -1;
+        const long long b0 = top_left(-(y2 - y1) * sg, (x2 - x1) * sg) ? 0 : 1;
+        const long long b1 = top_left(-(y0 - y2) * sg, (x0 - x2) * sg) ? 0 : 1;
+        const long long b2 = top_left(-(y1 - y0) * sg, (x1 - x0) * sg) ? 0 : 1;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const long long n0 = pos ? e0 : -e0, n1 = pos ? e1 : -e1, n2 = pos ? e2 : -e2;
+            const int x = px + q;
+            if (n0 >= b0 && n1 >= b1 && n2 >= b2 && x >= b.x0 && x <= b.x1) {
+                const double z = (double)r.z0 + ((double)e1 * r.dz1 + (double)e2 * r.dz2) * r.inv;
+                float zf = (float)z;
+                if (zf >= 0.0f && zf <= 1.0f) {
+                    if (zf == 0.0f) zf = 0.0f;                              // -0 -> +0
+                    if (zf < cur[q]) cur[q] = zf;                           // LESS
+                }
+            }
+            e0 += d0; e1 += d1; e2 += d2;
+        }
+    });
     if (vec) {
         *(float4*)(row + px) = make_float4(cur[0], cur[1], cur[2], cur[3]);
     } else if (row_in) {
@@ -209,7 +135,7 @@ __global__ __launch_bounds__(kThreads) void k_raster_tiles(PbrkRasterArgs a, Lay
 
 bool args_ok(const PbrkRasterArgs* a) {
     return a && a->vertices && a->indices && a->draws && a->depth && a->scratch && a->rejected && a->draw_count > 0 &&
-           a->width > 0 && a->height > 0 && a->width <= 16384 && a->height <= 16384 && a->vertex_stride >= 12 && (a->vertex_stride & 3) == 0;
+           dims_ok(a->width, a->height) && a->vertex_stride >= 12 && (a->vertex_stride & 3) == 0;
 }
 }  // namespace
 
@@ -222,13 +148,7 @@ extern "C" int pbrk_raster_setup(const PbrkRasterArgs* a, void* stream) {
     if (!args_ok(a)) return PBRK_E_ARG;
     if (a->tri_count == 0) return PBRK_OK;
     const Layout L = raster_layout(a->tri_count, a->width, a->height);
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync((char*)a->scratch + L.cnt, 0, ((size_t)L.ntiles + 1) * 4, st) != hipSuccess) return PBRK_E_LAUNCH;
-    const unsigned blocks = (a->tri_count + kThreads - 1) / kThreads;
-    hipLaunchKernelGGL(k_raster_setup, dim3(blocks), dim3(kThreads), 0, st, *a, L);
-    hipLaunchKernelGGL(k_raster_scan, dim3(1), dim3(1024), 0, st, (char*)a->scratch, L);
-    hipLaunchKernelGGL(k_raster_fill, dim3(blocks), dim3(kThreads), 0, st, (char*)a->scratch, a->tri_count, L);
-    return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
+    return launch_binning(k_raster_setup, *a, L, a->tri_count, (hipStream_t)stream) ? PBRK_OK : PBRK_E_LAUNCH;
 }
 
 extern "C" int pbrk_raster_tiles(const PbrkRasterArgs* a, void* stream) {
