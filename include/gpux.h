@@ -112,5 +112,7 @@ GPU_API uint64_t GPUX_OverlappedSubmitCount(void);
  * the library was loaded: a vertex index past the bound vertex buffer, a non-finite transformed vertex, or a vertex outside the
  * +-2^21-pixel guard band (where Vulkan would clip).  Counted on the device; the value includes every submission waited for. ---- */
 GPU_API uint64_t GPUX_RasterRejectedTriangles(void);
+/* fragments the voxelise pass (K14) kept since GPU_Init: the stores lightgrid_voxelize.glsl would have issued (synchronises) */
+GPU_API uint64_t GPUX_VoxelizeFragments(void);
 
 #endif

@@ -256,6 +256,25 @@ GPU_DescriptorSet* PBR_GeometryDescriptorSet(PBR_GeometryPass* pass, PBR_Materia
 void PBR_RecordGeometryPass(PBR_GeometryPass* pass, GPU_Graph* graph, const PBR_Mesh* mesh, const PBR_Mesh* skybox, const PBR_Globals* globals,
                             const float* jitter, const float* jitter_prev, uint32_t frame_idx);
 
+/* ---- voxelise pass (N7 / K14): render.cpp:113-149 (pipeline: lightgrid_voxelize.glsl, conservative rasterisation), :711-714 (an
+ *      N x N render pass without targets), asset_import.cpp:196-204 (a part's descriptor set), render.cpp:1039-1056 (one GPU_OpDraw per
+ *      part).  It stores lit surface colour into the grid of `lightgrid` and reads the depth map of `sun`; both must outlive the pass.
+ *      The frame-0 clear stays PBR_RecordLightgridClear. ---- */
+typedef struct PBR_VoxelizePass PBR_VoxelizePass;
+PBR_VoxelizePass* PBR_MakeVoxelizePass(PBR_Lightgrid* lightgrid, PBR_SunDepthPass* sun);
+void PBR_DestroyVoxelizePass(PBR_VoxelizePass* pass);
+GPU_Buffer* PBR_VoxelizeGlobalsBuffer(PBR_VoxelizePass* pass);              /* persistently mapped PBR_Globals */
+GPU_GraphicsPipeline* PBR_VoxelizePipeline(PBR_VoxelizePass* pass);
+GPU_RenderPass* PBR_VoxelizeRenderPass(PBR_VoxelizePass* pass);
+/* GLOBALS, SSBO0, SSBO1, IMG0, SUN_DEPTH_MAP, TEX0, TEX_EMISSIVE, SAMPLER_PERCENTAGE_CLOSER, SAMPLER_LINEAR_WRAP: bindings 0 .. 8 */
+GPU_PipelineLayout* PBR_VoxelizeLayout(PBR_VoxelizePass* pass);
+GPU_Sampler* PBR_VoxelizeShadowSampler(PBR_VoxelizePass* pass);             /* linear, clamp, GPU_CompareOp_Less (render.cpp:664-673) */
+/* the set a part of `mesh` with this material draws with; created on first use and kept until the pass is destroyed, so destroy the
+ * pass before any mesh or material it has seen */
+GPU_DescriptorSet* PBR_VoxelizeDescriptorSet(PBR_VoxelizePass* pass, const PBR_Mesh* mesh, PBR_Material* material);
+/* render.cpp:991, :1039-1056: copies globals (if not NULL) and draws every part of `mesh` that has a material */
+void PBR_RecordVoxelizePass(PBR_VoxelizePass* pass, GPU_Graph* graph, const PBR_Mesh* mesh, const PBR_Globals* globals);
+
 #ifdef __cplusplus
 }
 #endif

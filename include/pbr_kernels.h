@@ -307,6 +307,35 @@ int pbrk_geometry_tiles(const PbrkGeometryArgs* args, void* stream);
  * averaged in fp32 on the decoded values, stored as rint(255 x) */
 int pbrk_mip_chain_rgba8(void* pyramid, int width, int height, int levels, void* stream);
 
+/* ---- K14: the voxelise pass (lightgrid_voxelize.glsl, render.cpp:1039-1056) as a compute rasteriser: conservative coverage of an
+ *      N x N target, one store per fragment into the N^3 RGBA16F light grid; among the fragments of one voxel the largest
+ *      (triangle number, pixel row, pixel column) wins.  Contract: DESIGN.md K14.  Setup (one lane per triangle: vertex stage, snap,
+ *      conservative box walk, a 64-bit atomicMax of the fragment's key into an N^3 owner grid in `scratch`; triangles with a large
+ *      box go to a list that one workgroup per triangle covers), then resolve (one lane per owned voxel shades its winner and
+ *      stores 8 bytes).  Vertices and indices are the raw SSBO0 / SSBO1 of the draw's descriptor set. ---- */
+typedef struct PbrkVoxDraw {
+    float sun[16];                /* sun_space_from_world, column-major, as snapshotted at submit */
+    float sun_dir[4];             /* sun_direction */
+    float scale;                  /* lightgrid_scale */
+    uint32_t first_tri, first_vertex, pad;
+    const float* vertices; unsigned long long vertex_floats;      /* SSBO0 and its length in floats: a read past it is checked */
+    const uint32_t* indices;                                      /* SSBO1: [first_vertex, first_vertex + 3 x triangles) is in range */
+    const float* sun_depth; int sun_w, sun_h;                     /* SUN_DEPTH_MAP */
+    PbrkGeoTex tex[2];            /* TEX0 (base colour), TEX_EMISSIVE */
+} PbrkVoxDraw;
+typedef struct PbrkVoxelizeArgs {
+    const PbrkVoxDraw* draws;     /* device memory, first_tri ascending, every draw at least one triangle */
+    uint32_t draw_count, tri_count;
+    void* grid;                   /* RGBA16F [n][n][n], updated in place */
+    int n;                        /* multiple of 8, 8 .. 256 */
+    void* scratch;
+    unsigned long long* rejected;
+    unsigned long long* fragments;    /* device counter (may be NULL): += fragments kept, i.e. stores the shader would have issued */
+} PbrkVoxelizeArgs;
+size_t pbrk_voxelize_scratch_bytes(uint32_t tri_count, int n, int n_again);   /* n_again: ignored (the raster jobs' common signature) */
+int pbrk_voxelize_cover(const PbrkVoxelizeArgs* args, void* stream);    /* K14.cover: clear the owner grid, setup + small boxes, large boxes */
+int pbrk_voxelize_resolve(const PbrkVoxelizeArgs* args, void* stream);  /* K14.resolve */
+
 /* ---- diagnostics: the device samplers of the widened passes evaluated at caller-supplied coordinates, so that tests can feed them
  *      NaN / inf / 1e30 / boundary values directly (a ray that has marched far away must never become an out-of-bounds read).
  *      which: 0 = LIGHTGRID (RGBA16F n^3, coords xyz), 1 = sampler2DShadow (R32F w x h, coords u, v, ref; result in out[0]),

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Renders one viewable frame through the whole path (synthetic HDR cube -> IBL precompute -> metal-rough spheres G-buffer ->
 shade -> TAA x3 -> bloom -> tone map) and writes it as a PNG:   python3 tools/render_frame.py out.png [width height [live | raster]]
-With `raster` the G-buffer is not synthetic: the geometry pass (K13) rasterises synth_mesh_temple with procedural materials each frame.
+With `raster` the G-buffer is not synthetic: the geometry pass (K13) rasterises synth_mesh_temple with procedural materials each frame,
+and neither are the live shader's other inputs: the sun depth pass (K12) draws the shadow map, the voxelise pass (K14) fills the light
+grid from the mesh on frame 0 (render.cpp:1022-1056) and the sweep (K7) spreads it.
 With `live` the lighting pass is the reference's complete live shader (shafts, sun shadows, voxel GI) inside the reference's
 frame loop: light-grid sweep -> lighting (reading last frame's bloom_downscale_rt) -> TAA -> bloom -> final, eight frames."""
 import ctypes as C
@@ -62,8 +64,12 @@ def main():
         for k, m in enumerate(part_mat):
             L.PBR_MeshSetPartMaterial(mesh, k, materials[m])
         gp = L.PBR_MakeGeometryPass(C.byref(gb), pp, W, H)
-    lg = None
-    if live:
+        sp = L.PBR_MakeSunDepthPass(2048)
+        lg = L.PBR_MakeLightgrid(128)
+        vp = pbrhip.make_voxelize_pass(lg, sp)
+        lp = L.PBR_MakeLightingPassLive(C.byref(gb), C.byref(maps), W, H, L.PBR_SunDepthTexture(sp), L.PBR_LightgridTexture(lg), L.PBR_PostBloomDownscale(pp))
+        L.GPUX_SetShadeFlags(L.PBR_LightingPipeline(lp), pbrhip.Shade_LightShafts | pbrhip.Shade_SunShadows | pbrhip.Shade_VoxelGI)
+    elif live:
         lg = L.PBR_MakeLightgrid(grid.shape[0])
         pbrhip.upload_mip(L.PBR_LightgridTexture(lg), 0, grid)
         sun_tex = pbrhip.make_texture(pbrhip.Format_D32F_Or_X8D24UN, sun.shape[1], sun.shape[0], pbrhip.TextureFlag_RenderTarget)
@@ -78,7 +84,12 @@ def main():
         if live:
             glob.lightgrid_scale = 1.0 / synth.GI_SCENE_EXTENT
             L.PBR_RecordLightgridSweep(lg, g)                                   # render.cpp:1061-1072
-        if raster:                                                              # render.cpp:993, 1076-1115; a still camera
+        if raster:                                                              # render.cpp:993-1115; a still camera
+            L.PBR_RecordSunDepthPass(sp, g, mesh, C.byref(glob))
+            if frame == 0:                                                      # render.cpp:1024-1056: voxelised once, the grid persists
+                L.PBR_RecordLightgridClear(lg, g)
+                L.PBR_RecordVoxelizePass(vp, g, mesh, C.byref(glob))
+            L.PBR_RecordLightgridSweep(lg, g)
             for k in range(16):
                 glob.old_clip_space_from_world[k] = glob.clip_space_from_world[k]
             L.PBR_RecordGeometryPass(gp, g, mesh, None, C.byref(glob), None, None, frame)

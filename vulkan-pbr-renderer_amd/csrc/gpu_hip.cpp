@@ -48,7 +48,7 @@ static void gpu_fail(const char* fmt, ...) {
 // object model
 // ------------------------------------------------------------------------------------------
 enum BindKind { Bind_Texture, Bind_Sampler, Bind_Buffer, Bind_StorageImage };
-enum KernelId { Kernel_None = 0, Kernel_BrdfLut, Kernel_Irradiance, Kernel_Prefilter, Kernel_Lighting, Kernel_LightgridSweep, Kernel_TaaResolve, Kernel_FinalPost, Kernel_BloomDown, Kernel_BloomUp, Kernel_SunDepth, Kernel_Geometry };
+enum KernelId { Kernel_None = 0, Kernel_BrdfLut, Kernel_Irradiance, Kernel_Prefilter, Kernel_Lighting, Kernel_LightgridSweep, Kernel_TaaResolve, Kernel_FinalPost, Kernel_BloomDown, Kernel_BloomUp, Kernel_SunDepth, Kernel_Geometry, Kernel_Voxelize };
 
 struct GPU_Sampler { GPU_SamplerDesc desc; bool shared; };
 
@@ -90,7 +90,8 @@ struct GPU_GraphicsPipeline { GPU_PipelineLayout* layout; GPU_RenderPass* pass; 
 
 enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster };
 // one GPU_OpDrawIndexed of a raster job (K12 or K13): job triangles [first_tri, first_tri + index_count / 3), matrices from the set's
-// GLOBALS, the buffers bound at the draw and the pushed constants (K13 reads them: the skybox rebinds both inside the pass; K12 does not)
+// GLOBALS, the buffers bound at the draw and the pushed constants (K13 reads them: the skybox rebinds both inside the pass; K12 does not).
+// K14's GPU_OpDraw keeps its first vertex in first_index and reads its buffers from the set (SSBO0, SSBO1).
 struct RasterDraw { GPU_DescriptorSet* set; uint32_t first_tri, first_index, vertex_offset; BufferImpl* vb = nullptr; BufferImpl* ib = nullptr; float push[4] = {0, 0, 0, 0}; };
 struct Op {
     OpKind kind;
@@ -116,20 +117,21 @@ struct Op {
     bool folded = false;
     TextureImpl* blend_tex = nullptr; uint32_t blend_mip = 0;
     bool skip_level0 = false;                      // Op_Clear of all levels whose level 0 the next op overwrites entirely
-    // raster job (Op_Raster, K12 or K13): the indexed draws of one render-pass instance; tex = depth target, buf = vertices and
-    // buf2 = indices of the job's first draw (K12 has one pair per job)
+    // raster job (Op_Raster, K12, K13 or K14): the draws of one render-pass instance; tex = depth target (K14: the light grid), buf =
+    // vertices and buf2 = indices of the job's first draw (K12 has one pair per job)
     std::vector<RasterDraw> draws;
     uint32_t tri_count = 0, vertex_stride = 0;
     int raster_slot = -1;                          // GPU_Graph::raster scratch of this job
 };
 struct DrawParams { GPU_GraphicsPipeline* pipeline; GPU_DescriptorSet* set; };
-// per raster job (K12 or K13) of a graph, kept across submissions: bins / records (device), the draw table (device + pinned staging)
+// per raster job (K12, K13 or K14) of a graph, kept across submissions: bins / records (device), the draw table (device + pinned staging)
 struct RasterScratch { void* dev = nullptr; size_t dev_bytes = 0; void* draws_dev = nullptr; void* draws_host = nullptr; size_t draws_cap = 0; /* bytes */ };
-// what the two raster jobs differ in on the host, beside the kernel-specific halves of record_raster_draw, snapshot_raster_draws and exec_raster
+// what the three raster jobs differ in on the host, beside the kernel-specific halves of record_raster_draw, snapshot_raster_draws and exec_raster
 struct RasterKind { const char* op_name; const char* tag; const char* shader; const char* pass_name; GPU_CullMode cull; const char* cull_name; size_t draw_bytes; size_t (*scratch_bytes)(uint32_t, int, int); };
 static const RasterKind kSunDepthJob = {"K12.sun_depth", "K12", "sun_depth_pass.glsl", "sun depth", GPU_CullMode_TwoSided, "GPU_CullMode_TwoSided only", sizeof(PbrkRasterDraw), pbrk_raster_scratch_bytes};
 static const RasterKind kGeometryJob = {"K13.geometry", "K13", "geometry_pass.glsl", "geometry", GPU_CullMode_DrawCCW, "GPU_CullMode_DrawCCW only (render.cpp:232)", sizeof(PbrkGeoDraw), pbrk_geometry_scratch_bytes};
-static const RasterKind& raster_kind(KernelId k) { return k == Kernel_Geometry ? kGeometryJob : kSunDepthJob; }
+static const RasterKind kVoxelizeJob = {"K14.voxelize", "K14", "lightgrid_voxelize.glsl", "voxelise", GPU_CullMode_TwoSided, "GPU_CullMode_TwoSided only", sizeof(PbrkVoxDraw), pbrk_voxelize_scratch_bytes};
+static const RasterKind& raster_kind(KernelId k) { return k == Kernel_Geometry ? kGeometryJob : (k == Kernel_Voxelize ? kVoxelizeJob : kSunDepthJob); }
 
 struct GPU_Graph {
     hipStream_t stream = nullptr;
@@ -192,7 +194,7 @@ static struct {
     float prefilter_tol = 0.0f;                     // GPUX_SetPrefilterTolerance: 0 = exact sums (default)
     int kept_samples[32] = {0};                     // per output mip: samples kept by the last prefilter dispatch
     int replay = -1;                                // GPUX_SetGraphReplay: submissions go through an instantiated hipGraph (-1: PBR_GRAPH_REPLAY or 0)
-    unsigned long long* raster_rejected = nullptr;  // device counter of K12 (GPUX_RasterRejectedTriangles)
+    unsigned long long* raster_rejected = nullptr;  // device counters: [0] GPUX_RasterRejectedTriangles, [1] GPUX_VoxelizeFragments
     uint64_t raster_rejected_base = 0;              // what earlier GPU_Init .. GPU_Deinit spans counted
 } G;
 
@@ -207,6 +209,7 @@ static const char kTokenBloomDown[] = "HIPK10:bloom_downsample";
 static const char kTokenBloomUp[] = "HIPK11:bloom_upsample";
 static const char kTokenSun[] = "HIPK12:sun_depth_pass";
 static const char kTokenGeometry[] = "HIPK13:geometry_pass";
+static const char kTokenVoxelize[] = "HIPK14:lightgrid_voxelize";
 
 // ------------------------------------------------------------------------------------------
 // formats  [gpu.h:99-144]
@@ -583,6 +586,7 @@ static KernelId identify_shader(const GPU_ShaderDesc* d) {
         if (t == kTokenBloomUp) return Kernel_BloomUp;
         if (t == kTokenSun) return Kernel_SunDepth;
         if (t == kTokenGeometry) return Kernel_Geometry;
+        if (t == kTokenVoxelize) return Kernel_Voxelize;
         return Kernel_None;
     }
     std::string b = basename_of(d->glsl_debug_filepath);
@@ -598,6 +602,7 @@ static KernelId identify_shader(const GPU_ShaderDesc* d) {
     if (b == "lightgrid_sweep.glsl" && glsl_contains(d->glsl, "LIGHTMAP_IMG") && glsl_contains(d->glsl, "X_direction")) return Kernel_LightgridSweep;
     if (b == "sun_depth_pass.glsl" && glsl_contains(d->glsl, "sun_space_from_world") && glsl_contains(d->glsl, "vs_position")) return Kernel_SunDepth;
     if (b == "geometry_pass.glsl" && glsl_contains(d->glsl, "old_clip_space_from_world") && glsl_contains(d->glsl, "out_velocity")) return Kernel_Geometry;
+    if (b == "lightgrid_voxelize.glsl" && glsl_contains(d->glsl, "LIGHTMAP_IMG") && glsl_contains(d->glsl, "lightgrid_scale")) return Kernel_Voxelize;
     return Kernel_None;
 }
 static GPU_String token_for(KernelId k) {
@@ -613,6 +618,7 @@ static GPU_String token_for(KernelId k) {
     case Kernel_BloomUp: return GPU_String{kTokenBloomUp, sizeof kTokenBloomUp - 1};
     case Kernel_SunDepth: return GPU_String{kTokenSun, sizeof kTokenSun - 1};
     case Kernel_Geometry: return GPU_String{kTokenGeometry, sizeof kTokenGeometry - 1};
+    case Kernel_Voxelize: return GPU_String{kTokenVoxelize, sizeof kTokenVoxelize - 1};
     default: return GPU_String{nullptr, 0};
     }
 }
@@ -627,7 +633,7 @@ GPU_API GPU_String GPU_SPIRVFromGLSL(DS_Arena* arena, GPU_ShaderStage stage, GPU
     GPU_ShaderDesc probe = *desc;
     probe.spirv = empty;
     KernelId k = identify_shader(&probe);
-    bool stage_ok = (k == Kernel_Lighting || k == Kernel_TaaResolve || k == Kernel_FinalPost || k == Kernel_BloomDown || k == Kernel_BloomUp || k == Kernel_SunDepth || k == Kernel_Geometry) ? (stage == GPU_ShaderStage_Vertex || stage == GPU_ShaderStage_Fragment)
+    bool stage_ok = (k == Kernel_Lighting || k == Kernel_TaaResolve || k == Kernel_FinalPost || k == Kernel_BloomDown || k == Kernel_BloomUp || k == Kernel_SunDepth || k == Kernel_Geometry || k == Kernel_Voxelize) ? (stage == GPU_ShaderStage_Vertex || stage == GPU_ShaderStage_Fragment)
                                            : (stage == GPU_ShaderStage_Compute);
     if (k != Kernel_None && stage_ok) {
         if (out_errors) { out_errors->data = nullptr; out_errors->length = 0; }
@@ -635,7 +641,7 @@ GPU_API GPU_String GPU_SPIRVFromGLSL(DS_Arena* arena, GPU_ShaderStage stage, GPU
     }
     snprintf(g_last_error_text, sizeof g_last_error_text,
              "the HIP backend has no built-in kernel for shader \"%s\" (stage %d); supported: gen_brdf_integration_map.glsl, "
-             "gen_irradiance_map.glsl, gen_prefiltered_env_map.glsl, lightgrid_sweep.glsl (compute), lighting_pass.glsl, taa_resolve.glsl, bloom_downsample.glsl, bloom_upsample.glsl, final_post_process.glsl (full-screen), sun_depth_pass.glsl (depth-only raster), geometry_pass.glsl (G-buffer raster)",
+             "gen_irradiance_map.glsl, gen_prefiltered_env_map.glsl, lightgrid_sweep.glsl (compute), lighting_pass.glsl, taa_resolve.glsl, bloom_downsample.glsl, bloom_upsample.glsl, final_post_process.glsl (full-screen), sun_depth_pass.glsl (depth-only raster), geometry_pass.glsl (G-buffer raster), lightgrid_voxelize.glsl (conservative raster into the light grid)",
              basename_of(desc->glsl_debug_filepath).c_str(), (int)stage);
     if (!out_errors) { gpu_fail("GPU_SPIRVFromGLSL: %s", g_last_error_text); return empty; }
     g_last_error.shader_stage = stage; g_last_error.line = 0;
@@ -739,6 +745,29 @@ GPU_API GPU_GraphicsPipeline* GPU_MakeGraphicsPipeline(const GPU_GraphicsPipelin
         GPU_REQUIRE((stride & 3) == 0, nullptr, "GPU_MakeGraphicsPipeline: vertex stride %u is not a multiple of 4 bytes", stride);
         GPU_GraphicsPipeline* p = new GPU_GraphicsPipeline();
         p->layout = desc->layout; p->pass = desc->render_pass; p->kernel = k; p->shade_flags = 0; p->vertex_stride = stride;
+        return p;
+    }
+    if (k == Kernel_Voxelize) {
+        // K14: exactly the reference's state (render.cpp:113-149, 711-714): a pass without targets, no vertex inputs, conservative
+        const GPU_RenderPassDesc& rd = desc->render_pass->desc;
+        GPU_REQUIRE(rd.color_targets_count == 0 && rd.depth_stencil_target == nullptr, nullptr,
+                    "GPU_MakeGraphicsPipeline: lightgrid_voxelize.glsl needs a render pass without colour and depth targets (render.cpp:711-714)");
+        GPU_REQUIRE(rd.width == rd.height && rd.width >= 8 && rd.width <= 256 && (rd.width & 7) == 0, nullptr,
+                    "GPU_MakeGraphicsPipeline: the voxelise pass must be N x N with N a multiple of 8 in 8 .. 256 (got %u x %u)", rd.width, rd.height);
+        GPU_REQUIRE(desc->vertex_input_formats_count == 0, nullptr, "GPU_MakeGraphicsPipeline: lightgrid_voxelize.glsl has no vertex inputs (it reads SSBO0 / SSBO1)");
+        GPU_REQUIRE(desc->enable_conservative_rasterization, nullptr, "GPU_MakeGraphicsPipeline: lightgrid_voxelize.glsl is implemented with conservative rasterisation only (render.cpp:147)");
+        GPU_REQUIRE(desc->cull_mode == kVoxelizeJob.cull, nullptr, "GPU_MakeGraphicsPipeline: %s is implemented for %s", kVoxelizeJob.shader, kVoxelizeJob.cull_name);
+        GPU_REQUIRE(!desc->enable_depth_test && !desc->enable_depth_write && !desc->enable_blending, nullptr,
+                    "GPU_MakeGraphicsPipeline: lightgrid_voxelize.glsl is implemented without depth test, depth write and blending");
+        static const struct { const char* name; BindKind kind; } need[] = {{"GLOBALS", Bind_Buffer}, {"SSBO0", Bind_Buffer}, {"SSBO1", Bind_Buffer},
+            {"IMG0", Bind_StorageImage}, {"SUN_DEPTH_MAP", Bind_Texture}, {"TEX0", Bind_Texture}, {"TEX_EMISSIVE", Bind_Texture},
+            {"SAMPLER_PERCENTAGE_CLOSER", Bind_Sampler}, {"SAMPLER_LINEAR_WRAP", Bind_Sampler}};
+        for (const auto& nb : need) {
+            const int b = find_binding(desc->layout, nb.name);
+            GPU_REQUIRE(b >= 0 && desc->layout->bindings[(size_t)b].kind == nb.kind, nullptr, "GPU_MakeGraphicsPipeline: the voxelise pass layout has no \"%s\" binding of the right kind", nb.name);
+        }
+        GPU_GraphicsPipeline* p = new GPU_GraphicsPipeline();
+        p->layout = desc->layout; p->pass = desc->render_pass; p->kernel = k; p->shade_flags = 0;
         return p;
     }
     if (k == Kernel_Geometry) {
@@ -1142,8 +1171,13 @@ static void record_shade(GPU_Graph* g, uint32_t row0, uint32_t row1, bool explic
     g->ops.push_back(op);
 }
 
+static void record_voxelize_draw(GPU_Graph* g, const DrawParams& dp, uint32_t vertex_count, uint32_t instance_count, uint32_t first_vertex);
 GPU_API void GPU_OpDraw(GPU_Graph* g, uint32_t vertex_count, uint32_t instance_count, uint32_t first_vertex, uint32_t first_instance) {
     REC_GUARD(g);
+    if (g->in_pass && g->bound_draw >= 0 && g->draw_params[(size_t)g->bound_draw].pipeline->kernel == Kernel_Voxelize) {
+        record_voxelize_draw(g, g->draw_params[(size_t)g->bound_draw], vertex_count, instance_count, first_vertex);   // the shader never reads gl_InstanceIndex
+        return;
+    }
     GPU_REQUIRE_V(vertex_count == 3 && instance_count == 1 && first_vertex == 0 && first_instance == 0,
                   "GPU_OpDraw: unsupported (raster): only the full-screen triangle GPU_OpDraw(3,1,0,0) of the lighting pass is implemented");
     record_shade(g, 0, 0, false, __func__);
@@ -1174,7 +1208,7 @@ static void close_raster_job(GPU_Graph* g) {
         else ok = false;
     }
     if (ok && !G.raster_rejected) {
-        if (hipMalloc((void**)&G.raster_rejected, 8) != hipSuccess || hipMemset(G.raster_rejected, 0, 8) != hipSuccess) { G.raster_rejected = nullptr; ok = false; }
+        if (hipMalloc((void**)&G.raster_rejected, 16) != hipSuccess || hipMemset(G.raster_rejected, 0, 16) != hipSuccess) { G.raster_rejected = nullptr; ok = false; }
     }
     if (!ok) { (void)hipGetLastError(); op.tri_count = 0; op.draws.clear(); gpu_fail("GPU_OpEndRenderPass: allocation of the raster scratch (%zu bytes) failed", need); }
 }
@@ -1229,6 +1263,60 @@ static void record_raster_draw(GPU_Graph* g, const DrawParams& dp, uint32_t inde
     op.tri_count += tris;
 }
 
+// One GPU_OpDraw of the voxelise pass (K14, render.cpp:1039-1056): the draws of one render-pass instance that store into one light grid
+// are one job; which store to a voxel wins follows the triangles' submission order, which merging keeps.
+static void record_voxelize_draw(GPU_Graph* g, const DrawParams& dp, uint32_t vertex_count, uint32_t instance_count, uint32_t first_vertex) {
+    const char* fn = "GPU_OpDraw";
+    GPU_REQUIRE_V(dp.pipeline->pass == g->in_pass, "%s: pipeline was created for a different render pass", fn);
+    GPU_REQUIRE_V(dp.set->layout == dp.pipeline->layout, "%s: descriptor set and pipeline use different layouts", fn);
+    const uint32_t N = g->in_pass->desc.width;
+    Slot* gl = named_slot(dp.set, "GLOBALS");
+    GPU_REQUIRE_V(gl && gl->buf && gl->buf->base.size >= 548, "%s: voxelise pass: \"GLOBALS\" must be a buffer that holds lightgrid_scale (548 bytes, render.h:122-136)", fn);
+    Slot* vb = named_slot(dp.set, "SSBO0");
+    Slot* ib = named_slot(dp.set, "SSBO1");
+    GPU_REQUIRE_V(vb && vb->buf, "%s: voxelise pass: \"SSBO0\" (vertices) is not a bound buffer", fn);
+    GPU_REQUIRE_V(ib && ib->buf, "%s: voxelise pass: \"SSBO1\" (indices) is not a bound buffer", fn);
+    const uint64_t n_idx = ib->buf->base.size / 4;
+    GPU_REQUIRE_V((uint64_t)first_vertex + vertex_count <= n_idx, "%s: voxelise pass: vertices [%u, %llu) lie outside \"SSBO1\" (%llu indices)", fn,
+                  first_vertex, (unsigned long long)first_vertex + vertex_count, (unsigned long long)n_idx);
+    Slot* img = named_slot(dp.set, "IMG0");
+    GPU_REQUIRE_V(img && img->tex && img->mip == 0 && img->tex->base.format == GPU_Format_RGBA16F && img->tex->base.layer_count == 1 &&
+                  img->tex->base.width == N && img->tex->base.height == N && img->tex->base.depth == N,
+                  "%s: voxelise pass: \"IMG0\" must be mip 0 of a %u^3 RGBA16F 3-D storage image", fn, N);
+    Slot* sun = named_slot(dp.set, "SUN_DEPTH_MAP");
+    GPU_REQUIRE_V(sun && sun->tex && sun->whole && sun->tex->base.format == GPU_Format_D32F_Or_X8D24UN && sun->tex->base.layer_count == 1 && sun->tex->base.depth == 1,
+                  "%s: voxelise pass: \"SUN_DEPTH_MAP\" must be a whole 2D D32F texture (render.cpp:676)", fn);
+    for (const char* name : {"TEX0", "TEX_EMISSIVE"}) {
+        Slot* sl = named_slot(dp.set, name);
+        GPU_REQUIRE_V(sl && sl->tex && sl->whole && sl->tex->base.format == GPU_Format_RGBA8UN && sl->tex->base.layer_count == 1 && sl->tex->base.depth == 1,
+                      "%s: voxelise pass: \"%s\" must be a whole 2D RGBA8UN texture", fn, name);
+    }
+    Slot* sm = named_slot(dp.set, "SAMPLER_LINEAR_WRAP");
+    GPU_REQUIRE_V(sm && sm->sampler == &G.samplers[0], "%s: voxelise pass: \"SAMPLER_LINEAR_WRAP\" must be GPU_SamplerLinearWrap()", fn);
+    Slot* pc = named_slot(dp.set, "SAMPLER_PERCENTAGE_CLOSER");
+    GPU_REQUIRE_V(pc && pc->sampler && pc->sampler->desc.min_filter == GPU_Filter_Linear && pc->sampler->desc.mag_filter == GPU_Filter_Linear &&
+                  pc->sampler->desc.address_modes[0] == GPU_AddressMode_Clamp && pc->sampler->desc.address_modes[1] == GPU_AddressMode_Clamp &&
+                  pc->sampler->desc.compare_op == GPU_CompareOp_Less,
+                  "%s: voxelise pass: \"SAMPLER_PERCENTAGE_CLOSER\" must be a linear / clamp / GPU_CompareOp_Less sampler (render.cpp:664-673)", fn);
+    const uint32_t tris = vertex_count / 3;                                   // whole triangles only
+    if (tris == 0 || instance_count == 0) return;                             // any instance count > 0 draws the same triangles once
+    if (g->raster_op >= 0 && g->ops[(size_t)g->raster_op].tex != img->tex) close_raster_job(g);     // another grid: another job, in order
+    if (g->raster_op < 0) {
+        Op op; op.kind = Op_Raster; op.name = kVoxelizeJob.op_name;
+        op.pass = g->in_pass; op.gpipe = dp.pipeline; op.tex = img->tex;
+        op.raster_slot = (int)g->raster_used++;
+        g->ops.push_back(op);
+        g->raster_op = (int)g->ops.size() - 1;
+    }
+    Op& op = g->ops[(size_t)g->raster_op];
+    GPU_REQUIRE_V(op.gpipe->kernel == Kernel_Voxelize, "%s: a voxelise draw inside another raster pass", fn);
+    GPU_REQUIRE_V((uint64_t)op.tri_count + tris <= (1u << 26), "%s: more than 2^26 triangles in one %s pass", fn, kVoxelizeJob.pass_name);
+    RasterDraw d; d.set = dp.set; d.first_tri = op.tri_count; d.first_index = first_vertex; d.vertex_offset = 0;
+    d.vb = vb->buf; d.ib = ib->buf;
+    op.draws.push_back(d);
+    op.tri_count += tris;
+}
+
 GPU_API void GPU_OpDrawIndexed(GPU_Graph* g, uint32_t index_count, uint32_t instance_count, uint32_t first_index, uint32_t vertex_offset, uint32_t first_instance) {
     (void)first_instance;                                                     // the shader never reads gl_InstanceIndex
     REC_GUARD(g);
@@ -1252,6 +1340,12 @@ GPU_API uint64_t GPUX_RasterRejectedTriangles(void) {
     unsigned long long d = 0;
     if (G.init && G.raster_rejected && hipMemcpy(&d, G.raster_rejected, 8, hipMemcpyDeviceToHost) == hipSuccess) v += d;
     return v;
+}
+
+GPU_API uint64_t GPUX_VoxelizeFragments(void) {
+    unsigned long long d = 0;
+    if (G.init && G.raster_rejected && hipMemcpy(&d, G.raster_rejected + 1, 8, hipMemcpyDeviceToHost) != hipSuccess) d = 0;
+    return d;
 }
 
 // ---- transfers ----
@@ -1503,9 +1597,15 @@ static void exec_raster(GPU_Graph* g, Op& op, size_t& ev_used) {
     RasterScratch& rs = g->raster[(size_t)op.raster_slot];
     const RasterKind& rk = raster_kind(op.gpipe->kernel);
     const bool geo = op.gpipe->kernel == Kernel_Geometry;
+    const bool vox = op.gpipe->kernel == Kernel_Voxelize;
     PbrkRasterArgs sa;
     PbrkGeometryArgs ga;
-    if (geo) {
+    PbrkVoxelizeArgs va;
+    if (vox) {
+        va.draws = (const PbrkVoxDraw*)rs.draws_dev; va.draw_count = (uint32_t)op.draws.size(); va.tri_count = op.tri_count;
+        va.grid = op.tex->dev; va.n = (int)op.tex->base.width;
+        va.scratch = rs.dev; va.rejected = G.raster_rejected; va.fragments = G.raster_rejected + 1;
+    } else if (geo) {
         ga.draws = (const PbrkGeoDraw*)rs.draws_dev; ga.draw_count = (uint32_t)op.draws.size(); ga.tri_count = op.tri_count;
         for (int k = 0; k < 4; ++k) ga.color[k] = ((TextureImpl*)op.pass->targets[(size_t)k].texture)->dev;
         ga.velocity = ((TextureImpl*)op.pass->targets[4].texture)->dev;
@@ -1518,13 +1618,13 @@ static void exec_raster(GPU_Graph* g, Op& op, size_t& ev_used) {
         sa.depth = (float*)op.tex->dev; sa.width = (int)op.tex->base.width; sa.height = (int)op.tex->base.height;
         sa.scratch = rs.dev; sa.rejected = G.raster_rejected;
     }
-    timed(g, std::string(rk.tag) + ".setup", ev_used, [&] {
+    timed(g, std::string(rk.tag) + (vox ? ".cover" : ".setup"), ev_used, [&] {
         HIP_OK(hipMemcpyAsync(rs.draws_dev, rs.draws_host, op.draws.size() * rk.draw_bytes, hipMemcpyHostToDevice, st));
-        int rc = geo ? pbrk_geometry_setup(&ga, st) : pbrk_raster_setup(&sa, st);
+        int rc = vox ? pbrk_voxelize_cover(&va, st) : geo ? pbrk_geometry_setup(&ga, st) : pbrk_raster_setup(&sa, st);
         if (rc != PBRK_OK) gpu_fail("%s setup launch failed (%d)", rk.tag, rc);
     });
-    timed(g, std::string(rk.tag) + ".tiles", ev_used, [&] {
-        int rc = geo ? pbrk_geometry_tiles(&ga, st) : pbrk_raster_tiles(&sa, st);
+    timed(g, std::string(rk.tag) + (vox ? ".resolve" : ".tiles"), ev_used, [&] {
+        int rc = vox ? pbrk_voxelize_resolve(&va, st) : geo ? pbrk_geometry_tiles(&ga, st) : pbrk_raster_tiles(&sa, st);
         if (rc != PBRK_OK) gpu_fail("%s tile launch failed (%d)", rk.tag, rc);
     });
     for (const GPU_TextureView& tv : op.pass->targets) { ((TextureImpl*)tv.texture)->bordered_valid = false; ((TextureImpl*)tv.texture)->lut_cells_valid = false; }
@@ -2016,11 +2116,30 @@ static bool fill_geo_draw(const RasterDraw& d, PbrkGeoDraw& o) {          // bot
     o.first_tri = d.first_tri; o.first_index = d.first_index; o.vertex_offset = d.vertex_offset;
     return true;
 }
+static bool fill_vox_draw(const RasterDraw& d, PbrkVoxDraw& o) {          // sun matrix and direction, scale, the draw's buffers and textures
+    memset(&o, 0, sizeof o);
+    const BufferImpl* gb = named_slot(d.set, "GLOBALS")->buf;
+    read_globals(gb, 384, o.sun, 64); read_globals(gb, 512, o.sun_dir, 16); read_globals(gb, 544, &o.scale, 4);    // render.h:129, :131, :134
+    o.first_tri = d.first_tri; o.first_vertex = d.first_index;
+    o.vertices = (const float*)d.vb->dev; o.vertex_floats = d.vb->base.size / 4u; o.indices = (const uint32_t*)d.ib->dev;
+    const TextureImpl* sun = named_slot(d.set, "SUN_DEPTH_MAP")->tex;
+    o.sun_depth = (const float*)sun->dev; o.sun_w = (int)sun->base.width; o.sun_h = (int)sun->base.height;
+    static const char* const names[2] = {"TEX0", "TEX_EMISSIVE"};
+    for (int k = 0; k < 2; ++k) {
+        const TextureImpl* t = named_slot(d.set, names[k])->tex;
+        o.tex[k].texels = t->dev; o.tex[k].width = (int)t->base.width; o.tex[k].height = (int)t->base.height; o.tex[k].levels = (int)t->base.mip_level_count;
+    }
+    return true;
+}
 static bool snapshot_raster_draws(GPU_Graph* g) {
     for (const Op& op : g->ops) {
         if (op.kind != Op_Raster || !op.tri_count) continue;
         void* table = g->raster[(size_t)op.raster_slot].draws_host;
         const bool geo = op.gpipe->kernel == Kernel_Geometry;
+        if (op.gpipe->kernel == Kernel_Voxelize) {
+            for (size_t i = 0; i < op.draws.size(); ++i) if (!fill_vox_draw(op.draws[i], ((PbrkVoxDraw*)table)[i])) return false;
+            continue;
+        }
         for (size_t i = 0; i < op.draws.size(); ++i)
             if (!(geo ? fill_geo_draw(op.draws[i], ((PbrkGeoDraw*)table)[i]) : fill_sun_draw(op.draws[i], ((PbrkRasterDraw*)table)[i]))) return false;
     }

@@ -11,7 +11,8 @@
  * that a test can compare it with the same sequence driven from another language.  With a last argument the 8-bit
  * frame is written as a binary PPM.  With `raster` as the ninth argument the three frames of the chain start with the geometry pass
  * (render.cpp:1076-1115) over a small built-in mesh (a checkered floor and a block), so the lighting pass shades a rasterised
- * G-buffer instead of the synthetic one; every other output is unchanged.
+ * G-buffer instead of the synthetic one, and the light grid's lit voxels are not a stand-in either: the sun depth pass and the
+ * voxelise pass (render.cpp:995-1020, 1039-1056) draw that mesh into it; every other output is unchanged.
  */
 #include "pbr_host.h"
 
@@ -186,8 +187,25 @@ int main(int argc, char** argv) {
         GPU_DestroyGraph(g); GPU_DestroyBuffer(buf);
     }
 
-    /* ---- voxel light grid: clear, a ground slab of lit voxels, three sweeps (directions y, z, x) ---- */
-    {
+    /* ---- voxel light grid: clear, a ground slab of lit voxels, three sweeps (directions y, z, x); with `raster` the lit voxels are
+     *      not a stand-in: the sun depth pass (render.cpp:995-1020) and the voxelise pass (:1039-1056) draw the built-in mesh ---- */
+    if (raster) {
+        PBR_Lightgrid* lg = PBR_MakeLightgrid(128);
+        PBR_SunDepthPass* sun = PBR_MakeSunDepthPass(2048);
+        PBR_VoxelizePass* vp = PBR_MakeVoxelizePass(lg, sun);
+        if (!lg || !sun || !vp) return 1;
+        GPU_Graph* g = GPU_MakeGraph();
+        PBR_RecordLightgridClear(lg, g);                                     /* render.cpp:1028 */
+        PBR_RecordSunDepthPass(sun, g, mesh, &globals);
+        PBR_RecordVoxelizePass(vp, g, mesh, &globals);
+        for (int k = 0; k < 3; ++k) PBR_RecordLightgridSweep(lg, g);         /* render.cpp:1061-1072 */
+        GPU_GraphSubmit(g); GPU_GraphWait(g);
+        for (uint32_t i = 0; i < GPUX_GraphTimedOpCount(g); ++i)
+            printf("time_ms %s %.6f\n", GPUX_GraphTimedOpName(g, i), GPUX_GraphTimedOpMs(g, i));
+        printf("lightgrid_voxelized 1\nlightgrid_bits_sum %.9e\n", checksum_texture_mip(PBR_LightgridTexture(lg), 0, 0));
+        GPU_DestroyGraph(g);
+        PBR_DestroyVoxelizePass(vp); PBR_DestroySunDepthPass(sun); PBR_DestroyLightgrid(lg);
+    } else {
         PBR_Lightgrid* lg = PBR_MakeLightgrid(128);                          /* render.cpp:678 */
         GPU_Texture* grid = PBR_LightgridTexture(lg);
         uint32_t bytes = (uint32_t)GPUX_TextureMipBytes(grid, 0);

@@ -193,7 +193,7 @@ PROTOTYPES = {
     "GPUX_InvalidateTexture": (None, [TexP]),
     "GPUX_TextureTotalBytes": (C.c_uint64, [TexP]), "GPUX_TextureMipOffset": (C.c_uint64, [TexP, U32]),
     "GPUX_MakeCubemapFromEquirect": (TexP, [VP, U32, U32, U32, C.c_int]),
-    "GPUX_RasterRejectedTriangles": (C.c_uint64, []),
+    "GPUX_RasterRejectedTriangles": (C.c_uint64, []), "GPUX_VoxelizeFragments": (C.c_uint64, []),
     "GPUX_GraphStream": (VP, [VP]), "GPUX_EnableOpTiming": (None, [C.c_int]), "GPUX_SetTileStreams": (None, [C.c_int]), "GPUX_GraphTimedOpCount": (U32, [VP]),
     "GPUX_GraphTimedOpName": (C.c_char_p, [VP, U32]), "GPUX_GraphTimedOpMs": (C.c_float, [VP, U32]), "GPUX_GraphSpanMs": (C.c_float, [VP]),
     # --- host layer (include/pbr_host.h) ---
@@ -246,6 +246,10 @@ PROTOTYPES = {
     "PBR_GeometryGlobalsBuffer": (BufP, [VP]), "PBR_GeometryPipeline": (VP, [VP, U32]), "PBR_GeometryRenderPass": (VP, [VP, U32]),
     "PBR_GeometryLayout": (VP, [VP]), "PBR_GeometryDescriptorSet": (VP, [VP, VP]),
     "PBR_RecordGeometryPass": (None, [VP, VP, VP, VP, C.POINTER(PBR_Globals), C.POINTER(C.c_float), C.POINTER(C.c_float), U32]),
+    "PBR_MakeVoxelizePass": (VP, [VP, VP]), "PBR_DestroyVoxelizePass": (None, [VP]), "PBR_VoxelizeGlobalsBuffer": (BufP, [VP]),
+    "PBR_VoxelizePipeline": (VP, [VP]), "PBR_VoxelizeRenderPass": (VP, [VP]), "PBR_VoxelizeLayout": (VP, [VP]),
+    "PBR_VoxelizeShadowSampler": (VP, [VP]), "PBR_VoxelizeDescriptorSet": (VP, [VP, VP, VP]),
+    "PBR_RecordVoxelizePass": (None, [VP, VP, VP, C.POINTER(PBR_Globals)]),
     "PBR_MakeLightgrid": (VP, [U32]), "PBR_DestroyLightgrid": (None, [VP]), "PBR_LightgridTexture": (TexP, [VP]),
     "PBR_LightgridSweepDirection": (U32, [VP]), "PBR_RecordLightgridClear": (None, [VP, VP]),
     "PBR_RecordLightgridSweep": (None, [VP, VP]), "PBR_RecordLightgridSweepLines": (None, [VP, VP, U32, U32, U32, U32, U32]),
@@ -287,6 +291,8 @@ PROTOTYPES = {
     "pbrk_raster_setup": (C.c_int, [VP, VP]), "pbrk_raster_tiles": (C.c_int, [VP, VP]),
     "pbrk_geometry_scratch_bytes": (C.c_size_t, [U32, C.c_int, C.c_int]),
     "pbrk_geometry_setup": (C.c_int, [VP, VP]), "pbrk_geometry_tiles": (C.c_int, [VP, VP]),
+    "pbrk_voxelize_scratch_bytes": (C.c_size_t, [U32, C.c_int, C.c_int]),
+    "pbrk_voxelize_cover": (C.c_int, [VP, VP]), "pbrk_voxelize_resolve": (C.c_int, [VP, VP]),
     "pbrk_mip_chain_rgba8": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, VP]),
 }
 
@@ -405,6 +411,14 @@ def make_material(images):
     if not m:
         raise RuntimeError("PBR_MakeMaterial failed")
     return m
+
+
+def make_voxelize_pass(lightgrid, sun_depth_pass):
+    """PBR_Lightgrid*, PBR_SunDepthPass* -> PBR_VoxelizePass* (K14: lightgrid_voxelize.glsl drawn into the grid, shadowed by the sun map)."""
+    p = lib().PBR_MakeVoxelizePass(lightgrid, sun_depth_pass)
+    if not p:
+        raise RuntimeError("PBR_MakeVoxelizePass failed")
+    return p
 
 
 def partition(specular_size, min_size, irradiance_size, env_size, world, rank):
