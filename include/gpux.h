@@ -50,6 +50,11 @@ GPU_API void GPUX_OpDrawRows(GPU_Graph* graph, uint32_t row0, uint32_t row1);
 GPU_API void GPUX_OpCopyTextureMipToBuffer(GPU_Graph* graph, GPU_Texture* src, uint32_t mip_level, GPU_Buffer* dst, uint32_t dst_offset);
 GPU_API void GPUX_OpCopyBufferToTextureMip(GPU_Graph* graph, GPU_Buffer* src, uint32_t src_offset, GPU_Texture* dst, uint32_t mip_level);
 GPU_API uint64_t GPUX_TextureMipBytes(const GPU_Texture* texture, uint32_t mip_level);   /* all layers of one mip */
+/* K15: a 2-D BC1 / BC3 / BC5 texture keeps its blocks (the copies above move those, format-true) and owns a decoded RGBA8UN image
+ * that the draws sample; a level is decoded when GPU_MakeTexture(data), GPU_OpCopyBufferToTexture or GPUX_OpCopyBufferToTextureMip
+ * writes it (memory written behind the backend's back is not followed).  This copies one level of the decoded image
+ * (width x height x 4 bytes, tight rows) into a buffer, for tests; any other texture is an error. */
+GPU_API void GPUX_OpCopyDecodedTextureMipToBuffer(GPU_Graph* graph, GPU_Texture* src, uint32_t mip_level, GPU_Buffer* dst, uint32_t dst_offset);
 GPU_API void* GPUX_TextureDevicePtr(GPU_Texture* texture, uint32_t mip_level);            /* for RCCL / interop */
 GPU_API void* GPUX_BufferDevicePtr(GPU_Buffer* buffer);
 GPU_API void* GPUX_GraphStream(GPU_Graph* graph);                                         /* hipStream_t */

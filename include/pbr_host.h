@@ -238,6 +238,30 @@ PBR_Material* PBR_MakeMaterial(uint32_t size, const void* base_color, const void
 void PBR_DestroyMaterial(PBR_Material* material);
 GPU_Texture* PBR_MaterialTexture(PBR_Material* material, uint32_t which);    /* 0 .. 3 in the order above */
 void PBR_MeshSetPartMaterial(PBR_Mesh* mesh, uint32_t part, PBR_Material* material);   /* the material is not owned by the mesh */
+/* a material over textures the caller made (2-D RGBA8UN, BC1, BC3 or BC5; e.g. PBR_MakeTextureFromDDSFile) and keeps owning: they
+ * must outlive the material.  A NULL slot gets the 1 x 1 dummy of render.cpp:787-793 (white, flat normal, black, black), owned by
+ * the material. */
+PBR_Material* PBR_MakeMaterialFromTextures(GPU_Texture* const tex[4]);
+
+/* ---- .dds material textures (N8 / K15): what asset_import.cpp:30-60 (LoadMeshTexture, through ddspp) accepts ---- */
+enum { PBR_DDS_MAX_LEVELS = 16 };
+typedef struct PBR_DDSInfo {
+    GPU_Format format;            /* BC1_RGBA_UN (DXT1, DXGI 71), BC3_RGBA_UN (DXT5, 77), BC5_UN (ATI2 / BC5U, 83), RGBA8UN (DXGI 28, R G B A byte masks) */
+    uint32_t width, height;
+    uint32_t level_count;         /* 1 .. PBR_DDS_MAX_LEVELS */
+    uint64_t level_offset[PBR_DDS_MAX_LEVELS], level_size[PBR_DDS_MAX_LEVELS];   /* bytes from the start of the file; inside it */
+} PBR_DDSInfo;
+/* 0 and *out filled, or a negative PBR_DDS_E_* (PBR_DDSErrorString names it): not a DDS, a truncated header or payload, a level
+ * count the file (or a full chain) cannot hold, a cube / volume / array file, extents of 0 or above 16384, any other pixel format */
+enum { PBR_DDS_E_ARG = -1, PBR_DDS_E_MAGIC = -2, PBR_DDS_E_TRUNCATED = -3, PBR_DDS_E_FORMAT = -4, PBR_DDS_E_LAYOUT = -5, PBR_DDS_E_EXTENT = -6,
+       PBR_DDS_E_LEVELS = -7 };
+int PBR_ParseDDS(const void* bytes, size_t size, PBR_DDSInfo* out);
+const char* PBR_DDSErrorString(int code);
+enum { PBR_DDS_FILE_MIPS = 1 };   /* also upload the file's levels below 0, down to the count GPU_TextureFlag_HasMipmaps gives */
+/* flags == 0: GPU_MakeTexture(format, w, h, 1, 0, level 0), the reference's behaviour.  With PBR_DDS_FILE_MIPS a file of one level
+ * still gives a one-level texture; a file of several must hold every level of the chain.  NULL on any error (message on stderr). */
+GPU_Texture* PBR_MakeTextureFromDDSMemory(const void* bytes, size_t size, uint32_t flags);
+GPU_Texture* PBR_MakeTextureFromDDSFile(const char* filepath, uint32_t flags);
 
 typedef struct PBR_GeometryPass PBR_GeometryPass;
 /* the two render passes and pipelines of the reference: pass i writes gb's four colour planes, PBR_PostVelocity(pp, i) and gb->depth */

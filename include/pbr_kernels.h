@@ -336,6 +336,13 @@ size_t pbrk_voxelize_scratch_bytes(uint32_t tri_count, int n, int n_again);   /*
 int pbrk_voxelize_cover(const PbrkVoxelizeArgs* args, void* stream);    /* K14.cover: clear the owner grid, setup + small boxes, large boxes */
 int pbrk_voxelize_resolve(const PbrkVoxelizeArgs* args, void* stream);  /* K14.resolve */
 
+/* ---- K15: block-compressed material textures (the .dds files of asset_import.cpp:30-60).  One level of BC1 / BC3 / BC5 blocks
+ *      (ceil(width / 4) x ceil(height / 4), row major, 8 or 16 bytes each; 8- resp. 16-byte aligned) -> width x height RGBA8UN, tight
+ *      rows (4-byte aligned), texels outside the level dropped.  Any extent from 1 to 16384.  Contract (bit replication, truncating
+ *      division, BC5 = (R, G, 0, 255)): csrc/bc_core.h, DESIGN.md K15. ---- */
+enum { PBRK_BC1_RGB = 0, PBRK_BC1_RGBA = 1, PBRK_BC3 = 2, PBRK_BC5 = 3 };
+int pbrk_bc_decode(int format, const void* blocks, int width, int height, void* rgba8, void* stream);
+
 /* ---- diagnostics: the device samplers of the widened passes evaluated at caller-supplied coordinates, so that tests can feed them
  *      NaN / inf / 1e30 / boundary values directly (a ray that has marched far away must never become an out-of-bounds read).
  *      which: 0 = LIGHTGRID (RGBA16F n^3, coords xyz), 1 = sampler2DShadow (R32F w x h, coords u, v, ref; result in out[0]),

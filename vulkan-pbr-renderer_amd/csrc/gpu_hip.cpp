@@ -66,6 +66,9 @@ struct TextureImpl {
     bool bordered_valid = false;                   // apron twin valid for levels >= bordered_from
     int bordered_from = 0;
     bool owns_memory = true;          // false: GPUX_MakeTextureExternal (caller-owned HBM, e.g. a torch tensor)
+    // BC1 / BC3 / BC5 2-D textures (K15): `dev` keeps the compressed blocks; `decoded` is what the draws sample -- RGBA8UN, all levels
+    // back to back like an RGBA8UN texture of the same extents; a level is decoded when it is written
+    void* decoded = nullptr; std::vector<size_t> decoded_offset;
     // 2x2-footprint "cells" twin of the levels with n <= 512 (levels cells_first.., back to back), built per level on demand
     void* cells = nullptr; int cells_first = 0; std::vector<size_t> cells_off; std::vector<char> cells_valid;
     void* lut_cells = nullptr; bool lut_cells_valid = false;      // RG16F 2-D textures sampled by the shade pass
@@ -88,7 +91,7 @@ struct GPU_RenderPass { GPU_RenderPassDesc desc; std::vector<GPU_TextureView> ta
 struct GPU_GraphicsPipeline { GPU_PipelineLayout* layout; GPU_RenderPass* pass; KernelId kernel; int shade_flags; bool blend_additive = false;
                               uint32_t vertex_stride = 0; /* sun depth pass: bytes per vertex (gpu_vulkan.c:1745-1762) */ };
 
-enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster };
+enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster, Op_CopyDecodedT2B };
 // one GPU_OpDrawIndexed of a raster job (K12 or K13): job triangles [first_tri, first_tri + index_count / 3), matrices from the set's
 // GLOBALS, the buffers bound at the draw and the pushed constants (K13 reads them: the skybox rebinds both inside the pass; K12 does not).
 // K14's GPU_OpDraw keeps its first vertex in first_index and reads its buffers from the set (SSBO0, SSBO1).
@@ -425,6 +428,28 @@ static bool is_rgba8_pow2(const TextureImpl* t) {
     const uint32_t w = t->base.width, h = t->base.height;
     return t->base.format == GPU_Format_RGBA8UN && t->base.layer_count == 1 && t->base.depth == 1 && (w & (w - 1)) == 0 && (h & (h - 1)) == 0;
 }
+// K15: the block-compressed formats and their decoded twin
+static int bc_kernel_format(GPU_Format f) {
+    switch (f) {
+    case GPU_Format_BC1_RGB_UN: return PBRK_BC1_RGB;
+    case GPU_Format_BC1_RGBA_UN: return PBRK_BC1_RGBA;
+    case GPU_Format_BC3_RGBA_UN: return PBRK_BC3;
+    case GPU_Format_BC5_UN: return PBRK_BC5;
+    default: return -1;
+    }
+}
+static bool is_bc_format(GPU_Format f) { return bc_kernel_format(f) >= 0; }
+// what the material slots of K13 / K14 accept: a 2-D one-layer RGBA8UN texture, or a BC texture that carries a decoded image
+static bool is_material_2d(const TextureImpl* t) {
+    if (t->base.layer_count != 1 || t->base.depth != 1) return false;
+    return t->base.format == GPU_Format_RGBA8UN || (is_bc_format(t->base.format) && t->decoded);
+}
+static const void* material_texels(const TextureImpl* t) { return t->decoded ? t->decoded : t->dev; }
+// decode one level of a BC texture from its blocks into the decoded image, on `st`
+static int decode_bc_level(TextureImpl* t, uint32_t mip, hipStream_t st) {
+    return pbrk_bc_decode(bc_kernel_format(t->base.format), (const char*)t->dev + t->mip_offset[mip], (int)mip_dim(t->base.width, mip),
+                          (int)mip_dim(t->base.height, mip), (char*)t->decoded + t->decoded_offset[mip], st);
+}
 static bool is_f4_cube(const TextureImpl* t) {
     return t->base.format == GPU_Format_RGBA32F && (t->base.flags & GPU_TextureFlag_Cubemap) && t->base.width == t->base.height && t->base.depth == 1;
 }
@@ -435,6 +460,11 @@ static GPU_Texture* make_texture_impl(GPU_Format format, uint32_t width, uint32_
     GPU_REQUIRE(width > 0 && height > 0 && depth > 0, nullptr, "%s: zero extent", fn);   // gpu_vulkan.c:1339
     GPU_FormatInfo fi = GPUX_GetFormatInfo(format);
     GPU_REQUIRE(fi.block_size > 0, nullptr, "%s: invalid format %d", fn, (int)format);
+    const bool bc = is_bc_format(format);
+    // a compressed chain cannot be generated (and the reference never asks for one): levels of a BC texture arrive by copies
+    GPU_REQUIRE(!(bc && data && (flags & GPU_TextureFlag_HasMipmaps)), nullptr,
+                "%s: GPU_TextureFlag_HasMipmaps with data is not supported for block-compressed formats (create the texture without data and copy every level in)", fn);
+    GPU_REQUIRE(!(bc && (width > 16384 || height > 16384)), nullptr, "%s: block-compressed textures are limited to 16384 x 16384", fn);
     TextureImpl* t = new TextureImpl();
     t->base.width = width; t->base.height = height; t->base.depth = depth;
     t->base.layer_count = (flags & GPU_TextureFlag_Cubemap) ? 6 : 1;
@@ -457,8 +487,20 @@ static GPU_Texture* make_texture_impl(GPU_Format format, uint32_t width, uint32_
         if (e != hipSuccess) { gpu_fail("%s: hipMalloc(%zu) failed: %s", fn, t->bytes, hipGetErrorString(e)); delete t; return nullptr; }
         HIP_OK(hipMemset(t->dev, 0, t->bytes));
     }
+    if (bc && t->base.layer_count == 1 && depth == 1) {                        // K15: the decoded image the draws sample
+        size_t doff = 0;
+        for (uint32_t m = 0; m < mips; ++m) { t->decoded_offset.push_back(doff); doff += (size_t)mip_dim(width, m) * mip_dim(height, m) * 4; }
+        hipError_t e = hipMalloc(&t->decoded, doff);
+        if (e != hipSuccess) { gpu_fail("%s: hipMalloc(%zu) for the decoded image failed: %s", fn, doff, hipGetErrorString(e)); t->decoded = nullptr; GPU_DestroyTexture(&t->base); return nullptr; }
+        HIP_OK(hipMemset(t->decoded, 0, doff));
+    }
     if (data) {
         HIP_OK(hipMemcpy(t->dev, data, (size_t)GPUX_TextureMipBytes(&t->base, 0), hipMemcpyHostToDevice));
+        if (t->decoded) {                                                      // level 0 is decoded before the call returns
+            int rc = decode_bc_level(t, 0, nullptr);
+            if (rc != PBRK_OK) gpu_fail("%s: K15 launch failed (%d)", fn, rc);
+            HIP_OK(hipStreamSynchronize(nullptr));
+        }
         if (mips > 1) {                                                        // gpu_vulkan.c:1444-1446
             if (is_rgba8_pow2(t)) {
                 int rc = pbrk_mip_chain_rgba8(t->dev, (int)width, (int)height, (int)mips, nullptr);
@@ -515,6 +557,7 @@ GPU_API void GPU_DestroyTexture(GPU_Texture* tex) {
     if (t->cells) (void)hipFree(t->cells);
     if (t->range_dev) (void)hipFree(t->range_dev);
     if (t->lut_cells) (void)hipFree(t->lut_cells);
+    if (t->decoded) (void)hipFree(t->decoded);
     delete t;
 }
 
@@ -1226,8 +1269,8 @@ static void record_raster_draw(GPU_Graph* g, const DrawParams& dp, uint32_t inde
         for (const char* name : {"TEX0", "TEX1", "TEX_ORM", "TEX_EMISSIVE"}) {
             Slot* sl = named_slot(dp.set, name);
             GPU_REQUIRE_V(sl && sl->tex, "%s: geometry pass: \"%s\" is not bound", fn, name);
-            GPU_REQUIRE_V(sl->tex->base.format == GPU_Format_RGBA8UN && sl->tex->base.layer_count == 1 && sl->tex->base.depth == 1 && sl->whole,
-                          "%s: geometry pass: \"%s\" must be a whole 2D RGBA8UN texture", fn, name);
+            GPU_REQUIRE_V(is_material_2d(sl->tex) && sl->whole,
+                          "%s: geometry pass: \"%s\" must be a whole 2D RGBA8UN, BC1, BC3 or BC5 texture", fn, name);
         }
         Slot* sm = named_slot(dp.set, "SAMPLER_LINEAR_WRAP");
         GPU_REQUIRE_V(sm && sm->sampler == &G.samplers[0], "%s: geometry pass: \"SAMPLER_LINEAR_WRAP\" must be GPU_SamplerLinearWrap()", fn);
@@ -1288,8 +1331,8 @@ static void record_voxelize_draw(GPU_Graph* g, const DrawParams& dp, uint32_t ve
                   "%s: voxelise pass: \"SUN_DEPTH_MAP\" must be a whole 2D D32F texture (render.cpp:676)", fn);
     for (const char* name : {"TEX0", "TEX_EMISSIVE"}) {
         Slot* sl = named_slot(dp.set, name);
-        GPU_REQUIRE_V(sl && sl->tex && sl->whole && sl->tex->base.format == GPU_Format_RGBA8UN && sl->tex->base.layer_count == 1 && sl->tex->base.depth == 1,
-                      "%s: voxelise pass: \"%s\" must be a whole 2D RGBA8UN texture", fn, name);
+        GPU_REQUIRE_V(sl && sl->tex && sl->whole && is_material_2d(sl->tex),
+                      "%s: voxelise pass: \"%s\" must be a whole 2D RGBA8UN, BC1, BC3 or BC5 texture", fn, name);
     }
     Slot* sm = named_slot(dp.set, "SAMPLER_LINEAR_WRAP");
     GPU_REQUIRE_V(sm && sm->sampler == &G.samplers[0], "%s: voxelise pass: \"SAMPLER_LINEAR_WRAP\" must be GPU_SamplerLinearWrap()", fn);
@@ -1387,6 +1430,21 @@ static void record_t2b(GPU_Graph* g, GPU_Texture* src, uint32_t mip, GPU_Buffer*
 GPU_API void GPU_OpCopyTextureToBuffer(GPU_Graph* g, GPU_Texture* src, GPU_Buffer* dst) { REC_GUARD(g); record_t2b(g, src, 0, dst, 0, __func__); }   // mip 0 only (gpu_vulkan.c:2948)
 GPU_API void GPUX_OpCopyTextureMipToBuffer(GPU_Graph* g, GPU_Texture* src, uint32_t mip, GPU_Buffer* dst, uint32_t off) { REC_GUARD(g); record_t2b(g, src, mip, dst, off, __func__); }
 
+// K15 test accessor: one level of a BC texture's decoded image (RGBA8UN, tight rows) -> buffer
+GPU_API void GPUX_OpCopyDecodedTextureMipToBuffer(GPU_Graph* g, GPU_Texture* src, uint32_t mip, GPU_Buffer* dst, uint32_t dst_offset) {
+    REC_GUARD(g);
+    const char* fn = "GPUX_OpCopyDecodedTextureMipToBuffer";
+    GPU_REQUIRE_V(g->in_pass == nullptr, "%s: inside a render pass", fn);
+    GPU_REQUIRE_V(src && dst && mip < src->mip_level_count, "%s: bad arguments", fn);
+    TextureImpl* t = (TextureImpl*)src;
+    GPU_REQUIRE_V(is_bc_format(src->format) && t->decoded, "%s: the texture has no decoded image (only 2-D BC1 / BC3 / BC5 textures do)", fn);
+    const uint64_t bytes = (uint64_t)mip_dim(src->width, mip) * mip_dim(src->height, mip) * 4;
+    GPU_REQUIRE_V((uint64_t)dst_offset + bytes <= dst->size, "%s: buffer too small (%u bytes for %llu)", fn, dst->size, (unsigned long long)bytes);
+    Op op; op.kind = Op_CopyDecodedT2B; op.name = "copy.decoded_texture_to_buffer";
+    op.tex = t; op.mip = mip; op.buf = (BufferImpl*)dst; op.off_b = dst_offset; op.size = bytes;
+    g->ops.push_back(op);
+}
+
 GPU_API void GPU_OpGenerateMipmaps(GPU_Graph* g, GPU_Texture* tex) {
     REC_GUARD(g);
     GPU_REQUIRE_V(tex, "GPU_OpGenerateMipmaps: NULL texture");
@@ -1400,6 +1458,7 @@ GPU_API void GPU_OpBlit(GPU_Graph* g, const GPU_OpBlitInfo* info) {
     GPU_REQUIRE_V(g->in_pass == nullptr, "GPU_OpBlit: inside a render pass");                                        // gpu_vulkan.c:2787
     GPU_REQUIRE_V(info && info->src_texture && info->dst_texture, "GPU_OpBlit: NULL argument");
     const GPU_Texture* s = info->src_texture; const GPU_Texture* d = info->dst_texture;
+    GPU_REQUIRE_V(!is_bc_format(s->format) && !is_bc_format(d->format), "GPU_OpBlit: block-compressed textures cannot be blitted (copy their levels through a buffer)");
     if (s == d) GPU_REQUIRE_V(info->dst_mip_level != info->src_mip_level || info->src_layer != info->dst_layer, "GPU_OpBlit: blit of a subresource onto itself");   // :2792
     GPU_REQUIRE_V(info->src_mip_level < s->mip_level_count && info->dst_mip_level < d->mip_level_count && info->src_layer < s->layer_count && info->dst_layer < d->layer_count,
                   "GPU_OpBlit: bad subresource");
@@ -1436,6 +1495,7 @@ GPU_API void GPU_OpBlit(GPU_Graph* g, const GPU_OpBlitInfo* info) {
 static void record_clear(GPU_Graph* g, GPU_Texture* dst, uint32_t mip, int mode, const float* f, const uint32_t* u, const char* fn) {
     GPU_REQUIRE_V(g->in_pass == nullptr, "%s: inside a render pass", fn);
     GPU_REQUIRE_V(dst && (mip == GPU_MIP_LEVEL_ALL || mip < dst->mip_level_count), "%s: bad texture / mip", fn);
+    GPU_REQUIRE_V(!is_bc_format(dst->format), "%s: block-compressed textures cannot be cleared (copy their levels in from a buffer)", fn);
     Op op; op.kind = Op_Clear; op.name = "clear"; op.tex = (TextureImpl*)dst; op.mip = mip; op.clear_mode = mode;
     for (int i = 0; i < 4; ++i) { op.clear[i] = f ? f[i] : 0.0f; op.cleari[i] = u ? u[i] : 0; }
     g->ops.push_back(op);
@@ -1881,8 +1941,19 @@ static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
                                   per_layer * op.layer_count, hipMemcpyDefault, st));
         });
         op.tex->bordered_valid = false; op.tex->lut_cells_valid = false;
+        if (op.tex->decoded) {                                                 // K15: the level that was written, and only it
+            timed(g, "K15.bc_decode", ev_used, [&] {
+                int rc = decode_bc_level(op.tex, op.mip, st);
+                if (rc != PBRK_OK) gpu_fail("K15 launch failed (%d)", rc);
+            });
+        }
         return;
     }
+    case Op_CopyDecodedT2B:
+        timed(g, op.name, ev_used, [&] {
+            HIP_OK(hipMemcpyAsync((char*)op.buf->dev + op.off_b, (const char*)op.tex->decoded + op.tex->decoded_offset[op.mip], op.size, hipMemcpyDefault, st));
+        });
+        return;
     case Op_CopyT2B:
         timed(g, op.name, ev_used, [&] {
             HIP_OK(hipMemcpyAsync((char*)op.buf->dev + op.off_b, (const char*)op.tex->dev + op.tex->mip_offset[op.mip],
@@ -1960,7 +2031,7 @@ static bool op_replayable(const Op& op) {
     case Op_Dispatch: return op.cpipe->kernel == Kernel_LightgridSweep;
     case Op_MipGen: return true;
     case Op_Blit: return true;
-    case Op_CopyB2B: case Op_CopyB2T: case Op_CopyT2B: return false;          // host pointers may be involved: keep them out of captures
+    case Op_CopyB2B: case Op_CopyB2T: case Op_CopyT2B: case Op_CopyDecodedT2B: return false;          // host pointers may be involved: keep them out of captures
     case Op_Raster: return false;                                             // its draw table is uploaded from pinned staging at submit
     case Op_Clear: {
         const uint32_t tb = op.tex->texel_bytes;                              // one fill launch; the staged form of other texel sizes synchronises
@@ -2110,7 +2181,7 @@ static bool fill_geo_draw(const RasterDraw& d, PbrkGeoDraw& o) {          // bot
     static const char* const names[4] = {"TEX0", "TEX1", "TEX_ORM", "TEX_EMISSIVE"};
     for (int k = 0; k < 4; ++k) {
         const TextureImpl* t = named_slot(d.set, names[k])->tex;
-        o.tex[k].texels = t->dev; o.tex[k].width = (int)t->base.width; o.tex[k].height = (int)t->base.height; o.tex[k].levels = (int)t->base.mip_level_count;
+        o.tex[k].texels = material_texels(t); o.tex[k].width = (int)t->base.width; o.tex[k].height = (int)t->base.height; o.tex[k].levels = (int)t->base.mip_level_count;
     }
     o.vertices = d.vb->dev; o.indices = (const uint32_t*)d.ib->dev; o.vertex_count = d.vb->base.size / 44u;
     o.first_tri = d.first_tri; o.first_index = d.first_index; o.vertex_offset = d.vertex_offset;
@@ -2127,7 +2198,7 @@ static bool fill_vox_draw(const RasterDraw& d, PbrkVoxDraw& o) {          // sun
     static const char* const names[2] = {"TEX0", "TEX_EMISSIVE"};
     for (int k = 0; k < 2; ++k) {
         const TextureImpl* t = named_slot(d.set, names[k])->tex;
-        o.tex[k].texels = t->dev; o.tex[k].width = (int)t->base.width; o.tex[k].height = (int)t->base.height; o.tex[k].levels = (int)t->base.mip_level_count;
+        o.tex[k].texels = material_texels(t); o.tex[k].width = (int)t->base.width; o.tex[k].height = (int)t->base.height; o.tex[k].levels = (int)t->base.mip_level_count;
     }
     return true;
 }

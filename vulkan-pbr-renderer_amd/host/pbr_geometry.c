@@ -14,7 +14,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-struct PBR_Material { GPU_Texture* tex[4]; };
+struct PBR_Material { GPU_Texture* tex[4]; bool owned[4]; };
 
 PBR_Material* PBR_MakeMaterial(uint32_t size, const void* base_color, const void* normal, const void* orm, const void* emissive) {
     if (!size || (size & (size - 1)) || !base_color || !normal || !orm || !emissive) return NULL;
@@ -24,13 +24,29 @@ PBR_Material* PBR_MakeMaterial(uint32_t size, const void* base_color, const void
     for (int i = 0; i < 4; ++i) {
         m->tex[i] = GPU_MakeTexture(GPU_Format_RGBA8UN, size, size, 1, GPU_TextureFlag_HasMipmaps, src[i]);
         if (!m->tex[i]) { PBR_DestroyMaterial(m); return NULL; }
+        m->owned[i] = true;
+    }
+    return m;
+}
+
+PBR_Material* PBR_MakeMaterialFromTextures(GPU_Texture* const tex[4]) {
+    if (!tex) return NULL;
+    PBR_Material* m = (PBR_Material*)calloc(1, sizeof *m);
+    if (!m) return NULL;
+    /* render.cpp:787-793: dummy_white, dummy_normal_map, dummy_black, dummy_black */
+    static const uint32_t dummy[4] = {0xFFFFFFFFu, 0xFFFF7F7Fu, 0x00000000u, 0x00000000u};
+    for (int i = 0; i < 4; ++i) {
+        if (tex[i]) { m->tex[i] = tex[i]; continue; }
+        m->tex[i] = GPU_MakeTexture(GPU_Format_RGBA8UN, 1, 1, 1, 0, &dummy[i]);
+        if (!m->tex[i]) { PBR_DestroyMaterial(m); return NULL; }
+        m->owned[i] = true;
     }
     return m;
 }
 
 void PBR_DestroyMaterial(PBR_Material* m) {
     if (!m) return;
-    for (int i = 0; i < 4; ++i) GPU_DestroyTexture(m->tex[i]);
+    for (int i = 0; i < 4; ++i) if (m->owned[i]) GPU_DestroyTexture(m->tex[i]);
     free(m);
 }
 

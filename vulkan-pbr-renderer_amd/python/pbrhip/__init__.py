@@ -18,6 +18,11 @@ LIB_PATH = os.path.join(PKG_ROOT, "libgpu_hip.so")
  Format_RGBA16F, Format_R32F, Format_RG32F, Format_RGB32F, Format_RGBA32F, Format_R8I, Format_R16I, Format_RG16I,
  Format_RGBA16I, Format_R32I, Format_RG32I, Format_RGB32I, Format_RGBA32I, Format_R64I, Format_D16UN,
  Format_D32F_Or_X8D24UN) = range(24)
+Format_BC1_RGB_UN, Format_BC1_RGBA_UN, Format_BC3_RGBA_UN, Format_BC5_UN = 26, 27, 28, 29
+BC_BLOCK_BYTES = {Format_BC1_RGB_UN: 8, Format_BC1_RGBA_UN: 8, Format_BC3_RGBA_UN: 16, Format_BC5_UN: 16}
+PBRK_BC1_RGB, PBRK_BC1_RGBA, PBRK_BC3, PBRK_BC5 = 0, 1, 2, 3
+PBR_DDS_FILE_MIPS = 1
+PBR_DDS_MAX_LEVELS = 16
 TextureFlag_StorageImage, TextureFlag_RenderTarget, TextureFlag_HasMipmaps, TextureFlag_Cubemap = 1, 2, 4, 8
 BufferFlag_CPU, BufferFlag_GPU, BufferFlag_StorageBuffer = 1, 2, 4
 Shade_IBL, Shade_LightShafts = 1, 2
@@ -133,6 +138,11 @@ class GPU_GraphicsPipelineDesc(C.Structure):
                 ("blending_mode_additive", C.c_bool), ("enable_conservative_rasterization", C.c_bool), ("cull_mode", C.c_int)]
 
 
+class PBR_DDSInfo(C.Structure):
+    _fields_ = [("format", C.c_int), ("width", C.c_uint32), ("height", C.c_uint32), ("level_count", C.c_uint32),
+                ("level_offset", C.c_uint64 * PBR_DDS_MAX_LEVELS), ("level_size", C.c_uint64 * PBR_DDS_MAX_LEVELS)]
+
+
 class PBR_MeshPart(C.Structure):
     _fields_ = [("first_index", C.c_uint32), ("index_count", C.c_uint32)]
 
@@ -188,6 +198,7 @@ PROTOTYPES = {
     "GPUX_OpDispatchLines": (None, [VP, U32, U32, U32, U32]),
     "GPUX_SetShadeFlags": (None, [VP, C.c_int]), "GPUX_OpDrawRows": (None, [VP, U32, U32]),
     "GPUX_OpCopyTextureMipToBuffer": (None, [VP, TexP, U32, BufP, U32]), "GPUX_OpCopyBufferToTextureMip": (None, [VP, BufP, U32, TexP, U32]),
+    "GPUX_OpCopyDecodedTextureMipToBuffer": (None, [VP, TexP, U32, BufP, U32]),
     "GPUX_FoldedBlitCount": (C.c_uint64, []), "GPUX_SetGraphOverlap": (None, [C.c_int]), "GPUX_OverlappedSubmitCount": (C.c_uint64, []), "GPUX_TextureMipBytes": (C.c_uint64, [TexP, U32]), "GPUX_TextureDevicePtr": (VP, [TexP, U32]), "GPUX_BufferDevicePtr": (VP, [BufP]),
     "GPUX_MakeTextureExternal": (TexP, [C.c_int, U32, U32, U32, C.c_int, VP, C.c_uint64]),
     "GPUX_InvalidateTexture": (None, [TexP]),
@@ -242,6 +253,9 @@ PROTOTYPES = {
     "PBR_RecordSunDepthPass": (None, [VP, VP, VP, C.POINTER(PBR_Globals)]),
     "PBR_MakeMaterial": (VP, [U32, VP, VP, VP, VP]), "PBR_DestroyMaterial": (None, [VP]), "PBR_MaterialTexture": (TexP, [VP, U32]),
     "PBR_MeshSetPartMaterial": (None, [VP, U32, VP]),
+    "PBR_MakeMaterialFromTextures": (VP, [C.POINTER(TexP)]),
+    "PBR_ParseDDS": (C.c_int, [VP, C.c_size_t, C.POINTER(PBR_DDSInfo)]), "PBR_DDSErrorString": (C.c_char_p, [C.c_int]),
+    "PBR_MakeTextureFromDDSMemory": (TexP, [VP, C.c_size_t, U32]), "PBR_MakeTextureFromDDSFile": (TexP, [C.c_char_p, U32]),
     "PBR_MakeGeometryPass": (VP, [C.POINTER(PBR_GBuffer), VP, U32, U32]), "PBR_DestroyGeometryPass": (None, [VP]),
     "PBR_GeometryGlobalsBuffer": (BufP, [VP]), "PBR_GeometryPipeline": (VP, [VP, U32]), "PBR_GeometryRenderPass": (VP, [VP, U32]),
     "PBR_GeometryLayout": (VP, [VP]), "PBR_GeometryDescriptorSet": (VP, [VP, VP]),
@@ -294,6 +308,7 @@ PROTOTYPES = {
     "pbrk_voxelize_scratch_bytes": (C.c_size_t, [U32, C.c_int, C.c_int]),
     "pbrk_voxelize_cover": (C.c_int, [VP, VP]), "pbrk_voxelize_resolve": (C.c_int, [VP, VP]),
     "pbrk_mip_chain_rgba8": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, VP]),
+    "pbrk_bc_decode": (C.c_int, [C.c_int, VP, C.c_int, C.c_int, VP, VP]),
 }
 
 _LIB = None
@@ -376,6 +391,59 @@ def read_mip(tex, mip=0):
     L.GPU_DestroyGraph(g)
     L.GPU_DestroyBuffer(buf)
     return arr if (t.layer_count > 1 or d > 1) else arr[0]
+
+
+def _read_back(record, nbytes):
+    L = lib()
+    buf = L.GPU_MakeBuffer(nbytes, BufferFlag_CPU, None)
+    g = L.GPU_MakeGraph()
+    record(g, buf)
+    L.GPU_GraphSubmit(g)
+    L.GPU_GraphWait(g)
+    raw = C.string_at(buf.contents.data, nbytes)
+    L.GPU_DestroyGraph(g)
+    L.GPU_DestroyBuffer(buf)
+    return raw
+
+
+def read_mip_bytes(tex, mip=0):
+    """One mip as the texture stores it (for a BC texture: its blocks) -> bytes."""
+    L = lib()
+    return _read_back(lambda g, buf: L.GPUX_OpCopyTextureMipToBuffer(g, tex, mip, buf, 0), L.GPUX_TextureMipBytes(tex, mip))
+
+
+def read_decoded_mip(tex, mip=0):
+    """One level of a BC texture's decoded image (K15) -> uint8 [h][w][4]."""
+    L = lib()
+    t = tex.contents
+    w, h = max(1, t.width >> mip), max(1, t.height >> mip)
+    raw = _read_back(lambda g, buf: L.GPUX_OpCopyDecodedTextureMipToBuffer(g, tex, mip, buf, 0), w * h * 4)
+    return np.frombuffer(raw, np.uint8).reshape(h, w, 4).copy()
+
+
+def parse_dds(data: bytes):
+    """PBR_ParseDDS -> PBR_DDSInfo, or raises ValueError with the parser's reason."""
+    info = PBR_DDSInfo()
+    rc = lib().PBR_ParseDDS(data, len(data), C.byref(info))
+    if rc != 0:
+        raise ValueError(lib().PBR_DDSErrorString(rc).decode())
+    return info
+
+
+def make_texture_from_dds_file(path, flags=0):
+    t = lib().PBR_MakeTextureFromDDSFile(os.fsencode(path), flags)
+    if not t:
+        raise RuntimeError("PBR_MakeTextureFromDDSFile failed")
+    return t
+
+
+def make_material_from_textures(textures):
+    """four GPU_Texture* (or None: the 1 x 1 dummy of that slot) -> PBR_Material* that does not own them."""
+    arr = (TexP * 4)(*[t if t is not None else TexP() for t in textures])
+    m = lib().PBR_MakeMaterialFromTextures(arr)
+    if not m:
+        raise RuntimeError("PBR_MakeMaterialFromTextures failed")
+    return m
 
 
 def fill_globals(pos, ori=None, fov=75.0, aspect=16.0 / 9.0, near=0.02, far=1.0e4, sun_angle=(56.5, 97.0), frame_idx=0):
