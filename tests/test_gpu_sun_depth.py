@@ -342,6 +342,74 @@ def test_sun_depth_replay_overlap_and_globals_snapshot(gpu):
     L.PBR_DestroyMesh(mesh); L.PBR_DestroySunDepthPass(sp)
 
 
+def _timed_names(L, g):
+    return [L.GPUX_GraphTimedOpName(g, i).decode() for i in range(L.GPUX_GraphTimedOpCount(g))]
+
+
+def test_sun_depth_rebound_buffers_split_the_job_64(gpu):
+    """Two meshes with vertex / index buffers of their own drawn in one render-pass instance as A's first half, B, A's second half:
+    every change of the bound pair starts a new job (three K12.setup / K12.tiles), in order, onto the same map.  Binding the same
+    pair again between two draws does not.  Vertices on pixel centres, one depth per triangle, all depths distinct."""
+    import pbrhip
+    L = gpu
+    W, m = 64, 40
+    rng = np.random.default_rng(0x5EED1206)
+    depth = (rng.permutation(2 * m) + 1).astype(np.float64) / (2 * m + 2)
+    pos = [np.concatenate([(rng.integers(0, W, (3 * m, 2)) + 0.5), np.repeat(depth[k * m:(k + 1) * m], 3)[:, None]], 1).astype(np.float32) for k in range(2)]
+    idx = np.arange(3 * m, dtype=np.uint32)
+    h = 3 * (m // 2)
+    M = R.pixel_matrix(W, W)
+    ones = np.ones((W, W), np.float32)
+    want1, r1 = R.raster(ones, pos[0], idx, [(h, 1, 0, 0, M)])
+    want2, r2 = R.raster(want1, pos[1], idx, [(3 * m, 1, 0, 0, M)])
+    want3, r3 = R.raster(want2, pos[0], idx, [(3 * m - h, 1, h, 0, M)])
+    both, r4 = R.raster(ones, pos[0], idx, [(h, 1, 0, 0, M), (3 * m - h, 1, h, 0, M)])
+    assert r1 == r2 == r3 == r4 == 0
+    assert (want1 < ones).any() and (want2 < want1).any() and (want3 < want2).any() and (both < want1).any()     # every job shows in the map
+    sp = L.PBR_MakeSunDepthPass(W)
+    s = L.PBR_SunDepthDescriptorSet(sp)
+    _write_globals(L.PBR_SunDepthGlobalsBuffer(sp), _globals(M))
+    meshes = [pbrhip.make_mesh(p, idx, [(0, 3 * m)]) for p in pos]
+    graphs = [L.GPU_MakeGraph(), L.GPU_MakeGraph()]
+
+    def record(g, steps):
+        """steps: (mesh whose pair is bound in front of the draw, index_count, first_index)"""
+        L.GPU_OpClearDepthStencil(g, L.PBR_SunDepthTexture(sp), ALL)
+        L.GPU_OpPrepareRenderPass(g, L.PBR_SunDepthRenderPass(sp))
+        params = [L.GPU_OpPrepareDrawParams(g, L.PBR_SunDepthPipeline(sp), s) for _ in steps]
+        L.GPU_OpBeginRenderPass(g)
+        for p, (mesh, count, first) in zip(params, steps):
+            L.GPU_OpBindVertexBuffer(g, L.PBR_MeshVertexBuffer(mesh))
+            L.GPU_OpBindIndexBuffer(g, L.PBR_MeshIndexBuffer(mesh))
+            L.GPU_OpBindDrawParams(g, p)
+            L.GPU_OpDrawIndexed(g, count, 1, first, 0, 0)
+        L.GPU_OpEndRenderPass(g)
+
+    L.GPUX_EnableOpTiming(1)
+    try:
+        g = graphs[0]
+        record(g, [(meshes[0], h, 0), (meshes[1], 3 * m, 0), (meshes[0], 3 * m - h, h)])
+        L.GPU_GraphSubmit(g); L.GPU_GraphWait(g)
+        names = _timed_names(L, g)
+        print(f"A half, B, A half: timed ops {names}")
+        assert names.count("K12.setup") == 3 and names.count("K12.tiles") == 3, names
+        _check("rebound buffers 64^2: three jobs", _map(L, sp), want3)
+        g = graphs[1]
+        record(g, [(meshes[0], h, 0), (meshes[0], 3 * m - h, h)])
+        L.GPU_GraphSubmit(g); L.GPU_GraphWait(g)
+        names = _timed_names(L, g)
+        print(f"A half, the same pair bound again, A half: timed ops {names}")
+        assert names.count("K12.setup") == 1 and names.count("K12.tiles") == 1, names
+        _check("rebound buffers 64^2: the same pair again is one job", _map(L, sp), both)
+    finally:
+        L.GPUX_EnableOpTiming(0)
+    for g in graphs:
+        L.GPU_DestroyGraph(g)
+    for mesh in meshes:
+        L.PBR_DestroyMesh(mesh)
+    L.PBR_DestroySunDepthPass(sp)
+
+
 def _pipeline_desc(L, sp, **kw):
     import pbrhip
     path = b"shaders/sun_depth_pass.glsl"

@@ -197,6 +197,73 @@ def test_voxelize_second_pass_without_clear_replay_overlap_and_globals_snapshot(
     rig.destroy()
 
 
+def test_voxelize_two_grids_in_one_pass_32(gpu):
+    """One render-pass instance whose draws name two light grids in turn: d0 -> A, d1 -> B, d1 -> A, d0 -> B.  A draw that names
+    another grid than the open job's starts a new job (four K14.cover / K14.resolve), and the jobs run in order: a later job
+    overwrites exactly the voxels it owns, so each grid is what one job over its draws in that order leaves."""
+    import pbrhip
+    L = gpu
+    scene = S.cases_scene(32)
+    N = scene["N"]
+    d0, d1 = S.ref_draws(scene, scene["passes"][0])
+    rng = np.random.default_rng(0x5EED1407)
+    prior = [rng.uniform(0.0, 4.0, (N, N, N, 4)).astype(np.float16) for _ in range(2)]
+    want_a, info = V.voxelize(prior[0], scene["sun_map"], [d0, d1], N)
+    want_b, info_b = V.voxelize(prior[1], scene["sun_map"], [d1, d0], N)
+    last = scene["expect"]["last"]
+    shared = (info["tri"] == last) & (info["hits"] > 1)                      # d1 has one triangle: any other hit is one of d0's
+    print(f"two grids 32^3: {int(shared.sum())} voxels of A are owned by d0's job and then by d1's")
+    assert shared.sum() > 0 and (info["tri"] >= 0).sum() > shared.sum() and (info_b["tri"] >= 0).sum() > 0
+    rig = Rig(L, scene)
+    lg_b = L.PBR_MakeLightgrid(N)
+    tex = [rig.tex, L.PBR_LightgridTexture(lg_b)]
+    for t, p in zip(tex, prior):
+        pbrhip.upload_mip(t, 0, p)
+    rig.write_globals(globals_of(scene))
+    lay, mesh = L.PBR_VoxelizeLayout(rig.vp), rig.meshes[0]
+
+    def make_set(img0, mat):
+        s = L.GPU_InitDescriptorSet(None, lay)
+        L.GPU_SetBufferBinding(s, 0, L.PBR_VoxelizeGlobalsBuffer(rig.vp))
+        L.GPU_SetBufferBinding(s, 1, L.PBR_MeshVertexBuffer(mesh))
+        L.GPU_SetBufferBinding(s, 2, L.PBR_MeshIndexBuffer(mesh))
+        L.GPU_SetStorageImageBinding(s, 3, img0, 0)
+        L.GPU_SetTextureBinding(s, 4, L.PBR_SunDepthTexture(rig.sp))
+        L.GPU_SetTextureBinding(s, 5, L.PBR_MaterialTexture(mat, 0))
+        L.GPU_SetTextureBinding(s, 6, L.PBR_MaterialTexture(mat, 3))
+        L.GPU_SetSamplerBinding(s, 7, L.PBR_VoxelizeShadowSampler(rig.vp))
+        L.GPU_SetSamplerBinding(s, 8, L.GPU_SamplerLinearWrap())
+        L.GPU_FinalizeDescriptorSet(s)
+        return s
+
+    draws = scene["passes"][0]["draws"]
+    order = [(0, 0), (1, 1), (1, 0), (0, 1)]                                  # (draw, grid)
+    sets = [make_set(tex[t], rig.mats[draws[d]["material"]]) for d, t in order]
+    g = L.GPU_MakeGraph()
+    L.GPU_OpPrepareRenderPass(g, L.PBR_VoxelizeRenderPass(rig.vp))
+    params = [L.GPU_OpPrepareDrawParams(g, L.PBR_VoxelizePipeline(rig.vp), s) for s in sets]
+    L.GPU_OpBeginRenderPass(g)
+    for p, (d, t) in zip(params, order):
+        L.GPU_OpBindDrawParams(g, p)
+        L.GPU_OpDraw(g, draws[d]["vertex_count"], draws[d]["instance_count"], draws[d]["first_vertex"], 0)
+    L.GPU_OpEndRenderPass(g)
+    L.GPUX_EnableOpTiming(1)
+    try:
+        L.GPU_GraphSubmit(g); L.GPU_GraphWait(g)
+        names = [L.GPUX_GraphTimedOpName(g, i).decode() for i in range(L.GPUX_GraphTimedOpCount(g))]
+    finally:
+        L.GPUX_EnableOpTiming(0)
+    print(f"two grids 32^3: timed ops {names}")
+    assert names.count("K14.cover") == 4 and names.count("K14.resolve") == 4, names
+    check("two grids 32^3: grid A = [d0, d1]", pbrhip.read_mip(tex[0], 0), want_a)
+    check("two grids 32^3: grid B = [d1, d0]", pbrhip.read_mip(tex[1], 0), want_b)
+    L.GPU_DestroyGraph(g)
+    for s in sets:
+        L.GPU_DestroyDescriptorSet(s)
+    L.PBR_DestroyLightgrid(lg_b)
+    rig.destroy()
+
+
 class GPU_SamplerDesc(C.Structure):                                         # include/gpu_hip.h
     _fields_ = [("min_filter", C.c_int), ("mag_filter", C.c_int), ("mipmap_mode", C.c_int), ("address_modes", C.c_int * 3),
                 ("mip_lod_bias", C.c_float), ("min_lod", C.c_float), ("max_lod", C.c_float), ("compare_op", C.c_int)]

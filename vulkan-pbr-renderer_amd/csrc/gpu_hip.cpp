@@ -89,13 +89,14 @@ struct GPU_DescriptorArena { std::vector<GPU_DescriptorSet*> sets; };
 struct GPU_ComputePipeline { GPU_PipelineLayout* layout; KernelId kernel; };
 struct GPU_RenderPass { GPU_RenderPassDesc desc; std::vector<GPU_TextureView> targets; };
 struct GPU_GraphicsPipeline { GPU_PipelineLayout* layout; GPU_RenderPass* pass; KernelId kernel; int shade_flags; bool blend_additive = false;
-                              uint32_t vertex_stride = 0; /* sun depth pass: bytes per vertex (gpu_vulkan.c:1745-1762) */ };
+                              uint32_t vertex_stride = 0; /* raster kinds: bytes per vertex (gpu_vulkan.c:1745-1762) */
+                              const struct RasterKind* raster = nullptr; /* K12 / K13 / K14: the row of its raster kind */ };
 
 enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster, Op_CopyDecodedT2B };
-// one GPU_OpDrawIndexed of a raster job (K12 or K13): job triangles [first_tri, first_tri + index_count / 3), matrices from the set's
-// GLOBALS, the buffers bound at the draw and the pushed constants (K13 reads them: the skybox rebinds both inside the pass; K12 does not).
-// K14's GPU_OpDraw keeps its first vertex in first_index and reads its buffers from the set (SSBO0, SSBO1).
-struct RasterDraw { GPU_DescriptorSet* set; uint32_t first_tri, first_index, vertex_offset; BufferImpl* vb = nullptr; BufferImpl* ib = nullptr; float push[4] = {0, 0, 0, 0}; };
+// one draw of a raster job: job triangles from first_tri on, matrices from the set's GLOBALS, the buffers and the target its kind
+// names (K12 / K13: the buffers bound at the draw; K14: SSBO0 / SSBO1 of the set, first_index = its first vertex) and the pushed
+// constants (K13 reads them: the skybox rebinds both inside the pass)
+struct RasterDraw { GPU_DescriptorSet* set; uint32_t first_tri, first_index, vertex_offset; BufferImpl* vb = nullptr; BufferImpl* ib = nullptr; TextureImpl* target = nullptr; float push[4] = {0, 0, 0, 0}; };
 struct Op {
     OpKind kind;
     std::string name;
@@ -120,21 +121,15 @@ struct Op {
     bool folded = false;
     TextureImpl* blend_tex = nullptr; uint32_t blend_mip = 0;
     bool skip_level0 = false;                      // Op_Clear of all levels whose level 0 the next op overwrites entirely
-    // raster job (Op_Raster, K12, K13 or K14): the draws of one render-pass instance; tex = depth target (K14: the light grid), buf =
-    // vertices and buf2 = indices of the job's first draw (K12 has one pair per job)
+    // raster job (Op_Raster, kind: gpipe->raster): the draws of one render-pass instance that go together; tex = depth target (K14: the
+    // light grid), buf = vertices and buf2 = indices of the job's first draw (K12 has one pair per job)
     std::vector<RasterDraw> draws;
-    uint32_t tri_count = 0, vertex_stride = 0;
+    uint32_t tri_count = 0;
     int raster_slot = -1;                          // GPU_Graph::raster scratch of this job
 };
 struct DrawParams { GPU_GraphicsPipeline* pipeline; GPU_DescriptorSet* set; };
-// per raster job (K12, K13 or K14) of a graph, kept across submissions: bins / records (device), the draw table (device + pinned staging)
+// per raster job of a graph, kept across submissions: bins / records (device), the draw table (device + pinned staging)
 struct RasterScratch { void* dev = nullptr; size_t dev_bytes = 0; void* draws_dev = nullptr; void* draws_host = nullptr; size_t draws_cap = 0; /* bytes */ };
-// what the three raster jobs differ in on the host, beside the kernel-specific halves of record_raster_draw, snapshot_raster_draws and exec_raster
-struct RasterKind { const char* op_name; const char* tag; const char* shader; const char* pass_name; GPU_CullMode cull; const char* cull_name; size_t draw_bytes; size_t (*scratch_bytes)(uint32_t, int, int); };
-static const RasterKind kSunDepthJob = {"K12.sun_depth", "K12", "sun_depth_pass.glsl", "sun depth", GPU_CullMode_TwoSided, "GPU_CullMode_TwoSided only", sizeof(PbrkRasterDraw), pbrk_raster_scratch_bytes};
-static const RasterKind kGeometryJob = {"K13.geometry", "K13", "geometry_pass.glsl", "geometry", GPU_CullMode_DrawCCW, "GPU_CullMode_DrawCCW only (render.cpp:232)", sizeof(PbrkGeoDraw), pbrk_geometry_scratch_bytes};
-static const RasterKind kVoxelizeJob = {"K14.voxelize", "K14", "lightgrid_voxelize.glsl", "voxelise", GPU_CullMode_TwoSided, "GPU_CullMode_TwoSided only", sizeof(PbrkVoxDraw), pbrk_voxelize_scratch_bytes};
-static const RasterKind& raster_kind(KernelId k) { return k == Kernel_Geometry ? kGeometryJob : (k == Kernel_Voxelize ? kVoxelizeJob : kSunDepthJob); }
 
 struct GPU_Graph {
     hipStream_t stream = nullptr;
@@ -338,6 +333,10 @@ GPU_API void GPU_DestroyPipelineLayout(GPU_PipelineLayout* l) { delete l; }
 static int find_binding(const GPU_PipelineLayout* l, const char* name) {
     for (size_t i = 0; i < l->bindings.size(); ++i) if (l->bindings[i].name == name) return (int)i;
     return -1;
+}
+static Slot* named_slot(GPU_DescriptorSet* set, const char* name) {
+    int b = find_binding(set->layout, name);
+    return b < 0 ? nullptr : &set->slots[b];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -748,9 +747,59 @@ GPU_API GPU_RenderPass* GPU_MakeRenderPass(const GPU_RenderPassDesc* desc) {
 }
 GPU_API void GPU_DestroyRenderPass(GPU_RenderPass* rp) { delete rp; }
 
-// What both raster pipelines ask, in the order the checks have always had (K13 checks its colour targets between the two): the pass
-// covers its whole depth target (a texture has no zero extent, so width > 0 adds nothing to K12); depth test and write, the pass's
-// cull mode, nothing blended.
+static hipEvent_t next_event(GPU_Graph* g, size_t& used) {
+    if (used == g->ev.size()) { hipEvent_t e; HIP_OK(hipEventCreate(&e)); g->ev.push_back(e); }
+    return g->ev[used++];
+}
+
+// Runs `launch` bracketed by events when timing is on.
+template <class F>
+static void timed(GPU_Graph* g, const std::string& name, size_t& ev_used, F launch) {
+    if (G.timing) {
+        hipEvent_t a = next_event(g, ev_used);
+        HIP_OK(hipEventRecord(a, g->cur));
+        launch();
+        hipEvent_t b = next_event(g, ev_used);
+        HIP_OK(hipEventRecord(b, g->cur));
+        g->timed_names.push_back(name);
+    } else {
+        launch();
+    }
+}
+
+// Globals as they are at submit time: the caller fills the persistently mapped buffer before GPU_GraphSubmit (render.cpp:991)
+static void read_globals(const BufferImpl* buf, size_t offset, void* dst, size_t bytes) {
+    if (buf->pinned_host) memcpy(dst, (const char*)buf->dev + offset, bytes);
+    else HIP_OK(hipMemcpy(dst, (const char*)buf->dev + offset, bytes, hipMemcpyDeviceToHost));
+}
+
+// ------------------------------------------------------------------------------------------
+// raster jobs: sun depth (K12, render.cpp:993-1020), geometry (K13, :1076-1115), voxelise (K14, :1039-1056)
+// ------------------------------------------------------------------------------------------
+// The draws of one render-pass instance are ONE raster job (one Op_Raster): merging them is exact (K12: a per-pixel minimum; K13:
+// depth, then triangle number; K14: which store to a voxel wins follows the triangles' submission order, which merging keeps:
+// DESIGN.md K14), and one setup + one tile launch replace hundreds of per-part launches.  A job is closed (its scratch sized from the
+// known triangle count, no read-back) at GPU_OpEndRenderPass, or when its kind's same_job says that a draw cannot go on in it.
+// A kind's row holds what the jobs differ in on the host; the shared code at the end of the section reads it from the pipeline.
+struct RasterKind {
+    const char* op_name; const char* tag; const char* stage[2];              // stage: what GPUX_GraphTimedOpName calls the two launches
+    const char* shader; const char* pass_name; GPU_CullMode cull; const char* cull_name;
+    bool indexed;                                                             // drawn by GPU_OpDrawIndexed (false: by GPU_OpDraw)
+    size_t globals_bytes; const char* globals_msg;                            // what the kind reads of GLOBALS, and the refusal of a smaller buffer
+    size_t draw_bytes; size_t (*scratch_bytes)(uint32_t, int, int);
+    bool (*pipeline_ok)(const RasterKind& rk, const GPU_GraphicsPipelineDesc* desc);      // refuses every state the kind is not implemented for
+    // one draw: checks the bindings of d.set that the kind reads and the range of `count` indices from d.first_index, in the order the
+    // kind has always had; fills in the draw's buffers (d.vb, d.ib) and target
+    bool (*draw_ok)(GPU_Graph* g, uint32_t count, const char* fn, RasterDraw& d);
+    // does the draw go on in the open job of its pass?  (false: that job is closed and the draw opens the next one)
+    bool (*same_job)(const Op& job, const GPU_GraphicsPipeline* pipe, const RasterDraw& d);
+    bool (*fill_draw)(const RasterDraw& d, void* out);                       // the draw's entry of the job's draw table, at submit
+    int (*launch)(const Op& op, const RasterScratch& rs, hipStream_t st, int stage);      // fills the kind's Pbrk*Args, launches stage 0 or 1
+};
+
+// What K12 and K13 ask, in the order the checks have always had (K13 checks its colour targets between the two): the pass covers its
+// whole depth target (a texture has no zero extent, so width > 0 adds nothing to K12); depth test and write, the pass's cull mode,
+// nothing blended.
 static bool raster_target_ok(const GPU_GraphicsPipelineDesc* desc, const RasterKind& rk) {
     const GPU_RenderPassDesc& rd = desc->render_pass->desc;
     const GPU_Texture* dt = rd.depth_stencil_target;
@@ -765,75 +814,289 @@ static bool raster_state_ok(const GPU_GraphicsPipelineDesc* desc, const RasterKi
                 "GPU_MakeGraphicsPipeline: blending and conservative rasterisation are not implemented for %s", rk.shader);
     return true;
 }
+// K12: depth test + write, two-sided, position first; anything else would need a raster feature this backend does not have
+static bool sun_pipeline_ok(const RasterKind& rk, const GPU_GraphicsPipelineDesc* desc) {
+    const GPU_RenderPassDesc& rd = desc->render_pass->desc;
+    const GPU_Texture* dt = rd.depth_stencil_target;
+    GPU_REQUIRE(dt && dt->format == GPU_Format_D32F_Or_X8D24UN && rd.color_targets_count == 0, false,
+                "GPU_MakeGraphicsPipeline: sun_depth_pass.glsl needs a render pass with a D32F depth target and no colour targets (render.cpp:725-729)");
+    if (!raster_target_ok(desc, rk) || !raster_state_ok(desc, rk)) return false;
+    GPU_REQUIRE(desc->vertex_input_formats && desc->vertex_input_formats_count > 0 && desc->vertex_input_formats[0] == GPU_Format_RGB32F, false,
+                "GPU_MakeGraphicsPipeline: sun_depth_pass.glsl reads an RGB32F position as its first vertex attribute");
+    return true;
+}
+// K13: exactly the reference's state (render.cpp:190-233, 700-708)
+static bool geo_pipeline_ok(const RasterKind& rk, const GPU_GraphicsPipelineDesc* desc) {
+    const GPU_RenderPassDesc& rd = desc->render_pass->desc;
+    const GPU_Texture* dt = rd.depth_stencil_target;
+    GPU_REQUIRE(rd.color_targets_count == 5 && dt && dt->format == GPU_Format_D32F_Or_X8D24UN, false,
+                "GPU_MakeGraphicsPipeline: geometry_pass.glsl needs a render pass with five colour targets and a D32F depth target (render.cpp:700-708)");
+    if (!raster_target_ok(desc, rk)) return false;
+    for (uint32_t i = 0; i < 5; ++i) {
+        const GPU_Texture* ct = desc->render_pass->targets[i].texture;
+        GPU_REQUIRE(ct && desc->render_pass->targets[i].mip_level == 0 && ct->format == (i < 4 ? GPU_Format_RGBA8UN : GPU_Format_RG16F) &&
+                    ct->width == rd.width && ct->height == rd.height && ct->layer_count == 1 && ct->depth == 1, false,
+                    "GPU_MakeGraphicsPipeline: geometry pass colour target %u must be a %ux%u 2D %s texture (render.cpp:680-691)", i, rd.width, rd.height, i < 4 ? "RGBA8UN" : "RG16F");
+    }
+    if (!raster_state_ok(desc, rk)) return false;
+    GPU_REQUIRE(desc->vertex_input_formats && desc->vertex_input_formats_count == 4 && desc->vertex_input_formats[0] == GPU_Format_RGB32F &&
+                desc->vertex_input_formats[1] == GPU_Format_RGB32F && desc->vertex_input_formats[2] == GPU_Format_RGB32F && desc->vertex_input_formats[3] == GPU_Format_RG32F, false,
+                "GPU_MakeGraphicsPipeline: geometry_pass.glsl reads the 44-byte Vertex (RGB32F x3, RG32F; render.cpp:227)");
+    for (const char* name : {"GLOBALS", "TEX0", "TEX1", "TEX_ORM", "TEX_EMISSIVE", "SAMPLER_LINEAR_WRAP"})
+        GPU_REQUIRE(find_binding(desc->layout, name) >= 0, false, "GPU_MakeGraphicsPipeline: the geometry pass layout has no \"%s\" binding", name);
+    return true;
+}
+// K14: exactly the reference's state (render.cpp:113-149, 711-714): a pass without targets, no vertex inputs, conservative
+static bool vox_pipeline_ok(const RasterKind& rk, const GPU_GraphicsPipelineDesc* desc) {
+    const GPU_RenderPassDesc& rd = desc->render_pass->desc;
+    GPU_REQUIRE(rd.color_targets_count == 0 && rd.depth_stencil_target == nullptr, false,
+                "GPU_MakeGraphicsPipeline: lightgrid_voxelize.glsl needs a render pass without colour and depth targets (render.cpp:711-714)");
+    GPU_REQUIRE(rd.width == rd.height && rd.width >= 8 && rd.width <= 256 && (rd.width & 7) == 0, false,
+                "GPU_MakeGraphicsPipeline: the voxelise pass must be N x N with N a multiple of 8 in 8 .. 256 (got %u x %u)", rd.width, rd.height);
+    GPU_REQUIRE(desc->vertex_input_formats_count == 0, false, "GPU_MakeGraphicsPipeline: lightgrid_voxelize.glsl has no vertex inputs (it reads SSBO0 / SSBO1)");
+    GPU_REQUIRE(desc->enable_conservative_rasterization, false, "GPU_MakeGraphicsPipeline: lightgrid_voxelize.glsl is implemented with conservative rasterisation only (render.cpp:147)");
+    GPU_REQUIRE(desc->cull_mode == rk.cull, false, "GPU_MakeGraphicsPipeline: %s is implemented for %s", rk.shader, rk.cull_name);
+    GPU_REQUIRE(!desc->enable_depth_test && !desc->enable_depth_write && !desc->enable_blending, false,
+                "GPU_MakeGraphicsPipeline: lightgrid_voxelize.glsl is implemented without depth test, depth write and blending");
+    static const struct { const char* name; BindKind kind; } need[] = {{"GLOBALS", Bind_Buffer}, {"SSBO0", Bind_Buffer}, {"SSBO1", Bind_Buffer},
+        {"IMG0", Bind_StorageImage}, {"SUN_DEPTH_MAP", Bind_Texture}, {"TEX0", Bind_Texture}, {"TEX_EMISSIVE", Bind_Texture},
+        {"SAMPLER_PERCENTAGE_CLOSER", Bind_Sampler}, {"SAMPLER_LINEAR_WRAP", Bind_Sampler}};
+    for (const auto& nb : need) {
+        const int b = find_binding(desc->layout, nb.name);
+        GPU_REQUIRE(b >= 0 && desc->layout->bindings[(size_t)b].kind == nb.kind, false, "GPU_MakeGraphicsPipeline: the voxelise pass layout has no \"%s\" binding of the right kind", nb.name);
+    }
+    return true;
+}
+
+static bool index_range_ok(const BufferImpl* ib, uint32_t first, uint32_t count, const char* fn, const char* msg) {
+    const uint64_t n_idx = ib->base.size / 4;                                 // 32-bit indices (gpu_vulkan.c:2591-2593)
+    GPU_REQUIRE((uint64_t)first + count <= n_idx, false, msg, fn, first, (unsigned long long)first + count, (unsigned long long)n_idx);
+    return true;
+}
+// K12 and K13 read the buffers bound on the graph and write the pass's depth target; K12 reads no binding but GLOBALS
+static bool sun_draw_ok(GPU_Graph* g, uint32_t count, const char* fn, RasterDraw& d) {
+    GPU_REQUIRE(g->vertex_buffer, false, "%s: no vertex buffer bound (GPU_OpBindVertexBuffer)", fn);
+    GPU_REQUIRE(g->index_buffer, false, "%s: no index buffer bound (GPU_OpBindIndexBuffer)", fn);
+    d.vb = g->vertex_buffer; d.ib = g->index_buffer; d.target = (TextureImpl*)g->in_pass->desc.depth_stencil_target;
+    return index_range_ok(d.ib, d.first_index, count, fn, "%s: indices [%u, %llu) lie outside the bound index buffer (%llu indices)");
+}
+static bool geo_draw_ok(GPU_Graph* g, uint32_t count, const char* fn, RasterDraw& d) {
+    for (const char* name : {"TEX0", "TEX1", "TEX_ORM", "TEX_EMISSIVE"}) {
+        Slot* sl = named_slot(d.set, name);
+        GPU_REQUIRE(sl && sl->tex, false, "%s: geometry pass: \"%s\" is not bound", fn, name);
+        GPU_REQUIRE(is_material_2d(sl->tex) && sl->whole, false,
+                    "%s: geometry pass: \"%s\" must be a whole 2D RGBA8UN, BC1, BC3 or BC5 texture", fn, name);
+    }
+    Slot* sm = named_slot(d.set, "SAMPLER_LINEAR_WRAP");
+    GPU_REQUIRE(sm && sm->sampler == &G.samplers[0], false, "%s: geometry pass: \"SAMPLER_LINEAR_WRAP\" must be GPU_SamplerLinearWrap()", fn);
+    GPU_REQUIRE(g->push_size == 16, false, "%s: the geometry pass needs its 16-byte push constants (taa_jitter, taa_jitter_prev; render.cpp:1091-1094)", fn);
+    return sun_draw_ok(g, count, fn, d);
+}
+// K14 reads SSBO0 / SSBO1 of the draw's set (from vertex d.first_index on) and stores into the set's IMG0
+static bool vox_draw_ok(GPU_Graph* g, uint32_t count, const char* fn, RasterDraw& d) {
+    const uint32_t N = g->in_pass->desc.width;
+    Slot* vb = named_slot(d.set, "SSBO0");
+    Slot* ib = named_slot(d.set, "SSBO1");
+    GPU_REQUIRE(vb && vb->buf, false, "%s: voxelise pass: \"SSBO0\" (vertices) is not a bound buffer", fn);
+    GPU_REQUIRE(ib && ib->buf, false, "%s: voxelise pass: \"SSBO1\" (indices) is not a bound buffer", fn);
+    if (!index_range_ok(ib->buf, d.first_index, count, fn, "%s: voxelise pass: vertices [%u, %llu) lie outside \"SSBO1\" (%llu indices)")) return false;
+    Slot* img = named_slot(d.set, "IMG0");
+    GPU_REQUIRE(img && img->tex && img->mip == 0 && img->tex->base.format == GPU_Format_RGBA16F && img->tex->base.layer_count == 1 &&
+                img->tex->base.width == N && img->tex->base.height == N && img->tex->base.depth == N, false,
+                "%s: voxelise pass: \"IMG0\" must be mip 0 of a %u^3 RGBA16F 3-D storage image", fn, N);
+    Slot* sun = named_slot(d.set, "SUN_DEPTH_MAP");
+    GPU_REQUIRE(sun && sun->tex && sun->whole && sun->tex->base.format == GPU_Format_D32F_Or_X8D24UN && sun->tex->base.layer_count == 1 && sun->tex->base.depth == 1, false,
+                "%s: voxelise pass: \"SUN_DEPTH_MAP\" must be a whole 2D D32F texture (render.cpp:676)", fn);
+    for (const char* name : {"TEX0", "TEX_EMISSIVE"}) {
+        Slot* sl = named_slot(d.set, name);
+        GPU_REQUIRE(sl && sl->tex && sl->whole && is_material_2d(sl->tex), false,
+                    "%s: voxelise pass: \"%s\" must be a whole 2D RGBA8UN, BC1, BC3 or BC5 texture", fn, name);
+    }
+    Slot* sm = named_slot(d.set, "SAMPLER_LINEAR_WRAP");
+    GPU_REQUIRE(sm && sm->sampler == &G.samplers[0], false, "%s: voxelise pass: \"SAMPLER_LINEAR_WRAP\" must be GPU_SamplerLinearWrap()", fn);
+    Slot* pc = named_slot(d.set, "SAMPLER_PERCENTAGE_CLOSER");
+    GPU_REQUIRE(pc && pc->sampler && pc->sampler->desc.min_filter == GPU_Filter_Linear && pc->sampler->desc.mag_filter == GPU_Filter_Linear &&
+                pc->sampler->desc.address_modes[0] == GPU_AddressMode_Clamp && pc->sampler->desc.address_modes[1] == GPU_AddressMode_Clamp &&
+                pc->sampler->desc.compare_op == GPU_CompareOp_Less, false,
+                "%s: voxelise pass: \"SAMPLER_PERCENTAGE_CLOSER\" must be a linear / clamp / GPU_CompareOp_Less sampler (render.cpp:664-673)", fn);
+    d.vb = vb->buf; d.ib = ib->buf; d.target = img->tex;
+    return true;
+}
+
+// K12's draws share the job's vertex / index pair and stride; K13's name their own buffers; K14's share the job's grid
+static bool sun_same_job(const Op& job, const GPU_GraphicsPipeline* pipe, const RasterDraw& d) { return job.buf == d.vb && job.buf2 == d.ib && job.gpipe->vertex_stride == pipe->vertex_stride; }
+static bool geo_same_job(const Op&, const GPU_GraphicsPipeline*, const RasterDraw&) { return true; }
+static bool vox_same_job(const Op& job, const GPU_GraphicsPipeline*, const RasterDraw& d) { return job.tex == d.target; }
+
+// The draw tables of the raster jobs, filled from what every draw's GLOBALS holds now (the caller fills the mapped Globals before
+// submitting, render.cpp:991), before anything is launched.
+static bool fill_sun_draw(const RasterDraw& d, void* out) {
+    PbrkRasterDraw& o = *(PbrkRasterDraw*)out;
+    read_globals(named_slot(d.set, "GLOBALS")->buf, 384, o.m, 64);           // render.h:129: sun_space_from_world
+    // an orthographic matrix (last row (0, 0, 0, c > 0)) needs no near-plane clip
+    GPU_REQUIRE(o.m[3] == 0.0f && o.m[7] == 0.0f && o.m[11] == 0.0f && o.m[15] > 0.0f, false,
+                "GPU_GraphSubmit: perspective sun projection not implemented (sun_space_from_world's last row must be (0, 0, 0, c > 0))");
+    o.first_tri = d.first_tri; o.first_index = d.first_index; o.vertex_offset = d.vertex_offset; o.pad = 0;
+    return true;
+}
+static PbrkGeoTex material_tex(const TextureImpl* t) { return {material_texels(t), (int)t->base.width, (int)t->base.height, (int)t->base.mip_level_count, 0}; }
+static bool fill_geo_draw(const RasterDraw& d, void* out) {               // both matrices, the draw's textures and buffers
+    PbrkGeoDraw& o = *(PbrkGeoDraw*)out;
+    memset(&o, 0, sizeof o);
+    const BufferImpl* gb = named_slot(d.set, "GLOBALS")->buf;
+    read_globals(gb, 0, o.m, 64); read_globals(gb, 448, o.m_old, 64);      // render.h:123, :130
+    memcpy(o.jitter, d.push, 8); memcpy(o.jitter_prev, d.push + 2, 8);
+    static const char* const names[4] = {"TEX0", "TEX1", "TEX_ORM", "TEX_EMISSIVE"};
+    for (int k = 0; k < 4; ++k) o.tex[k] = material_tex(named_slot(d.set, names[k])->tex);
+    o.vertices = d.vb->dev; o.indices = (const uint32_t*)d.ib->dev; o.vertex_count = d.vb->base.size / 44u;
+    o.first_tri = d.first_tri; o.first_index = d.first_index; o.vertex_offset = d.vertex_offset;
+    return true;
+}
+static bool fill_vox_draw(const RasterDraw& d, void* out) {               // sun matrix and direction, scale, the draw's buffers and textures
+    PbrkVoxDraw& o = *(PbrkVoxDraw*)out;
+    memset(&o, 0, sizeof o);
+    const BufferImpl* gb = named_slot(d.set, "GLOBALS")->buf;
+    read_globals(gb, 384, o.sun, 64); read_globals(gb, 512, o.sun_dir, 16); read_globals(gb, 544, &o.scale, 4);    // render.h:129, :131, :134
+    o.first_tri = d.first_tri; o.first_vertex = d.first_index;
+    o.vertices = (const float*)d.vb->dev; o.vertex_floats = d.vb->base.size / 4u; o.indices = (const uint32_t*)d.ib->dev;
+    const TextureImpl* sun = named_slot(d.set, "SUN_DEPTH_MAP")->tex;
+    o.sun_depth = (const float*)sun->dev; o.sun_w = (int)sun->base.width; o.sun_h = (int)sun->base.height;
+    static const char* const names[2] = {"TEX0", "TEX_EMISSIVE"};
+    for (int k = 0; k < 2; ++k) o.tex[k] = material_tex(named_slot(d.set, names[k])->tex);
+    return true;
+}
+
+static int sun_launch(const Op& op, const RasterScratch& rs, hipStream_t st, int stage) {
+    PbrkRasterArgs a;
+    a.vertices = op.buf->dev; a.vertex_stride = op.gpipe->vertex_stride; a.vertex_count = op.buf->base.size / a.vertex_stride; a.indices = (const uint32_t*)op.buf2->dev;
+    a.draws = (const PbrkRasterDraw*)rs.draws_dev; a.draw_count = (uint32_t)op.draws.size(); a.tri_count = op.tri_count;
+    a.depth = (float*)op.tex->dev; a.width = (int)op.tex->base.width; a.height = (int)op.tex->base.height;
+    a.scratch = rs.dev; a.rejected = G.raster_rejected;
+    return stage == 0 ? pbrk_raster_setup(&a, st) : pbrk_raster_tiles(&a, st);
+}
+static int geo_launch(const Op& op, const RasterScratch& rs, hipStream_t st, int stage) {
+    PbrkGeometryArgs a;
+    a.draws = (const PbrkGeoDraw*)rs.draws_dev; a.draw_count = (uint32_t)op.draws.size(); a.tri_count = op.tri_count;
+    for (int k = 0; k < 4; ++k) a.color[k] = ((TextureImpl*)op.pass->targets[(size_t)k].texture)->dev;
+    a.velocity = ((TextureImpl*)op.pass->targets[4].texture)->dev;
+    a.depth = (float*)op.tex->dev; a.width = (int)op.tex->base.width; a.height = (int)op.tex->base.height;
+    a.scratch = rs.dev; a.rejected = G.raster_rejected;
+    return stage == 0 ? pbrk_geometry_setup(&a, st) : pbrk_geometry_tiles(&a, st);
+}
+static int vox_launch(const Op& op, const RasterScratch& rs, hipStream_t st, int stage) {
+    PbrkVoxelizeArgs a;
+    a.draws = (const PbrkVoxDraw*)rs.draws_dev; a.draw_count = (uint32_t)op.draws.size(); a.tri_count = op.tri_count;
+    a.grid = op.tex->dev; a.n = (int)op.tex->base.width;
+    a.scratch = rs.dev; a.rejected = G.raster_rejected; a.fragments = G.raster_rejected + 1;
+    return stage == 0 ? pbrk_voxelize_cover(&a, st) : pbrk_voxelize_resolve(&a, st);
+}
+
+static const RasterKind kSunDepthJob = {"K12.sun_depth", "K12", {"K12.setup", "K12.tiles"}, "sun_depth_pass.glsl", "sun depth", GPU_CullMode_TwoSided, "GPU_CullMode_TwoSided only", true,
+    448, "%s: \"GLOBALS\" must be a buffer that holds sun_space_from_world (render.h:122-136)", sizeof(PbrkRasterDraw), pbrk_raster_scratch_bytes, sun_pipeline_ok, sun_draw_ok, sun_same_job, fill_sun_draw, sun_launch};
+static const RasterKind kGeometryJob = {"K13.geometry", "K13", {"K13.setup", "K13.tiles"}, "geometry_pass.glsl", "geometry", GPU_CullMode_DrawCCW, "GPU_CullMode_DrawCCW only (render.cpp:232)", true,
+    512, "%s: \"GLOBALS\" must be a buffer that holds old_clip_space_from_world (render.h:122-136)", sizeof(PbrkGeoDraw), pbrk_geometry_scratch_bytes, geo_pipeline_ok, geo_draw_ok, geo_same_job, fill_geo_draw, geo_launch};
+static const RasterKind kVoxelizeJob = {"K14.voxelize", "K14", {"K14.cover", "K14.resolve"}, "lightgrid_voxelize.glsl", "voxelise", GPU_CullMode_TwoSided, "GPU_CullMode_TwoSided only", false,
+    548, "%s: voxelise pass: \"GLOBALS\" must be a buffer that holds lightgrid_scale (548 bytes, render.h:122-136)", sizeof(PbrkVoxDraw), pbrk_voxelize_scratch_bytes, vox_pipeline_ok, vox_draw_ok, vox_same_job, fill_vox_draw, vox_launch};
+
+// ---- the shared path: record, close, snapshot, execute ----
+static const RasterKind* bound_raster_row(const GPU_Graph* g) { return g->in_pass && g->bound_draw >= 0 ? g->draw_params[(size_t)g->bound_draw].pipeline->raster : nullptr; }
+
+static void close_raster_job(GPU_Graph* g) {
+    if (g->raster_op < 0) return;
+    Op& op = g->ops[(size_t)g->raster_op];
+    g->raster_op = -1;
+    if ((size_t)op.raster_slot >= g->raster.size()) g->raster.resize((size_t)op.raster_slot + 1);
+    RasterScratch& rs = g->raster[(size_t)op.raster_slot];
+    const RasterKind& rk = *op.gpipe->raster;
+    const size_t need = rk.scratch_bytes(op.tri_count, (int)op.tex->base.width, (int)op.tex->base.height);
+    bool ok = true;
+    if (rs.dev_bytes < need) {
+        (void)hipFree(rs.dev); rs.dev = nullptr; rs.dev_bytes = 0;
+        if (hipMalloc(&rs.dev, need) == hipSuccess) rs.dev_bytes = need; else { rs.dev = nullptr; ok = false; }
+    }
+    const size_t table = op.draws.size() * rk.draw_bytes;
+    if (ok && rs.draws_cap < table) {
+        (void)hipFree(rs.draws_dev); (void)hipHostFree(rs.draws_host); rs.draws_dev = nullptr; rs.draws_host = nullptr; rs.draws_cap = 0;
+        if (hipMalloc(&rs.draws_dev, table) == hipSuccess && hipHostMalloc((void**)&rs.draws_host, table, hipHostMallocDefault) == hipSuccess) rs.draws_cap = table;
+        else ok = false;
+    }
+    if (ok && !G.raster_rejected) {
+        if (hipMalloc((void**)&G.raster_rejected, 16) != hipSuccess || hipMemset(G.raster_rejected, 0, 16) != hipSuccess) { G.raster_rejected = nullptr; ok = false; }
+    }
+    if (!ok) { (void)hipGetLastError(); op.tri_count = 0; op.draws.clear(); gpu_fail("GPU_OpEndRenderPass: allocation of the raster scratch (%zu bytes) failed", need); }
+}
+
+// One draw of a raster job (fn: the entry point).  Everything a launch could trip over is checked here.
+static void record_raster_draw(GPU_Graph* g, const DrawParams& dp, uint32_t count, uint32_t instance_count, uint32_t first, uint32_t vertex_offset, const char* fn) {
+    const RasterKind& rk = *dp.pipeline->raster;
+    GPU_REQUIRE_V(dp.pipeline->pass == g->in_pass, "%s: pipeline was created for a different render pass", fn);
+    GPU_REQUIRE_V(dp.set->layout == dp.pipeline->layout, "%s: descriptor set and pipeline use different layouts", fn);
+    Slot* gl = named_slot(dp.set, "GLOBALS");
+    GPU_REQUIRE_V(gl && gl->buf && gl->buf->base.size >= rk.globals_bytes, rk.globals_msg, fn);
+    RasterDraw d; d.set = dp.set; d.first_index = first; d.vertex_offset = vertex_offset; memcpy(d.push, g->push, sizeof d.push);
+    if (!rk.draw_ok(g, count, fn, d)) return;
+    const uint32_t tris = count / 3;                                          // whole triangles only
+    if (tris == 0 || instance_count == 0) return;                             // any instance count > 0 draws the same triangles once
+    if (g->raster_op >= 0) {
+        const Op& cur = g->ops[(size_t)g->raster_op];
+        GPU_REQUIRE_V(cur.gpipe->raster == &rk, "%s: a %s draw inside another raster pass", fn, rk.pass_name);
+        if (!rk.same_job(cur, dp.pipeline, d)) close_raster_job(g);
+    }
+    if (g->raster_op < 0) {
+        Op op; op.kind = Op_Raster; op.name = rk.op_name;
+        op.pass = g->in_pass; op.gpipe = dp.pipeline; op.tex = d.target; op.buf = d.vb; op.buf2 = d.ib;
+        op.raster_slot = (int)g->raster_used++;
+        g->ops.push_back(op);
+        g->raster_op = (int)g->ops.size() - 1;
+    }
+    Op& op = g->ops[(size_t)g->raster_op];
+    GPU_REQUIRE_V((uint64_t)op.tri_count + tris <= (1u << 26), "%s: more than 2^26 triangles in one %s pass", fn, rk.pass_name);
+    d.first_tri = op.tri_count;
+    op.draws.push_back(d);
+    op.tri_count += tris;
+}
+
+static bool snapshot_raster_draws(GPU_Graph* g) {
+    for (const Op& op : g->ops) {
+        if (op.kind != Op_Raster || !op.tri_count) continue;
+        const RasterKind& rk = *op.gpipe->raster;
+        char* table = (char*)g->raster[(size_t)op.raster_slot].draws_host;
+        for (size_t i = 0; i < op.draws.size(); ++i) if (!rk.fill_draw(op.draws[i], table + i * rk.draw_bytes)) return false;
+    }
+    return true;
+}
+
+// A raster job: upload the draw table that GPU_GraphSubmit snapshotted, then its two launches
+static void exec_raster(GPU_Graph* g, Op& op, size_t& ev_used) {
+    if (!op.tri_count) return;
+    RasterScratch& rs = g->raster[(size_t)op.raster_slot];
+    const RasterKind& rk = *op.gpipe->raster;
+    for (int stage = 0; stage < 2; ++stage)
+        timed(g, rk.stage[stage], ev_used, [&] {
+            if (stage == 0) HIP_OK(hipMemcpyAsync(rs.draws_dev, rs.draws_host, op.draws.size() * rk.draw_bytes, hipMemcpyHostToDevice, g->cur));
+            int rc = rk.launch(op, rs, g->cur, stage);
+            if (rc != PBRK_OK) gpu_fail("%s %s launch failed (%d)", rk.tag, stage == 0 ? "setup" : "tile", rc);
+        });
+    for (const GPU_TextureView& tv : op.pass->targets) { ((TextureImpl*)tv.texture)->bordered_valid = false; ((TextureImpl*)tv.texture)->lut_cells_valid = false; }
+    op.tex->bordered_valid = false;
+}
 
 GPU_API GPU_GraphicsPipeline* GPU_MakeGraphicsPipeline(const GPU_GraphicsPipelineDesc* desc) {
     GPU_REQUIRE(desc && desc->layout && desc->render_pass, nullptr, "GPU_MakeGraphicsPipeline: NULL argument");
     KernelId k = identify_shader(&desc->fs);
     if (k == Kernel_None && identify_shader(&desc->vs) == Kernel_SunDepth) k = Kernel_SunDepth;      // the pass has a vertex stage only
-    if (k == Kernel_SunDepth) {
-        // K12: depth test + write, two-sided, position first; anything else would need a raster feature this backend does not have
-        const GPU_RenderPassDesc& rd = desc->render_pass->desc;
-        const GPU_Texture* dt = rd.depth_stencil_target;
-        GPU_REQUIRE(dt && dt->format == GPU_Format_D32F_Or_X8D24UN && rd.color_targets_count == 0, nullptr,
-                    "GPU_MakeGraphicsPipeline: sun_depth_pass.glsl needs a render pass with a D32F depth target and no colour targets (render.cpp:725-729)");
-        if (!raster_target_ok(desc, kSunDepthJob) || !raster_state_ok(desc, kSunDepthJob)) return nullptr;
-        GPU_REQUIRE(desc->vertex_input_formats && desc->vertex_input_formats_count > 0 && desc->vertex_input_formats[0] == GPU_Format_RGB32F, nullptr,
-                    "GPU_MakeGraphicsPipeline: sun_depth_pass.glsl reads an RGB32F position as its first vertex attribute");
-        uint32_t stride = 0;
-        for (uint32_t i = 0; i < desc->vertex_input_formats_count; ++i) {                   // gpu_vulkan.c:1745-1762
+    const RasterKind* rk = k == Kernel_SunDepth ? &kSunDepthJob : k == Kernel_Geometry ? &kGeometryJob : k == Kernel_Voxelize ? &kVoxelizeJob : nullptr;
+    if (rk) {
+        if (!rk->pipeline_ok(*rk, desc)) return nullptr;
+        uint32_t stride = 0;                                  // K12: anything behind the position; K13: the 44-byte Vertex; K14: none
+        for (uint32_t i = 0; i < desc->vertex_input_formats_count; ++i) {   // gpu_vulkan.c:1745-1762
             GPU_FormatInfo fi = GPUX_GetFormatInfo(desc->vertex_input_formats[i]);
             GPU_REQUIRE(fi.vertex_input, nullptr, "GPU_MakeGraphicsPipeline: vertex attribute %u has a format that is not a vertex input", i);
             stride += fi.block_size;
         }
         GPU_REQUIRE((stride & 3) == 0, nullptr, "GPU_MakeGraphicsPipeline: vertex stride %u is not a multiple of 4 bytes", stride);
         GPU_GraphicsPipeline* p = new GPU_GraphicsPipeline();
-        p->layout = desc->layout; p->pass = desc->render_pass; p->kernel = k; p->shade_flags = 0; p->vertex_stride = stride;
-        return p;
-    }
-    if (k == Kernel_Voxelize) {
-        // K14: exactly the reference's state (render.cpp:113-149, 711-714): a pass without targets, no vertex inputs, conservative
-        const GPU_RenderPassDesc& rd = desc->render_pass->desc;
-        GPU_REQUIRE(rd.color_targets_count == 0 && rd.depth_stencil_target == nullptr, nullptr,
-                    "GPU_MakeGraphicsPipeline: lightgrid_voxelize.glsl needs a render pass without colour and depth targets (render.cpp:711-714)");
-        GPU_REQUIRE(rd.width == rd.height && rd.width >= 8 && rd.width <= 256 && (rd.width & 7) == 0, nullptr,
-                    "GPU_MakeGraphicsPipeline: the voxelise pass must be N x N with N a multiple of 8 in 8 .. 256 (got %u x %u)", rd.width, rd.height);
-        GPU_REQUIRE(desc->vertex_input_formats_count == 0, nullptr, "GPU_MakeGraphicsPipeline: lightgrid_voxelize.glsl has no vertex inputs (it reads SSBO0 / SSBO1)");
-        GPU_REQUIRE(desc->enable_conservative_rasterization, nullptr, "GPU_MakeGraphicsPipeline: lightgrid_voxelize.glsl is implemented with conservative rasterisation only (render.cpp:147)");
-        GPU_REQUIRE(desc->cull_mode == kVoxelizeJob.cull, nullptr, "GPU_MakeGraphicsPipeline: %s is implemented for %s", kVoxelizeJob.shader, kVoxelizeJob.cull_name);
-        GPU_REQUIRE(!desc->enable_depth_test && !desc->enable_depth_write && !desc->enable_blending, nullptr,
-                    "GPU_MakeGraphicsPipeline: lightgrid_voxelize.glsl is implemented without depth test, depth write and blending");
-        static const struct { const char* name; BindKind kind; } need[] = {{"GLOBALS", Bind_Buffer}, {"SSBO0", Bind_Buffer}, {"SSBO1", Bind_Buffer},
-            {"IMG0", Bind_StorageImage}, {"SUN_DEPTH_MAP", Bind_Texture}, {"TEX0", Bind_Texture}, {"TEX_EMISSIVE", Bind_Texture},
-            {"SAMPLER_PERCENTAGE_CLOSER", Bind_Sampler}, {"SAMPLER_LINEAR_WRAP", Bind_Sampler}};
-        for (const auto& nb : need) {
-            const int b = find_binding(desc->layout, nb.name);
-            GPU_REQUIRE(b >= 0 && desc->layout->bindings[(size_t)b].kind == nb.kind, nullptr, "GPU_MakeGraphicsPipeline: the voxelise pass layout has no \"%s\" binding of the right kind", nb.name);
-        }
-        GPU_GraphicsPipeline* p = new GPU_GraphicsPipeline();
-        p->layout = desc->layout; p->pass = desc->render_pass; p->kernel = k; p->shade_flags = 0;
-        return p;
-    }
-    if (k == Kernel_Geometry) {
-        // K13: exactly the reference's state (render.cpp:190-233, 700-708)
-        const GPU_RenderPassDesc& rd = desc->render_pass->desc;
-        const GPU_Texture* dt = rd.depth_stencil_target;
-        GPU_REQUIRE(rd.color_targets_count == 5 && dt && dt->format == GPU_Format_D32F_Or_X8D24UN, nullptr,
-                    "GPU_MakeGraphicsPipeline: geometry_pass.glsl needs a render pass with five colour targets and a D32F depth target (render.cpp:700-708)");
-        if (!raster_target_ok(desc, kGeometryJob)) return nullptr;
-        for (uint32_t i = 0; i < 5; ++i) {
-            const GPU_Texture* ct = desc->render_pass->targets[i].texture;
-            GPU_REQUIRE(ct && desc->render_pass->targets[i].mip_level == 0 && ct->format == (i < 4 ? GPU_Format_RGBA8UN : GPU_Format_RG16F) &&
-                        ct->width == rd.width && ct->height == rd.height && ct->layer_count == 1 && ct->depth == 1, nullptr,
-                        "GPU_MakeGraphicsPipeline: geometry pass colour target %u must be a %ux%u 2D %s texture (render.cpp:680-691)", i, rd.width, rd.height, i < 4 ? "RGBA8UN" : "RG16F");
-        }
-        if (!raster_state_ok(desc, kGeometryJob)) return nullptr;
-        GPU_REQUIRE(desc->vertex_input_formats && desc->vertex_input_formats_count == 4 && desc->vertex_input_formats[0] == GPU_Format_RGB32F &&
-                    desc->vertex_input_formats[1] == GPU_Format_RGB32F && desc->vertex_input_formats[2] == GPU_Format_RGB32F && desc->vertex_input_formats[3] == GPU_Format_RG32F, nullptr,
-                    "GPU_MakeGraphicsPipeline: geometry_pass.glsl reads the 44-byte Vertex (RGB32F x3, RG32F; render.cpp:227)");
-        for (const char* name : {"GLOBALS", "TEX0", "TEX1", "TEX_ORM", "TEX_EMISSIVE", "SAMPLER_LINEAR_WRAP"})
-            GPU_REQUIRE(find_binding(desc->layout, name) >= 0, nullptr, "GPU_MakeGraphicsPipeline: the geometry pass layout has no \"%s\" binding", name);
-        GPU_GraphicsPipeline* p = new GPU_GraphicsPipeline();
-        p->layout = desc->layout; p->pass = desc->render_pass; p->kernel = k; p->shade_flags = 0; p->vertex_stride = 44;
+        p->layout = desc->layout; p->pass = desc->render_pass; p->kernel = k; p->shade_flags = 0; p->vertex_stride = stride; p->raster = rk;
         return p;
     }
     GPU_REQUIRE(k == Kernel_Lighting || k == Kernel_TaaResolve || k == Kernel_FinalPost || k == Kernel_BloomDown || k == Kernel_BloomUp, nullptr,
@@ -954,11 +1217,6 @@ static void push_constants(GPU_Graph* g, void* data, uint32_t size, const char* 
 GPU_API void GPU_OpPushComputeConstants(GPU_Graph* g, GPU_PipelineLayout* l, void* data, uint32_t size) { (void)l; push_constants(g, data, size, __func__); }
 GPU_API void GPU_OpPushGraphicsConstants(GPU_Graph* g, GPU_PipelineLayout* l, void* data, uint32_t size) { (void)l; push_constants(g, data, size, __func__); }
 
-static Slot* named_slot(GPU_DescriptorSet* set, const char* name) {
-    int b = find_binding(set->layout, name);
-    return b < 0 ? nullptr : &set->slots[b];
-}
-
 // Validates a dispatch against the bound pipeline/set at record time, so that nothing can fault at launch.
 static bool record_dispatch(GPU_Graph* g, Op& op, const char* fn) {
     GPU_REQUIRE(g->bound_cpipe, false, "%s: no compute pipeline bound", fn);
@@ -1077,7 +1335,6 @@ GPU_API void GPU_OpBeginRenderPass(GPU_Graph* g) {
     GPU_REQUIRE_V(g->preparing, "GPU_OpBeginRenderPass: GPU_OpPrepareRenderPass was not called");
     g->in_pass = g->preparing; g->preparing = nullptr; g->bound_draw = -1; g->raster_op = -1;
 }
-static void close_raster_job(GPU_Graph* g);
 GPU_API void GPU_OpEndRenderPass(GPU_Graph* g) {
     REC_GUARD(g);
     GPU_REQUIRE_V(g->in_pass, "GPU_OpEndRenderPass: not inside a render pass");
@@ -1214,159 +1471,21 @@ static void record_shade(GPU_Graph* g, uint32_t row0, uint32_t row1, bool explic
     g->ops.push_back(op);
 }
 
-static void record_voxelize_draw(GPU_Graph* g, const DrawParams& dp, uint32_t vertex_count, uint32_t instance_count, uint32_t first_vertex);
 GPU_API void GPU_OpDraw(GPU_Graph* g, uint32_t vertex_count, uint32_t instance_count, uint32_t first_vertex, uint32_t first_instance) {
     REC_GUARD(g);
-    if (g->in_pass && g->bound_draw >= 0 && g->draw_params[(size_t)g->bound_draw].pipeline->kernel == Kernel_Voxelize) {
-        record_voxelize_draw(g, g->draw_params[(size_t)g->bound_draw], vertex_count, instance_count, first_vertex);   // the shader never reads gl_InstanceIndex
-        return;
-    }
+    const RasterKind* rk = bound_raster_row(g);
+    if (rk && !rk->indexed) { record_raster_draw(g, g->draw_params[(size_t)g->bound_draw], vertex_count, instance_count, first_vertex, 0, __func__); return; }   // the shader never reads gl_InstanceIndex
     GPU_REQUIRE_V(vertex_count == 3 && instance_count == 1 && first_vertex == 0 && first_instance == 0,
                   "GPU_OpDraw: unsupported (raster): only the full-screen triangle GPU_OpDraw(3,1,0,0) of the lighting pass is implemented");
     record_shade(g, 0, 0, false, __func__);
 }
 GPU_API void GPUX_OpDrawRows(GPU_Graph* g, uint32_t row0, uint32_t row1) { REC_GUARD(g); record_shade(g, row0, row1, true, __func__); }
-// ---- raster jobs: the indexed draws of the sun depth pass (K12, render.cpp:993-1020) and of the geometry pass (K13, :1076-1115) ----
-// The draws of one render-pass instance are ONE raster job (one Op_Raster): the result does not depend on triangle order (K12: a
-// per-pixel minimum; K13: depth, then triangle number), so merging them is exact, and one setup + one tile launch replace hundreds of
-// per-part launches.  A job is closed (its scratch sized from the known triangle count, no read-back) at GPU_OpEndRenderPass, or,
-// for K12, when the pass binds another vertex / index buffer pair: K13's draws name their own buffers, K12's share the job's.
-static void close_raster_job(GPU_Graph* g) {
-    if (g->raster_op < 0) return;
-    Op& op = g->ops[(size_t)g->raster_op];
-    g->raster_op = -1;
-    if ((size_t)op.raster_slot >= g->raster.size()) g->raster.resize((size_t)op.raster_slot + 1);
-    RasterScratch& rs = g->raster[(size_t)op.raster_slot];
-    const RasterKind& rk = raster_kind(op.gpipe->kernel);
-    const size_t need = rk.scratch_bytes(op.tri_count, (int)op.tex->base.width, (int)op.tex->base.height);
-    bool ok = true;
-    if (rs.dev_bytes < need) {
-        (void)hipFree(rs.dev); rs.dev = nullptr; rs.dev_bytes = 0;
-        if (hipMalloc(&rs.dev, need) == hipSuccess) rs.dev_bytes = need; else { rs.dev = nullptr; ok = false; }
-    }
-    const size_t table = op.draws.size() * rk.draw_bytes;
-    if (ok && rs.draws_cap < table) {
-        (void)hipFree(rs.draws_dev); (void)hipHostFree(rs.draws_host); rs.draws_dev = nullptr; rs.draws_host = nullptr; rs.draws_cap = 0;
-        if (hipMalloc(&rs.draws_dev, table) == hipSuccess && hipHostMalloc((void**)&rs.draws_host, table, hipHostMallocDefault) == hipSuccess) rs.draws_cap = table;
-        else ok = false;
-    }
-    if (ok && !G.raster_rejected) {
-        if (hipMalloc((void**)&G.raster_rejected, 16) != hipSuccess || hipMemset(G.raster_rejected, 0, 16) != hipSuccess) { G.raster_rejected = nullptr; ok = false; }
-    }
-    if (!ok) { (void)hipGetLastError(); op.tri_count = 0; op.draws.clear(); gpu_fail("GPU_OpEndRenderPass: allocation of the raster scratch (%zu bytes) failed", need); }
-}
-
-// One indexed draw of a raster job.  Everything a launch could trip over is checked here.
-static void record_raster_draw(GPU_Graph* g, const DrawParams& dp, uint32_t index_count, uint32_t instance_count, uint32_t first_index, uint32_t vertex_offset) {
-    const char* fn = "GPU_OpDrawIndexed";
-    const bool geo = dp.pipeline->kernel == Kernel_Geometry;
-    const RasterKind& rk = raster_kind(dp.pipeline->kernel);
-    GPU_REQUIRE_V(dp.pipeline->pass == g->in_pass, "%s: pipeline was created for a different render pass", fn);
-    GPU_REQUIRE_V(dp.set->layout == dp.pipeline->layout, "%s: descriptor set and pipeline use different layouts", fn);
-    Slot* gl = named_slot(dp.set, "GLOBALS");
-    if (geo) {
-        GPU_REQUIRE_V(gl && gl->buf && gl->buf->base.size >= 512, "%s: \"GLOBALS\" must be a buffer that holds old_clip_space_from_world (render.h:122-136)", fn);
-        for (const char* name : {"TEX0", "TEX1", "TEX_ORM", "TEX_EMISSIVE"}) {
-            Slot* sl = named_slot(dp.set, name);
-            GPU_REQUIRE_V(sl && sl->tex, "%s: geometry pass: \"%s\" is not bound", fn, name);
-            GPU_REQUIRE_V(is_material_2d(sl->tex) && sl->whole,
-                          "%s: geometry pass: \"%s\" must be a whole 2D RGBA8UN, BC1, BC3 or BC5 texture", fn, name);
-        }
-        Slot* sm = named_slot(dp.set, "SAMPLER_LINEAR_WRAP");
-        GPU_REQUIRE_V(sm && sm->sampler == &G.samplers[0], "%s: geometry pass: \"SAMPLER_LINEAR_WRAP\" must be GPU_SamplerLinearWrap()", fn);
-        GPU_REQUIRE_V(g->push_size == 16, "%s: the geometry pass needs its 16-byte push constants (taa_jitter, taa_jitter_prev; render.cpp:1091-1094)", fn);
-    } else {
-        GPU_REQUIRE_V(gl && gl->buf && gl->buf->base.size >= 448, "%s: \"GLOBALS\" must be a buffer that holds sun_space_from_world (render.h:122-136)", fn);
-    }
-    GPU_REQUIRE_V(g->vertex_buffer, "%s: no vertex buffer bound (GPU_OpBindVertexBuffer)", fn);
-    GPU_REQUIRE_V(g->index_buffer, "%s: no index buffer bound (GPU_OpBindIndexBuffer)", fn);
-    const uint64_t n_idx = g->index_buffer->base.size / 4;                    // 32-bit indices (gpu_vulkan.c:2591-2593)
-    GPU_REQUIRE_V((uint64_t)first_index + index_count <= n_idx, "%s: indices [%u, %llu) lie outside the bound index buffer (%llu indices)", fn,
-                  first_index, (unsigned long long)first_index + index_count, (unsigned long long)n_idx);
-    const uint32_t tris = index_count / 3;                                    // whole triangles only
-    if (tris == 0 || instance_count == 0) return;                             // any instance count > 0 draws the same triangles once
-    if (!geo && g->raster_op >= 0) {
-        const Op& cur = g->ops[(size_t)g->raster_op];
-        if (cur.buf != g->vertex_buffer || cur.buf2 != g->index_buffer || cur.vertex_stride != dp.pipeline->vertex_stride) close_raster_job(g);
-    }
-    if (g->raster_op < 0) {
-        Op op; op.kind = Op_Raster; op.name = rk.op_name;
-        op.pass = g->in_pass; op.gpipe = dp.pipeline;
-        op.tex = (TextureImpl*)g->in_pass->desc.depth_stencil_target;
-        op.buf = g->vertex_buffer; op.buf2 = g->index_buffer; op.vertex_stride = dp.pipeline->vertex_stride;
-        op.raster_slot = (int)g->raster_used++;
-        g->ops.push_back(op);
-        g->raster_op = (int)g->ops.size() - 1;
-    }
-    Op& op = g->ops[(size_t)g->raster_op];
-    GPU_REQUIRE_V((uint64_t)op.tri_count + tris <= (1u << 26), "%s: more than 2^26 triangles in one %s pass", fn, rk.pass_name);
-    RasterDraw d; d.set = dp.set; d.first_tri = op.tri_count; d.first_index = first_index; d.vertex_offset = vertex_offset;
-    d.vb = g->vertex_buffer; d.ib = g->index_buffer; memcpy(d.push, g->push, sizeof d.push);
-    op.draws.push_back(d);
-    op.tri_count += tris;
-}
-
-// One GPU_OpDraw of the voxelise pass (K14, render.cpp:1039-1056): the draws of one render-pass instance that store into one light grid
-// are one job; which store to a voxel wins follows the triangles' submission order, which merging keeps.
-static void record_voxelize_draw(GPU_Graph* g, const DrawParams& dp, uint32_t vertex_count, uint32_t instance_count, uint32_t first_vertex) {
-    const char* fn = "GPU_OpDraw";
-    GPU_REQUIRE_V(dp.pipeline->pass == g->in_pass, "%s: pipeline was created for a different render pass", fn);
-    GPU_REQUIRE_V(dp.set->layout == dp.pipeline->layout, "%s: descriptor set and pipeline use different layouts", fn);
-    const uint32_t N = g->in_pass->desc.width;
-    Slot* gl = named_slot(dp.set, "GLOBALS");
-    GPU_REQUIRE_V(gl && gl->buf && gl->buf->base.size >= 548, "%s: voxelise pass: \"GLOBALS\" must be a buffer that holds lightgrid_scale (548 bytes, render.h:122-136)", fn);
-    Slot* vb = named_slot(dp.set, "SSBO0");
-    Slot* ib = named_slot(dp.set, "SSBO1");
-    GPU_REQUIRE_V(vb && vb->buf, "%s: voxelise pass: \"SSBO0\" (vertices) is not a bound buffer", fn);
-    GPU_REQUIRE_V(ib && ib->buf, "%s: voxelise pass: \"SSBO1\" (indices) is not a bound buffer", fn);
-    const uint64_t n_idx = ib->buf->base.size / 4;
-    GPU_REQUIRE_V((uint64_t)first_vertex + vertex_count <= n_idx, "%s: voxelise pass: vertices [%u, %llu) lie outside \"SSBO1\" (%llu indices)", fn,
-                  first_vertex, (unsigned long long)first_vertex + vertex_count, (unsigned long long)n_idx);
-    Slot* img = named_slot(dp.set, "IMG0");
-    GPU_REQUIRE_V(img && img->tex && img->mip == 0 && img->tex->base.format == GPU_Format_RGBA16F && img->tex->base.layer_count == 1 &&
-                  img->tex->base.width == N && img->tex->base.height == N && img->tex->base.depth == N,
-                  "%s: voxelise pass: \"IMG0\" must be mip 0 of a %u^3 RGBA16F 3-D storage image", fn, N);
-    Slot* sun = named_slot(dp.set, "SUN_DEPTH_MAP");
-    GPU_REQUIRE_V(sun && sun->tex && sun->whole && sun->tex->base.format == GPU_Format_D32F_Or_X8D24UN && sun->tex->base.layer_count == 1 && sun->tex->base.depth == 1,
-                  "%s: voxelise pass: \"SUN_DEPTH_MAP\" must be a whole 2D D32F texture (render.cpp:676)", fn);
-    for (const char* name : {"TEX0", "TEX_EMISSIVE"}) {
-        Slot* sl = named_slot(dp.set, name);
-        GPU_REQUIRE_V(sl && sl->tex && sl->whole && is_material_2d(sl->tex),
-                      "%s: voxelise pass: \"%s\" must be a whole 2D RGBA8UN, BC1, BC3 or BC5 texture", fn, name);
-    }
-    Slot* sm = named_slot(dp.set, "SAMPLER_LINEAR_WRAP");
-    GPU_REQUIRE_V(sm && sm->sampler == &G.samplers[0], "%s: voxelise pass: \"SAMPLER_LINEAR_WRAP\" must be GPU_SamplerLinearWrap()", fn);
-    Slot* pc = named_slot(dp.set, "SAMPLER_PERCENTAGE_CLOSER");
-    GPU_REQUIRE_V(pc && pc->sampler && pc->sampler->desc.min_filter == GPU_Filter_Linear && pc->sampler->desc.mag_filter == GPU_Filter_Linear &&
-                  pc->sampler->desc.address_modes[0] == GPU_AddressMode_Clamp && pc->sampler->desc.address_modes[1] == GPU_AddressMode_Clamp &&
-                  pc->sampler->desc.compare_op == GPU_CompareOp_Less,
-                  "%s: voxelise pass: \"SAMPLER_PERCENTAGE_CLOSER\" must be a linear / clamp / GPU_CompareOp_Less sampler (render.cpp:664-673)", fn);
-    const uint32_t tris = vertex_count / 3;                                   // whole triangles only
-    if (tris == 0 || instance_count == 0) return;                             // any instance count > 0 draws the same triangles once
-    if (g->raster_op >= 0 && g->ops[(size_t)g->raster_op].tex != img->tex) close_raster_job(g);     // another grid: another job, in order
-    if (g->raster_op < 0) {
-        Op op; op.kind = Op_Raster; op.name = kVoxelizeJob.op_name;
-        op.pass = g->in_pass; op.gpipe = dp.pipeline; op.tex = img->tex;
-        op.raster_slot = (int)g->raster_used++;
-        g->ops.push_back(op);
-        g->raster_op = (int)g->ops.size() - 1;
-    }
-    Op& op = g->ops[(size_t)g->raster_op];
-    GPU_REQUIRE_V(op.gpipe->kernel == Kernel_Voxelize, "%s: a voxelise draw inside another raster pass", fn);
-    GPU_REQUIRE_V((uint64_t)op.tri_count + tris <= (1u << 26), "%s: more than 2^26 triangles in one %s pass", fn, kVoxelizeJob.pass_name);
-    RasterDraw d; d.set = dp.set; d.first_tri = op.tri_count; d.first_index = first_vertex; d.vertex_offset = 0;
-    d.vb = vb->buf; d.ib = ib->buf;
-    op.draws.push_back(d);
-    op.tri_count += tris;
-}
-
 GPU_API void GPU_OpDrawIndexed(GPU_Graph* g, uint32_t index_count, uint32_t instance_count, uint32_t first_index, uint32_t vertex_offset, uint32_t first_instance) {
     (void)first_instance;                                                     // the shader never reads gl_InstanceIndex
     REC_GUARD(g);
-    GPU_REQUIRE_V(g->in_pass && g->bound_draw >= 0 && (g->draw_params[(size_t)g->bound_draw].pipeline->kernel == Kernel_SunDepth ||
-                                                       g->draw_params[(size_t)g->bound_draw].pipeline->kernel == Kernel_Geometry),
-                  "GPU_OpDrawIndexed: unsupported (raster): only the sun depth pass (sun_depth_pass.glsl) and the geometry pass (geometry_pass.glsl) draw indexed triangles");
-    record_raster_draw(g, g->draw_params[(size_t)g->bound_draw], index_count, instance_count, first_index, vertex_offset);
+    const RasterKind* rk = bound_raster_row(g);
+    GPU_REQUIRE_V(rk && rk->indexed, "GPU_OpDrawIndexed: unsupported (raster): only the sun depth pass (sun_depth_pass.glsl) and the geometry pass (geometry_pass.glsl) draw indexed triangles");
+    record_raster_draw(g, g->draw_params[(size_t)g->bound_draw], index_count, instance_count, first_index, vertex_offset, __func__);
 }
 GPU_API void GPU_OpBindVertexBuffer(GPU_Graph* g, GPU_Buffer* b) {
     REC_GUARD(g);
@@ -1610,26 +1729,6 @@ static float reference_roughness(int mip) {                      // gen_prefilte
     return r > 1.0f ? 1.0f : r;
 }
 
-static hipEvent_t next_event(GPU_Graph* g, size_t& used) {
-    if (used == g->ev.size()) { hipEvent_t e; HIP_OK(hipEventCreate(&e)); g->ev.push_back(e); }
-    return g->ev[used++];
-}
-
-// Runs `launch` bracketed by events when timing is on.
-template <class F>
-static void timed(GPU_Graph* g, const std::string& name, size_t& ev_used, F launch) {
-    if (G.timing) {
-        hipEvent_t a = next_event(g, ev_used);
-        HIP_OK(hipEventRecord(a, g->cur));
-        launch();
-        hipEvent_t b = next_event(g, ev_used);
-        HIP_OK(hipEventRecord(b, g->cur));
-        g->timed_names.push_back(name);
-    } else {
-        launch();
-    }
-}
-
 static hipEvent_t next_sync_event(GPU_Graph* g) {
     if (g->sync_used == g->sync_ev.size()) { hipEvent_t e; HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); g->sync_ev.push_back(e); }
     return g->sync_ev[g->sync_used++];
@@ -1642,53 +1741,6 @@ static void publish_side_work(GPU_Graph* g) {
     HIP_OK(hipEventRecord(e, g->cur));
     HIP_OK(hipStreamWaitEvent(g->stream, e, 0));
     for (hipStream_t s : g->side) if (s != g->cur) HIP_OK(hipStreamWaitEvent(s, e, 0));
-}
-
-// Globals as they are at submit time: the caller fills the persistently mapped buffer before GPU_GraphSubmit (render.cpp:991)
-static void read_globals(const BufferImpl* buf, size_t offset, void* dst, size_t bytes) {
-    if (buf->pinned_host) memcpy(dst, (const char*)buf->dev + offset, bytes);
-    else HIP_OK(hipMemcpy(dst, (const char*)buf->dev + offset, bytes, hipMemcpyDeviceToHost));
-}
-
-// A raster job: upload the draw table that GPU_GraphSubmit snapshotted, setup (transform, bin), tiles
-static void exec_raster(GPU_Graph* g, Op& op, size_t& ev_used) {
-    if (!op.tri_count) return;
-    hipStream_t st = g->cur;
-    RasterScratch& rs = g->raster[(size_t)op.raster_slot];
-    const RasterKind& rk = raster_kind(op.gpipe->kernel);
-    const bool geo = op.gpipe->kernel == Kernel_Geometry;
-    const bool vox = op.gpipe->kernel == Kernel_Voxelize;
-    PbrkRasterArgs sa;
-    PbrkGeometryArgs ga;
-    PbrkVoxelizeArgs va;
-    if (vox) {
-        va.draws = (const PbrkVoxDraw*)rs.draws_dev; va.draw_count = (uint32_t)op.draws.size(); va.tri_count = op.tri_count;
-        va.grid = op.tex->dev; va.n = (int)op.tex->base.width;
-        va.scratch = rs.dev; va.rejected = G.raster_rejected; va.fragments = G.raster_rejected + 1;
-    } else if (geo) {
-        ga.draws = (const PbrkGeoDraw*)rs.draws_dev; ga.draw_count = (uint32_t)op.draws.size(); ga.tri_count = op.tri_count;
-        for (int k = 0; k < 4; ++k) ga.color[k] = ((TextureImpl*)op.pass->targets[(size_t)k].texture)->dev;
-        ga.velocity = ((TextureImpl*)op.pass->targets[4].texture)->dev;
-        ga.depth = (float*)op.tex->dev; ga.width = (int)op.tex->base.width; ga.height = (int)op.tex->base.height;
-        ga.scratch = rs.dev; ga.rejected = G.raster_rejected;
-    } else {
-        sa.vertices = op.buf->dev; sa.vertex_stride = op.vertex_stride; sa.vertex_count = op.buf->base.size / op.vertex_stride;
-        sa.indices = (const uint32_t*)op.buf2->dev;
-        sa.draws = (const PbrkRasterDraw*)rs.draws_dev; sa.draw_count = (uint32_t)op.draws.size(); sa.tri_count = op.tri_count;
-        sa.depth = (float*)op.tex->dev; sa.width = (int)op.tex->base.width; sa.height = (int)op.tex->base.height;
-        sa.scratch = rs.dev; sa.rejected = G.raster_rejected;
-    }
-    timed(g, std::string(rk.tag) + (vox ? ".cover" : ".setup"), ev_used, [&] {
-        HIP_OK(hipMemcpyAsync(rs.draws_dev, rs.draws_host, op.draws.size() * rk.draw_bytes, hipMemcpyHostToDevice, st));
-        int rc = vox ? pbrk_voxelize_cover(&va, st) : geo ? pbrk_geometry_setup(&ga, st) : pbrk_raster_setup(&sa, st);
-        if (rc != PBRK_OK) gpu_fail("%s setup launch failed (%d)", rk.tag, rc);
-    });
-    timed(g, std::string(rk.tag) + (vox ? ".resolve" : ".tiles"), ev_used, [&] {
-        int rc = vox ? pbrk_voxelize_resolve(&va, st) : geo ? pbrk_geometry_tiles(&ga, st) : pbrk_raster_tiles(&sa, st);
-        if (rc != PBRK_OK) gpu_fail("%s tile launch failed (%d)", rk.tag, rc);
-    });
-    for (const GPU_TextureView& tv : op.pass->targets) { ((TextureImpl*)tv.texture)->bordered_valid = false; ((TextureImpl*)tv.texture)->lut_cells_valid = false; }
-    op.tex->bordered_valid = false;
 }
 
 static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
@@ -2162,60 +2214,6 @@ static uint64_t g_overlapped_submits = 0;
 GPU_API void GPUX_SetGraphOverlap(int on) { g_overlap_on = on; }
 GPU_API uint64_t GPUX_OverlappedSubmitCount(void) { return g_overlapped_submits; }
 static bool contains(const std::vector<TextureImpl*>& v, const TextureImpl* t) { for (const TextureImpl* x : v) if (x == t) return true; return false; }
-
-// The draw tables of the raster jobs, filled from what every draw's GLOBALS holds now (the caller fills the mapped Globals before
-// submitting, render.cpp:991), before anything is launched.
-static bool fill_sun_draw(const RasterDraw& d, PbrkRasterDraw& o) {
-    read_globals(named_slot(d.set, "GLOBALS")->buf, 384, o.m, 64);           // render.h:129: sun_space_from_world
-    // an orthographic matrix (last row (0, 0, 0, c > 0)) needs no near-plane clip
-    GPU_REQUIRE(o.m[3] == 0.0f && o.m[7] == 0.0f && o.m[11] == 0.0f && o.m[15] > 0.0f, false,
-                "GPU_GraphSubmit: perspective sun projection not implemented (sun_space_from_world's last row must be (0, 0, 0, c > 0))");
-    o.first_tri = d.first_tri; o.first_index = d.first_index; o.vertex_offset = d.vertex_offset; o.pad = 0;
-    return true;
-}
-static bool fill_geo_draw(const RasterDraw& d, PbrkGeoDraw& o) {          // both matrices, the draw's textures and buffers
-    memset(&o, 0, sizeof o);
-    const BufferImpl* gb = named_slot(d.set, "GLOBALS")->buf;
-    read_globals(gb, 0, o.m, 64); read_globals(gb, 448, o.m_old, 64);      // render.h:123, :130
-    memcpy(o.jitter, d.push, 8); memcpy(o.jitter_prev, d.push + 2, 8);
-    static const char* const names[4] = {"TEX0", "TEX1", "TEX_ORM", "TEX_EMISSIVE"};
-    for (int k = 0; k < 4; ++k) {
-        const TextureImpl* t = named_slot(d.set, names[k])->tex;
-        o.tex[k].texels = material_texels(t); o.tex[k].width = (int)t->base.width; o.tex[k].height = (int)t->base.height; o.tex[k].levels = (int)t->base.mip_level_count;
-    }
-    o.vertices = d.vb->dev; o.indices = (const uint32_t*)d.ib->dev; o.vertex_count = d.vb->base.size / 44u;
-    o.first_tri = d.first_tri; o.first_index = d.first_index; o.vertex_offset = d.vertex_offset;
-    return true;
-}
-static bool fill_vox_draw(const RasterDraw& d, PbrkVoxDraw& o) {          // sun matrix and direction, scale, the draw's buffers and textures
-    memset(&o, 0, sizeof o);
-    const BufferImpl* gb = named_slot(d.set, "GLOBALS")->buf;
-    read_globals(gb, 384, o.sun, 64); read_globals(gb, 512, o.sun_dir, 16); read_globals(gb, 544, &o.scale, 4);    // render.h:129, :131, :134
-    o.first_tri = d.first_tri; o.first_vertex = d.first_index;
-    o.vertices = (const float*)d.vb->dev; o.vertex_floats = d.vb->base.size / 4u; o.indices = (const uint32_t*)d.ib->dev;
-    const TextureImpl* sun = named_slot(d.set, "SUN_DEPTH_MAP")->tex;
-    o.sun_depth = (const float*)sun->dev; o.sun_w = (int)sun->base.width; o.sun_h = (int)sun->base.height;
-    static const char* const names[2] = {"TEX0", "TEX_EMISSIVE"};
-    for (int k = 0; k < 2; ++k) {
-        const TextureImpl* t = named_slot(d.set, names[k])->tex;
-        o.tex[k].texels = material_texels(t); o.tex[k].width = (int)t->base.width; o.tex[k].height = (int)t->base.height; o.tex[k].levels = (int)t->base.mip_level_count;
-    }
-    return true;
-}
-static bool snapshot_raster_draws(GPU_Graph* g) {
-    for (const Op& op : g->ops) {
-        if (op.kind != Op_Raster || !op.tri_count) continue;
-        void* table = g->raster[(size_t)op.raster_slot].draws_host;
-        const bool geo = op.gpipe->kernel == Kernel_Geometry;
-        if (op.gpipe->kernel == Kernel_Voxelize) {
-            for (size_t i = 0; i < op.draws.size(); ++i) if (!fill_vox_draw(op.draws[i], ((PbrkVoxDraw*)table)[i])) return false;
-            continue;
-        }
-        for (size_t i = 0; i < op.draws.size(); ++i)
-            if (!(geo ? fill_geo_draw(op.draws[i], ((PbrkGeoDraw*)table)[i]) : fill_sun_draw(op.draws[i], ((PbrkRasterDraw*)table)[i]))) return false;
-    }
-    return true;
-}
 
 GPU_API void GPU_GraphSubmit(GPU_Graph* g) {
     GPU_REQUIRE_V(g && !g->submitted, "GPU_GraphSubmit: graph is NULL or already submitted");
