@@ -154,6 +154,15 @@ int pbrk_mc_region_phase_stats(unsigned long long* out5);
 /* the region kernel's visiting order: the k-th region (0 .. 6 G^2 - 1) a tile of `face` stages at G regions per face edge -- its own
  * face's regions first, then the others in index order; -1 for arguments out of range.  Host-side twin of the kernel's loop. */
 int pbrk_mc_region_order(int face, int G, int k);
+/* the region kernel's launch-level cut on the shapes that run each slice's head word first (default 1; tests and A-B runs): mask words
+ * proved, once per launch, to be no-ops for every lane are not binned at all; the outputs are the same bit for bit either way */
+void pbrk_mc_set_launch_cut(int on);
+/* that proof on the host: weights[n] = the table's sample weights, min_bits / max_bits = the smallest / largest R, G, B bit pattern of
+ * the bordered level.  cut4[s] = the first cut mask word of slice s (words s, s + 4, ..), or the slice's first index at or behind
+ * ceil(n / 32) when none is cut.  Returns the number of words cut, -1 for bad arguments.  Needs no GPU. */
+int pbrk_mc_launch_cut(const float* weights, int n, unsigned min_bits, unsigned max_bits, int* cut4);
+/* the cut of the last region-kernel launch: {first cut word of slices 0 .. 3, mask words per region, words cut}; waits for the device */
+int pbrk_mc_launch_cut_stats(int* out6);
 
 /* ---- K5: deferred shade pass (shaders/lighting_pass.glsl:432-716, in-scope sub-blocks). */
 typedef struct PbrkShadeArgs {

@@ -70,6 +70,45 @@ __host__ __device__ __forceinline__ int mc_region_visit(int k, int own, int GG) 
     return k < GG ? own + k : (k < own + GG ? k - GG : k);
 }
 
+// k_mc_region.hip, header 2g: the launch-level cut.  Slice s of the sample table owns the mask words s, s + 4, ..; word s is its head,
+// run first over every region (head phase), the others are its tail.  wbits[NW]: per mask word the largest bit pattern of its
+// samples' weights (W_w); H[s]: the sum of the 32 weights of head word s, added in index order in double; min_bits / max_bits: the
+// smallest / largest R, G, B bit pattern of the bordered source level (m, M).  Tail word w of slice s is cut when every word
+// w' >= w of the slice satisfies, in double and evaluated left to right,
+//     W_w' * M * 2^25 * (1 + 2^-10) <= H_s * m
+// with m a normal positive float, M finite, every weight >= +0 (a bit pattern below +inf's) and H_s m 2^-25 >= 2^-100.  Then every
+// lane's three sums are at least H_s m (1 - 2^-12) once the head phase is over (each head sample is taken exactly once, its tap
+// weights are monotone roundings that add up to its weight within a few ulp, every tap is >= m, and 128 FMAs lose under 2^-17
+// relative), they never fall afterwards (all products >= 0), and every product of a cut word is <= W M <= acc 2^-25: by the
+// lemma at absorb_threshold each of its FMAs returns its sum unchanged, for every lane of every tile.  cut4[s]: the first cut
+// word of slice s, or the first index of the slice at or behind NW when none is cut.  Returns the number of words cut; 0 for tables
+// of at most 128 samples (one phase, no tail).
+__host__ __device__ inline int mc_launch_cut(const unsigned* wbits, int NW, const double* H, unsigned min_bits, unsigned max_bits, int* cut4) {
+    for (int s = 0; s < 4; ++s) cut4[s] = s >= NW ? s : s + 4 * ((NW - s + 3) / 4);
+    if (NW <= 4) return 0;
+    if (min_bits < 0x00800000u || min_bits >= 0x7f800000u || max_bits >= 0x7f800000u) return 0;
+    for (int w = 0; w < NW; ++w)
+        if (wbits[w] >= 0x7f800000u) return 0;
+    union { unsigned u; float f; } cm, cM, cW;
+    cm.u = min_bits; cM.u = max_bits;
+    const double m = (double)cm.f, M = (double)cM.f;
+    int ncut = 0;
+    for (int s = 0; s < 4; ++s) {
+        const double rhs = H[s] * m;
+        if (!(rhs * 0x1p-25 >= 0x1p-100)) continue;                // NaN fails
+        int c = cut4[s];
+        for (int w = c - 4; w > s; w -= 4) {
+            cW.u = wbits[w];
+            const double lhs = (double)cW.f * M * 0x1p25 * (1.0 + 0x1p-10);
+            if (!(lhs <= rhs)) break;
+            c = w;
+        }
+        ncut += (cut4[s] - c) / 4;
+        cut4[s] = c;
+    }
+    return ncut;
+}
+
 // k_mc_region.hip: taps from LDS-staged regions of the source level.  Returns false when the kernel does not apply
 // (the caller then takes the direct kernel); the decision depends on the level's shape only, never on the dispatched range.
 bool launch_mc_region(McArgs a, int nfaces, hipStream_t st);

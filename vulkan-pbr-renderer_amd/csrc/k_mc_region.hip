@@ -45,9 +45,26 @@
 //      sweeps with a constant divisor: under 1 % of their kernels).  Flags may differ from the earlier prologue's by the rounding of (ii);
 //      the samples accumulated, their order and the absorb decisions do not: same bytes (pbrk_mc_set_prologue(0) keeps the earlier
 //      prologue as the yardstick, tests/test_gpu_mc_prologue.py).
-// Each (texel, sample) pair is accumulated exactly once, in an order (66^2 shapes: own face's regions, then the other regions in
-// index order; else regions in index order; sample index inside a region) that depends on the level's shape and the texel's face
-// only, not on the tile: a row-sharded dispatch equals a full one bit for bit.
+//   2g. (round 8, head words first; the launch-level cut) slice s of the sample table owns the mask words s, s + 4, ..: word s is its
+//      head, the others its tail.  A tile runs the head words over every region flagged for them (visiting order of 2e), then the
+//      tail words the same way; any[r] carries one flag per phase and a region is staged for a phase only when that phase has a
+//      sample in it.  After the head phase every lane holds all 32 head samples of its slice, whichever regions they fell in, so its
+//      sums are at least H_s m (1 - 2^-12) -- H_s the head word's weights added up, m the smallest R, G, B of the bordered level --
+//      for EVERY lane of EVERY tile of the launch.  That turns "beyond sample ~450 nothing can change any sum", which every tile of
+//      C4 mip 1 rediscovered word by word (2c: a threshold test per word and region, count-only bodies for the unproved samples,
+//      binning and mask words for all 1389 samples), into one inequality per word and launch (mc_launch_cut, k_mc_internal.h):
+//      k_mc_cut, one wave behind k_mc_prep, writes the first cut word of each slice behind the maxima.  The kernel does not bin the
+//      samples of cut words (a thread's samples all belong to one slice: its loop simply ends earlier), so they hold no mask bit, flag
+//      no region and are never visited; the slice's expected count is formed in the kernel by crediting them up front.  Dropping
+//      them is exact -- every FMA of theirs would have returned its sum unchanged -- so a launch without a k_mc_prep result
+//      (pbrk_mc_set_prologue(0), pbrk_mc_set_absorb(0), stream capture, no free ring slot, pbrk_mc_set_launch_cut(0)) just keeps them:
+//      same bytes.  The words that remain keep the per-word test of 2c.  Under PBR_MC_STATS the cut samples still run through the flag
+//      computation and are counted as absorbed (stats[2], [6], [7]: the counters keep their meaning), then their bits are cleared.
+//      Tables of at most 128 samples have no tail: one phase.  Per shape (MC_HEAD_FIRST_SUB / MC_HEAD_FIRST_G1; DESIGN.md 4, "K4b,
+//      round 8"); the 34^2 / 18^2 shapes and the MFMA variant keep their order and bytes.
+// Each (texel, sample) pair is accumulated exactly once, in an order (66^2 shapes: head phase then tail phase; in each, own face's
+// regions, then the other regions in index order; else regions in index order; sample index inside a region) that depends on the
+// level's shape and the texel's face only, not on the tile: a row-sharded dispatch equals a full one bit for bit.
 #include "pbr_device.h"
 #include "pbr_kernels.h"
 #include "k_mc_internal.h"
@@ -69,6 +86,14 @@ typedef const __attribute__((address_space(4))) unsigned* cu32_t;
 // The smaller tile halves the frame spread delta the region flags are built from (fewer samples flagged for two regions) and
 // pays four times the binning / staging per texel: it wins where regions are small next to that spread (n_src <= 32).
 #define REG_MAX_S 16
+// Header 2g, decided per 66^2 shape by measurement: head words first (and with it the launch-level cut) on the quarter-face shape
+// (SUB) / on the whole-face shape (G == 1).  0 keeps the shape's earlier order and bytes.
+#ifndef MC_HEAD_FIRST_SUB
+#define MC_HEAD_FIRST_SUB 1
+#endif
+#ifndef MC_HEAD_FIRST_G1
+#define MC_HEAD_FIRST_G1 1
+#endif
 
 struct RegArgs {
     McArgs a;
@@ -81,6 +106,7 @@ struct RegArgs {
     int pole_row[2];            // faces +X / -X: tile row (relative to the dispatch's first row, clamped) nearest to the pole of the tangent frame
     const unsigned* tabmax;     // lean prologue, absorb: [NW] largest weight bit pattern per mask word, then [NR] largest staged R, G, B bit pattern per
                                 // region (k_mc_prep, once per launch); null with the parent's prologue
+    int cut;                    // header 2g: tabmax holds, behind the maxima, the first cut word of each slice (k_mc_cut); 0: no word is dropped
     int absorb;                 // skip mask words whose samples are absorbed by every lane's sums (pbrk_mc_set_absorb; bit-identical)
     unsigned long long* stats;  // optional: [0] += healed wave-slices, [1] += all wave-slices, [2] += (region, sample) flags, [3] += samples per tile, [4] += regions visited,
                                 // [5] += proved samples (SUB), [6] += absorbed wave-words, [7] += their wave-samples, [8] += of those run through the
@@ -267,7 +293,8 @@ __device__ __forceinline__ float absorb_threshold(float wmax, float m) {
     return t < 0x1p-100f ? 0x1p-100f : t;                               // NaN stays NaN
 }
 
-// One pass over the flagged samples of this wave's slice for the staged region.  Samples are taken two at a time so that the
+// One pass over the flagged samples of the words w0, w0 + REG_S, .. below w1 of this wave's slice (the whole slice, or the head word /
+// the tail words of header 2g) for the staged region.  Samples are taken two at a time so that the
 // second table entry's scalar load is in flight while the first sample computes.
 // cwords holds, per mask word, the samples proved to be in this region for the whole tile.  CERT: they run certain_sample; else
 // they are only credited in absorbed words.  cwords + NW (LEAN: wmg, the launch's table): per mask word, the bit pattern of its largest weight.  rbits: the bit
@@ -275,18 +302,18 @@ __device__ __forceinline__ float absorb_threshold(float wmax, float m) {
 // the workgroup's LDS counters {absorbed wave-words, their wave-samples, of those run through the count-only body}.
 template <int RS, bool SUB, int CLS, int REG_S, bool CERT, bool LEAN>
 __device__ __forceinline__ void region_pass(unsigned lds_base, const unsigned* __restrict__ mwords, const unsigned* __restrict__ cwords, cu32_t wmg,
-                                            unsigned rbits, unsigned* skc, int NW, int s,
+                                            unsigned rbits, unsigned* skc, int NW, int w0, int w1,
                                             ctab_t tab, f3 Pb, f3 Pt, f3 Pr, float half_n, float off,
                                             float ulo, float uhi, float vlo, float vhi,
                                             float& ar, float& ag, float& ab, unsigned& cnt) {
-    unsigned mnext = s < NW ? (unsigned)__builtin_amdgcn_readfirstlane((int)mwords[s]) : 0u;
-    unsigned cnext = (CERT && s < NW) ? (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[s]) : 0u;
-    for (int w = s; w < NW; w += REG_S) {
+    unsigned mnext = w0 < w1 ? (unsigned)__builtin_amdgcn_readfirstlane((int)mwords[w0]) : 0u;
+    unsigned cnext = (CERT && w0 < w1) ? (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[w0]) : 0u;
+    for (int w = w0; w < w1; w += REG_S) {
         unsigned m = mnext;
         unsigned c = cnext;
-        mnext = w + REG_S < NW ? (unsigned)__builtin_amdgcn_readfirstlane((int)mwords[w + REG_S]) : 0u;
+        mnext = w + REG_S < w1 ? (unsigned)__builtin_amdgcn_readfirstlane((int)mwords[w + REG_S]) : 0u;
         if (CERT) {
-            cnext = w + REG_S < NW ? (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[w + REG_S]) : 0u;
+            cnext = w + REG_S < w1 ? (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[w + REG_S]) : 0u;
             cnt += 64u * (unsigned)__builtin_popcount(m & c);              // every lane takes every proved sample
         }
         ctab_t tw = tab + (w << 5);
@@ -334,18 +361,19 @@ __device__ __forceinline__ void region_pass(unsigned lds_base, const unsigned* _
 
 // region_pass with less scalar work per word and per sample (round 5, 66^2 shapes; RUNS in k_mc_region).  Same words, samples,
 // bodies, absorb decisions and FMA order; cnt counts per LANE (every lane of a complete wave ends at expect[s]):
-//   * only the non-empty words of the slice are visited: one LDS read per lane (lane k: word s + REG_S k; NW <= 256) and a ballot;
+//   * only the non-empty words of the slice are visited: one LDS read per lane (lane k: word s + REG_S k; NW <= 256) and a ballot,
+//     masked by wsel (bit k: word s + REG_S k belongs to this pass -- all, the head word alone, or the tail words: header 2g);
 //   * CERT: the proved samples below the next tested one run as a run of certain_sample (no per-sample proved-bit test, no exec
 //     join), then the tested one, in index order;
 //   * tested samples use lane_sample (one ballot chain), and every loop issues the next table entry's load ahead of the body.
 template <int RS, bool SUB, int CLS, int REG_S, bool CERT, bool LEAN>
 __device__ __forceinline__ void region_pass_runs(unsigned lds_base, const unsigned* __restrict__ mwords, const unsigned* __restrict__ cwords, cu32_t wmg,
-                                                 unsigned rbits, unsigned* skc, int NW, int s,
+                                                 unsigned rbits, unsigned* skc, int NW, int s, unsigned long long wsel,
                                                  ctab_t tab, f3 Pb, f3 Pt, f3 Pr, float half_n, float off,
                                                  float ulo, float uhi, float vlo, float vhi,
                                                  float& ar, float& ag, float& ab, unsigned& cnt) {
     const int wl = s + REG_S * (int)(threadIdx.x & 63);
-    unsigned long long nz = __builtin_amdgcn_ballot_w64(wl < NW && mwords[wl] != 0u);
+    unsigned long long nz = __builtin_amdgcn_ballot_w64(wl < NW && mwords[wl] != 0u) & wsel;
     auto tested = [&](const v4f e) { lane_sample<RS, SUB, CLS>(e, lds_base, Pb, Pt, Pr, half_n, off, ulo, uhi, vlo, vhi, ar, ag, ab, cnt); };
     while (nz) {
         const int w = s + REG_S * (int)__builtin_ctzll(nz);
@@ -398,10 +426,15 @@ __device__ __forceinline__ void region_pass_runs(unsigned lds_base, const unsign
 // moves mu, mv by less than 5e-7 relative (rl enters three times, the root once: 4 x 2^-23 and their roundings), inside the 1.0001
 // they carry, and uc, vc by less than 2^-22 (|sc / ma| + 1) half_n texel, under 1e-3 texel up to n = 1024, inside the 0.05: the flags
 // stay a superset of what any texel of the tile reaches, and "certain" is claimed under the same inequalities.
-template <bool LEAN, bool G1>
+// TWO (header, 2g): any[r] holds two flags, byte 0 for the head words (0 .. 3) and byte 1 for the tail words.  lim: the first sample
+// index this thread does not bin -- 32 x the cut word of its slice (a thread's samples i = tid + 1024 k all fall into slice
+// (tid >> 5) & 3), n_tab without a cut.  keep_cut (counters only): the samples behind lim still run and set their mask bits, but no
+// region flag; the caller counts and clears those bits.
+template <bool LEAN, bool G1, bool TWO = false>
 __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsigned* dmax, int NR, int NW, int G, int RC, int n,
                                            f3 R, f3 T, f3 B, f3 Rc, f3 Tc, f3 Bc, ctab_t tab, int n_tab, int tid,
-                                           unsigned* cmask = nullptr, unsigned* wmax = nullptr, int ntail = 0) {
+                                           unsigned* cmask = nullptr, unsigned* wmax = nullptr, int ntail = 0,
+                                           int lim = 0x7fffffff, bool keep_cut = false) {
     const float nf = (float)n;
     const float half_n = 0.5f * nf;
     const float off = 0.5f * nf + 0.5f;
@@ -417,8 +450,11 @@ __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsig
     // (Rot - I) M_c with singular values {0, 2 sin(theta/2), 2 sin(theta/2)}: the spectral norm is the Frobenius norm / sqrt(2).
     // Inflated for the frames' own rounding (1e-7) and that of both evaluations.
     const float delta = __uint_as_float(*dmax) * 0.70710678f * 1.001f + 4e-6f;
-    for (int i = tid; i < n_tab; i += 1024) {
+    const int i_end = (TWO && !keep_cut) ? min(n_tab, lim) : n_tab;
+    for (int i = tid; i < i_end; i += 1024) {
         const v4f e = tab[i];
+        // TWO: the byte of any[r] this sample flags -- 0 head, 1 tail, 2 (never read) a cut sample run for the counters
+        const int ab = TWO ? (i >= lim ? 2 : (i >= 128 ? 1 : 0)) : 0;
         const float Lx = fmaf(e.x, Bc.x, fmaf(e.y, Tc.x, e.z * Rc.x));
         const float Ly = fmaf(e.x, Bc.y, fmaf(e.y, Tc.y, e.z * Rc.y));
         const float Lz = fmaf(e.x, Bc.z, fmaf(e.y, Tc.z, e.z * Rc.z));
@@ -453,7 +489,8 @@ __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsig
             if (LEAN && G1) {                                              // RC = n + 1: every tap position of the face lies in region f
                 if (certain) atomicOr(&cmask[i >> 5], bit);
                 atomicOr(&masks[f * NW + (i >> 5)], bit);
-                any[f] = 1u;
+                if (TWO) ((unsigned char*)any)[4 * f + ab] = 1;
+                else any[f] = 1u;
                 continue;
             }
             const int rc = LEAN ? 65 : RC;
@@ -463,7 +500,8 @@ __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsig
                 for (int gx = gx0; gx <= gx1; ++gx) {
                     const int r = (f * G + gy) * G + gx;
                     atomicOr(&masks[r * NW + (i >> 5)], bit);
-                    any[r] = 1u;
+                    if (TWO) ((unsigned char*)any)[4 * r + ab] = 1;
+                    else any[r] = 1u;
                 }
         }
     }
@@ -497,6 +535,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     // index order and their bytes: there the reordered sums bought nothing and moved C4 mip 3 to 2.5e-5 from the direct kernel,
     // past the 2e-5 of the every-texel cross-check (test_gpu_configs.py)
     constexpr bool OWN_FIRST = ABS;
+    // see the header, 2g: head words first, then the tail words; decided per 66^2 shape (MC_HEAD_FIRST_SUB / MC_HEAD_FIRST_G1)
+    constexpr bool TWO = RS == 66 && (SUB ? MC_HEAD_FIRST_SUB != 0 : MC_HEAD_FIRST_G1 != 0);
+    const bool cut_on = TWO && LEAN && q.cut != 0;                       // workgroup-uniform: the launch's cut words are not binned
     unsigned* cmask = dmax + 1;                                          // [NW] samples proved to tap one region from the whole tile
     unsigned* wmax = cmask + q.NW;                                       // [NW] (absorb, !LEAN) largest weight (bit pattern) per mask word
     unsigned* rmax = wmax + q.NW;                                        // [NR] (absorb, !LEAN) largest staged R, G, B bit pattern per region
@@ -551,8 +592,11 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     // ---- 1. binning ----
     if (ABS && tid < 4) skc[tid] = 0u;                                   // ordered by the barrier behind region_bin's clearing
     [[maybe_unused]] const unsigned long long st1 = STAMP();
-    region_bin<LEAN, !SUB>(masks, any, dmax, NR, NW, G, RC, n, R, T, B, Rc, Tc, Bc, tab, p.n_tab, tid, (CERT || ABS) ? cmask : nullptr,
-                           (absorb_on && !LEAN) ? wmax : nullptr, (absorb_on && !LEAN) ? 2 * NW + NR : ((CERT || ABS) ? NW : 0));
+    // the first cut word of this thread's slice (a vector load of one of four words behind the maxima)
+    const int lim = cut_on ? (int)q.tabmax[NW + NR + ((tid >> 5) & 3)] << 5 : 0x7fffffff;
+    region_bin<LEAN, !SUB, TWO>(masks, any, dmax, NR, NW, G, RC, n, R, T, B, Rc, Tc, Bc, tab, p.n_tab, tid, (CERT || ABS) ? cmask : nullptr,
+                                (absorb_on && !LEAN) ? wmax : nullptr, (absorb_on && !LEAN) ? 2 * NW + NR : ((CERT || ABS) ? NW : 0),
+                                lim, cut_on && q.stats != nullptr);
     [[maybe_unused]] unsigned long long st_stage = 0ull;
 #ifdef PBR_MC_PHASE_STAMPS
     __syncthreads();                                               // the wait for the slowest thread's binning is charged to binning
@@ -562,15 +606,34 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     // ---- 2. region passes ----
     float ar = 0.0f, ag = 0.0f, ab = 0.0f;
     unsigned cnt = 0;
+    if (cut_on) {
+        // expect[s] less the samples of the slice's cut words (full words, but for the table's last one), formed here as a credit: the
+        // count starts at what the cut took out, so nothing of it stays alive across the passes
+        const int cw = (int)wmg[NW + NR + s], last = NW - 1;
+        if (cw <= last) {
+            const int kc = (last - cw) / REG_S + 1;                  // cut words cw, cw + REG_S, .. <= last
+            cnt = (unsigned)(32 * kc - ((last - cw) % REG_S == 0 ? 32 * NW - p.n_tab : 0)) * (RUNS ? 1u : 64u);
+        }
+    }
     if (q.stats) {                                                 // diagnostics: (region, sample) flags of this tile, samples, regions visited
         __syncthreads();
-        unsigned fl = 0;
-        for (int k = tid; k < NR * NW; k += 1024) fl += __popc(masks[k]);
+        unsigned fl = 0, cfl = 0, cwd = 0;
+        for (int k = tid; k < NR * NW; k += 1024) {
+            const unsigned mk = masks[k];
+            fl += __popc(mk);
+            if (cut_on) {
+                // a word of the launch's cut: binned for the counters alone.  Its flags count as absorbed wave-samples of the four waves that
+                // would have met the word (the counters keep their meaning: flagged wave-samples that are not accumulated); its bits go.
+                const int w = k % NW;
+                if (w >= (int)q.tabmax[NW + NR + (w & 3)]) { cfl += __popc(mk); cwd += mk != 0u; masks[k] = 0u; }
+            }
+        }
         if (fl) atomicAdd(&q.stats[2], (unsigned long long)fl);
-        if (tid == 0) { atomicAdd(&q.stats[3], (unsigned long long)p.n_tab); unsigned v = 0; for (int r = 0; r < NR; ++r) v += any[r] != 0u; atomicAdd(&q.stats[4], (unsigned long long)v);
+        if (cwd) { atomicAdd(&skc[0], 4u * cwd); atomicAdd(&skc[1], 4u * cfl); }      // flushed with the tile's other absorbed words (step 4)
+        if (tid == 0) { atomicAdd(&q.stats[3], (unsigned long long)p.n_tab); unsigned v = 0; for (int r = 0; r < NR; ++r) v += (any[r] & (TWO ? 0xffffu : ~0u)) != 0u; atomicAdd(&q.stats[4], (unsigned long long)v);
                         if (CERT) { unsigned c = 0; for (int k = 0; k < NW; ++k) c += __popc(cmask[k]); atomicAdd(&q.stats[5], (unsigned long long)c); } }
     }
-    auto visit = [&](const int r) {                                // stage region r and run this wave's slice over it
+    auto visit = [&](const int r, const int ph) {                  // stage region r and run this wave's slice (TWO: its head word, ph 0, or its tail) over it
         const int f = r / (G * G);
         const int gy = (r / G) % G, gx = r % G;
         const int ox = gx * RC, oy = gy * RC;
@@ -641,16 +704,19 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         const unsigned* mw = masks + r * NW;
         const unsigned pass_base = lds_base - (unsigned)(oy * RS + ox) * 16u;      // taps are addressed with face coordinates
         unsigned* const sc = (ABS && q.stats) ? skc : nullptr;
+        // the words of this pass: the whole slice, or (TWO) its head word s / its tail words s + REG_S, ..
+        const unsigned long long wsel = TWO ? (ph ? ~1ull : 1ull) : ~0ull;
+        const int w0 = (TWO && ph) ? s + REG_S : s, w1 = (TWO && !ph) ? min(NW, s + 1) : NW;
         if (RUNS) {
             switch (f >> 1) {
-            case 0: region_pass_runs<RS, SUB, 0, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
-            case 1: region_pass_runs<RS, SUB, 1, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
-            default: region_pass_runs<RS, SUB, 2, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+            case 0: region_pass_runs<RS, SUB, 0, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, wsel, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+            case 1: region_pass_runs<RS, SUB, 1, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, wsel, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+            default: region_pass_runs<RS, SUB, 2, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, wsel, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
             }
         } else switch (f >> 1) {
-        case 0: region_pass<RS, SUB, 0, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
-        case 1: region_pass<RS, SUB, 1, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
-        default: region_pass<RS, SUB, 2, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+        case 0: region_pass<RS, SUB, 0, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, w0, w1, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+        case 1: region_pass<RS, SUB, 1, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, w0, w1, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+        default: region_pass<RS, SUB, 2, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, w0, w1, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
         }
         st_stage += stb - sta;
     };
@@ -660,18 +726,21 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         // of the level); any[] is final after binning, so the skip needs none.  (A 64-bit mask of the visited regions kept across
         // the passes, or a ballot search for the next one, spills VGPRs at the 64-VGPR budget of the quarter-face shape.)
         __syncthreads();                                           // binning done
-        for (int k = 0; k < NR; ++k) {
+        for (int kk = 0; kk < (TWO ? 2 * NR : NR); ++kk) {         // TWO: all regions for the head words, then all for the tail words (one
+            const int ph = TWO && kk >= NR, k = kk - (ph ? NR : 0);    // counter: a second loop variable costs a scalar register across the passes)
             const int r = OWN_FIRST ? mc_region_visit(k, face * (G * G), G * G) : k;
-            if (__builtin_amdgcn_readfirstlane((int)any[r]) == 0) continue;      // workgroup-uniform
+            const unsigned av = (unsigned)__builtin_amdgcn_readfirstlane((int)any[r]);      // workgroup-uniform
+            if ((TWO ? (av >> (8 * ph)) & 0xffu : av) == 0u) continue;
             __syncthreads();                                       // readers of the previous region done
-            visit(r);
+            visit(r, ph);
         }
     } else {
-        for (int k = 0; k < NR; ++k) {
+        for (int kk = 0; kk < (TWO ? 2 * NR : NR); ++kk) {
+            const int ph = TWO && kk >= NR, k = kk - (ph ? NR : 0);
             const int r = OWN_FIRST ? mc_region_visit(k, face * (G * G), G * G) : k;
             __syncthreads();                                       // binning done / readers of the previous region done
-            if (any[r] == 0u) continue;                            // workgroup-uniform
-            visit(r);
+            if ((TWO ? (any[r] >> (8 * ph)) & 0xffu : any[r]) == 0u) continue;      // workgroup-uniform
+            visit(r, ph);
         }
     }
 
@@ -1015,6 +1084,8 @@ static void launch_region_t(const RegArgs& q, unsigned grid, size_t lds, hipStre
 // pattern of the R, G, B of exactly the texels the region kernel stages for it (rx <= rcx, ry <= rcy: apron included).  Compared as
 // unsigned integers, as the lemma at absorb_threshold wants: a negative, -0, inf or NaN orders at or above +inf's pattern.
 // Block b < NR reduces region b; the blocks behind take 256 words each, one per thread.
+// Header 2g: out[NW + NR + 4 .. + NR): per region, the SMALLEST such bit pattern (k_mc_cut's m; a negative or -0 texel hides from it but
+// not from the largest pattern, which then switches the cut off).
 __global__ __launch_bounds__(256) void k_mc_prep(const float4* __restrict__ src, int n, int G, int RC, int NR,
                                                  const float4* __restrict__ tab, int n_tab, int NW, unsigned* __restrict__ out) {
     const int tid = threadIdx.x;
@@ -1026,23 +1097,68 @@ __global__ __launch_bounds__(256) void k_mc_prep(const float4* __restrict__ src,
         out[w] = m;
         return;
     }
-    __shared__ unsigned red;
-    if (tid == 0) red = 0u;
+    __shared__ unsigned red, redlo;
+    if (tid == 0) { red = 0u; redlo = 0xffffffffu; }
     __syncthreads();
     const int r = (int)blockIdx.x, nb = n + 2;
     const int f = r / (G * G), gy = (r / G) % G, gx = r % G;
     const int ox = gx * RC, oy = gy * RC;
     const int cols = min(RC, n + 1 - ox) + 1, rows = min(RC, n + 1 - oy) + 1;
     const float4* __restrict__ fsrc = src + ((size_t)f * nb + oy) * nb + ox;
-    unsigned m = 0u;
+    unsigned m = 0u, lo = 0xffffffffu;
     for (int k = tid; k < rows * cols; k += 256) {
         const int ry = k / cols, rx = k - ry * cols;
         const float4 v = fsrc[ry * nb + rx];
         m = max(m, max(__float_as_uint(v.x), max(__float_as_uint(v.y), __float_as_uint(v.z))));
+        lo = min(lo, min(__float_as_uint(v.x), min(__float_as_uint(v.y), __float_as_uint(v.z))));
     }
     atomicMax(&red, m);
+    atomicMin(&redlo, lo);
     __syncthreads();
-    if (tid == 0) out[NW + r] = red;
+    if (tid == 0) { out[NW + r] = red; out[NW + NR + 4 + r] = redlo; }
+}
+
+// ---- the launch's cut (header, 2g) ----
+// One wave behind k_mc_prep on the same stream: lanes 0 .. 3 add up the weights of their slice's head word in double, in index order;
+// lane 0 folds the regions' extrema and writes the first cut word of each slice to out[NW + NR .. + 4) (mc_launch_cut, k_mc_internal.h).
+__global__ __launch_bounds__(64) void k_mc_cut(const float4* __restrict__ tab, int n_tab, int NW, int NR, unsigned* __restrict__ out) {
+    __shared__ double H[4];
+    const int tid = threadIdx.x;
+    if (tid < 4) {
+        double h = 0.0;
+        if (NW > 4)
+            for (int i = 0; i < 32; ++i) h += (double)tab[(tid << 5) + i].w;
+        H[tid] = h;
+    }
+    __syncthreads();
+    if (tid != 0) return;
+    unsigned M = 0u, m = 0xffffffffu;
+    for (int r = 0; r < NR; ++r) { M = max(M, out[NW + r]); m = min(m, out[NW + NR + 4 + r]); }
+    int cut4[4];
+    mc_launch_cut(out, NW, H, m, M, cut4);
+    for (int s = 0; s < 4; ++s) out[NW + NR + s] = (unsigned)cut4[s];
+}
+
+// The same cut on the host, from the table's weights and the level's extrema (bit patterns): what k_mc_cut writes for them.  Needs no GPU.
+// cut4[s]: the first cut word of slice s (see mc_launch_cut).  Returns the number of words cut, or -1 for bad arguments.
+extern "C" int pbrk_mc_launch_cut(const float* weights, int n, unsigned min_bits, unsigned max_bits, int* cut4) {
+    if (!weights || !cut4 || n < 1 || n > 8192) return -1;
+    const int NW = (n + 31) / 32;
+    unsigned wbits[256];
+    for (int w = 0; w < NW; ++w) {
+        unsigned m = 0u;
+        for (int i = w << 5; i < (w << 5) + 32 && i < n; ++i) {
+            union { float f; unsigned u; } c;
+            c.f = weights[i];
+            m = c.u > m ? c.u : m;
+        }
+        wbits[w] = m;
+    }
+    double H[4] = {0.0, 0.0, 0.0, 0.0};
+    if (NW > 4)
+        for (int s = 0; s < 4; ++s)
+            for (int i = 0; i < 32; ++i) H[s] += (double)weights[(s << 5) + i];
+    return mc_launch_cut(wbits, NW, H, min_bits, max_bits, cut4);
 }
 
 // Scratch for those tables: a ring of slots in device memory, allocated once per device.  A slot is written by k_mc_prep and read
@@ -1097,6 +1213,26 @@ extern "C" void pbrk_mc_set_runs(int on) { g_mc_runs = on ? 1 : 0; }
 // The prologue of header 2f (k_mc_region LEAN; tests / A-B runs; 0: the prologue before it; the outputs are the same bit for bit either way)
 static int g_mc_lean = 1;
 extern "C" void pbrk_mc_set_prologue(int lean) { g_mc_lean = lean ? 1 : 0; }
+
+// The launch-level cut of header 2g (tests / A-B runs; the outputs are the same bit for bit either way)
+static int g_mc_launch_cut = 1;
+extern "C" void pbrk_mc_set_launch_cut(int on) { g_mc_launch_cut = on ? 1 : 0; }
+// The cut of the last region-kernel launch, for tests and probes: out6 = the first cut word of slices 0 .. 3, NW, words cut.  A launch
+// without a cut reports 0 words.  Waits for the device.
+static const unsigned* g_last_cut = nullptr;
+static int g_last_cut_nw = 0;
+extern "C" int pbrk_mc_launch_cut_stats(int* out6) {
+    if (!out6) return PBRK_E_ARG;
+    const int NW = g_last_cut_nw;
+    for (int s = 0; s < 4; ++s) out6[s] = s >= NW ? s : s + 4 * ((NW - s + 3) / 4);
+    out6[4] = NW; out6[5] = 0;
+    if (!g_last_cut) return PBRK_OK;
+    if (hipDeviceSynchronize() != hipSuccess) return PBRK_E_LAUNCH;
+    int c[4];
+    if (hipMemcpy(c, g_last_cut, 16, hipMemcpyDeviceToHost) != hipSuccess) return PBRK_E_LAUNCH;
+    for (int s = 0; s < 4; ++s) { out6[5] += (out6[s] - c[s]) / 4; out6[s] = c[s]; }
+    return PBRK_OK;
+}
 
 template <bool LEAN>
 static void launch_shape(int RS, const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
@@ -1174,15 +1310,24 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
     // a scratch slot (see prep_acquire) the launch takes the prologue that builds them itself: the same bytes.
     bool lean = g_mc_lean != 0;
     q.tabmax = nullptr;
+    q.cut = 0;
+    g_last_cut = nullptr; g_last_cut_nw = q.NW;
     if (lean && q.absorb) {
         std::lock_guard<std::mutex> hold(g_prep_lock);
         int slot = -1;
-        unsigned* scratch = q.NW + q.NR <= PREP_SLOT_WORDS ? prep_acquire(st, &slot) : nullptr;
+        unsigned* scratch = q.NW + 2 * q.NR + 4 <= PREP_SLOT_WORDS ? prep_acquire(st, &slot) : nullptr;
         if (!scratch) lean = false;
         else {
             int dev = 0; (void)hipGetDevice(&dev);
             q.tabmax = scratch;
             hipLaunchKernelGGL(k_mc_prep, dim3((unsigned)(q.NR + (q.NW + 255) / 256)), dim3(256), 0, st, a.src, a.n_src, q.G, q.RC, q.NR, a.tab, a.n_tab, q.NW, scratch);
+            // header 2g: the shapes that run their head words first drop the words k_mc_cut proves to be no-ops for the whole launch
+            const bool head_first = RS == 66 && (q.G == 1 ? MC_HEAD_FIRST_G1 != 0 : MC_HEAD_FIRST_SUB != 0);
+            if (head_first && g_mc_launch_cut && q.NW > 4) {
+                hipLaunchKernelGGL(k_mc_cut, dim3(1), dim3(64), 0, st, a.tab, a.n_tab, q.NW, q.NR, scratch);
+                q.cut = 1;
+                g_last_cut = scratch + q.NW + q.NR;
+            }
             launch_shape<true>(RS, q, grid, lds, st);
             if (hipEventRecord(g_prep[dev].ev[slot], st) == hipSuccess) g_prep[dev].used[slot] = true;
             return true;

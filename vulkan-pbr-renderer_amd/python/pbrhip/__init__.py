@@ -298,7 +298,10 @@ PROTOTYPES = {
     "pbrk_mc_region_flag_stats": (C.c_int, [C.POINTER(C.c_uint64)]), "pbrk_mc_region_window_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
     "pbrk_mc_region_skip_stats": (C.c_int, [C.POINTER(C.c_uint64)]), "pbrk_mc_set_absorb": (None, [C.c_int]),
     "pbrk_mc_set_runs": (None, [C.c_int]), "pbrk_mc_region_order": (C.c_int, [C.c_int, C.c_int, C.c_int]),
-    "pbrk_mc_set_prologue": (None, [C.c_int]), "pbrk_mc_region_phase_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
+    "pbrk_mc_set_prologue": (None, [C.c_int]), "pbrk_mc_set_launch_cut": (None, [C.c_int]),
+    "pbrk_mc_launch_cut": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.c_uint, C.c_uint, C.POINTER(C.c_int)]),
+    "pbrk_mc_launch_cut_stats": (C.c_int, [C.POINTER(C.c_int)]),
+    "pbrk_mc_region_phase_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
     "pbrk_lut_cells_build": (C.c_int, [VP, C.c_int, VP, VP]),
     "pbrk_equirect_to_cube": (C.c_int, [VP, C.c_int, C.c_int, VP, C.c_int, VP]),
     "pbrk_raster_scratch_bytes": (C.c_size_t, [U32, C.c_int, C.c_int]),
