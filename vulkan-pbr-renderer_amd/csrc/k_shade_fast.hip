@@ -32,7 +32,7 @@ __device__ __forceinline__ f3 pre_level_fetch(__amdgpu_buffer_rsrc_t rc, float f
     return cells_bilerp(bl4(rc, off), bl4(rc, off + 16), bl4(rc, off + 32), a, b);
 }
 
-template <bool kIBL, bool kShafts, bool kTab = false>
+template <bool kIBL, bool kShafts>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_shade_fast(const ShadeParams p) {
     __shared__ int lv_off[16];        // byte offset of level l inside the prefiltered cells twin
     if (threadIdx.x < 16) lv_off[threadIdx.x] = cells_level_off(p.pre_size, 0, min((int)threadIdx.x, p.pre_levels - 1)) * 16;
@@ -65,27 +65,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const float fcx = (float)px + 0.5f, fcy = (float)py + 0.5f;
     float xn, yn, noise_1, noise_2, noise_3;
     const float noise_offset = (1000 * 1.61803398875f) * p.frame_idx_mod_59;
-    if (kTab) {
-        // per-column / per-row constants from the host tables (k_shade.hip shade_tables: the same operations, correctly rounded):
-        // col[x] = { xn, .06711056 fcx, .06711056 (fcx + 90), .06711056 (fcx + 522) }, row[y] likewise with .00583715 and 20 / 55
-        __amdgpu_buffer_rsrc_t rcol = __builtin_amdgcn_make_buffer_rsrc((void*)p.col_tab, 0, p.width * 16, 0x00020000);
-        const float4 ct = bl4(rcol, px * 16);
-        typedef float v4ft __attribute__((ext_vector_type(4)));
-        const v4ft rt = ((const __attribute__((address_space(4))) v4ft*)p.row_tab)[__builtin_amdgcn_readfirstlane(py)];     // a wave is one row: scalar load
-        xn = ct.x; yn = rt.x;
-        noise_1 = __builtin_amdgcn_fractf(__builtin_amdgcn_fractf(52.9829189f * __builtin_amdgcn_fractf(ct.y + rt.y)) + noise_offset);
-        noise_2 = __builtin_amdgcn_fractf(__builtin_amdgcn_fractf(52.9829189f * __builtin_amdgcn_fractf(ct.z + rt.z)) + noise_offset);
-        noise_3 = __builtin_amdgcn_fractf(__builtin_amdgcn_fractf(52.9829189f * __builtin_amdgcn_fractf(ct.w + rt.w)) + noise_offset);
-    } else {
-        SharedRcp rw, rh;
-        rw.d = (float)p.width; rw.r = p.rcp_width; rh.d = (float)p.height; rh.r = p.rcp_height;
-        xn = fmaf(div_by(fcx, rw), 2.0f, -1.0f); yn = fmaf(div_by(fcy, rh), 2.0f, -1.0f);     // 2u is exact: (u*2) - 1
-        // :456-459 (exact; x - floor(x) == v_fract for the non-negative arguments here)
-        auto ignf = [](float x, float y) { return __builtin_amdgcn_fractf(52.9829189f * __builtin_amdgcn_fractf(0.06711056f * x + 0.00583715f * y)); };
-        noise_1 = __builtin_amdgcn_fractf(ignf(fcx, fcy) + noise_offset);
-        noise_2 = __builtin_amdgcn_fractf(ignf(fcx + 90.0f, fcy + 20.0f) + noise_offset);
-        noise_3 = __builtin_amdgcn_fractf(ignf(fcx + 522.0f, fcy + 55.0f) + noise_offset);
-    }
+    SharedRcp rw, rh;
+    rw.d = (float)p.width; rw.r = p.rcp_width; rh.d = (float)p.height; rh.r = p.rcp_height;
+    xn = fmaf(div_by(fcx, rw), 2.0f, -1.0f); yn = fmaf(div_by(fcy, rh), 2.0f, -1.0f);     // 2u is exact: (u*2) - 1
+    // :456-459 (exact; x - floor(x) == v_fract for the non-negative arguments here)
+    auto ignf = [](float x, float y) { return __builtin_amdgcn_fractf(52.9829189f * __builtin_amdgcn_fractf(0.06711056f * x + 0.00583715f * y)); };
+    noise_1 = __builtin_amdgcn_fractf(ignf(fcx, fcy) + noise_offset);
+    noise_2 = __builtin_amdgcn_fractf(ignf(fcx + 90.0f, fcy + 20.0f) + noise_offset);
+    noise_3 = __builtin_amdgcn_fractf(ignf(fcx + 522.0f, fcy + 55.0f) + noise_offset);
     float pw[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) pw[r] = ((p.wfc[r] * xn + p.wfc[4 + r] * yn) + p.wfc[8 + r] * depth) + p.wfc[12 + r];
@@ -236,18 +223,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 }
 
 int launch_shade_fast(const ShadeParams& p, bool ibl, bool shafts, hipStream_t stream) {
-    // kTab: measured SLOWER than recomputing (8K frame 564-576 vs 540-544 us, 1080p 24.8 vs 23.3 us: 24 fewer VALU instructions do not
-    // pay for one more vector-memory instruction per wave -- the kernel is bound by its memory instructions); opt-in
-    static int tab = -1;
-    if (tab < 0) { const char* e = getenv("PBR_SHADE_TABLES"); tab = e ? atoi(e) : 0; }
-    if (tab && p.col_tab && p.row_tab) {
-        dim3 grid((p.w + 63) / 64, (p.h + 3) / 4);
-        if (ibl && shafts) hipLaunchKernelGGL((k_shade_fast<true, true, true>), grid, dim3(256), 0, stream, p);
-        else if (ibl) hipLaunchKernelGGL((k_shade_fast<true, false, true>), grid, dim3(256), 0, stream, p);
-        else if (shafts) hipLaunchKernelGGL((k_shade_fast<false, true, true>), grid, dim3(256), 0, stream, p);
-        else hipLaunchKernelGGL((k_shade_fast<false, false, true>), grid, dim3(256), 0, stream, p);
-        return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
-    }
     dim3 grid((p.w + 63) / 64, (p.h + 3) / 4);
     if (ibl && shafts) hipLaunchKernelGGL((k_shade_fast<true, true>), grid, dim3(256), 0, stream, p);
     else if (ibl) hipLaunchKernelGGL((k_shade_fast<true, false>), grid, dim3(256), 0, stream, p);
