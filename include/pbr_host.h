@@ -140,6 +140,9 @@ typedef struct PBR_Globals {            /* RendererGlobalsBuffer, render.h:122-1
     float camera_pos[3];
     float frame_idx_mod_59;
     float lightgrid_scale;
+    /* != 0: the lighting pass draws the light-grid visualiser instead of the shaded frame (lighting_pass.glsl:463-491, the reference's G
+     * key: main.cpp:79, render.cpp:990) -- kernel K16 over the recorded rows, whatever the pipeline's shade flags; needs LIGHTGRID bound
+     * (PBR_MakeLightingPassLive).  PBR_FillGlobals writes 0; there is no entry point of its own: set the field after PBR_FillGlobals. */
     uint32_t visualize_lightgrid;
 } PBR_Globals;
 

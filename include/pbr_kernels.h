@@ -205,6 +205,21 @@ void pbrk_shade_set_fast(int on);                        /* 0: every mode throug
 /* LUT twin for K5: one 16-byte load per bilinear LUT fetch */
 int pbrk_lut_cells_build(const void* lut_half2, int size, void* cells_out, void* stream);
 
+/* ---- K16: the light-grid visualiser of the lighting pass (lighting_pass.glsl:463-491, Globals.visualize_lightgrid != 0): every pixel of
+ *      the rectangle, sky included, becomes a ray march through LIGHTGRID (up to 512 half-voxel steps, first trilinear sample with
+ *      alpha > 0.3, luminance remapped by its square root).  Reads nothing else of the lighting pass's inputs.  Contract:
+ *      csrc/gridview_core.h; bit-identical to a CPU evaluation of that header. ---- */
+typedef struct PbrkGridViewArgs {
+    int x0, x1, y0, y1;                 /* pixel rectangle to write */
+    int width, height;                  /* of the target; fs_uv = (pixel + 0.5) / extent */
+    const void* lightgrid;              /* half4 [n][n][n] */
+    int lightgrid_size;                 /* n, 1..1024 */
+    void* out;                          /* half4 or float4 [H][W] */
+    int out_format;                     /* PBRK_FMT_RGBA16F / PBRK_FMT_RGBA32F */
+    float globals[138];                 /* RendererGlobalsBuffer (552 bytes); read: world_space_from_clip, camera_pos, frame_idx_mod_59, lightgrid_scale */
+} PbrkGridViewArgs;
+int pbrk_lightgrid_view(const PbrkGridViewArgs* args, void* stream);
+
 /* ---- K8 / K9: post-process tail.  2-D sampler = linear clamp with coordinates snapped to 1/256
  *      texel (Vulkan subTexelPrecisionBits = 8), exact fp32 lerps. ---- */
 typedef struct PbrkTex2D { const void* data; int format, width, height; } PbrkTex2D;     /* device pointer, PBRK_FMT_* */
@@ -348,7 +363,8 @@ int pbrk_bc_decode(int format, const void* blocks, int width, int height, void* 
 /* ---- diagnostics: the device samplers of the widened passes evaluated at caller-supplied coordinates, so that tests can feed them
  *      NaN / inf / 1e30 / boundary values directly (a ray that has marched far away must never become an out-of-bounds read).
  *      which: 0 = LIGHTGRID (RGBA16F n^3, coords xyz), 1 = sampler2DShadow (R32F w x h, coords u, v, ref; result in out[0]),
- *      2 = the post-process 2-D sampler (RGBA16F w x h, coords u, v).  coords: device float[count][3]; out: device float[count][4]. */
+ *      2 = the post-process 2-D sampler (RGBA16F w x h, coords u, v), 3 = LIGHTGRID as K16 reads it (alpha and colour fetched
+ *      separately; the same bits as 0).  coords: device float[count][3]; out: device float[count][4]. */
 int pbrk_debug_sample(int which, const void* texture, int w, int h, int d, const void* coords, int count, void* out, void* stream);
 
 #ifdef __cplusplus

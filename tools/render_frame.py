@@ -5,7 +5,9 @@ With `raster` the G-buffer is not synthetic: the geometry pass (K13) rasterises 
 and neither are the live shader's other inputs: the sun depth pass (K12) draws the shadow map, the voxelise pass (K14) fills the light
 grid from the mesh on frame 0 (render.cpp:1022-1056) and the sweep (K7) spreads it.
 With `live` the lighting pass is the reference's complete live shader (shafts, sun shadows, voxel GI) inside the reference's
-frame loop: light-grid sweep -> lighting (reading last frame's bloom_downscale_rt) -> TAA -> bloom -> final, eight frames."""
+frame loop: light-grid sweep -> lighting (reading last frame's bloom_downscale_rt) -> TAA -> bloom -> final, eight frames.
+With --visualize-lightgrid (live or raster only: both bind a light grid) the lighting pass of every frame runs in the reference's
+light-grid visualiser mode (Globals.visualize_lightgrid = 1, its G key; kernel K16): the picture shows the voxelised scene itself."""
 import ctypes as C
 import os
 import struct
@@ -33,6 +35,9 @@ def write_png(path, rgb):
 
 
 def main():
+    visualize = "--visualize-lightgrid" in sys.argv
+    if visualize:
+        sys.argv.remove("--visualize-lightgrid")
     out = sys.argv[1]
     W, H = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (1280, 720)
     env = synth.synth_env(512, seed=0x5EED0001, workers=6)       # forked workers: before the HIP runtime is initialised
@@ -45,6 +50,8 @@ def main():
     L.PBR_GenBRDFIntegrationMap(maps.brdf_lut)
     live = len(sys.argv) > 4 and sys.argv[4] == "live"
     raster = len(sys.argv) > 4 and sys.argv[4] == "raster"
+    if visualize and not (live or raster):
+        sys.exit("--visualize-lightgrid needs a light grid: use it with `live` or `raster`")
     if live:
         gbd, grid, _, sun = synth.synth_gi_scene(W, H)
     elif raster:
@@ -93,6 +100,7 @@ def main():
             for k in range(16):
                 glob.old_clip_space_from_world[k] = glob.clip_space_from_world[k]
             L.PBR_RecordGeometryPass(gp, g, mesh, None, C.byref(glob), None, None, frame)
+        glob.visualize_lightgrid = 1 if visualize else 0
         L.PBR_RecordLightingPass(lp, g, C.byref(glob), 0, 0)
         L.PBR_RecordTaaResolve(pp, g, frame); L.PBR_RecordBloom(pp, g, frame); L.PBR_RecordFinalPostProcessBloom(pp, g, frame)
         L.GPU_GraphSubmit(g); L.GPU_GraphWait(g)

@@ -159,6 +159,10 @@ struct GPU_Graph {
     hipGraphExec_t exec = nullptr;
     bool replay_broken = false;                    // a capture failed on this graph: it stays on plain launches
     uint64_t replay_launches = 0, replay_updates = 0, replay_instantiations = 0;
+    // Which kernel each lighting op of the submission launches (5: K5, 16: K16 -- decided at execution time from the Globals), and the
+    // same for the submission `exec` was instantiated from.  hipGraphExecUpdate is not relied upon to notice a changed kernel function:
+    // when the two differ, the executable graph is destroyed and instantiated anew.
+    std::vector<uint8_t> launch_sig, exec_sig;
     // timing of the last waited submission
     std::vector<hipEvent_t> ev;
     std::vector<std::string> timed_names;
@@ -1891,6 +1895,30 @@ static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
         memset(&a, 0, sizeof a);
         a.width = (int)rp->desc.width; a.height = (int)rp->desc.height;
         a.x0 = 0; a.x1 = a.width; a.y0 = (int)op.row0; a.y1 = (int)op.row1;
+        // Globals first: visualize_lightgrid (word 137, main.cpp:79 / render.cpp:990) replaces the whole shading of every pixel with the
+        // light-grid ray march (lighting_pass.glsl:463-491) -- K16 over the same rows, none of K5's aprons / twins, whatever the flags
+        read_globals(named_slot(s, "GLOBALS")->buf, 0, a.globals, 552);
+        uint32_t visualize; memcpy(&visualize, &a.globals[137], 4);
+        if (visualize != 0) {
+            Slot* gs = named_slot(s, "LIGHTGRID");
+            TextureImpl* grid = gs ? gs->tex : nullptr;
+            GPU_REQUIRE_V(grid && grid->base.format == GPU_Format_RGBA16F && grid->base.layer_count == 1 && grid->base.depth >= 2 &&
+                          grid->base.width == grid->base.depth && grid->base.height == grid->base.depth && grid->base.depth <= 1024,
+                          "lighting pass: visualize_lightgrid is set, but \"LIGHTGRID\" is not bound to a cubic RGBA16F 3-D texture (render.cpp:678); nothing drawn");
+            PbrkGridViewArgs v;
+            v.x0 = 0; v.x1 = a.width; v.y0 = a.y0; v.y1 = a.y1; v.width = a.width; v.height = a.height;
+            v.lightgrid = grid->dev; v.lightgrid_size = (int)grid->base.width;
+            v.out = target->dev; v.out_format = target->base.format == GPU_Format_RGBA16F ? PBRK_FMT_RGBA16F : PBRK_FMT_RGBA32F;
+            memcpy(v.globals, a.globals, sizeof v.globals);
+            g->launch_sig.push_back(16);
+            timed(g, "K16.gridview", ev_used, [&] {
+                int rc = pbrk_lightgrid_view(&v, st);
+                if (rc != PBRK_OK) gpu_fail("K16 launch failed (%d)", rc);
+            });
+            target->bordered_valid = false;
+            return;
+        }
+        g->launch_sig.push_back(5);
         a.base_color = named_slot(s, "GBUFFER_BASE_COLOR")->tex->dev;
         a.normal = named_slot(s, "GBUFFER_NORMAL")->tex->dev;
         a.orm = named_slot(s, "GBUFFER_ORM")->tex->dev;
@@ -1943,7 +1971,6 @@ static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
         }
         a.out = target->dev;
         a.out_format = target->base.format == GPU_Format_RGBA16F ? PBRK_FMT_RGBA16F : PBRK_FMT_RGBA32F;
-        read_globals(named_slot(s, "GLOBALS")->buf, 0, a.globals, 552);
         timed(g, "K5.shade", ev_used, [&] {
             int rc = pbrk_shade(&a, st);
             if (rc != PBRK_OK) gpu_fail("K5 launch failed (%d)", rc);
@@ -2221,6 +2248,7 @@ GPU_API void GPU_GraphSubmit(GPU_Graph* g) {
     g->timed_names.clear(); g->timed_ms.clear();
     size_t ev_used = 0;
     g->sync_used = 0;
+    g->launch_sig.clear();
     g->cur = g->stream;
     // Submission order is execution order, as on the reference's single queue (vkQueueSubmit, gpu_vulkan.c:2481-2530): a graph
     // submitted while another one is still in flight (main.cpp:49-51, 91-99 keeps two) starts after everything enqueued so far on
@@ -2355,13 +2383,14 @@ GPU_API void GPU_GraphSubmit(GPU_Graph* g) {
     if (capture) {
         hipGraph_t cg = nullptr;
         bool ok = hipStreamEndCapture(g->stream, &cg) == hipSuccess && cg;
+        if (g->exec && g->exec_sig != g->launch_sig) { (void)hipGraphExecDestroy(g->exec); g->exec = nullptr; }   // another kernel behind a node: never "updated"
         if (ok && g->exec) {
             hipGraphNode_t bad = nullptr; hipGraphExecUpdateResult res;
             if (hipGraphExecUpdate(g->exec, cg, &bad, &res) == hipSuccess) ++g->replay_updates;
             else { (void)hipGetLastError(); (void)hipGraphExecDestroy(g->exec); g->exec = nullptr; }
         }
         if (ok && !g->exec) {
-            if (hipGraphInstantiate(&g->exec, cg, nullptr, nullptr, 0) == hipSuccess) ++g->replay_instantiations;
+            if (hipGraphInstantiate(&g->exec, cg, nullptr, nullptr, 0) == hipSuccess) { ++g->replay_instantiations; g->exec_sig = g->launch_sig; }
             else { (void)hipGetLastError(); g->exec = nullptr; ok = false; }
         }
         if (ok && hipGraphLaunch(g->exec, g->stream) == hipSuccess) ++g->replay_launches; else ok = false;

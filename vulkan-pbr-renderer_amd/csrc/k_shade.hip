@@ -133,22 +133,6 @@ __device__ __forceinline__ float acos_det(float x) {
     if (x > 0.5f) return 2.0f * asin_poly_det(sqrtf(0.5f * (1.0f - x)));
     return 1.5707963267948966f - asin_poly_det(x);
 }
-__device__ __forceinline__ void snap_split(float coord01, int extent, int& i0, int& i1, float& a) {
-    float f = coord01 * (float)extent - 0.5f;
-    f = floorf(f * 256.0f + 0.5f) * (1.0f / 256.0f);
-    float fl = floorf(f);
-    a = f - fl;
-    // clamp in the float domain first: a ray that has marched to 1e30 must not reach the float->int conversion (saturation +
-    // `i + 1` would be signed overflow, i.e. an arbitrary index); the clamped indices are the same as clamping the true index
-    int i = (int)fminf(fmaxf(fl, -1.0f), (float)extent);
-    i0 = min(max(i, 0), extent - 1); i1 = min(max(i + 1, 0), extent - 1);
-}
-__device__ __forceinline__ float lerp_x(float a, float b, float t) { return a + t * (b - a); }
-__device__ __forceinline__ float4 unpack_h4(uint2 v) {
-    __half2 lo = *reinterpret_cast<__half2*>(&v.x), hi = *reinterpret_cast<__half2*>(&v.y);
-    float2 a = __half22float2(lo), b = __half22float2(hi);
-    return make_float4(a.x, a.y, b.x, b.y);
-}
 // texture(sampler3D(LIGHTGRID, SAMPLER_LINEAR_CLAMP), p): trilinear, clamp, snapped coordinates
 __device__ __forceinline__ float4 grid_sample(const ShadeParams& p, float px, float py, float pz) {
     int i0, i1, j0, j1, k0, k1; float a, b, c;
@@ -511,10 +495,12 @@ __global__ void k_debug_sample_shade(int which, ShadeParams p, const float* __re
     else out[i] = make_float4(shadow_sample(p.sun_depth, p.sun_w, p.sun_h, a, b, c), 0.0f, 0.0f, 0.0f);
 }
 extern "C" __attribute__((visibility("hidden"))) int pbrk_debug_sample_post(const void* texture, int w, int h, const void* coords, int count, void* out, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int pbrk_debug_sample_gridview(const void* texture, int n, const void* coords, int count, void* out, void* stream);
 extern "C" int pbrk_debug_sample(int which, const void* texture, int w, int h, int d, const void* coords, int count, void* out, void* stream) {
-    if (!texture || !coords || !out || count < 1 || w < 1 || h < 1 || d < 1 || which < 0 || which > 2) return PBRK_E_ARG;
+    if (!texture || !coords || !out || count < 1 || w < 1 || h < 1 || d < 1 || which < 0 || which > 3) return PBRK_E_ARG;
     if (which == 2) return pbrk_debug_sample_post(texture, w, h, coords, count, out, stream);
-    if (which == 0 && !(w == h && h == d && w <= 1024)) return PBRK_E_ARG;
+    if ((which == 0 || which == 3) && !(w == h && h == d && w <= 1024)) return PBRK_E_ARG;
+    if (which == 3) return pbrk_debug_sample_gridview(texture, w, coords, count, out, stream);
     ShadeParams p;
     memset(&p, 0, sizeof p);
     p.grid = (const uint2*)texture; p.grid_n = w;

@@ -47,5 +47,24 @@ __device__ __forceinline__ int cells_level_off(int W, int first, int level) {
     return off;
 }
 
+// the pieces of the 3-D / 2-D snapped samplers that K5 (grid_sample, prev_level_sample) and K16 (k_gridview.hip, the channel-split
+// form of grid_sample) share
+__device__ __forceinline__ void snap_split(float coord01, int extent, int& i0, int& i1, float& a) {
+    float f = coord01 * (float)extent - 0.5f;
+    f = floorf(f * 256.0f + 0.5f) * (1.0f / 256.0f);
+    float fl = floorf(f);
+    a = f - fl;
+    // clamp in the float domain first: a ray that has marched to 1e30 must not reach the float->int conversion (saturation +
+    // `i + 1` would be signed overflow, i.e. an arbitrary index); the clamped indices are the same as clamping the true index
+    int i = (int)fminf(fmaxf(fl, -1.0f), (float)extent);
+    i0 = min(max(i, 0), extent - 1); i1 = min(max(i + 1, 0), extent - 1);
+}
+__device__ __forceinline__ float lerp_x(float a, float b, float t) { return a + t * (b - a); }
+__device__ __forceinline__ float4 unpack_h4(uint2 v) {
+    __half2 lo = *reinterpret_cast<__half2*>(&v.x), hi = *reinterpret_cast<__half2*>(&v.y);
+    float2 a = __half22float2(lo), b = __half22float2(hi);
+    return make_float4(a.x, a.y, b.x, b.y);
+}
+
 // k_shade_fast.hip
 int launch_shade_fast(const ShadeParams& p, bool ibl, bool shafts, hipStream_t stream);

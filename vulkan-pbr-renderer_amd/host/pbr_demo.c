@@ -2,7 +2,7 @@
  * pbr_demo.c -- headless C driver of the hot path through the GPU_* boundary (what main.cpp:35-51 +
  * HotreloadShaders + BuildRenderCommands do for this path, without window / mesh import / raster passes).
  *
- *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster]]]]
+ *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster [gridview]]]]]
  *
  * Loads a vertical-strip HDR cube (asset_import.cpp:17-27), runs the IBL precompute (render.cpp:505-619),
  * shades a flat synthetic G-buffer (a metallic floor under the sky), then runs three frames of the per-frame chain
@@ -12,7 +12,9 @@
  * frame is written as a binary PPM.  With `raster` as the ninth argument the three frames of the chain start with the geometry pass
  * (render.cpp:1076-1115) over a small built-in mesh (a checkered floor and a block), so the lighting pass shades a rasterised
  * G-buffer instead of the synthetic one, and the light grid's lit voxels are not a stand-in either: the sun depth pass and the
- * voxelise pass (render.cpp:995-1020, 1039-1056) draw that mesh into it; every other output is unchanged.
+ * voxelise pass (render.cpp:995-1020, 1039-1056) draw that mesh into it; every other output is unchanged.  With `gridview` as the
+ * tenth argument (after `raster`) one more frame is rendered with Globals.visualize_lightgrid set -- the reference's G key, kernel
+ * K16: the voxelised mesh itself -- and its checksum is printed as gridview_bits_sum; the other lines stay as they are.
  */
 #include "pbr_host.h"
 
@@ -203,6 +205,17 @@ int main(int argc, char** argv) {
         for (uint32_t i = 0; i < GPUX_GraphTimedOpCount(g); ++i)
             printf("time_ms %s %.6f\n", GPUX_GraphTimedOpName(g, i), GPUX_GraphTimedOpMs(g, i));
         printf("lightgrid_voxelized 1\nlightgrid_bits_sum %.9e\n", checksum_texture_mip(PBR_LightgridTexture(lg), 0, 0));
+        if (argc > 10 && strcmp(argv[10], "gridview") == 0) {               /* main.cpp:79: one more frame with visualize_lightgrid set (K16) */
+            PBR_LightingPass* vlp = PBR_MakeLightingPassLive(&gb, &maps, width, height, NULL, PBR_LightgridTexture(lg), NULL);
+            PBR_Globals vg = globals;
+            vg.visualize_lightgrid = 1;
+            PBR_RecordLightingPass(vlp, g, &vg, 0, 0);
+            GPU_GraphSubmit(g); GPU_GraphWait(g);
+            for (uint32_t i = 0; i < GPUX_GraphTimedOpCount(g); ++i)
+                printf("time_ms %s %.6f\n", GPUX_GraphTimedOpName(g, i), GPUX_GraphTimedOpMs(g, i));
+            printf("gridview_bits_sum %.9e\n", checksum_texture_mip(gb.lighting_result, 0, 0));
+            PBR_DestroyLightingPass(vlp);
+        }
         GPU_DestroyGraph(g);
         PBR_DestroyVoxelizePass(vp); PBR_DestroySunDepthPass(sun); PBR_DestroyLightgrid(lg);
     } else {

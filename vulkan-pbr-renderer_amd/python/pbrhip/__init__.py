@@ -121,6 +121,12 @@ class PbrkShadeArgs(C.Structure):
                 ("globals", C.c_float * 138)]
 
 
+class PbrkGridViewArgs(C.Structure):
+    _fields_ = [("x0", C.c_int), ("x1", C.c_int), ("y0", C.c_int), ("y1", C.c_int), ("width", C.c_int), ("height", C.c_int),
+                ("lightgrid", C.c_void_p), ("lightgrid_size", C.c_int), ("out", C.c_void_p), ("out_format", C.c_int),
+                ("globals", C.c_float * 138)]
+
+
 class GPU_TextureView(C.Structure):
     _fields_ = [("texture", C.POINTER(GPU_Texture)), ("mip_level", C.c_uint32)]
 
@@ -292,6 +298,7 @@ PROTOTYPES = {
     "pbrk_mc_filter": (C.c_int, [VP, VP, C.c_int, VP, C.c_int, C.c_float, C.c_float, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP]),
     "pbrk_cells_bytes": (C.c_size_t, [C.c_int]), "pbrk_cells_build": (C.c_int, [VP, C.c_int, VP, VP]),
     "pbrk_shade": (C.c_int, [C.POINTER(PbrkShadeArgs), VP]),
+    "pbrk_lightgrid_view": (C.c_int, [C.POINTER(PbrkGridViewArgs), VP]),
     "pbrk_mc_region_stats": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
     "pbrk_mc_region_flag_stats": (C.c_int, [C.POINTER(C.c_uint64)]), "pbrk_mc_region_window_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
     "pbrk_mc_region_skip_stats": (C.c_int, [C.POINTER(C.c_uint64)]), "pbrk_mc_set_absorb": (None, [C.c_int]),
