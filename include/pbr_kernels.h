@@ -138,7 +138,8 @@ int pbrk_mc_region_flag_stats(unsigned long long* out3);
 /* samples that binning proved to tap one region from every texel of their tile (they run the body without tests), summed over tiles */
 int pbrk_mc_region_window_stats(unsigned long long* out1);
 /* absorbed words of the region kernel (PBR_MC_STATS=1), since the last reset: {wave-words skipped, their wave-samples, of those the
- * samples run through the count-only body}.  A tile's region passes visit 4 x (its region flags) wave-samples in all. */
+ * samples run through the count-only body}.  A tile's region passes visit 4 x (its region flags) wave-samples in all: the flag, sample,
+ * region and proved-sample counters count per block of 256 texels, so a 32 x 32 tile enters them four times. */
 int pbrk_mc_region_skip_stats(unsigned long long* out3);
 /* skipping of mask words whose samples provably cannot change any lane's fp32 sums (default 1; tests and A-B runs): the outputs are
  * the same bit for bit either way */
@@ -161,8 +162,16 @@ void pbrk_mc_set_launch_cut(int on);
  * the bordered level.  cut4[s] = the first cut mask word of slice s (words s, s + 4, ..), or the slice's first index at or behind
  * ceil(n / 32) when none is cut.  Returns the number of words cut, -1 for bad arguments.  Needs no GPU. */
 int pbrk_mc_launch_cut(const float* weights, int n, unsigned min_bits, unsigned max_bits, int* cut4);
-/* the cut of the last region-kernel launch: {first cut word of slices 0 .. 3, mask words per region, words cut}; waits for the device */
+/* the same for a launch whose workgroups own S slices of the table (S = 1, 2 or 4; slice s: words s, s + S, ..): cut[s], s < S.
+ * S = 4 is pbrk_mc_launch_cut. */
+int pbrk_mc_launch_cut_slices(const float* weights, int n, int S, unsigned min_bits, unsigned max_bits, int* cut);
+/* the cut of the last region-kernel launch: {first cut word of slices 0 .. 3, mask words per region, words cut}; a launch of S < 4
+ * slices reports slice j % S in entry j and counts the words cut over its S slices; waits for the device */
 int pbrk_mc_launch_cut_stats(int* out6);
+/* the region kernel's tile on the quarter-face shape with at most 64 mask words: -1 (default) 32 x 32 texels x 1 slice where the
+ * level's output size reaches the measured threshold, 0 never, 1 wherever the shape allows it.  Every other level keeps 16 x 16 x 4.
+ * The two tiles add a texel's samples in different orders: close, not the same bytes.  Tests and A-B runs. */
+void pbrk_mc_set_tile32(int mode);
 
 /* ---- K5: deferred shade pass (shaders/lighting_pass.glsl:432-716, in-scope sub-blocks). */
 typedef struct PbrkShadeArgs {

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Time pbrk_mc_filter (K4b) on synthetic levels: picoseconds per sample evaluation and clocks per wave-sample per CU for a
-given (n_src, out_size, roughness).  Kernel choice follows the library (env PBR_MC_LDS / PBR_MC_REGION / PBR_MC_BINNED).
+given (n_src, out_size, roughness).  Kernel choice follows the library (env PBR_MC_LDS / PBR_MC_REGION / PBR_MC_BINNED); env
+PBR_MC_TILE32 = -1 | 0 | 1 goes to pbrk_mc_set_tile32 (the region kernel's 32 x 32 tile: by rule, never, wherever the shape allows).
    python3 tools/mc_probe.py n_src out_size [roughness] [rows] [face0 face1]"""
 import ctypes as C
 import os
@@ -22,6 +23,8 @@ def main():
     rows = int(sys.argv[4]) if len(sys.argv) > 4 else out
     f0, f1 = (int(sys.argv[5]), int(sys.argv[6])) if len(sys.argv) > 6 else (0, 6)
     L = pbrhip.init(0)
+    if os.environ.get("PBR_MC_TILE32"):
+        L.pbrk_mc_set_tile32(int(os.environ["PBR_MC_TILE32"]))
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(1)
     lvl = rng.random((6, n_src, n_src, 4), dtype=np.float32) + 0.1
@@ -66,6 +69,14 @@ def main():
             L.pbrk_mc_region_window_stats(wn)
             print(f"   binning: {fl[0] / fl[1]:.3f} regions flagged per sample, {fl[2] / tiles:.2f} regions visited per tile ({tiles} tile launches), "
                   f"{wn[0] / fl[1]:.3f} of the samples proved in-region for the whole tile (test-free body)", flush=True)
+        sk, c6, ph = (C.c_uint64 * 3)(), (C.c_int * 6)(), (C.c_uint64 * 5)()
+        if L.pbrk_mc_region_skip_stats(sk) == 0 and L.pbrk_mc_launch_cut_stats(c6) == 0 and fl[0]:
+            print(f"   absorbed: {sk[1] / (4 * fl[0]):.4f} of the flagged wave-samples ({sk[2]} through the count-only body); cut words {list(c6[:4])} of {c6[4]}, "
+                  f"{c6[5]} words cut", flush=True)
+        if L.pbrk_mc_region_phase_stats(ph) == 0 and ph[1] and L.pbrk_mc_region_stats(st, 0) == 0 and st[1]:
+            tiles = st[1] // 16                                # workgroups: sixteen waves each (the flag counters count blocks of 256 texels)
+            print("   clocks per tile (frames, clearing + binning, staging, region passes, reduction + store): "
+                  + ", ".join(f"{v / tiles:.0f}" for v in ph), flush=True)
         if L.pbrk_mc_region_stats(st, 1) == 0:
             print(f"   region kernel: {st[0]} of {st[1]} wave-slices recomputed with direct loads", flush=True)
     L.GPU_WaitUntilIdle(); L.GPU_Deinit()

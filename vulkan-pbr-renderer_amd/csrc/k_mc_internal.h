@@ -83,9 +83,11 @@ __host__ __device__ __forceinline__ int mc_region_visit(int k, int own, int GG) 
 // lemma at absorb_threshold each of its FMAs returns its sum unchanged, for every lane of every tile.  cut4[s]: the first cut
 // word of slice s, or the first index of the slice at or behind NW when none is cut.  Returns the number of words cut; 0 for tables
 // of at most 128 samples (one phase, no tail).
-__host__ __device__ inline int mc_launch_cut(const unsigned* wbits, int NW, const double* H, unsigned min_bits, unsigned max_bits, int* cut4) {
-    for (int s = 0; s < 4; ++s) cut4[s] = s >= NW ? s : s + 4 * ((NW - s + 3) / 4);
-    if (NW <= 4) return 0;
+// mc_launch_cut_s: the same for a launch whose workgroups own S slices (S = 1024 / TILE^2: 4 with 16 x 16 tiles, 1 with 32 x 32; header
+// 2h): slice s owns the words s, s + S, .., its head is word s, H has S entries and cut[s], s < S, is written.  No tail, no cut: NW <= S.
+__host__ __device__ inline int mc_launch_cut_s(const unsigned* wbits, int NW, int S, const double* H, unsigned min_bits, unsigned max_bits, int* cut) {
+    for (int s = 0; s < S; ++s) cut[s] = s >= NW ? s : s + S * ((NW - s + S - 1) / S);
+    if (NW <= S) return 0;
     if (min_bits < 0x00800000u || min_bits >= 0x7f800000u || max_bits >= 0x7f800000u) return 0;
     for (int w = 0; w < NW; ++w)
         if (wbits[w] >= 0x7f800000u) return 0;
@@ -93,20 +95,23 @@ __host__ __device__ inline int mc_launch_cut(const unsigned* wbits, int NW, cons
     cm.u = min_bits; cM.u = max_bits;
     const double m = (double)cm.f, M = (double)cM.f;
     int ncut = 0;
-    for (int s = 0; s < 4; ++s) {
+    for (int s = 0; s < S; ++s) {
         const double rhs = H[s] * m;
         if (!(rhs * 0x1p-25 >= 0x1p-100)) continue;                // NaN fails
-        int c = cut4[s];
-        for (int w = c - 4; w > s; w -= 4) {
+        int c = cut[s];
+        for (int w = c - S; w > s; w -= S) {
             cW.u = wbits[w];
             const double lhs = (double)cW.f * M * 0x1p25 * (1.0 + 0x1p-10);
             if (!(lhs <= rhs)) break;
             c = w;
         }
-        ncut += (cut4[s] - c) / 4;
-        cut4[s] = c;
+        ncut += (cut[s] - c) / S;
+        cut[s] = c;
     }
     return ncut;
+}
+__host__ __device__ inline int mc_launch_cut(const unsigned* wbits, int NW, const double* H, unsigned min_bits, unsigned max_bits, int* cut4) {
+    return mc_launch_cut_s(wbits, NW, 4, H, min_bits, max_bits, cut4);
 }
 
 // k_mc_region.hip: taps from LDS-staged regions of the source level.  Returns false when the kernel does not apply

@@ -62,6 +62,17 @@
 //      computation and are counted as absorbed (stats[2], [6], [7]: the counters keep their meaning), then their bits are cleared.
 //      Tables of at most 128 samples have no tail: one phase.  Per shape (MC_HEAD_FIRST_SUB / MC_HEAD_FIRST_G1; DESIGN.md 4, "K4b,
 //      round 8"); the 34^2 / 18^2 shapes keep their order and bytes.
+//   2h. (round 9, 32 x 32 tiles x 1 slice on the quarter-face shape) after 2b-2g a tile of C4 mip 1 keeps 512 of 1389 samples and
+//      accumulates about a fifth of the wave-samples flagged for it, but still pays a whole prologue -- binning, 3.6 stagings of 70 KB
+//      (most of them twice: head and tail phase), the barriers, the four-slice tree -- for 256 texels: about half of its clocks do not
+//      depend on the texels it holds.  TILE = 32 shares that prologue between 1024 texels: one slice (REG_S = 1024 / TILE^2 = 1), sixteen
+//      waves in a 4 x 4 grid of 8 x 8 quadrants, word 0 the head and every other word the tail, one accumulator per texel (so a lane's
+//      sums are those of the whole table: the per-word test of 2c passes two bits earlier, and the launch cut, mc_launch_cut_s with
+//      S = 1, weighs the heaviest head word H_0 against the whole table).  The wider tile spreads its frames further: more samples are
+//      flagged for two regions and fewer are proved (2b).  A texel's sum is added in one chain instead of four partial ones: close to
+//      the 16 x 16 x 4 bytes, not equal.  One ballot of region_pass_runs covers 64 words here, so the tile serves tables of at most
+//      2048 samples.  Which levels take it is mc_tile32's rule (level shape and output size only; pbrk_mc_set_tile32; MC_TILE32_SUB);
+//      every other level keeps 16 x 16 x 4 and its bytes.  DESIGN.md 4, "K4b, round 9"; profiles/r09_tile32.md.
 // Each (texel, sample) pair is accumulated exactly once, in an order (66^2 shapes: head phase then tail phase; in each, own face's
 // regions, then the other regions in index order; else regions in index order; sample index inside a region) that depends on the
 // level's shape and the texel's face only, not on the tile: a row-sharded dispatch equals a full one bit for bit.
@@ -82,7 +93,7 @@ typedef const __attribute__((address_space(3))) v4f* lds_v4f_p;
 typedef const __attribute__((address_space(4))) unsigned* cu32_t;
 
 // A 1024-thread workgroup owns a TILE x TILE block of output texels and 1024 / TILE^2 slices of the sample table:
-//   TILE 16 (the only instantiation): 256 texels x 4 slices (waves 4s .. 4s+3 own slice s).
+//   TILE 16: 256 texels x 4 slices (waves 4s .. 4s+3 own slice s);  TILE 32 (header 2h): 1024 texels x 1 slice.
 // The smaller tile halves the frame spread delta the region flags are built from (fewer samples flagged for two regions) and
 // pays four times the binning / staging per texel: it wins where regions are small next to that spread (n_src <= 32).
 #define REG_MAX_S 16
@@ -93,6 +104,15 @@ typedef const __attribute__((address_space(4))) unsigned* cu32_t;
 #endif
 #ifndef MC_HEAD_FIRST_G1
 #define MC_HEAD_FIRST_G1 1
+#endif
+
+// Header 2h: 32 x 32 tiles x 1 slice on the quarter-face shape where mc_tile32's rule holds.  0 keeps 16 x 16 x 4 and the parent's bytes
+// (pbrk_mc_set_tile32(1) still selects the tile).
+#ifndef MC_TILE32_SUB
+#define MC_TILE32_SUB 1
+#endif
+#ifndef MC_TILE32_MIN_SIZE
+#define MC_TILE32_MIN_SIZE 1024
 #endif
 
 struct RegArgs {
@@ -109,7 +129,7 @@ struct RegArgs {
     int absorb;                 // skip mask words whose samples are absorbed by every lane's sums (pbrk_mc_set_absorb; bit-identical)
     unsigned long long* stats;  // optional: [0] += healed wave-slices, [1] += all wave-slices, [2] += (region, sample) flags, [3] += samples per tile, [4] += regions visited,
                                 // [5] += proved samples (SUB), [6] += absorbed wave-words, [7] += their wave-samples, [8] += of those run through the
-                                // count-only body (a tile's region passes run 4 x [2] wave-samples in all); PBR_MC_PHASE_STAMPS builds: [9..13] += clocks of
+                                // count-only body (a tile's region passes run 4 x [2] wave-samples in all: [2] .. [5] count per block of 256 texels, a 32 x 32 tile four times); PBR_MC_PHASE_STAMPS builds: [9..13] += clocks of
                                 // a workgroup's first lane in frames, clearing + binning, staging, region passes, reduction + store
 };
 
@@ -360,7 +380,8 @@ __device__ __forceinline__ void region_pass(unsigned lds_base, const unsigned* _
 
 // region_pass with less scalar work per word and per sample (round 5, 66^2 shapes; RUNS in k_mc_region).  Same words, samples,
 // bodies, absorb decisions and FMA order; cnt counts per LANE (every lane of a complete wave ends at expect[s]):
-//   * only the non-empty words of the slice are visited: one LDS read per lane (lane k: word s + REG_S k; NW <= 256) and a ballot,
+//   * only the non-empty words of the slice are visited: one LDS read per lane (lane k: word s + REG_S k; one ballot covers 64 REG_S
+//     words -- NW <= 256 with four slices, NW <= 64 with one: launch_mc_region keeps longer tables off the one-slice tile) and a ballot,
 //     masked by wsel (bit k: word s + REG_S k belongs to this pass -- all, the head word alone, or the tail words: header 2g);
 //   * CERT: the proved samples below the next tested one run as a run of certain_sample (no per-sample proved-bit test, no exec
 //     join), then the tested one, in index order;
@@ -425,15 +446,15 @@ __device__ __forceinline__ void region_pass_runs(unsigned lds_base, const unsign
 // moves mu, mv by less than 5e-7 relative (rl enters three times, the root once: 4 x 2^-23 and their roundings), inside the 1.0001
 // they carry, and uc, vc by less than 2^-22 (|sc / ma| + 1) half_n texel, under 1e-3 texel up to n = 1024, inside the 0.05: the flags
 // stay a superset of what any texel of the tile reaches, and "certain" is claimed under the same inequalities.
-// TWO (header, 2g): any[r] holds two flags, byte 0 for the head words (0 .. 3) and byte 1 for the tail words.  lim: the first sample
-// index this thread does not bin -- 32 x the cut word of its slice (a thread's samples i = tid + 1024 k all fall into slice
-// (tid >> 5) & 3), n_tab without a cut.  keep_cut (counters only): the samples behind lim still run and set their mask bits, but no
+// TWO (header, 2g): any[r] holds two flags, byte 0 for the head words (0 .. S - 1: the samples below head_end = 32 S, S the workgroup's
+// slices) and byte 1 for the tail words.  lim: the first sample index this thread does not bin -- 32 x the cut word of its slice (a
+// thread's samples i = tid + 1024 k all fall into slice (tid >> 5) % S), n_tab without a cut.  keep_cut (counters only): the samples behind lim still run and set their mask bits, but no
 // region flag; the caller counts and clears those bits.
 template <bool LEAN, bool G1, bool TWO = false>
 __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsigned* dmax, int NR, int NW, int G, int RC, int n,
                                            f3 R, f3 T, f3 B, f3 Rc, f3 Tc, f3 Bc, ctab_t tab, int n_tab, int tid,
                                            unsigned* cmask = nullptr, unsigned* wmax = nullptr, int ntail = 0,
-                                           int lim = 0x7fffffff, bool keep_cut = false) {
+                                           int lim = 0x7fffffff, bool keep_cut = false, int head_end = 128) {
     const float nf = (float)n;
     const float half_n = 0.5f * nf;
     const float off = 0.5f * nf + 0.5f;
@@ -453,7 +474,7 @@ __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsig
     for (int i = tid; i < i_end; i += 1024) {
         const v4f e = tab[i];
         // TWO: the byte of any[r] this sample flags -- 0 head, 1 tail, 2 (never read) a cut sample run for the counters
-        const int ab = TWO ? (i >= lim ? 2 : (i >= 128 ? 1 : 0)) : 0;
+        const int ab = TWO ? (i >= lim ? 2 : (i >= head_end ? 1 : 0)) : 0;
         const float Lx = fmaf(e.x, Bc.x, fmaf(e.y, Tc.x, e.z * Rc.x));
         const float Ly = fmaf(e.x, Bc.y, fmaf(e.y, Tc.y, e.z * Rc.y));
         const float Lz = fmaf(e.x, Bc.z, fmaf(e.y, Tc.z, e.z * Rc.z));
@@ -568,9 +589,11 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     }
     // a wave covers an 8 x 8 quadrant of the tile (not 16 x 4): the smaller its extent, the fewer samples its lanes spread over
     // two regions (PBR_MC_WAVE_SHAPE experiment: see DESIGN.md)
+    constexpr int QW = TILE / 8, QSH = TILE == 32 ? 2 : 1;               // quadrants per tile edge (a power of two) and its log2: 2 x 2 (TILE 16), 4 x 4 (TILE 32)
+    static_assert(QW == 1 << QSH, "TILE is 16 or 32");
     const int q8 = t >> 6, l8 = t & 63;
-    const int x = tx * TILE + (q8 & 1) * 8 + (l8 & 7);
-    const int y = p.y0 + ty * TILE + (q8 >> 1) * 8 + (l8 >> 3);
+    const int x = tx * TILE + (q8 & (QW - 1)) * 8 + (l8 & 7);
+    const int y = p.y0 + ty * TILE + (q8 >> QSH) * 8 + (l8 >> 3);
     const int xc = min(x, p.size - 1), yc = min(y, p.y0 + p.rows - 1);
 
     const f3 R = face_texel_dir(face, xc, yc, p.size);
@@ -591,11 +614,12 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     // ---- 1. binning ----
     if (ABS && tid < 4) skc[tid] = 0u;                                   // ordered by the barrier behind region_bin's clearing
     [[maybe_unused]] const unsigned long long st1 = STAMP();
-    // the first cut word of this thread's slice (a vector load of one of four words behind the maxima)
-    const int lim = cut_on ? (int)q.tabmax[NW + NR + ((tid >> 5) & 3)] << 5 : 0x7fffffff;
+    // the first cut word of this thread's slice (a vector load of one of the REG_S words behind the maxima): samples tid + 1024 k lie
+    // in word (tid >> 5) + 32 k, that is in slice (tid >> 5) % REG_S
+    const int lim = cut_on ? (int)q.tabmax[NW + NR + ((tid >> 5) % REG_S)] << 5 : 0x7fffffff;
     region_bin<LEAN, !SUB, TWO>(masks, any, dmax, NR, NW, G, RC, n, R, T, B, Rc, Tc, Bc, tab, p.n_tab, tid, (CERT || ABS) ? cmask : nullptr,
                                 (absorb_on && !LEAN) ? wmax : nullptr, (absorb_on && !LEAN) ? 2 * NW + NR : ((CERT || ABS) ? NW : 0),
-                                lim, cut_on && q.stats != nullptr);
+                                lim, cut_on && q.stats != nullptr, 32 * REG_S);
     [[maybe_unused]] unsigned long long st_stage = 0ull;
 #ifdef PBR_MC_PHASE_STAMPS
     __syncthreads();                                               // the wait for the slowest thread's binning is charged to binning
@@ -621,16 +645,19 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
             const unsigned mk = masks[k];
             fl += __popc(mk);
             if (cut_on) {
-                // a word of the launch's cut: binned for the counters alone.  Its flags count as absorbed wave-samples of the four waves that
-                // would have met the word (the counters keep their meaning: flagged wave-samples that are not accumulated); its bits go.
+                // a word of the launch's cut: binned for the counters alone.  Its flags count as absorbed wave-samples of the waves of its
+                // slice (16 / REG_S: four, or all sixteen with one slice) that would have met the word (the counters keep their meaning: flagged wave-samples that are not accumulated); its bits go.
                 const int w = k % NW;
-                if (w >= (int)q.tabmax[NW + NR + (w & 3)]) { cfl += __popc(mk); cwd += mk != 0u; masks[k] = 0u; }
+                if (w >= (int)q.tabmax[NW + NR + (w % REG_S)]) { cfl += __popc(mk); cwd += mk != 0u; masks[k] = 0u; }
             }
         }
-        if (fl) atomicAdd(&q.stats[2], (unsigned long long)fl);
-        if (cwd) { atomicAdd(&skc[0], 4u * cwd); atomicAdd(&skc[1], 4u * cfl); }      // flushed with the tile's other absorbed words (step 4)
-        if (tid == 0) { atomicAdd(&q.stats[3], (unsigned long long)p.n_tab); unsigned v = 0; for (int r = 0; r < NR; ++r) v += (any[r] & (TWO ? 0xffffu : ~0u)) != 0u; atomicAdd(&q.stats[4], (unsigned long long)v);
-                        if (CERT) { unsigned c = 0; for (int k = 0; k < NW; ++k) c += __popc(cmask[k]); atomicAdd(&q.stats[5], (unsigned long long)c); } }
+        // [2] .. [5] are counted per block of 256 texels (four waves): a 32 x 32 tile adds its flags, samples, regions and proved samples
+        // four times, so "the passes visit 4 x [2] wave-samples" and every per-sample / per-tile ratio of these counters hold for both tiles
+        constexpr unsigned BLK = REG_TX / 256;
+        if (fl) atomicAdd(&q.stats[2], (unsigned long long)(fl * BLK));
+        if (cwd) { atomicAdd(&skc[0], (16u / REG_S) * cwd); atomicAdd(&skc[1], (16u / REG_S) * cfl); }      // flushed with the tile's other absorbed words (step 4)
+        if (tid == 0) { atomicAdd(&q.stats[3], (unsigned long long)p.n_tab * BLK); unsigned v = 0; for (int r = 0; r < NR; ++r) v += (any[r] & (TWO ? 0xffffu : ~0u)) != 0u; atomicAdd(&q.stats[4], (unsigned long long)(v * BLK));
+                        if (CERT) { unsigned c = 0; for (int k = 0; k < NW; ++k) c += __popc(cmask[k]); atomicAdd(&q.stats[5], (unsigned long long)(c * BLK)); } }
     }
     auto visit = [&](const int r, const int ph) {                  // stage region r and run this wave's slice (TWO: its head word, ph 0, or its tail) over it
         const int f = r / (G * G);
@@ -770,7 +797,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         atomicAdd(&q.stats[1], 1ull);
     }
 
-    // ---- 4. combine the slices (fixed tree) and store ----
+    // ---- 4. combine the slices (fixed tree; one slice: nothing to combine, red[] only hands the sums to the store) and store ----
     __syncthreads();                                               // everybody is done with the staged region
     if (absorb_on && q.stats && tid < 3 && skc[tid]) atomicAdd(&q.stats[6 + tid], (unsigned long long)skc[tid]);
     float* red = (float*)smem_r;
@@ -793,8 +820,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     int tid_o = tid;
     asm volatile("" : "+v"(tid_o));
     const int t_o = tid_o % REG_TX, q8_o = t_o >> 6, l8_o = t_o & 63;
-    const int x_o = tx * TILE + (q8_o & 1) * 8 + (l8_o & 7);
-    const int y_o = p.y0 + ty * TILE + (q8_o >> 1) * 8 + (l8_o >> 3);
+    const int x_o = tx * TILE + (q8_o & (QW - 1)) * 8 + (l8_o & 7);
+    const int y_o = p.y0 + ty * TILE + (q8_o >> QSH) * 8 + (l8_o >> 3);
     if (x_o < p.size && y_o < p.y0 + p.rows && s == 0) {
         float4 o;
         o.x = red[t_o * 3 + 0] / p.divisor; o.y = red[t_o * 3 + 1] / p.divisor; o.z = red[t_o * 3 + 2] / p.divisor; o.w = p.alpha;
@@ -888,14 +915,15 @@ __global__ __launch_bounds__(256) void k_mc_prep(const float4* __restrict__ src,
 }
 
 // ---- the launch's cut (header, 2g) ----
-// One wave behind k_mc_prep on the same stream: lanes 0 .. 3 add up the weights of their slice's head word in double, in index order;
-// lane 0 folds the regions' extrema and writes the first cut word of each slice to out[NW + NR .. + 4) (mc_launch_cut, k_mc_internal.h).
-__global__ __launch_bounds__(64) void k_mc_cut(const float4* __restrict__ tab, int n_tab, int NW, int NR, unsigned* __restrict__ out) {
+// One wave behind k_mc_prep on the same stream: lanes 0 .. S - 1 add up the weights of their slice's head word in double, in index order;
+// lane 0 folds the regions' extrema and writes the first cut word of each slice to out[NW + NR .. + 4) (mc_launch_cut_s, k_mc_internal.h).
+// S (1, 2 or 4) is the slice count of the region kernel behind it; all four slots are written, slot j with the cut of slice j % S.
+__global__ __launch_bounds__(64) void k_mc_cut(const float4* __restrict__ tab, int n_tab, int NW, int NR, int S, unsigned* __restrict__ out) {
     __shared__ double H[4];
     const int tid = threadIdx.x;
     if (tid < 4) {
         double h = 0.0;
-        if (NW > 4)
+        if (tid < S && NW > S)
             for (int i = 0; i < 32; ++i) h += (double)tab[(tid << 5) + i].w;
         H[tid] = h;
     }
@@ -904,14 +932,18 @@ __global__ __launch_bounds__(64) void k_mc_cut(const float4* __restrict__ tab, i
     unsigned M = 0u, m = 0xffffffffu;
     for (int r = 0; r < NR; ++r) { M = max(M, out[NW + r]); m = min(m, out[NW + NR + 4 + r]); }
     int cut4[4];
-    mc_launch_cut(out, NW, H, m, M, cut4);
-    for (int s = 0; s < 4; ++s) out[NW + NR + s] = (unsigned)cut4[s];
+    mc_launch_cut_s(out, NW, S, H, m, M, cut4);
+    for (int s = 0; s < 4; ++s) out[NW + NR + s] = (unsigned)cut4[s % S];
 }
 
 // The same cut on the host, from the table's weights and the level's extrema (bit patterns): what k_mc_cut writes for them.  Needs no GPU.
 // cut4[s]: the first cut word of slice s (see mc_launch_cut).  Returns the number of words cut, or -1 for bad arguments.
 extern "C" int pbrk_mc_launch_cut(const float* weights, int n, unsigned min_bits, unsigned max_bits, int* cut4) {
-    if (!weights || !cut4 || n < 1 || n > 8192) return -1;
+    return pbrk_mc_launch_cut_slices(weights, n, 4, min_bits, max_bits, cut4);
+}
+// The same for a launch of S slices per workgroup (S = 1, 2 or 4; mc_launch_cut_s): cut[s], s < S.
+extern "C" int pbrk_mc_launch_cut_slices(const float* weights, int n, int S, unsigned min_bits, unsigned max_bits, int* cut4) {
+    if (!weights || !cut4 || n < 1 || n > 8192 || (S != 1 && S != 2 && S != 4)) return -1;
     const int NW = (n + 31) / 32;
     unsigned wbits[256];
     for (int w = 0; w < NW; ++w) {
@@ -924,10 +956,10 @@ extern "C" int pbrk_mc_launch_cut(const float* weights, int n, unsigned min_bits
         wbits[w] = m;
     }
     double H[4] = {0.0, 0.0, 0.0, 0.0};
-    if (NW > 4)
-        for (int s = 0; s < 4; ++s)
+    if (NW > S)
+        for (int s = 0; s < S; ++s)
             for (int i = 0; i < 32; ++i) H[s] += (double)weights[(s << 5) + i];
-    return mc_launch_cut(wbits, NW, H, min_bits, max_bits, cut4);
+    return mc_launch_cut_s(wbits, NW, S, H, min_bits, max_bits, cut4);
 }
 
 // Scratch for those tables: a ring of slots in device memory, allocated once per device.  A slot is written by k_mc_prep and read
@@ -979,29 +1011,45 @@ extern "C" void pbrk_mc_set_prologue(int lean) { g_mc_lean = lean ? 1 : 0; }
 // The launch-level cut of header 2g (tests / A-B runs; the outputs are the same bit for bit either way)
 static int g_mc_launch_cut = 1;
 extern "C" void pbrk_mc_set_launch_cut(int on) { g_mc_launch_cut = on ? 1 : 0; }
+// The 32 x 32 tile of header 2h (tests / A-B runs): -1 the rule of mc_tile32 (default), 0 never, 1 wherever the shape allows it
+// (quarter faces, NW <= 64) whatever the output size.  The tile changes the order of a texel's sum: not the same bytes as 16 x 16 x 4.
+static int g_mc_tile32 = -1;
+extern "C" void pbrk_mc_set_tile32(int mode) { g_mc_tile32 = mode < 0 ? -1 : (mode ? 1 : 0); }
 // The cut of the last region-kernel launch, for tests and probes: out6 = the first cut word of slices 0 .. 3, NW, words cut.  A launch
-// without a cut reports 0 words.  Waits for the device.
+// without a cut reports 0 words.  A launch of S < 4 slices reports slice j % S in entry j (one slice: its first cut word four times);
+// the words cut are counted over the launch's S slices.  Waits for the device.
 static const unsigned* g_last_cut = nullptr;
-static int g_last_cut_nw = 0;
+static int g_last_cut_nw = 0, g_last_cut_s = 4;
 extern "C" int pbrk_mc_launch_cut_stats(int* out6) {
     if (!out6) return PBRK_E_ARG;
-    const int NW = g_last_cut_nw;
-    for (int s = 0; s < 4; ++s) out6[s] = s >= NW ? s : s + 4 * ((NW - s + 3) / 4);
+    const int NW = g_last_cut_nw, S = g_last_cut_s;
+    for (int j = 0; j < 4; ++j) { const int s = j % S; out6[j] = s >= NW ? s : s + S * ((NW - s + S - 1) / S); }
     out6[4] = NW; out6[5] = 0;
     if (!g_last_cut) return PBRK_OK;
     if (hipDeviceSynchronize() != hipSuccess) return PBRK_E_LAUNCH;
     int c[4];
     if (hipMemcpy(c, g_last_cut, 16, hipMemcpyDeviceToHost) != hipSuccess) return PBRK_E_LAUNCH;
-    for (int s = 0; s < 4; ++s) { out6[5] += (out6[s] - c[s]) / 4; out6[s] = c[s]; }
+    for (int s = 0; s < 4; ++s) { if (s < S) out6[5] += (out6[s] - c[s]) / S; out6[s] = c[s]; }
     return PBRK_OK;
 }
 
 template <bool LEAN>
-static void launch_shape(int RS, const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
-    if (RS == 18) launch_region_t<18, false, 16, false, LEAN>(q, grid, lds, st);
+static void launch_shape(int RS, int tile, const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
+    if (tile == 32) { if (g_mc_runs) launch_region_t<66, true, 32, true, LEAN>(q, grid, lds, st); else launch_region_t<66, true, 32, false, LEAN>(q, grid, lds, st); }
+    else if (RS == 18) launch_region_t<18, false, 16, false, LEAN>(q, grid, lds, st);
     else if (RS == 34) launch_region_t<34, false, 16, false, LEAN>(q, grid, lds, st);
     else if (q.G == 1) { if (g_mc_runs) launch_region_t<66, false, 16, true, LEAN>(q, grid, lds, st); else launch_region_t<66, false, 16, false, LEAN>(q, grid, lds, st); }
     else { if (g_mc_runs) launch_region_t<66, true, 16, true, LEAN>(q, grid, lds, st); else launch_region_t<66, true, 16, false, LEAN>(q, grid, lds, st); }
+}
+
+// Which tile serves a level (header 2h): a function of the level alone -- n_src, n_tab, the output size -- never of the dispatch's faces
+// or rows, so a row shard equals the full dispatch bit for bit.  32 x 32 x 1 needs the quarter-face shape (its body is the shortest and
+// its prologue the largest share) and NW <= 64 (one ballot of region_pass_runs); the rule adds size >= MC_TILE32_MIN_SIZE: below it
+// the level has too few 32 x 32 tiles to fill the chip (profiles/r09_tile32.md).
+static bool mc_tile32(int n_src, int n_tab, int size) {
+    if (n_src <= 64 || (n_tab + 31) / 32 > 64) return false;
+    const int mode = g_mc_tile32 < 0 ? (MC_TILE32_SUB ? -1 : 0) : g_mc_tile32;
+    return mode > 0 || (mode < 0 && size >= MC_TILE32_MIN_SIZE);
 }
 
 bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
@@ -1025,17 +1073,18 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
     const size_t lds_fixed = (size_t)RS * RS * 16 + (4 + (size_t)q.NR * q.NW + q.NR + 1 + q.NW) * 4;
     size_t lds = lds_fixed + (q.absorb ? (size_t)(q.NW + q.NR) * 4 : 0);
     if (lds > 80 * 1024) { q.absorb = 0; lds = lds_fixed; }
-    if (lds < (size_t)1024 * 3 * 4) lds = (size_t)1024 * 3 * 4;      // the slices' partial sums (REG_S * REG_TX = 1024 texel-slices)
+    if (lds < (size_t)1024 * 3 * 4) lds = (size_t)1024 * 3 * 4;      // the slices' partial sums (REG_S * REG_TX = 1024 texel-slices, whatever the tile)
     if (lds > 80 * 1024) return false;                             // two workgroups per CU or not at all
     if (stats_on < 0) {
         const char* e = getenv("PBR_MC_STATS"); stats_on = e ? atoi(e) : 0;
         if (stats_on) { if (hipMalloc(&g_reg_stats, REG_STATS_BYTES) != hipSuccess) g_reg_stats = nullptr; else (void)hipMemset(g_reg_stats, 0, REG_STATS_BYTES); }
     }
     q.stats = g_reg_stats;
-    // Tile size: 16 x 16 output texels x 4 slices of the sample table everywhere.  Measured and dropped: 8 x 8 tiles x 16
-    // slices (halve the frame spread, pay four times the per-tile work: C4 mip 2 44.0 -> 53.5 ms), 32 x 16 and 32 x 32 tiles (no gain
-    // on the big levels, losses on the small ones).
-    const int tile = 16, nslices = 4;
+    // Tile size: 16 x 16 output texels x 4 slices of the sample table, but for the quarter-face level with a short table and a big
+    // output (mc_tile32: header 2h), which takes 32 x 32 texels x 1 slice.  Measured and dropped: 8 x 8 tiles x 16
+    // slices (halve the frame spread, pay four times the per-tile work: C4 mip 2 44.0 -> 53.5 ms), 32 x 16 tiles, and 32 x 32 tiles on
+    // the whole-face and the small shapes (no gain on the big levels, losses on the small ones).
+    const int tile = mc_tile32(a.n_src, a.n_tab, a.size) ? 32 : 16, nslices = 1024 / (tile * tile);
     for (int s = 0; s < REG_MAX_S; ++s) q.expect[s] = 0;
     for (int w = 0; w < q.NW; ++w) { int c = a.n_tab - w * 32; q.expect[w % nslices] += c > 32 ? 32 : c; }
     q.a.tiles_x = (a.size + tile - 1) / tile;
@@ -1056,7 +1105,7 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
     bool lean = g_mc_lean != 0;
     q.tabmax = nullptr;
     q.cut = 0;
-    g_last_cut = nullptr; g_last_cut_nw = q.NW;
+    g_last_cut = nullptr; g_last_cut_nw = q.NW; g_last_cut_s = nslices;
     if (lean && q.absorb) {
         std::lock_guard<std::mutex> hold(g_prep_lock);
         int slot = -1;
@@ -1068,17 +1117,17 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
             hipLaunchKernelGGL(k_mc_prep, dim3((unsigned)(q.NR + (q.NW + 255) / 256)), dim3(256), 0, st, a.src, a.n_src, q.G, q.RC, q.NR, a.tab, a.n_tab, q.NW, scratch);
             // header 2g: the shapes that run their head words first drop the words k_mc_cut proves to be no-ops for the whole launch
             const bool head_first = RS == 66 && (q.G == 1 ? MC_HEAD_FIRST_G1 != 0 : MC_HEAD_FIRST_SUB != 0);
-            if (head_first && g_mc_launch_cut && q.NW > 4) {
-                hipLaunchKernelGGL(k_mc_cut, dim3(1), dim3(64), 0, st, a.tab, a.n_tab, q.NW, q.NR, scratch);
+            if (head_first && g_mc_launch_cut && q.NW > nslices) {
+                hipLaunchKernelGGL(k_mc_cut, dim3(1), dim3(64), 0, st, a.tab, a.n_tab, q.NW, q.NR, nslices, scratch);
                 q.cut = 1;
                 g_last_cut = scratch + q.NW + q.NR;
             }
-            launch_shape<true>(RS, q, grid, lds, st);
+            launch_shape<true>(RS, tile, q, grid, lds, st);
             if (hipEventRecord(g_prep[dev].ev[slot], st) == hipSuccess) g_prep[dev].used[slot] = true;
             return true;
         }
     }
-    if (lean) launch_shape<true>(RS, q, grid, lds, st);
-    else launch_shape<false>(RS, q, grid, lds, st);
+    if (lean) launch_shape<true>(RS, tile, q, grid, lds, st);
+    else launch_shape<false>(RS, tile, q, grid, lds, st);
     return true;
 }
