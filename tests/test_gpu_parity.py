@@ -812,3 +812,105 @@ def test_device_samplers_at_wild_coordinates(gpu):
     for t_ in (gtex, dtex, itex):
         L.GPU_DestroyTexture(t_)
     L.GPU_DestroyBuffer(cbuf); L.GPU_DestroyBuffer(obuf)
+
+
+def _timed_op_names(L, g):
+    return [L.GPUX_GraphTimedOpName(g, i).decode() for i in range(L.GPUX_GraphTimedOpCount(g))]
+
+
+_PRECOMPUTE_FIRST = ["apron.env", "cells.env", "K3.irradiance", "apron.env", "K4a.prefilter_copy.mip0", "cells.env", "K4b.prefilter_mc.mip1",
+                     "K4b.prefilter_mc.mip2", "K4b.prefilter_mc.mip3", "K4b.prefilter_mc.mip4", "K4b.prefilter_mc.mip5", "K1.brdf_lut", "K2.mip_chain"]
+_PRECOMPUTE_AGAIN = ["K3.irradiance", "K4a.prefilter_copy.mip0", "K4b.prefilter_mc.mip1", "K4b.prefilter_mc.mip2", "K4b.prefilter_mc.mip3",
+                     "K4b.prefilter_mc.mip4", "K4b.prefilter_mc.mip5", "K1.brdf_lut", "K2.mip_chain"]
+
+
+def test_timed_op_names_of_the_precompute(gpu):
+    """bench.py and the tools under tools/ pick their rows by timed-op name.  The irradiance map, the prefiltered chain of a 32^2 cube
+    (every level), the BRDF LUT and a mip chain, recorded into one graph from a 32^2 environment and submitted twice: the names of each
+    submission, in order.  The first one builds the environment's apron and cells twins where a dispatch first samples a level
+    (irradiance: level 5; the copy: level 1; mip 1: level 4); the second finds them all."""
+    import pbrhip
+    from pbrhip import synth
+    L = gpu
+    env_tex = pbrhip.make_texture(pbrhip.Format_RGBA32F, 32, 32, pbrhip.TextureFlag_Cubemap | pbrhip.TextureFlag_HasMipmaps, synth.synth_env(32, seed=0x5EED00AB))
+    other = pbrhip.make_texture(pbrhip.Format_RGBA32F, 8, 8, pbrhip.TextureFlag_Cubemap | pbrhip.TextureFlag_HasMipmaps, synth.synth_env(8, seed=0x5EED00AC))
+    maps = pbrhip.PBR_IBLMaps()
+    L.PBR_MakeIBLMaps(C.byref(maps), 16, 32, 32)
+    levels = maps.tex_specular_env_map.contents.mip_level_count
+    assert levels == 6
+    units = [(pbrhip.Unit_Irradiance, 0, 6, 16)] + [(pbrhip.Unit_Prefilter, m, 6, 32 >> m) for m in range(levels)] + [(pbrhip.Unit_BrdfLut, 0, 1, 32)]
+    arr = (pbrhip.PBR_WorkUnit * len(units))(*[pbrhip.PBR_WorkUnit(kind, mip, 0, faces, 0, rows, 0.0) for kind, mip, faces, rows in units])
+    pipes = L.PBR_MakeIBLPipelines(); arena = L.GPU_MakeDescriptorArena(); g = L.GPU_MakeGraph()
+    L.GPUX_EnableOpTiming(1)
+    try:
+        names = []
+        for _ in range(2):
+            L.PBR_RecordUnits(pipes, g, arena, env_tex, C.byref(maps), arr, len(units))
+            L.GPU_OpGenerateMipmaps(g, other)
+            L.GPU_GraphSubmit(g); L.GPU_GraphWait(g)
+            names.append(_timed_op_names(L, g))
+            print(names[-1])
+        assert names[0] == _PRECOMPUTE_FIRST
+        assert names[1] == _PRECOMPUTE_AGAIN
+        smallest = pbrhip.read_mip(maps.tex_specular_env_map, levels - 1)     # 6 faces of 1 x 1
+        assert smallest.shape[0] == 6 and float(smallest[..., :3].min()) > 0.0
+    finally:
+        L.GPUX_EnableOpTiming(0)
+    L.GPU_DestroyGraph(g); L.GPU_DestroyDescriptorArena(arena); L.PBR_DestroyIBLPipelines(pipes)
+    L.PBR_DestroyIBLMaps(C.byref(maps)); L.GPU_DestroyTexture(other); L.GPU_DestroyTexture(env_tex)
+
+
+_FRAME_FIRST = ["K7.sweep_x", "apron.prefiltered", "cells.prefiltered", "apron.irradiance", "K5.shade", "K8.taa_resolve",
+                "K10.bloom_downsample", "K10.bloom_downsample", "K10.bloom_downsample", "K10.bloom_downsample", "K10.bloom_downsample", "K10.bloom_downsample",
+                "K11.bloom_upsample", "K11.bloom_upsample", "K11.bloom_upsample", "K11.bloom_upsample", "K11.bloom_upsample", "K11.bloom_upsample",
+                "K9.final_post_process"]
+_FRAME_AGAIN = ["K7.sweep_x", "K5.shade", "K8.taa_resolve",
+                "K10.bloom_downsample", "K10.bloom_downsample", "K10.bloom_downsample", "K10.bloom_downsample", "K10.bloom_downsample", "K10.bloom_downsample",
+                "K11.bloom_upsample", "K11.bloom_upsample", "K11.bloom_upsample", "K11.bloom_upsample", "K11.bloom_upsample", "K11.bloom_upsample",
+                "K9.final_post_process"]
+
+
+def test_timed_op_names_of_the_frame_chain(gpu):
+    """The same pin for one frame of the 320x180 chain of test_post.py::test_gpu_frame_chain_hipgraph_replay_is_identical (sweep,
+    shade, TAA resolve, bloom, tone map), per-op timing on and replay off, submitted twice: only the first submission builds the twins
+    the shade samples, and the 1:1 blit that fold_blits folds into the last upsample has no entry."""
+    import pbrhip
+    from pbrhip import synth
+    L = gpu
+    W, H = 320, 180
+    gbd = synth.synth_gbuffer_spheres(W, H)
+    _, _, vel, vel_prev, history = synth.synth_post_inputs(0x5EED00D1, W, H)
+    env_tex = pbrhip.make_texture(pbrhip.Format_RGBA32F, 64, 64, pbrhip.TextureFlag_Cubemap | pbrhip.TextureFlag_HasMipmaps, synth.synth_env(64, seed=0x5EED00AA))
+    maps = pbrhip.PBR_IBLMaps()
+    L.PBR_MakeIBLMaps(C.byref(maps), 16, 64, 64)
+    L.PBR_GenIrradianceMap(env_tex, maps.irradiance_map); L.PBR_GenPrefilteredEnvMap(env_tex, maps.tex_specular_env_map, 1); L.PBR_GenBRDFIntegrationMap(maps.brdf_lut)
+    gb = pbrhip.PBR_GBuffer()
+    L.PBR_MakeGBuffer(C.byref(gb), W, H, pbrhip.Format_RGBA16F)
+    for nm, key in (("base_color", "base"), ("normal", "normal"), ("orm", "orm"), ("emissive", "emissive"), ("depth", "depth")):
+        pbrhip.upload_mip(getattr(gb, nm), 0, gbd[key])
+    lp = L.PBR_MakeLightingPass(C.byref(gb), C.byref(maps), W, H)
+    pp = L.PBR_MakePostProcess(C.byref(gb), W, H, pbrhip.Format_BGRA8UN)
+    pbrhip.upload_mip(L.PBR_PostVelocity(pp, 0), 0, vel); pbrhip.upload_mip(L.PBR_PostVelocity(pp, 1), 0, vel_prev)
+    pbrhip.upload_mip(L.PBR_PostTaaOutput(pp, 1), 0, history)
+    lg = L.PBR_MakeLightgrid(128)
+    pbrhip.upload_mip(L.PBR_LightgridTexture(lg), 0, synth.synth_lightgrid(128, lit=False).view(np.uint16))
+    glob = pbrhip.fill_globals(gbd["cam_pos"], aspect=W / H, frame_idx=0)
+    g = L.GPU_MakeGraph()
+    L.GPUX_SetGraphReplay(0); L.GPUX_EnableOpTiming(1)
+    try:
+        names = []
+        for _ in range(2):
+            L.PBR_RecordLightgridSweepLines(lg, g, 0, 0, 128, 0, 128)
+            L.PBR_RecordLightingPass(lp, g, C.byref(glob), 0, 0)
+            L.PBR_RecordTaaResolve(pp, g, 0); L.PBR_RecordBloom(pp, g, 0); L.PBR_RecordFinalPostProcessBloom(pp, g, 0)
+            L.GPU_GraphSubmit(g); L.GPU_GraphWait(g)
+            names.append(_timed_op_names(L, g))
+            print(names[-1])
+        assert names[0] == _FRAME_FIRST
+        assert names[1] == _FRAME_AGAIN
+        assert int(pbrhip.read_mip(L.PBR_PostBackbuffer(pp), 0).max()) > 0
+    finally:
+        L.GPUX_EnableOpTiming(0)
+    L.GPU_DestroyGraph(g)
+    L.PBR_DestroyLightgrid(lg); L.PBR_DestroyPostProcess(pp); L.PBR_DestroyLightingPass(lp); L.PBR_DestroyGBuffer(C.byref(gb))
+    L.PBR_DestroyIBLMaps(C.byref(maps)); L.GPU_DestroyTexture(env_tex)

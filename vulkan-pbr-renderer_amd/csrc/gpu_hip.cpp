@@ -50,6 +50,10 @@ static void gpu_fail(const char* fmt, ...) {
 enum BindKind { Bind_Texture, Bind_Sampler, Bind_Buffer, Bind_StorageImage };
 enum KernelId { Kernel_None = 0, Kernel_BrdfLut, Kernel_Irradiance, Kernel_Prefilter, Kernel_Lighting, Kernel_LightgridSweep, Kernel_TaaResolve, Kernel_FinalPost, Kernel_BloomDown, Kernel_BloomUp, Kernel_SunDepth, Kernel_Geometry, Kernel_Voxelize };
 
+// the full-screen passes behind the lighting pass (K8 .. K11), and the two of them that make the bloom chain
+static bool is_bloom_kernel(KernelId k) { return k == Kernel_BloomDown || k == Kernel_BloomUp; }
+static bool is_post_kernel(KernelId k) { return is_bloom_kernel(k) || k == Kernel_FinalPost || k == Kernel_TaaResolve; }
+
 struct GPU_Sampler { GPU_SamplerDesc desc; bool shared; };
 
 struct LayoutBinding { std::string name; BindKind kind; GPU_Format format; };
@@ -187,7 +191,6 @@ struct TableKey {
 
 static struct {
     GPU_Graph* last_submitted = nullptr;            // submission order between graphs (the reference has one queue: gpu_vulkan.c:2481)
-    int tile_streams = -1;                          // side streams for small independent precompute dispatches (-1: PBR_TILE_STREAMS or 4)
     bool init = false;
     int device = -1;
     GPU_Sampler samplers[6];
@@ -195,7 +198,12 @@ static struct {
     bool timing = false;
     float prefilter_tol = 0.0f;                     // GPUX_SetPrefilterTolerance: 0 = exact sums (default)
     int kept_samples[32] = {0};                     // per output mip: samples kept by the last prefilter dispatch
-    int replay = -1;                                // GPUX_SetGraphReplay: submissions go through an instantiated hipGraph (-1: PBR_GRAPH_REPLAY or 0)
+    // submit-time settings, each read once on first use (env_setting; -1: not read yet) unless its GPUX_Set* call came first
+    int fold = -1;                                  // PBR_GRAPH_FOLD or 1: fold_blits
+    int order = -1;                                 // PBR_GRAPH_ORDER or 1; 0: diagnostic only (shows that the ordering test can fail)
+    int overlap = -1;                               // GPUX_SetGraphOverlap, PBR_GRAPH_OVERLAP or 1: head / tail overlap of frames in flight
+    int replay = -1;                                // GPUX_SetGraphReplay, PBR_GRAPH_REPLAY or 0: submissions go through an instantiated hipGraph
+    int tile_streams = -1;                          // GPUX_SetTileStreams, PBR_TILE_STREAMS or 4: side streams for small independent precompute dispatches
     unsigned long long* raster_rejected = nullptr;  // device counters: [0] GPUX_RasterRejectedTriangles, [1] GPUX_VoxelizeFragments
     uint64_t raster_rejected_base = 0;              // what earlier GPU_Init .. GPU_Deinit spans counted
 } G;
@@ -679,7 +687,7 @@ GPU_API GPU_String GPU_SPIRVFromGLSL(DS_Arena* arena, GPU_ShaderStage stage, GPU
     GPU_ShaderDesc probe = *desc;
     probe.spirv = empty;
     KernelId k = identify_shader(&probe);
-    bool stage_ok = (k == Kernel_Lighting || k == Kernel_TaaResolve || k == Kernel_FinalPost || k == Kernel_BloomDown || k == Kernel_BloomUp || k == Kernel_SunDepth || k == Kernel_Geometry || k == Kernel_Voxelize) ? (stage == GPU_ShaderStage_Vertex || stage == GPU_ShaderStage_Fragment)
+    bool stage_ok = (k == Kernel_Lighting || is_post_kernel(k) || k == Kernel_SunDepth || k == Kernel_Geometry || k == Kernel_Voxelize) ? (stage == GPU_ShaderStage_Vertex || stage == GPU_ShaderStage_Fragment)
                                            : (stage == GPU_ShaderStage_Compute);
     if (k != Kernel_None && stage_ok) {
         if (out_errors) { out_errors->data = nullptr; out_errors->length = 0; }
@@ -944,6 +952,11 @@ static bool fill_sun_draw(const RasterDraw& d, void* out) {
     return true;
 }
 static PbrkGeoTex material_tex(const TextureImpl* t) { return {material_texels(t), (int)t->base.width, (int)t->base.height, (int)t->base.mip_level_count, 0}; }
+// the post passes' view of a whole 2-D texture, and the PBRK_FMT_* of the colour target they store to
+static PbrkTex2D tex2d(const TextureImpl* t, int fmt) { PbrkTex2D r; r.data = t->dev; r.format = fmt; r.width = (int)t->base.width; r.height = (int)t->base.height; return r; }
+static int out_fmt(GPU_Format f) {
+    return f == GPU_Format_RGBA16F ? PBRK_FMT_RGBA16F : (f == GPU_Format_RGBA32F ? PBRK_FMT_RGBA32F : (f == GPU_Format_RGBA8UN ? PBRK_FMT_RGBA8UN : PBRK_FMT_BGRA8UN));
+}
 static bool fill_geo_draw(const RasterDraw& d, void* out) {               // both matrices, the draw's textures and buffers
     PbrkGeoDraw& o = *(PbrkGeoDraw*)out;
     memset(&o, 0, sizeof o);
@@ -1103,7 +1116,7 @@ GPU_API GPU_GraphicsPipeline* GPU_MakeGraphicsPipeline(const GPU_GraphicsPipelin
         p->layout = desc->layout; p->pass = desc->render_pass; p->kernel = k; p->shade_flags = 0; p->vertex_stride = stride; p->raster = rk;
         return p;
     }
-    GPU_REQUIRE(k == Kernel_Lighting || k == Kernel_TaaResolve || k == Kernel_FinalPost || k == Kernel_BloomDown || k == Kernel_BloomUp, nullptr,
+    GPU_REQUIRE(k == Kernel_Lighting || is_post_kernel(k), nullptr,
                 "GPU_MakeGraphicsPipeline: unsupported (raster): only the full-screen lighting_pass / taa_resolve / final_post_process pipelines have HIP kernels (got \"%s\")",
                 basename_of(desc->fs.glsl_debug_filepath).c_str());
     GPU_REQUIRE(desc->vertex_input_formats_count == 0, nullptr, "GPU_MakeGraphicsPipeline: unsupported (raster): vertex inputs");
@@ -1111,7 +1124,7 @@ GPU_API GPU_GraphicsPipeline* GPU_MakeGraphicsPipeline(const GPU_GraphicsPipelin
     GPU_GraphicsPipeline* p = new GPU_GraphicsPipeline();
     p->layout = desc->layout; p->pass = desc->render_pass; p->kernel = k; p->shade_flags = GPUX_Shade_IBL;
     if (desc->enable_blending) {                                              // gpu_vulkan.c:1828-1842
-        if (!(desc->blending_mode_additive && (k == Kernel_BloomDown || k == Kernel_BloomUp))) {
+        if (!(desc->blending_mode_additive && is_bloom_kernel(k))) {
             gpu_fail("GPU_MakeGraphicsPipeline: blending is implemented for the additive bloom passes only"); delete p; return nullptr;
         }
         p->blend_additive = true;
@@ -1365,6 +1378,16 @@ static bool check_post_plane(Slot* s, GPU_Format f, uint32_t w, uint32_t h, cons
     return true;
 }
 
+// The Op_Shade of a checked full-screen draw: rows [row0, row1) of the pass, or all of them
+static void push_shade_op(GPU_Graph* g, Op& op, const DrawParams& dp, uint32_t row0, uint32_t row1, bool explicit_rows, const char* fn) {
+    const uint32_t H = g->in_pass->desc.height;
+    op.kind = Op_Shade;
+    op.gpipe = dp.pipeline; op.set = dp.set; op.pass = g->in_pass;
+    op.row0 = explicit_rows ? row0 : 0; op.row1 = explicit_rows ? row1 : H;
+    GPU_REQUIRE_V(op.row0 < op.row1 && op.row1 <= H, "%s: rows [%u,%u) outside the %u-row pass", fn, op.row0, op.row1, H);
+    g->ops.push_back(op);
+}
+
 // taa_resolve.glsl / final_post_process.glsl drawn as the full-screen triangle (render.cpp:1131-1137, 1181-1187)
 static void record_post(GPU_Graph* g, const DrawParams& dp, uint32_t row0, uint32_t row1, bool explicit_rows, const char* fn) {
     GPU_RenderPass* rp = g->in_pass;
@@ -1372,7 +1395,7 @@ static void record_post(GPU_Graph* g, const DrawParams& dp, uint32_t row0, uint3
     GPU_REQUIRE_V(rp->targets.size() == 1 && rp->targets[0].texture && rp->targets[0].mip_level < rp->targets[0].texture->mip_level_count, "%s: the pass needs one colour target", fn);
     TextureImpl* target = (TextureImpl*)rp->targets[0].texture;
     const uint32_t tmip = rp->targets[0].mip_level;
-    const bool bloom = dp.pipeline->kernel == Kernel_BloomDown || dp.pipeline->kernel == Kernel_BloomUp;
+    const bool bloom = is_bloom_kernel(dp.pipeline->kernel);
     GPU_REQUIRE_V(bloom || tmip == 0, "%s: only the bloom passes render into mip levels", fn);
     GPU_REQUIRE_V(mip_dim(target->base.width, tmip) == W && mip_dim(target->base.height, tmip) == H && target->base.layer_count == 1 && target->base.depth == 1,
                   "%s: colour target (mip %u) must be %ux%u", fn, tmip, W, H);
@@ -1385,12 +1408,9 @@ static void record_post(GPU_Graph* g, const DrawParams& dp, uint32_t row0, uint3
         GPU_REQUIRE_V(!(in->tex == target && smip == tmip), "%s: bloom pass reads the level it writes", fn);
         GPU_REQUIRE_V(g->push_size >= 4, "%s: the bloom shaders need their `int dst_mip_level` push constant", fn);
         Op op;
-        op.kind = Op_Shade; op.gpipe = dp.pipeline; op.set = s; op.pass = rp;
         memcpy(op.push, g->push, g->push_size); op.push_size = g->push_size;
         op.mip = smip; op.mip2 = tmip;
-        op.row0 = explicit_rows ? row0 : 0; op.row1 = explicit_rows ? row1 : H;
-        GPU_REQUIRE_V(op.row0 < op.row1 && op.row1 <= H, "%s: rows [%u,%u) outside the %u-row pass", fn, op.row0, op.row1, H);
-        g->ops.push_back(op);
+        push_shade_op(g, op, dp, row0, row1, explicit_rows, fn);
         return;
     }
     if (dp.pipeline->kernel == Kernel_TaaResolve) {
@@ -1409,11 +1429,7 @@ static void record_post(GPU_Graph* g, const DrawParams& dp, uint32_t row0, uint3
         GPU_REQUIRE_V(named_slot(s, "TEX0")->tex != target, "%s: target aliases TEX0", fn);
     }
     Op op;
-    op.kind = Op_Shade;
-    op.gpipe = dp.pipeline; op.set = s; op.pass = rp;
-    op.row0 = explicit_rows ? row0 : 0; op.row1 = explicit_rows ? row1 : H;
-    GPU_REQUIRE_V(op.row0 < op.row1 && op.row1 <= H, "%s: rows [%u,%u) outside the %u-row pass", fn, op.row0, op.row1, H);
-    g->ops.push_back(op);
+    push_shade_op(g, op, dp, row0, row1, explicit_rows, fn);
 }
 
 static void record_shade(GPU_Graph* g, uint32_t row0, uint32_t row1, bool explicit_rows, const char* fn) {
@@ -1423,10 +1439,7 @@ static void record_shade(GPU_Graph* g, uint32_t row0, uint32_t row1, bool explic
     GPU_REQUIRE_V(dp.set->layout == dp.pipeline->layout, "%s: descriptor set and pipeline use different layouts", fn);
     GPU_RenderPass* rp = g->in_pass;
     uint32_t W = rp->desc.width, H = rp->desc.height;
-    if (dp.pipeline->kernel == Kernel_TaaResolve || dp.pipeline->kernel == Kernel_FinalPost || dp.pipeline->kernel == Kernel_BloomDown || dp.pipeline->kernel == Kernel_BloomUp) {
-        record_post(g, dp, row0, row1, explicit_rows, fn);
-        return;
-    }
+    if (is_post_kernel(dp.pipeline->kernel)) { record_post(g, dp, row0, row1, explicit_rows, fn); return; }
     GPU_REQUIRE_V(dp.pipeline->kernel == Kernel_Lighting, "%s: unsupported (raster)", fn);
     GPU_REQUIRE_V(rp->targets.size() == 1 && rp->targets[0].texture, "%s: lighting pass needs one colour target", fn);
     TextureImpl* target = (TextureImpl*)rp->targets[0].texture;
@@ -1468,11 +1481,7 @@ static void record_shade(GPU_Graph* g, uint32_t row0, uint32_t row1, bool explic
                       "%s: \"BRDF_INTEGRATION_MAP\" must be a square RG16F texture", fn);
     }
     Op op;
-    op.kind = Op_Shade;
-    op.gpipe = dp.pipeline; op.set = s; op.pass = rp;
-    op.row0 = explicit_rows ? row0 : 0; op.row1 = explicit_rows ? row1 : H;
-    GPU_REQUIRE_V(op.row0 < op.row1 && op.row1 <= H, "%s: rows [%u,%u) outside the %u-row pass", fn, op.row0, op.row1, H);
-    g->ops.push_back(op);
+    push_shade_op(g, op, dp, row0, row1, explicit_rows, fn);
 }
 
 GPU_API void GPU_OpDraw(GPU_Graph* g, uint32_t vertex_count, uint32_t instance_count, uint32_t first_vertex, uint32_t first_instance) {
@@ -1747,269 +1756,359 @@ static void publish_side_work(GPU_Graph* g) {
     for (hipStream_t s : g->side) if (s != g->cur) HIP_OK(hipStreamWaitEvent(s, e, 0));
 }
 
-static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
-    hipStream_t st = g->cur;
-    switch (op.kind) {
-    case Op_Dispatch: {
-        if (op.cpipe->kernel == Kernel_LightgridSweep) {
-            TextureImpl* it = named_slot(op.set, "IMG0")->tex;
-            int32_t dir; memcpy(&dir, op.push, 4);
-            timed(g, dir == 0 ? "K7.sweep_x" : (dir == 1 ? "K7.sweep_y" : "K7.sweep_z"), ev_used, [&] {
-                int rc = pbrk_lightgrid_sweep(it->dev, (int)it->base.width, (int)it->base.height, (int)it->base.depth, dir,
-                                              (int)op.row0, (int)op.row1, (int)op.face0, (int)op.face1, st);
-                if (rc != PBRK_OK) gpu_fail("K7 launch failed (%d)", rc);
-            });
-            return;
-        }
-        Slot* out = named_slot(op.set, "OUTPUT");
-        TextureImpl* ot = out->tex;
-        uint32_t size = mip_dim(ot->base.width, out->mip);
-        void* out_ptr = (char*)ot->dev + ot->mip_offset[out->mip];
-        GPUX_IBLConstants c = {0, 0.0f, 0.0f, 0};
-        bool explicit_c = false;
-        if (op.push_size == sizeof(GPUX_IBLConstants)) { memcpy(&c, op.push, sizeof c); explicit_c = true; }
-        else if (op.push_size >= 4) memcpy(&c.mip_level, op.push, 4);
-        char nm[96];
-        if (op.cpipe->kernel == Kernel_BrdfLut) {
-            int n = (explicit_c && c.sample_count > 0) ? c.sample_count : 4096;
-            DeviceTable* ang = get_table(2, n, 0.0f, 0);
-            DeviceTable* vcs = get_table(3, (int)size, 0.0f, 0);
-            if (!ang || !vcs) return;
-            int fmt = ot->base.format == GPU_Format_RG16F ? PBRK_FMT_RG16F : (ot->base.format == GPU_Format_RG32F ? PBRK_FMT_RG32F : PBRK_FMT_RGBA32F);
-            timed(g, "K1.brdf_lut", ev_used, [&] {
-                int rc = pbrk_brdf_lut(out_ptr, fmt, (int)size, n, ang->dev, vcs->dev, (int)op.row0, (int)op.row1, st);
-                if (rc != PBRK_OK) gpu_fail("K1 launch failed (%d)", rc);
-            });
-            ot->bordered_valid = false; ot->lut_cells_valid = false;
-            return;
-        }
-        Slot* env = named_slot(op.set, "TEX_ENV_CUBE");
-        TextureImpl* et = env->tex;
-        int W = (int)et->base.width, levels = (int)et->base.mip_level_count;
-        float lod; int n; float divisor, alpha = 0.0f; DeviceTable* tab = nullptr;
-        bool copy = false;
-        if (op.cpipe->kernel == Kernel_Prefilter) {
-            int mip = c.mip_level;
-            if (mip == 0) { copy = true; lod = explicit_c ? c.src_lod : 1.0f; }
-            else {
-                lod = explicit_c ? c.src_lod : 3.0f + (float)mip;
-                n = (explicit_c && c.sample_count > 0) ? c.sample_count : 8192;
-                float rough = explicit_c ? c.roughness : reference_roughness(mip);
-                if (!(rough > 0.0f)) { gpu_fail("prefilter: roughness must be > 0 for Monte-Carlo mips (got %g)", rough); return; }
-                tab = get_table(0, n, rough, 0);
-                if (!tab) return;
-                divisor = 3.14159265358979323846f; alpha = tab->alpha;
-            }
-            snprintf(nm, sizeof nm, copy ? "K4a.prefilter_copy.mip%d" : "K4b.prefilter_mc.mip%d", mip);
-        } else {
-            lod = explicit_c ? c.src_lod : 6.0f;                 // gen_irradiance_map.glsl:94
-            n = (explicit_c && c.sample_count > 0) ? c.sample_count : 1024;
-            tab = get_table(1, n, 0.0f, 0);
-            if (!tab) return;
-            divisor = (float)n; alpha = 0.0f;
-            snprintf(nm, sizeof nm, "K3.irradiance");
-        }
-        int l = (int)floorf(lod);
-        if (l < 0) l = 0;
-        if (l > levels - 1) l = levels - 1;                     // sampler clamps LOD to the chain
-        if ((float)l != lod && lod < (float)(levels - 1)) { gpu_fail("%s: fractional source LOD %g is not supported by the precompute kernels", nm, lod); return; }
-        if (!et->bordered_valid || et->bordered_from > l) {
-            timed(g, "apron.env", ev_used, [&] { ensure_bordered(et, st, l); });
-            if (!et->bordered_valid || et->bordered_from > l) return;
-            publish_side_work(g);
-        }
-        int n_src = W >> l; if (n_src < 1) n_src = 1;
-        const void* src = (const char*)et->bordered + pbrk_bordered_level_offset(W, l) * 16;
-        const void* cells = nullptr;
-        if (!copy) {
-            if (cells_ready(et, l)) cells = ensure_cells(et, l, st);
-            else { timed(g, "cells.env", ev_used, [&] { cells = ensure_cells(et, l, st); }); publish_side_work(g); }
-        }
-        int n_keep = tab ? tab->count : 0;
-        if (!copy && op.cpipe->kernel == Kernel_Prefilter && G.prefilter_tol > 0.0f) {         // opt-in: tolerance-budgeted sample cut (gpux.h)
-            float mn = 0.0f, mx = 0.0f;
-            if (level_range(et, l, st, &mn, &mx)) n_keep = bounded_sample_count(tab, mn, mx, G.prefilter_tol);
-        }
-        if (!copy && op.cpipe->kernel == Kernel_Prefilter && c.mip_level >= 0 && c.mip_level < 32) G.kept_samples[c.mip_level] = n_keep;
-        timed(g, nm, ev_used, [&] {
-            int rc = copy ? pbrk_prefilter_copy(src, n_src, out_ptr, (int)size, (int)op.face0, (int)op.face1, (int)op.row0, (int)op.row1, st)
-                          : pbrk_mc_filter(src, cells, n_src, tab->dev, n_keep, divisor, alpha, out_ptr, (int)size,
-                                           (int)op.face0, (int)op.face1, (int)op.row0, (int)op.row1, st);
-            if (rc != PBRK_OK) gpu_fail("%s launch failed (%d)", nm, rc);
-        });
-        ot->bordered_valid = false;
-        return;
+// ---- one function per kernel family; exec_op at the end of the section picks one by the op's kind and kernel ----
+static void exec_sweep(GPU_Graph* g, Op& op, size_t& ev_used) {
+    TextureImpl* it = named_slot(op.set, "IMG0")->tex;
+    int32_t dir; memcpy(&dir, op.push, 4);
+    timed(g, dir == 0 ? "K7.sweep_x" : (dir == 1 ? "K7.sweep_y" : "K7.sweep_z"), ev_used, [&] {
+        int rc = pbrk_lightgrid_sweep(it->dev, (int)it->base.width, (int)it->base.height, (int)it->base.depth, dir,
+                                      (int)op.row0, (int)op.row1, (int)op.face0, (int)op.face1, g->cur);
+        if (rc != PBRK_OK) gpu_fail("K7 launch failed (%d)", rc);
+    });
+}
+
+// The push constants of a precompute dispatch: a whole GPUX_IBLConstants block (true), or the reference's 4-byte `int mip_level`
+static bool ibl_constants(const Op& op, GPUX_IBLConstants& c) {
+    c = {0, 0.0f, 0.0f, 0};
+    if (op.push_size == sizeof(GPUX_IBLConstants)) { memcpy(&c, op.push, sizeof c); return true; }
+    if (op.push_size >= 4) memcpy(&c.mip_level, op.push, 4);
+    return false;
+}
+
+static void exec_brdf_lut(GPU_Graph* g, Op& op, size_t& ev_used) {
+    Slot* out = named_slot(op.set, "OUTPUT");
+    TextureImpl* ot = out->tex;
+    uint32_t size = mip_dim(ot->base.width, out->mip);
+    void* out_ptr = (char*)ot->dev + ot->mip_offset[out->mip];
+    GPUX_IBLConstants c;
+    const bool explicit_c = ibl_constants(op, c);
+    int n = (explicit_c && c.sample_count > 0) ? c.sample_count : 4096;
+    DeviceTable* ang = get_table(2, n, 0.0f, 0);
+    DeviceTable* vcs = get_table(3, (int)size, 0.0f, 0);
+    if (!ang || !vcs) return;
+    int fmt = ot->base.format == GPU_Format_RG16F ? PBRK_FMT_RG16F : (ot->base.format == GPU_Format_RG32F ? PBRK_FMT_RG32F : PBRK_FMT_RGBA32F);
+    timed(g, "K1.brdf_lut", ev_used, [&] {
+        int rc = pbrk_brdf_lut(out_ptr, fmt, (int)size, n, ang->dev, vcs->dev, (int)op.row0, (int)op.row1, g->cur);
+        if (rc != PBRK_OK) gpu_fail("K1 launch failed (%d)", rc);
+    });
+    ot->bordered_valid = false; ot->lut_cells_valid = false;
+}
+
+// What an irradiance (K3) or prefilter (K4a: the copy of mip 0, K4b: Monte Carlo) dispatch asks for, decoded once from its push
+// constants: exec_ibl_filter launches from it, dispatch_samples_per_texel sizes the dispatch with it.
+struct IblPlan {
+    bool ok = true;                  // false: nothing can be launched (bad_roughness, or the table could not be made)
+    bool bad_roughness = false;      // a Monte-Carlo mip with roughness <= 0: only exec_ibl_filter reports it
+    bool copy = false;               // K4a
+    int mip = 0;                     // the prefilter's branch and output mip (c.mip_level)
+    float lod = 0.0f;                // source LOD
+    int n = 0;                       // samples asked for (the copy: 0)
+    float rough = 0.0f, divisor = 1.0f;
+    int table_kind = -1;             // get_table kind (0: prefilter, 1: irradiance; -1: the copy has none)
+    DeviceTable* tab = nullptr;      // that table
+    char name[96];                   // its GPUX_GraphTimedOpName
+};
+static IblPlan plan_ibl(const Op& op) {
+    IblPlan p;
+    GPUX_IBLConstants c;
+    const bool explicit_c = ibl_constants(op, c);
+    p.mip = c.mip_level;
+    if (op.cpipe->kernel == Kernel_Irradiance) {
+        p.lod = explicit_c ? c.src_lod : 6.0f;                   // gen_irradiance_map.glsl:94
+        p.n = (explicit_c && c.sample_count > 0) ? c.sample_count : 1024;
+        p.divisor = (float)p.n; p.table_kind = 1;
+        snprintf(p.name, sizeof p.name, "K3.irradiance");
+    } else if (p.mip == 0) {
+        p.copy = true; p.lod = explicit_c ? c.src_lod : 1.0f;
+        snprintf(p.name, sizeof p.name, "K4a.prefilter_copy.mip%d", p.mip);
+    } else {
+        p.lod = explicit_c ? c.src_lod : 3.0f + (float)p.mip;
+        p.n = (explicit_c && c.sample_count > 0) ? c.sample_count : 8192;
+        p.rough = explicit_c ? c.roughness : reference_roughness(p.mip);
+        p.divisor = 3.14159265358979323846f; p.table_kind = 0;
+        snprintf(p.name, sizeof p.name, "K4b.prefilter_mc.mip%d", p.mip);
+        if (!(p.rough > 0.0f)) { p.bad_roughness = true; p.ok = false; return p; }
     }
-    case Op_Shade: {
-        GPU_DescriptorSet* s = op.set;
-        GPU_RenderPass* rp = op.pass;
-        TextureImpl* target = (TextureImpl*)rp->targets[0].texture;
-        if (op.gpipe->kernel == Kernel_TaaResolve || op.gpipe->kernel == Kernel_FinalPost || op.gpipe->kernel == Kernel_BloomDown || op.gpipe->kernel == Kernel_BloomUp) {
-            auto tex2d = [](TextureImpl* t, int fmt) { PbrkTex2D r; r.data = t->dev; r.format = fmt; r.width = (int)t->base.width; r.height = (int)t->base.height; return r; };
-            auto out_fmt = [](GPU_Format f) {
-                return f == GPU_Format_RGBA16F ? PBRK_FMT_RGBA16F : (f == GPU_Format_RGBA32F ? PBRK_FMT_RGBA32F : (f == GPU_Format_RGBA8UN ? PBRK_FMT_RGBA8UN : PBRK_FMT_BGRA8UN));
-            };
-            if (op.gpipe->kernel == Kernel_BloomDown || op.gpipe->kernel == Kernel_BloomUp) {
-                TextureImpl* in = named_slot(s, "TEX0")->tex;
-                PbrkBloomArgs a;
-                a.src.data = (char*)in->dev + in->mip_offset[op.mip]; a.src.format = PBRK_FMT_RGBA16F;
-                a.src.width = (int)mip_dim(in->base.width, op.mip); a.src.height = (int)mip_dim(in->base.height, op.mip);
-                a.dst = (char*)target->dev + target->mip_offset[op.mip2];
-                a.dst_width = (int)rp->desc.width; a.dst_height = (int)rp->desc.height;
-                int32_t lvl; memcpy(&lvl, op.push, 4); a.dst_mip_level = lvl;
-                a.upsample = op.gpipe->kernel == Kernel_BloomUp; a.blend_additive = op.gpipe->blend_additive;
-                a.blend_src = op.blend_tex ? (const void*)((const char*)op.blend_tex->dev + op.blend_tex->mip_offset[op.blend_mip]) : nullptr;
-                a.y0 = (int)op.row0; a.y1 = (int)op.row1;
-                timed(g, a.upsample ? "K11.bloom_upsample" : "K10.bloom_downsample", ev_used, [&] {
-                    int rc = pbrk_bloom_pass(&a, st);
-                    if (rc != PBRK_OK) gpu_fail("bloom launch failed (%d)", rc);
-                });
-                return;
-            }
-            if (op.gpipe->kernel == Kernel_TaaResolve) {
-                PbrkTaaArgs a;
-                a.lighting_result = tex2d(named_slot(s, "LIGHTING_RESULT")->tex, PBRK_FMT_RGBA16F);
-                a.gbuffer_depth = tex2d(named_slot(s, "GBUFFER_DEPTH")->tex, PBRK_FMT_R32F);
-                a.gbuffer_velocity = tex2d(named_slot(s, "GBUFFER_VELOCITY")->tex, PBRK_FMT_RG16F);
-                a.gbuffer_velocity_prev = tex2d(named_slot(s, "GBUFFER_VELOCITY_PREV")->tex, PBRK_FMT_RG16F);
-                a.prev_frame_result = tex2d(named_slot(s, "PREV_FRAME_RESULT")->tex, PBRK_FMT_RGBA16F);
-                a.out = target->dev; a.out_format = out_fmt(target->base.format);
-                a.width = (int)rp->desc.width; a.height = (int)rp->desc.height; a.y0 = (int)op.row0; a.y1 = (int)op.row1;
-                timed(g, "K8.taa_resolve", ev_used, [&] {
-                    int rc = pbrk_taa_resolve(&a, st);
-                    if (rc != PBRK_OK) gpu_fail("K8 launch failed (%d)", rc);
-                });
-            } else {
-                PbrkFinalArgs a;
-                a.src = tex2d(named_slot(s, "TEX0")->tex, PBRK_FMT_RGBA16F);
-                a.out = target->dev; a.out_format = out_fmt(target->base.format);
-                a.width = (int)rp->desc.width; a.height = (int)rp->desc.height; a.y0 = (int)op.row0; a.y1 = (int)op.row1;
-                timed(g, "K9.final_post_process", ev_used, [&] {
-                    int rc = pbrk_final_post_process(&a, st);
-                    if (rc != PBRK_OK) gpu_fail("K9 launch failed (%d)", rc);
-                });
-            }
-            return;
-        }
-        PbrkShadeArgs a;
-        memset(&a, 0, sizeof a);
-        a.width = (int)rp->desc.width; a.height = (int)rp->desc.height;
-        a.x0 = 0; a.x1 = a.width; a.y0 = (int)op.row0; a.y1 = (int)op.row1;
-        // Globals first: visualize_lightgrid (word 137, main.cpp:79 / render.cpp:990) replaces the whole shading of every pixel with the
-        // light-grid ray march (lighting_pass.glsl:463-491) -- K16 over the same rows, none of K5's aprons / twins, whatever the flags
-        read_globals(named_slot(s, "GLOBALS")->buf, 0, a.globals, 552);
-        uint32_t visualize; memcpy(&visualize, &a.globals[137], 4);
-        if (visualize != 0) {
-            Slot* gs = named_slot(s, "LIGHTGRID");
-            TextureImpl* grid = gs ? gs->tex : nullptr;
-            GPU_REQUIRE_V(grid && grid->base.format == GPU_Format_RGBA16F && grid->base.layer_count == 1 && grid->base.depth >= 2 &&
-                          grid->base.width == grid->base.depth && grid->base.height == grid->base.depth && grid->base.depth <= 1024,
-                          "lighting pass: visualize_lightgrid is set, but \"LIGHTGRID\" is not bound to a cubic RGBA16F 3-D texture (render.cpp:678); nothing drawn");
-            PbrkGridViewArgs v;
-            v.x0 = 0; v.x1 = a.width; v.y0 = a.y0; v.y1 = a.y1; v.width = a.width; v.height = a.height;
-            v.lightgrid = grid->dev; v.lightgrid_size = (int)grid->base.width;
-            v.out = target->dev; v.out_format = target->base.format == GPU_Format_RGBA16F ? PBRK_FMT_RGBA16F : PBRK_FMT_RGBA32F;
-            memcpy(v.globals, a.globals, sizeof v.globals);
-            g->launch_sig.push_back(16);
-            timed(g, "K16.gridview", ev_used, [&] {
-                int rc = pbrk_lightgrid_view(&v, st);
-                if (rc != PBRK_OK) gpu_fail("K16 launch failed (%d)", rc);
-            });
-            target->bordered_valid = false;
-            return;
-        }
-        g->launch_sig.push_back(5);
-        a.base_color = named_slot(s, "GBUFFER_BASE_COLOR")->tex->dev;
-        a.normal = named_slot(s, "GBUFFER_NORMAL")->tex->dev;
-        a.orm = named_slot(s, "GBUFFER_ORM")->tex->dev;
-        a.emissive = named_slot(s, "GBUFFER_EMISSIVE")->tex->dev;
-        a.depth = named_slot(s, "GBUFFER_DEPTH")->tex->dev;
-        TextureImpl* pre = named_slot(s, "PREFILTERED_ENV_MAP")->tex;
-        if (!pre->bordered_valid || pre->bordered_from > 0) { timed(g, "apron.prefiltered", ev_used, [&] { ensure_bordered(pre, g->stream); }); if (!pre->bordered_valid) return; }
-        a.prefiltered_bordered = pre->bordered; a.prefiltered_size = (int)pre->base.width; a.prefiltered_levels = (int)pre->base.mip_level_count;
-        {
-            bool all = true;
-            for (int l = 0; l < (int)pre->base.mip_level_count; ++l) if (((int)pre->base.width >> l) <= 512 && !cells_ready(pre, l)) all = false;
-            auto build = [&] { for (int l = 0; l < (int)pre->base.mip_level_count; ++l) if (((int)pre->base.width >> l) <= 512) ensure_cells(pre, l, g->stream); };
-            if (all) build(); else timed(g, "cells.prefiltered", ev_used, build);
-            a.prefiltered_cells = pre->cells; a.prefiltered_cells_first = pre->cells_first;
-        }
-        a.flags = 0;
-        if (op.gpipe->shade_flags & GPUX_Shade_IBL) {
-            a.flags |= PBRK_SHADE_IBL;
-            TextureImpl* irr = named_slot(s, "TEX_IRRADIANCE_MAP")->tex;
-            if (!irr->bordered_valid || irr->bordered_from > 0) { timed(g, "apron.irradiance", ev_used, [&] { ensure_bordered(irr, g->stream); }); if (!irr->bordered_valid) return; }
-            a.irradiance_bordered = irr->bordered; a.irradiance_size = (int)irr->base.width;
-            a.irradiance_cells = ensure_cells(irr, 0, g->stream);
+    if (p.table_kind >= 0) {
+        p.tab = get_table(p.table_kind, p.n, p.rough, 0);        // cached; only entries with non-zero weight are kept
+        p.ok = p.tab != nullptr;
+    }
+    return p;
+}
+
+static void exec_ibl_filter(GPU_Graph* g, Op& op, size_t& ev_used) {
+    hipStream_t st = g->cur;
+    Slot* out = named_slot(op.set, "OUTPUT");
+    TextureImpl* ot = out->tex;
+    uint32_t size = mip_dim(ot->base.width, out->mip);
+    void* out_ptr = (char*)ot->dev + ot->mip_offset[out->mip];
+    TextureImpl* et = named_slot(op.set, "TEX_ENV_CUBE")->tex;
+    int W = (int)et->base.width, levels = (int)et->base.mip_level_count;
+    const IblPlan p = plan_ibl(op);
+    if (p.bad_roughness) { gpu_fail("prefilter: roughness must be > 0 for Monte-Carlo mips (got %g)", p.rough); return; }
+    if (!p.ok) return;
+    const bool mc_prefilter = op.cpipe->kernel == Kernel_Prefilter && !p.copy;
+    int l = (int)floorf(p.lod);
+    if (l < 0) l = 0;
+    if (l > levels - 1) l = levels - 1;                     // sampler clamps LOD to the chain
+    if ((float)l != p.lod && p.lod < (float)(levels - 1)) { gpu_fail("%s: fractional source LOD %g is not supported by the precompute kernels", p.name, p.lod); return; }
+    if (!et->bordered_valid || et->bordered_from > l) {
+        timed(g, "apron.env", ev_used, [&] { ensure_bordered(et, st, l); });
+        if (!et->bordered_valid || et->bordered_from > l) return;
+        publish_side_work(g);
+    }
+    int n_src = W >> l; if (n_src < 1) n_src = 1;
+    const void* src = (const char*)et->bordered + pbrk_bordered_level_offset(W, l) * 16;
+    const void* cells = nullptr;
+    if (!p.copy) {
+        if (cells_ready(et, l)) cells = ensure_cells(et, l, st);
+        else { timed(g, "cells.env", ev_used, [&] { cells = ensure_cells(et, l, st); }); publish_side_work(g); }
+    }
+    int n_keep = p.tab ? p.tab->count : 0;
+    if (mc_prefilter && G.prefilter_tol > 0.0f) {            // opt-in: tolerance-budgeted sample cut (gpux.h)
+        float mn = 0.0f, mx = 0.0f;
+        if (level_range(et, l, st, &mn, &mx)) n_keep = bounded_sample_count(p.tab, mn, mx, G.prefilter_tol);
+    }
+    if (mc_prefilter && p.mip >= 0 && p.mip < 32) G.kept_samples[p.mip] = n_keep;
+    const float alpha = p.table_kind == 0 ? p.tab->alpha : 0.0f;
+    timed(g, p.name, ev_used, [&] {
+        int rc = p.copy ? pbrk_prefilter_copy(src, n_src, out_ptr, (int)size, (int)op.face0, (int)op.face1, (int)op.row0, (int)op.row1, st)
+                        : pbrk_mc_filter(src, cells, n_src, p.tab->dev, n_keep, p.divisor, alpha, out_ptr, (int)size,
+                                         (int)op.face0, (int)op.face1, (int)op.row0, (int)op.row1, st);
+        if (rc != PBRK_OK) gpu_fail("%s launch failed (%d)", p.name, rc);
+    });
+    ot->bordered_valid = false;
+}
+
+// sample evaluations per output texel of a precompute dispatch
+static double dispatch_samples_per_texel(const Op& op) {
+    const IblPlan p = plan_ibl(op);
+    if (op.cpipe->kernel == Kernel_Irradiance) return p.n;
+    if (p.copy) return 4.0;                                                 // the copy level: one bilinear fetch, HBM-bound
+    return p.tab ? (double)p.tab->count : (double)p.n;
+}
+
+static void exec_bloom(GPU_Graph* g, Op& op, size_t& ev_used) {
+    GPU_RenderPass* rp = op.pass;
+    TextureImpl* target = (TextureImpl*)rp->targets[0].texture;
+    TextureImpl* in = named_slot(op.set, "TEX0")->tex;
+    PbrkBloomArgs a;
+    a.src.data = (char*)in->dev + in->mip_offset[op.mip]; a.src.format = PBRK_FMT_RGBA16F;
+    a.src.width = (int)mip_dim(in->base.width, op.mip); a.src.height = (int)mip_dim(in->base.height, op.mip);
+    a.dst = (char*)target->dev + target->mip_offset[op.mip2];
+    a.dst_width = (int)rp->desc.width; a.dst_height = (int)rp->desc.height;
+    int32_t lvl; memcpy(&lvl, op.push, 4); a.dst_mip_level = lvl;
+    a.upsample = op.gpipe->kernel == Kernel_BloomUp; a.blend_additive = op.gpipe->blend_additive;
+    a.blend_src = op.blend_tex ? (const void*)((const char*)op.blend_tex->dev + op.blend_tex->mip_offset[op.blend_mip]) : nullptr;
+    a.y0 = (int)op.row0; a.y1 = (int)op.row1;
+    timed(g, a.upsample ? "K11.bloom_upsample" : "K10.bloom_downsample", ev_used, [&] {
+        int rc = pbrk_bloom_pass(&a, g->cur);
+        if (rc != PBRK_OK) gpu_fail("bloom launch failed (%d)", rc);
+    });
+}
+
+static void exec_taa(GPU_Graph* g, Op& op, size_t& ev_used) {
+    GPU_DescriptorSet* s = op.set;
+    GPU_RenderPass* rp = op.pass;
+    TextureImpl* target = (TextureImpl*)rp->targets[0].texture;
+    PbrkTaaArgs a;
+    a.lighting_result = tex2d(named_slot(s, "LIGHTING_RESULT")->tex, PBRK_FMT_RGBA16F);
+    a.gbuffer_depth = tex2d(named_slot(s, "GBUFFER_DEPTH")->tex, PBRK_FMT_R32F);
+    a.gbuffer_velocity = tex2d(named_slot(s, "GBUFFER_VELOCITY")->tex, PBRK_FMT_RG16F);
+    a.gbuffer_velocity_prev = tex2d(named_slot(s, "GBUFFER_VELOCITY_PREV")->tex, PBRK_FMT_RG16F);
+    a.prev_frame_result = tex2d(named_slot(s, "PREV_FRAME_RESULT")->tex, PBRK_FMT_RGBA16F);
+    a.out = target->dev; a.out_format = out_fmt(target->base.format);
+    a.width = (int)rp->desc.width; a.height = (int)rp->desc.height; a.y0 = (int)op.row0; a.y1 = (int)op.row1;
+    timed(g, "K8.taa_resolve", ev_used, [&] {
+        int rc = pbrk_taa_resolve(&a, g->cur);
+        if (rc != PBRK_OK) gpu_fail("K8 launch failed (%d)", rc);
+    });
+}
+
+static void exec_final(GPU_Graph* g, Op& op, size_t& ev_used) {
+    GPU_RenderPass* rp = op.pass;
+    TextureImpl* target = (TextureImpl*)rp->targets[0].texture;
+    PbrkFinalArgs a;
+    a.src = tex2d(named_slot(op.set, "TEX0")->tex, PBRK_FMT_RGBA16F);
+    a.out = target->dev; a.out_format = out_fmt(target->base.format);
+    a.width = (int)rp->desc.width; a.height = (int)rp->desc.height; a.y0 = (int)op.row0; a.y1 = (int)op.row1;
+    timed(g, "K9.final_post_process", ev_used, [&] {
+        int rc = pbrk_final_post_process(&a, g->cur);
+        if (rc != PBRK_OK) gpu_fail("K9 launch failed (%d)", rc);
+    });
+}
+
+// K16 over the rows of a lighting op whose Globals (`globals`: the 552 bytes exec_shade has just read) set visualize_lightgrid
+static void exec_gridview(GPU_Graph* g, Op& op, size_t& ev_used, const float* globals) {
+    GPU_RenderPass* rp = op.pass;
+    TextureImpl* target = (TextureImpl*)rp->targets[0].texture;
+    Slot* gs = named_slot(op.set, "LIGHTGRID");
+    TextureImpl* grid = gs ? gs->tex : nullptr;
+    GPU_REQUIRE_V(grid && grid->base.format == GPU_Format_RGBA16F && grid->base.layer_count == 1 && grid->base.depth >= 2 &&
+                  grid->base.width == grid->base.depth && grid->base.height == grid->base.depth && grid->base.depth <= 1024,
+                  "lighting pass: visualize_lightgrid is set, but \"LIGHTGRID\" is not bound to a cubic RGBA16F 3-D texture (render.cpp:678); nothing drawn");
+    PbrkGridViewArgs v;
+    v.width = (int)rp->desc.width; v.height = (int)rp->desc.height;
+    v.x0 = 0; v.x1 = v.width; v.y0 = (int)op.row0; v.y1 = (int)op.row1;
+    v.lightgrid = grid->dev; v.lightgrid_size = (int)grid->base.width;
+    v.out = target->dev; v.out_format = target->base.format == GPU_Format_RGBA16F ? PBRK_FMT_RGBA16F : PBRK_FMT_RGBA32F;
+    memcpy(v.globals, globals, sizeof v.globals);
+    g->launch_sig.push_back(16);
+    timed(g, "K16.gridview", ev_used, [&] {
+        int rc = pbrk_lightgrid_view(&v, g->cur);
+        if (rc != PBRK_OK) gpu_fail("K16 launch failed (%d)", rc);
+    });
+    target->bordered_valid = false;
+}
+
+// The sampler twins that the lighting op (K5) reads and that are built lazily, in the order exec_shade builds them: the apron of the
+// prefiltered cube from level 0 and the cells of its levels of size <= 512; under GPUX_Shade_IBL the apron and the level-0 cells of
+// the irradiance cube and the cells of the BRDF LUT.  exec_shade builds what is missing of them, op_replayable asks whether anything
+// is, graph_replayable takes the sampled maps from them.
+enum TwinKind { Twin_Apron, Twin_SmallCells /* of every level of size <= 512 */, Twin_Cells0 /* of level 0 */, Twin_LutCells };
+struct ShadeTwin { TextureImpl* tex; TwinKind kind; const char* timed_name; /* of its build; NULL: not timed */ };
+static int shade_twins(GPU_DescriptorSet* s, int shade_flags, ShadeTwin tw[5]) {
+    auto tex = [&](const char* name) { Slot* sl = named_slot(s, name); return sl ? sl->tex : nullptr; };
+    int n = 0;
+    if (TextureImpl* pre = tex("PREFILTERED_ENV_MAP")) { tw[n++] = {pre, Twin_Apron, "apron.prefiltered"}; tw[n++] = {pre, Twin_SmallCells, "cells.prefiltered"}; }
+    if (!(shade_flags & GPUX_Shade_IBL)) return n;
+    if (TextureImpl* irr = tex("TEX_IRRADIANCE_MAP")) { tw[n++] = {irr, Twin_Apron, "apron.irradiance"}; tw[n++] = {irr, Twin_Cells0, nullptr}; }
+    if (TextureImpl* lut = tex("BRDF_INTEGRATION_MAP")) tw[n++] = {lut, Twin_LutCells, nullptr};
+    return n;
+}
+static bool shade_twin_ready(const ShadeTwin& tw) {
+    TextureImpl* t = tw.tex;
+    switch (tw.kind) {
+    case Twin_Apron: return t->bordered_valid && t->bordered_from <= 0;
+    case Twin_SmallCells:
+        for (int l = 0; l < (int)t->base.mip_level_count; ++l) if (((int)t->base.width >> l) <= 512 && !cells_ready(t, l)) return false;
+        return true;
+    case Twin_Cells0: return cells_ready(t, 0);
+    case Twin_LutCells: return t->lut_cells_valid;
+    }
+    return false;
+}
+// Builds a missing twin on the graph's main stream.  False: the op cannot be launched (its apron failed; K5 does without cells).
+static bool build_shade_twin(GPU_Graph* g, const ShadeTwin& tw, size_t& ev_used) {
+    TextureImpl* t = tw.tex;
+    switch (tw.kind) {
+    case Twin_Apron:
+        timed(g, tw.timed_name, ev_used, [&] { ensure_bordered(t, g->stream); });
+        return t->bordered_valid;
+    case Twin_SmallCells:
+        timed(g, tw.timed_name, ev_used, [&] { for (int l = 0; l < (int)t->base.mip_level_count; ++l) if (((int)t->base.width >> l) <= 512) ensure_cells(t, l, g->stream); });
+        return true;
+    case Twin_Cells0: ensure_cells(t, 0, g->stream); return true;
+    case Twin_LutCells: {
+        const int n = (int)t->base.width;
+        if (!t->lut_cells && hipMalloc(&t->lut_cells, (size_t)(n + 1) * (n + 1) * 16) != hipSuccess) t->lut_cells = nullptr;
+        if (t->lut_cells && pbrk_lut_cells_build(t->dev, n, t->lut_cells, g->stream) == PBRK_OK) t->lut_cells_valid = true;
+        return true;
+    }
+    }
+    return false;
+}
+static void* cells_of(TextureImpl* t, int level) { return cells_ready(t, level) ? (char*)t->cells + t->cells_off[(size_t)(level - t->cells_first)] : nullptr; }
+
+static void exec_shade(GPU_Graph* g, Op& op, size_t& ev_used) {
+    GPU_DescriptorSet* s = op.set;
+    GPU_RenderPass* rp = op.pass;
+    TextureImpl* target = (TextureImpl*)rp->targets[0].texture;
+    PbrkShadeArgs a;
+    memset(&a, 0, sizeof a);
+    a.width = (int)rp->desc.width; a.height = (int)rp->desc.height;
+    a.x0 = 0; a.x1 = a.width; a.y0 = (int)op.row0; a.y1 = (int)op.row1;
+    // Globals first: visualize_lightgrid (word 137, main.cpp:79 / render.cpp:990) replaces the whole shading of every pixel with the
+    // light-grid ray march (lighting_pass.glsl:463-491) -- K16 over the same rows, none of K5's aprons / twins, whatever the flags
+    read_globals(named_slot(s, "GLOBALS")->buf, 0, a.globals, 552);
+    uint32_t visualize; memcpy(&visualize, &a.globals[137], 4);
+    if (visualize != 0) { exec_gridview(g, op, ev_used, a.globals); return; }
+    g->launch_sig.push_back(5);
+    a.base_color = named_slot(s, "GBUFFER_BASE_COLOR")->tex->dev;
+    a.normal = named_slot(s, "GBUFFER_NORMAL")->tex->dev;
+    a.orm = named_slot(s, "GBUFFER_ORM")->tex->dev;
+    a.emissive = named_slot(s, "GBUFFER_EMISSIVE")->tex->dev;
+    a.depth = named_slot(s, "GBUFFER_DEPTH")->tex->dev;
+    ShadeTwin tw[5];
+    const int n_tw = shade_twins(s, op.gpipe->shade_flags, tw);
+    for (int i = 0; i < n_tw; ++i) if (!shade_twin_ready(tw[i]) && !build_shade_twin(g, tw[i], ev_used)) return;
+    TextureImpl* pre = named_slot(s, "PREFILTERED_ENV_MAP")->tex;
+    a.prefiltered_bordered = pre->bordered; a.prefiltered_size = (int)pre->base.width; a.prefiltered_levels = (int)pre->base.mip_level_count;
+    a.prefiltered_cells = pre->cells; a.prefiltered_cells_first = pre->cells_first;
+    a.flags = 0;
+    if (op.gpipe->shade_flags & GPUX_Shade_IBL) {
+        a.flags |= PBRK_SHADE_IBL;
+        TextureImpl* irr = named_slot(s, "TEX_IRRADIANCE_MAP")->tex;
+        a.irradiance_bordered = irr->bordered; a.irradiance_size = (int)irr->base.width;
+        a.irradiance_cells = cells_of(irr, 0);
+        TextureImpl* lut = named_slot(s, "BRDF_INTEGRATION_MAP")->tex;
+        a.lut = lut->dev; a.lut_size = (int)lut->base.width;
+        a.lut_cells = lut->lut_cells_valid ? lut->lut_cells : nullptr;
+    }
+    if (op.gpipe->shade_flags & GPUX_Shade_VoxelGI) {
+        a.flags |= PBRK_SHADE_GI;
+        TextureImpl* grid = named_slot(s, "LIGHTGRID")->tex;
+        a.lightgrid = grid->dev; a.lightgrid_size = (int)grid->base.width;
+        TextureImpl* prev = named_slot(s, "PREV_FRAME_RESULT")->tex;
+        a.prev_frame_levels = (int)(prev->base.mip_level_count < 8 ? prev->base.mip_level_count : 8);
+        a.prev_frame_w = (int)prev->base.width; a.prev_frame_h = (int)prev->base.height;
+        for (int l = 0; l < a.prev_frame_levels; ++l) a.prev_frame[l] = (char*)prev->dev + prev->mip_offset[l];
+        if (!(op.gpipe->shade_flags & GPUX_Shade_IBL)) {                   // the LUT fetch of :681 feeds the GI specular term too
             TextureImpl* lut = named_slot(s, "BRDF_INTEGRATION_MAP")->tex;
             a.lut = lut->dev; a.lut_size = (int)lut->base.width;
-            if (!lut->lut_cells_valid) {
-                size_t bytes = (size_t)(a.lut_size + 1) * (a.lut_size + 1) * 16;
-                if (!lut->lut_cells && hipMalloc(&lut->lut_cells, bytes) != hipSuccess) lut->lut_cells = nullptr;
-                if (lut->lut_cells && pbrk_lut_cells_build(lut->dev, a.lut_size, lut->lut_cells, g->stream) == PBRK_OK) lut->lut_cells_valid = true;
-            }
-            a.lut_cells = lut->lut_cells_valid ? lut->lut_cells : nullptr;
         }
-        if (op.gpipe->shade_flags & GPUX_Shade_VoxelGI) {
-            a.flags |= PBRK_SHADE_GI;
-            TextureImpl* grid = named_slot(s, "LIGHTGRID")->tex;
-            a.lightgrid = grid->dev; a.lightgrid_size = (int)grid->base.width;
-            TextureImpl* prev = named_slot(s, "PREV_FRAME_RESULT")->tex;
-            a.prev_frame_levels = (int)(prev->base.mip_level_count < 8 ? prev->base.mip_level_count : 8);
-            a.prev_frame_w = (int)prev->base.width; a.prev_frame_h = (int)prev->base.height;
-            for (int l = 0; l < a.prev_frame_levels; ++l) a.prev_frame[l] = (char*)prev->dev + prev->mip_offset[l];
-            if (!(op.gpipe->shade_flags & GPUX_Shade_IBL)) {                   // the LUT fetch of :681 feeds the GI specular term too
-                TextureImpl* lut = named_slot(s, "BRDF_INTEGRATION_MAP")->tex;
-                a.lut = lut->dev; a.lut_size = (int)lut->base.width;
-            }
-        }
-        if (op.gpipe->shade_flags & GPUX_Shade_LightShafts) a.flags |= PBRK_SHADE_SHAFTS;
-        if (op.gpipe->shade_flags & GPUX_Shade_SunShadows) {
-            TextureImpl* sun = named_slot(s, "SUN_DEPTH_MAP")->tex;
-            a.flags |= PBRK_SHADE_SHADOWS;
-            a.sun_depth = sun->dev; a.sun_depth_w = (int)sun->base.width; a.sun_depth_h = (int)sun->base.height;
-        }
-        a.out = target->dev;
-        a.out_format = target->base.format == GPU_Format_RGBA16F ? PBRK_FMT_RGBA16F : PBRK_FMT_RGBA32F;
-        timed(g, "K5.shade", ev_used, [&] {
-            int rc = pbrk_shade(&a, st);
-            if (rc != PBRK_OK) gpu_fail("K5 launch failed (%d)", rc);
-        });
-        target->bordered_valid = false;
+    }
+    if (op.gpipe->shade_flags & GPUX_Shade_LightShafts) a.flags |= PBRK_SHADE_SHAFTS;
+    if (op.gpipe->shade_flags & GPUX_Shade_SunShadows) {
+        TextureImpl* sun = named_slot(s, "SUN_DEPTH_MAP")->tex;
+        a.flags |= PBRK_SHADE_SHADOWS;
+        a.sun_depth = sun->dev; a.sun_depth_w = (int)sun->base.width; a.sun_depth_h = (int)sun->base.height;
+    }
+    a.out = target->dev;
+    a.out_format = target->base.format == GPU_Format_RGBA16F ? PBRK_FMT_RGBA16F : PBRK_FMT_RGBA32F;
+    timed(g, "K5.shade", ev_used, [&] {
+        int rc = pbrk_shade(&a, g->cur);
+        if (rc != PBRK_OK) gpu_fail("K5 launch failed (%d)", rc);
+    });
+    target->bordered_valid = false;
+}
+
+static void exec_mipgen(GPU_Graph* g, Op& op, size_t& ev_used) {
+    timed(g, op.name, ev_used, [&] {
+        int rc = is_rgba8_pow2(op.tex) ? pbrk_mip_chain_rgba8(op.tex->dev, (int)op.tex->base.width, (int)op.tex->base.height, (int)op.tex->base.mip_level_count, g->cur)
+                                       : pbrk_mip_chain(op.tex->dev, (int)op.tex->base.width, (int)op.tex->base.mip_level_count, g->cur);
+        if (rc != PBRK_OK) gpu_fail("K2 launch failed (%d)", rc);
+    });
+    op.tex->bordered_valid = false;
+}
+
+static void exec_blit(GPU_Graph* g, Op& op, size_t& ev_used) {
+    hipStream_t st = g->cur;
+    if (op.folded) { op.tex2->bordered_valid = false; op.tex2->lut_cells_valid = false; return; }   // its consumer reads the source (fold_blits)
+    if (op.size) {                                                         // 1:1 copy of one layer
+        const void* src = (const char*)op.tex->dev + op.tex->mip_offset[op.mip] + op.size * op.layer0;
+        void* dst = (char*)op.tex2->dev + op.tex2->mip_offset[op.mip2] + op.size * op.layer2;
+        timed(g, op.name, ev_used, [&] { HIP_OK(hipMemcpyAsync(dst, src, op.size, hipMemcpyDeviceToDevice, st)); });
+        op.tex2->bordered_valid = false; op.tex2->lut_cells_valid = false;
         return;
     }
-    case Op_Raster: exec_raster(g, op, ev_used); return;
-    case Op_MipGen: {
-        timed(g, op.name, ev_used, [&] {
-            int rc = is_rgba8_pow2(op.tex) ? pbrk_mip_chain_rgba8(op.tex->dev, (int)op.tex->base.width, (int)op.tex->base.height, (int)op.tex->base.mip_level_count, st)
-                                           : pbrk_mip_chain(op.tex->dev, (int)op.tex->base.width, (int)op.tex->base.mip_level_count, st);
-            if (rc != PBRK_OK) gpu_fail("K2 launch failed (%d)", rc);
-        });
-        op.tex->bordered_valid = false;
-        return;
-    }
-    case Op_Blit: {
-        if (op.folded) { op.tex2->bordered_valid = false; op.tex2->lut_cells_valid = false; return; }   // its consumer reads the source (fold_blits)
-        if (op.size) {                                                         // 1:1 copy of one layer
-            const void* src = (const char*)op.tex->dev + op.tex->mip_offset[op.mip] + op.size * op.layer0;
-            void* dst = (char*)op.tex2->dev + op.tex2->mip_offset[op.mip2] + op.size * op.layer2;
-            timed(g, op.name, ev_used, [&] { HIP_OK(hipMemcpyAsync(dst, src, op.size, hipMemcpyDeviceToDevice, st)); });
-            op.tex2->bordered_valid = false; op.tex2->lut_cells_valid = false;
-            return;
-        }
-        uint32_t nsw = mip_dim(op.tex->base.width, op.mip), nsh = mip_dim(op.tex->base.height, op.mip);
-        uint32_t ndw = mip_dim(op.tex2->base.width, op.mip2), ndh = mip_dim(op.tex2->base.height, op.mip2);
-        size_t layer_bytes_s = (size_t)nsw * nsh * 16, layer_bytes_d = (size_t)ndw * ndh * 16;
-        const void* src = (const char*)op.tex->dev + op.tex->mip_offset[op.mip] + layer_bytes_s * op.layer0;
-        void* dst = (char*)op.tex2->dev + op.tex2->mip_offset[op.mip2] + layer_bytes_d * op.layer2;
-        timed(g, op.name, ev_used, [&] {
-            int rc = (nsw == nsh && ndw == ndh && nsw == 2 * ndw) ? pbrk_box_downsample(src, (int)nsw, dst, 1, st)
-                                                                  : pbrk_blit_linear(src, (int)nsw, (int)nsh, dst, (int)ndw, (int)ndh, 1, st);
-            if (rc != PBRK_OK) gpu_fail("blit launch failed (%d)", rc);
-        });
-        op.tex2->bordered_valid = false;
-        return;
-    }
+    uint32_t nsw = mip_dim(op.tex->base.width, op.mip), nsh = mip_dim(op.tex->base.height, op.mip);
+    uint32_t ndw = mip_dim(op.tex2->base.width, op.mip2), ndh = mip_dim(op.tex2->base.height, op.mip2);
+    size_t layer_bytes_s = (size_t)nsw * nsh * 16, layer_bytes_d = (size_t)ndw * ndh * 16;
+    const void* src = (const char*)op.tex->dev + op.tex->mip_offset[op.mip] + layer_bytes_s * op.layer0;
+    void* dst = (char*)op.tex2->dev + op.tex2->mip_offset[op.mip2] + layer_bytes_d * op.layer2;
+    timed(g, op.name, ev_used, [&] {
+        int rc = (nsw == nsh && ndw == ndh && nsw == 2 * ndw) ? pbrk_box_downsample(src, (int)nsw, dst, 1, st)
+                                                              : pbrk_blit_linear(src, (int)nsw, (int)nsh, dst, (int)ndw, (int)ndh, 1, st);
+        if (rc != PBRK_OK) gpu_fail("blit launch failed (%d)", rc);
+    });
+    op.tex2->bordered_valid = false;
+}
+
+// the four memcpy ops
+static void exec_copy(GPU_Graph* g, Op& op, size_t& ev_used) {
+    hipStream_t st = g->cur;
+    switch (op.kind) {
     case Op_CopyB2B:
         timed(g, op.name, ev_used, [&] { HIP_OK(hipMemcpyAsync((char*)op.buf2->dev + op.off_b, (const char*)op.buf->dev + op.off_a, op.size, hipMemcpyDefault, st)); });
         return;
@@ -2039,61 +2138,74 @@ static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
                                   GPUX_TextureMipBytes(&op.tex->base, op.mip), hipMemcpyDefault, st));
         });
         return;
-    case Op_Clear: {
-        TextureImpl* t = op.tex;
-        uint32_t m0 = op.mip == GPU_MIP_LEVEL_ALL ? 0 : op.mip, m1 = op.mip == GPU_MIP_LEVEL_ALL ? t->base.mip_level_count : op.mip + 1;
-        // Levels are back to back in the allocation ([mip][layer][y][x], tight), so GPU_MIP_LEVEL_ALL is ONE fill of the whole
-        // texture instead of one per level: the reference clears bloom_upscale_rt this way every frame (render.cpp:1156; 11 levels at
-        // 1080p = 11 fill kernels of ~5 us each in rocprofv3's trace, a quarter of the post-process tail, before round 3).
-        const bool whole = op.mip == GPU_MIP_LEVEL_ALL;
-        for (uint32_t m = m0; m < (whole ? m0 + 1 : m1); ++m) {
-            size_t bytes = whole ? t->bytes : (size_t)GPUX_TextureMipBytes(&t->base, m);
-            void* p = (char*)t->dev + t->mip_offset[m];
-            if (whole && op.skip_level0) { p = (char*)t->dev + t->mip_offset[1]; bytes = t->bytes - t->mip_offset[1]; }   // fold_blits
-            // build one texel pattern on the host and replicate it (clears are rare: upload a staging row)
-            uint32_t tb = t->texel_bytes;
-            std::vector<uint8_t> texel(tb, 0);
-            if (op.clear_mode == 2 || t->base.format == GPU_Format_R32F) { memcpy(texel.data(), &op.clear[0], 4 < tb ? 4 : tb); }
-            else if (op.clear_mode == 1) { for (uint32_t k = 0; k * 4 < tb && k < 4; ++k) memcpy(texel.data() + 4 * k, &op.cleari[k], 4); }
-            else if (t->base.format == GPU_Format_RGBA32F || t->base.format == GPU_Format_RG32F) { memcpy(texel.data(), op.clear, tb); }
-            else if (t->base.format == GPU_Format_RGBA8UN || t->base.format == GPU_Format_BGRA8UN) {
-                int order[4] = {0, 1, 2, 3};
-                if (t->base.format == GPU_Format_BGRA8UN) { order[0] = 2; order[2] = 0; }
-                for (int k = 0; k < 4; ++k) { float v = op.clear[order[k]]; v = v < 0 ? 0 : (v > 1 ? 1 : v); texel[k] = (uint8_t)(v * 255.0f + 0.5f); }
-            } else {
-                bool zero = op.clear[0] == 0 && op.clear[1] == 0 && op.clear[2] == 0 && op.clear[3] == 0;
-                if (!zero) { gpu_fail("GPU_OpClearColorF: non-zero clears of format %d are not implemented", (int)t->base.format); return; }
-            }
-            // one fill launch for every texel size and alignment (k_cube.hip)
-            if (tb == 1 || tb == 2 || tb == 4 || tb == 8 || tb == 16) {
-                int rc = pbrk_fill_pattern(p, bytes, texel.data(), (int)tb, st);
-                if (rc != PBRK_OK) gpu_fail("clear launch failed (%d)", rc);
-            } else {
-                std::vector<uint8_t> host(bytes);
-                for (size_t o = 0; o < bytes; o += tb) memcpy(host.data() + o, texel.data(), tb);
-                HIP_OK(hipMemcpyAsync(p, host.data(), bytes, hipMemcpyHostToDevice, st));
-                HIP_OK(hipStreamSynchronize(st));      // the staging vector dies at scope exit
-            }
-        }
-        t->bordered_valid = false; t->lut_cells_valid = false;
-        return;
-    }
+    default: return;
     }
 }
 
-// sample evaluations per output texel of a precompute dispatch (the same decoding of the push constants as exec_op)
-static double dispatch_samples_per_texel(const Op& op) {
-    GPUX_IBLConstants c = {0, 0.0f, 0.0f, 0};
-    bool explicit_c = op.push_size == sizeof(GPUX_IBLConstants);
-    if (explicit_c) memcpy(&c, op.push, sizeof c);
-    else if (op.push_size >= 4) memcpy(&c.mip_level, op.push, 4);
-    if (op.cpipe->kernel == Kernel_Irradiance) return (explicit_c && c.sample_count > 0) ? c.sample_count : 1024;
-    if (c.mip_level == 0) return 4.0;                                       // the copy level: one bilinear fetch, HBM-bound
-    int n = (explicit_c && c.sample_count > 0) ? c.sample_count : 8192;
-    float rough = explicit_c ? c.roughness : reference_roughness(c.mip_level);
-    if (!(rough > 0.0f)) return n;
-    DeviceTable* tab = get_table(0, n, rough, 0);                           // cached; only entries with non-zero weight are kept
-    return tab ? (double)tab->count : (double)n;
+// a clear is ONE fill launch for these texel sizes, at every alignment (k_cube.hip); the staged form of the others synchronises
+static bool fill_texel_ok(uint32_t tb) { return tb == 1 || tb == 2 || tb == 4 || tb == 8 || tb == 16; }
+
+static void exec_clear(GPU_Graph* g, Op& op, size_t& ev_used) {
+    (void)ev_used;                                                             // clears are not timed
+    hipStream_t st = g->cur;
+    TextureImpl* t = op.tex;
+    uint32_t m0 = op.mip == GPU_MIP_LEVEL_ALL ? 0 : op.mip, m1 = op.mip == GPU_MIP_LEVEL_ALL ? t->base.mip_level_count : op.mip + 1;
+    // Levels are back to back in the allocation ([mip][layer][y][x], tight), so GPU_MIP_LEVEL_ALL is ONE fill of the whole
+    // texture instead of one per level: the reference clears bloom_upscale_rt this way every frame (render.cpp:1156; 11 levels at
+    // 1080p = 11 fill kernels of ~5 us each in rocprofv3's trace, a quarter of the post-process tail, before round 3).
+    const bool whole = op.mip == GPU_MIP_LEVEL_ALL;
+    for (uint32_t m = m0; m < (whole ? m0 + 1 : m1); ++m) {
+        size_t bytes = whole ? t->bytes : (size_t)GPUX_TextureMipBytes(&t->base, m);
+        void* p = (char*)t->dev + t->mip_offset[m];
+        if (whole && op.skip_level0) { p = (char*)t->dev + t->mip_offset[1]; bytes = t->bytes - t->mip_offset[1]; }   // fold_blits
+        // build one texel pattern on the host and replicate it (clears are rare: upload a staging row)
+        uint32_t tb = t->texel_bytes;
+        std::vector<uint8_t> texel(tb, 0);
+        if (op.clear_mode == 2 || t->base.format == GPU_Format_R32F) { memcpy(texel.data(), &op.clear[0], 4 < tb ? 4 : tb); }
+        else if (op.clear_mode == 1) { for (uint32_t k = 0; k * 4 < tb && k < 4; ++k) memcpy(texel.data() + 4 * k, &op.cleari[k], 4); }
+        else if (t->base.format == GPU_Format_RGBA32F || t->base.format == GPU_Format_RG32F) { memcpy(texel.data(), op.clear, tb); }
+        else if (t->base.format == GPU_Format_RGBA8UN || t->base.format == GPU_Format_BGRA8UN) {
+            int order[4] = {0, 1, 2, 3};
+            if (t->base.format == GPU_Format_BGRA8UN) { order[0] = 2; order[2] = 0; }
+            for (int k = 0; k < 4; ++k) { float v = op.clear[order[k]]; v = v < 0 ? 0 : (v > 1 ? 1 : v); texel[k] = (uint8_t)(v * 255.0f + 0.5f); }
+        } else {
+            bool zero = op.clear[0] == 0 && op.clear[1] == 0 && op.clear[2] == 0 && op.clear[3] == 0;
+            if (!zero) { gpu_fail("GPU_OpClearColorF: non-zero clears of format %d are not implemented", (int)t->base.format); return; }
+        }
+        if (fill_texel_ok(tb)) {
+            int rc = pbrk_fill_pattern(p, bytes, texel.data(), (int)tb, st);
+            if (rc != PBRK_OK) gpu_fail("clear launch failed (%d)", rc);
+        } else {
+            std::vector<uint8_t> host(bytes);
+            for (size_t o = 0; o < bytes; o += tb) memcpy(host.data() + o, texel.data(), tb);
+            HIP_OK(hipMemcpyAsync(p, host.data(), bytes, hipMemcpyHostToDevice, st));
+            HIP_OK(hipStreamSynchronize(st));      // the staging vector dies at scope exit
+        }
+    }
+    t->bordered_valid = false; t->lut_cells_valid = false;
+}
+
+static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
+    switch (op.kind) {
+    case Op_Dispatch:
+        switch (op.cpipe->kernel) {
+        case Kernel_LightgridSweep: exec_sweep(g, op, ev_used); return;
+        case Kernel_BrdfLut: exec_brdf_lut(g, op, ev_used); return;
+        default: exec_ibl_filter(g, op, ev_used); return;                    // K3, K4a, K4b
+        }
+    case Op_Shade:
+        switch (op.gpipe->kernel) {
+        case Kernel_BloomDown: case Kernel_BloomUp: exec_bloom(g, op, ev_used); return;
+        case Kernel_TaaResolve: exec_taa(g, op, ev_used); return;
+        case Kernel_FinalPost: exec_final(g, op, ev_used); return;
+        default: exec_shade(g, op, ev_used); return;                         // K5, or K16 when the Globals ask for it
+        }
+    case Op_Raster: exec_raster(g, op, ev_used); return;
+    case Op_MipGen: exec_mipgen(g, op, ev_used); return;
+    case Op_Blit: exec_blit(g, op, ev_used); return;
+    case Op_Clear: exec_clear(g, op, ev_used); return;
+    case Op_CopyB2B: case Op_CopyB2T: case Op_CopyT2B: case Op_CopyDecodedT2B: exec_copy(g, op, ev_used); return;
+    }
 }
 
 // ---- hipGraph replay of the per-frame chain --------------------------------------------------------------------------
@@ -2112,23 +2224,13 @@ static bool op_replayable(const Op& op) {
     case Op_Blit: return true;
     case Op_CopyB2B: case Op_CopyB2T: case Op_CopyT2B: case Op_CopyDecodedT2B: return false;          // host pointers may be involved: keep them out of captures
     case Op_Raster: return false;                                             // its draw table is uploaded from pinned staging at submit
-    case Op_Clear: {
-        const uint32_t tb = op.tex->texel_bytes;                              // one fill launch; the staged form of other texel sizes synchronises
-        return tb == 1 || tb == 2 || tb == 4 || tb == 8 || tb == 16;
-    }
+    case Op_Clear: return fill_texel_ok(op.tex->texel_bytes);
     case Op_Shade: {
-        KernelId k = op.gpipe->kernel;
-        if (k == Kernel_TaaResolve || k == Kernel_FinalPost || k == Kernel_BloomDown || k == Kernel_BloomUp) return true;
-        GPU_DescriptorSet* s = op.set;
-        TextureImpl* pre = named_slot(s, "PREFILTERED_ENV_MAP")->tex;
-        if (!pre->bordered_valid || pre->bordered_from > 0) return false;
-        for (int l = 0; l < (int)pre->base.mip_level_count; ++l) if (((int)pre->base.width >> l) <= 512 && !cells_ready(pre, l)) return false;
-        if (op.gpipe->shade_flags & GPUX_Shade_IBL) {
-            TextureImpl* irr = named_slot(s, "TEX_IRRADIANCE_MAP")->tex;
-            if (!irr->bordered_valid || irr->bordered_from > 0 || !cells_ready(irr, 0)) return false;
-            if (!named_slot(s, "BRDF_INTEGRATION_MAP")->tex->lut_cells_valid) return false;
-        }
-        return named_slot(s, "GLOBALS")->buf->pinned_host;
+        if (is_post_kernel(op.gpipe->kernel)) return true;
+        ShadeTwin tw[5];
+        const int n = shade_twins(op.set, op.gpipe->shade_flags, tw);
+        for (int i = 0; i < n; ++i) if (!shade_twin_ready(tw[i])) return false;
+        return named_slot(op.set, "GLOBALS")->buf->pinned_host;
     }
     }
     return false;
@@ -2136,7 +2238,7 @@ static bool op_replayable(const Op& op) {
 
 // Graph-level eligibility.  op_replayable() looks at the sampler twins as they are NOW; an earlier op of the same graph that writes
 // one of the maps a later shade op samples (Op_Clear / Op_MipGen / Op_Blit / a storage-image dispatch drop the apron, cells and LUT
-// twins in exec_op) would have that shade op rebuild its twins -- allocation + synchronisation -- inside the capture.
+// twins when they execute) would have that shade op rebuild its twins -- allocation + synchronisation -- inside the capture.
 // Such a graph takes the plain path: the textures written by the ops seen so far are tracked and compared with what each shade
 // op samples.
 static bool graph_replayable(GPU_Graph* g) {
@@ -2149,12 +2251,10 @@ static bool graph_replayable(GPU_Graph* g) {
         case Op_Blit: if (op.tex2) written.push_back(op.tex2); break;          // tex = source, tex2 = destination
         case Op_Dispatch: { Slot* o = named_slot(op.set, "IMG0"); if (o && o->tex) written.push_back(o->tex); break; }
         case Op_Shade: {
-            KernelId k = op.gpipe->kernel;
-            if (k == Kernel_TaaResolve || k == Kernel_FinalPost || k == Kernel_BloomDown || k == Kernel_BloomUp) break;
-            for (const char* name : {"PREFILTERED_ENV_MAP", "TEX_IRRADIANCE_MAP", "BRDF_INTEGRATION_MAP"}) {
-                Slot* sl = named_slot(op.set, name);
-                if (sl && sl->tex && is_written(sl->tex)) return false;
-            }
+            if (is_post_kernel(op.gpipe->kernel)) break;
+            ShadeTwin tw[5];                                                   // all three maps, whatever the op's flags: a bound map counts even when it is not sampled
+            const int n = shade_twins(op.set, GPUX_Shade_IBL, tw);
+            for (int i = 0; i < n; ++i) if (is_written(tw[i].tex)) return false;
             break;
         }
         default: break;
@@ -2176,13 +2276,19 @@ GPU_API void GPUX_GraphReplayStats(GPU_Graph* g, uint64_t* launches, uint64_t* u
 // upsample can add onto the blit's SOURCE and write the sum to the target, and the copy (33 MB of traffic, one launch per 1080p frame)
 // need not exist.  Folded only when the ops between the two provably touch neither subresource: bloom draws with other sources and
 // targets; anything else in between keeps the blit.  Same values, same additions: the target's bits do not change.
+// A submit-time setting: what its GPUX_Set* call stored in `cached`, else the environment's value or `dflt`, read once on first use
+static int env_setting(int& cached, const char* name, int dflt) {
+    if (cached < 0) { const char* e = getenv(name); cached = e ? atoi(e) : dflt; }
+    return cached;
+}
+static bool overlap_enabled() { return env_setting(G.overlap, "PBR_GRAPH_OVERLAP", 1) != 0; }
+static bool replay_enabled() { return env_setting(G.replay, "PBR_GRAPH_REPLAY", 0) != 0; }
+
 static uint64_t g_folded_blits = 0;
 GPU_API uint64_t GPUX_FoldedBlitCount(void) { return g_folded_blits; }
 static void fold_blits(GPU_Graph* g) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("PBR_GRAPH_FOLD"); on = e ? atoi(e) : 1; }
     for (Op& op : g->ops) { op.folded = false; op.blend_tex = nullptr; op.skip_level0 = false; }
-    if (!on) return;
+    if (!env_setting(G.fold, "PBR_GRAPH_FOLD", 1)) return;
     for (size_t i = 0; i < g->ops.size(); ++i) {
         Op& b = g->ops[i];
         // a clear of ALL levels directly followed by a whole-level copy onto level 0 (render.cpp:1156-1163): level 0 -- three quarters of
@@ -2195,7 +2301,7 @@ static void fold_blits(GPU_Graph* g) {
             b.tex->base.format != GPU_Format_RGBA16F || b.tex == b.tex2) continue;
         for (size_t j = i + 1; j < g->ops.size(); ++j) {
             Op& d = g->ops[j];
-            if (d.kind != Op_Shade || !(d.gpipe->kernel == Kernel_BloomDown || d.gpipe->kernel == Kernel_BloomUp)) break;
+            if (d.kind != Op_Shade || !is_bloom_kernel(d.gpipe->kernel)) break;
             TextureImpl* target = (TextureImpl*)d.pass->targets[0].texture;
             Slot* in = named_slot(d.set, "TEX0");
             if (!in || !in->tex) break;
@@ -2235,11 +2341,164 @@ static bool op_access(const Op& op, std::vector<TextureImpl*>& r, std::vector<Te
     default: return false;
     }
 }
-static int g_overlap_on = -1;                   // -1: PBR_GRAPH_OVERLAP or the default (1)
 static uint64_t g_overlapped_submits = 0;
-GPU_API void GPUX_SetGraphOverlap(int on) { g_overlap_on = on; }
+GPU_API void GPUX_SetGraphOverlap(int on) { G.overlap = on; }
 GPU_API uint64_t GPUX_OverlappedSubmitCount(void) { return g_overlapped_submits; }
 static bool contains(const std::vector<TextureImpl*>& v, const TextureImpl* t) { for (const TextureImpl* x : v) if (x == t) return true; return false; }
+
+// ---- GPU_GraphSubmit, step by step ----
+// Submission order is execution order, as on the reference's single queue (vkQueueSubmit, gpu_vulkan.c:2481-2530): a graph
+// submitted while another one is still in flight (main.cpp:49-51, 91-99 keeps two) starts after everything enqueued so far on
+// the previous graph's stream -- its kernels, lazily built sampler twins, and any exchange the caller appended through
+// GPUX_GraphStream.  Side streams fork from g->stream, so they inherit the dependency.
+// Frames in flight (main.cpp:49-51, 91-99 keeps two graphs): the tail of a frame's graph -- its bloom chain, a dozen small dependent
+// launches that leave most of the chip idle -- touches only the bloom targets, the TAA result it reads and the backbuffer.  The next
+// graph's leading ops (light-grid sweep, shade, TAA resolve) touch none of those: they wait for the event in front of the previous
+// graph's first bloom draw instead of for its end, and run beside that tail; the first op that shares a texture with the tail (and
+// everything behind it) waits for the end as before.  Whole-texture granularity, every texture bound to an op counts; an op this
+// analysis does not follow ends the overlap.  PBR_GRAPH_OVERLAP=0: every graph waits for all of its predecessor.
+struct OrderPoint {
+    GPU_Graph* prev = nullptr;       // set: ops [0, before) wait for prev's mid event only; the wait for its end is still to be enqueued
+    size_t before = 0;               // index of the first op that must wait for the previous graph's end
+};
+static OrderPoint order_after_previous(GPU_Graph* g) {
+    OrderPoint o;
+    GPU_Graph* prev = G.last_submitted;
+    G.last_submitted = g;
+    if (!env_setting(G.order, "PBR_GRAPH_ORDER", 1) || !prev || prev == g) return o;
+    if (!prev->order_ev) HIP_OK(hipEventCreateWithFlags(&prev->order_ev, hipEventDisableTiming));
+    HIP_OK(hipEventRecord(prev->order_ev, prev->stream));
+    if (overlap_enabled() && prev->mid_recorded && !replay_enabled()) {
+        std::vector<TextureImpl*> r, w;
+        for (; o.before < g->ops.size(); ++o.before) {
+            r.clear(); w.clear();
+            if (!op_access(g->ops[o.before], r, w)) break;
+            bool clash = false;
+            for (TextureImpl* t : w) clash |= contains(prev->tail_reads, t) || contains(prev->tail_writes, t);
+            for (TextureImpl* t : r) clash |= contains(prev->tail_writes, t);
+            if (clash) break;
+        }
+    }
+    if (o.before > 0) { HIP_OK(hipStreamWaitEvent(g->stream, prev->mid_ev, 0)); o.prev = prev; ++g_overlapped_submits; }
+    else HIP_OK(hipStreamWaitEvent(g->stream, prev->order_ev, 0));
+    return o;
+}
+
+// This graph's own head / tail split: the tail starts at the first bloom draw.  Returns its index (the op count: no split) and leaves
+// what the tail touches in g->tail_reads / g->tail_writes for the next submission's order_after_previous.
+static size_t split_head_tail(GPU_Graph* g, bool overlap_on) {
+    size_t mid_idx = g->ops.size();
+    for (size_t i = 0; i < g->ops.size(); ++i)
+        if (g->ops[i].kind == Op_Shade && is_bloom_kernel(g->ops[i].gpipe->kernel)) { mid_idx = i; break; }
+    g->mid_recorded = false; g->tail_reads.clear(); g->tail_writes.clear();
+    if (!overlap_on || mid_idx == 0) return g->ops.size();
+    bool known = true;
+    for (size_t i = mid_idx; i < g->ops.size() && known; ++i) known = op_access(g->ops[i], g->tail_reads, g->tail_writes);
+    if (!known) { mid_idx = g->ops.size(); g->tail_reads.clear(); g->tail_writes.clear(); }
+    return mid_idx;
+}
+
+// Row-ranged precompute dispatches (the work units of a partitioned job) are too small to keep 256 CUs x 8 waves busy one
+// at a time: consecutive ones whose outputs are disjoint and which do not read each other's output go round-robin onto
+// side streams, fenced by a fork event before the first and join events after the last.  Everything else stays in order.
+struct TileRegion {
+    struct Wr { TextureImpl* t; uint32_t mip, f0, f1, r0, r1; };
+    GPU_Graph* g;
+    int n_side;
+    std::vector<Wr> writes; std::vector<TextureImpl*> reads;       // what the dispatches of the open region write and read
+    bool open = false; size_t rr = 0;
+
+    explicit TileRegion(GPU_Graph* graph) : g(graph) {
+        env_setting(G.tile_streams, "PBR_TILE_STREAMS", 4);
+        if (G.tile_streams > 16) G.tile_streams = 16;
+        n_side = G.tile_streams;
+    }
+    // join: the main stream goes on after everything the side streams hold
+    void close() {
+        if (!open) return;
+        for (hipStream_t s : g->side) { hipEvent_t e = next_sync_event(g); HIP_OK(hipEventRecord(e, s)); HIP_OK(hipStreamWaitEvent(g->stream, e, 0)); }
+        writes.clear(); reads.clear(); open = false; g->cur = g->stream;
+    }
+    // is the op a dispatch that may run beside its neighbours?
+    bool wants_side_stream(const Op& op, Slot*& out, Slot*& env) const {
+        out = env = nullptr;
+        if (!(n_side >= 2 && op.kind == Op_Dispatch && op.rows_explicit && (op.cpipe->kernel == Kernel_Prefilter || op.cpipe->kernel == Kernel_Irradiance))) return false;
+        out = named_slot(op.set, "OUTPUT");
+        env = named_slot(op.set, "TEX_ENV_CUBE");
+        bool tile = true;
+        // a launch of several full-chip rounds (2048 resident workgroups x 256 texels x 8192 samples each) gains nothing from
+        // company and keeps its own event timing clean: only smaller ones are overlapped
+        // (a whole level fills the chip by itself from ~1e9 evaluations on; shares of a level -- a rank's tiles -- come in
+        // groups with ragged tails and gain up to the bound above)
+        if (out && out->tex) {
+            uint32_t size = mip_dim(out->tex->base.width, out->mip);
+            double evals = (double)(op.face1 - op.face0) * (op.row1 - op.row0) * size * dispatch_samples_per_texel(op);
+            bool whole = op.face0 == 0 && op.face1 == out->tex->base.layer_count && op.row0 == 0 && op.row1 == size;
+            if (evals >= (whole ? 1.0e9 : 2.0e6 * 8192.0)) tile = false;
+            // fork + join cost ~0.25 ms of cross-stream signalling: whole small levels alone (the tail of a single-GPU job) do not
+            // repay it -- they join a region that shares of a level have opened, but do not open one
+            if (whole && !open) tile = false;
+        }
+        return tile && out && env && out->tex && env->tex;
+    }
+    // Picks the stream the op launches on (g->cur): a side stream of the region (true) -- opening one, or closing it first when the op
+    // clashes with what the region holds -- or, behind a closed region, the main stream (false).  The caller sets g->cur back.
+    bool place(const Op& op) {
+        Slot* out; Slot* env;
+        if (!wants_side_stream(op, out, env)) { close(); return false; }
+        Wr w = {out->tex, out->mip, op.face0, op.face1, op.row0, op.row1};
+        bool clash = w.t == env->tex;
+        for (const Wr& o : writes) {
+            if (o.t == env->tex) clash = true;
+            if (o.t == w.t && o.mip == w.mip && o.f0 < w.f1 && w.f0 < o.f1 && o.r0 < w.r1 && w.r0 < o.r1) clash = true;
+        }
+        for (TextureImpl* r : reads) if (r == w.t) clash = true;
+        if (clash) close();
+        if (w.t == env->tex) return false;                                 // reads what it writes: never overlapped
+        if (!open) {                                                       // fork
+            while ((int)g->side.size() > n_side) { (void)hipStreamSynchronize(g->side.back()); (void)hipStreamDestroy(g->side.back()); g->side.pop_back(); }
+            while ((int)g->side.size() < n_side) { hipStream_t s; HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); g->side.push_back(s); }
+            hipEvent_t e = next_sync_event(g);
+            HIP_OK(hipEventRecord(e, g->stream));
+            for (hipStream_t s : g->side) HIP_OK(hipStreamWaitEvent(s, e, 0));
+            open = true;
+        }
+        writes.push_back(w); reads.push_back(env->tex);
+        g->cur = g->side[rr++ % g->side.size()];
+        return true;
+    }
+};
+
+// hipGraph replay: is this submission captured?  (G.timing and capture exclude each other, so the span events stay outside.)
+static bool begin_capture(GPU_Graph* g) {
+    if (!replay_enabled() || G.timing || g->replay_broken || g->ops.empty() || !graph_replayable(g)) return false;
+    if (hipStreamBeginCapture(g->stream, hipStreamCaptureModeRelaxed) == hipSuccess) return true;
+    (void)hipGetLastError(); g->replay_broken = true;
+    return false;
+}
+// Ends the capture; updates the executable graph kept from the previous submission or instantiates a new one, and launches it.
+static void finish_capture(GPU_Graph* g, size_t& ev_used) {
+    hipGraph_t cg = nullptr;
+    bool ok = hipStreamEndCapture(g->stream, &cg) == hipSuccess && cg;
+    if (g->exec && g->exec_sig != g->launch_sig) { (void)hipGraphExecDestroy(g->exec); g->exec = nullptr; }   // another kernel behind a node: never "updated"
+    if (ok && g->exec) {
+        hipGraphNode_t bad = nullptr; hipGraphExecUpdateResult res;
+        if (hipGraphExecUpdate(g->exec, cg, &bad, &res) == hipSuccess) ++g->replay_updates;
+        else { (void)hipGetLastError(); (void)hipGraphExecDestroy(g->exec); g->exec = nullptr; }
+    }
+    if (ok && !g->exec) {
+        if (hipGraphInstantiate(&g->exec, cg, nullptr, nullptr, 0) == hipSuccess) { ++g->replay_instantiations; g->exec_sig = g->launch_sig; }
+        else { (void)hipGetLastError(); g->exec = nullptr; ok = false; }
+    }
+    if (ok && hipGraphLaunch(g->exec, g->stream) == hipSuccess) ++g->replay_launches; else ok = false;
+    if (cg) (void)hipGraphDestroy(cg);
+    if (ok) return;
+    // nothing of the captured work has run: take the plain path for this and every later submission of this graph
+    (void)hipGetLastError();
+    g->replay_broken = true;
+    if (g->exec) { (void)hipGraphExecDestroy(g->exec); g->exec = nullptr; }
+    for (Op& op : g->ops) exec_op(g, op, ev_used);
+}
 
 GPU_API void GPU_GraphSubmit(GPU_Graph* g) {
     GPU_REQUIRE_V(g && !g->submitted, "GPU_GraphSubmit: graph is NULL or already submitted");
@@ -2250,159 +2509,39 @@ GPU_API void GPU_GraphSubmit(GPU_Graph* g) {
     g->sync_used = 0;
     g->launch_sig.clear();
     g->cur = g->stream;
-    // Submission order is execution order, as on the reference's single queue (vkQueueSubmit, gpu_vulkan.c:2481-2530): a graph
-    // submitted while another one is still in flight (main.cpp:49-51, 91-99 keeps two) starts after everything enqueued so far on
-    // the previous graph's stream -- its kernels, lazily built sampler twins, and any exchange the caller appended through
-    // GPUX_GraphStream.  Side streams fork from g->stream, so they inherit the dependency.
-    static int order_on = -1;                                     // PBR_GRAPH_ORDER=0: diagnostic only (shows that the ordering test can fail)
-    if (order_on < 0) { const char* e = getenv("PBR_GRAPH_ORDER"); order_on = e ? atoi(e) : 1; }
     fold_blits(g);
-    // Frames in flight (main.cpp:49-51, 91-99 keeps two graphs): the tail of a frame's graph -- its bloom chain, a dozen small dependent
-    // launches that leave most of the chip idle -- touches only the bloom targets, the TAA result it reads and the backbuffer.  The next
-    // graph's leading ops (light-grid sweep, shade, TAA resolve) touch none of those: they wait for the event in front of the previous
-    // graph's first bloom draw instead of for its end, and run beside that tail; the first op that shares a texture with the tail (and
-    // everything behind it) waits for the end as before.  Whole-texture granularity, every texture bound to an op counts; an op this
-    // analysis does not follow ends the overlap.  PBR_GRAPH_OVERLAP=0: every graph waits for all of its predecessor.
-    if (g_overlap_on < 0) { const char* e = getenv("PBR_GRAPH_OVERLAP"); g_overlap_on = e ? atoi(e) : 1; }
-    const int overlap_on = g_overlap_on;
-    if (G.replay < 0) { const char* e = getenv("PBR_GRAPH_REPLAY"); G.replay = e ? (atoi(e) != 0) : 0; }
-    size_t order_before = 0;                                      // index of the first op that must wait for the previous graph's end
-    GPU_Graph* order_prev = nullptr;
-    if (order_on && G.last_submitted && G.last_submitted != g) {
-        GPU_Graph* prev = G.last_submitted;
-        if (!prev->order_ev) HIP_OK(hipEventCreateWithFlags(&prev->order_ev, hipEventDisableTiming));
-        HIP_OK(hipEventRecord(prev->order_ev, prev->stream));
-        if (overlap_on && prev->mid_recorded && G.replay != 1) {
-            std::vector<TextureImpl*> r, w;
-            for (; order_before < g->ops.size(); ++order_before) {
-                r.clear(); w.clear();
-                if (!op_access(g->ops[order_before], r, w)) break;
-                bool clash = false;
-                for (TextureImpl* t : w) clash |= contains(prev->tail_reads, t) || contains(prev->tail_writes, t);
-                for (TextureImpl* t : r) clash |= contains(prev->tail_writes, t);
-                if (clash) break;
-            }
-        }
-        if (order_before > 0) { HIP_OK(hipStreamWaitEvent(g->stream, prev->mid_ev, 0)); order_prev = prev; ++g_overlapped_submits; }
-        else HIP_OK(hipStreamWaitEvent(g->stream, prev->order_ev, 0));
-    }
-    G.last_submitted = g;
-    // this graph's own head / tail split: the tail starts at the first bloom draw
-    size_t mid_idx = g->ops.size();
-    for (size_t i = 0; i < g->ops.size(); ++i)
-        if (g->ops[i].kind == Op_Shade && (g->ops[i].gpipe->kernel == Kernel_BloomDown || g->ops[i].gpipe->kernel == Kernel_BloomUp)) { mid_idx = i; break; }
-    g->mid_recorded = false; g->tail_reads.clear(); g->tail_writes.clear();
-    if (overlap_on && mid_idx > 0 && mid_idx < g->ops.size()) {
-        bool known = true;
-        for (size_t i = mid_idx; i < g->ops.size() && known; ++i) known = op_access(g->ops[i], g->tail_reads, g->tail_writes);
-        if (!known) { mid_idx = g->ops.size(); g->tail_reads.clear(); g->tail_writes.clear(); }
-    } else mid_idx = g->ops.size();
+    OrderPoint order = order_after_previous(g);
+    const size_t mid_idx = split_head_tail(g, overlap_enabled());
     // the chain property the next submission relies on: this graph's mid event (or, without one, its end) implies the END of the graph
     // before it -- so the wait for that end never comes later than the mid event
-    if (order_before > mid_idx) order_before = mid_idx;
-    size_t op_index = 0;
-    if (G.replay < 0) { const char* e = getenv("PBR_GRAPH_REPLAY"); G.replay = e ? (atoi(e) != 0) : 0; }
-    bool capture = G.replay == 1 && !G.timing && !g->replay_broken && !g->ops.empty();
-    if (capture) capture = graph_replayable(g);
+    if (order.before > mid_idx) order.before = mid_idx;
     g->span_recorded = false;
     if (G.timing) {
         if (!g->span_a) { HIP_OK(hipEventCreate(&g->span_a)); HIP_OK(hipEventCreate(&g->span_b)); }
         HIP_OK(hipEventRecord(g->span_a, g->stream));
     }
-    if (capture && hipStreamBeginCapture(g->stream, hipStreamCaptureModeRelaxed) != hipSuccess) { (void)hipGetLastError(); capture = false; g->replay_broken = true; }
-    // Row-ranged precompute dispatches (the work units of a partitioned job) are too small to keep 256 CUs x 8 waves busy one
-    // at a time: consecutive ones whose outputs are disjoint and which do not read each other's output go round-robin onto
-    // side streams, fenced by a fork event before the first and join events after the last.  Everything else stays in order.
-    if (G.tile_streams < 0) { const char* e = getenv("PBR_TILE_STREAMS"); G.tile_streams = e ? atoi(e) : 4; }
-    if (G.tile_streams > 16) G.tile_streams = 16;
-    const int n_side = G.tile_streams;
-    struct Wr { TextureImpl* t; uint32_t mip, f0, f1, r0, r1; };
-    std::vector<Wr> writes; std::vector<TextureImpl*> reads;
-    bool open = false; size_t rr = 0;
-    auto close_region = [&] {
-        if (!open) return;
-        for (hipStream_t s : g->side) { hipEvent_t e = next_sync_event(g); HIP_OK(hipEventRecord(e, s)); HIP_OK(hipStreamWaitEvent(g->stream, e, 0)); }
-        writes.clear(); reads.clear(); open = false; g->cur = g->stream;
-    };
-    for (Op& op : g->ops) {
-        if (order_prev && op_index == order_before) {                  // from here on: after everything the previous graph enqueued
-            close_region();
-            HIP_OK(hipStreamWaitEvent(g->stream, order_prev->order_ev, 0));
-            order_prev = nullptr;
+    const bool capture = begin_capture(g);
+    TileRegion region(g);
+    for (size_t i = 0; i < g->ops.size(); ++i) {
+        if (order.prev && i == order.before) {                         // from here on: after everything the previous graph enqueued
+            region.close();
+            HIP_OK(hipStreamWaitEvent(g->stream, order.prev->order_ev, 0));
+            order.prev = nullptr;
         }
-        if (op_index == mid_idx && !capture) {                         // head done: the next graph's independent ops may start
-            close_region();
+        if (i == mid_idx && !capture) {                                // head done: the next graph's independent ops may start
+            region.close();
             if (!g->mid_ev) HIP_OK(hipEventCreateWithFlags(&g->mid_ev, hipEventDisableTiming));
             HIP_OK(hipEventRecord(g->mid_ev, g->stream));
             g->mid_recorded = true;
         }
-        ++op_index;
-        bool tile = n_side >= 2 && op.kind == Op_Dispatch && op.rows_explicit &&
-                    (op.cpipe->kernel == Kernel_Prefilter || op.cpipe->kernel == Kernel_Irradiance);
-        Slot* out = tile ? named_slot(op.set, "OUTPUT") : nullptr;
-        Slot* env = tile ? named_slot(op.set, "TEX_ENV_CUBE") : nullptr;
-        // a launch of several full-chip rounds (2048 resident workgroups x 256 texels x 8192 samples each) gains nothing from
-        // company and keeps its own event timing clean: only smaller ones are overlapped
-        // (a whole level fills the chip by itself from ~1e9 evaluations on; shares of a level -- a rank's tiles -- come in
-        // groups with ragged tails and gain up to the bound above)
-        if (tile && out && out->tex) {
-            uint32_t size = mip_dim(out->tex->base.width, out->mip);
-            double evals = (double)(op.face1 - op.face0) * (op.row1 - op.row0) * size * dispatch_samples_per_texel(op);
-            bool whole = op.face0 == 0 && op.face1 == out->tex->base.layer_count && op.row0 == 0 && op.row1 == size;
-            if (evals >= (whole ? 1.0e9 : 2.0e6 * 8192.0)) tile = false;
-            // fork + join cost ~0.25 ms of cross-stream signalling: whole small levels alone (the tail of a single-GPU job) do not
-            // repay it -- they join a region that shares of a level have opened, but do not open one
-            if (whole && !open) tile = false;
-        }
-        if (!tile || !out || !env || !out->tex || !env->tex) { close_region(); exec_op(g, op, ev_used); continue; }
-        Wr w = {out->tex, out->mip, op.face0, op.face1, op.row0, op.row1};
-        bool clash = w.t == env->tex;
-        for (const Wr& o : writes) {
-            if (o.t == env->tex) clash = true;
-            if (o.t == w.t && o.mip == w.mip && o.f0 < w.f1 && w.f0 < o.f1 && o.r0 < w.r1 && w.r0 < o.r1) clash = true;
-        }
-        for (TextureImpl* r : reads) if (r == w.t) clash = true;
-        if (clash) close_region();
-        if (w.t == env->tex) { exec_op(g, op, ev_used); continue; }        // reads what it writes: never overlapped
-        if (!open) {
-            while ((int)g->side.size() > n_side) { (void)hipStreamSynchronize(g->side.back()); (void)hipStreamDestroy(g->side.back()); g->side.pop_back(); }
-            while ((int)g->side.size() < n_side) { hipStream_t s; HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); g->side.push_back(s); }
-            hipEvent_t e = next_sync_event(g);
-            HIP_OK(hipEventRecord(e, g->stream));
-            for (hipStream_t s : g->side) HIP_OK(hipStreamWaitEvent(s, e, 0));
-            open = true;
-        }
-        writes.push_back(w); reads.push_back(env->tex);
-        g->cur = g->side[rr++ % g->side.size()];
-        exec_op(g, op, ev_used);
+        region.place(g->ops[i]);
+        exec_op(g, g->ops[i], ev_used);
         g->cur = g->stream;
     }
-    close_region();
-    if (order_prev) { HIP_OK(hipStreamWaitEvent(g->stream, order_prev->order_ev, 0)); order_prev = nullptr; }   // every op was independent: still end after it
+    region.close();
+    if (order.prev) HIP_OK(hipStreamWaitEvent(g->stream, order.prev->order_ev, 0));   // every op was independent: still end after it
     if (G.timing) { HIP_OK(hipEventRecord(g->span_b, g->stream)); g->span_recorded = true; }
-    if (capture) {
-        hipGraph_t cg = nullptr;
-        bool ok = hipStreamEndCapture(g->stream, &cg) == hipSuccess && cg;
-        if (g->exec && g->exec_sig != g->launch_sig) { (void)hipGraphExecDestroy(g->exec); g->exec = nullptr; }   // another kernel behind a node: never "updated"
-        if (ok && g->exec) {
-            hipGraphNode_t bad = nullptr; hipGraphExecUpdateResult res;
-            if (hipGraphExecUpdate(g->exec, cg, &bad, &res) == hipSuccess) ++g->replay_updates;
-            else { (void)hipGetLastError(); (void)hipGraphExecDestroy(g->exec); g->exec = nullptr; }
-        }
-        if (ok && !g->exec) {
-            if (hipGraphInstantiate(&g->exec, cg, nullptr, nullptr, 0) == hipSuccess) { ++g->replay_instantiations; g->exec_sig = g->launch_sig; }
-            else { (void)hipGetLastError(); g->exec = nullptr; ok = false; }
-        }
-        if (ok && hipGraphLaunch(g->exec, g->stream) == hipSuccess) ++g->replay_launches; else ok = false;
-        if (cg) (void)hipGraphDestroy(cg);
-        if (!ok) {
-            // nothing of the captured work has run: take the plain path for this and every later submission of this graph
-            (void)hipGetLastError();
-            g->replay_broken = true;
-            if (g->exec) { (void)hipGraphExecDestroy(g->exec); g->exec = nullptr; }
-            for (Op& op : g->ops) exec_op(g, op, ev_used);
-        }
-    }
+    if (capture) finish_capture(g, ev_used);
     g->submitted = true;
 }
 
