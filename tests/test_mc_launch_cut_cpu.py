@@ -194,7 +194,7 @@ def test_cut_on_the_boundary_of_the_inequality(L, tables, rough):
 # ---- no-op chain ------------------------------------------------------------------------------
 
 def tap_weights(wgt, a, b):
-    """The kernel's six roundings (region_sample): returns (w00, w10, w01, w11)."""
+    """The kernel's six roundings (tap_accumulate): returns (w00, w10, w01, w11)."""
     wa = rnd(mul(wgt, a)); w11 = rnd(mul(wa, b)); w10 = rnd(wa - w11)
     wt = rnd(wgt - wa); w01 = rnd(mul(wt, b)); w00 = rnd(wt - w01)
     assert 0 <= min(w00, w10, w01, w11) and max(w00, w10, w01, w11) <= wgt

@@ -82,6 +82,7 @@
 
 #include <stdlib.h>
 #include <mutex>
+#include <type_traits>
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 // The sample table is read-only for the whole launch: a pointer into the constant address space makes every wave-uniform
@@ -145,88 +146,49 @@ __device__ __forceinline__ void face_coords(int f, float x, float y, float z, fl
     }
 }
 
-// One sample of a pass: accumulate it in the lanes whose direction falls into the staged region.
-// CLS = major axis of the region's face (0: x, 1: y, 2: z): the hardware's tie rule (z >= y >= x) in two comparisons.
-// ACC = false: the count-only body of an absorbed word -- the same frame transform, predicates, ballots and pair count, no taps.
-template <int RS, bool SUB, int CLS, bool ACC = true>
-__device__ __forceinline__ void region_sample(const v4f e, unsigned lds_base, f3 Pb, f3 Pt, f3 Pr, float half_n, float off,
-                                              float ulo, float uhi, float vlo, float vhi,
-                                              float& ar, float& ag, float& ab, unsigned& cnt) {
-    // (sc, tc, ma) = permuted frame * local direction, same FMA order as the direct kernel's L
-    const float sc = fmaf(e.x, Pb.x, fmaf(e.y, Pt.x, e.z * Pr.x));
-    const float tc = fmaf(e.x, Pb.y, fmaf(e.y, Pt.y, e.z * Pr.y));
-    const float ma = fmaf(e.x, Pb.z, fmaf(e.y, Pt.z, e.z * Pr.z));
-    // in-face test with the hardware's tie rule; each comparison's lane mask is taken by its own ballot (the compiler folds
-    // a ballot of ONE comparison into the v_cmp's SGPR result, not a ballot of their conjunction)
-    bool c1, c2;
+// What a sample body needs of the staged region: set up once per (region, pass) in k_mc_region's visit, wave-uniform but for the frame.
+struct RegionView {
+    unsigned lds_base;          // LDS byte address of the staged region less its origin's: taps are addressed with face coordinates
+    f3 Pb, Pt, Pr;              // the texel's frame under the face's signed permutation: rows give (sc, tc, ma) directly
+    float half_n, off;          // bordered tap coordinates u = sc / ma * half_n + off, in [0.5, n + 0.5]
+    float ulo, uhi, vlo, vhi;   // the region's cells (SUB): [ulo, uhi) x [vlo, vhi)
+};
+
+// (sc, tc, ma) = permuted frame * local direction, same FMA order as the direct kernel's L
+__device__ __forceinline__ void to_face(const v4f e, const RegionView& V, float& sc, float& tc, float& ma) {
+    sc = fmaf(e.x, V.Pb.x, fmaf(e.y, V.Pt.x, e.z * V.Pr.x));
+    tc = fmaf(e.x, V.Pb.y, fmaf(e.y, V.Pt.y, e.z * V.Pr.y));
+    ma = fmaf(e.x, V.Pb.z, fmaf(e.y, V.Pt.z, e.z * V.Pr.z));
+}
+
+// In-face test.  CLS = major axis of the region's face (0: x, 1: y, 2: z): the hardware's tie rule (z >= y >= x) in two comparisons.
+template <int CLS>
+__device__ __forceinline__ void on_face(float sc, float tc, float ma, bool& c1, bool& c2) {
     if (CLS == 0) { c1 = ma > fabsf(sc); c2 = ma > fabsf(tc); }
     else if (CLS == 1) { c1 = ma >= fabsf(sc); c2 = ma > fabsf(tc); }
     else { c1 = ma >= fabsf(sc); c2 = ma >= fabsf(tc); }
-    unsigned long long inm = __builtin_amdgcn_ballot_w64(c1) & __builtin_amdgcn_ballot_w64(c2);
-    // Lanes whose direction is not on this face (or, SUB, not in this region's cells) sit the sample out under the exec
-    // mask; a wave none of whose lanes is on the face skips the rest.  The (lane, sample) pairs taken are counted per wave
-    // with scalar instructions.
-    if (inm == 0) return;
-    if (!ACC && !SUB) { cnt += (unsigned)__builtin_popcountll(inm); return; }
-    bool in = c1 && c2;
-    const float h = __builtin_amdgcn_rcpf(ma) * half_n;
-    const float u = fmaf(sc, h, off), v = fmaf(tc, h, off);                   // bordered tap coordinates, [0.5, n + 0.5]
-    const int il = (int)u, jl = (int)v;
-    if (SUB) {
-        // floor(u) in [ox, ox + rcx) <=> u in [ox, ox + rcx) (integer bounds): four float comparisons, no integer arithmetic
-        const bool c3 = u >= ulo, c4 = u < uhi, c5 = v >= vlo, c6 = v < vhi;
-        inm &= __builtin_amdgcn_ballot_w64(c3) & __builtin_amdgcn_ballot_w64(c4) & __builtin_amdgcn_ballot_w64(c5) & __builtin_amdgcn_ballot_w64(c6);
-        in = in && c3 && c4 && c5 && c6;
-    }
-    cnt += (unsigned)__builtin_popcountll(inm);
-    if (ACC && in) {
-        const float a = __builtin_amdgcn_fractf(u), b = __builtin_amdgcn_fractf(v);
-        // whole 16-byte texels: ds_read_b128 runs at 256 B/clk/CU, the 12-byte form the compiler would pick at 96 (the
-        // empty asm keeps the fourth component alive); LDS byte address = jl * row + (il << 4) + base (the region's origin
-        // is folded into the base) in one shift-add and one 24-bit multiply-add
-        unsigned t16, addr;
-        asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(t16) : "v"(il), "s"(lds_base));
-        asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(addr) : "v"(jl), "s"(RS * 16), "v"(t16));
-        lds_v4f_p tp = (lds_v4f_p)(unsigned long long)addr;
-        v4f q00 = tp[0], q10 = tp[1], q01 = tp[RS], q11 = tp[RS + 1];
-        asm("" : "+v"(q00)); asm("" : "+v"(q10)); asm("" : "+v"(q01)); asm("" : "+v"(q11));
-        // weights of the four taps with the sample weight folded in
-        const float wgt = e.w;
-        const float wa = wgt * a;
-        const float w11 = wa * b;
-        const float w10 = wa - w11;
-        const float wt = wgt - wa;
-        const float w01 = wt * b;
-        const float w00 = wt - w01;
-        ar = fmaf(w11, q11.x, fmaf(w01, q01.x, fmaf(w10, q10.x, fmaf(w00, q00.x, ar))));
-        ag = fmaf(w11, q11.y, fmaf(w01, q01.y, fmaf(w10, q10.y, fmaf(w00, q00.y, ag))));
-        ab = fmaf(w11, q11.z, fmaf(w01, q01.z, fmaf(w10, q10.z, fmaf(w00, q00.z, ab))));
-    }
 }
 
-// The same sample when binning has proved that EVERY texel of the tile taps this region of this face: all 64 lanes are in, so
-// the tests, ballots and the exec mask fall away; u, v, taps, weights and the FMA order are those of region_sample, bit for bit.
+// The bilinear tap at bordered coordinates (u, v) of the staged region, weight w folded in: THE chain of twelve FMAs every lemma of
+// this file speaks about (absorbed words, the launch cut, "a row shard equals the full dispatch"); every sample body ends in it.
 template <int RS>
-__device__ __forceinline__ void certain_sample(const v4f e, unsigned lds_base, f3 Pb, f3 Pt, f3 Pr, float half_n, float off,
-                                               float& ar, float& ag, float& ab) {
-    const float sc = fmaf(e.x, Pb.x, fmaf(e.y, Pt.x, e.z * Pr.x));
-    const float tc = fmaf(e.x, Pb.y, fmaf(e.y, Pt.y, e.z * Pr.y));
-    const float ma = fmaf(e.x, Pb.z, fmaf(e.y, Pt.z, e.z * Pr.z));
-    const float h = __builtin_amdgcn_rcpf(ma) * half_n;
-    const float u = fmaf(sc, h, off), v = fmaf(tc, h, off);
+__device__ __forceinline__ void tap_accumulate(float w, float u, float v, unsigned lds_base, float& ar, float& ag, float& ab) {
     const int il = (int)u, jl = (int)v;
     const float a = __builtin_amdgcn_fractf(u), b = __builtin_amdgcn_fractf(v);
+    // whole 16-byte texels: ds_read_b128 runs at 256 B/clk/CU, the 12-byte form the compiler would pick at 96 (the
+    // empty asm keeps the fourth component alive); LDS byte address = jl * row + (il << 4) + base (the region's origin
+    // is folded into the base) in one shift-add and one 24-bit multiply-add
     unsigned t16, addr;
     asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(t16) : "v"(il), "s"(lds_base));
     asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(addr) : "v"(jl), "s"(RS * 16), "v"(t16));
     lds_v4f_p tp = (lds_v4f_p)(unsigned long long)addr;
     v4f q00 = tp[0], q10 = tp[1], q01 = tp[RS], q11 = tp[RS + 1];
     asm("" : "+v"(q00)); asm("" : "+v"(q10)); asm("" : "+v"(q01)); asm("" : "+v"(q11));
-    const float wgt = e.w;
-    const float wa = wgt * a;
+    // weights of the four taps with the sample weight folded in
+    const float wa = w * a;
     const float w11 = wa * b;
     const float w10 = wa - w11;
-    const float wt = wgt - wa;
+    const float wt = w - wa;
     const float w01 = wt * b;
     const float w00 = wt - w01;
     ar = fmaf(w11, q11.x, fmaf(w01, q01.x, fmaf(w10, q10.x, fmaf(w00, q00.x, ar))));
@@ -234,48 +196,63 @@ __device__ __forceinline__ void certain_sample(const v4f e, unsigned lds_base, f
     ab = fmaf(w11, q11.z, fmaf(w01, q01.z, fmaf(w10, q10.z, fmaf(w00, q00.z, ab))));
 }
 
+// One sample of a pass: accumulate it in the lanes whose direction falls into the staged region.
+// ACC = false: the count-only body of an absorbed word -- the same frame transform, predicates, ballots and pair count, no taps.
+template <int RS, bool SUB, int CLS, bool ACC = true>
+__device__ __forceinline__ void region_sample(const v4f e, const RegionView& V, float& ar, float& ag, float& ab, unsigned& cnt) {
+    float sc, tc, ma;
+    to_face(e, V, sc, tc, ma);
+    // each comparison's lane mask is taken by its own ballot (the compiler folds a ballot of ONE comparison into the v_cmp's
+    // SGPR result, not a ballot of their conjunction)
+    bool c1, c2;
+    on_face<CLS>(sc, tc, ma, c1, c2);
+    unsigned long long inm = __builtin_amdgcn_ballot_w64(c1) & __builtin_amdgcn_ballot_w64(c2);
+    // Lanes whose direction is not on this face (or, SUB, not in this region's cells) sit the sample out under the exec
+    // mask; a wave none of whose lanes is on the face skips the rest.  The (lane, sample) pairs taken are counted per wave
+    // with scalar instructions.
+    if (inm == 0) return;
+    if (!ACC && !SUB) { cnt += (unsigned)__builtin_popcountll(inm); return; }
+    bool in = c1 && c2;
+    const float h = __builtin_amdgcn_rcpf(ma) * V.half_n;
+    const float u = fmaf(sc, h, V.off), v = fmaf(tc, h, V.off);
+    if (SUB) {
+        // floor(u) in [ox, ox + rcx) <=> u in [ox, ox + rcx) (integer bounds): four float comparisons, no integer arithmetic
+        const bool c3 = u >= V.ulo, c4 = u < V.uhi, c5 = v >= V.vlo, c6 = v < V.vhi;
+        inm &= __builtin_amdgcn_ballot_w64(c3) & __builtin_amdgcn_ballot_w64(c4) & __builtin_amdgcn_ballot_w64(c5) & __builtin_amdgcn_ballot_w64(c6);
+        in = in && c3 && c4 && c5 && c6;
+    }
+    cnt += (unsigned)__builtin_popcountll(inm);
+    if (ACC && in) tap_accumulate<RS>(e.w, u, v, V.lds_base, ar, ag, ab);
+}
+
+// The same sample when binning has proved that EVERY texel of the tile taps this region of this face: all 64 lanes are in, so
+// the tests, ballots and the exec mask fall away.
+template <int RS>
+__device__ __forceinline__ void certain_sample(const v4f e, const RegionView& V, float& ar, float& ag, float& ab) {
+    float sc, tc, ma;
+    to_face(e, V, sc, tc, ma);
+    const float h = __builtin_amdgcn_rcpf(ma) * V.half_n;
+    tap_accumulate<RS>(e.w, fmaf(sc, h, V.off), fmaf(tc, h, V.off), V.lds_base, ar, ag, ab);
+}
+
 // ---- scalar-lean loop (round 5, 66^2 shapes) ----
 // The same sample as region_sample, counted PER LANE: cnt += 1 in the lanes that take it, under the exec mask the body runs with
 // anyway.  That drops the second ballot chain (one 4-way s_and_b64 chain for the count, another for the exec mask) and the
-// s_bcnt1; only the wave-uniform early exit of SUB keeps a ballot.  Taps, weights and FMA order are region_sample's, bit for bit.
+// s_bcnt1; only the wave-uniform early exit of SUB keeps a ballot.
 template <int RS, bool SUB, int CLS, bool ACC = true>
-__device__ __forceinline__ void lane_sample(const v4f e, unsigned lds_base, f3 Pb, f3 Pt, f3 Pr, float half_n, float off,
-                                            float ulo, float uhi, float vlo, float vhi,
-                                            float& ar, float& ag, float& ab, unsigned& cnt) {
-    const float sc = fmaf(e.x, Pb.x, fmaf(e.y, Pt.x, e.z * Pr.x));
-    const float tc = fmaf(e.x, Pb.y, fmaf(e.y, Pt.y, e.z * Pr.y));
-    const float ma = fmaf(e.x, Pb.z, fmaf(e.y, Pt.z, e.z * Pr.z));
+__device__ __forceinline__ void lane_sample(const v4f e, const RegionView& V, float& ar, float& ag, float& ab, unsigned& cnt) {
+    float sc, tc, ma;
+    to_face(e, V, sc, tc, ma);
     bool c1, c2;
-    if (CLS == 0) { c1 = ma > fabsf(sc); c2 = ma > fabsf(tc); }
-    else if (CLS == 1) { c1 = ma >= fabsf(sc); c2 = ma > fabsf(tc); }
-    else { c1 = ma >= fabsf(sc); c2 = ma >= fabsf(tc); }
+    on_face<CLS>(sc, tc, ma, c1, c2);
     bool in = c1 && c2;
     if (SUB && __builtin_amdgcn_ballot_w64(in) == 0ull) return;    // no lane on the face: skip the projection
-    const float h = __builtin_amdgcn_rcpf(ma) * half_n;
-    const float u = fmaf(sc, h, off), v = fmaf(tc, h, off);
-    if (SUB) in = in && u >= ulo && u < uhi && v >= vlo && v < vhi;
+    const float h = __builtin_amdgcn_rcpf(ma) * V.half_n;
+    const float u = fmaf(sc, h, V.off), v = fmaf(tc, h, V.off);
+    if (SUB) in = in && u >= V.ulo && u < V.uhi && v >= V.vlo && v < V.vhi;
     if (in) {
         cnt += 1u;
-        if (ACC) {
-            const int il = (int)u, jl = (int)v;
-            const float a = __builtin_amdgcn_fractf(u), b = __builtin_amdgcn_fractf(v);
-            unsigned t16, addr;
-            asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(t16) : "v"(il), "s"(lds_base));
-            asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(addr) : "v"(jl), "s"(RS * 16), "v"(t16));
-            lds_v4f_p tp = (lds_v4f_p)(unsigned long long)addr;
-            v4f q00 = tp[0], q10 = tp[1], q01 = tp[RS], q11 = tp[RS + 1];
-            asm("" : "+v"(q00)); asm("" : "+v"(q10)); asm("" : "+v"(q01)); asm("" : "+v"(q11));
-            const float wgt = e.w;
-            const float wa = wgt * a;
-            const float w11 = wa * b;
-            const float w10 = wa - w11;
-            const float wt = wgt - wa;
-            const float w01 = wt * b;
-            const float w00 = wt - w01;
-            ar = fmaf(w11, q11.x, fmaf(w01, q01.x, fmaf(w10, q10.x, fmaf(w00, q00.x, ar))));
-            ag = fmaf(w11, q11.y, fmaf(w01, q01.y, fmaf(w10, q10.y, fmaf(w00, q00.y, ag))));
-            ab = fmaf(w11, q11.z, fmaf(w01, q01.z, fmaf(w10, q10.z, fmaf(w00, q00.z, ab))));
-        }
+        if (ACC) tap_accumulate<RS>(e.w, u, v, V.lds_base, ar, ag, ab);
     }
 }
 
@@ -298,7 +275,7 @@ __device__ __forceinline__ void each_sample(unsigned m, ctab_t tw, F&& f) {
 // Lemma.  acc' = fma(x, y, acc) is rounded once, to nearest even.  If acc is a normal positive float and 0 <= x y <= acc 2^-25, then
 // acc' == acc: with 2^e <= acc < 2^(e+1), acc 2^-25 < 2^(e-24) = ulp(acc) / 2, so the exact sum acc + x y lies less than half an ulp
 // above acc and rounds back to it.  acc being unchanged, the same bound covers the next FMA of the chain.
-// A sample's tap weights (wa, w11, w10, wt, w01, w00 of region_sample / certain_sample) are formed from its weight w >= 0 and
+// A sample's tap weights (wa, w11, w10, wt, w01, w00 of tap_accumulate) are formed from its weight w >= 0 and
 // a, b in [0, 1) by monotone roundings: each lies in [0, w].  Its taps are texels of the staged region, so with M = the largest
 // R, G, B component staged for the region (border included; all finite and >= +0) every product of the sample's twelve FMAs is <= w M.
 // A mask word whose largest weight is W is therefore a no-op for a lane when W M <= acc 2^-25 holds for each of its three sums; a
@@ -312,18 +289,25 @@ __device__ __forceinline__ float absorb_threshold(float wmax, float m) {
     return t < 0x1p-100f ? 0x1p-100f : t;                               // NaN stays NaN
 }
 
+// skc (stats only): the workgroup's LDS counters {absorbed wave-words, their wave-samples, of those run through the count-only body}, for one
+// absorbed word: m its flagged samples, mu those not proved -- by value: formed in this lane-0 branch, the mask the caller walks next turns per-lane.
+__device__ __forceinline__ void count_absorbed(unsigned* skc, unsigned m, unsigned mu) {
+    if (skc && (threadIdx.x & 63) == 0) {
+        atomicAdd(&skc[0], 1u);
+        atomicAdd(&skc[1], (unsigned)__builtin_popcount(m));
+        atomicAdd(&skc[2], (unsigned)__builtin_popcount(mu));
+    }
+}
+
 // One pass over the flagged samples of the words w0, w0 + REG_S, .. below w1 of this wave's slice (the whole slice, or the head word /
-// the tail words of header 2g) for the staged region.  Samples are taken two at a time so that the
+// the tail words of header 2g) for the staged region V.  Samples are taken two at a time so that the
 // second table entry's scalar load is in flight while the first sample computes.
 // cwords holds, per mask word, the samples proved to be in this region for the whole tile.  CERT: they run certain_sample; else
 // they are only credited in absorbed words.  cwords + NW (LEAN: wmg, the launch's table): per mask word, the bit pattern of its largest weight.  rbits: the bit
-// pattern of the staged region's largest component, not below +inf's where absorbed words must not be skipped.  skc (stats only):
-// the workgroup's LDS counters {absorbed wave-words, their wave-samples, of those run through the count-only body}.
+// pattern of the staged region's largest component, not below +inf's where absorbed words must not be skipped.  skc: see count_absorbed.
 template <int RS, bool SUB, int CLS, int REG_S, bool CERT, bool LEAN>
-__device__ __forceinline__ void region_pass(unsigned lds_base, const unsigned* __restrict__ mwords, const unsigned* __restrict__ cwords, cu32_t wmg,
-                                            unsigned rbits, unsigned* skc, int NW, int w0, int w1,
-                                            ctab_t tab, f3 Pb, f3 Pt, f3 Pr, float half_n, float off,
-                                            float ulo, float uhi, float vlo, float vhi,
+__device__ __forceinline__ void region_pass(const RegionView& V, const unsigned* __restrict__ mwords, const unsigned* __restrict__ cwords, cu32_t wmg,
+                                            unsigned rbits, unsigned* skc, int NW, int w0, int w1, ctab_t tab,
                                             float& ar, float& ag, float& ab, unsigned& cnt) {
     unsigned mnext = w0 < w1 ? (unsigned)__builtin_amdgcn_readfirstlane((int)mwords[w0]) : 0u;
     unsigned cnext = (CERT && w0 < w1) ? (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[w0]) : 0u;
@@ -345,16 +329,12 @@ __device__ __forceinline__ void region_pass(unsigned lds_base, const unsigned* _
                     c = (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[w]);
                     cnt += 64u * (unsigned)__builtin_popcount(m & c);
                 }
-                if (skc && (threadIdx.x & 63) == 0) {
-                    atomicAdd(&skc[0], 1u);
-                    atomicAdd(&skc[1], (unsigned)__builtin_popcount(m));
-                    atomicAdd(&skc[2], (unsigned)__builtin_popcount(m & ~c));
-                }
+                count_absorbed(skc, m, m & ~c);
                 m &= ~c;
                 while (m) {
                     const int i0 = __builtin_ctz(m);
                     m &= m - 1u;
-                    region_sample<RS, SUB, CLS, false>(tw[i0], lds_base, Pb, Pt, Pr, half_n, off, ulo, uhi, vlo, vhi, ar, ag, ab, cnt);
+                    region_sample<RS, SUB, CLS, false>(tw[i0], V, ar, ag, ab, cnt);
                 }
                 continue;
             }
@@ -368,11 +348,11 @@ __device__ __forceinline__ void region_pass(unsigned lds_base, const unsigned* _
             const v4f e0 = tw[i0];
             const v4f e1 = tw[i1];
             // samples in index order whichever body they take: the order of a texel's sum stays (region as visited, sample index)
-            if (CERT && ((c >> i0) & 1u)) certain_sample<RS>(e0, lds_base, Pb, Pt, Pr, half_n, off, ar, ag, ab);
-            else region_sample<RS, SUB, CLS>(e0, lds_base, Pb, Pt, Pr, half_n, off, ulo, uhi, vlo, vhi, ar, ag, ab, cnt);
+            if (CERT && ((c >> i0) & 1u)) certain_sample<RS>(e0, V, ar, ag, ab);
+            else region_sample<RS, SUB, CLS>(e0, V, ar, ag, ab, cnt);
             if (two) {
-                if (CERT && ((c >> i1) & 1u)) certain_sample<RS>(e1, lds_base, Pb, Pt, Pr, half_n, off, ar, ag, ab);
-                else region_sample<RS, SUB, CLS>(e1, lds_base, Pb, Pt, Pr, half_n, off, ulo, uhi, vlo, vhi, ar, ag, ab, cnt);
+                if (CERT && ((c >> i1) & 1u)) certain_sample<RS>(e1, V, ar, ag, ab);
+                else region_sample<RS, SUB, CLS>(e1, V, ar, ag, ab, cnt);
             }
         }
     }
@@ -387,14 +367,12 @@ __device__ __forceinline__ void region_pass(unsigned lds_base, const unsigned* _
 //     join), then the tested one, in index order;
 //   * tested samples use lane_sample (one ballot chain), and every loop issues the next table entry's load ahead of the body.
 template <int RS, bool SUB, int CLS, int REG_S, bool CERT, bool LEAN>
-__device__ __forceinline__ void region_pass_runs(unsigned lds_base, const unsigned* __restrict__ mwords, const unsigned* __restrict__ cwords, cu32_t wmg,
-                                                 unsigned rbits, unsigned* skc, int NW, int s, unsigned long long wsel,
-                                                 ctab_t tab, f3 Pb, f3 Pt, f3 Pr, float half_n, float off,
-                                                 float ulo, float uhi, float vlo, float vhi,
+__device__ __forceinline__ void region_pass_runs(const RegionView& V, const unsigned* __restrict__ mwords, const unsigned* __restrict__ cwords, cu32_t wmg,
+                                                 unsigned rbits, unsigned* skc, int NW, int s, unsigned long long wsel, ctab_t tab,
                                                  float& ar, float& ag, float& ab, unsigned& cnt) {
     const int wl = s + REG_S * (int)(threadIdx.x & 63);
     unsigned long long nz = __builtin_amdgcn_ballot_w64(wl < NW && mwords[wl] != 0u) & wsel;
-    auto tested = [&](const v4f e) { lane_sample<RS, SUB, CLS>(e, lds_base, Pb, Pt, Pr, half_n, off, ulo, uhi, vlo, vhi, ar, ag, ab, cnt); };
+    auto tested = [&](const v4f e) { lane_sample<RS, SUB, CLS>(e, V, ar, ag, ab, cnt); };
     while (nz) {
         const int w = s + REG_S * (int)__builtin_ctzll(nz);
         nz &= nz - 1ull;
@@ -407,14 +385,8 @@ __device__ __forceinline__ void region_pass_runs(unsigned lds_base, const unsign
             if (__builtin_amdgcn_ballot_w64(!(ar >= T && ag >= T && ab >= T)) == 0ull) {
                 if (!CERT) c = (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[w]);
                 cnt += (unsigned)__builtin_popcount(m & c);                // every lane takes every proved sample
-                if (skc && (threadIdx.x & 63) == 0) {
-                    atomicAdd(&skc[0], 1u);
-                    atomicAdd(&skc[1], (unsigned)__builtin_popcount(m));
-                    atomicAdd(&skc[2], (unsigned)__builtin_popcount(m & ~c));
-                }
-                each_sample(m & ~c, tw, [&](const v4f e) {
-                    lane_sample<RS, SUB, CLS, false>(e, lds_base, Pb, Pt, Pr, half_n, off, ulo, uhi, vlo, vhi, ar, ag, ab, cnt);
-                });
+                count_absorbed(skc, m, m & ~c);
+                each_sample(m & ~c, tw, [&](const v4f e) { lane_sample<RS, SUB, CLS, false>(e, V, ar, ag, ab, cnt); });
                 continue;
             }
         }
@@ -423,7 +395,7 @@ __device__ __forceinline__ void region_pass_runs(unsigned lds_base, const unsign
         unsigned mc = m & c, mu = m & ~c;
         for (;;) {
             const unsigned below = mu ? (mu & (0u - mu)) - 1u : ~0u;     // the samples before the next tested one (all: none left)
-            each_sample(mc & below, tw, [&](const v4f e) { certain_sample<RS>(e, lds_base, Pb, Pt, Pr, half_n, off, ar, ag, ab); });
+            each_sample(mc & below, tw, [&](const v4f e) { certain_sample<RS>(e, V, ar, ag, ab); });
             mc &= ~below;
             if (!mu) break;
             const int it = __builtin_ctz(mu);
@@ -450,11 +422,10 @@ __device__ __forceinline__ void region_pass_runs(unsigned lds_base, const unsign
 // slices) and byte 1 for the tail words.  lim: the first sample index this thread does not bin -- 32 x the cut word of its slice (a
 // thread's samples i = tid + 1024 k all fall into slice (tid >> 5) % S), n_tab without a cut.  keep_cut (counters only): the samples behind lim still run and set their mask bits, but no
 // region flag; the caller counts and clears those bits.
-template <bool LEAN, bool G1, bool TWO = false>
+template <bool LEAN, bool G1, bool TWO>
 __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsigned* dmax, int NR, int NW, int G, int RC, int n,
                                            f3 R, f3 T, f3 B, f3 Rc, f3 Tc, f3 Bc, ctab_t tab, int n_tab, int tid,
-                                           unsigned* cmask = nullptr, unsigned* wmax = nullptr, int ntail = 0,
-                                           int lim = 0x7fffffff, bool keep_cut = false, int head_end = 128) {
+                                           unsigned* cmask, unsigned* wmax, int ntail, int lim, bool keep_cut, int head_end) {
     const float nf = (float)n;
     const float half_n = 0.5f * nf;
     const float off = 0.5f * nf + 0.5f;
@@ -527,6 +498,146 @@ __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsig
     }
 }
 
+// Block -> (face, tx, ty).  Tiles in plain block order: consecutive tiles go round-robin over the 8 XCDs.  An XCD-contiguous remap (one
+// eighth of the grid per XCD) put all tiles around the pole of the tangent frame -- where every sample is flagged for several regions and
+// a tile takes up to 3x as long -- on ONE XCD, and the launch waited for it (a single-face dispatch of a +-X face: 10.2 vs 7.6 ms).
+// The whole level fits every XCD's L2, so locality has nothing to lose.
+__device__ __forceinline__ void tile_of_block(const RegArgs& q, int& face, int& tx, int& ty) {
+    const McArgs& p = q.a;
+    const unsigned tile = blockIdx.x;
+    face = p.face0 + (int)(tile / (unsigned)p.tiles_per_face);
+    const int tf = (int)(tile % (unsigned)p.tiles_per_face);
+    ty = tf / p.tiles_x;
+    tx = tf % p.tiles_x;
+    // Longest tiles first: around the pole of the tangent frame (tangent_of: inside the +X face, its antipode inside -X) the frames
+    // of a tile twist against each other, a sample lands in several regions and a tile takes up to 3x as long.  In row order those
+    // tiles came last on the -X face (pole at 3/4 of its height) and the launch ended in their tail; here the rows of these two
+    // faces are dealt outwards from the pole row, so the long tiles start first and the short ones fill in behind them.
+    if (face < 2) {
+        const int ny = p.tiles_per_face / p.tiles_x, pr = q.pole_row[face];
+        const int a = min(pr, ny - 1 - pr);
+        if (ty <= 2 * a) { const int h = (ty + 1) >> 1; ty = (ty & 1) ? pr + h : pr - h; }
+        else { const int rest = ty - 2 * a; ty = (pr > ny - 1 - pr) ? pr - a - rest : pr + a + rest; }
+    }
+}
+
+// Output texel of thread t of a slice.  A wave covers an 8 x 8 quadrant of the tile (not 16 x 4): the smaller its extent, the fewer
+// samples its lanes spread over two regions (PBR_MC_WAVE_SHAPE experiment: see DESIGN.md)
+template <int TILE>
+__device__ __forceinline__ void texel_of_thread(const McArgs& p, int tx, int ty, int t, int& x, int& y) {
+    constexpr int QW = TILE / 8, QSH = TILE == 32 ? 2 : 1;               // quadrants per tile edge (a power of two) and its log2: 2 x 2 (TILE 16), 4 x 4 (TILE 32)
+    static_assert(QW == 1 << QSH, "TILE is 16 or 32");
+    const int q8 = t >> 6, l8 = t & 63;
+    x = tx * TILE + (q8 & (QW - 1)) * 8 + (l8 & 7);
+    y = p.y0 + ty * TILE + (q8 >> QSH) * 8 + (l8 >> 3);
+}
+
+// Header 2g: the samples of a slice's cut words (cw, cw + REG_S, .. : full words, but for the table's last one), in the unit cnt counts in
+template <int REG_S, bool RUNS>
+__device__ __forceinline__ unsigned cut_credit(int cw, int NW, int n_tab) {
+    const int last = NW - 1, kc = (last - cw) / REG_S + 1;           // cut words cw, cw + REG_S, .. <= last
+    if (cw > last) return 0u;
+    return (unsigned)(32 * kc - ((last - cw) % REG_S == 0 ? 32 * NW - n_tab : 0)) * (RUNS ? 1u : 64u);
+}
+
+// Staging of the lean 66^2 shapes (header 2f iii): the region's (rcx + 1) x (rcy + 1) texels at fsrc (row pitch nb) by rows.
+// Wave w takes rows w, w + 16, ..: the row is wave-uniform, a lane's column is its index -- no division per texel; columns 64
+// and 65 go to the first 132 threads, one texel each.  Addresses are clamped into the region, so every load is
+// unconditional and all of a thread's loads are issued before its first LDS write; the guards are on the writes.
+template <int RS>
+__device__ __forceinline__ void stage_rows(float4* region, const float4* __restrict__ fsrc, int nb, int rcx, int rcy, int tid) {
+    // The thread index is formed again per staging (opaque to the optimiser): hoisted out of the region loop, the lane's source and
+    // LDS offsets stay alive across the passes and spill at the 64-VGPR budget.
+    int tid_s = tid;
+    asm volatile("" : "+v"(tid_s));
+    const int wv = __builtin_amdgcn_readfirstlane(tid_s >> 6), ln = tid_s & 63;
+    // row bases are wave-uniform (scalar); a lane adds its clamped column as a 32-bit byte offset
+    const unsigned cx = (unsigned)min(ln, rcx) << 4;
+    const char* const base = (const char*)fsrc;
+    const unsigned rowb = (unsigned)nb << 4;
+    const float4 v0 = *(const float4*)(base + (size_t)((unsigned)min(wv, rcy) * rowb) + cx);
+    const float4 v1 = *(const float4*)(base + (size_t)((unsigned)min(wv + 16, rcy) * rowb) + cx);
+    const float4 v2 = *(const float4*)(base + (size_t)((unsigned)min(wv + 32, rcy) * rowb) + cx);
+    const float4 v3 = *(const float4*)(base + (size_t)((unsigned)min(wv + 48, rcy) * rowb) + cx);
+    const float4 v4 = *(const float4*)(base + (size_t)((unsigned)min(wv + 64, rcy) * rowb) + cx);
+    const int ey = tid_s >> 1, ex = 64 + (tid_s & 1);              // tid < 132: rows 0 .. 65
+    const float4 ve = *(const float4*)(base + (unsigned)(min(ey, rcy) * nb + min(ex, rcx)) * 16u);
+    if (ln <= rcx) {
+        float4* const dst = region + wv * RS + ln;
+        if (wv <= rcy) dst[0] = v0;
+        if (wv + 16 <= rcy) dst[16 * RS] = v1;
+        if (wv + 32 <= rcy) dst[32 * RS] = v2;
+        if (wv + 48 <= rcy) dst[48 * RS] = v3;
+        if (wv + 64 <= rcy) dst[64 * RS] = v4;
+    }
+    if (tid_s < 2 * RS && ex <= rcx && ey <= rcy) region[ey * RS + ex] = ve;
+}
+
+// Staging of every other shape: two sweeps of the workgroup over RS x RS with a constant divisor.  MAXIMA (absorb, !LEAN): the largest R, G, B
+// bit pattern (any negative / inf / NaN orders above +inf) goes to *rmax_r, if given: wave maximum, one LDS atomic per wave, ahead of the caller's barrier.
+template <int RS, bool MAXIMA>
+__device__ __forceinline__ void stage_sweeps(float4* region, const float4* __restrict__ fsrc, int nb, int rcx, int rcy, int tid, unsigned* rmax_r) {
+    unsigned vmax = 0u;
+    for (int k = tid; k < RS * RS; k += 1024) {
+        const int ry = k / RS, rx = k - ry * RS;
+        if (rx <= rcx && ry <= rcy) {
+            const float4 v = fsrc[ry * nb + rx];
+            region[k] = v;
+            if (MAXIMA) vmax = max(vmax, max(__float_as_uint(v.x), max(__float_as_uint(v.y), __float_as_uint(v.z))));
+        }
+    }
+    if (MAXIMA && rmax_r) {
+        // xor butterflies inside each 32-lane half (ds_swizzle: the pattern is an immediate, no lane-address registers), halves via readlane
+        vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (16 << 10) | 0x1f));
+        vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (8 << 10) | 0x1f));
+        vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (4 << 10) | 0x1f));
+        vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (2 << 10) | 0x1f));
+        vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (1 << 10) | 0x1f));
+        const unsigned wv = max((unsigned)__builtin_amdgcn_readlane((int)vmax, 0), (unsigned)__builtin_amdgcn_readlane((int)vmax, 32));
+        if ((tid & 63) == 0) atomicMax(rmax_r, wv);
+    }
+}
+
+// Header, step 3: a wave that missed a sample recomputes its slice (words s, s + REG_S, ..) with direct loads, as the direct kernel would
+template <int REG_S>
+__device__ __forceinline__ void heal_slice(const McArgs& p, ctab_t tab, int NW, int s, f3 R, f3 T, f3 B, float& ar, float& ag, float& ab) {
+    const int nb = p.n_src + 2;
+    const float nf = (float)p.n_src, off = 0.5f * nf + 0.5f;
+    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.src, 0, (int)p.src_bytes, 0x00020000);
+    ar = 0.0f; ag = 0.0f; ab = 0.0f;
+    for (int w = s; w < NW; w += REG_S) {
+        const int i1 = min((w << 5) + 32, p.n_tab);
+        for (int i = w << 5; i < i1; ++i) {
+            const v4f e = tab[i];
+            f3 L;
+            L.x = fmaf(e.x, B.x, fmaf(e.y, T.x, e.z * R.x));
+            L.y = fmaf(e.x, B.y, fmaf(e.y, T.y, e.z * R.y));
+            L.z = fmaf(e.x, B.z, fmaf(e.y, T.z, e.z * R.z));
+            f3 c = sample_bordered<false>(rs, L, nf, off, nb, nb * 16);
+            ar = fmaf(e.w, c.x, ar); ag = fmaf(e.w, c.y, ag); ab = fmaf(e.w, c.z, ab);
+        }
+    }
+}
+
+// Header, step 4: the sums of texel t over the REG_S slices, by a fixed tree, end in red[3 t ..] (one slice: nothing to combine, red[] only
+// hands the sums to the store).  The caller's barrier has ended every read of the staged region red[] overlays.
+template <int REG_TX, int REG_S>
+__device__ __forceinline__ void reduce_slices(float* red, int s, int t, float ar, float ag, float ab) {
+    red[(s * REG_TX + t) * 3 + 0] = ar;
+    red[(s * REG_TX + t) * 3 + 1] = ag;
+    red[(s * REG_TX + t) * 3 + 2] = ab;
+    __syncthreads();
+    for (int stride = REG_S / 2; stride >= 1; stride >>= 1) {
+        if (s < stride) {
+            const int a2 = (s * REG_TX + t) * 3, b2 = ((s + stride) * REG_TX + t) * 3;
+            red[a2 + 0] += red[b2 + 0];
+            red[a2 + 1] += red[b2 + 1];
+            red[a2 + 2] += red[b2 + 2];
+        }
+        __syncthreads();
+    }
+}
+
 // Clock of the calling lane (PBR_MC_PHASE_STAMPS builds only: where a tile's time goes; the product build has no stamp in it)
 #ifdef PBR_MC_PHASE_STAMPS
 #define STAMP() ((unsigned long long)__builtin_readcyclecounter())
@@ -536,16 +647,10 @@ __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsig
 
 // RUNS (66^2 shapes only): the region loop visits the flagged regions only and runs region_pass_runs (round 5; cnt per lane)
 // LEAN: the prologue of header 2f (pbrk_mc_set_prologue); false: the one before it, kept as the yardstick
+// The body reads: frames, bin, credit, the loop of (stage, pass) over the flagged regions, check / heal, reduce / store.
 template <int RS, bool SUB, int TILE, bool RUNS = false, bool LEAN = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_mc_region(const RegArgs q) {
     constexpr int REG_TX = TILE * TILE, REG_S = 1024 / REG_TX;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_r[];
-    float4* region = (float4*)smem_r;
-    const unsigned lds_base = (unsigned)(unsigned long long)smem_r;      // LDS byte offset of the staged region (low half of the flat address)
-    unsigned* skc = (unsigned*)(smem_r + RS * RS * 16);                  // [4] (absorb, stats) counters of the absorbed words: a fixed address
-    unsigned* masks = skc + 4;
-    unsigned* any = masks + q.NR * q.NW;
-    unsigned* dmax = any + q.NR;
     constexpr bool CERT = SUB;                                           // see the header, 2b
     // see the header, 2c: compiled for the 66^2 region shapes only.  The 34^2 / 18^2 levels of C4 (mips 3, 4: weights fall to ~e^-6)
     // never absorb a word, and the test alone cost them 7 % (measured); without it their code is that of round 3
@@ -558,9 +663,20 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     // see the header, 2g: head words first, then the tail words; decided per 66^2 shape (MC_HEAD_FIRST_SUB / MC_HEAD_FIRST_G1)
     constexpr bool TWO = RS == 66 && (SUB ? MC_HEAD_FIRST_SUB != 0 : MC_HEAD_FIRST_G1 != 0);
     const bool cut_on = TWO && LEAN && q.cut != 0;                       // workgroup-uniform: the launch's cut words are not binned
+    // LDS layout: the staged region (RS^2 texels), then in words skc[4] | masks[NR NW] | any[NR] | dmax[1] | cmask[NW] | wmax[NW] | rmax[NR].
+    // launch_mc_region's lds_fixed is this chain up to cmask, its absorb term the last two.  region_bin clears masks .. dmax and the
+    // ntail words behind dmax: the arrays this launch reads.  All three move together.
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_r[];
+    float4* region = (float4*)smem_r;
+    const unsigned lds_base = (unsigned)(unsigned long long)smem_r;      // LDS byte offset of the staged region (low half of the flat address)
+    unsigned* skc = (unsigned*)(smem_r + RS * RS * 16);                  // [4] (absorb, stats) counters of the absorbed words: a fixed address
+    unsigned* masks = skc + 4;
+    unsigned* any = masks + q.NR * q.NW;
+    unsigned* dmax = any + q.NR;
     unsigned* cmask = dmax + 1;                                          // [NW] samples proved to tap one region from the whole tile
     unsigned* wmax = cmask + q.NW;                                       // [NW] (absorb, !LEAN) largest weight (bit pattern) per mask word
     unsigned* rmax = wmax + q.NW;                                        // [NR] (absorb, !LEAN) largest staged R, G, B bit pattern per region
+    const int ntail = (absorb_on && !LEAN) ? 2 * q.NW + q.NR : ((CERT || ABS) ? q.NW : 0);
     cu32_t wmg = (cu32_t)(unsigned long long)q.tabmax;                   // (absorb, LEAN) the same two for the whole launch: [NW], then [NR]
     [[maybe_unused]] const unsigned long long st0 = STAMP();
     const McArgs& p = q.a;
@@ -568,32 +684,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     const int s = __builtin_amdgcn_readfirstlane(tid / REG_TX);
     const int t = tid % REG_TX;
 
-    // Tiles in plain block order: consecutive tiles go round-robin over the 8 XCDs.  An XCD-contiguous remap (one eighth of the
-    // grid per XCD) put all tiles around the pole of the tangent frame -- where every sample is flagged for several regions and a tile
-    // takes up to 3x as long -- on ONE XCD, and the launch waited for it (a single-face dispatch of a +-X face: 10.2 vs 7.6 ms).
-    // The whole level fits every XCD's L2, so locality has nothing to lose.
-    unsigned tile = blockIdx.x;
-    const int face = p.face0 + (int)(tile / (unsigned)p.tiles_per_face);
-    const int tf = (int)(tile % (unsigned)p.tiles_per_face);
-    int ty = tf / p.tiles_x;
-    const int tx = tf % p.tiles_x;
-    // Longest tiles first: around the pole of the tangent frame (tangent_of: inside the +X face, its antipode inside -X) the frames
-    // of a tile twist against each other, a sample lands in several regions and a tile takes up to 3x as long.  In row order those
-    // tiles came last on the -X face (pole at 3/4 of its height) and the launch ended in their tail; here the rows of these two
-    // faces are dealt outwards from the pole row, so the long tiles start first and the short ones fill in behind them.
-    if (face < 2) {
-        const int ny = p.tiles_per_face / p.tiles_x, pr = q.pole_row[face];
-        const int a = min(pr, ny - 1 - pr);
-        if (ty <= 2 * a) { const int h = (ty + 1) >> 1; ty = (ty & 1) ? pr + h : pr - h; }
-        else { const int rest = ty - 2 * a; ty = (pr > ny - 1 - pr) ? pr - a - rest : pr + a + rest; }
-    }
-    // a wave covers an 8 x 8 quadrant of the tile (not 16 x 4): the smaller its extent, the fewer samples its lanes spread over
-    // two regions (PBR_MC_WAVE_SHAPE experiment: see DESIGN.md)
-    constexpr int QW = TILE / 8, QSH = TILE == 32 ? 2 : 1;               // quadrants per tile edge (a power of two) and its log2: 2 x 2 (TILE 16), 4 x 4 (TILE 32)
-    static_assert(QW == 1 << QSH, "TILE is 16 or 32");
-    const int q8 = t >> 6, l8 = t & 63;
-    const int x = tx * TILE + (q8 & (QW - 1)) * 8 + (l8 & 7);
-    const int y = p.y0 + ty * TILE + (q8 >> QSH) * 8 + (l8 >> 3);
+    int face, tx, ty, x, y;
+    tile_of_block(q, face, tx, ty);
+    texel_of_thread<TILE>(p, tx, ty, t, x, y);
     const int xc = min(x, p.size - 1), yc = min(y, p.y0 + p.rows - 1);
 
     const f3 R = face_texel_dir(face, xc, yc, p.size);
@@ -618,8 +711,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     // in word (tid >> 5) + 32 k, that is in slice (tid >> 5) % REG_S
     const int lim = cut_on ? (int)q.tabmax[NW + NR + ((tid >> 5) % REG_S)] << 5 : 0x7fffffff;
     region_bin<LEAN, !SUB, TWO>(masks, any, dmax, NR, NW, G, RC, n, R, T, B, Rc, Tc, Bc, tab, p.n_tab, tid, (CERT || ABS) ? cmask : nullptr,
-                                (absorb_on && !LEAN) ? wmax : nullptr, (absorb_on && !LEAN) ? 2 * NW + NR : ((CERT || ABS) ? NW : 0),
-                                lim, cut_on && q.stats != nullptr, 32 * REG_S);
+                                (absorb_on && !LEAN) ? wmax : nullptr, ntail, lim, cut_on && q.stats != nullptr, 32 * REG_S);
     [[maybe_unused]] unsigned long long st_stage = 0ull;
 #ifdef PBR_MC_PHASE_STAMPS
     __syncthreads();                                               // the wait for the slowest thread's binning is charged to binning
@@ -628,16 +720,9 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 
     // ---- 2. region passes ----
     float ar = 0.0f, ag = 0.0f, ab = 0.0f;
-    unsigned cnt = 0;
-    if (cut_on) {
-        // expect[s] less the samples of the slice's cut words (full words, but for the table's last one), formed here as a credit: the
-        // count starts at what the cut took out, so nothing of it stays alive across the passes
-        const int cw = (int)wmg[NW + NR + s], last = NW - 1;
-        if (cw <= last) {
-            const int kc = (last - cw) / REG_S + 1;                  // cut words cw, cw + REG_S, .. <= last
-            cnt = (unsigned)(32 * kc - ((last - cw) % REG_S == 0 ? 32 * NW - p.n_tab : 0)) * (RUNS ? 1u : 64u);
-        }
-    }
+    // expect[s] less the samples of the slice's cut words, formed here as a credit: the count starts at what the cut took out, so
+    // nothing of it stays alive across the passes
+    unsigned cnt = cut_on ? cut_credit<REG_S, RUNS>((int)wmg[NW + NR + s], NW, p.n_tab) : 0u;
     if (q.stats) {                                                 // diagnostics: (region, sample) flags of this tile, samples, regions visited
         __syncthreads();
         unsigned fl = 0, cfl = 0, cwd = 0;
@@ -667,107 +752,51 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         const float4* __restrict__ fsrc = p.src + ((size_t)f * nb + oy) * nb + ox;
         const unsigned long long sta = STAMP();
         unsigned rbits = 0x7f800000u;                              // wave-uniform; the pattern of +inf (never below itself) when absorbed words must not be skipped
-        if (LEAN && RS == 66) {
-            // wave w takes rows w, w + 16, ..: the row is wave-uniform, a lane's column is its index -- no division per texel; columns 64
-            // and 65 go to the first 132 threads, one texel each.  Addresses are clamped into the region, so every load is
-            // unconditional and all of a thread's loads are issued before its first LDS write; the guards are on the writes.
-            // The thread index is formed again per staging (opaque to the optimiser): hoisted out of the region loop, the lane's source and
-            // LDS offsets stay alive across the passes and spill at the 64-VGPR budget.
-            int tid_s = tid;
-            asm volatile("" : "+v"(tid_s));
-            const int wv = __builtin_amdgcn_readfirstlane(tid_s >> 6), ln = tid_s & 63;
-            // row bases are wave-uniform (scalar); a lane adds its clamped column as a 32-bit byte offset
-            const unsigned cx = (unsigned)min(ln, rcx) << 4;
-            const char* const base = (const char*)fsrc;
-            const unsigned rowb = (unsigned)nb << 4;
-            const float4 v0 = *(const float4*)(base + (size_t)((unsigned)min(wv, rcy) * rowb) + cx);
-            const float4 v1 = *(const float4*)(base + (size_t)((unsigned)min(wv + 16, rcy) * rowb) + cx);
-            const float4 v2 = *(const float4*)(base + (size_t)((unsigned)min(wv + 32, rcy) * rowb) + cx);
-            const float4 v3 = *(const float4*)(base + (size_t)((unsigned)min(wv + 48, rcy) * rowb) + cx);
-            const float4 v4 = *(const float4*)(base + (size_t)((unsigned)min(wv + 64, rcy) * rowb) + cx);
-            const int ey = tid_s >> 1, ex = 64 + (tid_s & 1);      // tid < 132: rows 0 .. 65
-            const float4 ve = *(const float4*)(base + (unsigned)(min(ey, rcy) * nb + min(ex, rcx)) * 16u);
-            if (ln <= rcx) {
-                float4* const dst = region + wv * RS + ln;
-                if (wv <= rcy) dst[0] = v0;
-                if (wv + 16 <= rcy) dst[16 * RS] = v1;
-                if (wv + 32 <= rcy) dst[32 * RS] = v2;
-                if (wv + 48 <= rcy) dst[48 * RS] = v3;
-                if (wv + 64 <= rcy) dst[64 * RS] = v4;
-            }
-            if (tid_s < 2 * RS && ex <= rcx && ey <= rcy) region[ey * RS + ex] = ve;
-            if (absorb_on) rbits = wmg[NW + r];                    // scalar load, in flight across the barrier
-            __syncthreads();
-        } else {
-            unsigned vmax = 0u;                                        // largest R, G, B bit pattern: any negative / inf / NaN orders above +inf
-            for (int k = tid; k < RS * RS; k += 1024) {
-                const int ry = k / RS, rx = k - ry * RS;
-                if (rx <= rcx && ry <= rcy) {
-                    const float4 v = fsrc[ry * nb + rx];
-                    region[k] = v;
-                    if (ABS && !LEAN) vmax = max(vmax, max(__float_as_uint(v.x), max(__float_as_uint(v.y), __float_as_uint(v.z))));
-                }
-            }
-            if (absorb_on && !LEAN) {                                  // wave maximum, one LDS atomic per wave, ahead of the barrier
-                // xor butterflies inside each 32-lane half (ds_swizzle: the pattern is an immediate, no lane-address registers), halves via readlane
-                vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (16 << 10) | 0x1f));
-                vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (8 << 10) | 0x1f));
-                vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (4 << 10) | 0x1f));
-                vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (2 << 10) | 0x1f));
-                vmax = max(vmax, (unsigned)__builtin_amdgcn_ds_swizzle((int)vmax, (1 << 10) | 0x1f));
-                const unsigned wv = max((unsigned)__builtin_amdgcn_readlane((int)vmax, 0), (unsigned)__builtin_amdgcn_readlane((int)vmax, 32));
-                if ((tid & 63) == 0) atomicMax(&rmax[r], wv);
-            }
-            __syncthreads();
-            if (absorb_on) rbits = LEAN ? wmg[NW + r] : (unsigned)__builtin_amdgcn_readfirstlane((int)rmax[r]);
-        }
+        if (LEAN && RS == 66) stage_rows<RS>(region, fsrc, nb, rcx, rcy, tid);
+        else stage_sweeps<RS, ABS && !LEAN>(region, fsrc, nb, rcx, rcy, tid, (absorb_on && !LEAN) ? &rmax[r] : nullptr);
+        if (absorb_on && LEAN) rbits = wmg[NW + r];                // scalar load, in flight across the barrier
+        __syncthreads();
+        if (absorb_on && !LEAN) rbits = (unsigned)__builtin_amdgcn_readfirstlane((int)rmax[r]);
         const unsigned long long stb = STAMP();
-        // signed permutation of the frame for this face: rows give (sc, tc, ma) directly
-        f3 Pb, Pt, Pr;
-        face_coords(f, B.x, B.y, B.z, Pb.x, Pb.y, Pb.z);
-        face_coords(f, T.x, T.y, T.z, Pt.x, Pt.y, Pt.z);
-        face_coords(f, R.x, R.y, R.z, Pr.x, Pr.y, Pr.z);
+        RegionView V;
+        V.lds_base = lds_base - (unsigned)(oy * RS + ox) * 16u;
+        // signed permutation of the frame for this face
+        face_coords(f, B.x, B.y, B.z, V.Pb.x, V.Pb.y, V.Pb.z);
+        face_coords(f, T.x, T.y, T.z, V.Pt.x, V.Pt.y, V.Pt.z);
+        face_coords(f, R.x, R.y, R.z, V.Pr.x, V.Pr.y, V.Pr.z);
+        V.half_n = half_n; V.off = off;
+        V.ulo = (float)ox; V.uhi = (float)(ox + rcx); V.vlo = (float)oy; V.vhi = (float)(oy + rcy);
         const unsigned* mw = masks + r * NW;
-        const unsigned pass_base = lds_base - (unsigned)(oy * RS + ox) * 16u;      // taps are addressed with face coordinates
         unsigned* const sc = (ABS && q.stats) ? skc : nullptr;
         // the words of this pass: the whole slice, or (TWO) its head word s / its tail words s + REG_S, ..
         const unsigned long long wsel = TWO ? (ph ? ~1ull : 1ull) : ~0ull;
         const int w0 = (TWO && ph) ? s + REG_S : s, w1 = (TWO && !ph) ? min(NW, s + 1) : NW;
-        if (RUNS) {
-            switch (f >> 1) {
-            case 0: region_pass_runs<RS, SUB, 0, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, wsel, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
-            case 1: region_pass_runs<RS, SUB, 1, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, wsel, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
-            default: region_pass_runs<RS, SUB, 2, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, s, wsel, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
-            }
-        } else switch (f >> 1) {
-        case 0: region_pass<RS, SUB, 0, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, w0, w1, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
-        case 1: region_pass<RS, SUB, 1, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, w0, w1, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
-        default: region_pass<RS, SUB, 2, REG_S, CERT, LEAN>(pass_base, mw, cmask, wmg, rbits, sc, NW, w0, w1, tab, Pb, Pt, Pr, half_n, off, (float)ox, (float)(ox + rcx), (float)oy, (float)(oy + rcy), ar, ag, ab, cnt); break;
+        auto pass = [&](auto cls) {                                // cls: the face's major axis as a compile-time constant
+            constexpr int CLS = decltype(cls)::value;
+            if (RUNS) region_pass_runs<RS, SUB, CLS, REG_S, CERT, LEAN>(V, mw, cmask, wmg, rbits, sc, NW, s, wsel, tab, ar, ag, ab, cnt);
+            else region_pass<RS, SUB, CLS, REG_S, CERT, LEAN>(V, mw, cmask, wmg, rbits, sc, NW, w0, w1, tab, ar, ag, ab, cnt);
+        };
+        switch (f >> 1) {
+        case 0: pass(std::integral_constant<int, 0>()); break;
+        case 1: pass(std::integral_constant<int, 1>()); break;
+        default: pass(std::integral_constant<int, 2>()); break;
         }
         st_stage += stb - sta;
     };
     [[maybe_unused]] const unsigned long long st2b = STAMP();
-    if (RUNS) {
-        // the barrier ahead of each staging runs for the flagged regions only (once per visited region instead of once per region
-        // of the level); any[] is final after binning, so the skip needs none.  (A 64-bit mask of the visited regions kept across
-        // the passes, or a ballot search for the next one, spills VGPRs at the 64-VGPR budget of the quarter-face shape.)
-        __syncthreads();                                           // binning done
-        for (int kk = 0; kk < (TWO ? 2 * NR : NR); ++kk) {         // TWO: all regions for the head words, then all for the tail words (one
-            const int ph = TWO && kk >= NR, k = kk - (ph ? NR : 0);    // counter: a second loop variable costs a scalar register across the passes)
-            const int r = OWN_FIRST ? mc_region_visit(k, face * (G * G), G * G) : k;
-            const unsigned av = (unsigned)__builtin_amdgcn_readfirstlane((int)any[r]);      // workgroup-uniform
-            if ((TWO ? (av >> (8 * ph)) & 0xffu : av) == 0u) continue;
-            __syncthreads();                                       // readers of the previous region done
-            visit(r, ph);
-        }
-    } else {
-        for (int kk = 0; kk < (TWO ? 2 * NR : NR); ++kk) {
-            const int ph = TWO && kk >= NR, k = kk - (ph ? NR : 0);
-            const int r = OWN_FIRST ? mc_region_visit(k, face * (G * G), G * G) : k;
-            __syncthreads();                                       // binning done / readers of the previous region done
-            if ((TWO ? (any[r] >> (8 * ph)) & 0xffu : any[r]) == 0u) continue;      // workgroup-uniform
-            visit(r, ph);
-        }
+    // A barrier ahead of each staging: binning done / readers of the previous region done.  RUNS: it runs for the flagged regions only
+    // (once per visited region instead of once per region of the level, and one for binning); any[] is final after binning, so the skip
+    // needs none.  (A 64-bit mask of the visited regions kept across the passes, or a ballot search for the next one, spills VGPRs at the
+    // 64-VGPR budget of the quarter-face shape.)
+    if (RUNS) __syncthreads();
+    for (int kk = 0; kk < (TWO ? 2 * NR : NR); ++kk) {             // TWO: all regions for the head words, then all for the tail words (one
+        const int ph = TWO && kk >= NR, k = kk - (ph ? NR : 0);    // counter: a second loop variable costs a scalar register across the passes)
+        const int r = OWN_FIRST ? mc_region_visit(k, face * (G * G), G * G) : k;
+        if (!RUNS) __syncthreads();
+        const unsigned av = RUNS ? (unsigned)__builtin_amdgcn_readfirstlane((int)any[r]) : any[r];      // workgroup-uniform
+        if ((TWO ? (av >> (8 * ph)) & 0xffu : av) == 0u) continue;
+        if (RUNS) __syncthreads();
+        visit(r, ph);
     }
 
     // ---- 3. completeness check; a wave that missed a sample recomputes its slice with direct loads ----
@@ -776,52 +805,24 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     // RUNS: cnt per lane; a wave recomputes when any lane's count is off (a stronger test than the total)
     [[maybe_unused]] const unsigned long long st3 = STAMP();
     const bool healed = RUNS ? __builtin_amdgcn_ballot_w64(cnt != (unsigned)q.expect[s]) != 0ull : cnt != 64u * (unsigned)q.expect[s];
-    if (healed) {
-        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)p.src, 0, (int)p.src_bytes, 0x00020000);
-        ar = 0.0f; ag = 0.0f; ab = 0.0f;
-        for (int w = s; w < NW; w += REG_S) {
-            const int i1 = min((w << 5) + 32, p.n_tab);
-            for (int i = w << 5; i < i1; ++i) {
-                const v4f e = tab[i];
-                f3 L;
-                L.x = fmaf(e.x, B.x, fmaf(e.y, T.x, e.z * R.x));
-                L.y = fmaf(e.x, B.y, fmaf(e.y, T.y, e.z * R.y));
-                L.z = fmaf(e.x, B.z, fmaf(e.y, T.z, e.z * R.z));
-                f3 c = sample_bordered<false>(rs, L, nf, off, nb, nb * 16);
-                ar = fmaf(e.w, c.x, ar); ag = fmaf(e.w, c.y, ag); ab = fmaf(e.w, c.z, ab);
-            }
-        }
-    }
+    if (healed) heal_slice<REG_S>(p, tab, NW, s, R, T, B, ar, ag, ab);
     if (q.stats && (tid & 63) == 0) {
         if (healed) atomicAdd(&q.stats[0], 1ull);
         atomicAdd(&q.stats[1], 1ull);
     }
 
-    // ---- 4. combine the slices (fixed tree; one slice: nothing to combine, red[] only hands the sums to the store) and store ----
+    // ---- 4. combine the slices and store ----
     __syncthreads();                                               // everybody is done with the staged region
     if (absorb_on && q.stats && tid < 3 && skc[tid]) atomicAdd(&q.stats[6 + tid], (unsigned long long)skc[tid]);
     float* red = (float*)smem_r;
-    red[(s * REG_TX + t) * 3 + 0] = ar;
-    red[(s * REG_TX + t) * 3 + 1] = ag;
-    red[(s * REG_TX + t) * 3 + 2] = ab;
-    __syncthreads();
-    for (int stride = REG_S / 2; stride >= 1; stride >>= 1) {
-        if (s < stride) {
-            const int a2 = (s * REG_TX + t) * 3, b2 = ((s + stride) * REG_TX + t) * 3;
-            red[a2 + 0] += red[b2 + 0];
-            red[a2 + 1] += red[b2 + 1];
-            red[a2 + 2] += red[b2 + 2];
-        }
-        __syncthreads();
-    }
+    reduce_slices<REG_TX, REG_S>(red, s, t, ar, ag, ab);
     // The texel's coordinates are formed AGAIN from the thread index (opaque to the optimiser) instead of being kept alive across
     // the passes: at the 64-VGPR budget the quarter-face instantiation otherwise spills them (4 VGPRs, 16 bytes of scratch per lane
     // and tile: harmless in time, but rocprofv3's WRITE_SIZE of C4 mip 1 read 853 MB against 403 MB of output).
-    int tid_o = tid;
+    int tid_o = tid, x_o, y_o;
     asm volatile("" : "+v"(tid_o));
-    const int t_o = tid_o % REG_TX, q8_o = t_o >> 6, l8_o = t_o & 63;
-    const int x_o = tx * TILE + (q8_o & (QW - 1)) * 8 + (l8_o & 7);
-    const int y_o = p.y0 + ty * TILE + (q8_o >> QSH) * 8 + (l8_o >> 3);
+    const int t_o = tid_o % REG_TX;
+    texel_of_thread<TILE>(p, tx, ty, t_o, x_o, y_o);
     if (x_o < p.size && y_o < p.y0 + p.rows && s == 0) {
         float4 o;
         o.x = red[t_o * 3 + 0] / p.divisor; o.y = red[t_o * 3 + 1] / p.divisor; o.z = red[t_o * 3 + 2] / p.divisor; o.w = p.alpha;
@@ -844,29 +845,20 @@ extern "C" int pbrk_mc_region_order(int face, int G, int k) {
 static unsigned long long* g_reg_stats = nullptr;      // device counters, enabled by PBR_MC_STATS=1
 #define REG_STATS_BYTES 128                            // 16 slots (RegArgs::stats)
 
+// out[0 .. count) = the device counters RegArgs::stats[first_slot ..]
+static int read_stats(unsigned long long* out, int first_slot, int count) {
+    if (!g_reg_stats || !out) return PBRK_E_ARG;
+    return hipMemcpy(out, g_reg_stats + first_slot, (size_t)count * 8, hipMemcpyDeviceToHost) == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
+}
 extern "C" int pbrk_mc_region_stats(unsigned long long* out2, int reset) {
-    if (!g_reg_stats || !out2) return PBRK_E_ARG;
-    if (hipMemcpy(out2, g_reg_stats, 16, hipMemcpyDeviceToHost) != hipSuccess) return PBRK_E_LAUNCH;
-    if (reset && hipMemset(g_reg_stats, 0, REG_STATS_BYTES) != hipSuccess) return PBRK_E_LAUNCH;
-    return PBRK_OK;
+    const int rc = read_stats(out2, 0, 2);
+    if (rc != PBRK_OK) return rc;
+    return (reset && hipMemset(g_reg_stats, 0, REG_STATS_BYTES) != hipSuccess) ? PBRK_E_LAUNCH : PBRK_OK;
 }
-extern "C" int pbrk_mc_region_skip_stats(unsigned long long* out3) {      // absorbed words: see RegArgs::stats [6..8]
-    if (!g_reg_stats || !out3) return PBRK_E_ARG;
-    return hipMemcpy(out3, g_reg_stats + 6, 24, hipMemcpyDeviceToHost) == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
-}
-extern "C" int pbrk_mc_region_window_stats(unsigned long long* out1) {      // samples run through the test-free body (sum over tiles)
-    if (!g_reg_stats || !out1) return PBRK_E_ARG;
-    return hipMemcpy(out1, g_reg_stats + 5, 8, hipMemcpyDeviceToHost) == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
-}
-extern "C" int pbrk_mc_region_flag_stats(unsigned long long* out3) {
-    if (!g_reg_stats || !out3) return PBRK_E_ARG;
-    return hipMemcpy(out3, g_reg_stats + 2, 24, hipMemcpyDeviceToHost) == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
-}
-
-extern "C" int pbrk_mc_region_phase_stats(unsigned long long* out5) {      // PBR_MC_PHASE_STAMPS builds; zeros otherwise (RegArgs::stats [9..13])
-    if (!g_reg_stats || !out5) return PBRK_E_ARG;
-    return hipMemcpy(out5, g_reg_stats + 9, 40, hipMemcpyDeviceToHost) == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
-}
+extern "C" int pbrk_mc_region_skip_stats(unsigned long long* out3) { return read_stats(out3, 6, 3); }        // absorbed words: see RegArgs::stats [6..8]
+extern "C" int pbrk_mc_region_window_stats(unsigned long long* out1) { return read_stats(out1, 5, 1); }      // samples run through the test-free body (sum over tiles)
+extern "C" int pbrk_mc_region_flag_stats(unsigned long long* out3) { return read_stats(out3, 2, 3); }
+extern "C" int pbrk_mc_region_phase_stats(unsigned long long* out5) { return read_stats(out5, 9, 5); }       // PBR_MC_PHASE_STAMPS builds; zeros otherwise (RegArgs::stats [9..13])
 
 template <int RS, bool SUB, int TILE, bool RUNS = false, bool LEAN = false>
 static void launch_region_t(const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
@@ -1033,13 +1025,20 @@ extern "C" int pbrk_mc_launch_cut_stats(int* out6) {
     return PBRK_OK;
 }
 
+// the 66^2 shapes: the round-5 loop (pbrk_mc_set_runs) or the one before it
+template <bool SUB, int TILE, bool LEAN>
+static void launch_66(const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
+    if (g_mc_runs) launch_region_t<66, SUB, TILE, true, LEAN>(q, grid, lds, st);
+    else launch_region_t<66, SUB, TILE, false, LEAN>(q, grid, lds, st);
+}
+
 template <bool LEAN>
 static void launch_shape(int RS, int tile, const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
-    if (tile == 32) { if (g_mc_runs) launch_region_t<66, true, 32, true, LEAN>(q, grid, lds, st); else launch_region_t<66, true, 32, false, LEAN>(q, grid, lds, st); }
+    if (tile == 32) launch_66<true, 32, LEAN>(q, grid, lds, st);
     else if (RS == 18) launch_region_t<18, false, 16, false, LEAN>(q, grid, lds, st);
     else if (RS == 34) launch_region_t<34, false, 16, false, LEAN>(q, grid, lds, st);
-    else if (q.G == 1) { if (g_mc_runs) launch_region_t<66, false, 16, true, LEAN>(q, grid, lds, st); else launch_region_t<66, false, 16, false, LEAN>(q, grid, lds, st); }
-    else { if (g_mc_runs) launch_region_t<66, true, 16, true, LEAN>(q, grid, lds, st); else launch_region_t<66, true, 16, false, LEAN>(q, grid, lds, st); }
+    else if (q.G == 1) launch_66<false, 16, LEAN>(q, grid, lds, st);
+    else launch_66<true, 16, LEAN>(q, grid, lds, st);
 }
 
 // Which tile serves a level (header 2h): a function of the level alone -- n_src, n_tab, the output size -- never of the dispatch's faces
@@ -1067,7 +1066,7 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
     else { RS = 66; q.RC = 65; q.G = (a.n_src + 1 + 64) / 65; }
     q.NR = 6 * q.G * q.G;
     q.NW = (a.n_tab + 31) / 32;
-    // counters, region flags, any[], dmax, proved-sample flags, (absorb) wmax[], rmax[]; where the last two do not fit, the level runs
+    // the LDS layout at the top of k_mc_region: counters, region flags, any[], dmax, proved-sample flags, (absorb) wmax[], rmax[]; where the last two do not fit, the level runs
     // without them.  The absorbed-word skip is compiled for the 66^2 shapes only (k_mc_region, ABS).
     q.absorb = RS == 66 ? g_mc_absorb : 0;
     const size_t lds_fixed = (size_t)RS * RS * 16 + (4 + (size_t)q.NR * q.NW + q.NR + 1 + q.NW) * 4;
