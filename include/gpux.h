@@ -55,6 +55,15 @@ GPU_API uint64_t GPUX_TextureMipBytes(const GPU_Texture* texture, uint32_t mip_l
  * writes it (memory written behind the backend's back is not followed).  This copies one level of the decoded image
  * (width x height x 4 bytes, tight rows) into a buffer, for tests; any other texture is an error. */
 GPU_API void GPUX_OpCopyDecodedTextureMipToBuffer(GPU_Graph* graph, GPU_Texture* src, uint32_t mip_level, GPU_Buffer* dst, uint32_t dst_offset);
+/* K17: the SH9 form of an environment's diffuse lighting (csrc/sh_core.h), as graph ops so that they order with
+ * everything else recorded on the graph.  Source and target are square RGBA32F cubemaps.
+ * Project: faces [face0, face1) x rows [row0, row1) of one level -> 27 doubles (216 bytes, index 3 k + c; offset a multiple of 8):
+ * the partial sum of those rows -- callers add partials themselves.  Deterministic: the same op gives the same bytes.
+ * IrradianceFromSH9: the whole level from 27 doubles, E / (2 pi) like K3, alpha 0, NOT clamped (the series may ring negative).
+ * Both are plain launches and may be captured under GPUX_SetGraphReplay(1). */
+GPU_API void GPUX_OpProjectSH9(GPU_Graph* graph, GPU_Texture* cube, uint32_t mip_level, uint32_t face0, uint32_t face1, uint32_t row0, uint32_t row1,
+                               GPU_Buffer* dst, uint32_t dst_offset);
+GPU_API void GPUX_OpIrradianceFromSH9(GPU_Graph* graph, GPU_Buffer* src, uint32_t src_offset, GPU_Texture* irradiance_cube, uint32_t mip_level);
 GPU_API void* GPUX_TextureDevicePtr(GPU_Texture* texture, uint32_t mip_level);            /* for RCCL / interop */
 GPU_API void* GPUX_BufferDevicePtr(GPU_Buffer* buffer);
 GPU_API void* GPUX_GraphStream(GPU_Graph* graph);                                         /* hipStream_t */

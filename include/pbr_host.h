@@ -58,6 +58,21 @@ void PBR_GenIrradianceMap(GPU_Texture* tex_env_cube, GPU_Texture* irradiance_map
 /* render.cpp:542-589; min_size = 16 reproduces the reference's `if (size < 16) break;`, 1 runs the whole chain */
 void PBR_GenPrefilteredEnvMap(GPU_Texture* tex_env_cube, GPU_Texture* tex_specular_env_map, uint32_t min_size);
 void PBR_GenBRDFIntegrationMap(GPU_Texture* brdf_lut);                                       /* render.cpp:591-619 */
+
+/* ---- K17 (no reference counterpart): the nine-coefficient spherical-harmonic form of the environment's diffuse
+ * lighting -- the 27 numbers other IBL bakers emit and engines consume in place of an irradiance cube.  Contract (csrc/sh_core.h):
+ * coef[3 k + c] = sum over ALL texels of the level of L_c Y_k(d) domega with the exact texel solid angle, fp64; real basis without
+ * Condon-Shortley phase in the order 1, y, z, x, xy, yz, 3zz-1, xz, xx-yy; irradiance in the reference's E / (2 pi) normalisation
+ * (a constant environment c gives c / 2), NOT clamped: under a strong sun the series rings and may go negative.
+ * PBR_GenIrradianceMap (K3: 1024 samples of LOD 6) stays the reference path and the default everywhere. ---- */
+int  PBR_ProjectSH9(GPU_Texture* cube, uint32_t mip_level, double out[27]);     /* blocking (own graph + mapped buffer); 0 on success */
+/* project level src_mip_level and write mip 0 of irradiance_map from it; PBR_MakeLightingPass* binds the result unchanged */
+void PBR_GenIrradianceMapSH(GPU_Texture* tex_env_cube, uint32_t src_mip_level, GPU_Texture* irradiance_map);
+void PBR_EvalSH9Irradiance(const double coef[27], const float n[3], float rgb[3]);   /* host, the same contract; n is normalised in double */
+/* text: one '#' line naming basis order and convention, then 9 lines of 3 values (%.17g: the bits survive).  0 on success; the
+ * reader refuses anything else (a missing or truncated line, a token that is not a number, trailing text). */
+int  PBR_WriteSH9File(const char* path, const double coef[27]);
+int  PBR_ReadSH9File(const char* path, double coef[27]);
 /* Records (does not submit) the dispatches of an explicit unit list into `graph`: the sharded form of the above.
  * `arena` receives the per-unit descriptor sets (caller resets it after GPU_GraphWait). */
 typedef struct PBR_IBLPipelines PBR_IBLPipelines;

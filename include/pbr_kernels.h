@@ -369,6 +369,19 @@ int pbrk_voxelize_resolve(const PbrkVoxelizeArgs* args, void* stream);  /* K14.r
 enum { PBRK_BC1_RGB = 0, PBRK_BC1_RGBA = 1, PBRK_BC3 = 2, PBRK_BC5 = 3 };
 int pbrk_bc_decode(int format, const void* blocks, int width, int height, void* rgba8, void* stream);
 
+/* ---- K17: the nine-coefficient spherical-harmonic (SH9) form of the environment's diffuse lighting (the reference
+ *      has none).  Contract -- directions, exact texel solid angles, basis order, the E / (2 pi) normalisation of
+ *      gen_irradiance_map.glsl:84-97, no clamp: csrc/sh_core.h, DESIGN.md K17.  n and size: any value from 1 to 16384.
+ *      project: rows [y0, y1) of faces [face0, face1) of one level -> double[27] (index 3 k + c), a partial sum that callers add
+ *      themselves; two launches (one 27-double partial per workgroup into `scratch`, then one workgroup adds them in index order),
+ *      no floating-point atomics: equal arguments give equal bytes.  scratch: pbrk_sh9_scratch_bytes(n) bytes, 8-byte aligned.
+ *      irradiance: the same sub-range of a size^2 level from 27 device doubles, alpha 0.  Nothing is read back. ---- */
+size_t pbrk_sh9_scratch_bytes(int n);
+int pbrk_sh9_project(const void* level /* float4 [6][n][n] */, int n, int face0, int face1, int y0, int y1,
+                     void* scratch, double* out27_device, void* stream);
+int pbrk_sh9_irradiance(const double* coef27_device, void* out_level /* float4 [6][size][size] */, int size,
+                        int face0, int face1, int y0, int y1, void* stream);
+
 /* ---- diagnostics: the device samplers of the widened passes evaluated at caller-supplied coordinates, so that tests can feed them
  *      NaN / inf / 1e30 / boundary values directly (a ray that has marched far away must never become an out-of-bounds read).
  *      which: 0 = LIGHTGRID (RGBA16F n^3, coords xyz), 1 = sampler2DShadow (R32F w x h, coords u, v, ref; result in out[0]),

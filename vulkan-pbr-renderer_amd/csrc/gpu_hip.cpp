@@ -96,7 +96,7 @@ struct GPU_GraphicsPipeline { GPU_PipelineLayout* layout; GPU_RenderPass* pass; 
                               uint32_t vertex_stride = 0; /* raster kinds: bytes per vertex (gpu_vulkan.c:1745-1762) */
                               const struct RasterKind* raster = nullptr; /* K12 / K13 / K14: the row of its raster kind */ };
 
-enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster, Op_CopyDecodedT2B };
+enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster, Op_CopyDecodedT2B, Op_ProjectSH9, Op_IrradianceSH9 };
 // one draw of a raster job: job triangles from first_tri on, matrices from the set's GLOBALS, the buffers and the target its kind
 // names (K12 / K13: the buffers bound at the draw; K14: SSBO0 / SSBO1 of the set, first_index = its first vertex) and the pushed
 // constants (K13 reads them: the skybox rebinds both inside the pass)
@@ -158,6 +158,7 @@ struct GPU_Graph {
     BufferImpl* vertex_buffer = nullptr; BufferImpl* index_buffer = nullptr;     // GPU_OpBindVertexBuffer / GPU_OpBindIndexBuffer
     int raster_op = -1;                            // index in ops of the raster job of the open render pass (-1: none yet)
     std::vector<RasterScratch> raster; size_t raster_used = 0;
+    void* sh_scratch = nullptr; size_t sh_scratch_bytes = 0;   // K17 partials (GPUX_OpProjectSH9): sized at record time, kept across submissions
     // hipGraph replay (GPUX_SetGraphReplay): the executable graph of the previous submission, updated in place when the
     // next one has the same shape
     hipGraphExec_t exec = nullptr;
@@ -1212,6 +1213,7 @@ GPU_API void GPU_DestroyGraph(GPU_Graph* g) {
     if (g->span_b) (void)hipEventDestroy(g->span_b);
     if (g->exec) (void)hipGraphExecDestroy(g->exec);
     for (RasterScratch& r : g->raster) { (void)hipFree(r.dev); (void)hipFree(r.draws_dev); (void)hipHostFree(r.draws_host); }
+    (void)hipFree(g->sh_scratch);
     if (G.last_submitted == g) G.last_submitted = nullptr;        // idle by contract (gpu.h:453): nothing left to order against
     (void)hipStreamDestroy(g->stream);
     delete g;
@@ -1575,6 +1577,48 @@ GPU_API void GPUX_OpCopyDecodedTextureMipToBuffer(GPU_Graph* g, GPU_Texture* src
     Op op; op.kind = Op_CopyDecodedT2B; op.name = "copy.decoded_texture_to_buffer";
     op.tex = t; op.mip = mip; op.buf = (BufferImpl*)dst; op.off_b = dst_offset; op.size = bytes;
     g->ops.push_back(op);
+}
+
+// ---- K17: SH9 projection of a cube level into a buffer, and the irradiance cube of nine coefficients ----
+// op.tex / op.mip = the cube level, op.buf / op.off_b = the 27 doubles, faces [face0, face1) x rows [row0, row1)
+static bool record_sh9(GPU_Graph* g, OpKind kind, const char* name, GPU_Texture* cube, uint32_t mip, GPU_Buffer* buf, uint32_t offset, const char* fn) {
+    GPU_REQUIRE(g->in_pass == nullptr, false, "%s: inside a render pass", fn);
+    GPU_REQUIRE(cube && buf && mip < cube->mip_level_count, false, "%s: bad arguments", fn);
+    GPU_REQUIRE(is_f4_cube((TextureImpl*)cube), false, "%s: the texture must be a square RGBA32F cubemap", fn);
+    GPU_REQUIRE((offset % 8) == 0, false, "%s: buffer offset %u is not a multiple of 8", fn, offset);
+    GPU_REQUIRE((uint64_t)offset + 27 * sizeof(double) <= buf->size, false, "%s: buffer too small (%u bytes for 216 at offset %u)", fn, buf->size, offset);
+    Op op; op.kind = kind; op.name = name;
+    op.tex = (TextureImpl*)cube; op.mip = mip; op.buf = (BufferImpl*)buf; op.off_b = offset;
+    op.face0 = 0; op.face1 = 6; op.row0 = 0; op.row1 = mip_dim(cube->width, mip);
+    g->ops.push_back(op);
+    return true;
+}
+GPU_API void GPUX_OpProjectSH9(GPU_Graph* g, GPU_Texture* cube, uint32_t mip, uint32_t face0, uint32_t face1, uint32_t row0, uint32_t row1,
+                               GPU_Buffer* dst, uint32_t dst_offset) {
+    REC_GUARD(g);
+    const char* fn = "GPUX_OpProjectSH9";
+    GPU_REQUIRE_V(cube && mip < cube->mip_level_count, "%s: bad arguments", fn);
+    const uint32_t n = mip_dim(cube->width, mip);
+    GPU_REQUIRE_V(face0 < face1 && face1 <= 6 && row0 < row1 && row1 <= n, "%s: empty or out-of-range faces [%u, %u) x rows [%u, %u) of a %u^2 level", fn,
+                  face0, face1, row0, row1, n);
+    GPU_REQUIRE_V(n <= 16384, "%s: levels above 16384^2 are not implemented", fn);
+    if (!record_sh9(g, Op_ProjectSH9, "K17.sh_project", cube, mip, dst, dst_offset, fn)) return;
+    { Op& op = g->ops.back(); op.face0 = face0; op.face1 = face1; op.row0 = row0; op.row1 = row1; }
+    // the partials' scratch grows here, not at submit: nothing allocates inside a captured submission, and the graph is idle while it records
+    const size_t need = pbrk_sh9_scratch_bytes((int)n);
+    if (need > g->sh_scratch_bytes) {
+        void* p = nullptr;
+        if (hipMalloc(&p, need) != hipSuccess) { (void)hipGetLastError(); g->ops.pop_back(); gpu_fail("%s: allocation of the partials' scratch (%zu bytes) failed", fn, need); return; }
+        (void)hipFree(g->sh_scratch);
+        g->sh_scratch = p; g->sh_scratch_bytes = need;
+    }
+}
+GPU_API void GPUX_OpIrradianceFromSH9(GPU_Graph* g, GPU_Buffer* src, uint32_t src_offset, GPU_Texture* irradiance_cube, uint32_t mip) {
+    REC_GUARD(g);
+    const char* fn = "GPUX_OpIrradianceFromSH9";
+    GPU_REQUIRE_V(irradiance_cube && mip < irradiance_cube->mip_level_count, "%s: bad arguments", fn);
+    GPU_REQUIRE_V(mip_dim(irradiance_cube->width, mip) <= 16384, "%s: levels above 16384^2 are not implemented", fn);
+    record_sh9(g, Op_IrradianceSH9, "K17.sh_irradiance", irradiance_cube, mip, src, src_offset, fn);
 }
 
 GPU_API void GPU_OpGenerateMipmaps(GPU_Graph* g, GPU_Texture* tex) {
@@ -2082,6 +2126,20 @@ static void exec_mipgen(GPU_Graph* g, Op& op, size_t& ev_used) {
     op.tex->bordered_valid = false;
 }
 
+// K17: two launches (partials, then their sum in index order) resp. one; no read-back, nothing allocated
+static void exec_sh9(GPU_Graph* g, Op& op, size_t& ev_used) {
+    const int n = (int)mip_dim(op.tex->base.width, op.mip);
+    void* level = (char*)op.tex->dev + op.tex->mip_offset[op.mip];
+    double* coef = (double*)((char*)op.buf->dev + op.off_b);
+    timed(g, op.name, ev_used, [&] {
+        int rc = op.kind == Op_ProjectSH9
+                     ? pbrk_sh9_project(level, n, (int)op.face0, (int)op.face1, (int)op.row0, (int)op.row1, g->sh_scratch, coef, g->cur)
+                     : pbrk_sh9_irradiance(coef, level, n, (int)op.face0, (int)op.face1, (int)op.row0, (int)op.row1, g->cur);
+        if (rc != PBRK_OK) gpu_fail("%s launch failed (%d)", op.name.c_str(), rc);
+    });
+    if (op.kind == Op_IrradianceSH9) op.tex->bordered_valid = false;
+}
+
 static void exec_blit(GPU_Graph* g, Op& op, size_t& ev_used) {
     hipStream_t st = g->cur;
     if (op.folded) { op.tex2->bordered_valid = false; op.tex2->lut_cells_valid = false; return; }   // its consumer reads the source (fold_blits)
@@ -2205,6 +2263,7 @@ static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
     case Op_Blit: exec_blit(g, op, ev_used); return;
     case Op_Clear: exec_clear(g, op, ev_used); return;
     case Op_CopyB2B: case Op_CopyB2T: case Op_CopyT2B: case Op_CopyDecodedT2B: exec_copy(g, op, ev_used); return;
+    case Op_ProjectSH9: case Op_IrradianceSH9: exec_sh9(g, op, ev_used); return;
     }
 }
 
@@ -2224,6 +2283,7 @@ static bool op_replayable(const Op& op) {
     case Op_Blit: return true;
     case Op_CopyB2B: case Op_CopyB2T: case Op_CopyT2B: case Op_CopyDecodedT2B: return false;          // host pointers may be involved: keep them out of captures
     case Op_Raster: return false;                                             // its draw table is uploaded from pinned staging at submit
+    case Op_ProjectSH9: case Op_IrradianceSH9: return true;                   // plain launches on device-visible pointers; the scratch exists since recording
     case Op_Clear: return fill_texel_ok(op.tex->texel_bytes);
     case Op_Shade: {
         if (is_post_kernel(op.gpipe->kernel)) return true;
@@ -2247,7 +2307,7 @@ static bool graph_replayable(GPU_Graph* g) {
     for (const Op& op : g->ops) {
         if (!op_replayable(op)) return false;
         switch (op.kind) {
-        case Op_Clear: case Op_MipGen: written.push_back(op.tex); break;
+        case Op_Clear: case Op_MipGen: case Op_IrradianceSH9: written.push_back(op.tex); break;
         case Op_Blit: if (op.tex2) written.push_back(op.tex2); break;          // tex = source, tex2 = destination
         case Op_Dispatch: { Slot* o = named_slot(op.set, "IMG0"); if (o && o->tex) written.push_back(o->tex); break; }
         case Op_Shade: {
@@ -2338,6 +2398,8 @@ static bool op_access(const Op& op, std::vector<TextureImpl*>& r, std::vector<Te
     case Op_MipGen: r.push_back(op.tex); w.push_back(op.tex); return true;
     case Op_Blit: r.push_back(op.tex); w.push_back(op.tex2); return true;
     case Op_Clear: w.push_back(op.tex); return true;
+    case Op_ProjectSH9: r.push_back(op.tex); return false;                     // its buffer is not followed: ends the walk like any buffer
+    case Op_IrradianceSH9: w.push_back(op.tex); return false;
     default: return false;
     }
 }

@@ -2,7 +2,7 @@
  * pbr_demo.c -- headless C driver of the hot path through the GPU_* boundary (what main.cpp:35-51 +
  * HotreloadShaders + BuildRenderCommands do for this path, without window / mesh import / raster passes).
  *
- *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster [gridview]]]]]
+ *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster [gridview]]]]] [sh9 FILE]
  *
  * Loads a vertical-strip HDR cube (asset_import.cpp:17-27), runs the IBL precompute (render.cpp:505-619),
  * shades a flat synthetic G-buffer (a metallic floor under the sky), then runs three frames of the per-frame chain
@@ -15,6 +15,8 @@
  * voxelise pass (render.cpp:995-1020, 1039-1056) draw that mesh into it; every other output is unchanged.  With `gridview` as the
  * tenth argument (after `raster`) one more frame is rendered with Globals.visualize_lightgrid set -- the reference's G key, kernel
  * K16: the voxelised mesh itself -- and its checksum is printed as gridview_bits_sum; the other lines stay as they are.
+ * With `sh9 FILE` as the LAST two arguments (after whichever of the above are given) the SH9 coefficients of level 0 of the loaded
+ * environment (K17) are written to FILE and their sum is printed as sh9_sum; the other lines stay as they are.
  */
 #include "pbr_host.h"
 
@@ -80,6 +82,8 @@ static PBR_Mesh* demo_mesh(PBR_Material** material_out) {
 }
 
 int main(int argc, char** argv) {
+    const char* sh9_path = NULL;
+    if (argc >= 4 && strcmp(argv[argc - 2], "sh9") == 0) { sh9_path = argv[argc - 1]; argc -= 2; }
     if (argc < 2) { fprintf(stderr, "usage: %s cube_strip.hdr [irr lut spec min_size [width height]]\n", argv[0]); return 2; }
     uint32_t irr = argc > 2 ? (uint32_t)atoi(argv[2]) : 32, lut = argc > 3 ? (uint32_t)atoi(argv[3]) : 256;
     uint32_t spec = argc > 4 ? (uint32_t)atoi(argv[4]) : 256, min_size = argc > 5 ? (uint32_t)atoi(argv[5]) : 16;
@@ -90,6 +94,12 @@ int main(int argc, char** argv) {
     GPU_Texture* tex_env_cube = PBR_MakeTextureFromHDRIFile(argv[1]);        /* main.cpp:47 */
     if (!tex_env_cube) return 1;
     printf("env_size %u\nenv_mips %u\n", tex_env_cube->width, tex_env_cube->mip_level_count);
+    if (sh9_path) {
+        double coef[27], sum = 0.0;
+        if (PBR_ProjectSH9(tex_env_cube, 0, coef) != 0 || PBR_WriteSH9File(sh9_path, coef) != 0) { fprintf(stderr, "sh9: cannot write %s\n", sh9_path); return 1; }
+        for (int i = 0; i < 27; ++i) sum += coef[i];
+        printf("sh9_sum %.17g\n", sum);
+    }
 
     PBR_IBLMaps maps;
     PBR_MakeIBLMaps(&maps, irr, lut, spec);                                  /* render.cpp:794-796 */

@@ -319,6 +319,15 @@ PROTOTYPES = {
     "pbrk_voxelize_cover": (C.c_int, [VP, VP]), "pbrk_voxelize_resolve": (C.c_int, [VP, VP]),
     "pbrk_mip_chain_rgba8": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, VP]),
     "pbrk_bc_decode": (C.c_int, [C.c_int, VP, C.c_int, C.c_int, VP, VP]),
+    # --- K17: SH9 projection / irradiance ---
+    "pbrk_sh9_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "pbrk_sh9_project": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP, VP]),
+    "pbrk_sh9_irradiance": (C.c_int, [VP, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP]),
+    "GPUX_OpProjectSH9": (None, [VP, TexP, U32, U32, U32, U32, U32, BufP, U32]),
+    "GPUX_OpIrradianceFromSH9": (None, [VP, BufP, U32, TexP, U32]),
+    "PBR_ProjectSH9": (C.c_int, [TexP, U32, C.POINTER(C.c_double)]), "PBR_GenIrradianceMapSH": (None, [TexP, U32, TexP]),
+    "PBR_EvalSH9Irradiance": (None, [C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "PBR_WriteSH9File": (C.c_int, [C.c_char_p, C.POINTER(C.c_double)]), "PBR_ReadSH9File": (C.c_int, [C.c_char_p, C.POINTER(C.c_double)]),
 }
 
 _LIB = None
@@ -429,6 +438,29 @@ def read_decoded_mip(tex, mip=0):
     w, h = max(1, t.width >> mip), max(1, t.height >> mip)
     raw = _read_back(lambda g, buf: L.GPUX_OpCopyDecodedTextureMipToBuffer(g, tex, mip, buf, 0), w * h * 4)
     return np.frombuffer(raw, np.uint8).reshape(h, w, 4).copy()
+
+
+def project_sh9(tex, mip, faces=(0, 6), rows=None):
+    """SH9 coefficients (K17) of rows [rows) of faces [faces) of one level of an RGBA32F cube -> float64 [9][3] (k, channel).
+    A sub-range gives that range's partial sum; rows=None is the whole level."""
+    L = lib()
+    n = max(1, tex.contents.width >> mip)
+    r0, r1 = (0, n) if rows is None else rows
+    raw = _read_back(lambda g, buf: L.GPUX_OpProjectSH9(g, tex, mip, faces[0], faces[1], r0, r1, buf, 0), 216)
+    return np.frombuffer(raw, np.float64).reshape(9, 3).copy()
+
+
+def irradiance_from_sh9(coef, tex, mip=0):
+    """Writes one level of an RGBA32F cube with the irradiance (E / 2 pi, alpha 0, not clamped) of 27 SH9 coefficients."""
+    L = lib()
+    coef = np.ascontiguousarray(coef, np.float64).reshape(27)
+    buf = L.GPU_MakeBuffer(216, BufferFlag_CPU, coef.ctypes.data_as(VP))
+    g = L.GPU_MakeGraph()
+    L.GPUX_OpIrradianceFromSH9(g, buf, 0, tex, mip)
+    L.GPU_GraphSubmit(g)
+    L.GPU_GraphWait(g)
+    L.GPU_DestroyGraph(g)
+    L.GPU_DestroyBuffer(buf)
 
 
 def parse_dds(data: bytes):
