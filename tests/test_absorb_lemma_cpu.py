@@ -7,27 +7,10 @@ from fractions import Fraction as F
 
 import numpy as np
 
+from f32_exact import round_f32
+
 f32 = np.float32
 TWO_M25 = F(1, 2 ** 25)
-
-
-def round_f32(q):
-    """Exact value q rounded to the nearest fp32, ties to even (no overflow handling: callers stay in range)."""
-    if q == 0:
-        return F(0)
-    sign = -1 if q < 0 else 1
-    a = abs(q)
-    e = a.numerator.bit_length() - a.denominator.bit_length()
-    while F(2) ** e > a:
-        e -= 1
-    while F(2) ** (e + 1) <= a:
-        e += 1
-    e = max(e, -126)                                         # subnormals share the spacing of 2^-126
-    ulp = F(2) ** (e - 23)
-    k, r = divmod(a, ulp)
-    if r > ulp / 2 or (r == ulp / 2 and k % 2 == 1):
-        k += 1
-    return sign * k * ulp
 
 
 def fma_f32(x, y, acc):

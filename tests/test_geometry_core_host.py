@@ -14,7 +14,7 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(ROOT, "vulkan-pbr-renderer_amd", "python"))
 import geometry_raster_ref as G  # noqa: E402
-import test_gpu_geometry as T  # noqa: E402  (scene builders only; nothing there touches the GPU at import)
+import geometry_scenes as T  # noqa: E402
 
 
 class Tex(C.Structure):

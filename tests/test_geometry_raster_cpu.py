@@ -8,16 +8,10 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import geometry_raster_ref as G  # noqa: E402
 import sun_raster_ref as R  # noqa: E402
+from geometry_scenes import perspective  # noqa: E402
 
 f32 = np.float32
-
-
-def _perspective(W, H, eye=(0.0, 0.0, 0.0), fov=70.0, near=0.1, far=100.0):
-    t = 1.0 / np.tan(np.radians(fov) / 2)
-    P = np.array([[t * H / W, 0, 0, 0], [0, -t, 0, 0], [0, 0, far / (near - far), near * far / (near - far)], [0, 0, -1, 0]], np.float64)
-    V = np.eye(4)
-    V[:3, 3] = -np.asarray(eye, np.float64)
-    return (P @ V).T.astype(f32).ravel(), t
+T_FOV = 1.0 / np.tan(np.radians(70.0) / 2)                   # perspective()'s focal scale at its default field of view
 
 
 def _const_material(rgba_base=(255, 255, 255, 255), size=4):
@@ -94,7 +88,7 @@ def test_near_plane_split_floor():
     """A floor triangle (y = -1) from far in front of the camera to behind it, wider than the guard band: with y_n = t / s for the
     floor point at distance s, exactly the pixel rows with t / far < y_n are covered, at depth (far / (near - far)) (1 - near / s) ... """
     W = H = 16
-    M, t = _perspective(W, H)
+    M, t = perspective(W, H), T_FOV
     near, far = 0.1, 100.0
     pos = [(-4000.0, -1.0, -3000.0), (0.0, -1.0, 500.0), (4000.0, -1.0, -3000.0)]
     outs = []
@@ -169,8 +163,8 @@ def test_velocity_of_a_camera_translation():
     """Static wall at z = -5, old camera moved by (dx, dy, 0): velocity = (t (H/W) dx / 5, -t dy / 5) everywhere, jitter cancelled."""
     W, H = 16, 8
     dx, dy = 0.3, -0.2
-    M, t = _perspective(W, H)
-    Mo, _ = _perspective(W, H, eye=(dx, dy, 0.0))
+    M, t = perspective(W, H), T_FOV
+    Mo = perspective(W, H, eye=(dx, dy, 0.0))
     wall = [(-40.0, 30.0, -5.0), (-40.0, -30.0, -5.0), (40.0, 30.0, -5.0)]
     outs = [G.raster(_targets(W, H), [_draw(M, [wall[k] for k in o], _const_material(), Mo=Mo, jitter=(0.01, -0.02), jitter_prev=(-0.03, 0.015))])
             for o in ((0, 1, 2), (0, 2, 1))]

@@ -2,21 +2,14 @@
 for every format and extent of the CPU tests; the compressed bytes stay what was uploaded; a mip chain filled by copies; errors.
 Textures are at most 64 x 64."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import bc_decode_ref as R  # noqa: E402
+import bc_decode_ref as R
+from gpu_rigs import gpu_format
 
 pytestmark = pytest.mark.gpu
-
-
-def gpu_format(fmt):
-    import pbrhip
-    return {"bc1_rgb": pbrhip.Format_BC1_RGB_UN, "bc1_rgba": pbrhip.Format_BC1_RGBA_UN, "bc3": pbrhip.Format_BC3_RGBA_UN, "bc5": pbrhip.Format_BC5_UN}[fmt]
 
 
 _CASES = R.cases()

@@ -3,21 +3,18 @@ once with RGBA8UN one-level twins uploaded from the numpy restatement of the dec
 byte-identical between the two draws (tolerance 0: the kernels see the same RGBA8 texels either way).  And the .dds loader: files
 written from the golden blocks, loaded with and without their levels, compared with the restatement and drawn with.
 Textures are at most 64 x 64, frames 64 x 48, a few hundred triangles."""
-import ctypes as C
 import os
 import struct
-import sys
 
 import numpy as np
 import pytest
 
+import bc_decode_ref as R
+import voxelize_scenes as S
+from geometry_scenes import random_scene
+from gpu_rigs import GeometryRig as GeoRig, VoxelizeRig as VoxRig, gpu_format
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, HERE)
-import bc_decode_ref as R  # noqa: E402
-import test_gpu_geometry as TG  # noqa: E402
-import test_gpu_voxelize as TV  # noqa: E402
-import voxelize_scenes as S  # noqa: E402
-from test_gpu_bc_decode import gpu_format  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -51,40 +48,6 @@ class Materials:
             self.L.GPU_DestroyTexture(t)
 
 
-class GeoRig(TG.Rig):
-    def __init__(self, L, scene, mats):
-        import pbrhip
-        self.L, self.scene = L, scene
-        W, H = scene["W"], scene["H"]
-        self.gb = pbrhip.PBR_GBuffer()
-        L.PBR_MakeGBuffer(C.byref(self.gb), W, H, pbrhip.Format_RGBA16F)
-        self.pp = L.PBR_MakePostProcess(C.byref(self.gb), W, H, pbrhip.Format_RGBA8UN)
-        self.gp = L.PBR_MakeGeometryPass(C.byref(self.gb), self.pp, W, H)
-        assert self.gp
-        self.mats = mats
-        self.meshes = []
-        for ps in scene["passes"]:
-            for d in ps["draws"]:
-                v, ix = scene["meshes"][d["mesh"]]
-                mesh = pbrhip.make_mesh(v, ix, [(d["first_index"], d["index_count"])])
-                L.PBR_MeshSetPartMaterial(mesh, 0, self.mats[d["material"]])
-                self.meshes.append(mesh)
-        self.bufs = []
-
-
-class VoxRig(TV.Rig):
-    def __init__(self, L, scene, mats):
-        import pbrhip
-        self.L, self.scene = L, scene
-        self.lg = L.PBR_MakeLightgrid(scene["N"])
-        self.sp = L.PBR_MakeSunDepthPass(scene["sun_map"].shape[0])
-        pbrhip.upload_mip(L.PBR_SunDepthTexture(self.sp), 0, scene["sun_map"])
-        self.vp = pbrhip.make_voxelize_pass(self.lg, self.sp)
-        self.mats = mats
-        self.meshes = [pbrhip.make_mesh(v, ix, [(0, len(ix))]) for v, ix in scene["meshes"]]
-        self.tex = L.PBR_LightgridTexture(self.lg)
-
-
 def draw_geometry(L, scene, specs, twins, mats=None):
     m = mats or Materials(L, specs, twins)
     rig = GeoRig(L, scene, m.mats)
@@ -111,7 +74,7 @@ def same_targets(name, a, b):
 
 @pytest.fixture(scope="module")
 def geo_scene():
-    return TG.random_scene(64, 48, 300, seed=0x5EED1501)                      # two draws, materials 0 and 1
+    return random_scene(64, 48, 300, seed=0x5EED1501)                      # two draws, materials 0 and 1
 
 
 def test_geometry_pass_with_bc_materials_equals_rgba8_twins(gpu, geo_scene):

@@ -56,10 +56,9 @@ def test_region_kernel_ragged_row_shards_equal_full(gpu, c2_env, c4_env):
     are no multiple of the 16-row tile, three shards per face) reproduces the whole-level dispatch bit for bit, and no wave had to
     fall back to direct loads (its completeness self-check).  Oracle parity of the same levels: test_c4_* / test_c2_*."""
     import pbrhip
-    from pbrhip import synth
+    from pbrhip import mc, synth
     L = gpu
-    st = (C.c_uint64 * 2)()
-    assert L.pbrk_mc_region_stats(st, 1) in (0, -1)                     # reset (available once the kernel has run with PBR_MC_STATS=1)
+    mc.reset_counters(L)                                                # available once the kernel has run with PBR_MC_STATS=1
     env256 = synth.synth_env(256, seed=0x5EED00AD)
     cases = ((env256, 256, 512, (1,)),            # mip 1: 256^2 from a 16^2 level  -> 18^2 regions
              (c2_env, 1024, 1024, (1, 2)),        # mip 1: 512^2 from 64^2 -> 66^2 whole-face; mip 2: 256^2 from 32^2 -> 34^2
@@ -89,8 +88,8 @@ def test_region_kernel_ragged_row_shards_equal_full(gpu, c2_env, c4_env):
             assert np.array_equal(got.view(np.uint32), full[m].view(np.uint32)), (W, S, m)
             assert float(np.abs(got[..., :3]).max()) > 0.0
         L.PBR_DestroyIBLMaps(C.byref(maps)); L.GPU_DestroyTexture(tex)
-    assert L.pbrk_mc_region_stats(st, 0) == 0
-    assert st[1] > 0 and st[0] == 0, (int(st[0]), int(st[1]))          # the region kernel ran; nothing had to be recomputed
+    st = mc.counters(L, "region")
+    assert st["slices"] > 0 and st["healed"] == 0, (st["healed"], st["slices"])          # the region kernel ran; nothing had to be recomputed
     L.GPU_DestroyGraph(g); L.GPU_DestroyDescriptorArena(arena); L.PBR_DestroyIBLPipelines(pipes)
 
 

@@ -380,7 +380,7 @@ def test_soak_random_environments_and_rows(gpu):
     mip chain bit for bit -- then two environments at sizes the region kernel serves (256 -> 512, 512 -> 1024): three random
     (face, row) pairs of every level >= 256^2 vs the oracle.  The region kernel's completeness counter must stay at zero."""
     import pbrhip, pbr_oracle as O
-    from pbrhip import synth
+    from pbrhip import mc, synth
     L = gpu
     rng = np.random.default_rng(0x50AC)
     sun0 = synth.SUN_DIR.copy()
@@ -425,6 +425,6 @@ def test_soak_random_environments_and_rows(gpu):
             L.PBR_DestroyIBLMaps(C.byref(maps)); L.GPU_DestroyTexture(tex)
     finally:
         synth.SUN_DIR = sun0
-    st = (C.c_uint64 * 2)()
-    if L.pbrk_mc_region_stats(st, 0) == 0:
-        assert st[0] == 0, f"{st[0]} of {st[1]} wave-slices had to be recomputed"
+    st = mc.counters(L, "region", missing_ok=True)
+    if st:
+        assert st["healed"] == 0, f"{st['healed']} of {st['slices']} wave-slices had to be recomputed"

@@ -2,91 +2,54 @@
 is skipped.  The outputs must not move by a single bit: every case here runs with skipping on and off (pbrk_mc_set_absorb) and
 compares the raw bytes, and the kernel's completeness self-check must never have to recompute a wave-slice."""
 import ctypes as C
-import hashlib
 
 import numpy as np
 import pytest
+
+import pbrhip
+from pbrhip import mc
 
 pytestmark = pytest.mark.gpu
 
 C4_W, C4_S, C4_MIN = 2048, 4096, 128          # bench C4: 2048^2 environment -> 4096^2 prefiltered cube, Monte-Carlo mips 1..5
 
 
-def _lib():
-    import pbrhip
-    return pbrhip
-
-
-def _env_tex(env):
-    pbrhip = _lib()
-    return pbrhip.make_texture(pbrhip.Format_RGBA32F, env.shape[1], env.shape[1],
-                               pbrhip.TextureFlag_Cubemap | pbrhip.TextureFlag_HasMipmaps, env)
-
-
-def _reset(L):
-    st = (C.c_uint64 * 2)()
-    L.pbrk_mc_region_stats(st, 1)
-
-
 def _healed(L):
-    st = (C.c_uint64 * 2)()
-    assert L.pbrk_mc_region_stats(st, 0) == 0
-    return int(st[0]), int(st[1])
+    c = mc.counters(L, "region")
+    return c["healed"], c["slices"]
 
 
 def _skips(L):
-    sk = (C.c_uint64 * 3)()
-    assert L.pbrk_mc_region_skip_stats(sk) == 0
-    fl = (C.c_uint64 * 3)()
-    assert L.pbrk_mc_region_flag_stats(fl) == 0
-    return int(sk[0]), int(sk[1]), int(sk[2]), 4 * int(fl[0])      # words, samples, count-only samples, wave-samples visited
-
-
-def _digest(a):
-    return hashlib.sha256(np.ascontiguousarray(a).view(np.uint8)).hexdigest()
+    c = mc.counters(L, "skip", "flag")
+    return c["abs_words"], c["abs_samples"], c["count_only"], 4 * c["flags"]      # words, samples, count-only samples, wave-samples visited
 
 
 def _prefilter(L, tex, S, min_size, absorb, mips):
     """Whole chain with skipping on / off; returns {mip: sha256 of the raw bytes} and the counters of the run."""
-    pbrhip = _lib()
     spec = pbrhip.make_texture(pbrhip.Format_RGBA32F, S, S, pbrhip.TextureFlag_Cubemap | pbrhip.TextureFlag_HasMipmaps | pbrhip.TextureFlag_StorageImage)
     try:
-        L.pbrk_mc_set_absorb(absorb)
-        _reset(L)
-        L.PBR_GenPrefilteredEnvMap(tex, spec, min_size)
-        L.GPU_WaitUntilIdle()
-        counters = (_healed(L), _skips(L))
-        out = {}
-        for m in mips:
-            a = pbrhip.read_mip(spec, m)
-            out[m] = (_digest(a), float(np.abs(a[..., :3]).max()) if np.isfinite(a[..., :3]).all() else None)
+        with mc.switches(L, absorb=absorb):
+            mc.reset_counters(L)
+            L.PBR_GenPrefilteredEnvMap(tex, spec, min_size)
+            L.GPU_WaitUntilIdle()
+            counters = (_healed(L), _skips(L))
+            out = {}
+            for m in mips:
+                a = pbrhip.read_mip(spec, m)
+                out[m] = (mc.digest(a), float(np.abs(a[..., :3]).max()) if np.isfinite(a[..., :3]).all() else None)
     finally:
-        L.pbrk_mc_set_absorb(1)
         L.GPU_DestroyTexture(spec)
     return out, counters
 
 
 def _per_mip_skips(L, tex, S, mip):
     """One level dispatched on its own (skipping on): the counters of that level alone."""
-    pbrhip = _lib()
-    maps = pbrhip.PBR_IBLMaps()
-    L.PBR_MakeIBLMaps(C.byref(maps), 8, 64, S)
-    pipes = L.PBR_MakeIBLPipelines(); arena = L.GPU_MakeDescriptorArena(); g = L.GPU_MakeGraph()
-    try:
-        size = S >> mip
-        units = [pbrhip.PBR_WorkUnit(pbrhip.Unit_Prefilter, mip, 0, 6, 0, size, 0.0)]
-        arr = (pbrhip.PBR_WorkUnit * 1)(*units)
-        _reset(L)
-        L.PBR_RecordUnits(pipes, g, arena, tex, C.byref(maps), arr, 1)
-        L.GPU_GraphSubmit(g); L.GPU_GraphWait(g); L.GPU_ResetDescriptorArena(arena)
+    with mc.dispatch_prefilter_units(L, tex, S, [pbrhip.PBR_WorkUnit(pbrhip.Unit_Prefilter, mip, 0, 6, 0, S >> mip, 0.0)]):
         return _healed(L), _skips(L)
-    finally:
-        L.GPU_DestroyGraph(g); L.GPU_DestroyDescriptorArena(arena); L.PBR_DestroyIBLPipelines(pipes)
-        L.PBR_DestroyIBLMaps(C.byref(maps))
 
 
 def _on_off(L, env, S=C4_S, min_size=C4_MIN, mips=(1, 2, 3, 4, 5)):
-    tex = _env_tex(env)
+    tex = mc.env_texture(env)
     try:
         on, c_on = _prefilter(L, tex, S, min_size, 1, mips)
         off, c_off = _prefilter(L, tex, S, min_size, 0, mips)
@@ -106,7 +69,7 @@ def test_c4_skip_on_equals_off_and_skips_on_mips_1_2(gpu, c4_env):
     on, sk = _on_off(L, c4_env)
     assert all(on[m][1] and on[m][1] > 0 for m in (1, 2, 3, 4)), on
     assert sk[0] > 0 and 0 < sk[1] <= sk[3] and sk[2] <= sk[1], sk
-    tex = _env_tex(c4_env)
+    tex = mc.env_texture(c4_env)
     try:
         for mip in (1, 2, 3, 4):
             (healed, slices), (words, samples, count_only, visited) = _per_mip_skips(L, tex, C4_S, mip)
@@ -150,10 +113,9 @@ def test_negative_and_inf_texels(gpu, c4_env):
 def test_ragged_row_shards_equal_full_dispatch_with_skipping(gpu, c4_env):
     """Rows that are no multiple of the 16-row tile, three shards per face, skipping on: the same bytes as the whole-level dispatch
     (quarter-face regions at 512 -> mip 1, whole-face regions at 4096 -> mip 2)."""
-    pbrhip = _lib()
     L = gpu
     L.pbrk_mc_set_absorb(1)
-    tex = _env_tex(c4_env)
+    tex = mc.env_texture(c4_env)
     pipes = L.PBR_MakeIBLPipelines(); arena = L.GPU_MakeDescriptorArena(); g = L.GPU_MakeGraph()
     try:
         for S, mips in ((512, (1,)), (C4_S, (1, 2))):
@@ -161,7 +123,7 @@ def test_ragged_row_shards_equal_full_dispatch_with_skipping(gpu, c4_env):
             L.PBR_MakeIBLMaps(C.byref(maps), 8, 64, S)
             spec = maps.tex_specular_env_map
             L.PBR_GenPrefilteredEnvMap(tex, spec, 256)
-            full = {m: _digest(pbrhip.read_mip(spec, m)) for m in mips}
+            full = {m: mc.digest(pbrhip.read_mip(spec, m)) for m in mips}
             for m in mips:
                 L.GPU_OpClearColorF(g, spec, m, 0.0, 0.0, 0.0, 0.0)
             L.GPU_GraphSubmit(g); L.GPU_GraphWait(g)
@@ -172,12 +134,12 @@ def test_ragged_row_shards_equal_full_dispatch_with_skipping(gpu, c4_env):
                     cuts = (0, 5 + f, 131 - 2 * f, size)
                     units += [pbrhip.PBR_WorkUnit(pbrhip.Unit_Prefilter, m, f, f + 1, cuts[k], cuts[k + 1], 0.0) for k in range(3)]
             arr = (pbrhip.PBR_WorkUnit * len(units))(*units)
-            _reset(L)
+            mc.reset_counters(L)
             L.PBR_RecordUnits(pipes, g, arena, tex, C.byref(maps), arr, len(units))
             L.GPU_GraphSubmit(g); L.GPU_GraphWait(g); L.GPU_ResetDescriptorArena(arena)
             assert _healed(L)[0] == 0
             for m in mips:
-                assert _digest(pbrhip.read_mip(spec, m)) == full[m], (S, m)
+                assert mc.digest(pbrhip.read_mip(spec, m)) == full[m], (S, m)
             L.PBR_DestroyIBLMaps(C.byref(maps))
     finally:
         L.GPU_DestroyGraph(g); L.GPU_DestroyDescriptorArena(arena); L.PBR_DestroyIBLPipelines(pipes)

@@ -4,12 +4,10 @@ bytes with the cut (pbrk_mc_set_launch_cut(1), the default) must be those withou
 skipping, the round-5 loop and the lean prologue on and off (the cut exists only where k_mc_prep ran: absorb and prologue on), with
 nothing healed, and with no fewer absorbed wave-samples in the counters.  Row windows of 256^2 levels through pbrk_mc_filter, as in
 test_gpu_mc_prologue.py."""
-import ctypes as C
-
-import numpy as np
 import pytest
 
-from test_gpu_mc_prologue import OUT, WINDOWS, _ZERO_OUT, _Dev, _bordered, _level, _table
+from mc_cases import OUT, WINDOWS, level
+from pbrhip import mc
 
 pytestmark = pytest.mark.gpu
 
@@ -18,42 +16,19 @@ SHAPES = [(128, 0.03), (64, 0.15)]
 
 
 def _run(L, bord, rough, cut, n_tab=None, windows=WINDOWS):
-    """The windows into one cleared 256^2 cube with the launch cut on or off; returns a dict of the bytes and the counters."""
-    dtab, n_full, alpha = _table(L, rough)
-    out = _Dev(L, _ZERO_OUT.nbytes, _ZERO_OUT)
-    L.pbrk_mc_set_launch_cut(cut)
-    try:
-        st = (C.c_uint64 * 2)()
-        L.pbrk_mc_region_stats(st, 1)
-        for f0, f1, y0, rows in windows:
-            rc = L.pbrk_mc_filter(bord.dev.ptr, None, bord.n_src, dtab.ptr, n_tab or n_full, float(np.pi), alpha,
-                                  out.ptr, OUT, f0, f1, y0, y0 + rows, None)
-            assert rc == 0, rc
-        data = out.read()
-        sk = (C.c_uint64 * 3)()
-        c6 = (C.c_int * 6)()
-        assert L.pbrk_mc_region_skip_stats(sk) == 0
-        assert L.pbrk_mc_launch_cut_stats(c6) == 0            # the last window's launch
-        assert L.pbrk_mc_region_stats(st, 1) == 0
-        return {"bytes": data, "healed": int(st[0]), "slices": int(st[1]), "abs_samples": int(sk[1]), "cut4": list(c6)[:4],
-                "words_cut": int(c6[5])}
-    finally:
-        L.pbrk_mc_set_launch_cut(1)
-        out.free()
+    """The windows into one cleared 256^2 cube with the launch cut on or off; returns a dict of the bytes and the counters (cut: the
+    last window's launch)."""
+    with mc.switches(L, launch_cut=cut):
+        mc.reset_counters(L)
+        data = mc.filter_windows(L, bord, rough, windows, OUT, n_tab)
+        return {"bytes": data, **mc.counters(L, "skip", "cut", "region", reset=True)}
 
 
 def _on_off(L, bord, rough, absorb=1, runs=1, prologue=1, n_tab=None, windows=WINDOWS):
     """Cut on against cut off under one setting of the other switches.  Returns (on, off)."""
-    try:
-        L.pbrk_mc_set_absorb(absorb)
-        L.pbrk_mc_set_runs(runs)
-        L.pbrk_mc_set_prologue(prologue)
+    with mc.switches(L, absorb=absorb, runs=runs, prologue=prologue):
         on = _run(L, bord, rough, 1, n_tab, windows)
         off = _run(L, bord, rough, 0, n_tab, windows)
-    finally:
-        L.pbrk_mc_set_prologue(1)
-        L.pbrk_mc_set_runs(1)
-        L.pbrk_mc_set_absorb(1)
     tag = f"n_src {bord.n_src} absorb {absorb} runs {runs} prologue {prologue}"
     assert on["bytes"] == off["bytes"], f"{tag}: the launch cut changed the output bytes"
     assert on["healed"] == 0 and off["healed"] == 0 and on["slices"] > 0 and off["slices"] == on["slices"], (tag, on["healed"], off["healed"])
@@ -68,7 +43,7 @@ def _on_off(L, bord, rough, absorb=1, runs=1, prologue=1, n_tab=None, windows=WI
 
 @pytest.mark.parametrize("n_src,rough", SHAPES)
 def test_cut_on_equals_cut_off(gpu, n_src, rough):
-    bord = _bordered(gpu, _level(n_src))
+    bord = mc.BorderedLevel(gpu, level(n_src))
     try:
         ref = None
         for absorb in (1, 0):
@@ -84,12 +59,12 @@ def test_cut_on_equals_cut_off(gpu, n_src, rough):
 @pytest.mark.parametrize("n_src,rough", SHAPES)
 def test_table_length_no_multiple_of_32(gpu, n_src, rough):
     """A table that ends inside a mask word: the last word of one slice is short, in the kernel's count of a slice's samples too."""
-    _, n_full, _ = _table(gpu, rough)
+    _, n_full, _ = mc.prefilter_table(gpu, rough)
     n_tab = n_full - 13
     if n_tab % 32 == 0:
         n_tab -= 1
     assert n_tab > 160 and n_tab % 32 != 0
-    bord = _bordered(gpu, _level(n_src))
+    bord = mc.BorderedLevel(gpu, level(n_src))
     try:
         for absorb, runs in ((1, 1), (1, 0), (0, 1)):
             _on_off(gpu, bord, rough, absorb, runs, 1, n_tab)
@@ -100,14 +75,14 @@ def test_table_length_no_multiple_of_32(gpu, n_src, rough):
 @pytest.mark.parametrize("n_src,rough", SHAPES)
 def test_bright_patch_cuts_later(gpu, n_src, rough):
     """A 1e5:1 bright 4 x 4 patch: the level's maximum is its peak, so the proof holds for fewer words -- and still exactly."""
-    bord = _bordered(gpu, _level(n_src))
+    bord = mc.BorderedLevel(gpu, level(n_src))
     try:
         clean, _ = _on_off(gpu, bord, rough)
     finally:
         bord.free()
-    lvl = _level(n_src)
+    lvl = level(n_src)
     lvl[2, 10:14, 10:14, :3] *= 1e5
-    bord = _bordered(gpu, lvl)
+    bord = mc.BorderedLevel(gpu, lvl)
     try:
         bright, _ = _on_off(gpu, bord, rough)
     finally:
@@ -124,9 +99,9 @@ def test_negative_or_minus_zero_texel_switches_the_cut_off(gpu, n_src, rough, wh
     L = gpu
     y = 20 if where == "inside" else (64 if n_src > 65 else n_src - 1)
     for ch, bad in ((1, -1e-6), (2, -0.0)):
-        lvl = _level(n_src)
+        lvl = level(n_src)
         lvl[4, y, 20, ch] = bad
-        bord = _bordered(L, lvl)
+        bord = mc.BorderedLevel(L, lvl)
         try:
             on = _run(L, bord, rough, 1)
             off = _run(L, bord, rough, 0)
@@ -140,7 +115,7 @@ def test_negative_or_minus_zero_texel_switches_the_cut_off(gpu, n_src, rough, wh
 def test_row_shards_equal_the_full_dispatch(gpu, n_src, rough):
     """The order of a texel's sum (phase, region as visited, sample index) and the cut depend on the launch's level and table only: ragged
     row shards of two faces give the bytes of one dispatch over the same rows."""
-    bord = _bordered(gpu, _level(n_src))
+    bord = mc.BorderedLevel(gpu, level(n_src))
     try:
         full = _run(gpu, bord, rough, 1, windows=[(0, 2, 40, 120)])
         shards = _run(gpu, bord, rough, 1, windows=[(0, 1, 40, 37), (0, 1, 77, 83), (1, 2, 40, 16), (1, 2, 56, 51), (1, 2, 107, 53)])

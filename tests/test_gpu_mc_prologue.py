@@ -8,121 +8,31 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from mc_cases import OUT, WINDOWS, level
+from pbrhip import mc
+
 pytestmark = pytest.mark.gpu
 
-OUT = 256
 # (n_src, roughness): 18^2, 34^2, 66^2 whole face, 66^2 with rows not contiguous in LDS (nb < RS), quarter faces, G == 2 with a short
 # last region of 36 cells
 SHAPES = [(16, 0.6), (32, 0.4), (64, 0.15), (48, 0.15), (128, 0.03), (100, 0.03)]
 BIG = [(64, 0.15), (48, 0.15), (128, 0.03), (100, 0.03)]            # the 66^2 shapes: absorbed words, round-5 loop
-# (face0, face1, y0, rows): the tangent frame's pole rows 63 and 192 on faces +-X; a ragged window on the others
-WINDOWS = [(0, 2, 48, 32), (0, 2, 176, 32), (2, 6, 53, 37)]
-
-_tables = {}
-
-
-class _Dev:
-    """A device buffer of the backend (GPU_MakeBuffer), optionally filled from a numpy array."""
-
-    def __init__(self, L, nbytes, data=None):
-        import pbrhip
-        self.L, self.nbytes = L, nbytes
-        self.buf = L.GPU_MakeBuffer(nbytes, pbrhip.BufferFlag_GPU, data.ctypes.data_as(C.c_void_p) if data is not None else None)
-        assert self.buf
-        self.ptr = L.GPUX_BufferDevicePtr(self.buf)
-
-    def read(self):
-        import pbrhip
-        L = self.L
-        host = L.GPU_MakeBuffer(self.nbytes, pbrhip.BufferFlag_CPU, None)
-        g = L.GPU_MakeGraph()
-        try:
-            L.GPU_WaitUntilIdle()
-            L.GPU_OpCopyBufferToBuffer(g, self.buf, host, 0, 0, self.nbytes); L.GPU_GraphSubmit(g); L.GPU_GraphWait(g)
-            return bytes((C.c_char * self.nbytes).from_address(host.contents.data))
-        finally:
-            L.GPU_DestroyGraph(g)
-            L.GPU_DestroyBuffer(host)
-
-    def free(self):
-        if self.buf:
-            self.L.GPU_WaitUntilIdle()
-            self.L.GPU_DestroyBuffer(self.buf)
-            self.buf = None
-
-
-class _Bordered:
-    """A bordered source level on the device (pbrk_border_build from the plain level)."""
-
-    def __init__(self, L, lvl):
-        lvl = np.ascontiguousarray(lvl, dtype=np.float32)
-        self.n_src = lvl.shape[1]
-        pyr = _Dev(L, lvl.nbytes, lvl)
-        self.dev = _Dev(L, 6 * (self.n_src + 2) ** 2 * 16, np.zeros((6, self.n_src + 2, self.n_src + 2, 4), np.float32))
-        try:
-            assert L.pbrk_border_build(pyr.ptr, self.dev.ptr, self.n_src, 1, None) == 0
-        finally:
-            pyr.free()                                                 # waits for the device first
-
-    def free(self):
-        self.dev.free()
-
-
-def _table(L, rough):
-    """The reference's prefilter table for a roughness, on the device; kept for the session (a few hundred KB)."""
-    if rough not in _tables:
-        tab = np.zeros((8192, 4), dtype=np.float32)
-        alpha = C.c_float()
-        n_tab = L.pbrk_host_prefilter_table(8192, rough, tab.ctypes.data_as(C.c_void_p), C.byref(alpha))
-        assert 0 < n_tab <= 8192
-        _tables[rough] = (_Dev(L, tab.nbytes, tab), n_tab, alpha.value)
-    return _tables[rough]
-
-
-def _level(n_src, seed=7):
-    return np.random.default_rng(seed + n_src).random((6, n_src, n_src, 4), dtype=np.float32) + 0.1
-
-
-def _bordered(L, lvl):
-    return _Bordered(L, lvl)
-
-
-_ZERO_OUT = np.zeros((6, OUT, OUT, 4), np.float32)
 
 
 def _run(L, bord, rough, n_tab=None):
     """All windows into one cleared 256^2 cube; returns (bytes, healed wave-slices, wave-slices, absorbed wave-words)."""
-    dtab, n_full, alpha = _table(L, rough)
-    out = _Dev(L, _ZERO_OUT.nbytes, _ZERO_OUT)
-    try:
-        st = (C.c_uint64 * 2)()
-        L.pbrk_mc_region_stats(st, 1)                                  # the counters exist after the kernel's first launch
-        for f0, f1, y0, rows in WINDOWS:
-            rc = L.pbrk_mc_filter(bord.dev.ptr, None, bord.n_src, dtab.ptr, n_tab or n_full, float(np.pi), alpha,
-                                  out.ptr, OUT, f0, f1, y0, y0 + rows, None)
-            assert rc == 0, rc
-        data = out.read()
-        sk = (C.c_uint64 * 3)()
-        assert L.pbrk_mc_region_skip_stats(sk) == 0
-        assert L.pbrk_mc_region_stats(st, 1) == 0
-        return data, int(st[0]), int(st[1]), int(sk[0])
-    finally:
-        out.free()
+    mc.reset_counters(L)
+    data = mc.filter_windows(L, bord, rough, WINDOWS, OUT, n_tab)
+    c = mc.counters(L, "skip", "region", reset=True)
+    return data, c["healed"], c["slices"], c["abs_words"]
 
 
 def _both(L, bord, rough, absorb=1, runs=1, n_tab=None):
     """The same dispatches with the lean prologue and with the one before it: equal bytes, nothing healed.  Returns the lean run."""
-    try:
-        L.pbrk_mc_set_absorb(absorb)
-        L.pbrk_mc_set_runs(runs)
-        L.pbrk_mc_set_prologue(1)
+    with mc.switches(L, absorb=absorb, runs=runs):
         new = _run(L, bord, rough, n_tab)
-        L.pbrk_mc_set_prologue(0)
-        old = _run(L, bord, rough, n_tab)
-    finally:
-        L.pbrk_mc_set_prologue(1)
-        L.pbrk_mc_set_runs(1)
-        L.pbrk_mc_set_absorb(1)
+        with mc.switches(L, prologue=0):
+            old = _run(L, bord, rough, n_tab)
     assert new[0] == old[0], f"n_src {bord.n_src} absorb {absorb} runs {runs}: the lean prologue changed the output bytes"
     assert new[1] == 0 and old[1] == 0 and new[2] > 0 and old[2] > 0, (new[1:], old[1:])
     return new
@@ -130,7 +40,7 @@ def _both(L, bord, rough, absorb=1, runs=1, n_tab=None):
 
 @pytest.mark.parametrize("n_src,rough", SHAPES)
 def test_lean_prologue_equals_parent(gpu, n_src, rough):
-    bord = _bordered(gpu, _level(n_src))
+    bord = mc.BorderedLevel(gpu, level(n_src))
     try:
         for absorb in (1, 0):
             for runs in ((1, 0) if (n_src, rough) in BIG else (1,)):
@@ -142,9 +52,9 @@ def test_lean_prologue_equals_parent(gpu, n_src, rough):
 @pytest.mark.parametrize("n_src,rough", BIG)
 def test_bright_patch(gpu, n_src, rough):
     """A 1e5:1 bright 4 x 4 patch in one face: the region maximum is its peak, lanes near it absorb far more than the others."""
-    lvl = _level(n_src)
+    lvl = level(n_src)
     lvl[2, 10:14, 10:14, :3] *= 1e5
-    bord = _bordered(gpu, lvl)
+    bord = mc.BorderedLevel(gpu, lvl)
     try:
         for absorb in (1, 0):
             _both(gpu, bord, rough, absorb)
@@ -158,16 +68,16 @@ def test_negative_and_minus_zero_switch_region_off(gpu, n_src, rough, where):
     """One small negative component and one -0.0: by bit pattern both order above +inf, so their region must stop absorbing --
     inside a region, and in the last texel row a region stages (the first row of the region below it, or the face's border)."""
     L = gpu
-    bord = _bordered(L, _level(n_src))
+    bord = mc.BorderedLevel(L, level(n_src))
     try:
         clean = _both(L, bord, rough)
     finally:
         bord.free()
-    lvl = _level(n_src)
+    lvl = level(n_src)
     y = 20 if where == "inside" else (64 if n_src > 65 else n_src - 1)   # bordered row y + 1: row 65 of region gy = 0, or the last row of the face
     lvl[4, y, 20, 1] = -1e-6
     lvl[4, y, 30, 2] = -0.0
-    bord = _bordered(L, lvl)
+    bord = mc.BorderedLevel(L, lvl)
     try:
         patched = _both(L, bord, rough)
     finally:
@@ -179,12 +89,12 @@ def test_negative_and_minus_zero_switch_region_off(gpu, n_src, rough, where):
 @pytest.mark.parametrize("n_src,rough", BIG)
 def test_table_length_no_multiple_of_32(gpu, n_src, rough):
     """A table that ends inside a mask word: the word's maximum must come from the samples it holds alone."""
-    _, n_full, _ = _table(gpu, rough)
+    _, n_full, _ = mc.prefilter_table(gpu, rough)
     n_tab = n_full - 13
     if n_tab % 32 == 0:
         n_tab -= 1
     assert n_tab > 32 and n_tab % 32 != 0
-    bord = _bordered(gpu, _level(n_src))
+    bord = mc.BorderedLevel(gpu, level(n_src))
     try:
         for absorb in (1, 0):
             _both(gpu, bord, rough, absorb, 1, n_tab)
@@ -195,13 +105,10 @@ def test_table_length_no_multiple_of_32(gpu, n_src, rough):
 def test_dispatches_in_flight_on_several_streams(gpu):
     """Row windows of two levels of different region shapes (mip 1: quarter faces of a 128^2 source, mip 2: whole 64^2 faces), 36
     dispatches dealt over four tile streams -- more than the scratch ring has slots -- against the same dispatches in order on one."""
-    import hashlib
     import pbrhip
     L = gpu
     S = 1024
-    env = np.random.default_rng(11).random((6, 2048, 2048, 4), dtype=np.float32) + 0.1
-    tex = pbrhip.make_texture(pbrhip.Format_RGBA32F, 2048, 2048, pbrhip.TextureFlag_Cubemap | pbrhip.TextureFlag_HasMipmaps, env)
-    del env
+    tex = mc.env_texture(np.random.default_rng(11).random((6, 2048, 2048, 4), dtype=np.float32) + 0.1)
     maps = pbrhip.PBR_IBLMaps()
     L.PBR_MakeIBLMaps(C.byref(maps), 8, 64, S)
     spec = maps.tex_specular_env_map
@@ -219,22 +126,19 @@ def test_dispatches_in_flight_on_several_streams(gpu):
         for m in (1, 2):
             L.GPU_OpClearColorF(g, spec, m, 0.0, 0.0, 0.0, 0.0)
         L.GPU_GraphSubmit(g); L.GPU_GraphWait(g)
-        st = (C.c_uint64 * 2)()
-        L.pbrk_mc_region_stats(st, 1)
+        mc.reset_counters(L)
         L.PBR_RecordUnits(pipes, g, arena, tex, C.byref(maps), arr, len(units))
         L.GPU_GraphSubmit(g); L.GPU_GraphWait(g); L.GPU_ResetDescriptorArena(arena)
-        assert L.pbrk_mc_region_stats(st, 1) == 0
-        assert st[0] == 0 and st[1] > 0, (st[0], st[1])
-        return [hashlib.sha256(np.ascontiguousarray(pbrhip.read_mip(spec, m)).view(np.uint8)).hexdigest() for m in (1, 2)]
+        st = mc.counters(L, "region", reset=True)
+        assert st["healed"] == 0 and st["slices"] > 0, (st["healed"], st["slices"])
+        return [mc.digest(pbrhip.read_mip(spec, m)) for m in (1, 2)]
 
     try:
-        L.pbrk_mc_set_prologue(1)
         serial = run(0)
         assert run(4) == serial
-        L.pbrk_mc_set_prologue(0)
-        assert run(4) == serial
+        with mc.switches(L, prologue=0):
+            assert run(4) == serial
     finally:
-        L.pbrk_mc_set_prologue(1)
         L.GPUX_SetTileStreams(-1)
         L.GPU_DestroyGraph(g); L.GPU_DestroyDescriptorArena(arena); L.PBR_DestroyIBLPipelines(pipes)
         L.PBR_DestroyIBLMaps(C.byref(maps))

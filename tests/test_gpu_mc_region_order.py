@@ -2,10 +2,11 @@
 first, then all the others in index order.  The own face holds a texel's big terms, so every later word is tested for absorption (2c) against a grown sum on
 every face, not only on the faces with the lowest index.  Checked here: the order function itself (no GPU), the per-face skip
 fractions, the level totals against the index-order loop's figures, and the error against the fp64 oracle."""
-import ctypes as C
-
 import numpy as np
 import pytest
+
+import pbrhip
+from pbrhip import mc
 
 C4_W, C4_S, C4_MIN = 2048, 4096, 128          # bench C4: 2048^2 environment -> 4096^2 prefiltered cube, Monte-Carlo mips 1..5
 REL = 1e-4                                    # the bound of the oracle comparisons of these levels (test_gpu_fullsize.py, bench.py --check)
@@ -21,16 +22,11 @@ INDEX_ORDER_SKIPPED = {2: 374_376_440, 1: 449_714_944}
 MIN_OVER_MAX = {2: 0.93, 1: 0.96}
 
 
-def _lib():
-    import pbrhip
-    return pbrhip
-
-
 def test_order_is_a_permutation_starting_with_the_own_face():
     """No GPU: pbrk_mc_region_order is the kernel's own inline (mc_region_visit).  For every face and every G in use (1: whole
     faces; 2: the quarter faces of n = 128; 3, 4: larger sources of the same shape) the visits are a permutation of 0 .. 6 G^2 - 1,
     begin with the own face's regions in index order and go on with the others in index order."""
-    L = _lib().lib()
+    L = pbrhip.lib()
     for G in (1, 2, 3, 4):
         GG, NR = G * G, 6 * G * G
         for face in range(6):
@@ -42,29 +38,11 @@ def test_order_is_a_permutation_starting_with_the_own_face():
     assert L.pbrk_mc_region_order(0, 0, 0) == -1
 
 
-def _env_tex(env):
-    pbrhip = _lib()
-    return pbrhip.make_texture(pbrhip.Format_RGBA32F, env.shape[1], env.shape[1],
-                               pbrhip.TextureFlag_Cubemap | pbrhip.TextureFlag_HasMipmaps, env)
-
-
 def _dispatch_counters(L, tex, S, mip, f0, f1):
     """Faces [f0, f1) of one level dispatched alone: healed wave-slices, wave-slices, absorbed wave-samples, wave-samples visited."""
-    pbrhip = _lib()
-    maps = pbrhip.PBR_IBLMaps()
-    L.PBR_MakeIBLMaps(C.byref(maps), 8, 64, S)
-    pipes = L.PBR_MakeIBLPipelines(); arena = L.GPU_MakeDescriptorArena(); g = L.GPU_MakeGraph()
-    try:
-        arr = (pbrhip.PBR_WorkUnit * 1)(pbrhip.PBR_WorkUnit(pbrhip.Unit_Prefilter, mip, f0, f1, 0, S >> mip, 0.0))
-        st = (C.c_uint64 * 2)(); sk = (C.c_uint64 * 3)(); fl = (C.c_uint64 * 3)()
-        L.pbrk_mc_region_stats(st, 1)                                  # reset (the counters exist after the kernel's first launch)
-        L.PBR_RecordUnits(pipes, g, arena, tex, C.byref(maps), arr, 1)
-        L.GPU_GraphSubmit(g); L.GPU_GraphWait(g); L.GPU_ResetDescriptorArena(arena)
-        assert L.pbrk_mc_region_stats(st, 0) == 0 and L.pbrk_mc_region_skip_stats(sk) == 0 and L.pbrk_mc_region_flag_stats(fl) == 0
-        return int(st[0]), int(st[1]), int(sk[1]), 4 * int(fl[0])
-    finally:
-        L.GPU_DestroyGraph(g); L.GPU_DestroyDescriptorArena(arena); L.PBR_DestroyIBLPipelines(pipes)
-        L.PBR_DestroyIBLMaps(C.byref(maps))
+    with mc.dispatch_prefilter_units(L, tex, S, [pbrhip.PBR_WorkUnit(pbrhip.Unit_Prefilter, mip, f0, f1, 0, S >> mip, 0.0)]):
+        c = mc.counters(L, "region", "skip", "flag")
+        return c["healed"], c["slices"], c["abs_samples"], 4 * c["flags"]
 
 
 @pytest.mark.gpu
@@ -72,7 +50,7 @@ def test_skip_fraction_no_longer_follows_the_face_index(gpu, c4_env):
     """C4 mips 2 (whole-face regions) and 1 (quarter faces), every face dispatched alone: see MIN_OVER_MAX."""
     L = gpu
     L.pbrk_mc_set_absorb(1); L.pbrk_mc_set_runs(1)
-    tex = _env_tex(c4_env)
+    tex = mc.env_texture(c4_env)
     try:
         _dispatch_counters(L, tex, C4_S, 2, 0, 1)                      # first launch: allocates the counters
         for mip in (2, 1):
@@ -92,7 +70,7 @@ def test_level_totals_not_below_index_order(gpu, c4_env):
     """The whole level in one dispatch absorbs at least the wave-samples the index-order loop absorbed (one-sided)."""
     L = gpu
     L.pbrk_mc_set_absorb(1); L.pbrk_mc_set_runs(1)
-    tex = _env_tex(c4_env)
+    tex = mc.env_texture(c4_env)
     try:
         _dispatch_counters(L, tex, C4_S, 2, 0, 1)
         for mip in (2, 1):
@@ -109,10 +87,9 @@ def test_rows_against_the_fp64_oracle(gpu, c4_env):
     """A few rows of C4 mips 1 and 2 (faces +X, -Y, +Z, -Z: first, middle and last rows, one next to a face edge) against the fp64
     oracle at the bound the existing oracle comparisons use for these levels; the worst error per level is printed."""
     import pbr_oracle as O
-    pbrhip = _lib()
     L = gpu
     L.pbrk_mc_set_absorb(1); L.pbrk_mc_set_runs(1)
-    tex = _env_tex(c4_env)
+    tex = mc.env_texture(c4_env)
     spec = pbrhip.make_texture(pbrhip.Format_RGBA32F, C4_S, C4_S, pbrhip.TextureFlag_Cubemap | pbrhip.TextureFlag_HasMipmaps | pbrhip.TextureFlag_StorageImage)
     try:
         L.PBR_GenPrefilteredEnvMap(tex, spec, C4_MIN)

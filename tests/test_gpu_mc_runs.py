@@ -2,57 +2,33 @@
 a barrier per visited region only) against the loop it replaces (pbrk_mc_set_runs(0)): the outputs must be the same bytes, with
 absorbed-word skipping on and off, and the completeness self-check must never recompute a wave-slice."""
 import ctypes as C
-import hashlib
 
-import numpy as np
 import pytest
+
+import pbrhip
+from pbrhip import mc
 
 pytestmark = pytest.mark.gpu
 
 C4_S, C4_MIN = 4096, 128
 
 
-def _lib():
-    import pbrhip
-    return pbrhip
-
-
-def _digest(a):
-    return hashlib.sha256(np.ascontiguousarray(a).view(np.uint8)).hexdigest()
-
-
-def _reset(L):
-    st = (C.c_uint64 * 2)()
-    L.pbrk_mc_region_stats(st, 1)                                      # the counters exist after the kernel's first launch
-
-
 def _healed(L):
-    st = (C.c_uint64 * 2)()
-    assert L.pbrk_mc_region_stats(st, 1) == 0
-    return int(st[0]), int(st[1])
-
-
-def _env_tex(env):
-    pbrhip = _lib()
-    return pbrhip.make_texture(pbrhip.Format_RGBA32F, env.shape[1], env.shape[1],
-                               pbrhip.TextureFlag_Cubemap | pbrhip.TextureFlag_HasMipmaps, env)
+    c = mc.counters(L, "region", reset=True)
+    return c["healed"], c["slices"]
 
 
 def _chain(L, env, runs, absorb, S=C4_S, min_size=C4_MIN, mips=(1, 2, 3, 4)):
-    pbrhip = _lib()
-    tex = _env_tex(env)
+    tex = mc.env_texture(env)
     spec = pbrhip.make_texture(pbrhip.Format_RGBA32F, S, S, pbrhip.TextureFlag_Cubemap | pbrhip.TextureFlag_HasMipmaps | pbrhip.TextureFlag_StorageImage)
     try:
-        L.pbrk_mc_set_runs(runs)
-        L.pbrk_mc_set_absorb(absorb)
-        _reset(L)
-        L.PBR_GenPrefilteredEnvMap(tex, spec, min_size)
-        L.GPU_WaitUntilIdle()
-        healed = _healed(L)
-        return {m: _digest(pbrhip.read_mip(spec, m)) for m in mips}, healed
+        with mc.switches(L, runs=runs, absorb=absorb):
+            mc.reset_counters(L)
+            L.PBR_GenPrefilteredEnvMap(tex, spec, min_size)
+            L.GPU_WaitUntilIdle()
+            healed = _healed(L)
+            return {m: mc.digest(pbrhip.read_mip(spec, m)) for m in mips}, healed
     finally:
-        L.pbrk_mc_set_runs(1)
-        L.pbrk_mc_set_absorb(1)
         L.GPU_DestroyTexture(spec)
         L.GPU_DestroyTexture(tex)
 
@@ -85,20 +61,18 @@ def test_bright_sun_and_tolerance_cut_tables(gpu, c4_env):
 
 def test_ragged_row_shards_with_runs(gpu, c4_env):
     """Rows that are no multiple of the 16-row tile, three shards per face: the same bytes as the old loop's whole-level dispatch."""
-    pbrhip = _lib()
     L = gpu
-    tex = _env_tex(c4_env)
+    tex = mc.env_texture(c4_env)
     pipes = L.PBR_MakeIBLPipelines(); arena = L.GPU_MakeDescriptorArena(); g = L.GPU_MakeGraph()
     try:
         for S, mips in ((512, (1,)), (C4_S, (1, 2))):
             maps = pbrhip.PBR_IBLMaps()
             L.PBR_MakeIBLMaps(C.byref(maps), 8, 64, S)
             spec = maps.tex_specular_env_map
-            L.pbrk_mc_set_runs(0)
-            L.PBR_GenPrefilteredEnvMap(tex, spec, 256)
-            L.GPU_WaitUntilIdle()
-            full = {m: _digest(pbrhip.read_mip(spec, m)) for m in mips}
-            L.pbrk_mc_set_runs(1)
+            with mc.switches(L, runs=0):
+                L.PBR_GenPrefilteredEnvMap(tex, spec, 256)
+                L.GPU_WaitUntilIdle()
+                full = {m: mc.digest(pbrhip.read_mip(spec, m)) for m in mips}
             for m in mips:
                 L.GPU_OpClearColorF(g, spec, m, 0.0, 0.0, 0.0, 0.0)
             L.GPU_GraphSubmit(g); L.GPU_GraphWait(g)
@@ -109,52 +83,37 @@ def test_ragged_row_shards_with_runs(gpu, c4_env):
                     cuts = (0, 5 + f, 131 - 2 * f, size)
                     units += [pbrhip.PBR_WorkUnit(pbrhip.Unit_Prefilter, m, f, f + 1, cuts[k], cuts[k + 1], 0.0) for k in range(3)]
             arr = (pbrhip.PBR_WorkUnit * len(units))(*units)
-            _reset(L)
+            mc.reset_counters(L)
             L.PBR_RecordUnits(pipes, g, arena, tex, C.byref(maps), arr, len(units))
             L.GPU_GraphSubmit(g); L.GPU_GraphWait(g); L.GPU_ResetDescriptorArena(arena)
             assert _healed(L)[0] == 0
             for m in mips:
-                assert _digest(pbrhip.read_mip(spec, m)) == full[m], (S, m)
+                assert mc.digest(pbrhip.read_mip(spec, m)) == full[m], (S, m)
             L.PBR_DestroyIBLMaps(C.byref(maps))
     finally:
-        L.pbrk_mc_set_runs(1)
         L.GPU_DestroyGraph(g); L.GPU_DestroyDescriptorArena(arena); L.PBR_DestroyIBLPipelines(pipes)
         L.GPU_DestroyTexture(tex)
 
 
 def _faces(L, tex, S, mips, faces, runs):
     """Faces [f0, f1) of the given mips dispatched alone; returns {mip: digest of those faces} and the healed counters."""
-    pbrhip = _lib()
-    maps = pbrhip.PBR_IBLMaps()
-    L.PBR_MakeIBLMaps(C.byref(maps), 8, 64, S)
-    pipes = L.PBR_MakeIBLPipelines(); arena = L.GPU_MakeDescriptorArena(); g = L.GPU_MakeGraph()
-    try:
-        L.pbrk_mc_set_runs(runs)
-        units = [pbrhip.PBR_WorkUnit(pbrhip.Unit_Prefilter, m, faces[0], faces[1], 0, S >> m, 0.0) for m in mips]
-        arr = (pbrhip.PBR_WorkUnit * len(units))(*units)
-        _reset(L)
-        L.PBR_RecordUnits(pipes, g, arena, tex, C.byref(maps), arr, len(units))
-        L.GPU_GraphSubmit(g); L.GPU_GraphWait(g); L.GPU_ResetDescriptorArena(arena)
+    units = [pbrhip.PBR_WorkUnit(pbrhip.Unit_Prefilter, m, faces[0], faces[1], 0, S >> m, 0.0) for m in mips]
+    with mc.switches(L, runs=runs), mc.dispatch_prefilter_units(L, tex, S, units) as maps:
         healed = _healed(L)
-        return {m: _digest(pbrhip.read_mip(maps.tex_specular_env_map, m)[faces[0]:faces[1]]) for m in mips}, healed
-    finally:
-        L.pbrk_mc_set_runs(1)
-        L.GPU_DestroyGraph(g); L.GPU_DestroyDescriptorArena(arena); L.PBR_DestroyIBLPipelines(pipes)
-        L.PBR_DestroyIBLMaps(C.byref(maps))
+        return {m: mc.digest(pbrhip.read_mip(maps.tex_specular_env_map, m)[faces[0]:faces[1]]) for m in mips}, healed
 
 
 def test_pole_faces_alone(gpu, c4_env):
     """Faces +-X dispatched on their own: the tiles around the tangent frame's pole flag the most regions (a sample in several
     regions, sparse words in the neighbours), and the dispatch starts with them."""
     L = gpu
-    tex = _env_tex(c4_env)
+    tex = mc.env_texture(c4_env)
     try:
         for absorb in (1, 0):
-            L.pbrk_mc_set_absorb(absorb)
-            new, h_new = _faces(L, tex, C4_S, (1, 2), (0, 2), 1)
-            old, h_old = _faces(L, tex, C4_S, (1, 2), (0, 2), 0)
+            with mc.switches(L, absorb=absorb):
+                new, h_new = _faces(L, tex, C4_S, (1, 2), (0, 2), 1)
+                old, h_old = _faces(L, tex, C4_S, (1, 2), (0, 2), 0)
             assert new == old, absorb
             assert h_new[0] == 0 and h_old[0] == 0 and h_new[1] > 0, (h_new, h_old)
     finally:
-        L.pbrk_mc_set_absorb(1)
         L.GPU_DestroyTexture(tex)

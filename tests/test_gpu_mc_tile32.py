@@ -10,14 +10,15 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_gpu_mc_prologue import OUT, WINDOWS, _ZERO_OUT, _Dev, _bordered, _level, _table
+from mc_cases import FULL, OUT, WINDOWS, level as _level
+from pbrhip import mc
 
 pytestmark = pytest.mark.gpu
 
 N_SRC, ROUGH = 128, 0.03
 ROUGH_LONG = 0.04                                             # 2300 samples: its first 2048 / 2049 are the table-length cases
-FULL = [(0, 6, 0, OUT)]
 TOL = 2e-5                                                    # test_c4_every_texel_region_kernel_against_direct_kernel
+NO_REGION = {"healed": 0, "slices": 0, "cut4": [0] * 4, "nw": 0, "words_cut": 0}      # what a run of the direct kernel reports
 
 
 def _bits(v):
@@ -26,31 +27,12 @@ def _bits(v):
 
 def _run(L, bord, rough, tile32, windows=WINDOWS, n_tab=None, cut=1, direct=False):
     """The windows into one cleared 256^2 cube; returns a dict of the bytes and the counters of the run (cut: the last window's launch)."""
-    dtab, n_full, alpha = _table(L, rough)
-    out = _Dev(L, _ZERO_OUT.nbytes, _ZERO_OUT)
-    L.pbrk_mc_set_tile32(tile32)
-    L.pbrk_mc_set_launch_cut(cut)
-    if direct:
-        L.pbrk_mc_set_kernels(0, 0)
-    try:
-        st = (C.c_uint64 * 2)()
-        L.pbrk_mc_region_stats(st, 1)
-        for f0, f1, y0, rows in windows:
-            rc = L.pbrk_mc_filter(bord.dev.ptr, None, bord.n_src, dtab.ptr, n_tab or n_full, float(np.pi), alpha,
-                                  out.ptr, OUT, f0, f1, y0, y0 + rows, None)
-            assert rc == 0, rc
-        data = out.read()
-        c6 = (C.c_int * 6)()
-        if not direct:
-            assert L.pbrk_mc_launch_cut_stats(c6) == 0
-        rc = L.pbrk_mc_region_stats(st, 1)                     # the counters exist after the region kernel's first launch
-        assert rc == 0 or direct, rc
-        return {"bytes": data, "healed": int(st[0]), "slices": int(st[1]), "cut4": list(c6)[:4], "nw": int(c6[4]), "words_cut": int(c6[5])}
-    finally:
-        L.pbrk_mc_set_kernels(-1, -1)
-        L.pbrk_mc_set_launch_cut(1)
-        L.pbrk_mc_set_tile32(-1)
-        out.free()
+    with mc.switches(L, tile32=tile32, launch_cut=cut, **({"kernels": (0, 0)} if direct else {})):
+        mc.reset_counters(L)
+        data = mc.filter_windows(L, bord, rough, windows, OUT, n_tab)
+        if direct:                                            # the counters exist after the region kernel's first launch
+            return {"bytes": data, **NO_REGION, **mc.counters(L, "region", reset=True, missing_ok=True)}
+        return {"bytes": data, **mc.counters(L, "cut", "region", reset=True)}
 
 
 def _one_slice(r):
@@ -70,7 +52,7 @@ def _worst(a, b):
 
 @pytest.fixture(scope="module")
 def level(gpu):
-    bord = _bordered(gpu, _level(N_SRC))
+    bord = mc.BorderedLevel(gpu, _level(N_SRC))
     yield bord
     bord.free()
 
@@ -102,24 +84,21 @@ def test_every_texel_against_the_direct_kernel(gpu, level, direct_full):
 def test_one_set_of_bytes_over_the_switches(gpu, level):
     L = gpu
     ref = None
-    try:
-        for absorb in (1, 0):
-            for runs in (1, 0):
-                for prologue in (1, 0):
-                    for cut in (1, 0):
-                        L.pbrk_mc_set_absorb(absorb); L.pbrk_mc_set_runs(runs); L.pbrk_mc_set_prologue(prologue)
+    for absorb in (1, 0):
+        for runs in (1, 0):
+            for prologue in (1, 0):
+                for cut in (1, 0):
+                    with mc.switches(L, absorb=absorb, runs=runs, prologue=prologue):
                         r = _run(L, level, ROUGH, 1, cut=cut)
-                        tag = f"absorb {absorb} runs {runs} prologue {prologue} cut {cut}"
-                        assert r["healed"] == 0 and r["slices"] > 0, (tag, r["healed"], r["slices"])
-                        assert _one_slice(r), (tag, r["cut4"])
-                        if absorb and prologue and cut:
-                            assert r["words_cut"] > 0, f"{tag}: nothing cut, the case checks nothing"
-                        else:
-                            assert r["words_cut"] == 0, tag       # no k_mc_prep result, or the cut switched off: nothing is dropped
-                        ref = ref or r
-                        assert r["bytes"] == ref["bytes"], tag
-    finally:
-        L.pbrk_mc_set_prologue(1); L.pbrk_mc_set_runs(1); L.pbrk_mc_set_absorb(1)
+                    tag = f"absorb {absorb} runs {runs} prologue {prologue} cut {cut}"
+                    assert r["healed"] == 0 and r["slices"] > 0, (tag, r["healed"], r["slices"])
+                    assert _one_slice(r), (tag, r["cut4"])
+                    if absorb and prologue and cut:
+                        assert r["words_cut"] > 0, f"{tag}: nothing cut, the case checks nothing"
+                    else:
+                        assert r["words_cut"] == 0, tag       # no k_mc_prep result, or the cut switched off: nothing is dropped
+                    ref = ref or r
+                    assert r["bytes"] == ref["bytes"], tag
 
 
 @pytest.mark.parametrize("f0,f1", [(0, 1), (1, 2), (3, 4), (0, 2), (4, 6)])
@@ -139,7 +118,7 @@ def test_row_shards_equal_the_full_dispatch(gpu, level, f0, f1):
 @pytest.mark.parametrize("rough,n_tab", [(ROUGH, 1000), (ROUGH_LONG, 2048)])
 def test_table_lengths_the_tile_serves(gpu, level, rough, n_tab):
     """1000 samples end inside a mask word; 2048 fill 64 words, the last table one ballot of the run loop covers."""
-    assert _table(gpu, rough)[1] >= n_tab
+    assert mc.prefilter_table(gpu, rough)[1] >= n_tab
     got = _run(gpu, level, rough, 1, FULL, n_tab)
     assert _one_slice(got) and got["nw"] == (n_tab + 31) // 32 and got["healed"] == 0 and got["words_cut"] > 0, (got["cut4"], got["nw"], got["healed"])
     off = _run(gpu, level, rough, 1, FULL, n_tab, cut=0)
@@ -153,12 +132,12 @@ def test_table_lengths_the_tile_serves(gpu, level, rough, n_tab):
 def test_longer_tables_and_whole_faces_keep_the_16_tile(gpu, level):
     """2049 samples are 65 mask words: the level falls back to 16 x 16 x 4 and gives the bytes of pbrk_mc_set_tile32(0); so does the
     whole-face shape (n_src = 64), whatever the table."""
-    assert _table(gpu, ROUGH_LONG)[1] >= 2049
+    assert mc.prefilter_table(gpu, ROUGH_LONG)[1] >= 2049
     forced = _run(gpu, level, ROUGH_LONG, 1, n_tab=2049)
     never = _run(gpu, level, ROUGH_LONG, 0, n_tab=2049)
     assert not _one_slice(forced) and forced["nw"] == 65 and forced["healed"] == 0 and never["healed"] == 0
     assert forced["bytes"] == never["bytes"]
-    whole = _bordered(gpu, _level(64))
+    whole = mc.BorderedLevel(gpu, _level(64))
     try:
         forced = _run(gpu, whole, 0.15, 1)
         never = _run(gpu, whole, 0.15, 0)
@@ -189,7 +168,7 @@ def test_reported_cut_is_the_host_twin(gpu, level):
     lvl = _level(N_SRC)
     lvl[2, 10:14, 10:14, :3] *= 1e5
     kb, cb = _host_cut(L, ROUGH, lvl)
-    bord = _bordered(L, lvl)
+    bord = mc.BorderedLevel(L, lvl)
     try:
         bright = _run(L, bord, ROUGH, 1)
         off = _run(L, bord, ROUGH, 1, cut=0)
@@ -208,7 +187,7 @@ def test_negative_or_minus_zero_texel_switches_the_cut_off(gpu, where):
     for ch, bad in ((1, -1e-6), (2, -0.0)):
         lvl = _level(N_SRC)
         lvl[4, y, 20, ch] = bad
-        bord = _bordered(L, lvl)
+        bord = mc.BorderedLevel(L, lvl)
         try:
             on = _run(L, bord, ROUGH, 1)
             off = _run(L, bord, ROUGH, 1, cut=0)

@@ -4,83 +4,18 @@ identity is what the contract implies: fp64 interpolation from exact integers, t
 bit-identical, an EXACT shadow tap, no pow / exp2.  Scenes: tests/voxelize_scenes.py (at most 128^3 and a few hundred triangles; the
 end-to-end frame a few thousand)."""
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import sun_raster_ref as R  # noqa: E402
-import voxelize_raster_ref as V  # noqa: E402
-import voxelize_scenes as S  # noqa: E402
+import sun_raster_ref as R
+import voxelize_raster_ref as V
+import voxelize_scenes as S
+from gpu_rigs import VoxelizeRig as Rig, voxelize_globals as globals_of
 
 pytestmark = pytest.mark.gpu
 
 f32 = np.float32
-
-
-def globals_of(scene, **over):
-    import pbrhip
-    g = pbrhip.PBR_Globals()
-    sun, sun_dir, scale = over.get("sun", scene["sun"]), over.get("sun_dir", scene["sun_dir"]), over.get("scale", scene["scale"])
-    for k in range(16):
-        g.sun_space_from_world[k] = float(sun[k])
-    for k in range(4):
-        g.sun_direction[k] = float(sun_dir[k])
-    g.lightgrid_scale = float(scale)
-    return g
-
-
-class Rig:
-    """Light grid, a sun depth pass whose map is uploaded, the voxelise pass, materials and one PBR_Mesh per mesh of a scene."""
-
-    def __init__(self, L, scene):
-        import pbrhip
-        self.L, self.scene = L, scene
-        self.lg = L.PBR_MakeLightgrid(scene["N"])
-        self.sp = L.PBR_MakeSunDepthPass(scene["sun_map"].shape[0])
-        pbrhip.upload_mip(L.PBR_SunDepthTexture(self.sp), 0, scene["sun_map"])
-        self.vp = pbrhip.make_voxelize_pass(self.lg, self.sp)
-        self.mats = [pbrhip.make_material(m) for m in scene["materials"]]
-        self.meshes = [pbrhip.make_mesh(v, ix, [(0, len(ix))]) for v, ix in scene["meshes"]]
-        self.tex = L.PBR_LightgridTexture(self.lg)
-
-    def write_globals(self, g):
-        C.memmove(self.L.PBR_VoxelizeGlobalsBuffer(self.vp).contents.data, C.addressof(g), C.sizeof(g))
-
-    def record_pass(self, g, ps):
-        """The raw call sequence of render.cpp:1039-1056: the draws of one pass share a render-pass instance, each with its own set."""
-        L = self.L
-        if ps["clear"]:
-            L.PBR_RecordLightgridClear(self.lg, g)
-        L.GPU_OpPrepareRenderPass(g, L.PBR_VoxelizeRenderPass(self.vp))
-        params = [L.GPU_OpPrepareDrawParams(g, L.PBR_VoxelizePipeline(self.vp), L.PBR_VoxelizeDescriptorSet(self.vp, self.meshes[d["mesh"]], self.mats[d["material"]]))
-                  for d in ps["draws"]]
-        L.GPU_OpBeginRenderPass(g)
-        for p, d in zip(params, ps["draws"]):
-            L.GPU_OpBindDrawParams(g, p)
-            L.GPU_OpDraw(g, d["vertex_count"], d["instance_count"], d["first_vertex"], 0)
-        L.GPU_OpEndRenderPass(g)
-
-    def record(self, g, write_globals=True):
-        if write_globals:
-            self.write_globals(globals_of(self.scene))
-        for ps in self.scene["passes"]:
-            self.record_pass(g, ps)
-
-    def read(self):
-        import pbrhip
-        return pbrhip.read_mip(self.tex, 0)
-
-    def destroy(self):
-        L = self.L
-        L.PBR_DestroyVoxelizePass(self.vp)
-        for m in self.meshes:
-            L.PBR_DestroyMesh(m)
-        for m in self.mats:
-            L.PBR_DestroyMaterial(m)
-        L.PBR_DestroySunDepthPass(self.sp); L.PBR_DestroyLightgrid(self.lg)
 
 
 def check(name, got, want):

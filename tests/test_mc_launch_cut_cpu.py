@@ -12,60 +12,14 @@ from fractions import Fraction as F
 import numpy as np
 import pytest
 
+from f32_exact import SC, bits, from_bits, mul, rnd, round_f32, to_int
+from mc_cases import level
+from mc_cut_ref import head_sum, run_sample
+
 f32 = np.float32
 ROUGH = (0.03, 0.15)                                          # the tables of C4 mip 1 (1389 samples) and mip 2 (8192)
 # (m, M): ratios from 1 to 1e6
 RANGES = [(1.0, 1.0), (0.1, 1.1), (0.37, 25.0), (1e-3, 1.0), (0.01, 1e3), (2.5e-4, 250.0), (1.0, 1e6)]
-
-
-def round_f32(q):
-    """Exact value q rounded to the nearest fp32, ties to even (callers stay in range)."""
-    if q == 0:
-        return F(0)
-    sign = -1 if q < 0 else 1
-    a = abs(q)
-    e = a.numerator.bit_length() - a.denominator.bit_length()
-    while F(2) ** e > a:
-        e -= 1
-    while F(2) ** (e + 1) <= a:
-        e += 1
-    e = max(e, -126)
-    ulp = F(2) ** (e - 23)
-    k, r = divmod(a, ulp)
-    if r > ulp / 2 or (r == ulp / 2 and k % 2 == 1):
-        k += 1
-    return sign * k * ulp
-
-
-# The chains below run tens of thousands of FMAs.  Every fp32 value is a multiple of 2^-149 and every product of two a multiple of
-# 2^-298, so the same exact arithmetic runs on integers scaled by 2^SC (Fraction(x, 2^SC) is the value); test_integer_rounding_is_
-# the_fraction_rounding ties the two together.
-SC = 400
-
-
-def to_int(v):
-    q = F(float(v)) * 2 ** SC
-    assert q.denominator == 1
-    return q.numerator
-
-
-def rnd(x):
-    """round_f32 on a non-negative scaled integer"""
-    if x == 0:
-        return 0
-    e = max(x.bit_length() - 1 - SC, -126)
-    sh = e - 23 + SC                                          # the ulp as a power of two of the scaled integer
-    k, r = x >> sh, x & ((1 << sh) - 1)
-    half = 1 << (sh - 1)
-    if r > half or (r == half and k & 1):
-        k += 1
-    return k << sh
-
-
-def mul(a, b):
-    p = a * b
-    assert p & ((1 << SC) - 1) == 0
-    return p >> SC
 
 
 def test_integer_rounding_is_the_fraction_rounding():
@@ -78,14 +32,6 @@ def test_integer_rounding_is_the_fraction_rounding():
         assert F(rnd(mul(to_int(a), to_int(b)) + to_int(c)), 2 ** SC) == want
         assert F(rnd(to_int(c)), 2 ** SC) == F(c)
     assert rnd(to_int(2.0 ** -149) >> 1) == 0                 # a tie at half the smallest subnormal rounds to even
-
-
-def bits(v):
-    return int(np.array([v], dtype=np.float32).view(np.uint32)[0])
-
-
-def from_bits(b):
-    return float(np.array([b], dtype=np.uint32).view(np.float32)[0])
 
 
 @pytest.fixture(scope="module")
@@ -115,13 +61,6 @@ def lib_cut(L, w, m_bits, M_bits):
 
 def slice_end(s, NW):
     return s if s >= NW else s + 4 * ((NW - s + 3) // 4)
-
-
-def head_sum(w, s):
-    h = 0.0
-    for i in range(32):
-        h += float(w[32 * s + i])                             # double, index order
-    return h
 
 
 def word_ok(w, wd, s, m, M):
@@ -192,26 +131,6 @@ def test_cut_on_the_boundary_of_the_inequality(L, tables, rough):
 
 
 # ---- no-op chain ------------------------------------------------------------------------------
-
-def tap_weights(wgt, a, b):
-    """The kernel's six roundings (tap_accumulate): returns (w00, w10, w01, w11)."""
-    wa = rnd(mul(wgt, a)); w11 = rnd(mul(wa, b)); w10 = rnd(wa - w11)
-    wt = rnd(wgt - wa); w01 = rnd(mul(wt, b)); w00 = rnd(wt - w01)
-    assert 0 <= min(w00, w10, w01, w11) and max(w00, w10, w01, w11) <= wgt
-    return w00, w10, w01, w11
-
-
-def run_sample(acc, wgt, a, b, taps):
-    """One sample: four FMAs per sum, in the kernel's order (w00, w10, w01, w11); taps[c] = the four texels of channel c."""
-    tw = tap_weights(wgt, a, b)
-    out = []
-    for c in range(3):
-        r = acc[c]
-        for k in range(4):
-            r = rnd(mul(tw[k], taps[c][k]) + r)
-        out.append(r)
-    return out
-
 
 def chain_case(L, w, m, M, s, rng, reverse_head=False, grow_tail=False):
     m, M = float(f32(m)), float(f32(M))
@@ -308,12 +227,11 @@ def test_bad_arguments(L, tables):
 
 @pytest.mark.parametrize("n_src,rough", [(128, 0.03), (64, 0.15), (100, 0.03), (48, 0.15)])
 def test_generated_levels_give_a_cut(L, tables, n_src, rough):
-    """The levels of tests/test_gpu_mc_launch_cut.py: every texel of the bordered level is a texel of the level (or a mean of such), so
+    """The levels of tests/test_gpu_mc_launch_cut.py (mc_cases.level): every texel of the bordered level is a texel of the level (or a mean of such), so
     the level's own extrema bound the cut from the safe side.  The bright patch moves the cut later and leaves one."""
-    from test_gpu_mc_prologue import _level
     w = tables[rough][:, 3]
     NW = (len(w) + 31) // 32
-    lvl = _level(n_src)[..., :3]
+    lvl = level(n_src)[..., :3]
     k, cut = lib_cut(L, w, bits(lvl.min()), bits(lvl.max()))
     assert k >= NW // 4, (k, NW)
     kb, cutb = lib_cut(L, w, bits(lvl.min()), bits(lvl.max() * f32(1e5)))

@@ -1,5 +1,5 @@
 """The launch-level cut for S slices per workgroup (k_mc_region.hip, header 2h; mc_launch_cut_s in k_mc_internal.h) through its host
-entry pbrk_mc_launch_cut_slices, checked exactly with fractions with the helpers of test_mc_launch_cut_cpu.py.  Slice s of S owns the
+entry pbrk_mc_launch_cut_slices, checked exactly with fractions with the helpers of f32_exact.py and mc_cut_ref.py.  Slice s of S owns the
 mask words s, s + S, ..; word s is its head.  S = 4 is the 16 x 16 tile's cut (pbrk_mc_launch_cut), S = 1 the 32 x 32 tile's: one
 head word, weighed against the whole table.
 
@@ -10,11 +10,15 @@ head word, weighed against the whole table.
   * every sample of a cut word leaves a lane's three fp32 sums unchanged, bit for bit, for sums at the proved lower bound -- the
     slice's head word accumulated with every tap at m."""
 import ctypes as C
+from fractions import Fraction as F
 
 import numpy as np
 import pytest
 
-from test_mc_launch_cut_cpu import F, SC, bits, f32, from_bits, head_sum, run_sample, to_int
+from f32_exact import SC, bits, from_bits, to_int
+from mc_cut_ref import head_sum, run_sample
+
+f32 = np.float32
 
 SLICES = (1, 2, 4)
 # (roughness of the reference's table, samples taken from its front): 1389 is the whole roughness-0.03 table (C4 mip 1); 2048 samples

@@ -13,32 +13,9 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import geometry_raster_ref as G  # noqa: E402
 import voxelize_raster_ref as V  # noqa: E402
+from geometry_scenes import flat_material, vertices  # noqa: E402
 
 f32 = np.float32
-
-
-def vertices(pos, uv=None):
-    pos = np.asarray(pos, f32)
-    v = np.zeros((len(pos), 11), f32)
-    v[:, 0:3] = pos
-    v[:, 3:6] = (0.0, 0.0, 1.0)
-    v[:, 6:9] = (1.0, 0.0, 0.0)
-    if uv is not None:
-        v[:, 9:11] = uv
-    return v
-
-
-def flat_material(size=32, seed=1):
-    """Material whose emissive texels are all distinct (as tests/test_gpu_geometry.py's): a triangle with one uv on a texel centre
-    shows that texel's colour."""
-    rng = np.random.default_rng(seed)
-    base = np.full((size, size, 4), 255, np.uint8)
-    base[..., :3] = rng.integers(0, 256, (size, size, 3))
-    nrm = np.full((size, size, 4), 128, np.uint8)
-    orm = rng.integers(0, 256, (size, size, 4)).astype(np.uint8)
-    k = np.arange(size * size).reshape(size, size)
-    emi = np.stack([k % 256, k // 256 * 16 + 7, (k * 7) % 256, np.full_like(k, 255)], -1).astype(np.uint8)
-    return [base, nrm, orm, emi]
 
 
 def constant_material(base, emissive, size=4):

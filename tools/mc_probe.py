@@ -13,6 +13,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "vulkan-pbr-renderer_amd", "python"))
 import pbrhip  # noqa: E402
+from pbrhip import mc  # noqa: E402
 if os.environ.get("PBRHIP_LIB"):
     pbrhip.LIB_PATH = os.environ["PBRHIP_LIB"]
 
@@ -61,24 +62,20 @@ def main():
     print(f"n_src {n_src} out {out} rows {rows} faces {f0}-{f1} n_tab {n_tab}: {ms:.3f} ms  {ps:.3f} ps/eval  {clk:.1f} clk per wave-sample per CU @2.4GHz  "
           f"{65 * evals / ms * 1e-9:.1f} TFLOP/s alg  checksum {chk:.6e}", flush=True)
     if os.environ.get("PBR_MC_STATS") == "1":
-        st = (C.c_uint64 * 2)()
-        fl = (C.c_uint64 * 3)()
-        if L.pbrk_mc_region_flag_stats(fl) == 0 and fl[1]:
-            tiles = fl[1] // n_tab
-            wn = (C.c_uint64 * 1)()
-            L.pbrk_mc_region_window_stats(wn)
-            print(f"   binning: {fl[0] / fl[1]:.3f} regions flagged per sample, {fl[2] / tiles:.2f} regions visited per tile ({tiles} tile launches), "
-                  f"{wn[0] / fl[1]:.3f} of the samples proved in-region for the whole tile (test-free body)", flush=True)
-        sk, c6, ph = (C.c_uint64 * 3)(), (C.c_int * 6)(), (C.c_uint64 * 5)()
-        if L.pbrk_mc_region_skip_stats(sk) == 0 and L.pbrk_mc_launch_cut_stats(c6) == 0 and fl[0]:
-            print(f"   absorbed: {sk[1] / (4 * fl[0]):.4f} of the flagged wave-samples ({sk[2]} through the count-only body); cut words {list(c6[:4])} of {c6[4]}, "
-                  f"{c6[5]} words cut", flush=True)
-        if L.pbrk_mc_region_phase_stats(ph) == 0 and ph[1] and L.pbrk_mc_region_stats(st, 0) == 0 and st[1]:
-            tiles = st[1] // 16                                # workgroups: sixteen waves each (the flag counters count blocks of 256 texels)
+        c = mc.counters(L, "flag", "window", "skip", "cut", "phase", "region", reset=True, missing_ok=True)
+        if c.get("flag_samples"):
+            tiles = c["flag_samples"] // n_tab
+            print(f"   binning: {c['flags'] / c['flag_samples']:.3f} regions flagged per sample, {c['visits'] / tiles:.2f} regions visited per tile ({tiles} tile launches), "
+                  f"{c.get('proved', 0) / c['flag_samples']:.3f} of the samples proved in-region for the whole tile (test-free body)", flush=True)
+        if "abs_samples" in c and "cut4" in c and c.get("flags"):
+            print(f"   absorbed: {c['abs_samples'] / (4 * c['flags']):.4f} of the flagged wave-samples ({c['count_only']} through the count-only body); cut words {c['cut4']} of {c['nw']}, "
+                  f"{c['words_cut']} words cut", flush=True)
+        if c.get("phase", (0, 0))[1] and c.get("slices"):
+            tiles = c["slices"] // 16                          # workgroups: sixteen waves each (the flag counters count blocks of 256 texels)
             print("   clocks per tile (frames, clearing + binning, staging, region passes, reduction + store): "
-                  + ", ".join(f"{v / tiles:.0f}" for v in ph), flush=True)
-        if L.pbrk_mc_region_stats(st, 1) == 0:
-            print(f"   region kernel: {st[0]} of {st[1]} wave-slices recomputed with direct loads", flush=True)
+                  + ", ".join(f"{v / tiles:.0f}" for v in c["phase"]), flush=True)
+        if "healed" in c:
+            print(f"   region kernel: {c['healed']} of {c['slices']} wave-slices recomputed with direct loads", flush=True)
     L.GPU_WaitUntilIdle(); L.GPU_Deinit()
 
 

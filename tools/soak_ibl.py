@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "vulkan-pbr-renderer_amd", "python")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import pbrhip  # noqa: E402
 import pbr_oracle as O  # noqa: E402
-from pbrhip import synth  # noqa: E402
+from pbrhip import mc, synth  # noqa: E402
 
 
 def rel(a, b, floor=1e-3):
@@ -69,10 +69,10 @@ def main():
         worst = max(worst, max(errs.values()))
         print(f"region sizes, run {run}: env {W}^2 -> specular {out}^2 sun {np.round(d, 2)}: max rel over 3 random rows per mip {({m: f'{e:.1e}' for m, e in errs.items()})}", flush=True)
         L.PBR_DestroyIBLMaps(C.byref(maps)); L.GPU_DestroyTexture(env_tex)
-    st = (C.c_uint64 * 2)()
-    if L.pbrk_mc_region_stats(st, 0) == 0:
-        print(f"region kernel self-check: {st[0]} of {st[1]} wave-slices recomputed with direct loads")
-        if st[0]:
+    st = mc.counters(L, "region", missing_ok=True)
+    if st:
+        print(f"region kernel self-check: {st['healed']} of {st['slices']} wave-slices recomputed with direct loads")
+        if st["healed"]:
             return 1
     print(f"WORST {worst:.3e}")
     return 0 if worst < 1e-4 else 1
