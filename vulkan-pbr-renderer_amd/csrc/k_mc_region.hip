@@ -22,8 +22,9 @@
 //      region of the same face (the bound of step 1 read as "certainly" instead of "possibly"): those run a body without the
 //      in-face / in-region tests, their six ballots, the exec masking and the pair count -- 37 instead of 45 instructions.
 //      Measured (one box, A/B): C4 mip 1 36.7 -> 35.1 ms.  The same on the whole-face levels (39 -> 37 instructions) LOSES
-//      3-5 % -- the wave-uniform choice of body per sample costs more than two comparisons -- so it is compiled for SUB only;
-//      two separate loops (proved samples, then the rest) were slower on every level.
+//      3-5 % -- the wave-uniform choice of body per sample costs more than two comparisons -- so the round-3 pass compiles it for
+//      SUB only (2i: the run loop of 2d has no such choice); two separate loops (proved samples, then the rest) were slower on every
+//      level.
 //   2c. (round 4, absorbed words) a mask word whose samples provably cannot change any lane's fp32 sums is not accumulated
 //      (the lemma at absorb_threshold); its samples only run the count-only body, so the check of step 3 still sees every pair.
 //      Compiled for the 66^2 region shapes only (ABS).
@@ -73,6 +74,19 @@
 //      the 16 x 16 x 4 bytes, not equal.  One ballot of region_pass_runs covers 64 words here, so the tile serves tables of at most
 //      2048 samples.  Which levels take it is mc_tile32's rule (level shape and output size only; pbrk_mc_set_tile32; MC_TILE32_SUB);
 //      every other level keeps 16 x 16 x 4 and its bytes.  DESIGN.md 4, "K4b, round 9"; profiles/r09_tile32.md.
+//   2i. (round 10, proved runs on the whole-face shapes) the run loop of 2d walks the proved samples below the next tested one as a
+//      tight loop found with bit operations per run, so the proof of 2b costs no choice per sample.  It was only ever compiled for
+//      SUB; CERT now holds under RUNS on the whole-face shapes too: the 66^2 one (MC_CERT_G1; both LEAN values) and the 34^2 one, which
+//      gets the RUNS instantiation for it (no absorb test, index order, one phase as before; counts per lane).  A proved sample runs
+//      37 VALU instructions instead of 40 and no exec join.  The samples accumulated, their order and arithmetic do not change: same
+//      bytes; pbrk_mc_set_runs(0) keeps region_pass with CERT = SUB as the yardstick.  The proof is read per SAMPLE by every pass
+//      (cmask has no region index), so it must hold for exactly one flagged region: on these shapes binning sets the bit only when
+//      one face alone is flagged (region_bin, SOLE) -- in C4 mip 2 one (tile, sample) pair of 2e8 met the two rounded inequalities
+//      within an ulp, was proved on +X and flagged on +Y, and the +Y pass credited it again (four wave-slices recomputed by step 3).
+//      The quarter-face shape keeps its binning (one region per sample there as well, and the same ulp could meet it; not seen, and step
+//      3 catches it).  Measured (profiles/r10_certain_g1.md): C4 mip 2 24.45 -> 23.65 ms, mip 3 11.67 -> 11.09 ms, the job 50.2 -> 48.9 ms.
+//      The 18^2 shape (mip 4) LOSES with the run loop (3.71 -> 4.11 ms: 78 % proved, runs of three or four samples): it keeps the
+//      round-3 pass and has no RUNS instantiation.  A table of more than 64 words per slice would take the round-3 pass (launch_runs).
 // Each (texel, sample) pair is accumulated exactly once, in an order (66^2 shapes: head phase then tail phase; in each, own face's
 // regions, then the other regions in index order; else regions in index order; sample index inside a region) that depends on the
 // level's shape and the texel's face only, not on the tile: a row-sharded dispatch equals a full one bit for bit.
@@ -106,6 +120,11 @@ typedef const __attribute__((address_space(4))) unsigned* cu32_t;
 #ifndef MC_HEAD_FIRST_G1
 #define MC_HEAD_FIRST_G1 1
 #endif
+// Header 2i, decided per whole-face shape by measurement: under RUNS the samples binning proves for the whole tile run as test-free runs
+// (CERT in k_mc_region).  The 34^2 shape takes them; MC_CERT_G1 is the 66^2 whole-face shape: 0 keeps the machine code it had without.
+#ifndef MC_CERT_G1
+#define MC_CERT_G1 1
+#endif
 
 // Header 2h: 32 x 32 tiles x 1 slice on the quarter-face shape where mc_tile32's rule holds.  0 keeps 16 x 16 x 4 and the parent's bytes
 // (pbrk_mc_set_tile32(1) still selects the tile).
@@ -129,7 +148,7 @@ struct RegArgs {
     int cut;                    // header 2g: tabmax holds, behind the maxima, the first cut word of each slice (k_mc_cut); 0: no word is dropped
     int absorb;                 // skip mask words whose samples are absorbed by every lane's sums (pbrk_mc_set_absorb; bit-identical)
     unsigned long long* stats;  // optional: [0] += healed wave-slices, [1] += all wave-slices, [2] += (region, sample) flags, [3] += samples per tile, [4] += regions visited,
-                                // [5] += proved samples (SUB), [6] += absorbed wave-words, [7] += their wave-samples, [8] += of those run through the
+                                // [5] += proved samples (CERT), [6] += absorbed wave-words, [7] += their wave-samples, [8] += of those run through the
                                 // count-only body (a tile's region passes run 4 x [2] wave-samples in all: [2] .. [5] count per block of 256 texels, a 32 x 32 tile four times); PBR_MC_PHASE_STAMPS builds: [9..13] += clocks of
                                 // a workgroup's first lane in frames, clearing + binning, staging, region passes, reduction + store
 };
@@ -409,10 +428,14 @@ __device__ __forceinline__ void region_pass_runs(const RegionView& V, const unsi
 // direction is pushed through the tile-centre frame; a rigorous bound on how far a texel's own frame can move it yields the
 // regions; one bit per (region, sample) in `masks`, any[r] != 0 when region r has a bit.  Leaves with a barrier pending: callers
 // synchronise before reading the masks.
-// cmask (optional, [NW]): bit i set when sample i is PROVED to tap one region of one face from every texel of the tile -- certainly
+// cmask (PROOF, [NW]): bit i set when sample i is PROVED to tap one region of one face from every texel of the tile -- certainly
 // on the face (ma' - |sc'| >= (ma - |sc|) - sqrt(2) delta > 0), its tap bounds inside the face and inside one region's cells.  Such
 // a sample has exactly one region flag.  wmax (optional, [NW]): per mask word, the largest bit pattern of its samples' weights (for
 // weights >= +0 the largest weight; anything else orders above +inf).  The ntail words behind dmax are zeroed with the masks.
+// SOLE (header, 2i; one region per face): the bit is set only when that face is the ONLY one flagged for the sample.  The inequalities
+// say so (ma - sqrt(2) delta > |sc| on one face excludes ma' + sqrt(2) delta >= |sc'| on every other), but both sides are rounded:
+// when they meet within an ulp a sample was proved on one face and flagged on its neighbour, and the neighbour's pass, which reads
+// the proof per sample and not per region, took it as proved there too.
 // LEAN (header, 2f): G and RC are compile-time facts -- G1: one region per face, r = f and no division; else the quarter-face shape,
 // RC = 65 -- and the reach bound takes v_rcp_f32 / v_sqrt_f32 (1 ulp each) for the two divisions and two square roots.  That
 // moves mu, mv by less than 5e-7 relative (rl enters three times, the root once: 4 x 2^-23 and their roundings), inside the 1.0001
@@ -422,7 +445,7 @@ __device__ __forceinline__ void region_pass_runs(const RegionView& V, const unsi
 // slices) and byte 1 for the tail words.  lim: the first sample index this thread does not bin -- 32 x the cut word of its slice (a
 // thread's samples i = tid + 1024 k all fall into slice (tid >> 5) % S), n_tab without a cut.  keep_cut (counters only): the samples behind lim still run and set their mask bits, but no
 // region flag; the caller counts and clears those bits.
-template <bool LEAN, bool G1, bool TWO>
+template <bool LEAN, bool G1, bool TWO, bool PROOF, bool SOLE>
 __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsigned* dmax, int NR, int NW, int G, int RC, int n,
                                            f3 R, f3 T, f3 B, f3 Rc, f3 Tc, f3 Bc, ctab_t tab, int n_tab, int tid,
                                            unsigned* cmask, unsigned* wmax, int ntail, int lim, bool keep_cut, int head_end) {
@@ -451,6 +474,8 @@ __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsig
         const float Lz = fmaf(e.x, Bc.z, fmaf(e.y, Tc.z, e.z * Rc.z));
         const unsigned bit = 1u << (i & 31);
         if (!LEAN && wmax) atomicMax(&wmax[i >> 5], __float_as_uint(e.w));
+        [[maybe_unused]] int nflag = 0;                                    // SOLE: the faces flagged for this sample, and whether one of them proved it
+        [[maybe_unused]] bool proved = false;
 #pragma unroll
         for (int f = 0; f < 6; ++f) {
             float sc, tc, ma;
@@ -475,8 +500,9 @@ __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsig
                 if (uh < 0.0f || ul > nf || vh < 0.0f || vl > nf) continue;      // cannot be on this face at all
                 lo_u = (int)fmaxf(ul, 0.0f); hi_u = (int)fminf(uh, nf);
                 lo_v = (int)fmaxf(vl, 0.0f); hi_v = (int)fminf(vh, nf);
-                certain = cmask && ma - d2 > fabsf(sc) && ma - d2 > fabsf(tc) && ul >= 0.0f && uh <= nf && vl >= 0.0f && vh <= nf;
+                certain = PROOF && cmask && ma - d2 > fabsf(sc) && ma - d2 > fabsf(tc) && ul >= 0.0f && uh <= nf && vl >= 0.0f && vh <= nf;
             }
+            if (SOLE) { ++nflag; proved = proved || certain; certain = false; }
             if (LEAN && G1) {                                              // RC = n + 1: every tap position of the face lies in region f
                 if (certain) atomicOr(&cmask[i >> 5], bit);
                 atomicOr(&masks[f * NW + (i >> 5)], bit);
@@ -495,6 +521,7 @@ __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsig
                     else any[r] = 1u;
                 }
         }
+        if (SOLE && proved && nflag == 1) atomicOr(&cmask[i >> 5], bit);
     }
 }
 
@@ -645,13 +672,14 @@ __device__ __forceinline__ void reduce_slices(float* red, int s, int t, float ar
 #define STAMP() 0ull
 #endif
 
-// RUNS (66^2 shapes only): the region loop visits the flagged regions only and runs region_pass_runs (round 5; cnt per lane)
+// RUNS (66^2 shapes and the 34^2 shape): the region loop visits the flagged regions only and runs region_pass_runs (round 5; cnt per lane)
 // LEAN: the prologue of header 2f (pbrk_mc_set_prologue); false: the one before it, kept as the yardstick
 // The body reads: frames, bin, credit, the loop of (stage, pass) over the flagged regions, check / heal, reduce / store.
 template <int RS, bool SUB, int TILE, bool RUNS = false, bool LEAN = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_mc_region(const RegArgs q) {
     constexpr int REG_TX = TILE * TILE, REG_S = 1024 / REG_TX;
-    constexpr bool CERT = SUB;                                           // see the header, 2b
+    // see the header, 2b and 2i: quarter faces always; whole faces only with the run loop, which pays no per-sample choice of body
+    constexpr bool CERT = SUB || (RUNS && (RS != 66 || MC_CERT_G1 != 0));
     // see the header, 2c: compiled for the 66^2 region shapes only.  The 34^2 / 18^2 levels of C4 (mips 3, 4: weights fall to ~e^-6)
     // never absorb a word, and the test alone cost them 7 % (measured); without it their code is that of round 3
     constexpr bool ABS = RS == 66;
@@ -710,7 +738,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     // the first cut word of this thread's slice (a vector load of one of the REG_S words behind the maxima): samples tid + 1024 k lie
     // in word (tid >> 5) + 32 k, that is in slice (tid >> 5) % REG_S
     const int lim = cut_on ? (int)q.tabmax[NW + NR + ((tid >> 5) % REG_S)] << 5 : 0x7fffffff;
-    region_bin<LEAN, !SUB, TWO>(masks, any, dmax, NR, NW, G, RC, n, R, T, B, Rc, Tc, Bc, tab, p.n_tab, tid, (CERT || ABS) ? cmask : nullptr,
+    region_bin<LEAN, !SUB, TWO, CERT || ABS, CERT && !SUB>(masks, any, dmax, NR, NW, G, RC, n, R, T, B, Rc, Tc, Bc, tab, p.n_tab, tid, (CERT || ABS) ? cmask : nullptr,
                                 (absorb_on && !LEAN) ? wmax : nullptr, ntail, lim, cut_on && q.stats != nullptr, 32 * REG_S);
     [[maybe_unused]] unsigned long long st_stage = 0ull;
 #ifdef PBR_MC_PHASE_STAMPS
@@ -1025,20 +1053,24 @@ extern "C" int pbrk_mc_launch_cut_stats(int* out6) {
     return PBRK_OK;
 }
 
-// the 66^2 shapes: the round-5 loop (pbrk_mc_set_runs) or the one before it
-template <bool SUB, int TILE, bool LEAN>
-static void launch_66(const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
-    if (g_mc_runs) launch_region_t<66, SUB, TILE, true, LEAN>(q, grid, lds, st);
-    else launch_region_t<66, SUB, TILE, false, LEAN>(q, grid, lds, st);
+// The round-5 loop (pbrk_mc_set_runs) on the shapes that have it (HAS_RUNS), or the pass before it.  One ballot of region_pass_runs
+// covers 64 words per slice: a longer table takes the pass before it as well (launch_mc_region admits at most 8192 samples, 256 words,
+// and mc_tile32 at most 64 words on the one-slice tile, so today that never happens).
+template <int RS, bool SUB, int TILE, bool LEAN, bool HAS_RUNS = true>
+static void launch_runs(const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
+    if constexpr (HAS_RUNS) {
+        if (g_mc_runs && q.NW <= 64 * (1024 / (TILE * TILE))) { launch_region_t<RS, SUB, TILE, true, LEAN>(q, grid, lds, st); return; }
+    }
+    launch_region_t<RS, SUB, TILE, false, LEAN>(q, grid, lds, st);
 }
 
 template <bool LEAN>
 static void launch_shape(int RS, int tile, const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
-    if (tile == 32) launch_66<true, 32, LEAN>(q, grid, lds, st);
-    else if (RS == 18) launch_region_t<18, false, 16, false, LEAN>(q, grid, lds, st);
-    else if (RS == 34) launch_region_t<34, false, 16, false, LEAN>(q, grid, lds, st);
-    else if (q.G == 1) launch_66<false, 16, LEAN>(q, grid, lds, st);
-    else launch_66<true, 16, LEAN>(q, grid, lds, st);
+    if (tile == 32) launch_runs<66, true, 32, LEAN>(q, grid, lds, st);
+    else if (RS == 18) launch_runs<18, false, 16, LEAN, false>(q, grid, lds, st);    // header 2i: the run loop loses on this shape
+    else if (RS == 34) launch_runs<34, false, 16, LEAN>(q, grid, lds, st);
+    else if (q.G == 1) launch_runs<66, false, 16, LEAN>(q, grid, lds, st);
+    else launch_runs<66, true, 16, LEAN>(q, grid, lds, st);
 }
 
 // Which tile serves a level (header 2h): a function of the level alone -- n_src, n_tab, the output size -- never of the dispatch's faces
