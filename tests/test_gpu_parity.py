@@ -190,38 +190,100 @@ def _run_prefilter(gpu, env_tex, out_size, min_size):
     return spec
 
 
+LUT_TEXEL_BYTES = {"RG32F": 8, "RGBA32F": 16, "RG16F": 4}
+
+
+class _LutRig:
+    """The host tables K1 reads (sample angles; cos / sin of every column's view angle), as the backend builds them, on the device."""
+
+    def __init__(self, L, size, nsamples):
+        import pbrhip
+        self.L, self.size, self.nsamples = L, size, nsamples
+        ang = np.zeros((nsamples, 4), np.float32)
+        L.pbrk_host_sample_angles(nsamples, ang.ctypes.data_as(C.c_void_p))
+        libm = C.CDLL("libm.so.6")                                                  # the host's fp32 libm, as the backend builds its table (gpu_hip.cpp)
+        for fn in (libm.acosf, libm.cosf, libm.sinf):
+            fn.restype = C.c_float; fn.argtypes = [C.c_float]
+        vcs = np.zeros((size, 2), np.float32)
+        for x in range(size):                                                       # V = Rotate((0,0,1), (1,0,0), acos(NdotV)): cos / sin of that angle
+            th = libm.acosf(C.c_float(float((np.float32(x) + np.float32(0.5)) / np.float32(size))))
+            vcs[x] = (libm.cosf(th), libm.sinf(th))
+        self.buffers = [L.GPU_MakeBuffer(ang.nbytes, pbrhip.BufferFlag_GPU, ang.ctypes.data_as(C.c_void_p)),
+                        L.GPU_MakeBuffer(vcs.nbytes, pbrhip.BufferFlag_GPU, vcs.ctypes.data_as(C.c_void_p))]
+
+    def run(self, fmt="RG32F", rows=None, fill=None):
+        """One dispatch of rows [y0, y1) (default: all) into a fresh buffer, pre-filled with the byte `fill` if given; the buffer's bytes."""
+        import pbrhip
+        L, size = self.L, self.size
+        nbytes = size * size * LUT_TEXEL_BYTES[fmt]
+        init = np.full(nbytes, fill, np.uint8) if fill is not None else None
+        out = L.GPU_MakeBuffer(nbytes, pbrhip.BufferFlag_GPU, init.ctypes.data_as(C.c_void_p) if init is not None else None)
+        host = L.GPU_MakeBuffer(nbytes, pbrhip.BufferFlag_CPU, None)
+        y0, y1 = rows or (0, size)
+        assert L.pbrk_brdf_lut(L.GPUX_BufferDevicePtr(out), getattr(pbrhip, "PBRK_FMT_" + fmt), size, self.nsamples,
+                               L.GPUX_BufferDevicePtr(self.buffers[0]), L.GPUX_BufferDevicePtr(self.buffers[1]), y0, y1, None) == 0
+        g = L.GPU_MakeGraph()
+        L.GPU_WaitUntilIdle()
+        L.GPU_OpCopyBufferToBuffer(g, out, host, 0, 0, nbytes); L.GPU_GraphSubmit(g); L.GPU_GraphWait(g)
+        got = np.frombuffer((C.c_char * nbytes).from_address(host.contents.data), np.uint8).copy()
+        L.GPU_DestroyGraph(g)
+        L.GPU_DestroyBuffer(out); L.GPU_DestroyBuffer(host)
+        return got
+
+    def close(self):
+        for b in self.buffers:
+            self.L.GPU_DestroyBuffer(b)
+
+
 @pytest.mark.parametrize("nsamples", [5000, 12288])
 def test_brdf_lut_any_sample_count(gpu, nsamples):
     """K1 keeps the sample directions in LDS; since round 3 they pass through it in chunks of 4096, so sample counts
     beyond one chunk (a ragged second chunk: 5000; three chunks: 12288 -- more than the 9600 that once fitted) work and equal the
     oracle.  Low-level kernel ABI (pbrk_brdf_lut) with the host tables, 64^2 map, fp32 target."""
-    import pbrhip, pbr_oracle as O
-    L = gpu
+    import pbr_oracle as O
     size = 64
-    ang = np.zeros((nsamples, 4), np.float32)
-    L.pbrk_host_sample_angles(nsamples, ang.ctypes.data_as(C.c_void_p))
-    libm = C.CDLL("libm.so.6")                                                      # the host's fp32 libm, as the backend builds its table (gpu_hip.cpp)
-    for fn in (libm.acosf, libm.cosf, libm.sinf):
-        fn.restype = C.c_float; fn.argtypes = [C.c_float]
-    vcs = np.zeros((size, 2), np.float32)
-    for x in range(size):                                                           # V = Rotate((0,0,1), (1,0,0), acos(NdotV)): cos / sin of that angle
-        th = libm.acosf(C.c_float(float((np.float32(x) + np.float32(0.5)) / np.float32(size))))
-        vcs[x] = (libm.cosf(th), libm.sinf(th))
-    d_ang = L.GPU_MakeBuffer(ang.nbytes, pbrhip.BufferFlag_GPU, ang.ctypes.data_as(C.c_void_p))
-    d_vcs = L.GPU_MakeBuffer(vcs.nbytes, pbrhip.BufferFlag_GPU, vcs.ctypes.data_as(C.c_void_p))
-    out = L.GPU_MakeBuffer(size * size * 8, pbrhip.BufferFlag_GPU, None)
-    host = L.GPU_MakeBuffer(size * size * 8, pbrhip.BufferFlag_CPU, None)
-    assert L.pbrk_brdf_lut(L.GPUX_BufferDevicePtr(out), pbrhip.PBRK_FMT_RG32F, size, nsamples, L.GPUX_BufferDevicePtr(d_ang), L.GPUX_BufferDevicePtr(d_vcs), 0, size, None) == 0
-    g = L.GPU_MakeGraph()
-    L.GPU_WaitUntilIdle()
-    L.GPU_OpCopyBufferToBuffer(g, out, host, 0, 0, size * size * 8); L.GPU_GraphSubmit(g); L.GPU_GraphWait(g)
-    got = np.frombuffer((C.c_char * (size * size * 8)).from_address(host.contents.data), np.float32).reshape(size, size, 2).copy()
+    rig = _LutRig(gpu, size, nsamples)
+    try:
+        got = rig.run().view(np.float32).reshape(size, size, 2)
+    finally:
+        rig.close()
     want = O.brdf_lut(size, nsamples)[..., :2]
     e = np.abs(got.astype(np.float64) - want) / np.maximum(np.abs(want), 1e-3)
     assert e.max() < REL, float(e.max())
-    L.GPU_DestroyGraph(g)
-    for b in (d_ang, d_vcs, out, host):
-        L.GPU_DestroyBuffer(b)
+
+
+@pytest.mark.parametrize("size,nsamples", [(1, 1), (3, 63), (17, 100), (24, 65), (40, 4096)])
+def test_brdf_lut_ragged_sizes_and_sample_counts(gpu, size, nsamples):
+    """K1 off the multiples of its 16-row blocks, 8 waves per workgroup and 64 lanes: 40 = 2 * 16 + 8 rows (a ragged last row
+    block); 17 columns x 2 row blocks = 34 items (idle waves in the last workgroup); 1 and 63 samples (lanes without a sample
+    still join the butterfly); 65 (one sample in the second pass over the lanes).  Row shards that start and end off a multiple
+    of 16 give the full dispatch's bits and touch no other row; the three target formats of the raw entry point agree."""
+    import pbr_oracle as O
+    rig = _LutRig(gpu, size, nsamples)
+    try:
+        full_bytes = rig.run()
+        full = full_bytes.view(np.float32).reshape(size, size, 2)
+        want = O.brdf_lut(size, nsamples)[..., :2]
+        assert np.isfinite(want).all()
+        e = np.abs(full.astype(np.float64) - want) / np.maximum(np.abs(want), 1e-3)
+        print("max rel", e.max())
+        assert e.max() < REL, float(e.max())
+        if (size, nsamples) == (40, 4096):
+            rows_of = lambda b: b.reshape(size, size * 8)
+            for (y0, y1) in ((0, 7), (7, 23), (23, 40)):
+                got = rows_of(rig.run(rows=(y0, y1), fill=0xA5))
+                assert np.array_equal(got[y0:y1], rows_of(full_bytes)[y0:y1]), (y0, y1)
+                assert np.all(got[:y0] == 0xA5) and np.all(got[y1:] == 0xA5), (y0, y1)
+        if (size, nsamples) == (17, 100):
+            rgba = rig.run("RGBA32F").view(np.float32).reshape(size, size, 4)
+            assert np.array_equal(rgba[..., :2].view(np.uint32), full.view(np.uint32))
+            assert np.all(rgba[..., 2] == 0.0) and np.all(rgba[..., 3] == 1.0)
+            h = rig.run("RG16F").view(np.uint16).reshape(size, size, 2).astype(np.int32)
+            ref = full.astype(np.float16).view(np.uint16).astype(np.int32)
+            assert np.abs(h - ref).max() <= 1
+            assert (h != ref).mean() < 0.01
+    finally:
+        rig.close()
 
 
 def test_prefilter_env64_vs_oracle_a(gpu, env64, golden_dir):

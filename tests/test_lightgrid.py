@@ -54,6 +54,87 @@ def test_oracle_sweep_properties():
     assert np.array_equal(part[:, :, :64], full[:, :, :64]) and np.array_equal(part[:, :, 64:], g[:, :, 64:])
 
 
+# Shapes (d, h, w) and directions off the reference's cube: odd pitches, line axes longer than 128, tiles of 3, 4, 8 and 9 lines.
+RAGGED = [((5, 128, 131), 0), ((5, 128, 131), 1), ((3, 131, 129), 0), ((3, 131, 129), 1), ((130, 3, 9), 2), ((129, 6, 4), 2), ((4, 8, 128), 0)]
+SHIFTED = ((4, 8, 130), 0)          # swept through the raw entry point from voxel 1 of every line: the unpaired paths on an even pitch
+_ragged_cache = {}
+
+
+def _ragged_case(shape, direction, sprinkle):
+    """(grid, oracle's sweep of it) of one ragged case, computed once and shared by the CPU and GPU tests: read-only."""
+    from pbrhip import synth
+    key = (shape, direction, sprinkle)
+    if key not in _ragged_cache:
+        idx = (RAGGED + [SHIFTED]).index((shape, direction))
+        grid = synth.synth_lightgrid_hostile(shape, 0x5EED0700 + 2 * idx + int(sprinkle), sprinkle=sprinkle)
+        if (shape, direction) == SHIFTED:
+            want = grid.copy()
+            want[:, :, 1:129] = O.lightgrid_sweep(np.ascontiguousarray(grid[:, :, 1:129]), direction)
+        else:
+            want = O.lightgrid_sweep(grid, direction)
+        grid.setflags(write=False); want.setflags(write=False)
+        _ragged_cache[key] = (grid, want)
+    return _ragged_cache[key]
+
+
+def _isnan16(bits):
+    return (bits & 0x7FFF) > 0x7C00
+
+
+def _assert_same_halves(got, want, what):
+    """Bit equality, except that where `want` is a NaN any NaN will do."""
+    nan = _isnan16(want)
+    assert np.array_equal(_isnan16(got), nan), f"{what}: NaN-ness differs on {(_isnan16(got) != nan).sum()} halves"
+    assert np.array_equal(got[~nan], want[~nan]), f"{what}: {(got[~nan] != want[~nan]).sum()} halves differ"
+
+
+def _shader_sweep_numpy(grid, direction):
+    """lightgrid_sweep.glsl:9-75 restated in numpy, every line of the image at once: fp32 arithmetic in the shader's literal
+    order, fp16 stores by astype."""
+    g = np.array(grid, np.uint16)
+    lines = np.moveaxis(g, {0: 2, 1: 1, 2: 0}[direction], 0)[:128]          # [x][...][4], a view: :10-22, :28
+    f32 = np.float32
+    sky = np.array([1.0, 1.2, 2.0], f32)                                    # :23
+    with np.errstate(all="ignore"):
+        old = lines.view(np.float16).astype(f32)                            # :28-29
+        val = old.copy()
+        occupied = (old[..., 3] > f32(0.5))[..., None]                      # :39, :55
+        for order, last in ((range(128), 127), (range(127, -1, -1), 0)):    # :35-48, :51-66
+            m = np.broadcast_to(sky, old.shape[1:-1] + (3,))
+            for x in order:
+                t = val[x, ..., :3] + m                                     # :43
+                nm = f32(0.5) * t                                           # :44
+                val[x, ..., :3] = np.where(occupied[x], val[x, ..., :3], t - nm)    # :45
+                m = np.where(occupied[x], old[x, ..., :3], nm)              # :40
+            val[last, ..., :3] = val[last, ..., :3] + m                     # :48, :66
+        mixed = old * (f32(1.0) - f32(0.35)) + val * f32(0.35)              # :70 mix(x, y, a) = x * (1 - a) + y * a
+        store = old[..., 3] < f32(0.5)                                      # :71
+        lines[store] = mixed.astype(np.float16).view(np.uint16)[store]      # :72
+    return g
+
+
+@pytest.mark.parametrize("sprinkle", [False, True], ids=["finite", "sprinkled"])
+def test_oracle_matches_numpy_restatement_off_the_cube(sprinkle):
+    """The three fixtures pin the oracle to the shader text on 128^3 grids of tame values only.  Here it must equal an
+    independent restatement of the shader on every ragged shape of the GPU tests below and on hostile values: all signs,
+    subnormals, 65504, alphas beside 0.5, and (sprinkled) Inf and NaN.  Also the conditions that make those grids a test."""
+    for shape, direction in RAGGED + [SHIFTED]:
+        grid, want = _ragged_case(shape, direction, sprinkle)
+        src = np.ascontiguousarray(grid[:, :, 1:129]) if (shape, direction) == SHIFTED else grid
+        mine = _shader_sweep_numpy(src, direction)
+        ref = want[:, :, 1:129] if (shape, direction) == SHIFTED else want
+        _assert_same_halves(ref, mine, f"{shape} direction {direction}")
+        changed = (want != grid).any(axis=-1)
+        nan = _isnan16(want).any(axis=-1)
+        if not sprinkle:
+            assert not ((want & 0x7C00) == 0x7C00).any(), "the finite grid sweeps to finite values"
+            assert changed.mean() >= 0.5
+        else:
+            assert changed.mean() >= 0.5, (shape, direction, changed.mean())
+            assert (nan & changed).sum() <= 0.10 * changed.sum(), (shape, direction, (nan & changed).sum() / changed.sum())
+            assert (nan & changed).any() and (((want & 0x7FFF) == 0x7C00).any(axis=-1) & changed).any()
+
+
 # ------------------------------------------------------------------------------------------- GPU
 
 def _sweep_pipeline(L, fmt):
@@ -212,3 +293,66 @@ def test_gpu_sweep_boundary_errors(gpu):
         L.GPU_DestroyComputePipeline(pipe); L.GPU_DestroyPipelineLayout(layout)
     finally:
         L.GPUX_SetErrorHandler(None, None)
+
+
+def _odd_cut(n):
+    return (n // 2) | 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape,direction", RAGGED, ids=[f"{s[0]}x{s[1]}x{s[2]}-dir{d}" for s, d in RAGGED])
+def test_gpu_sweep_ragged_shapes(gpu, shape, direction):
+    """K7 through the boundary where the image is no cube: odd row pitches (8-byte loads and the unpaired contiguous
+    stores), line axes longer than the 128 swept steps, tiles of 3, 4, 8 and 9 lines.  Whole image against the oracle, so
+    voxels past step 127 and their bits are covered; then the same sweep as three sub-ranges cut at odd lines."""
+    import pbrhip
+    L = gpu
+    d, h, w = shape
+    ny, nz = {0: (h, d), 1: (d, w), 2: (w, h)}[direction]
+    cy, cz = _odd_cut(ny), _odd_cut(nz)
+    assert 0 < cy < ny and 0 < cz < nz and cy % 2 == 1 and cz % 2 == 1
+    layout, b_img, pipe = _sweep_pipeline(L, pbrhip.Format_RGBA16F)
+    tex = pbrhip.make_texture(pbrhip.Format_RGBA16F, w, h, pbrhip.TextureFlag_StorageImage, depth=d)
+    ds = L.GPU_InitDescriptorSet(None, layout)
+    L.GPU_SetStorageImageBinding(ds, b_img, tex, 0)
+    L.GPU_FinalizeDescriptorSet(ds)
+    try:
+        for sprinkle in (False, True):
+            grid, want = _ragged_case(shape, direction, sprinkle)
+            pbrhip.upload_mip(tex, 0, grid)
+            _dispatch(L, layout, pipe, ds, direction, lines=(0, ny, 0, nz))
+            whole = pbrhip.read_mip(tex, 0).view(np.uint16).reshape(grid.shape)
+            _assert_same_halves(whole, want, f"one dispatch, sprinkle={sprinkle}")
+            pbrhip.upload_mip(tex, 0, grid)
+            for lines in ((0, ny, 0, cz), (0, cy, cz, nz), (cy, ny, cz, nz)):
+                _dispatch(L, layout, pipe, ds, direction, lines=lines)
+            parts = pbrhip.read_mip(tex, 0).view(np.uint16).reshape(grid.shape)
+            _assert_same_halves(parts, want, f"three sub-ranges, sprinkle={sprinkle}")
+            if not sprinkle:
+                assert np.array_equal(parts, whole)
+    finally:
+        L.GPU_DestroyDescriptorSet(ds)
+        L.GPU_DestroyTexture(tex)
+        L.GPU_DestroyComputePipeline(pipe); L.GPU_DestroyPipelineLayout(layout)
+
+
+@pytest.mark.gpu
+def test_gpu_sweep_from_an_8_byte_aligned_pointer(gpu):
+    """The raw entry point on an image pointer 8 bytes past the texture's base: a 4 x 8 x 130 image swept along x covers voxels
+    1..128 of every line, all inside the allocation.  Even pitch, odd start: the 8-byte loads and the unpaired contiguous stores."""
+    import pbrhip
+    L = gpu
+    (d, h, w), direction = SHIFTED
+    tex = pbrhip.make_texture(pbrhip.Format_RGBA16F, w, h, pbrhip.TextureFlag_StorageImage, depth=d)
+    try:
+        base = L.GPUX_TextureDevicePtr(tex, 0)
+        assert base % 16 == 0
+        for sprinkle in (False, True):
+            grid, want = _ragged_case((d, h, w), direction, sprinkle)
+            pbrhip.upload_mip(tex, 0, grid)
+            assert L.pbrk_lightgrid_sweep(base + 8, w, h, d, direction, 0, h, 0, d, None) == 0
+            L.GPU_WaitUntilIdle()
+            got = pbrhip.read_mip(tex, 0).view(np.uint16).reshape(grid.shape)
+            _assert_same_halves(got, want, f"shifted view, sprinkle={sprinkle}")
+    finally:
+        L.GPU_DestroyTexture(tex)

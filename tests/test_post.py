@@ -199,6 +199,300 @@ def test_gpu_post_boundary_errors(gpu):
         L.GPUX_SetErrorHandler(None, None)
 
 
+# ------------------------------------------------------------------------------------------- K8 / K9 off the reference's shapes
+
+TAA_SEED = 0x5EED00E1
+_taa_cache = {}
+
+
+def _taa_case(W, H, history_size=None, sky=False):
+    """(inputs, oracle's fp32 resolve) of one small frame, computed once and shared: read-only."""
+    from pbrhip.synth import synth_post_inputs
+    key = (W, H, history_size, sky)
+    if key not in _taa_cache:
+        lighting, depth, vel, vel_prev, history = synth_post_inputs(TAA_SEED, W, H)
+        if history_size is not None:
+            history = synth_post_inputs(TAA_SEED + 1, *history_size)[4]
+        if sky:                                                     # closest_depth stays 10000: the velocity tap goes to uv (0, 0)
+            depth[5:12, 7:20] = 20000.0
+            depth[20:30, 30:50] = np.inf
+        want = O.taa_resolve(lighting, depth, vel, vel_prev, history)
+        assert np.isfinite(want).all()
+        arrays = (lighting, depth, vel, vel_prev, history, want)
+        for a in arrays:
+            a.setflags(write=False)
+        _taa_cache[key] = arrays
+    return _taa_cache[key]
+
+
+class _PostRig:
+    """A G-buffer and post-process object of one size with the inputs of a case uploaded (frame index 0: history is taa_output_rt[1])."""
+
+    def __init__(self, L, W, H, case, backbuffer=None):
+        import pbrhip
+        self.L, self.W, self.H = L, W, H
+        lighting, depth, vel, vel_prev, history, _ = case
+        self.gb = pbrhip.PBR_GBuffer()
+        L.PBR_MakeGBuffer(C.byref(self.gb), W, H, pbrhip.Format_RGBA16F)
+        self.pp = L.PBR_MakePostProcess(C.byref(self.gb), W, H, backbuffer or pbrhip.Format_RGBA8UN)
+        assert self.pp
+        _upload(self.gb.lighting_result, lighting); _upload(self.gb.depth, depth)
+        _upload(L.PBR_PostVelocity(self.pp, 0), vel); _upload(L.PBR_PostVelocity(self.pp, 1), vel_prev)
+        self.own_history = history.shape[:2] == (H, W)
+        if self.own_history:
+            _upload(L.PBR_PostTaaOutput(self.pp, 1), history)
+        self.extra = []
+
+    def texture(self, fmt, w, h, data=None):
+        import pbrhip
+        t = pbrhip.make_texture(fmt, w, h, pbrhip.TextureFlag_RenderTarget)
+        if data is not None:
+            _upload(t, data)
+        self.extra.append(t)
+        return t
+
+    def resolve_host_layer(self, rows=None):
+        """RGBA16F through PBR_RecordTaaResolve / ...Rows."""
+        import pbrhip
+        L = self.L
+        g = L.GPU_MakeGraph()
+        if rows is None:
+            L.PBR_RecordTaaResolve(self.pp, g, 0)
+        else:
+            for (r0, r1) in rows:
+                L.PBR_RecordTaaResolveRows(self.pp, g, 0, r0, r1)
+        L.GPU_GraphSubmit(g); L.GPU_GraphWait(g); L.GPU_DestroyGraph(g)
+        return pbrhip.read_mip(L.PBR_PostTaaOutput(self.pp, 0), 0)
+
+    def resolve_raw(self, history_tex=None):
+        """RGBA32F through pbrk_taa_resolve."""
+        import pbrhip
+        L, W, H = self.L, self.W, self.H
+        out = self.texture(pbrhip.Format_RGBA32F, W, H)
+        a = pbrhip.PbrkTaaArgs(_tex2d(pbrhip, L, self.gb.lighting_result, pbrhip.PBRK_FMT_RGBA16F), _tex2d(pbrhip, L, self.gb.depth, pbrhip.PBRK_FMT_R32F),
+                               _tex2d(pbrhip, L, L.PBR_PostVelocity(self.pp, 0), pbrhip.PBRK_FMT_RG16F), _tex2d(pbrhip, L, L.PBR_PostVelocity(self.pp, 1), pbrhip.PBRK_FMT_RG16F),
+                               _tex2d(pbrhip, L, history_tex or L.PBR_PostTaaOutput(self.pp, 1), pbrhip.PBRK_FMT_RGBA16F), L.GPUX_TextureDevicePtr(out, 0),
+                               pbrhip.PBRK_FMT_RGBA32F, W, H, 0, H)
+        assert L.pbrk_taa_resolve(C.byref(a), None) == 0
+        L.GPU_WaitUntilIdle()
+        return pbrhip.read_mip(out, 0)
+
+    def resolve_boundary(self, history_tex):
+        """RGBA16F through the GPU_* boundary with a descriptor set of its own: the reference's TAA pass (render.cpp:298-336, 732-739,
+        1131-1137) with any texture bound as PREV_FRAME_RESULT."""
+        import pbrhip
+        L, W, H = self.L, self.W, self.H
+        out = self.texture(pbrhip.Format_RGBA16F, W, H)
+        dummy = self.texture(pbrhip.Format_RGBA16F, 1, 1)
+        layout = L.GPU_InitPipelineLayout()
+        tex0_b = L.GPU_TextureBinding(layout, b"TEX0")
+        sampler_b = L.GPU_SamplerBinding(layout, b"SAMPLER_LINEAR_CLAMP")
+        planes = [(L.GPU_TextureBinding(layout, name), tex) for name, tex in (
+            (b"PREV_FRAME_RESULT", history_tex), (b"GBUFFER_DEPTH", self.gb.depth), (b"GBUFFER_VELOCITY", L.PBR_PostVelocity(self.pp, 0)),
+            (b"GBUFFER_VELOCITY_PREV", L.PBR_PostVelocity(self.pp, 1)), (b"LIGHTING_RESULT", self.gb.lighting_result))]
+        L.GPU_FinalizePipelineLayout(layout)
+        views = (pbrhip.GPU_TextureView * 1)(pbrhip.GPU_TextureView(out, 0))
+        rd = pbrhip.GPU_RenderPassDesc()
+        rd.color_targets_count = 1; rd.color_targets = views; rd.width = W; rd.height = H
+        rp = L.GPU_MakeRenderPass(C.byref(rd))
+        path = b"../src/demo_pbr_renderer/shaders/taa_resolve.glsl"
+        d = pbrhip.GPU_GraphicsPipelineDesc()
+        d.layout = layout; d.render_pass = rp
+        d.vs.glsl_debug_filepath = pbrhip.GPU_String(path, len(path)); d.fs.glsl_debug_filepath = d.vs.glsl_debug_filepath
+        errs = pbrhip.GPU_GLSLErrorArray()
+        d.vs.spirv = L.GPU_SPIRVFromGLSL(None, pbrhip.ShaderStage_Vertex, layout, C.byref(d.vs), C.byref(errs))
+        d.fs.spirv = L.GPU_SPIRVFromGLSL(None, pbrhip.ShaderStage_Fragment, layout, C.byref(d.fs), C.byref(errs))
+        pipe = L.GPU_MakeGraphicsPipeline(C.byref(d))
+        assert rp and pipe and errs.length == 0
+        ds = L.GPU_InitDescriptorSet(None, layout)
+        L.GPU_SetSamplerBinding(ds, sampler_b, L.GPU_SamplerLinearClamp())
+        L.GPU_SetTextureBinding(ds, tex0_b, dummy)
+        for b, tex in planes:
+            L.GPU_SetTextureBinding(ds, b, tex)
+        L.GPU_FinalizeDescriptorSet(ds)
+        g = L.GPU_MakeGraph()
+        L.GPU_OpPrepareRenderPass(g, rp)
+        dp = L.GPU_OpPrepareDrawParams(g, pipe, ds)
+        L.GPU_OpBeginRenderPass(g)
+        L.GPU_OpBindDrawParams(g, dp)
+        L.GPU_OpDraw(g, 3, 1, 0, 0)
+        L.GPU_OpEndRenderPass(g)
+        L.GPU_GraphSubmit(g); L.GPU_GraphWait(g); L.GPU_DestroyGraph(g)
+        got = pbrhip.read_mip(out, 0)
+        L.GPU_DestroyDescriptorSet(ds); L.GPU_DestroyGraphicsPipeline(pipe); L.GPU_DestroyRenderPass(rp); L.GPU_DestroyPipelineLayout(layout)
+        return got
+
+    def close(self):
+        L = self.L
+        for t in self.extra:
+            L.GPU_DestroyTexture(t)
+        L.PBR_DestroyPostProcess(self.pp); L.PBR_DestroyGBuffer(C.byref(self.gb))
+
+
+def _assert_taa_bits(got, want32, what):
+    if got.dtype == np.float32:
+        assert np.array_equal(got.view(np.uint32), want32.view(np.uint32)), f"{what}: {(got.view(np.uint32) != want32.view(np.uint32)).sum()} fp32 words differ"
+    else:
+        want = want32.astype(np.float16)
+        assert np.array_equal(got.view(np.uint16), want.view(np.uint16)), f"{what}: {(got.view(np.uint16) != want.view(np.uint16)).sum()} halves differ"
+
+
+def _sentinel(like):
+    """An array of the shape and type of `like` whose every byte is 0xA5 (a finite value in every format used here)."""
+    return np.full(like.nbytes, 0xA5, np.uint8).view(like.dtype).reshape(like.shape)
+
+
+def _same_bytes(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [(1, 1), (2, 3), (5, 4), (61, 37), (67, 9)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_gpu_taa_small_and_ragged_frames(gpu, size):
+    """K8 on frames smaller than one 64 x 4 block or ragged against it (in 1 x 1 and 2 x 3 every clamp of the exact path is
+    active): RGBA16F through the host layer and RGBA32F through the raw entry point, bit for bit against the oracle."""
+    W, H = size
+    case = _taa_case(W, H)
+    if size == (61, 37):                                            # the history path is really taken: most pixels reproject on-screen
+        vel = case[2].astype(np.float32)
+        yy, xx = np.mgrid[0:H, 0:W]
+        tap = vel[np.clip(yy - 1, 0, H - 1), np.clip(xx - 1, 0, W - 1)]         # :230 the velocity of the closest-depth tap, (-1, -1)
+        ru = (xx + 0.5) / W - 0.5 * tap[..., 0]; rv = (yy + 0.5) / H - 0.5 * tap[..., 1]
+        assert ((ru >= 0) & (ru <= 1) & (rv >= 0) & (rv <= 1)).mean() >= 0.80
+    rig = _PostRig(gpu, W, H, case)
+    try:
+        _assert_taa_bits(rig.resolve_host_layer(), case[5], "host layer")
+        _assert_taa_bits(rig.resolve_raw(), case[5], "raw entry point")
+    finally:
+        rig.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("history_size", [(122, 74), (40, 23)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_gpu_taa_history_of_another_size(gpu, history_size):
+    """The boundary accepts a PREV_FRAME_RESULT of any size and the shader samples it by uv (taa_resolve.glsl:131-171): a 61 x 37
+    frame with a larger and a smaller history, through the raw entry point and through the GPU_* boundary.  The exact path, which
+    counts the outer Catmull-Rom taps in texels of the frame, must not be taken here (it was, until the launch checked the sizes)."""
+    import pbrhip
+    W, H = 61, 37
+    case = _taa_case(W, H, history_size=history_size)
+    rig = _PostRig(gpu, W, H, case)
+    try:
+        assert not rig.own_history
+        history_tex = rig.texture(pbrhip.Format_RGBA16F, history_size[0], history_size[1], case[4])
+        _assert_taa_bits(rig.resolve_raw(history_tex), case[5], "raw entry point")
+        _assert_taa_bits(rig.resolve_boundary(history_tex), case[5], "boundary")
+    finally:
+        rig.close()
+
+
+@pytest.mark.gpu
+def test_gpu_taa_row_bands(gpu):
+    """61 x 37: the row bands (0,1), (1,36), (36,37) drawn into a sentinel-filled target leave every other row alone and together
+    equal the full draw."""
+    L = gpu
+    W, H = 61, 37
+    case = _taa_case(W, H)
+    rig = _PostRig(L, W, H, case)
+    try:
+        full = rig.resolve_host_layer()
+        _assert_taa_bits(full, case[5], "full draw")
+        target = L.PBR_PostTaaOutput(rig.pp, 0)
+        sentinel = _sentinel(full)
+        bands = [(0, 1), (1, 36), (36, 37)]
+        for (r0, r1) in bands:
+            _upload(target, sentinel)
+            got = rig.resolve_host_layer(rows=[(r0, r1)])
+            assert _same_bytes(got[r0:r1], full[r0:r1]), (r0, r1)
+            assert _same_bytes(got[:r0], sentinel[:r0]) and _same_bytes(got[r1:], sentinel[r1:]), (r0, r1)
+        _upload(target, sentinel)
+        assert _same_bytes(rig.resolve_host_layer(rows=bands), full)
+    finally:
+        rig.close()
+
+
+@pytest.mark.gpu
+def test_gpu_taa_sky_depth_patches(gpu):
+    """61 x 37 with a patch of depth 20000 and one of +inf: no tap there is closer than 10000 and the shader reads the velocity at
+    uv (0, 0) through the sampler (:205-230).  The sampler's zero-weight neighbours make the depth tap NaN for the pixels left of and
+    above the +inf patch too (p + 0 * (q - p)): they take the same branch."""
+    L = gpu
+    W, H = 61, 37
+    case = _taa_case(W, H, sky=True)
+    assert (case[1] >= 10000).sum() == 7 * 13 + 10 * 20
+    rig = _PostRig(L, W, H, case)
+    try:
+        _assert_taa_bits(rig.resolve_host_layer(), case[5], "sky patches, host layer")
+        _assert_taa_bits(rig.resolve_raw(), case[5], "sky patches, raw entry point")
+    finally:
+        rig.close()
+
+
+def _final_formats(pbrhip):
+    return [(pbrhip.Format_RGBA32F, pbrhip.PBRK_FMT_RGBA32F), (pbrhip.Format_RGBA16F, pbrhip.PBRK_FMT_RGBA16F),
+            (pbrhip.Format_RGBA8UN, pbrhip.PBRK_FMT_RGBA8UN), (pbrhip.Format_BGRA8UN, pbrhip.PBRK_FMT_BGRA8UN)]
+
+
+def _final_raw(L, pbrhip, src, target, kfmt, W, H, y0, y1):
+    fa = pbrhip.PbrkFinalArgs(_tex2d(pbrhip, L, src, pbrhip.PBRK_FMT_RGBA16F), L.GPUX_TextureDevicePtr(target, 0), kfmt, W, H, y0, y1)
+    assert L.pbrk_final_post_process(C.byref(fa), None) == 0
+    L.GPU_WaitUntilIdle()
+    return pbrhip.read_mip(target, 0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [(64, 9), (1028, 3), (61, 37), (66, 5)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_gpu_final_post_process_both_kernels_all_formats(gpu, size):
+    """K9 at one size of source and target: widths that are a multiple of 4 take the streaming kernel (64 x 9: 144 quads, less than a
+    block; 1028 x 3: 771 quads, three blocks and a ragged fourth), the others the general one.  All four target formats; row bands
+    into a sentinel-filled target for 1028 x 3 and 61 x 37."""
+    import pbrhip
+    from pbrhip.synth import synth_post_inputs
+    L = gpu
+    W, H = size
+    frame = synth_post_inputs(0x5EED00E2, W, H)[0]
+    want = O.final_post_process(frame)
+    src = pbrhip.make_texture(pbrhip.Format_RGBA16F, W, H, pbrhip.TextureFlag_RenderTarget)
+    _upload(src, frame)
+    targets = []
+    try:
+        outs = {}
+        for fmt, kfmt in _final_formats(pbrhip):
+            target = pbrhip.make_texture(fmt, W, H, pbrhip.TextureFlag_RenderTarget)
+            targets.append(target)
+            full = outs[kfmt] = _final_raw(L, pbrhip, src, target, kfmt, W, H, 0, H)
+            if size in ((1028, 3), (61, 37)):
+                sentinel = _sentinel(full)
+                bands = [(0, 1), (1, H - 1), (H - 1, H)]
+                for (r0, r1) in bands:
+                    _upload(target, sentinel)
+                    got = _final_raw(L, pbrhip, src, target, kfmt, W, H, r0, r1)
+                    assert _same_bytes(got[r0:r1], full[r0:r1]), (kfmt, r0, r1)
+                    assert _same_bytes(got[:r0], sentinel[:r0]) and _same_bytes(got[r1:], sentinel[r1:]), (kfmt, r0, r1)
+                _upload(target, sentinel)
+                for (r0, r1) in bands:
+                    got = _final_raw(L, pbrhip, src, target, kfmt, W, H, r0, r1)
+                assert _same_bytes(got, full), kfmt
+        got = outs[pbrhip.PBRK_FMT_RGBA32F]
+        rel = np.abs(got - want) / np.maximum(want, 1e-3)
+        print("RGBA32F max rel", rel.max())
+        assert rel.max() < 1e-5, rel.max()
+        got = outs[pbrhip.PBRK_FMT_RGBA16F].view(np.uint16).astype(np.int32)
+        ref = want.astype(np.float16).view(np.uint16).astype(np.int32)          # values in [0, 1]: adjacent bit patterns are adjacent halves
+        print("RGBA16F max ulp", np.abs(got - ref).max())
+        assert np.abs(got - ref).max() <= 1 and np.all(got[..., 3] == 0x3C00)
+        rgba, bgra = outs[pbrhip.PBRK_FMT_RGBA8UN], outs[pbrhip.PBRK_FMT_BGRA8UN]
+        diff = np.abs(rgba.astype(np.int32) - O.unorm8(want).astype(np.int32))
+        print("RGBA8UN max code", diff.max(), "exact", (diff == 0).mean())
+        assert diff.max() <= 1 and (diff == 0).mean() > 0.995, (diff.max(), (diff == 0).mean())
+        assert np.all(rgba[..., 3] == 255)
+        assert np.array_equal(bgra, rgba[..., [2, 1, 0, 3]])
+    finally:
+        for t in targets:
+            L.GPU_DestroyTexture(t)
+        L.GPU_DestroyTexture(src)
+
+
 # ------------------------------------------------------------------------------------------- bloom chain
 
 @pytest.fixture(scope="module")

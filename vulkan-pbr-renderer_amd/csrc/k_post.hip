@@ -10,7 +10,7 @@
 // Arithmetic follows the shader statement by statement (no contraction, correctly rounded divide / sqrt), so K8 is
 // bit-identical to the oracle and, through Oracle-A, to the shader text executed on the CPU.
 // Both kernels are HBM-shaped by bytes (K8: 36 B per pixel = 8 lighting + 4 depth + 4 + 4 velocity + 8 history + 8
-// written; K9: 8 B read + 4 B written); K8 issues 31 vector loads per pixel and is bound by the L1 path.
+// written; K9: 8 B read + 4 B written); K8 issues 34 vector loads per pixel and is bound by the L1 path.
 #include "pbr_device.h"
 #include "pbr_kernels.h"
 
@@ -123,7 +123,7 @@ __device__ __forceinline__ float2 fetch_rg16f(__amdgpu_buffer_rsrc_t rs, int w, 
     return make_float2(h2f(v & 0xffff), h2f(v >> 16));
 }
 
-// kCentreExact (frames up to 8192^2): every tap the shader aims at a texel centre -- the 3x3 neighbourhood, depth, the
+// kCentreExact (frames up to 8192^2 whose history has the frame's size): every tap the shader aims at a texel centre -- the 3x3 neighbourhood, depth, the
 // velocity tap and the outer Catmull-Rom taps -- is one texel fetch, and the outer taps need neither their division by the
 // texture size nor the bilinear split (their texel is floor(sp - 0.5) - 1 / + 2).  Otherwise every tap goes through the sampler.
 struct TaaParams { PbrkTaaArgs a; float psx, psy; };       // 1 / width, 1 / height: the shader's divisions (:190), done once on the host
@@ -143,8 +143,15 @@ __global__ __launch_bounds__(256) void k_taa_resolve(TaaParams P) {
 
     float tot[3] = {0, 0, 0}, wsum = 0.0f, m1[3] = {0, 0, 0}, m2[3] = {0, 0, 0};
     float closest_depth = 10000.0f, cdu = 0.0f, cdv = 0.0f;
-    const float depth = kCentreExact ? ((const float*)A.gbuffer_depth.data)[(size_t)py * A.gbuffer_depth.width + px]
-                                     : sample_r32f(A.gbuffer_depth, uvx, uvy);  // :221 (same tap nine times)
+    float depth;                                                                // :221 (same tap nine times)
+    if (kCentreExact) {
+        // depth decides a branch (:222), so its tap keeps all of the sampler's arithmetic: the right and lower neighbours enter with a
+        // zero weight, p + 0 * (q - p), which is p unless one of them is not finite; then it is NaN and no tap is the closest
+        const float* D = (const float*)A.gbuffer_depth.data;
+        const size_t r0 = (size_t)py * W, r1 = (size_t)min(py + 1, H - 1) * W;
+        const int x1 = min(px + 1, W - 1);
+        depth = lerpx(lerpx(D[r0 + px], D[r0 + x1], 0.0f), lerpx(D[r1 + px], D[r1 + x1], 0.0f), 0.0f);
+    } else depth = sample_r32f(A.gbuffer_depth, uvx, uvy);
 #pragma unroll
     for (int x = -1; x <= 1; ++x)                                               // :205-227
 #pragma unroll
@@ -701,7 +708,8 @@ extern "C" int pbrk_taa_resolve(const PbrkTaaArgs* a, void* stream) {
     for (int k = 0; k < 4; ++k) if (same[k]->width != a->width || same[k]->height != a->height) return PBRK_E_ARG;
     if (a->out == a->prev_frame_result.data || a->out == a->lighting_result.data) return PBRK_E_ARG;
     if ((long long)a->width * a->height > (1ll << 27) || (long long)a->prev_frame_result.width * a->prev_frame_result.height > (1ll << 27)) return PBRK_E_ARG;   // 32-bit byte offsets
-    const bool centre = a->width <= 8192 && a->height <= 8192;
+    // the exact path counts its outer history taps in texels of the frame: only a history of the frame's size has them at its own centres
+    const bool centre = a->width <= 8192 && a->height <= 8192 && a->prev_frame_result.width == a->width && a->prev_frame_result.height == a->height;
     const bool half = a->out_format == PBRK_FMT_RGBA16F;
     dim3 grid((a->width + 63) / 64, (a->y1 - a->y0 + 3) / 4), block(256);
     hipStream_t st = (hipStream_t)stream;

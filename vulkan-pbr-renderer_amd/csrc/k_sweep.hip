@@ -59,6 +59,13 @@ __device__ __forceinline__ void store_stream2(uint2* p, uint2 v0, uint2 v1) {   
     __builtin_nontemporal_store(q, (u32x4n*)p);
 }
 
+// one voxel as one 8-B load: plain loads of adjacent voxels are fused into 16-B loads whatever their alignment, a relaxed
+// single-thread atomic load is the same instruction and is left alone
+__device__ __forceinline__ uint2 load_voxel(const uint2* p) {
+    const unsigned long long q = __hip_atomic_load((const unsigned long long*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SINGLETHREAD);
+    return make_uint2((unsigned)q, (unsigned)(q >> 32));
+}
+
 __device__ __forceinline__ float half_bits_to_float(unsigned h) { return __half2float(__ushort_as_half((unsigned short)h)); }
 
 // Streamed form: the line is cut into 8 chunks of 16 steps.  All loads are issued up front, in chunk order; chunk c is written to
@@ -66,7 +73,9 @@ __device__ __forceinline__ float half_bits_to_float(unsigned h) { return __half2
 // flight.  The backward sweep releases each finished chunk to wave 3 (which has no channel to sweep), and wave 3 streams it
 // back to HBM while waves 0-2 continue down the line.  The memory phases (2.4 us + 4 us when run back to back) hide under the
 // 7.5 us dependent chain.
-template <bool kContig>      // kContig: lines run along x (each line is contiguous); else adjacent lines are adjacent voxels
+template <bool kContig, bool kVecLoads>   // kContig: lines run along x (each line is contiguous); else adjacent lines are adjacent voxels
+                                          // kVecLoads (kContig only): every line starts on a 16-B boundary, 16-B loads (a template parameter and not
+                                          // a branch: with both forms in one kernel the waits no longer release the loads chunk by chunk)
 __global__ __launch_bounds__(256) void k_lightgrid_sweep(uint2* __restrict__ img, SweepGeom g) {
     extern __shared__ uint2 tile[];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -77,7 +86,8 @@ __global__ __launch_bounds__(256) void k_lightgrid_sweep(uint2* __restrict__ img
     constexpr int kChunk = 16, kChunks = kLen / kChunk;
 
     // ---- loads, chunk-major: 4 voxels per thread and chunk.
-    //      lines along x (contiguous): thread -> (line t>>2, 4 consecutive voxels): 2 x 16 B, 128 B per line and chunk;
+    //      lines along x (contiguous): thread -> (line t>>2, 4 consecutive voxels): 2 x 16 B, 128 B per line and chunk, where every
+    //      line starts on a 16-B boundary (kVecLoads = g.pair_stores: pointer, base and pitch even in voxels), else the same voxels as 4 x 8 B;
     //      lines along y / z: thread -> (line = lane, steps wave + 4j): 4 x 8 B, 512 B rows across the lanes.
     //      Loads are unconditional (lines beyond a partial tile re-read its last line; only stores are predicated), so that
     //      nothing but the data dependence orders them: the compiler's vmcnt waits then release chunk after chunk.
@@ -85,10 +95,13 @@ __global__ __launch_bounds__(256) void k_lightgrid_sweep(uint2* __restrict__ img
     const int ll = min(kContig ? (t >> 2) : lane, nvalid - 1);
 #pragma unroll
     for (int c = 0; c < kChunks; ++c) {
-        if (kContig) {
+        if (kContig && kVecLoads) {
             const uint4* p = (const uint4*)(base + (long long)ll * g.fstride + (c * kChunk + (t & 3) * 4));
             uint4 a = p[0], b = p[1];
             v[c][0] = make_uint2(a.x, a.y); v[c][1] = make_uint2(a.z, a.w); v[c][2] = make_uint2(b.x, b.y); v[c][3] = make_uint2(b.z, b.w);
+        } else if (kContig) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[c][j] = load_voxel(base + (long long)ll * g.fstride + (c * kChunk + (t & 3) * 4 + j));
         } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) v[c][j] = base[(long long)ll + (long long)(c * kChunk + wave + 4 * j) * g.xstride];
@@ -106,6 +119,10 @@ __global__ __launch_bounds__(256) void k_lightgrid_sweep(uint2* __restrict__ img
     // (no result here is near the fp32 subnormal range unless it is ~1e-30 below anything an fp16 store can see),
     // so m' = fl(0.5*v + 0.5*m) = fmaf(0.5, m, 0.5*v) and v' = t - 0.5*t = m' bit for bit: the dependent chain is one
     // FMA and one select per step, everything else is off the chain.  wv[x] holds 0.5 * (forward result of voxel x).
+    // The one exception is t = +-Inf (an infinite voxel or moving light): there v' = Inf - Inf is NaN while m' stays Inf.  The
+    // forward sweep lets that pass: an infinite wv[x] makes the backward h of the voxel infinite or NaN, and so (through m) every h
+    // down to the next occupied voxel -- exactly the voxels whose value is NaN in the shader.  The backward sweep turns a non-finite
+    // h into NaN off the chain: h + 0 * h (the zero has the sign of h, so -0 survives).
     float wv[kLen];
     float m = sky;                                                            // :36
 
@@ -167,7 +184,7 @@ __global__ __launch_bounds__(256) void k_lightgrid_sweep(uint2* __restrict__ img
                     float ov = half_bits_to_float(cv[j]), a = half_bits_to_float(ab);
                     float h = fmaf(move_ratio, m, wv[x]);                     // = 0.5 * (forward value + m) = the voxel's new value
                     m = a > 0.5f ? ov : h;
-                    float vv = h;
+                    float vv = fmaf(0.0f, h, h);                              // h, NaN for an infinite h
                     if (x == 0) vv = vv + m;                                  // :67 (m is final here)
                     float mixed = ov * keep + vv * 0.35f;
                     unsigned short nb = __half_as_ushort(__float2half_rn(mixed));
@@ -264,12 +281,15 @@ extern "C" int pbrk_lightgrid_sweep(void* image_rgba16f, int w, int h, int d, in
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess) return PBRK_E_LAUNCH;
     if (attr_device != device) {
-        if (hipFuncSetAttribute((const void*)k_lightgrid_sweep<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes) != hipSuccess) return PBRK_E_LAUNCH;
-        if (hipFuncSetAttribute((const void*)k_lightgrid_sweep<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes) != hipSuccess) return PBRK_E_LAUNCH;
+        const void* kernels[3] = {(const void*)k_lightgrid_sweep<true, true>, (const void*)k_lightgrid_sweep<true, false>, (const void*)k_lightgrid_sweep<false, false>};
+        for (const void* k : kernels)
+            if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes) != hipSuccess) return PBRK_E_LAUNCH;
         attr_device = device;
     }
-    if (g.contiguous_lines) hipLaunchKernelGGL(k_lightgrid_sweep<true>, dim3((g.nf + kTile - 1) / kTile, ns), dim3(256), kLdsBytes, (hipStream_t)stream, (uint2*)image_rgba16f, g);
-    else hipLaunchKernelGGL(k_lightgrid_sweep<false>, dim3((g.nf + kTile - 1) / kTile, ns), dim3(256), kLdsBytes, (hipStream_t)stream,
-                       (uint2*)image_rgba16f, g);
+    const dim3 grid((g.nf + kTile - 1) / kTile, ns);
+    // 16-B loads need what 16-B stores of contiguous lines need: every line of the range starts on a 16-B boundary
+    if (g.contiguous_lines && g.pair_stores) hipLaunchKernelGGL((k_lightgrid_sweep<true, true>), grid, dim3(256), kLdsBytes, (hipStream_t)stream, (uint2*)image_rgba16f, g);
+    else if (g.contiguous_lines) hipLaunchKernelGGL((k_lightgrid_sweep<true, false>), grid, dim3(256), kLdsBytes, (hipStream_t)stream, (uint2*)image_rgba16f, g);
+    else hipLaunchKernelGGL((k_lightgrid_sweep<false, false>), grid, dim3(256), kLdsBytes, (hipStream_t)stream, (uint2*)image_rgba16f, g);
     return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
 }

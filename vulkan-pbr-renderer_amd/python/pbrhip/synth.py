@@ -421,6 +421,23 @@ def synth_lightgrid(size=128, seed=0x5EED00B7, lit=True):
     return g
 
 
+def synth_lightgrid_hostile(shape, seed, sprinkle=False):
+    """A light grid of raw bit patterns, uint16 [d][h][w][4], for the sweep's edge cases.  Every half is a uniformly random
+    16-bit pattern, with exponent-31 patterns made finite by clearing bit 10: all signs, subnormals, values up to 65504 and every
+    relation of alpha to 0.5; 1 % of the alphas are the three halves around 0.5 (0x37FF, 0x3800, 0x3801).  `sprinkle` then sets
+    each half with probability 1 / 512 to +Inf, -Inf or a NaN (0x7E00, 0xFE01)."""
+    rng = np.random.default_rng(seed)
+    d, h, w = shape
+    g = rng.integers(0, 1 << 16, (d, h, w, 4), dtype=np.uint16)
+    g[(g & 0x7C00) == 0x7C00] &= np.uint16(0xFBFF)
+    beside = rng.random((d, h, w)) < 0.01
+    g[beside, 3] = rng.choice(np.array([0x37FF, 0x3800, 0x3801], np.uint16), int(beside.sum()))
+    if sprinkle:
+        hit = rng.random(g.shape) < 1.0 / 512.0
+        g[hit] = rng.choice(np.array([0x7C00, 0xFC00, 0x7E00, 0xFE01], np.uint16), int(hit.sum()))
+    return g
+
+
 def synth_post_inputs(seed, W, H):
     """Seeded inputs of the post-process tail: an HDR frame with a few very bright texels, a depth plane, smooth
     sub-pixel velocities with a patch of large motion (history rejection) and a strip that reprojects off-screen."""
