@@ -648,6 +648,105 @@ def test_gpu_bloom_instantiations_agree_on_small_and_ragged_frames(gpu, size):
     L.PBR_DestroyPostProcess(pp); L.PBR_DestroyGBuffer(C.byref(gb))
 
 
+BLOOM_SEED = 0x5EED00E3
+FORCE_WIDE, FORCE_ONE_PIXEL, FORCE_SMALL = (0, 0), (1 << 40, 0), (1 << 40, 1 << 40)     # pbrk_bloom_set_thresholds(quad_min, small_max)
+# kind: (source size, target size, upsample, dst_mip_levels, [(thresholds, bands that partition the target, further bands)])
+_BLOOM_BAND_CASES = {
+    # exact 2 : 1 down: k_bloom_down_pair | k_bloom_pass<false>; level 1 has the firefly clamp active
+    "down_exact": ((132, 76), (66, 38), False, (1, 2), [(FORCE_WIDE, [(0, 1), (1, 37), (37, 38)], []), (FORCE_ONE_PIXEL, [(0, 1), (1, 37), (37, 38)], [])]),
+    # exact 1 : 2 up: k_bloom_quad on even bands, the one-pixel kernel on the odd band (1, 37) | k_bloom_pass<true> on all of them
+    "up_exact": ((33, 19), (66, 38), True, (0, 1), [(FORCE_WIDE, [(0, 2), (2, 36), (36, 38)], [(1, 37)]), (FORCE_ONE_PIXEL, [(0, 2), (2, 36), (36, 38)], [(1, 37)])]),
+    # not 2 : 1, every tap through the sampler: k_bloom_pass | k_bloom_small
+    "down_general": ((67, 33), (33, 16), False, (1, 2), [(FORCE_ONE_PIXEL, [(0, 1), (1, 15), (15, 16)], []), (FORCE_SMALL, [(0, 1), (1, 15), (15, 16)], [])]),
+    "up_general": ((33, 16), (67, 33), True, (0, 1), [(FORCE_ONE_PIXEL, [(0, 1), (1, 32), (32, 33)], []), (FORCE_SMALL, [(0, 1), (1, 32), (32, 33)], [])]),
+}
+_bloom_band_cache = {}
+
+
+def _bloom_band_case(kind, level):
+    """(source, operand, reference) of one pass, computed once and shared: read-only.  Upsamples are additive, as in the chain:
+    fp16(frag.rgb + operand.rgb), alpha from frag (O.bloom_chain)."""
+    from pbrhip.synth import synth_post_inputs
+    key = (kind, level)
+    if key not in _bloom_band_cache:
+        (sw, sh), (dw, dh), up, _, _ = _BLOOM_BAND_CASES[kind]
+        src = synth_post_inputs(BLOOM_SEED, sw, sh)[0]
+        frag = O.bloom_pass(src, dw, dh, level, up)
+        if up:
+            operand = synth_post_inputs(BLOOM_SEED + 1, dw, dh)[0]
+            want = np.concatenate([frag[..., :3] + operand[..., :3].astype(np.float32), frag[..., 3:]], axis=-1).astype(np.float16)
+        else:
+            operand, want = None, frag.astype(np.float16)
+        assert np.isfinite(want.astype(np.float32)).all()
+        if not up and level == 1:
+            assert (frag[..., :3] == 1.0).any(), "the firefly clamp is active"
+        for a in (src, operand, want):
+            if a is not None:
+                a.setflags(write=False)
+        _bloom_band_cache[key] = (src, operand, want)
+    return _bloom_band_cache[key]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", list(_BLOOM_BAND_CASES))
+def test_gpu_bloom_pass_row_bands(gpu, kind):
+    """pbrk_bloom_pass driven directly, with each kernel forced by the thresholds, on the smallest shapes that are ragged against a
+    64-lane row and a 4-row block, full and in row bands y0 / y1 (the host layer only ever records whole levels).  The full draw has
+    the oracle's bits; a band has the full draw's rows and leaves every other row alone; the bands one after another give the full
+    draw.  Additive passes run with the target as its own operand (pre-filled with data) and with a separate blend_src (target
+    sentinel-filled)."""
+    import pbrhip
+    L = gpu
+    (sw, sh), (dw, dh), up, levels, selections = _BLOOM_BAND_CASES[kind]
+    src_tex = pbrhip.make_texture(pbrhip.Format_RGBA16F, sw, sh, pbrhip.TextureFlag_RenderTarget)
+    dst_tex = pbrhip.make_texture(pbrhip.Format_RGBA16F, dw, dh, pbrhip.TextureFlag_RenderTarget)
+    operand_tex = pbrhip.make_texture(pbrhip.Format_RGBA16F, dw, dh, pbrhip.TextureFlag_RenderTarget)
+    src2d = _tex2d(pbrhip, L, src_tex, pbrhip.PBRK_FMT_RGBA16F)
+    dst_ptr, operand_ptr = L.GPUX_TextureDevicePtr(dst_tex, 0), L.GPUX_TextureDevicePtr(operand_tex, 0)
+
+    def draw(level, blend_src, y0, y1):
+        a = pbrhip.PbrkBloomArgs(src2d, dst_ptr, dw, dh, level, int(up), int(up), y0, y1, blend_src)
+        assert L.pbrk_bloom_pass(C.byref(a), None) == 0, (kind, level, y0, y1)
+        L.GPU_WaitUntilIdle()
+        return pbrhip.read_mip(dst_tex, 0)
+
+    try:
+        for level in levels:
+            src, operand, want = _bloom_band_case(kind, level)
+            _upload(src_tex, src)
+            if up:
+                _upload(operand_tex, operand)
+            # what the target holds before a draw: its own operand (blend_src = NULL), or a sentinel
+            modes = [(None, operand), (operand_ptr, _sentinel(want))] if up else [(None, _sentinel(want))]
+            for thresholds, partition, further in selections:
+                L.pbrk_bloom_set_thresholds(*thresholds)
+                for blend_src, before in modes:
+                    what = (kind, level, thresholds, "blend_src" if blend_src else "in place")
+                    _upload(dst_tex, before)
+                    full = draw(level, blend_src, 0, dh)
+                    assert _same_bytes(full, want), (what, int((full.view(np.uint16) != want.view(np.uint16)).sum()))
+                    for (r0, r1) in partition + further:
+                        _upload(dst_tex, before)
+                        got = draw(level, blend_src, r0, r1)
+                        assert _same_bytes(got[r0:r1], full[r0:r1]), (what, r0, r1)
+                        assert _same_bytes(got[:r0], before[:r0]) and _same_bytes(got[r1:], before[r1:]), (what, r0, r1)
+                    _upload(dst_tex, before)
+                    for (r0, r1) in partition:
+                        got = draw(level, blend_src, r0, r1)
+                    assert _same_bytes(got, full), what
+        # the argument errors of the entry point (no launch)
+        for y0, y1 in ((5, 5), (6, 5), (0, dh + 1)):
+            a = pbrhip.PbrkBloomArgs(src2d, dst_ptr, dw, dh, levels[0], int(up), 0, y0, y1, None)
+            assert L.pbrk_bloom_pass(C.byref(a), None) == -1, (y0, y1)
+        a = pbrhip.PbrkBloomArgs(src2d, src2d.data, dw, dh, levels[0], int(up), 0, 0, dh, None)
+        assert L.pbrk_bloom_pass(C.byref(a), None) == -1, "dst == src.data"
+    finally:
+        L.pbrk_bloom_set_thresholds(-1, -1)
+        L.GPU_WaitUntilIdle()
+        for t in (src_tex, dst_tex, operand_tex):
+            L.GPU_DestroyTexture(t)
+
+
 @pytest.mark.gpu
 def test_gpu_graph_folds_keep_a_blit_and_a_clear_that_something_else_can_see(gpu):
     """The submit-time folds (gpu_hip.cpp fold_blits) apply to the bloom chain's own pattern only.  Here the same clear + 1:1 blit are

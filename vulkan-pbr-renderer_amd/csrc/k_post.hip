@@ -1,6 +1,8 @@
-// k_post.hip -- K8 / K9: the post-process tail that consumes the shade pass.
-//   K8 k_taa_resolve        shaders/taa_resolve.glsl:180-287   (full-screen draw, render.cpp:1131-1137)
-//   K9 k_final_post_process shaders/final_post_process.glsl:2-10,31-34 (render.cpp:1181-1187)
+// k_post.hip -- K8 / K9 and K10 / K11: the post-process tail that consumes the shade pass.
+//   K8  k_taa_resolve        shaders/taa_resolve.glsl:180-287   (full-screen draw, render.cpp:1131-1137)
+//   K9  k_final_post_process shaders/final_post_process.glsl:2-10,31-34 (render.cpp:1181-1187)
+//   K10 / K11 k_bloom_pass, k_bloom_small, k_bloom_down_pair, k_bloom_quad   shaders/bloom_downsample.glsl:38-98, bloom_upsample.glsl:23-58
+//                            (render.cpp:1139-1176): the instantiations of one pass, chosen by pbrk_bloom_pass
 //
 // Sampler (SAMPLER_LINEAR_CLAMP on 2-D textures): texel coordinates are snapped to 1/256 texel before the bilinear
 // split -- Vulkan's subTexelPrecisionBits = 8, what the reference's target GPUs do -- then weights and lerps are exact
@@ -11,6 +13,10 @@
 // bit-identical to the oracle and, through Oracle-A, to the shader text executed on the CPU.
 // Both kernels are HBM-shaped by bytes (K8: 36 B per pixel = 8 lighting + 4 depth + 4 + 4 velocity + 8 history + 8
 // written; K9: 8 B read + 4 B written); K8 issues 34 vector loads per pixel and is bound by the L1 path.
+// Every step the kernels share is written once: the sampler's blend (bilerp, over a Tap from split_tap), the RGBA16F unpack
+// (unpack_rgba16f; unpack_row for whole rows), the bloom shaders' weighted sums (down_fold / up_fold under down_sum / up_sum), the
+// whole-row window loads of the exact 2 : 1 passes (bloom_row) and the one-pixel additive blend and store (blend_store).  What stays
+// apart does so for a measured reason, given where it stands (profiles/post_one_copy.md has the numbers).
 #include "pbr_device.h"
 #include "pbr_kernels.h"
 
@@ -32,17 +38,41 @@ __device__ __forceinline__ float lerpx(float p, float q, float t) { return p + t
 __device__ __forceinline__ float lerpc(float p, float q, float t) { return (t == 0.5f || t == 0.25f) ? fmaf(t, q - p, p) : p + t * (q - p); }
 
 struct Rgba { float x, y, z, w; };
+__device__ __forceinline__ float2 lerpx(float2 p, float2 q, float t) { return make_float2(lerpx(p.x, q.x, t), lerpx(p.y, q.y, t)); }
+__device__ __forceinline__ Rgba lerpx(const Rgba& p, const Rgba& q, float t) { return Rgba{lerpx(p.x, q.x, t), lerpx(p.y, q.y, t), lerpx(p.z, q.z, t), lerpx(p.w, q.w, t)}; }
+// the sampler's blend of a tap's four texels (scalars or texels): x first, then y
+template <class T>
+__device__ __forceinline__ T bilerp(const T& t00, const T& t10, const T& t01, const T& t11, float a, float b) { return lerpx(lerpx(t00, t10, a), lerpx(t01, t11, a), b); }
 
-__device__ __forceinline__ Rgba texel_rgba16f(const PbrkTex2D& t, int i, int j) {
-    uint2 v = ((const uint2*)t.data)[(size_t)j * t.width + i];
-    return Rgba{h2f(v.x & 0xffff), h2f(v.x >> 16), h2f(v.y & 0xffff), h2f(v.y >> 16)};
+__device__ __forceinline__ Rgba unpack_rgba16f(uint2 v) { return Rgba{h2f(v.x & 0xffff), h2f(v.x >> 16), h2f(v.y & 0xffff), h2f(v.y >> 16)}; }
+__device__ __forceinline__ float2 unpack_rg16f(unsigned v) { return make_float2(h2f(v & 0xffff), h2f(v >> 16)); }
+__device__ __forceinline__ void rgb_of(const Rgba& v, float* o) { o[0] = v.x; o[1] = v.y; o[2] = v.z; }
+// N consecutive texels (rgb) from the 2 N words of a row (alpha is never converted: through unpack_rgba16f the pair kernels schedule differently)
+template <int N>
+__device__ __forceinline__ void unpack_row(const unsigned* w, float (*t)[3]) {
+#pragma unroll
+    for (int c = 0; c < N; ++c) { t[c][0] = h2f(w[2 * c] & 0xffff); t[c][1] = h2f(w[2 * c] >> 16); t[c][2] = h2f(w[2 * c + 1] & 0xffff); }
 }
-__device__ __forceinline__ float2 texel_rg16f(const PbrkTex2D& t, int i, int j) {
-    unsigned v = ((const unsigned*)t.data)[(size_t)j * t.width + i];
-    return make_float2(h2f(v & 0xffff), h2f(v >> 16));
+
+// pointer-addressed texel fetches
+__device__ __forceinline__ Rgba texel_rgba16f(const PbrkTex2D& t, int i, int j) { return unpack_rgba16f(((const uint2*)t.data)[(size_t)j * t.width + i]); }
+__device__ __forceinline__ float2 texel_rg16f(const PbrkTex2D& t, int i, int j) { return unpack_rg16f(((const unsigned*)t.data)[(size_t)j * t.width + i]); }
+// buffer-addressed texel fetches: one 32-bit offset per load instead of a 64-bit address (textures are < 2 GiB, checked on the host)
+typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t tex_rsrc(const PbrkTex2D& t, int texel_bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)t.data, 0, t.width * t.height * texel_bytes, 0x00020000);
+}
+__device__ __forceinline__ Rgba fetch_rgba16f(__amdgpu_buffer_rsrc_t rs, int w, int i, int j) {
+    u32x2v v = __builtin_amdgcn_raw_buffer_load_b64(rs, (j * w + i) * 8, 0, 0);
+    return unpack_rgba16f(make_uint2(v.x, v.y));
+}
+__device__ __forceinline__ float2 fetch_rg16f(__amdgpu_buffer_rsrc_t rs, int w, int i, int j) {
+    return unpack_rg16f(__builtin_amdgcn_raw_buffer_load_b32(rs, (j * w + i) * 4, 0, 0));
 }
 
 // snapped bilinear split of one axis: returns the two clamped texel indices and the weight of the second
+// (snap_split in k_shade_internal.h is the same arithmetic with another clamp instruction, for K5 / K16)
 __device__ __forceinline__ void split_axis(float coord01, int extent, int& i0, int& i1, float& a) {
     float f = coord01 * (float)extent - 0.5f;
     f = floorf(f * 256.0f + 0.5f) * (1.0f / 256.0f);
@@ -51,26 +81,25 @@ __device__ __forceinline__ void split_axis(float coord01, int extent, int& i0, i
     int i = (int)fminf(fmaxf(fl, -1.0f), (float)extent);       // clamp before the conversion: no saturation / overflow for wild coordinates
     i0 = clampi(i, 0, extent - 1); i1 = clampi(i + 1, 0, extent - 1);
 }
+// one bilinear tap: the texel pairs of both axes and the weights of the second of each
+struct Tap { int i0, i1, j0, j1; float a, b; };
+__device__ __forceinline__ Tap split_tap(float u, float v, int width, int height) {
+    Tap p;
+    split_axis(u, width, p.i0, p.i1, p.a); split_axis(v, height, p.j0, p.j1, p.b);
+    return p;
+}
+// the sampler: fetch four, bilerp; texel(i, j) is any of the fetches above
+template <class Texel>
+__device__ __forceinline__ auto sample(const Tap& p, Texel texel) { return bilerp(texel(p.i0, p.j0), texel(p.i1, p.j0), texel(p.i0, p.j1), texel(p.i1, p.j1), p.a, p.b); }
 
 __device__ __forceinline__ Rgba sample_rgba16f(const PbrkTex2D& t, float u, float v) {
-    int i0, i1, j0, j1; float a, b;
-    split_axis(u, t.width, i0, i1, a); split_axis(v, t.height, j0, j1, b);
-    Rgba t00 = texel_rgba16f(t, i0, j0), t10 = texel_rgba16f(t, i1, j0), t01 = texel_rgba16f(t, i0, j1), t11 = texel_rgba16f(t, i1, j1);
-    return Rgba{lerpx(lerpx(t00.x, t10.x, a), lerpx(t01.x, t11.x, a), b), lerpx(lerpx(t00.y, t10.y, a), lerpx(t01.y, t11.y, a), b),
-                lerpx(lerpx(t00.z, t10.z, a), lerpx(t01.z, t11.z, a), b), lerpx(lerpx(t00.w, t10.w, a), lerpx(t01.w, t11.w, a), b)};
+    return sample(split_tap(u, v, t.width, t.height), [&](int i, int j) { return texel_rgba16f(t, i, j); });
 }
 __device__ __forceinline__ float2 sample_rg16f(const PbrkTex2D& t, float u, float v) {
-    int i0, i1, j0, j1; float a, b;
-    split_axis(u, t.width, i0, i1, a); split_axis(v, t.height, j0, j1, b);
-    float2 t00 = texel_rg16f(t, i0, j0), t10 = texel_rg16f(t, i1, j0), t01 = texel_rg16f(t, i0, j1), t11 = texel_rg16f(t, i1, j1);
-    return make_float2(lerpx(lerpx(t00.x, t10.x, a), lerpx(t01.x, t11.x, a), b), lerpx(lerpx(t00.y, t10.y, a), lerpx(t01.y, t11.y, a), b));
+    return sample(split_tap(u, v, t.width, t.height), [&](int i, int j) { return texel_rg16f(t, i, j); });
 }
 __device__ __forceinline__ float sample_r32f(const PbrkTex2D& t, float u, float v) {
-    int i0, i1, j0, j1; float a, b;
-    split_axis(u, t.width, i0, i1, a); split_axis(v, t.height, j0, j1, b);
-    const float* p = (const float*)t.data;
-    float t00 = p[(size_t)j0 * t.width + i0], t10 = p[(size_t)j0 * t.width + i1], t01 = p[(size_t)j1 * t.width + i0], t11 = p[(size_t)j1 * t.width + i1];
-    return lerpx(lerpx(t00, t10, a), lerpx(t01, t11, a), b);
+    return sample(split_tap(u, v, t.width, t.height), [&](int i, int j) { return ((const float*)t.data)[(size_t)j * t.width + i]; });
 }
 
 __device__ __forceinline__ float mitchell_netravali(float x) {            // taa_resolve.glsl:13-26
@@ -83,44 +112,11 @@ __device__ __forceinline__ float mitchell_netravali(float x) {            // taa
     return 0.0f;
 }
 
-// one axis of SampleHistoryTextureCatmullRom (:139-167): tap coordinates (already divided by the size) and weights
-struct CrAxis { float p0, p12, p3, w0, w12, w3; };
-__device__ __forceinline__ CrAxis catmull_rom_axis(float uv, float ts) {
-    float sp = uv * ts;
-    float tp1 = floorf(sp - 0.5f) + 0.5f;
-    float f = sp - tp1;
-    CrAxis r;
-    r.w0 = f * (-0.5f + f * (1.0f - 0.5f * f));
-    float w1 = 1.0f + f * f * (-2.5f + 1.5f * f);
-    float w2 = f * (0.5f + f * (2.0f - 1.5f * f));
-    r.w3 = f * f * (-0.5f + 0.5f * f);
-    r.w12 = w1 + w2;
-    float offset12 = w2 / (w1 + w2);
-    r.p0 = (tp1 - 1.0f) / ts; r.p3 = (tp1 + 2.0f) / ts; r.p12 = (tp1 + offset12) / ts;
-    return r;
-}
-
 __device__ __forceinline__ uint2 pack_half4(float r0, float r1, float r2) {
     uint2 v;
     v.x = (unsigned)__half_as_ushort(__float2half_rn(r0)) | ((unsigned)__half_as_ushort(__float2half_rn(r1)) << 16);
     v.y = (unsigned)__half_as_ushort(__float2half_rn(r2)) | (0x3c00u << 16);
     return v;
-}
-
-__device__ __forceinline__ Rgba unpack_rgba16f(uint2 v) { return Rgba{h2f(v.x & 0xffff), h2f(v.x >> 16), h2f(v.y & 0xffff), h2f(v.y >> 16)}; }
-
-// buffer-addressed texel fetches: one 32-bit offset per load instead of a 64-bit address (textures are < 2 GiB, checked on the host)
-typedef unsigned u32x2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t tex_rsrc(const PbrkTex2D& t, int texel_bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)t.data, 0, t.width * t.height * texel_bytes, 0x00020000);
-}
-__device__ __forceinline__ Rgba fetch_rgba16f(__amdgpu_buffer_rsrc_t rs, int w, int i, int j) {
-    u32x2v v = __builtin_amdgcn_raw_buffer_load_b64(rs, (j * w + i) * 8, 0, 0);
-    return Rgba{h2f(v.x & 0xffff), h2f(v.x >> 16), h2f(v.y & 0xffff), h2f(v.y >> 16)};
-}
-__device__ __forceinline__ float2 fetch_rg16f(__amdgpu_buffer_rsrc_t rs, int w, int i, int j) {
-    unsigned v = __builtin_amdgcn_raw_buffer_load_b32(rs, (j * w + i) * 4, 0, 0);
-    return make_float2(h2f(v & 0xffff), h2f(v >> 16));
 }
 
 // kCentreExact (frames up to 8192^2 whose history has the frame's size): every tap the shader aims at a texel centre -- the 3x3 neighbourhood, depth, the
@@ -150,7 +146,7 @@ __global__ __launch_bounds__(256) void k_taa_resolve(TaaParams P) {
         const float* D = (const float*)A.gbuffer_depth.data;
         const size_t r0 = (size_t)py * W, r1 = (size_t)min(py + 1, H - 1) * W;
         const int x1 = min(px + 1, W - 1);
-        depth = lerpx(lerpx(D[r0 + px], D[r0 + x1], 0.0f), lerpx(D[r1 + px], D[r1 + x1], 0.0f), 0.0f);
+        depth = bilerp(D[r0 + px], D[r0 + x1], D[r1 + px], D[r1 + x1], 0.0f, 0.0f);
     } else depth = sample_r32f(A.gbuffer_depth, uvx, uvy);
 #pragma unroll
     for (int x = -1; x <= 1; ++x)                                               // :205-227
@@ -175,13 +171,7 @@ __global__ __launch_bounds__(256) void k_taa_resolve(TaaParams P) {
     if (kCentreExact && closest_depth < 10000.0f) vel = fetch_rg16f(rs_v, W, clampi(px - 1, 0, W - 1), clampi(py - 1, 0, H - 1));
     else vel = sample_rg16f(A.gbuffer_velocity, cdu, cdv);                      // :230
     const float ru = uvx - vel.x * 0.5f, rv = uvy - vel.y * 0.5f;               // :231
-    float2 pvel;                                                                // :232
-    {
-        int i0, i1, j0, j1; float a, b;
-        split_axis(ru, W, i0, i1, a); split_axis(rv, H, j0, j1, b);
-        float2 t00 = fetch_rg16f(rs_pv, W, i0, j0), t10 = fetch_rg16f(rs_pv, W, i1, j0), t01 = fetch_rg16f(rs_pv, W, i0, j1), t11 = fetch_rg16f(rs_pv, W, i1, j1);
-        pvel = make_float2(lerpx(lerpx(t00.x, t10.x, a), lerpx(t01.x, t11.x, a), b), lerpx(lerpx(t00.y, t10.y, a), lerpx(t01.y, t11.y, a), b));
-    }
+    const float2 pvel = sample(split_tap(ru, rv, W, H), [&](int i, int j) { return fetch_rg16f(rs_pv, W, i, j); });   // :232
 
     // :234 history, 9 bilinear taps in the shader's order
     float prev[3] = {0, 0, 0};
@@ -213,20 +203,20 @@ __global__ __launch_bounds__(256) void k_taa_resolve(TaaParams P) {
                 split_axis((tp1 + 2.0f) / tss[axis], extent, i0[2], i1[2], frac[2]);
             }
         }
+        auto texel = [&](int i, int j) { return fetch_rgba16f(rs_hi, HW, i, j); };
 #pragma unroll
         for (int row = 0; row < 3; ++row)
 #pragma unroll
             for (int col = 0; col < 3; ++col) {
+                // bilerp's blends in bilerp's order, without those of a texel with itself (an exact axis has one texel for both of the tap's)
                 const bool x_exact = kCentreExact && col != 1, y_exact = kCentreExact && row != 1;
-                Rgba t00 = fetch_rgba16f(rs_hi, HW, ci0[col], cj0[row]);
-                Rgba top = t00;
-                if (!x_exact) { Rgba t10 = fetch_rgba16f(rs_hi, HW, ci1[col], cj0[row]); top = Rgba{lerpx(t00.x, t10.x, ca[col]), lerpx(t00.y, t10.y, ca[col]), lerpx(t00.z, t10.z, ca[col]), 0.f}; }
+                Rgba top = texel(ci0[col], cj0[row]);
+                if (!x_exact) top = lerpx(top, texel(ci1[col], cj0[row]), ca[col]);
                 Rgba s = top;
                 if (!y_exact) {
-                    Rgba t01 = fetch_rgba16f(rs_hi, HW, ci0[col], cj1[row]);
-                    Rgba bot = t01;
-                    if (!x_exact) { Rgba t11 = fetch_rgba16f(rs_hi, HW, ci1[col], cj1[row]); bot = Rgba{lerpx(t01.x, t11.x, ca[col]), lerpx(t01.y, t11.y, ca[col]), lerpx(t01.z, t11.z, ca[col]), 0.f}; }
-                    s = Rgba{lerpx(top.x, bot.x, cb[row]), lerpx(top.y, bot.y, cb[row]), lerpx(top.z, bot.z, cb[row]), 0.f};
+                    Rgba bot = texel(ci0[col], cj1[row]);
+                    if (!x_exact) bot = lerpx(bot, texel(ci1[col], cj1[row]), ca[col]);
+                    s = lerpx(top, bot, cb[row]);
                 }
                 prev[0] = prev[0] + (s.x * wxs[col]) * wys[row];
                 prev[1] = prev[1] + (s.y * wxs[col]) * wys[row];
@@ -303,12 +293,10 @@ __global__ __launch_bounds__(256) void k_final_post_process_stream(PbrkFinalArgs
     const uint4* src = (const uint4*)((const uint2*)A.src.data + first);
     uint4 v0 = src[0], v1 = src[1];
     const unsigned raw[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-    float r[4][3];
+    float t[4][3], r[4][3];
+    unpack_row<4>(raw, t);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        Rgba s{h2f(raw[2 * k] & 0xffff), h2f(raw[2 * k] >> 16), h2f(raw[2 * k + 1] & 0xffff), 1.0f};
-        tone_map(s, r[k][0], r[k][1], r[k][2]);
-    }
+    for (int k = 0; k < 4; ++k) tone_map(Rgba{t[k][0], t[k][1], t[k][2], 1.0f}, r[k][0], r[k][1], r[k][2]);
     if (kOutFmt == PBRK_FMT_RGBA8UN || kOutFmt == PBRK_FMT_BGRA8UN) {
         ((uint4*)((unsigned*)A.out + first))[0] = make_uint4(pack8<kOutFmt>(r[0][0], r[0][1], r[0][2]), pack8<kOutFmt>(r[1][0], r[1][1], r[1][2]),
                                                              pack8<kOutFmt>(r[2][0], r[2][1], r[2][2]), pack8<kOutFmt>(r[3][0], r[3][1], r[3][2]));
@@ -324,12 +312,50 @@ __global__ __launch_bounds__(256) void k_final_post_process_stream(PbrkFinalArgs
     }
 }
 
-// K10 / K11: bloom passes.  Column / row tap coordinates repeat (5 distinct offsets for the 13-tap downsample, 3 for the
-// tent), so the snapped bilinear split is done once per distinct offset and the taps index the results.
+// K10 / K11: bloom passes
 struct BloomParams { PbrkBloomArgs a; float x_step, y_step, rcp_dw, rcp_dh; int exact2to1; };
-typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 
+// The shaders' sums, bloom_downsample.glsl:50-97 and bloom_upsample.glsl:43-58: four-tap groups added left to right, then folded with the
+// weights in the shaders' order; the firefly clamp of the first downsample and the upsample's factor / 16 as the shaders write them.
+__device__ __forceinline__ float group4(float a, float b, float c, float d) { return ((a + b) + c) + d; }
+__device__ __forceinline__ float down_fold(float centre, float corners, float edges, float inner, int dst_mip_level) {
+    float sum = centre * 0.125f;
+    sum = sum + corners * 0.03125f;
+    sum = sum + edges * 0.0625f;
+    sum = sum + inner * 0.125f;
+    if (dst_mip_level == 1) sum = fminf(sum, 1.0f);
+    return sum;
+}
+__device__ __forceinline__ float up_fold(float centre, float edges, float corners, int dst_mip_level) {
+    const float factor = dst_mip_level == 0 ? 0.06f : 1.0f;
+    float sum = centre * 4.0f;
+    sum = sum + edges * 2.0f;
+    sum = sum + corners;
+    return sum * factor / 16.0f;
+}
+// the same over tap(kx, ky), one channel of the tap at offset (kx - 2, ky - 2) texels (down) or (kx - 1, ky - 1) radii (up)
+template <class TapFn>
+__device__ __forceinline__ float down_sum(TapFn tap, int dst_mip_level) {
+    return down_fold(tap(2, 2), group4(tap(0, 0), tap(4, 0), tap(0, 4), tap(4, 4)), group4(tap(2, 0), tap(0, 2), tap(4, 2), tap(2, 4)),
+                     group4(tap(1, 1), tap(3, 1), tap(1, 3), tap(3, 3)), dst_mip_level);
+}
+template <class TapFn>
+__device__ __forceinline__ float up_sum(TapFn tap, int dst_mip_level) {
+    return up_fold(tap(1, 1), group4(tap(1, 0), tap(0, 1), tap(2, 1), tap(1, 2)), group4(tap(0, 0), tap(2, 0), tap(0, 2), tap(2, 2)), dst_mip_level);
+}
+
+// the tail of a one-pixel pass: the additive blend with the operand (blend_src, or the target itself) and the store
+__device__ __forceinline__ void blend_store(const PbrkBloomArgs& A, int px, int py, float* r) {
+    uint2* o = (uint2*)A.dst + (size_t)py * A.dst_width + px;
+    if (A.blend_additive) {
+        const Rgba d = unpack_rgba16f(A.blend_src ? ((const uint2*)A.blend_src)[(size_t)py * A.dst_width + px] : *o);
+        r[0] = r[0] + d.x; r[1] = r[1] + d.y; r[2] = r[2] + d.z;
+    }
+    *o = pack_half4(r[0], r[1], r[2]);
+}
 // The general path of a bloom pass: every tap through the snapped bilinear sampler (any size ratio, border pixels of the exact passes).
+// Column / row tap coordinates repeat (5 distinct offsets for the 13-tap downsample, 3 for the tent), so the snapped bilinear split is
+// done once per distinct offset and the taps index the results.
 template <bool kUp>
 __device__ __forceinline__ void bloom_general(const BloomParams& P, const __amdgpu_buffer_rsrc_t rs, const int px, const int py, float* r) {
     const PbrkBloomArgs& A = P.a;
@@ -345,41 +371,42 @@ __device__ __forceinline__ void bloom_general(const BloomParams& P, const __amdg
         split_axis(u + off * P.x_step, SW, ci0[k], ci1[k], ca[k]);
         split_axis(v + off * P.y_step, SH, cj0[k], cj1[k], cb[k]);
     }
-    auto tap = [&](int kx, int ky, float* o) {
-        Rgba t00 = fetch_rgba16f(rs, SW, ci0[kx], cj0[ky]), t10 = fetch_rgba16f(rs, SW, ci1[kx], cj0[ky]);
-        Rgba t01 = fetch_rgba16f(rs, SW, ci0[kx], cj1[ky]), t11 = fetch_rgba16f(rs, SW, ci1[kx], cj1[ky]);
-        o[0] = lerpx(lerpx(t00.x, t10.x, ca[kx]), lerpx(t01.x, t11.x, ca[kx]), cb[ky]);
-        o[1] = lerpx(lerpx(t00.y, t10.y, ca[kx]), lerpx(t01.y, t11.y, ca[kx]), cb[ky]);
-        o[2] = lerpx(lerpx(t00.z, t10.z, ca[kx]), lerpx(t01.z, t11.z, ca[kx]), cb[ky]);
-    };
-    if (kUp) {                                                                          // bloom_upsample.glsl:43-58
-        float t[9][3];
+    auto texel = [&](int i, int j) { return fetch_rgba16f(rs, SW, i, j); };
+    float t[kOffs][kOffs][3];                                                           // [ky][kx]: all nine (up); the 13 whose offsets are both even or both odd (down)
+    auto fill = [&](int kx, int ky) { rgb_of(sample(Tap{ci0[kx], ci1[kx], cj0[ky], cj1[ky], ca[kx], cb[ky]}, texel), t[ky][kx]); };
+    constexpr int kStep = kUp ? 1 : 2;                                                  // the shaders' order, a..i then j k l m: row by row costs k_bloom_pass<false> a wave
 #pragma unroll
-        for (int k = 0; k < 9; ++k) tap(k % 3, k / 3, t[k]);                            // a b c / d e f / g h i
-        const float factor = A.dst_mip_level == 0 ? 0.06f : 1.0f;
+    for (int k = 0; k < 9; ++k) fill(kStep * (k % 3), kStep * (k / 3));
+    if (!kUp) { fill(1, 1); fill(3, 1); fill(1, 3); fill(3, 3); }
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float sum = t[4][c] * 4.0f;
-            sum = sum + (((t[1][c] + t[3][c]) + t[5][c]) + t[7][c]) * 2.0f;
-            sum = sum + (((t[0][c] + t[2][c]) + t[6][c]) + t[8][c]);
-            r[c] = sum * factor / 16.0f;
-        }
-    } else {                                                                            // bloom_downsample.glsl:50-97
-        float t[13][3];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) tap(2 * (k % 3), 2 * (k / 3), t[k]);                // a..i at offsets -2, 0, 2
-        tap(1, 1, t[9]); tap(3, 1, t[10]); tap(1, 3, t[11]); tap(3, 3, t[12]);          // j k l m at (+-1, +-1)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float sum = t[4][c] * 0.125f;
-            sum = sum + (((t[0][c] + t[2][c]) + t[6][c]) + t[8][c]) * 0.03125f;
-            sum = sum + (((t[1][c] + t[3][c]) + t[5][c]) + t[7][c]) * 0.0625f;
-            sum = sum + (((t[9][c] + t[10][c]) + t[11][c]) + t[12][c]) * 0.125f;
-            if (A.dst_mip_level == 1) sum = fminf(sum, 1.0f);
-            r[c] = sum;
-        }
+    for (int c = 0; c < 3; ++c) {
+        auto tap = [&](int kx, int ky) { return t[ky][kx][c]; };
+        if constexpr (kUp) r[c] = up_sum(tap, A.dst_mip_level);
+        else r[c] = down_sum(tap, A.dst_mip_level);
     }
 }
+
+// N consecutive texels (rgb) of row y starting at column x0: whole-row loads when the run lies inside the level, else texel by texel
+// with the sampler's clamp to edge (a tap whose two texels clamp to the same one returns it whatever its fraction: p + t (p - p)).
+template <int N>
+__device__ __forceinline__ void bloom_row(const __amdgpu_buffer_rsrc_t rs, const int SW, const int SH, const int x0, const int y, const bool inside, float (*t)[3]) {
+    static_assert(N == 5 || N == 6 || N == 8, "window width");
+    if (inside) {
+        const int off = (y * SW + x0) * 8;
+        unsigned w[16];                                                                 // loads written out, two first: as a loop k_bloom_down_pair schedules 5 % slower
+        const u32x4v q0 = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0), q1 = __builtin_amdgcn_raw_buffer_load_b128(rs, off + 16, 0, 0);
+        w[0] = q0.x; w[1] = q0.y; w[2] = q0.z; w[3] = q0.w; w[4] = q1.x; w[5] = q1.y; w[6] = q1.z; w[7] = q1.w;
+        if (N == 5) { const u32x2v q2 = __builtin_amdgcn_raw_buffer_load_b64(rs, off + 32, 0, 0); w[8] = q2.x; w[9] = q2.y; }
+        else { const u32x4v q2 = __builtin_amdgcn_raw_buffer_load_b128(rs, off + 32, 0, 0); w[8] = q2.x; w[9] = q2.y; w[10] = q2.z; w[11] = q2.w; }
+        if (N == 8) { const u32x4v q3 = __builtin_amdgcn_raw_buffer_load_b128(rs, off + 48, 0, 0); w[12] = q3.x; w[13] = q3.y; w[14] = q3.z; w[15] = q3.w; }
+        unpack_row<N>(w, t);
+    } else {
+        const int yc = clampi(y, 0, SH - 1);
+#pragma unroll
+        for (int c = 0; c < N; ++c) rgb_of(fetch_rgba16f(rs, SW, clampi(x0 + c, 0, SW - 1), yc), t[c]);
+    }
+}
+
 template <bool kUp>
 __global__ __launch_bounds__(256) void k_bloom_pass(BloomParams P) {
     const PbrkBloomArgs& A = P.a;
@@ -400,46 +427,29 @@ __global__ __launch_bounds__(256) void k_bloom_pass(BloomParams P) {
                 float hx[6][5][3];                                                      // rows x horizontal taps (offsets -2..2) x rgb
 #pragma unroll
                 for (int rr = 0; rr < 6; ++rr) {
-                    const int off = ((2 * py - 2 + rr) * SW + 2 * px - 2) * 8;
-                    u32x4v q0 = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0), q1 = __builtin_amdgcn_raw_buffer_load_b128(rs, off + 16, 0, 0);
-                    u32x4v q2 = __builtin_amdgcn_raw_buffer_load_b128(rs, off + 32, 0, 0);
-                    const unsigned w[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
                     float t[6][3];
-#pragma unroll
-                    for (int c = 0; c < 6; ++c) { t[c][0] = h2f(w[2 * c] & 0xffff); t[c][1] = h2f(w[2 * c] >> 16); t[c][2] = h2f(w[2 * c + 1] & 0xffff); }
+                    bloom_row<6>(rs, SW, SH, 2 * px - 2, 2 * py - 2 + rr, true, t);
 #pragma unroll
                     for (int k = 0; k < 5; ++k)
 #pragma unroll
                         for (int c = 0; c < 3; ++c) hx[rr][k][c] = lerpc(t[k][c], t[k + 1][c], 0.5f);
                 }
-                auto tapd = [&](int kx, int ky, int c) { return lerpc(hx[ky][kx][c], hx[ky + 1][kx][c], 0.5f); };
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    float sum = tapd(2, 2, c) * 0.125f;
-                    sum = sum + (((tapd(0, 0, c) + tapd(4, 0, c)) + tapd(0, 4, c)) + tapd(4, 4, c)) * 0.03125f;
-                    sum = sum + (((tapd(2, 0, c) + tapd(0, 2, c)) + tapd(4, 2, c)) + tapd(2, 4, c)) * 0.0625f;
-                    sum = sum + (((tapd(1, 1, c) + tapd(3, 1, c)) + tapd(1, 3, c)) + tapd(3, 3, c)) * 0.125f;
-                    if (A.dst_mip_level == 1) sum = fminf(sum, 1.0f);
-                    r[c] = sum;
-                }
+                for (int c = 0; c < 3; ++c) r[c] = down_sum([&](int kx, int ky) { return lerpc(hx[ky][kx][c], hx[ky + 1][kx][c], 0.5f); }, A.dst_mip_level);
                 done = true;
             }
         } else {
             const int i = px >> 1, j = py >> 1;
             if (i >= 2 && i <= SW - 3 && j >= 2 && j <= SH - 3) {
+                // lerpx, not lerpc: these fractions differ by lane, and lerpc would pay for both of its forms and a select (107 VGPRs for 86)
                 const bool ox = px & 1, oy = py & 1;
                 const float fx_side = ox ? 0.75f : 0.25f, fx_mid = ox ? 0.25f : 0.75f;      // fractions of the taps at -1.5 / +1.5 and at 0
                 const float fy_side = oy ? 0.75f : 0.25f, fy_mid = oy ? 0.25f : 0.75f;
                 float hx[5][3][3];                                                      // rows x horizontal taps (left, centre, right) x rgb
 #pragma unroll
                 for (int rr = 0; rr < 5; ++rr) {
-                    const int off = ((j - 2 + rr) * SW + i - 2) * 8;
-                    u32x4v q0 = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0), q1 = __builtin_amdgcn_raw_buffer_load_b128(rs, off + 16, 0, 0);
-                    u32x2v q2 = __builtin_amdgcn_raw_buffer_load_b64(rs, off + 32, 0, 0);
-                    const unsigned w[10] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y};
                     float t[5][3];
-#pragma unroll
-                    for (int c = 0; c < 5; ++c) { t[c][0] = h2f(w[2 * c] & 0xffff); t[c][1] = h2f(w[2 * c] >> 16); t[c][2] = h2f(w[2 * c + 1] & 0xffff); }
+                    bloom_row<5>(rs, SW, SH, i - 2, j - 2 + rr, true, t);
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
                         hx[rr][0][c] = lerpx(t[0][c], t[1][c], fx_side);
@@ -452,25 +462,14 @@ __global__ __launch_bounds__(256) void k_bloom_pass(BloomParams P) {
                     if (ky == 2) return lerpx(hx[3][kx][c], hx[4][kx][c], fy_side);
                     return lerpx(oy ? hx[2][kx][c] : hx[1][kx][c], oy ? hx[3][kx][c] : hx[2][kx][c], fy_mid);
                 };
-                const float factor = A.dst_mip_level == 0 ? 0.06f : 1.0f;
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    float sum = tapu(1, 1, c) * 4.0f;
-                    sum = sum + (((tapu(1, 0, c) + tapu(0, 1, c)) + tapu(2, 1, c)) + tapu(1, 2, c)) * 2.0f;
-                    sum = sum + (((tapu(0, 0, c) + tapu(2, 0, c)) + tapu(0, 2, c)) + tapu(2, 2, c));
-                    r[c] = sum * factor / 16.0f;
-                }
+                for (int c = 0; c < 3; ++c) r[c] = up_sum([&](int kx, int ky) { return tapu(kx, ky, c); }, A.dst_mip_level);
                 done = true;
             }
         }
     }
     if (!done) bloom_general<kUp>(P, rs, px, py, r);
-    uint2* o = (uint2*)A.dst + (size_t)py * A.dst_width + px;
-    if (A.blend_additive) {
-        Rgba d = unpack_rgba16f(A.blend_src ? ((const uint2*)A.blend_src)[(size_t)py * A.dst_width + px] : *o);
-        r[0] = r[0] + d.x; r[1] = r[1] + d.y; r[2] = r[2] + d.z;
-    }
-    *o = pack_half4(r[0], r[1], r[2]);
+    blend_store(A, px, py, r);
 }
 
 // K10 / K11, SMALL levels through the general sampler (the passes of a 1080p frame below 240 x 135, whose sizes are not 2 : 1): a level
@@ -502,13 +501,8 @@ __global__ __launch_bounds__(256) void k_bloom_small(BloomParams P) {
         const float cx = (j & 1) ? 1.0f : -1.0f, cy = (j & 2) ? 1.0f : -1.0f;
         const float ex = j == 1 ? -1.0f : j == 2 ? 1.0f : 0.0f, ey = j == 0 ? -1.0f : j == 3 ? 1.0f : 0.0f;
         const float offx = (edge ? ex : cx) * mag, offy = (edge ? ey : cy) * mag;        // exact: +-2, +-1 or 0 (a centre lane repeats its tap)
-        int i0, i1, j0, j1; float a, b;
-        split_axis(u + offx * P.x_step, SW, i0, i1, a);
-        split_axis(v + offy * P.y_step, SH, j0, j1, b);
-        Rgba t00 = fetch_rgba16f(rs, SW, i0, j0), t10 = fetch_rgba16f(rs, SW, i1, j0);
-        Rgba t01 = fetch_rgba16f(rs, SW, i0, j1), t11 = fetch_rgba16f(rs, SW, i1, j1);
-        const float t[3] = {lerpx(lerpx(t00.x, t10.x, a), lerpx(t01.x, t11.x, a), b), lerpx(lerpx(t00.y, t10.y, a), lerpx(t01.y, t11.y, a), b),
-                            lerpx(lerpx(t00.z, t10.z, a), lerpx(t01.z, t11.z, a), b)};
+        float t[3];
+        rgb_of(sample(split_tap(u + offx * P.x_step, v + offy * P.y_step, SW, SH), [&](int x, int y) { return fetch_rgba16f(rs, SW, x, y); }), t);
 #pragma unroll
         for (int c = 0; c < 3; ++c) g[c] = j == 0 ? t[c] : (centre ? g[c] : g[c] + t[c]);   // ((t0 + t1) + t2) + t3; the centre group is its one tap
     }
@@ -517,52 +511,9 @@ __global__ __launch_bounds__(256) void k_bloom_small(BloomParams P) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float g1 = __shfl(g[c], base + 1), g2 = __shfl(g[c], base + 2), g3 = __shfl(g[c], base + 3);
-        if (kUp) {                                                                      // bloom_upsample.glsl:43-58
-            const float factor = A.dst_mip_level == 0 ? 0.06f : 1.0f;
-            float sum = g[c] * 4.0f;
-            sum = sum + g1 * 2.0f;
-            sum = sum + g2;
-            r[c] = sum * factor / 16.0f;
-        } else {                                                                        // bloom_downsample.glsl:50-97
-            float sum = g[c] * 0.125f;
-            sum = sum + g1 * 0.03125f;
-            sum = sum + g2 * 0.0625f;
-            sum = sum + g3 * 0.125f;
-            if (A.dst_mip_level == 1) sum = fminf(sum, 1.0f);
-            r[c] = sum;
-        }
+        r[c] = kUp ? up_fold(g[c], g1, g2, A.dst_mip_level) : down_fold(g[c], g1, g2, g3, A.dst_mip_level);
     }
-    if (!live || q != 0) return;
-    uint2* o = (uint2*)A.dst + (size_t)py * A.dst_width + px;
-    if (A.blend_additive) {
-        Rgba d = unpack_rgba16f(A.blend_src ? ((const uint2*)A.blend_src)[(size_t)py * A.dst_width + px] : *o);
-        r[0] = r[0] + d.x; r[1] = r[1] + d.y; r[2] = r[2] + d.z;
-    }
-    *o = pack_half4(r[0], r[1], r[2]);
-}
-
-// N consecutive texels (rgb) of row y starting at column x0: whole-row loads when the run lies inside the level, else texel by texel
-// with the sampler's clamp to edge (a tap whose two texels clamp to the same one returns it whatever its fraction: p + t (p - p)).
-template <int N>
-__device__ __forceinline__ void bloom_row(const __amdgpu_buffer_rsrc_t rs, const int SW, const int SH, const int x0, const int y, const bool inside, float (*t)[3]) {
-    static_assert(N == 5 || N == 8, "window width");
-    if (inside) {
-        const int off = (y * SW + x0) * 8;
-        unsigned w[16];
-        u32x4v q0 = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0), q1 = __builtin_amdgcn_raw_buffer_load_b128(rs, off + 16, 0, 0);
-        w[0] = q0.x; w[1] = q0.y; w[2] = q0.z; w[3] = q0.w; w[4] = q1.x; w[5] = q1.y; w[6] = q1.z; w[7] = q1.w;
-        if (N == 5) { u32x2v q2 = __builtin_amdgcn_raw_buffer_load_b64(rs, off + 32, 0, 0); w[8] = q2.x; w[9] = q2.y; }
-        else {
-            u32x4v q2 = __builtin_amdgcn_raw_buffer_load_b128(rs, off + 32, 0, 0), q3 = __builtin_amdgcn_raw_buffer_load_b128(rs, off + 48, 0, 0);
-            w[8] = q2.x; w[9] = q2.y; w[10] = q2.z; w[11] = q2.w; w[12] = q3.x; w[13] = q3.y; w[14] = q3.z; w[15] = q3.w;
-        }
-#pragma unroll
-        for (int c = 0; c < N; ++c) { t[c][0] = h2f(w[2 * c] & 0xffff); t[c][1] = h2f(w[2 * c] >> 16); t[c][2] = h2f(w[2 * c + 1] & 0xffff); }
-    } else {
-        const int yc = clampi(y, 0, SH - 1);
-#pragma unroll
-        for (int c = 0; c < N; ++c) { const Rgba v = fetch_rgba16f(rs, SW, clampi(x0 + c, 0, SW - 1), yc); t[c][0] = v.x; t[c][1] = v.y; t[c][2] = v.z; }
-    }
+    if (live && q == 0) blend_store(A, px, py, r);
 }
 
 // K11, exact 1 : 2 upsample of LARGE levels: one thread per 2 x 2 block of target pixels.  The four pixels (2i + ox, 2j + oy) read the SAME
@@ -574,6 +525,8 @@ __device__ __forceinline__ void bloom_row(const __amdgpu_buffer_rsrc_t rs, const
 // latency-bound and a four-pixel thread is four times as long.  (The downsample had a 2 x 2 form too -- 8 x 8 window, 25 distinct taps for
 // 52 -- which kept 158 registers and two waves per SIMD on the 960 x 540 pass, 65 % of their lifetime waiting for 32 loads: the pair form
 // below replaced it, 16.8 -> 14.2 us.)
+// The window code and the pair tail are this kernel's own: one function for the window shared with k_bloom_pass<true>, or a blend-and-store
+// shared with a one-pair-per-thread downsample, each made the 960 x 540 pass slower (7.9 -> 8.3 / 8.0 us).
 __global__ __launch_bounds__(256) void k_bloom_quad(BloomParams P) {
     const PbrkBloomArgs& A = P.a;
     const int qx = blockIdx.x * 64 + (threadIdx.x & 63);
@@ -597,7 +550,6 @@ __global__ __launch_bounds__(256) void k_bloom_quad(BloomParams P) {
                 hx[rr][0][2][c] = lerpc(t[3][c], t[4][c], 0.25f); hx[rr][1][2][c] = lerpc(t[3][c], t[4][c], 0.75f);
             }
         }
-        const float factor = A.dst_mip_level == 0 ? 0.06f : 1.0f;
 #pragma unroll
         for (int oy = 0; oy < 2; ++oy)
 #pragma unroll
@@ -609,12 +561,7 @@ __global__ __launch_bounds__(256) void k_bloom_quad(BloomParams P) {
                     return lerpc(hx[oy ? 2 : 1][ox][kx][c], hx[oy ? 3 : 2][ox][kx][c], fy_mid);
                 };
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    float sum = tapu(1, 1, c) * 4.0f;
-                    sum = sum + (((tapu(1, 0, c) + tapu(0, 1, c)) + tapu(2, 1, c)) + tapu(1, 2, c)) * 2.0f;
-                    sum = sum + (((tapu(0, 0, c) + tapu(2, 0, c)) + tapu(0, 2, c)) + tapu(2, 2, c));
-                    r[oy][ox][c] = sum * factor / 16.0f;
-                }
+                for (int c = 0; c < 3; ++c) r[oy][ox][c] = up_sum([&](int kx, int ky) { return tapu(kx, ky, c); }, A.dst_mip_level);
             }
     }
 #pragma unroll
@@ -674,16 +621,8 @@ __global__ __launch_bounds__(256) void k_bloom_down_pair(BloomParams P) {
 #pragma unroll
     for (int dx = 0; dx < 2; ++dx)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            auto ev = [&](int kx, int ky) { return E[ky >> 1][dx + (kx >> 1)][c]; };
-            auto od = [&](int kx, int ky) { return O[ky >> 1][dx + (kx >> 1)][c]; };
-            float sum = ev(2, 2) * 0.125f;
-            sum = sum + (((ev(0, 0) + ev(4, 0)) + ev(0, 4)) + ev(4, 4)) * 0.03125f;
-            sum = sum + (((ev(2, 0) + ev(0, 2)) + ev(4, 2)) + ev(2, 4)) * 0.0625f;
-            sum = sum + (((od(1, 1) + od(3, 1)) + od(1, 3)) + od(3, 3)) * 0.125f;
-            if (A.dst_mip_level == 1) sum = fminf(sum, 1.0f);
-            r[dx][c] = sum;
-        }
+        for (int c = 0; c < 3; ++c)
+            r[dx][c] = down_sum([&](int kx, int ky) { return (kx & 1) ? O[ky >> 1][dx + (kx >> 1)][c] : E[ky >> 1][dx + (kx >> 1)][c]; }, A.dst_mip_level);
     const uint2 a = pack_half4(r[0][0], r[0][1], r[0][2]), b = pack_half4(r[1][0], r[1][1], r[1][2]);
     *(uint4*)((uint2*)A.dst + (size_t)py * A.dst_width + 2 * qx) = make_uint4(a.x, a.y, b.x, b.y);
 }
@@ -696,10 +635,12 @@ __global__ void k_debug_sample_post(PbrkTex2D t, const float* __restrict__ coord
 }
 
 bool tex_ok(const PbrkTex2D& t, int fmt) { return t.data && t.format == fmt && t.width > 0 && t.height > 0; }
+bool band_ok(int y0, int y1, int height) { return y0 >= 0 && y0 < y1 && y1 <= height; }
+int launched() { return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH; }
 }  // namespace
 
 extern "C" int pbrk_taa_resolve(const PbrkTaaArgs* a, void* stream) {
-    if (!a || !a->out || a->width < 1 || a->height < 1 || a->y0 < 0 || a->y0 >= a->y1 || a->y1 > a->height) return PBRK_E_ARG;
+    if (!a || !a->out || a->width < 1 || a->height < 1 || !band_ok(a->y0, a->y1, a->height)) return PBRK_E_ARG;
     if (!tex_ok(a->lighting_result, PBRK_FMT_RGBA16F) || !tex_ok(a->prev_frame_result, PBRK_FMT_RGBA16F) || !tex_ok(a->gbuffer_depth, PBRK_FMT_R32F) ||
         !tex_ok(a->gbuffer_velocity, PBRK_FMT_RG16F) || !tex_ok(a->gbuffer_velocity_prev, PBRK_FMT_RG16F)) return PBRK_E_FORMAT;
     if (a->out_format != PBRK_FMT_RGBA16F && a->out_format != PBRK_FMT_RGBA32F) return PBRK_E_FORMAT;
@@ -711,43 +652,41 @@ extern "C" int pbrk_taa_resolve(const PbrkTaaArgs* a, void* stream) {
     // the exact path counts its outer history taps in texels of the frame: only a history of the frame's size has them at its own centres
     const bool centre = a->width <= 8192 && a->height <= 8192 && a->prev_frame_result.width == a->width && a->prev_frame_result.height == a->height;
     const bool half = a->out_format == PBRK_FMT_RGBA16F;
-    dim3 grid((a->width + 63) / 64, (a->y1 - a->y0 + 3) / 4), block(256);
-    hipStream_t st = (hipStream_t)stream;
+    static void (*const kernels[2][2])(TaaParams) = {{k_taa_resolve<false, false>, k_taa_resolve<false, true>}, {k_taa_resolve<true, false>, k_taa_resolve<true, true>}};
     TaaParams tp; tp.a = *a; tp.psx = 1.0f / (float)a->lighting_result.width; tp.psy = 1.0f / (float)a->lighting_result.height;
-    if (centre && half) hipLaunchKernelGGL((k_taa_resolve<true, true>), grid, block, 0, st, tp);
-    else if (centre) hipLaunchKernelGGL((k_taa_resolve<true, false>), grid, block, 0, st, tp);
-    else if (half) hipLaunchKernelGGL((k_taa_resolve<false, true>), grid, block, 0, st, tp);
-    else hipLaunchKernelGGL((k_taa_resolve<false, false>), grid, block, 0, st, tp);
-    return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
+    hipLaunchKernelGGL(kernels[centre][half], dim3((a->width + 63) / 64, (a->y1 - a->y0 + 3) / 4), dim3(256), 0, (hipStream_t)stream, tp);
+    return launched();
 }
 
 extern "C" int pbrk_final_post_process(const PbrkFinalArgs* a, void* stream) {
-    if (!a || !a->out || a->width < 1 || a->height < 1 || a->y0 < 0 || a->y0 >= a->y1 || a->y1 > a->height) return PBRK_E_ARG;
+    if (!a || !a->out || a->width < 1 || a->height < 1 || !band_ok(a->y0, a->y1, a->height)) return PBRK_E_ARG;
     if (!tex_ok(a->src, PBRK_FMT_RGBA16F)) return PBRK_E_FORMAT;
     if (a->out == a->src.data) return PBRK_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
+    static const struct { int format; void (*general)(PbrkFinalArgs); void (*stream)(PbrkFinalArgs); } kernels[] = {
+        {PBRK_FMT_RGBA8UN, k_final_post_process<PBRK_FMT_RGBA8UN>, k_final_post_process_stream<PBRK_FMT_RGBA8UN>},
+        {PBRK_FMT_BGRA8UN, k_final_post_process<PBRK_FMT_BGRA8UN>, k_final_post_process_stream<PBRK_FMT_BGRA8UN>},
+        {PBRK_FMT_RGBA16F, k_final_post_process<PBRK_FMT_RGBA16F>, k_final_post_process_stream<PBRK_FMT_RGBA16F>},
+        {PBRK_FMT_RGBA32F, k_final_post_process<PBRK_FMT_RGBA32F>, k_final_post_process_stream<PBRK_FMT_RGBA32F>}};
     const bool stream_map = a->src.width == a->width && a->src.height == a->height && a->width <= 8192 && a->height <= 8192 && (a->width & 3) == 0;
-    dim3 block(256);
-    dim3 grid = stream_map ? dim3((unsigned)((((size_t)(a->width >> 2) * (a->y1 - a->y0)) + 255) / 256)) : dim3((a->width + 63) / 64, (a->y1 - a->y0 + 3) / 4);
-#define PBRK_FINAL_LAUNCH(F) do { if (stream_map) hipLaunchKernelGGL((k_final_post_process_stream<F>), grid, block, 0, st, *a); \
-                                  else hipLaunchKernelGGL((k_final_post_process<F>), grid, block, 0, st, *a); } while (0)
-    switch (a->out_format) {
-    case PBRK_FMT_RGBA8UN: PBRK_FINAL_LAUNCH(PBRK_FMT_RGBA8UN); break;
-    case PBRK_FMT_BGRA8UN: PBRK_FINAL_LAUNCH(PBRK_FMT_BGRA8UN); break;
-    case PBRK_FMT_RGBA16F: PBRK_FINAL_LAUNCH(PBRK_FMT_RGBA16F); break;
-    case PBRK_FMT_RGBA32F: PBRK_FINAL_LAUNCH(PBRK_FMT_RGBA32F); break;
-    default: return PBRK_E_FORMAT;
-    }
-#undef PBRK_FINAL_LAUNCH
-    return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
+    const dim3 grid = stream_map ? dim3((unsigned)((((size_t)(a->width >> 2) * (a->y1 - a->y0)) + 255) / 256)) : dim3((a->width + 63) / 64, (a->y1 - a->y0 + 3) / 4);
+    for (const auto& k : kernels)
+        if (k.format == a->out_format) {
+            hipLaunchKernelGGL(stream_map ? k.stream : k.general, grid, dim3(256), 0, (hipStream_t)stream, *a);
+            return launched();
+        }
+    return PBRK_E_FORMAT;
 }
 
 // which instantiation a bloom pass takes (all bit-identical): < 0 = the environment variable or the default
 static long long g_quad_min = -1, g_small_max = -1;
 extern "C" void pbrk_bloom_set_thresholds(long long quad_min_pixels, long long small_max_pixels) { g_quad_min = quad_min_pixels; g_small_max = small_max_pixels; }
+static long long threshold(long long& value, const char* env, long long fallback) {
+    if (value < 0) { const char* e = getenv(env); value = e ? atoll(e) : fallback; }
+    return value;
+}
 
 extern "C" int pbrk_bloom_pass(const PbrkBloomArgs* a, void* stream) {
-    if (!a || !a->dst || a->dst_width < 1 || a->dst_height < 1 || a->y0 < 0 || a->y0 >= a->y1 || a->y1 > a->dst_height) return PBRK_E_ARG;
+    if (!a || !a->dst || a->dst_width < 1 || a->dst_height < 1 || !band_ok(a->y0, a->y1, a->dst_height)) return PBRK_E_ARG;
     if (!tex_ok(a->src, PBRK_FMT_RGBA16F)) return PBRK_E_FORMAT;
     if ((long long)a->src.width * a->src.height > (1ll << 27) || a->dst == a->src.data) return PBRK_E_ARG;
     BloomParams p;
@@ -759,37 +698,27 @@ extern "C" int pbrk_bloom_pass(const PbrkBloomArgs* a, void* stream) {
     const bool small = a->src.width <= 8192 && a->src.height <= 8192 && a->dst_width <= 8192 && a->dst_height <= 8192;
     p.exact2to1 = small && (a->upsample ? (a->dst_width == 2 * a->src.width && a->dst_height == 2 * a->src.height)
                                         : (a->src.width == 2 * a->dst_width && a->src.height == 2 * a->dst_height));
+    const int rows = a->y1 - a->y0;
+    const long long pixels = (long long)a->dst_width * rows;
     // two (downsample) / 2 x 2 (upsample) pixels per thread where the level is large enough to fill the chip with such threads (PBR_BLOOM_QUAD_MIN_PIXELS)
-    if (g_quad_min < 0) { const char* e = getenv("PBR_BLOOM_QUAD_MIN_PIXELS"); g_quad_min = e ? atoll(e) : 100000; }
-    const long long quad_min = g_quad_min;
     const bool wide = p.exact2to1 && ((uintptr_t)a->dst & 15) == 0 && ((uintptr_t)a->src.data & 15) == 0 && ((uintptr_t)a->blend_src & 15) == 0 &&
-                      (long long)a->dst_width * (a->y1 - a->y0) >= quad_min;
+                      pixels >= threshold(g_quad_min, "PBR_BLOOM_QUAD_MIN_PIXELS", 100000);
+    void (*kernel)(BloomParams);
+    dim3 grid((a->dst_width + 63) / 64, (rows + 3) / 4);                                // one pixel per thread
     if (wide && !a->upsample && !a->blend_additive && !(a->dst_width & 1)) {
-        hipLaunchKernelGGL(k_bloom_down_pair, dim3((a->dst_width / 2 + 63) / 64, (a->y1 - a->y0 + 3) / 4), dim3(256), 0, (hipStream_t)stream, p);
-        return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
-    }
-    if (wide && a->upsample && !((a->dst_width | a->dst_height | a->y0 | a->y1) & 1)) {
-        dim3 qgrid((a->dst_width / 2 + 63) / 64, ((a->y1 - a->y0) / 2 + 3) / 4);
-        hipLaunchKernelGGL(k_bloom_quad, qgrid, dim3(256), 0, (hipStream_t)stream, p);
-        return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
-    }
-    // four lanes per pixel where a level is too small to fill the chip and goes through the general sampler (PBR_BLOOM_SMALL_MAX_PIXELS)
-    if (g_small_max < 0) { const char* e = getenv("PBR_BLOOM_SMALL_MAX_PIXELS"); g_small_max = e ? atoll(e) : 40000; }
-    const long long small_max = g_small_max;
-    if (!p.exact2to1 && (long long)a->dst_width * (a->y1 - a->y0) <= small_max) {
-        dim3 sgrid((a->dst_width + 63) / 64, a->y1 - a->y0);
-        if (a->upsample) hipLaunchKernelGGL((k_bloom_small<true>), sgrid, dim3(256), 0, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL((k_bloom_small<false>), sgrid, dim3(256), 0, (hipStream_t)stream, p);
-        return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
-    }
-    dim3 grid((a->dst_width + 63) / 64, (a->y1 - a->y0 + 3) / 4), block(256);
-    if (a->upsample) hipLaunchKernelGGL((k_bloom_pass<true>), grid, block, 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((k_bloom_pass<false>), grid, block, 0, (hipStream_t)stream, p);
-    return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
+        kernel = k_bloom_down_pair; grid.x = (a->dst_width / 2 + 63) / 64;
+    } else if (wide && a->upsample && !((a->dst_width | a->dst_height | a->y0 | a->y1) & 1)) {
+        kernel = k_bloom_quad; grid = dim3((a->dst_width / 2 + 63) / 64, (rows / 2 + 3) / 4);
+    } else if (!p.exact2to1 && pixels <= threshold(g_small_max, "PBR_BLOOM_SMALL_MAX_PIXELS", 40000)) {
+        // four lanes per pixel where a level is too small to fill the chip and goes through the general sampler (PBR_BLOOM_SMALL_MAX_PIXELS)
+        kernel = a->upsample ? k_bloom_small<true> : k_bloom_small<false>; grid.y = rows;
+    } else kernel = a->upsample ? k_bloom_pass<true> : k_bloom_pass<false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, p);
+    return launched();
 }
 
 extern "C" __attribute__((visibility("hidden"))) int pbrk_debug_sample_post(const void* texture, int w, int h, const void* coords, int count, void* out, void* stream) {
     PbrkTex2D t; t.data = texture; t.format = PBRK_FMT_RGBA16F; t.width = w; t.height = h;
     hipLaunchKernelGGL(k_debug_sample_post, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, t, (const float*)coords, count, (float4*)out);
-    return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
+    return launched();
 }

@@ -49,6 +49,7 @@ __device__ __forceinline__ int cells_level_off(int W, int first, int level) {
 
 // the pieces of the 3-D / 2-D snapped samplers that K5 (grid_sample, prev_level_sample) and K16 (k_gridview.hip, the channel-split
 // form of grid_sample) share
+// (split_axis in k_post.hip is the same arithmetic with another clamp instruction, for K8 - K11)
 __device__ __forceinline__ void snap_split(float coord01, int extent, int& i0, int& i1, float& a) {
     float f = coord01 * (float)extent - 0.5f;
     f = floorf(f * 256.0f + 0.5f) * (1.0f / 256.0f);

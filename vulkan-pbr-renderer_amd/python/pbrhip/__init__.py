@@ -103,6 +103,11 @@ class PbrkFinalArgs(C.Structure):
                 ("y0", C.c_int), ("y1", C.c_int)]
 
 
+class PbrkBloomArgs(C.Structure):
+    _fields_ = [("src", PbrkTex2D), ("dst", C.c_void_p), ("dst_width", C.c_int), ("dst_height", C.c_int), ("dst_mip_level", C.c_int),
+                ("upsample", C.c_int), ("blend_additive", C.c_int), ("y0", C.c_int), ("y1", C.c_int), ("blend_src", C.c_void_p)]
+
+
 Shade_IBL, Shade_LightShafts, Shade_SunShadows, Shade_VoxelGI = 1, 2, 4, 8
 PBRK_FMT_RG16F, PBRK_FMT_RG32F, PBRK_FMT_RGBA16F, PBRK_FMT_RGBA32F, PBRK_FMT_R32F, PBRK_FMT_RGBA8UN, PBRK_FMT_BGRA8UN = 1, 2, 3, 4, 5, 6, 7
 
