@@ -172,6 +172,12 @@ int pbrk_mc_launch_cut_stats(int* out6);
  * level's output size reaches the measured threshold, 0 never, 1 wherever the shape allows it.  Every other level keeps 16 x 16 x 4.
  * The two tiles add a texel's samples in different orders: close, not the same bytes.  Tests and A-B runs. */
 void pbrk_mc_set_tile32(int mode);
+/* half_n folded into the frame rows of the region kernel's run loop (k_mc_region.hip, 2j) on levels whose edge is a power of two: one
+ * multiply less per proved sample.  Default 1; bit-identical either way; every other level keeps the multiply whatever the switch
+ * says.  Tests and A-B runs. */
+void pbrk_mc_set_fold(int on);
+/* 1 when the last region-kernel launch ran a folded instantiation, else 0 */
+int pbrk_mc_last_fold(void);
 
 /* ---- K5: deferred shade pass (shaders/lighting_pass.glsl:432-716, in-scope sub-blocks). */
 typedef struct PbrkShadeArgs {

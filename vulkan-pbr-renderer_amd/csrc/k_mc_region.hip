@@ -87,6 +87,33 @@
 //      3 catches it).  Measured (profiles/r10_certain_g1.md): C4 mip 2 24.45 -> 23.65 ms, mip 3 11.67 -> 11.09 ms, the job 50.2 -> 48.9 ms.
 //      The 18^2 shape (mip 4) LOSES with the run loop (3.71 -> 4.11 ms: 78 % proved, runs of three or four samples): it keeps the
 //      round-3 pass and has no RUNS instantiation.  A table of more than 64 words per slice would take the round-3 pass (launch_runs).
+//   2j. (round 11, half_n folded into the frame rows; FOLD) a sample body forms (sc, tc, ma) = Pframe e, h = rcp(ma) half_n and the tap
+//      coordinates u = fma(sc, h, off), v = fma(tc, h, off).  Lemma: when half_n = 2^k (n_src a power of two), multiplying the six
+//      entries of the sc and tc rows of Pframe by half_n, once per (region, pass), gives sc' = 2^k sc and tc' = 2^k tc bit for bit --
+//      every product and every FMA of to_face's chain is the earlier one times 2^k, and rounding to nearest commutes with a power of
+//      two -- and fma(sc', rcp(ma), off) rounds the same exact number as fma(sc, rcp(ma) 2^k, off): the same u, v, taps, weights and
+//      sums.  The proved body (certain_sample) loses its multiply: 36 VALU instead of 37.  The tested body (lane_sample) compares the
+//      scaled coordinates with ma_s = ma half_n (exact): ma_s > |sc'| is ma > |sc|, so the in-face decisions, and with them the
+//      partition of the directions among the faces, stay; its multiply has only moved (44 / 40 VALU as before).  Condition: no
+//      non-zero intermediate is subnormal and nothing overflows.  The rows are components of unit vectors and the table entries
+//      components of unit directions, each 0 or at least ~1e-8 in magnitude, so no non-zero product comes near 2^-126, and 2^k <= 512
+//      is far from overflow.  A violation could change at most a term of subnormal size in sc or tc, which no comparison and no
+//      tap can see: it is far below half an ulp of any sum it enters.  When n_src is NO power of two the scaled rows are rounded,
+//      sc' is no longer half_n sc, and two neighbouring faces would compare differently rounded copies of what are today the same
+//      three numbers, permuted: their in-face tests would stop being one partition of the directions, and step 3 would heal
+//      wave-slices.  Such levels keep the multiply: the fold is a compile-time flag of k_mc_region, instantiated for the four lean run
+//      loops (RUNS and LEAN: <66, true, 32>, <66, true, 16>, <66, false, 16>, <34, false, 16>) and chosen by the host from n_src alone
+//      (launch_runs: a row shard equals the full dispatch), under pbrk_mc_set_fold (default 1; pbrk_mc_last_fold tells what the last
+//      launch took).  FOLD = false is the machine code the instantiation had before.  heal_slice, binning and the direct kernel
+//      are untouched; the 18^2 shape has no proved body and no folded instantiation.  Measured (profiles/r11_fold.md): C4 mip 2 falls
+//      by 0.2 ms, mip 3 by 0.13, mip 1 by 0.05, the job by 0.4 ms (48.94 -> 48.53), in four sessions: under the 0.5 ms the round asked of a gain.
+//      Taking consecutive proved samples two at a time (one 32-byte scalar fetch, no bit search per sample) was built on top, LOST
+//      11-14 % on every shape and is not in the library: 5.5 SALU per sample instead of 9, but the LDS reads of a tap waited three times.
+//      That pointed at the waits: the four empty asm statements of tap_accumulate are four uses, and the compiler waits ahead of each
+//      use -- on the 66^2 shapes the reads go out two and two.  The folded instantiation of the 66^2 whole-face shape keeps the four
+//      texels alive with ONE statement (JOIN, MC_TAP_JOIN_G1): all four reads fly, one wait; same instructions and arithmetic.  Mip 2
+//      23.75 -> 22.99 ms, the job 48.94 -> 47.92 ms; the 34^2 shape (its loop already waits once) and the 18^2 shape lose with it, the
+//      quarter-face shape gains nothing: they keep the four statements.
 // Each (texel, sample) pair is accumulated exactly once, in an order (66^2 shapes: head phase then tail phase; in each, own face's
 // regions, then the other regions in index order; else regions in index order; sample index inside a region) that depends on the
 // level's shape and the texel's face only, not on the tile: a row-sharded dispatch equals a full one bit for bit.
@@ -124,6 +151,12 @@ typedef const __attribute__((address_space(4))) unsigned* cu32_t;
 // (CERT in k_mc_region).  The 34^2 shape takes them; MC_CERT_G1 is the 66^2 whole-face shape: 0 keeps the machine code it had without.
 #ifndef MC_CERT_G1
 #define MC_CERT_G1 1
+#endif
+
+// Header 2j, decided per shape by measurement: the folded instantiation of the 66^2 whole-face shape keeps a tap's four texels alive with
+// one statement, so that their LDS reads wait once (tap_accumulate, JOIN).  0 keeps the two waits; the other shapes lose or gain nothing with it.
+#ifndef MC_TAP_JOIN_G1
+#define MC_TAP_JOIN_G1 1
 #endif
 
 // Header 2h: 32 x 32 tiles x 1 slice on the quarter-face shape where mc_tile32's rule holds.  0 keeps 16 x 16 x 4 and the parent's bytes
@@ -190,7 +223,10 @@ __device__ __forceinline__ void on_face(float sc, float tc, float ma, bool& c1, 
 
 // The bilinear tap at bordered coordinates (u, v) of the staged region, weight w folded in: THE chain of twelve FMAs every lemma of
 // this file speaks about (absorbed words, the launch cut, "a row shard equals the full dispatch"); every sample body ends in it.
-template <int RS>
+// JOIN (header, 2j): the four texels are kept alive by ONE statement.  Each empty asm is a use of its read, and the compiler waits for a
+// read ahead of its first use: four statements split the reads into two groups with a wait behind each, one statement lets all four
+// fly and waits once.  Same instructions otherwise, same arithmetic; taken where it measured as a gain (MC_TAP_JOIN_G1).
+template <int RS, bool JOIN = false>
 __device__ __forceinline__ void tap_accumulate(float w, float u, float v, unsigned lds_base, float& ar, float& ag, float& ab) {
     const int il = (int)u, jl = (int)v;
     const float a = __builtin_amdgcn_fractf(u), b = __builtin_amdgcn_fractf(v);
@@ -202,7 +238,8 @@ __device__ __forceinline__ void tap_accumulate(float w, float u, float v, unsign
     asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(addr) : "v"(jl), "s"(RS * 16), "v"(t16));
     lds_v4f_p tp = (lds_v4f_p)(unsigned long long)addr;
     v4f q00 = tp[0], q10 = tp[1], q01 = tp[RS], q11 = tp[RS + 1];
-    asm("" : "+v"(q00)); asm("" : "+v"(q10)); asm("" : "+v"(q01)); asm("" : "+v"(q11));
+    if (JOIN) asm("" : "+v"(q00), "+v"(q10), "+v"(q01), "+v"(q11));
+    else { asm("" : "+v"(q00)); asm("" : "+v"(q10)); asm("" : "+v"(q01)); asm("" : "+v"(q11)); }
     // weights of the four taps with the sample weight folded in
     const float wa = w * a;
     const float w11 = wa * b;
@@ -246,32 +283,35 @@ __device__ __forceinline__ void region_sample(const v4f e, const RegionView& V, 
 
 // The same sample when binning has proved that EVERY texel of the tile taps this region of this face: all 64 lanes are in, so
 // the tests, ballots and the exec mask fall away.
-template <int RS>
+// FOLD (header, 2j): the sc and tc rows of V carry half_n, so sc and tc arrive scaled and the reciprocal is taken as it is.
+template <int RS, bool FOLD = false, bool JOIN = false>
 __device__ __forceinline__ void certain_sample(const v4f e, const RegionView& V, float& ar, float& ag, float& ab) {
     float sc, tc, ma;
     to_face(e, V, sc, tc, ma);
-    const float h = __builtin_amdgcn_rcpf(ma) * V.half_n;
-    tap_accumulate<RS>(e.w, fmaf(sc, h, V.off), fmaf(tc, h, V.off), V.lds_base, ar, ag, ab);
+    const float h = FOLD ? __builtin_amdgcn_rcpf(ma) : __builtin_amdgcn_rcpf(ma) * V.half_n;
+    tap_accumulate<RS, JOIN>(e.w, fmaf(sc, h, V.off), fmaf(tc, h, V.off), V.lds_base, ar, ag, ab);
 }
 
 // ---- scalar-lean loop (round 5, 66^2 shapes) ----
 // The same sample as region_sample, counted PER LANE: cnt += 1 in the lanes that take it, under the exec mask the body runs with
 // anyway.  That drops the second ballot chain (one 4-way s_and_b64 chain for the count, another for the exec mask) and the
 // s_bcnt1; only the wave-uniform early exit of SUB keeps a ballot.
-template <int RS, bool SUB, int CLS, bool ACC = true>
+// FOLD (header, 2j): sc and tc arrive scaled by half_n; the in-face test compares them with ma half_n (exact: the same decisions), and
+// the multiply of the reciprocal has moved there.
+template <int RS, bool SUB, int CLS, bool ACC = true, bool FOLD = false, bool JOIN = false>
 __device__ __forceinline__ void lane_sample(const v4f e, const RegionView& V, float& ar, float& ag, float& ab, unsigned& cnt) {
     float sc, tc, ma;
     to_face(e, V, sc, tc, ma);
     bool c1, c2;
-    on_face<CLS>(sc, tc, ma, c1, c2);
+    on_face<CLS>(sc, tc, FOLD ? ma * V.half_n : ma, c1, c2);
     bool in = c1 && c2;
     if (SUB && __builtin_amdgcn_ballot_w64(in) == 0ull) return;    // no lane on the face: skip the projection
-    const float h = __builtin_amdgcn_rcpf(ma) * V.half_n;
+    const float h = FOLD ? __builtin_amdgcn_rcpf(ma) : __builtin_amdgcn_rcpf(ma) * V.half_n;
     const float u = fmaf(sc, h, V.off), v = fmaf(tc, h, V.off);
     if (SUB) in = in && u >= V.ulo && u < V.uhi && v >= V.vlo && v < V.vhi;
     if (in) {
         cnt += 1u;
-        if (ACC) tap_accumulate<RS>(e.w, u, v, V.lds_base, ar, ag, ab);
+        if (ACC) tap_accumulate<RS, JOIN>(e.w, u, v, V.lds_base, ar, ag, ab);
     }
 }
 
@@ -385,13 +425,15 @@ __device__ __forceinline__ void region_pass(const RegionView& V, const unsigned*
 //   * CERT: the proved samples below the next tested one run as a run of certain_sample (no per-sample proved-bit test, no exec
 //     join), then the tested one, in index order;
 //   * tested samples use lane_sample (one ballot chain), and every loop issues the next table entry's load ahead of the body.
-template <int RS, bool SUB, int CLS, int REG_S, bool CERT, bool LEAN>
+template <int RS, bool SUB, int CLS, int REG_S, bool CERT, bool LEAN, bool FOLD>
 __device__ __forceinline__ void region_pass_runs(const RegionView& V, const unsigned* __restrict__ mwords, const unsigned* __restrict__ cwords, cu32_t wmg,
                                                  unsigned rbits, unsigned* skc, int NW, int s, unsigned long long wsel, ctab_t tab,
                                                  float& ar, float& ag, float& ab, unsigned& cnt) {
     const int wl = s + REG_S * (int)(threadIdx.x & 63);
     unsigned long long nz = __builtin_amdgcn_ballot_w64(wl < NW && mwords[wl] != 0u) & wsel;
-    auto tested = [&](const v4f e) { lane_sample<RS, SUB, CLS>(e, V, ar, ag, ab, cnt); };
+    // header 2j: with the fold, the 66^2 whole-face shape also takes the tap whose four reads wait once (per shape, by measurement)
+    constexpr bool JOIN = FOLD && RS == 66 && !SUB && MC_TAP_JOIN_G1 != 0;
+    auto tested = [&](const v4f e) { lane_sample<RS, SUB, CLS, true, FOLD, JOIN>(e, V, ar, ag, ab, cnt); };
     while (nz) {
         const int w = s + REG_S * (int)__builtin_ctzll(nz);
         nz &= nz - 1ull;
@@ -405,7 +447,7 @@ __device__ __forceinline__ void region_pass_runs(const RegionView& V, const unsi
                 if (!CERT) c = (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[w]);
                 cnt += (unsigned)__builtin_popcount(m & c);                // every lane takes every proved sample
                 count_absorbed(skc, m, m & ~c);
-                each_sample(m & ~c, tw, [&](const v4f e) { lane_sample<RS, SUB, CLS, false>(e, V, ar, ag, ab, cnt); });
+                each_sample(m & ~c, tw, [&](const v4f e) { lane_sample<RS, SUB, CLS, false, FOLD>(e, V, ar, ag, ab, cnt); });
                 continue;
             }
         }
@@ -414,7 +456,7 @@ __device__ __forceinline__ void region_pass_runs(const RegionView& V, const unsi
         unsigned mc = m & c, mu = m & ~c;
         for (;;) {
             const unsigned below = mu ? (mu & (0u - mu)) - 1u : ~0u;     // the samples before the next tested one (all: none left)
-            each_sample(mc & below, tw, [&](const v4f e) { certain_sample<RS>(e, V, ar, ag, ab); });
+            each_sample(mc & below, tw, [&](const v4f e) { certain_sample<RS, FOLD, JOIN>(e, V, ar, ag, ab); });
             mc &= ~below;
             if (!mu) break;
             const int it = __builtin_ctz(mu);
@@ -674,10 +716,12 @@ __device__ __forceinline__ void reduce_slices(float* red, int s, int t, float ar
 
 // RUNS (66^2 shapes and the 34^2 shape): the region loop visits the flagged regions only and runs region_pass_runs (round 5; cnt per lane)
 // LEAN: the prologue of header 2f (pbrk_mc_set_prologue); false: the one before it, kept as the yardstick
+// FOLD (header, 2j; power-of-two levels under RUNS and LEAN): half_n rides in the sc and tc rows of the permuted frame
 // The body reads: frames, bin, credit, the loop of (stage, pass) over the flagged regions, check / heal, reduce / store.
-template <int RS, bool SUB, int TILE, bool RUNS = false, bool LEAN = false>
+template <int RS, bool SUB, int TILE, bool RUNS = false, bool LEAN = false, bool FOLD = false>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_mc_region(const RegArgs q) {
     constexpr int REG_TX = TILE * TILE, REG_S = 1024 / REG_TX;
+    static_assert(!FOLD || (RUNS && LEAN && RS != 18), "FOLD: the run loop of the lean 66^2 / 34^2 shapes only");
     // see the header, 2b and 2i: quarter faces always; whole faces only with the run loop, which pays no per-sample choice of body
     constexpr bool CERT = SUB || (RUNS && (RS != 66 || MC_CERT_G1 != 0));
     // see the header, 2c: compiled for the 66^2 region shapes only.  The 34^2 / 18^2 levels of C4 (mips 3, 4: weights fall to ~e^-6)
@@ -793,6 +837,10 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         face_coords(f, T.x, T.y, T.z, V.Pt.x, V.Pt.y, V.Pt.z);
         face_coords(f, R.x, R.y, R.z, V.Pr.x, V.Pr.y, V.Pr.z);
         V.half_n = half_n; V.off = off;
+        if (FOLD) {                                                // header 2j: six exact multiplies per staging for one per sample
+            V.Pb.x *= half_n; V.Pt.x *= half_n; V.Pr.x *= half_n;
+            V.Pb.y *= half_n; V.Pt.y *= half_n; V.Pr.y *= half_n;
+        }
         V.ulo = (float)ox; V.uhi = (float)(ox + rcx); V.vlo = (float)oy; V.vhi = (float)(oy + rcy);
         const unsigned* mw = masks + r * NW;
         unsigned* const sc = (ABS && q.stats) ? skc : nullptr;
@@ -801,7 +849,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         const int w0 = (TWO && ph) ? s + REG_S : s, w1 = (TWO && !ph) ? min(NW, s + 1) : NW;
         auto pass = [&](auto cls) {                                // cls: the face's major axis as a compile-time constant
             constexpr int CLS = decltype(cls)::value;
-            if (RUNS) region_pass_runs<RS, SUB, CLS, REG_S, CERT, LEAN>(V, mw, cmask, wmg, rbits, sc, NW, s, wsel, tab, ar, ag, ab, cnt);
+            if (RUNS) region_pass_runs<RS, SUB, CLS, REG_S, CERT, LEAN, FOLD>(V, mw, cmask, wmg, rbits, sc, NW, s, wsel, tab, ar, ag, ab, cnt);
             else region_pass<RS, SUB, CLS, REG_S, CERT, LEAN>(V, mw, cmask, wmg, rbits, sc, NW, w0, w1, tab, ar, ag, ab, cnt);
         };
         switch (f >> 1) {
@@ -888,11 +936,13 @@ extern "C" int pbrk_mc_region_window_stats(unsigned long long* out1) { return re
 extern "C" int pbrk_mc_region_flag_stats(unsigned long long* out3) { return read_stats(out3, 2, 3); }
 extern "C" int pbrk_mc_region_phase_stats(unsigned long long* out5) { return read_stats(out5, 9, 5); }       // PBR_MC_PHASE_STAMPS builds; zeros otherwise (RegArgs::stats [9..13])
 
-template <int RS, bool SUB, int TILE, bool RUNS = false, bool LEAN = false>
+static int g_last_fold = 0;                            // whether the last region launch took a FOLD instantiation (pbrk_mc_last_fold)
+template <int RS, bool SUB, int TILE, bool RUNS = false, bool LEAN = false, bool FOLD = false>
 static void launch_region_t(const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
     static bool attr_set = false;
-    if (!attr_set) { (void)hipFuncSetAttribute((const void*)k_mc_region<RS, SUB, TILE, RUNS, LEAN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
-    hipLaunchKernelGGL((k_mc_region<RS, SUB, TILE, RUNS, LEAN>), dim3(grid), dim3(1024), lds, st, q);
+    if (!attr_set) { (void)hipFuncSetAttribute((const void*)k_mc_region<RS, SUB, TILE, RUNS, LEAN, FOLD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
+    g_last_fold = FOLD ? 1 : 0;
+    hipLaunchKernelGGL((k_mc_region<RS, SUB, TILE, RUNS, LEAN, FOLD>), dim3(grid), dim3(1024), lds, st, q);
 }
 
 // ---- the launch's maxima (header, 2f) ----
@@ -1035,6 +1085,11 @@ extern "C" void pbrk_mc_set_launch_cut(int on) { g_mc_launch_cut = on ? 1 : 0; }
 // (quarter faces, NW <= 64) whatever the output size.  The tile changes the order of a texel's sum: not the same bytes as 16 x 16 x 4.
 static int g_mc_tile32 = -1;
 extern "C" void pbrk_mc_set_tile32(int mode) { g_mc_tile32 = mode < 0 ? -1 : (mode ? 1 : 0); }
+// half_n folded into the frame rows on power-of-two levels (header 2j; tests / A-B runs; the outputs are the same bit for bit either way)
+static int g_mc_fold = 1;
+extern "C" void pbrk_mc_set_fold(int on) { g_mc_fold = on ? 1 : 0; }
+// 1 when the last region-kernel launch ran a FOLD instantiation, else 0 (also before the first launch)
+extern "C" int pbrk_mc_last_fold(void) { return g_last_fold; }
 // The cut of the last region-kernel launch, for tests and probes: out6 = the first cut word of slices 0 .. 3, NW, words cut.  A launch
 // without a cut reports 0 words.  A launch of S < 4 slices reports slice j % S in entry j (one slice: its first cut word four times);
 // the words cut are counted over the launch's S slices.  Waits for the device.
@@ -1059,7 +1114,15 @@ extern "C" int pbrk_mc_launch_cut_stats(int* out6) {
 template <int RS, bool SUB, int TILE, bool LEAN, bool HAS_RUNS = true>
 static void launch_runs(const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
     if constexpr (HAS_RUNS) {
-        if (g_mc_runs && q.NW <= 64 * (1024 / (TILE * TILE))) { launch_region_t<RS, SUB, TILE, true, LEAN>(q, grid, lds, st); return; }
+        if (g_mc_runs && q.NW <= 64 * (1024 / (TILE * TILE))) {
+            // header 2j: a rule of the level alone (n_src), so a row shard equals the full dispatch; only the lean run loop has the instantiation
+            if constexpr (LEAN) {
+                const int n = q.a.n_src;
+                if (g_mc_fold && (n & (n - 1)) == 0) { launch_region_t<RS, SUB, TILE, true, true, true>(q, grid, lds, st); return; }
+            }
+            launch_region_t<RS, SUB, TILE, true, LEAN>(q, grid, lds, st);
+            return;
+        }
     }
     launch_region_t<RS, SUB, TILE, false, LEAN>(q, grid, lds, st);
 }
