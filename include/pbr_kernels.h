@@ -217,6 +217,7 @@ int pbrk_shade(const PbrkShadeArgs* args, void* stream);
  * pixel workgroups, every tap through range-checked buffer loads of the cells twins; the default for the modes without sun
  * shadows / voxel GI when the twins exist).  Both agree with the oracle at the same tolerance; they are not bit-identical. */
 void pbrk_shade_set_fast(int on);                        /* 0: every mode through the general kernel k_shade (env PBR_SHADE_FAST); -1 = default */
+int  pbrk_shade_last_kernel(void);                       /* instantiation of the most recent successful pbrk_shade: 0 general, 1 fast, 2 GI (-1: none yet) */
 /* LUT twin for K5: one 16-byte load per bilinear LUT fetch */
 int pbrk_lut_cells_build(const void* lut_half2, int size, void* cells_out, void* stream);
 

@@ -511,6 +511,8 @@ extern "C" int pbrk_debug_sample(int which, const void* texture, int w, int h, i
 
 static int g_fast_mode = -1;                    // -1: PBR_SHADE_FAST or the default (1)
 extern "C" void pbrk_shade_set_fast(int on) { g_fast_mode = on; }
+static int g_last_kernel = -1;                  // instantiation of the most recent successful pbrk_shade: 0 general, 1 fast, 2 GI
+extern "C" int pbrk_shade_last_kernel(void) { return g_last_kernel; }
 
 extern "C" int pbrk_shade(const PbrkShadeArgs* a, void* stream) {
     if (!a || a->width < 1 || a->height < 1) return PBRK_E_ARG;
@@ -562,9 +564,13 @@ extern "C" int pbrk_shade(const PbrkShadeArgs* a, void* stream) {
         size_t cb = 0;
         for (int l = 0; l < a->prefiltered_levels; ++l) { int n = a->prefiltered_size >> l; if (n < 1) n = 1; cb += pbrk_cells_bytes(n); }
         p.pre_cells_bytes = (int)cb;
-        return launch_shade_fast(p, (a->flags & PBRK_SHADE_IBL) != 0, (a->flags & PBRK_SHADE_SHAFTS) != 0, (hipStream_t)stream);
+        const int rc = launch_shade_fast(p, (a->flags & PBRK_SHADE_IBL) != 0, (a->flags & PBRK_SHADE_SHAFTS) != 0, (hipStream_t)stream);
+        if (rc == PBRK_OK) g_last_kernel = 1;
+        return rc;
     }
     if (a->flags & PBRK_SHADE_GI) hipLaunchKernelGGL(k_shade<true>, dim3((p.w + 31) / 32, (p.h + 7) / 8), dim3(256), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(k_shade<false>, dim3((p.w + 63) / 64, (p.h + 3) / 4), dim3(256), 0, (hipStream_t)stream, p);
-    return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
+    if (hipGetLastError() != hipSuccess) return PBRK_E_LAUNCH;
+    g_last_kernel = (a->flags & PBRK_SHADE_GI) ? 2 : 0;
+    return PBRK_OK;
 }
