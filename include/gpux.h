@@ -106,6 +106,14 @@ GPU_API float GPUX_GraphSpanMs(GPU_Graph* graph);
  * between a fork and a join event; anything else executes in recording order on the graph's stream.  0 or 1 turns it off,
  * a negative count restores the default (environment PBR_TILE_STREAMS, else 4).  Results do not depend on the setting. ---- */
 GPU_API void GPUX_SetTileStreams(int count);
+/* ---- whole levels side by side: a run of at least two consecutive K3/K4 dispatches of whole levels (GPUX_OpDispatchRows over every
+ * row, or GPU_OpDispatch) that pass the same independence check runs as one region, largest dispatch first, each on the least loaded
+ * of `count` streams, the graph's own among them (2 .. the GPUX_SetTileStreams value; below 2: the default, 2).  on = 0: whole levels stay a serial chain.
+ * GPUX_SetTileStreams(0 or 1) turns this off too.  GPUX_LevelOverlapCount: dispatches the last submission placed this way.  Inside
+ * a region a timed op's figure is its span beside its neighbours; GPUX_GraphSpanMs is the job's.  Results do not depend on any of it. ---- */
+GPU_API void GPUX_SetLevelOverlap(int on);
+GPU_API void GPUX_SetLevelStreams(int count);
+GPU_API uint32_t GPUX_LevelOverlapCount(void);
 
 /* ---- hipGraph replay of the per-frame chain: with replay on, GPU_GraphSubmit captures the launches of a graph whose ops are all
  * launch-only (light-grid sweep, draws of the shade / TAA / bloom / tone-map pipelines, blits, memset clears, mip generation) and

@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <string>
 #include <vector>
@@ -205,10 +206,13 @@ static struct {
     int overlap = -1;                               // GPUX_SetGraphOverlap, PBR_GRAPH_OVERLAP or 1: head / tail overlap of frames in flight
     int replay = -1;                                // GPUX_SetGraphReplay, PBR_GRAPH_REPLAY or 0: submissions go through an instantiated hipGraph
     int tile_streams = -1;                          // GPUX_SetTileStreams, PBR_TILE_STREAMS or 4: side streams for small independent precompute dispatches
+    int level_overlap = 1;                          // GPUX_SetLevelOverlap: independent whole levels of a submission run side by side (TileRegion)
+    int level_streams = -1;                         // GPUX_SetLevelStreams, or kLevelStreams: the streams they are spread over
     unsigned long long* raster_rejected = nullptr;  // device counters: [0] GPUX_RasterRejectedTriangles, [1] GPUX_VoxelizeFragments
     uint64_t raster_rejected_base = 0;              // what earlier GPU_Init .. GPU_Deinit spans counted
 } G;
 
+static const int kLevelStreams = 2;                 // the only count that gained on all three bench workloads: profiles/level_streams.md
 static const char kTokenLut[] = "HIPK1:gen_brdf_integration_map";
 static const char kTokenIrr[] = "HIPK3:gen_irradiance_map";
 static const char kTokenPre[] = "HIPK4:gen_prefiltered_env_map";
@@ -1880,6 +1884,32 @@ static IblPlan plan_ibl(const Op& op) {
     return p;
 }
 
+// The level of `et` a launchable plan samples; -1 for a fractional LOD inside the chain, which the precompute kernels do not take
+static int ibl_source_level(const TextureImpl* et, const IblPlan& p) {
+    const int levels = (int)et->base.mip_level_count;
+    int l = (int)floorf(p.lod);
+    if (l < 0) l = 0;
+    if (l > levels - 1) l = levels - 1;                     // sampler clamps LOD to the chain
+    return ((float)l != p.lod && p.lod < (float)(levels - 1)) ? -1 : l;
+}
+
+// The twins a precompute dispatch samples -- the apron from level l on and, unless it is the copy, the cells of level l -- built on
+// g->cur where they are missing, and published.  False: the apron could not be built (reported).
+static bool ensure_ibl_twins(GPU_Graph* g, TextureImpl* et, int l, bool want_cells, size_t& ev_used) {
+    hipStream_t st = g->cur;
+    if (!et->bordered_valid || et->bordered_from > l) {
+        timed(g, "apron.env", ev_used, [&] { ensure_bordered(et, st, l); });
+        if (!et->bordered_valid || et->bordered_from > l) return false;
+        publish_side_work(g);
+    }
+    if (want_cells && !cells_ready(et, l)) {
+        const void* built = nullptr;
+        timed(g, "cells.env", ev_used, [&] { built = ensure_cells(et, l, st); });
+        if (built) publish_side_work(g);                    // a level too big for a cells twin enqueues nothing
+    }
+    return true;
+}
+
 static void exec_ibl_filter(GPU_Graph* g, Op& op, size_t& ev_used) {
     hipStream_t st = g->cur;
     Slot* out = named_slot(op.set, "OUTPUT");
@@ -1887,27 +1917,17 @@ static void exec_ibl_filter(GPU_Graph* g, Op& op, size_t& ev_used) {
     uint32_t size = mip_dim(ot->base.width, out->mip);
     void* out_ptr = (char*)ot->dev + ot->mip_offset[out->mip];
     TextureImpl* et = named_slot(op.set, "TEX_ENV_CUBE")->tex;
-    int W = (int)et->base.width, levels = (int)et->base.mip_level_count;
+    int W = (int)et->base.width;
     const IblPlan p = plan_ibl(op);
     if (p.bad_roughness) { gpu_fail("prefilter: roughness must be > 0 for Monte-Carlo mips (got %g)", p.rough); return; }
     if (!p.ok) return;
     const bool mc_prefilter = op.cpipe->kernel == Kernel_Prefilter && !p.copy;
-    int l = (int)floorf(p.lod);
-    if (l < 0) l = 0;
-    if (l > levels - 1) l = levels - 1;                     // sampler clamps LOD to the chain
-    if ((float)l != p.lod && p.lod < (float)(levels - 1)) { gpu_fail("%s: fractional source LOD %g is not supported by the precompute kernels", p.name, p.lod); return; }
-    if (!et->bordered_valid || et->bordered_from > l) {
-        timed(g, "apron.env", ev_used, [&] { ensure_bordered(et, st, l); });
-        if (!et->bordered_valid || et->bordered_from > l) return;
-        publish_side_work(g);
-    }
+    const int l = ibl_source_level(et, p);
+    if (l < 0) { gpu_fail("%s: fractional source LOD %g is not supported by the precompute kernels", p.name, p.lod); return; }
+    if (!ensure_ibl_twins(g, et, l, !p.copy, ev_used)) return;
     int n_src = W >> l; if (n_src < 1) n_src = 1;
     const void* src = (const char*)et->bordered + pbrk_bordered_level_offset(W, l) * 16;
-    const void* cells = nullptr;
-    if (!p.copy) {
-        if (cells_ready(et, l)) cells = ensure_cells(et, l, st);
-        else { timed(g, "cells.env", ev_used, [&] { cells = ensure_cells(et, l, st); }); publish_side_work(g); }
-    }
+    const void* cells = p.copy ? nullptr : ensure_cells(et, l, st);          // built by now: the pointer (NULL: the level has no cells twin)
     int n_keep = p.tab ? p.tab->count : 0;
     if (mc_prefilter && G.prefilter_tol > 0.0f) {            // opt-in: tolerance-budgeted sample cut (gpux.h)
         float mn = 0.0f, mx = 0.0f;
@@ -1930,6 +1950,14 @@ static double dispatch_samples_per_texel(const Op& op) {
     if (op.cpipe->kernel == Kernel_Irradiance) return p.n;
     if (p.copy) return 4.0;                                                 // the copy level: one bilinear fetch, HBM-bound
     return p.tab ? (double)p.tab->count : (double)p.n;
+}
+
+// Builds a precompute dispatch's twins ahead of its launch (on g->cur); a dispatch that cannot be launched is left to exec_ibl_filter.
+static void prepare_ibl_twins(GPU_Graph* g, const Op& op, size_t& ev_used) {
+    TextureImpl* et = named_slot(op.set, "TEX_ENV_CUBE")->tex;
+    const IblPlan p = plan_ibl(op);
+    const int l = p.ok ? ibl_source_level(et, p) : -1;
+    if (l >= 0) ensure_ibl_twins(g, et, l, !p.copy, ev_used);
 }
 
 static void exec_bloom(GPU_Graph* g, Op& op, size_t& ev_used) {
@@ -2460,74 +2488,144 @@ static size_t split_head_tail(GPU_Graph* g, bool overlap_on) {
     return mid_idx;
 }
 
-// Row-ranged precompute dispatches (the work units of a partitioned job) are too small to keep 256 CUs x 8 waves busy one
-// at a time: consecutive ones whose outputs are disjoint and which do not read each other's output go round-robin onto
-// side streams, fenced by a fork event before the first and join events after the last.  Everything else stays in order.
+// Precompute dispatches (K3, K4a, K4b) that do not depend on each other run side by side on side streams, fenced by one fork event
+// before the first and one join event per stream after the last.  Independent means: outputs disjoint by (texture, mip, faces, rows),
+// and no dispatch samples a texture another dispatch of the region writes.  Everything else stays in recording order.
+// Two kinds of region:
+//   shares -- row-ranged dispatches of less than a whole level (the work units of a partitioned job) are too small to keep 256 CUs x 8
+//     waves busy one at a time: consecutive ones go round-robin onto all side streams as they come.  A whole level that follows joins
+//     the open region.
+//   whole levels -- a job on one GPU is a chain of whole levels (GPUX_OpDispatchRows over every row, or GPU_OpDispatch), none of which
+//     reads another, yet in a chain each waits for the last workgroup of the one before: the small levels leave most of the chip idle
+//     and every big launch ends in a ragged round.  A run of at least two independent whole levels is taken as one region
+//     (level_run): their twins are built ahead of the fork, the dispatches are sorted by cost (samples per texel x texels) and each
+//     goes, largest first, onto the least loaded of `n_level` streams: the graph's own and n_level - 1 side streams, so that two
+//     streams cost one fork wait and one join: 0.012 ms, measured as the span of a job of two tiny levels with the overlap on
+//     against off (profiles/level_streams.md, where the stream count is measured too).
+//     GPUX_SetLevelOverlap(0) keeps whole levels in their chain; GPUX_LevelOverlapCount counts the dispatches placed this way.
+// Timing: an op's event pair is recorded on the stream it runs on, so inside a region its time is its span BESIDE its neighbours, and
+// the sum of the ops exceeds the job: GPUX_GraphSpanMs is the job's figure.  For per-kernel times, profile with the overlap off.
+static uint32_t g_level_overlap_count = 0;
 struct TileRegion {
     struct Wr { TextureImpl* t; uint32_t mip, f0, f1, r0, r1; };
     GPU_Graph* g;
-    int n_side;
+    int n_side, n_level;
     std::vector<Wr> writes; std::vector<TextureImpl*> reads;       // what the dispatches of the open region write and read
-    bool open = false; size_t rr = 0;
+    bool open = false; size_t rr = 0, n_open = 0;                  // n_open: side streams the open region forked
 
     explicit TileRegion(GPU_Graph* graph) : g(graph) {
         env_setting(G.tile_streams, "PBR_TILE_STREAMS", 4);
         if (G.tile_streams > 16) G.tile_streams = 16;
         n_side = G.tile_streams;
+        n_level = !G.level_overlap ? 0 : (G.level_streams < 2 ? kLevelStreams : G.level_streams);
+        if (n_level > n_side) n_level = n_side;
+    }
+    void fork(size_t n) {
+        while ((int)g->side.size() > n_side) { (void)hipStreamSynchronize(g->side.back()); (void)hipStreamDestroy(g->side.back()); g->side.pop_back(); }
+        while ((int)g->side.size() < n_side) { hipStream_t s; HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); g->side.push_back(s); }
+        hipEvent_t e = next_sync_event(g);
+        HIP_OK(hipEventRecord(e, g->stream));
+        for (size_t s = 0; s < n; ++s) HIP_OK(hipStreamWaitEvent(g->side[s], e, 0));
+        open = true; n_open = n;
     }
     // join: the main stream goes on after everything the side streams hold
     void close() {
         if (!open) return;
-        for (hipStream_t s : g->side) { hipEvent_t e = next_sync_event(g); HIP_OK(hipEventRecord(e, s)); HIP_OK(hipStreamWaitEvent(g->stream, e, 0)); }
+        for (size_t s = 0; s < n_open; ++s) { hipEvent_t e = next_sync_event(g); HIP_OK(hipEventRecord(e, g->side[s])); HIP_OK(hipStreamWaitEvent(g->stream, e, 0)); }
         writes.clear(); reads.clear(); open = false; g->cur = g->stream;
     }
-    // is the op a dispatch that may run beside its neighbours?
-    bool wants_side_stream(const Op& op, Slot*& out, Slot*& env) const {
-        out = env = nullptr;
-        if (!(n_side >= 2 && op.kind == Op_Dispatch && op.rows_explicit && (op.cpipe->kernel == Kernel_Prefilter || op.cpipe->kernel == Kernel_Irradiance))) return false;
+    // is the op a K3 / K4 dispatch with an output and a source?  `whole`: it covers every face and row of its level
+    static bool ibl_dispatch(const Op& op, Slot*& out, Slot*& env, bool& whole) {
+        out = env = nullptr; whole = false;
+        if (!(op.kind == Op_Dispatch && (op.cpipe->kernel == Kernel_Prefilter || op.cpipe->kernel == Kernel_Irradiance))) return false;
         out = named_slot(op.set, "OUTPUT");
         env = named_slot(op.set, "TEX_ENV_CUBE");
-        bool tile = true;
-        // a launch of several full-chip rounds (2048 resident workgroups x 256 texels x 8192 samples each) gains nothing from
-        // company and keeps its own event timing clean: only smaller ones are overlapped
-        // (a whole level fills the chip by itself from ~1e9 evaluations on; shares of a level -- a rank's tiles -- come in
-        // groups with ragged tails and gain up to the bound above)
-        if (out && out->tex) {
-            uint32_t size = mip_dim(out->tex->base.width, out->mip);
-            double evals = (double)(op.face1 - op.face0) * (op.row1 - op.row0) * size * dispatch_samples_per_texel(op);
-            bool whole = op.face0 == 0 && op.face1 == out->tex->base.layer_count && op.row0 == 0 && op.row1 == size;
-            if (evals >= (whole ? 1.0e9 : 2.0e6 * 8192.0)) tile = false;
-            // fork + join cost ~0.25 ms of cross-stream signalling: whole small levels alone (the tail of a single-GPU job) do not
-            // repay it -- they join a region that shares of a level have opened, but do not open one
-            if (whole && !open) tile = false;
-        }
-        return tile && out && env && out->tex && env->tex;
+        if (!(out && env && out->tex && env->tex)) return false;
+        whole = op.face0 == 0 && op.face1 == out->tex->base.layer_count && op.row0 == 0 && op.row1 == mip_dim(out->tex->base.width, out->mip);
+        return true;
     }
-    // Picks the stream the op launches on (g->cur): a side stream of the region (true) -- opening one, or closing it first when the op
-    // clashes with what the region holds -- or, behind a closed region, the main stream (false).  The caller sets g->cur back.
-    bool place(const Op& op) {
-        Slot* out; Slot* env;
-        if (!wants_side_stream(op, out, env)) { close(); return false; }
-        Wr w = {out->tex, out->mip, op.face0, op.face1, op.row0, op.row1};
-        bool clash = w.t == env->tex;
+    static double evaluations(const Op& op, const Slot* out) {
+        return (double)(op.face1 - op.face0) * (op.row1 - op.row0) * mip_dim(out->tex->base.width, out->mip) * dispatch_samples_per_texel(op);
+    }
+    // does a dispatch that writes `w` and samples `env` depend on, or feed, what the region holds?
+    bool clashes(const Wr& w, const TextureImpl* env) const {
+        bool clash = w.t == env;
         for (const Wr& o : writes) {
-            if (o.t == env->tex) clash = true;
+            if (o.t == env) clash = true;
             if (o.t == w.t && o.mip == w.mip && o.f0 < w.f1 && w.f0 < o.f1 && o.r0 < w.r1 && w.r0 < o.r1) clash = true;
         }
         for (TextureImpl* r : reads) if (r == w.t) clash = true;
-        if (clash) close();
-        if (w.t == env->tex) return false;                                 // reads what it writes: never overlapped
-        if (!open) {                                                       // fork
-            while ((int)g->side.size() > n_side) { (void)hipStreamSynchronize(g->side.back()); (void)hipStreamDestroy(g->side.back()); g->side.pop_back(); }
-            while ((int)g->side.size() < n_side) { hipStream_t s; HIP_OK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); g->side.push_back(s); }
-            hipEvent_t e = next_sync_event(g);
-            HIP_OK(hipEventRecord(e, g->stream));
-            for (hipStream_t s : g->side) HIP_OK(hipStreamWaitEvent(s, e, 0));
-            open = true;
-        }
+        return clash;
+    }
+    // Picks the stream the op launches on (g->cur): a side stream of the shares region (true) -- opening one, or closing it first when
+    // the op clashes with what the region holds -- or, behind a closed region, the main stream (false).  The caller sets g->cur back.
+    bool place(const Op& op) {
+        Slot* out; Slot* env; bool whole;
+        // a share of several full-chip rounds (2048 resident workgroups x 256 texels x 8192 samples each) gains nothing from company
+        // and keeps its own event timing clean: only smaller ones are overlapped; a whole level does not open a region by itself
+        bool tile = n_side >= 2 && ibl_dispatch(op, out, env, whole) && (whole ? open : op.rows_explicit && evaluations(op, out) < 2.0e6 * 8192.0);
+        if (!tile) { close(); return false; }
+        Wr w = {out->tex, out->mip, op.face0, op.face1, op.row0, op.row1};
+        if (clashes(w, env->tex)) close();
+        if (w.t == env->tex || (whole && !open)) return false;             // reads what it writes: never overlapped; a whole level opens none
+        if (!open) fork((size_t)n_side);
         writes.push_back(w); reads.push_back(env->tex);
         g->cur = g->side[rr++ % g->side.size()];
         return true;
+    }
+    // With no region open: the end of the run of independent whole levels that starts at op i and stays below `limit`, when it
+    // holds at least two (one fork and one join are paid per region, not per dispatch); i otherwise.
+    size_t level_run(size_t i, size_t limit) {
+        if (open || n_level < 2) return i;
+        size_t j = i;
+        for (; j < limit; ++j) {
+            const Op& op = g->ops[j];
+            Slot* out; Slot* env; bool whole;
+            if (!ibl_dispatch(op, out, env, whole) || !whole) break;
+            Wr w = {out->tex, out->mip, op.face0, op.face1, op.row0, op.row1};
+            if (clashes(w, env->tex)) break;
+            writes.push_back(w); reads.push_back(env->tex);
+        }
+        writes.clear(); reads.clear();
+        return j - i >= 2 ? j : i;
+    }
+    // Runs ops [i, j), a run level_run found, as one region.  The twins they sample are built first, in recording order on the main
+    // stream: the fork publishes them to every stream, and no stream waits for another inside the region.
+    void run_levels(size_t i, size_t j, size_t& ev_used) {
+        typedef std::pair<size_t, size_t> Range;                            // timed entries [first, second) of g->timed_names
+        const size_t base = g->timed_names.size();
+        std::vector<Range> twins(j - i), launch(j - i);
+        std::vector<std::pair<double, size_t>> by_cost;
+        for (size_t k = i; k < j; ++k) {
+            Slot* out; Slot* env; bool whole;
+            ibl_dispatch(g->ops[k], out, env, whole);
+            twins[k - i].first = g->timed_names.size();
+            prepare_ibl_twins(g, g->ops[k], ev_used);
+            twins[k - i].second = g->timed_names.size();
+            by_cost.push_back({evaluations(g->ops[k], out), k});
+        }
+        std::stable_sort(by_cost.begin(), by_cost.end(), [](const std::pair<double, size_t>& a, const std::pair<double, size_t>& b) { return a.first > b.first; });
+        std::vector<double> load(std::min((size_t)n_level, j - i), 0.0);   // [0]: the graph's own stream, which needs no fork and no join
+        fork(load.size() - 1);
+        for (const std::pair<double, size_t>& c : by_cost) {
+            const size_t s = (size_t)(std::min_element(load.begin(), load.end()) - load.begin());
+            load[s] += c.first;
+            g->cur = s ? g->side[s - 1] : g->stream;
+            launch[c.second - i].first = g->timed_names.size();
+            exec_op(g, g->ops[c.second], ev_used);
+            launch[c.second - i].second = g->timed_names.size();
+        }
+        g_level_overlap_count += (uint32_t)(j - i);
+        close();
+        // The timed ops are reported in recording order, each behind the twins it had built, as in a serial chain: entry e owns the
+        // events g->ev[2e] and g->ev[2e + 1] (timed), so names and event pairs are permuted together.
+        if (g->timed_names.size() == base) return;
+        std::vector<std::string> names; std::vector<hipEvent_t> evs;
+        for (size_t k = 0; k < j - i; ++k)
+            for (const Range& r : {twins[k], launch[k]})
+                for (size_t e = r.first; e < r.second; ++e) { names.push_back(g->timed_names[e]); evs.push_back(g->ev[2 * e]); evs.push_back(g->ev[2 * e + 1]); }
+        std::copy(names.begin(), names.end(), g->timed_names.begin() + (ptrdiff_t)base);
+        std::copy(evs.begin(), evs.end(), g->ev.begin() + (ptrdiff_t)(2 * base));
     }
 };
 
@@ -2584,6 +2682,7 @@ GPU_API void GPU_GraphSubmit(GPU_Graph* g) {
     }
     const bool capture = begin_capture(g);
     TileRegion region(g);
+    g_level_overlap_count = 0;
     for (size_t i = 0; i < g->ops.size(); ++i) {
         if (order.prev && i == order.before) {                         // from here on: after everything the previous graph enqueued
             region.close();
@@ -2596,6 +2695,9 @@ GPU_API void GPU_GraphSubmit(GPU_Graph* g) {
             HIP_OK(hipEventRecord(g->mid_ev, g->stream));
             g->mid_recorded = true;
         }
+        // a run of whole levels stays on one side of the previous graph's end (it has none of this graph's bloom draws in it)
+        const size_t run_end = region.level_run(i, order.prev && i < order.before ? order.before : g->ops.size());
+        if (run_end > i) { region.run_levels(i, run_end, ev_used); i = run_end - 1; continue; }
         region.place(g->ops[i]);
         exec_op(g, g->ops[i], ev_used);
         g->cur = g->stream;
@@ -2623,6 +2725,9 @@ GPU_API void GPU_GraphWait(GPU_Graph* g) {
 
 GPU_API void GPUX_EnableOpTiming(int enable) { G.timing = enable != 0; }
 GPU_API void GPUX_SetTileStreams(int count) { G.tile_streams = count < 0 ? -1 : count; }
+GPU_API void GPUX_SetLevelOverlap(int on) { G.level_overlap = on != 0; }
+GPU_API void GPUX_SetLevelStreams(int count) { G.level_streams = count < 2 ? -1 : count; }
+GPU_API uint32_t GPUX_LevelOverlapCount(void) { return g_level_overlap_count; }
 GPU_API uint32_t GPUX_GraphTimedOpCount(GPU_Graph* g) { return g ? (uint32_t)g->timed_ms.size() : 0; }
 GPU_API const char* GPUX_GraphTimedOpName(GPU_Graph* g, uint32_t i) { return (g && i < g->timed_names.size()) ? g->timed_names[i].c_str() : ""; }
 GPU_API float GPUX_GraphTimedOpMs(GPU_Graph* g, uint32_t i) { return (g && i < g->timed_ms.size()) ? g->timed_ms[i] : 0.0f; }
