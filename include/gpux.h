@@ -64,6 +64,12 @@ GPU_API void GPUX_OpCopyDecodedTextureMipToBuffer(GPU_Graph* graph, GPU_Texture*
 GPU_API void GPUX_OpProjectSH9(GPU_Graph* graph, GPU_Texture* cube, uint32_t mip_level, uint32_t face0, uint32_t face1, uint32_t row0, uint32_t row1,
                                GPU_Buffer* dst, uint32_t dst_offset);
 GPU_API void GPUX_OpIrradianceFromSH9(GPU_Graph* graph, GPU_Buffer* src, uint32_t src_offset, GPU_Texture* irradiance_cube, uint32_t mip_level);
+/* K18: one level (every layer) of a 2-D or cube RGBA32F / RGBA16F texture -> BC6H_UF16 blocks (mode 11; csrc/bc6h_core.h)
+ * at dst_offset (a multiple of 16): ceil(w / 4) x ceil(h / 4) blocks of 16 bytes per layer, row-major, layer after layer --
+ * GPUX_BC6HMipBytes in all (0 for a texture the op does not take).  A plain launch, ordered with the rest of the graph; may be captured
+ * under GPUX_SetGraphReplay(1). */
+GPU_API void GPUX_OpEncodeBC6H(GPU_Graph* graph, GPU_Texture* src, uint32_t mip_level, GPU_Buffer* dst, uint32_t dst_offset);
+GPU_API uint64_t GPUX_BC6HMipBytes(const GPU_Texture* texture, uint32_t mip_level);
 GPU_API void* GPUX_TextureDevicePtr(GPU_Texture* texture, uint32_t mip_level);            /* for RCCL / interop */
 GPU_API void* GPUX_BufferDevicePtr(GPU_Buffer* buffer);
 GPU_API void* GPUX_GraphStream(GPU_Graph* graph);                                         /* hipStream_t */

@@ -281,6 +281,35 @@ enum { PBR_DDS_FILE_MIPS = 1 };   /* also upload the file's levels below 0, down
 GPU_Texture* PBR_MakeTextureFromDDSMemory(const void* bytes, size_t size, uint32_t flags);
 GPU_Texture* PBR_MakeTextureFromDDSFile(const char* filepath, uint32_t flags);
 
+/* ---- the bake's maps as .dds files (N11 / K18, host/pbr_ddsout.c): one DX10-header container per texture with its mip chain; cubes
+ *      carry the TEXTURECUBE flag and all six faces, data face-major (+X -X +Y -Y +Z -Z, the layer order), each face's levels in order. ---- */
+typedef struct PBR_DDSInfoEx {
+    uint32_t dxgi_format;         /* 2 RGBA32F, 10 RGBA16F, 34 RG16F, 95 BC6H_UF16, 28 RGBA8UN, 71 BC1, 77 BC3, 83 BC5 (legacy FourCCs map to these) */
+    uint32_t width, height;
+    uint32_t layers;              /* 1, or 6 for a cube */
+    uint32_t level_count;         /* 1 .. PBR_DDS_MAX_LEVELS */
+    uint64_t level_offset[6][PBR_DDS_MAX_LEVELS];   /* [layer][level]: bytes from the start of the file; inside it */
+    uint64_t level_size[PBR_DDS_MAX_LEVELS];        /* bytes of one layer of a level */
+} PBR_DDSInfoEx;
+/* like PBR_ParseDDS (same error codes; that function and what it accepts stay as they are), but also cubes and the float / BC6H formats */
+int PBR_ParseDDSEx(const void* bytes, size_t size, PBR_DDSInfoEx* out);
+/* the 148 header bytes of such a file and, if layout is not NULL, where every (layer, level) goes; returns the file's size, 0 for
+ * arguments that have no DDS form (a format outside the list above, extents of 0 or above 16384, layers not 1 or 6, a non-square cube,
+ * more levels than a full chain or than PBR_DDS_MAX_LEVELS).  Host only. */
+uint64_t PBR_BuildDDSHeader(uint32_t dxgi_format, uint32_t width, uint32_t height, uint32_t layers, uint32_t level_count, uint8_t header[148],
+                            PBR_DDSInfoEx* layout);
+enum { PBR_DDS_OUT_SAME = 0,          /* RGBA32F -> DXGI 2, RGBA16F -> DXGI 10, RG16F -> DXGI 34 (the BRDF LUT) */
+       PBR_DDS_OUT_RGBA16F = 1,       /* RGBA32F narrowed on the host: round to nearest even, sign and Inf kept (csrc/bc6h_core.h) */
+       PBR_DDS_OUT_BC6H_UF16 = 2 };   /* RGBA32F / RGBA16F -> DXGI 95 through GPUX_OpEncodeBC6H, every level in one graph */
+/* levels [first_mip, first_mip + mip_count) of a 2-D or cube texture (mip_count 0: to the end of the chain) as file bytes the caller
+ * frees; blocking.  NULL (message on stderr) for a format / output pair outside the list, a bad range or a failed allocation. */
+void* PBR_EncodeTextureDDS(GPU_Texture* texture, uint32_t first_mip, uint32_t mip_count, int out_format, size_t* out_size);
+int PBR_WriteTextureDDS(const char* path, GPU_Texture* texture, uint32_t first_mip, uint32_t mip_count, int out_format);   /* 0 on success */
+/* RGBA32F, RGBA16F and RG16F files, 2-D or cube, with the file's levels: one level gives a texture without mips, several must be the
+ * whole chain of GPU_TextureFlag_HasMipmaps.  NULL on any error (message on stderr).  BC6H files are not loaded. */
+GPU_Texture* PBR_MakeTextureFromFloatDDSMemory(const void* bytes, size_t size);
+GPU_Texture* PBR_MakeTextureFromFloatDDSFile(const char* filepath);
+
 typedef struct PBR_GeometryPass PBR_GeometryPass;
 /* the two render passes and pipelines of the reference: pass i writes gb's four colour planes, PBR_PostVelocity(pp, i) and gb->depth */
 PBR_GeometryPass* PBR_MakeGeometryPass(const PBR_GBuffer* gb, PBR_PostProcess* pp, uint32_t width, uint32_t height);

@@ -389,6 +389,15 @@ int pbrk_sh9_project(const void* level /* float4 [6][n][n] */, int n, int face0,
 int pbrk_sh9_irradiance(const double* coef27_device, void* out_level /* float4 [6][size][size] */, int size,
                         int face0, int face1, int y0, int y1, void* stream);
 
+/* ---- K18: BC6H_UF16 encode of one level (the output side of the bake, host/pbr_ddsout.c).  `layers` images of
+ *      width x height RGBA32F (16-byte aligned) or RGBA16F (8-byte aligned) texels, tight, layer after layer -> ceil(width / 4) x
+ *      ceil(height / 4) blocks of 16 bytes per layer, row major within a layer, layer after layer (16-byte aligned).  Mode 11 only;
+ *      texels past the edge of the level repeat the last row / column.  Any extent from 1 to 16384, 1 to 65535 layers; another source
+ *      format is PBRK_E_FORMAT.  Contract (half codes, candidates, index and anchor rules, integer only): csrc/bc6h_core.h, DESIGN.md K18. ---- */
+uint64_t pbrk_bc6h_level_bytes(int width, int height, int layers);      /* 0 for a non-positive argument */
+int pbrk_bc6h_encode(const void* level, int src_format /* PBRK_FMT_RGBA32F / PBRK_FMT_RGBA16F */, int width, int height, int layers,
+                     void* blocks_out, void* stream);
+
 /* ---- diagnostics: the device samplers of the widened passes evaluated at caller-supplied coordinates, so that tests can feed them
  *      NaN / inf / 1e30 / boundary values directly (a ray that has marched far away must never become an out-of-bounds read).
  *      which: 0 = LIGHTGRID (RGBA16F n^3, coords xyz), 1 = sampler2DShadow (R32F w x h, coords u, v, ref; result in out[0]),

@@ -2,7 +2,7 @@
  * pbr_demo.c -- headless C driver of the hot path through the GPU_* boundary (what main.cpp:35-51 +
  * HotreloadShaders + BuildRenderCommands do for this path, without window / mesh import / raster passes).
  *
- *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster [gridview]]]]] [sh9 FILE]
+ *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster [gridview]]]]] [sh9 FILE] [dds PREFIX]
  *
  * Loads a vertical-strip HDR cube (asset_import.cpp:17-27), runs the IBL precompute (render.cpp:505-619),
  * shades a flat synthetic G-buffer (a metallic floor under the sky), then runs three frames of the per-frame chain
@@ -17,6 +17,9 @@
  * K16: the voxelised mesh itself -- and its checksum is printed as gridview_bits_sum; the other lines stay as they are.
  * With `sh9 FILE` as the LAST two arguments (after whichever of the above are given) the SH9 coefficients of level 0 of the loaded
  * environment (K17) are written to FILE and their sum is printed as sh9_sum; the other lines stay as they are.
+ * With `dds PREFIX` as the last two arguments (after `sh9 FILE` if both are given) the bake is saved as PREFIX_specular.dds (BC6H_UF16
+ * through K18, the levels down to min_size), PREFIX_irradiance.dds and PREFIX_lut.dds (as they are), and the three file sizes are
+ * printed as dds_bytes; the other lines stay as they are.
  */
 #include "pbr_host.h"
 
@@ -83,6 +86,8 @@ static PBR_Mesh* demo_mesh(PBR_Material** material_out) {
 
 int main(int argc, char** argv) {
     const char* sh9_path = NULL;
+    const char* dds_prefix = NULL;
+    if (argc >= 4 && strcmp(argv[argc - 2], "dds") == 0) { dds_prefix = argv[argc - 1]; argc -= 2; }
     if (argc >= 4 && strcmp(argv[argc - 2], "sh9") == 0) { sh9_path = argv[argc - 1]; argc -= 2; }
     if (argc < 2) { fprintf(stderr, "usage: %s cube_strip.hdr [irr lut spec min_size [width height]]\n", argv[0]); return 2; }
     uint32_t irr = argc > 2 ? (uint32_t)atoi(argv[2]) : 32, lut = argc > 3 ? (uint32_t)atoi(argv[3]) : 256;
@@ -114,6 +119,23 @@ int main(int argc, char** argv) {
     for (uint32_t m = 0; m < maps.tex_specular_env_map->mip_level_count && size >= min_size; ++m, size /= 2)
         printf("specular_mip%u_sum %.9e\n", m, checksum_texture_mip(maps.tex_specular_env_map, m, 1));
     printf("lut_bits_sum %.9e\n", checksum_texture_mip(maps.brdf_lut, 0, 0));
+    if (dds_prefix) {
+        uint32_t filtered = 0;                                               /* the levels the prefilter wrote */
+        for (uint32_t sz = spec; filtered < maps.tex_specular_env_map->mip_level_count && sz >= min_size; sz /= 2) filtered++;
+        struct { const char* name; GPU_Texture* tex; uint32_t levels; int format; } files[3] = {
+            {"specular", maps.tex_specular_env_map, filtered, PBR_DDS_OUT_BC6H_UF16}, {"irradiance", maps.irradiance_map, 0, PBR_DDS_OUT_SAME},
+            {"lut", maps.brdf_lut, 0, PBR_DDS_OUT_SAME}};
+        for (int i = 0; i < 3; ++i) {
+            char path[4096];
+            size_t bytes = 0;
+            void* data = PBR_EncodeTextureDDS(files[i].tex, 0, files[i].levels, files[i].format, &bytes);
+            FILE* f = NULL;
+            if (!data || snprintf(path, sizeof path, "%s_%s.dds", dds_prefix, files[i].name) >= (int)sizeof path || !(f = fopen(path, "wb")) ||
+                fwrite(data, 1, bytes, f) != bytes || fclose(f) != 0) { fprintf(stderr, "dds: cannot write %s_%s.dds\n", dds_prefix, files[i].name); return 1; }
+            free(data);
+            printf("dds_bytes %s %zu\n", files[i].name, bytes);
+        }
+    }
 
     /* a flat synthetic G-buffer: lower half = rough gold floor facing +Z at NDC depth .998, upper half = sky */
     PBR_GBuffer gb;

@@ -23,6 +23,7 @@ BC_BLOCK_BYTES = {Format_BC1_RGB_UN: 8, Format_BC1_RGBA_UN: 8, Format_BC3_RGBA_U
 PBRK_BC1_RGB, PBRK_BC1_RGBA, PBRK_BC3, PBRK_BC5 = 0, 1, 2, 3
 PBR_DDS_FILE_MIPS = 1
 PBR_DDS_MAX_LEVELS = 16
+PBR_DDS_OUT_SAME, PBR_DDS_OUT_RGBA16F, PBR_DDS_OUT_BC6H_UF16 = 0, 1, 2
 TextureFlag_StorageImage, TextureFlag_RenderTarget, TextureFlag_HasMipmaps, TextureFlag_Cubemap = 1, 2, 4, 8
 BufferFlag_CPU, BufferFlag_GPU, BufferFlag_StorageBuffer = 1, 2, 4
 Shade_IBL, Shade_LightShafts = 1, 2
@@ -147,6 +148,11 @@ class GPU_GraphicsPipelineDesc(C.Structure):
                 ("vertex_input_formats", C.POINTER(C.c_int)), ("vertex_input_formats_count", C.c_uint32),
                 ("enable_depth_test", C.c_bool), ("enable_depth_write", C.c_bool), ("enable_blending", C.c_bool),
                 ("blending_mode_additive", C.c_bool), ("enable_conservative_rasterization", C.c_bool), ("cull_mode", C.c_int)]
+
+
+class PBR_DDSInfoEx(C.Structure):
+    _fields_ = [("dxgi_format", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("layers", C.c_uint32), ("level_count", C.c_uint32),
+                ("level_offset", (C.c_uint64 * PBR_DDS_MAX_LEVELS) * 6), ("level_size", C.c_uint64 * PBR_DDS_MAX_LEVELS)]
 
 
 class PBR_DDSInfo(C.Structure):
@@ -334,6 +340,15 @@ PROTOTYPES = {
     "PBR_ProjectSH9": (C.c_int, [TexP, U32, C.POINTER(C.c_double)]), "PBR_GenIrradianceMapSH": (None, [TexP, U32, TexP]),
     "PBR_EvalSH9Irradiance": (None, [C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "PBR_WriteSH9File": (C.c_int, [C.c_char_p, C.POINTER(C.c_double)]), "PBR_ReadSH9File": (C.c_int, [C.c_char_p, C.POINTER(C.c_double)]),
+    # --- K18: BC6H encode, .dds output ---
+    "pbrk_bc6h_level_bytes": (C.c_uint64, [C.c_int, C.c_int, C.c_int]),
+    "pbrk_bc6h_encode": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP]),
+    "GPUX_OpEncodeBC6H": (None, [VP, TexP, U32, BufP, U32]), "GPUX_BC6HMipBytes": (C.c_uint64, [TexP, U32]),
+    "PBR_ParseDDSEx": (C.c_int, [VP, C.c_size_t, C.POINTER(PBR_DDSInfoEx)]),
+    "PBR_BuildDDSHeader": (C.c_uint64, [U32, U32, U32, U32, U32, C.POINTER(C.c_uint8), C.POINTER(PBR_DDSInfoEx)]),
+    "PBR_EncodeTextureDDS": (VP, [TexP, U32, U32, C.c_int, C.POINTER(C.c_size_t)]),
+    "PBR_WriteTextureDDS": (C.c_int, [C.c_char_p, TexP, U32, U32, C.c_int]),
+    "PBR_MakeTextureFromFloatDDSMemory": (TexP, [VP, C.c_size_t]), "PBR_MakeTextureFromFloatDDSFile": (TexP, [C.c_char_p]),
 }
 
 _LIB = None
@@ -606,3 +621,54 @@ def rccl_comm_init(world, rank, unique_id: bytes):
 
 def rccl_comm_destroy(comm):
     rccl().ncclCommDestroy(comm)
+
+
+def parse_dds_ex(data: bytes):
+    """PBR_ParseDDSEx -> PBR_DDSInfoEx (cubes, float and BC6H formats too), or raises ValueError with the parser's reason."""
+    info = PBR_DDSInfoEx()
+    rc = lib().PBR_ParseDDSEx(data, len(data), C.byref(info))
+    if rc != 0:
+        raise ValueError(lib().PBR_DDSErrorString(rc).decode())
+    return info
+
+
+def encode_bc6h(tex, mip=0):
+    """One level (every layer) of an RGBA32F / RGBA16F texture as BC6H_UF16 blocks (K18) -> uint8 [layers * bh * bw][16]."""
+    L = lib()
+    nbytes = L.GPUX_BC6HMipBytes(tex, mip)
+    if nbytes == 0:
+        raise ValueError("encode_bc6h: not a level of a 2-D or cube RGBA32F / RGBA16F texture")
+    raw = _read_back(lambda g, buf: L.GPUX_OpEncodeBC6H(g, tex, mip, buf, 0), nbytes)
+    return np.frombuffer(raw, np.uint8).reshape(-1, 16).copy()
+
+
+def encode_dds(tex, first_mip=0, mip_count=0, out_format=PBR_DDS_OUT_SAME):
+    """PBR_EncodeTextureDDS -> the file's bytes."""
+    L = lib()
+    size = C.c_size_t(0)
+    p = L.PBR_EncodeTextureDDS(tex, first_mip, mip_count, out_format, C.byref(size))
+    if not p:
+        raise RuntimeError("PBR_EncodeTextureDDS failed")
+    try:
+        return C.string_at(p, size.value)
+    finally:
+        _libc_free(p)
+
+
+def _libc_free(p):
+    libc = C.CDLL(None)
+    libc.free.argtypes = [VP]
+    libc.free.restype = None
+    libc.free(p)
+
+
+def write_dds(path, tex, first_mip=0, mip_count=0, out_format=PBR_DDS_OUT_SAME):
+    if lib().PBR_WriteTextureDDS(os.fsencode(path), tex, first_mip, mip_count, out_format) != 0:
+        raise RuntimeError("PBR_WriteTextureDDS failed")
+
+
+def make_texture_from_float_dds_file(path):
+    t = lib().PBR_MakeTextureFromFloatDDSFile(os.fsencode(path))
+    if not t:
+        raise RuntimeError("PBR_MakeTextureFromFloatDDSFile failed")
+    return t
