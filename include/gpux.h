@@ -70,6 +70,11 @@ GPU_API void GPUX_OpIrradianceFromSH9(GPU_Graph* graph, GPU_Buffer* src, uint32_
  * under GPUX_SetGraphReplay(1). */
 GPU_API void GPUX_OpEncodeBC6H(GPU_Graph* graph, GPU_Texture* src, uint32_t mip_level, GPU_Buffer* dst, uint32_t dst_offset);
 GPU_API uint64_t GPUX_BC6HMipBytes(const GPU_Texture* texture, uint32_t mip_level);
+/* K19: the way back: GPUX_BC6HMipBytes(dst, mip_level) bytes of BC6H_UF16 blocks (any of the 14 modes; csrc/bc6h_decode_core.h, DESIGN.md
+ * K19) at src_offset (a multiple of 16), laid out as GPUX_OpEncodeBC6H writes them -> one level, every layer, of a 2-D or cube RGBA32F /
+ * RGBA16F texture; alpha 1.  A texture writer like any other: the target's sampler twins are rebuilt before the next use.  Anything
+ * else is one error at record time with nothing recorded.  A plain launch; may be captured under GPUX_SetGraphReplay(1). */
+GPU_API void GPUX_OpDecodeBC6H(GPU_Graph* graph, GPU_Buffer* src, uint32_t src_offset, GPU_Texture* dst, uint32_t mip_level);
 GPU_API void* GPUX_TextureDevicePtr(GPU_Texture* texture, uint32_t mip_level);            /* for RCCL / interop */
 GPU_API void* GPUX_BufferDevicePtr(GPU_Buffer* buffer);
 GPU_API void* GPUX_GraphStream(GPU_Graph* graph);                                         /* hipStream_t */

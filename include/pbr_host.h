@@ -306,9 +306,19 @@ enum { PBR_DDS_OUT_SAME = 0,          /* RGBA32F -> DXGI 2, RGBA16F -> DXGI 10, 
 void* PBR_EncodeTextureDDS(GPU_Texture* texture, uint32_t first_mip, uint32_t mip_count, int out_format, size_t* out_size);
 int PBR_WriteTextureDDS(const char* path, GPU_Texture* texture, uint32_t first_mip, uint32_t mip_count, int out_format);   /* 0 on success */
 /* RGBA32F, RGBA16F and RG16F files, 2-D or cube, with the file's levels: one level gives a texture without mips, several must be the
- * whole chain of GPU_TextureFlag_HasMipmaps.  NULL on any error (message on stderr).  BC6H files are not loaded. */
+ * whole chain of GPU_TextureFlag_HasMipmaps.  NULL on any error (message on stderr).  BC6H files are not loaded by this function. */
 GPU_Texture* PBR_MakeTextureFromFloatDDSMemory(const void* bytes, size_t size);
 GPU_Texture* PBR_MakeTextureFromFloatDDSFile(const char* filepath);
+/* BC6H_UF16 files (DXGI 95 as PBR_ParseDDSEx reports it; N12 / K19, host/pbr_ddsin.c), 2-D or cube, any of the format's 14 modes, as an
+ * RGBA32F or RGBA16F texture (`target`) the lighting pass takes: every level is decoded once by GPUX_OpDecodeBC6H, all of them in one
+ * graph from one staging buffer.  One level gives a texture without mips, several one with GPU_TextureFlag_HasMipmaps; the file may hold
+ * fewer levels than the chain (pbr_demo ... dds writes the specular cube down to min_size): the others stay zero, as GPU_MakeTexture
+ * leaves them.  NULL on any error (message on stderr). */
+GPU_Texture* PBR_MakeTextureFromBC6HDDSMemory(const void* bytes, size_t size, GPU_Format target);
+GPU_Texture* PBR_MakeTextureFromBC6HDDSFile(const char* filepath, GPU_Format target);
+/* ceil(w / 4) x ceil(h / 4) BC6H_UF16 blocks, row-major -> w x h x 3 half bit patterns (0 .. 0x7BFF), tight rows: the arithmetic of
+ * csrc/bc6h_decode_core.h on the host, for callers without a GPU and for the tests.  Nothing is done for a NULL pointer or an extent of 0. */
+void PBR_DecodeBC6HBlocks(const void* blocks, uint32_t w, uint32_t h, uint16_t* rgb_half);
 
 typedef struct PBR_GeometryPass PBR_GeometryPass;
 /* the two render passes and pipelines of the reference: pass i writes gb's four colour planes, PBR_PostVelocity(pp, i) and gb->depth */

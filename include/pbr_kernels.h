@@ -398,6 +398,15 @@ uint64_t pbrk_bc6h_level_bytes(int width, int height, int layers);      /* 0 for
 int pbrk_bc6h_encode(const void* level, int src_format /* PBRK_FMT_RGBA32F / PBRK_FMT_RGBA16F */, int width, int height, int layers,
                      void* blocks_out, void* stream);
 
+/* ---- K19: BC6H_UF16 decode of one level, all 14 modes (the input side, host/pbr_ddsin.c).  `layers` images of
+ *      ceil(width / 4) x ceil(height / 4) blocks, laid out as pbrk_bc6h_encode writes them (16-byte aligned) -> width x height RGBA32F
+ *      (16-byte aligned) or RGBA16F (8-byte aligned) texels, tight, layer after layer.  RGBA16F gets the half codes 0 .. 0x7BFF as they
+ *      are, RGBA32F their exact widening (subnormal halves included, done in integers); alpha is 1.0; texels of a block outside the level
+ *      are dropped; a block of a reserved mode gives zeros.  Any extent from 1 to 16384, 1 to 65535 layers; another target format is
+ *      PBRK_E_FORMAT, anything else PBRK_E_ARG, with nothing launched.  Contract (integer only): csrc/bc6h_decode_core.h, DESIGN.md K19. ---- */
+int pbrk_bc6h_decode(const void* blocks, int width, int height, int layers, void* level_out,
+                     int dst_format /* PBRK_FMT_RGBA32F / PBRK_FMT_RGBA16F */, void* stream);
+
 /* ---- diagnostics: the device samplers of the widened passes evaluated at caller-supplied coordinates, so that tests can feed them
  *      NaN / inf / 1e30 / boundary values directly (a ray that has marched far away must never become an out-of-bounds read).
  *      which: 0 = LIGHTGRID (RGBA16F n^3, coords xyz), 1 = sampler2DShadow (R32F w x h, coords u, v, ref; result in out[0]),

@@ -97,7 +97,7 @@ struct GPU_GraphicsPipeline { GPU_PipelineLayout* layout; GPU_RenderPass* pass; 
                               uint32_t vertex_stride = 0; /* raster kinds: bytes per vertex (gpu_vulkan.c:1745-1762) */
                               const struct RasterKind* raster = nullptr; /* K12 / K13 / K14: the row of its raster kind */ };
 
-enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster, Op_CopyDecodedT2B, Op_ProjectSH9, Op_IrradianceSH9, Op_EncodeBC6H };
+enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster, Op_CopyDecodedT2B, Op_ProjectSH9, Op_IrradianceSH9, Op_EncodeBC6H, Op_DecodeBC6H };
 // one draw of a raster job: job triangles from first_tri on, matrices from the set's GLOBALS, the buffers and the target its kind
 // names (K12 / K13: the buffers bound at the draw; K14: SSBO0 / SSBO1 of the set, first_index = its first vertex) and the pushed
 // constants (K13 reads them: the skybox rebinds both inside the pass)
@@ -1646,6 +1646,21 @@ GPU_API void GPUX_OpEncodeBC6H(GPU_Graph* g, GPU_Texture* src, uint32_t mip, GPU
     op.tex = (TextureImpl*)src; op.mip = mip; op.buf = (BufferImpl*)dst; op.off_b = dst_offset; op.size = bytes;
     g->ops.push_back(op);
 }
+// K19: the way back.  op.buf / op.off_a = the blocks, op.tex / op.mip = the level written (all layers), op.size = the blocks' bytes
+GPU_API void GPUX_OpDecodeBC6H(GPU_Graph* g, GPU_Buffer* src, uint32_t src_offset, GPU_Texture* dst, uint32_t mip) {
+    REC_GUARD(g);
+    const char* fn = "GPUX_OpDecodeBC6H";
+    GPU_REQUIRE_V(g->in_pass == nullptr, "%s: inside a render pass", fn);
+    GPU_REQUIRE_V(src && dst && mip < dst->mip_level_count, "%s: bad arguments", fn);
+    GPU_REQUIRE_V(bc6h_source_format(dst->format) >= 0 && dst->depth == 1, "%s: the target must be a 2-D or cube RGBA32F / RGBA16F texture", fn);
+    GPU_REQUIRE_V(mip_dim(dst->width, mip) <= 16384 && mip_dim(dst->height, mip) <= 16384, "%s: levels above 16384 a side are not implemented", fn);
+    GPU_REQUIRE_V((src_offset % 16) == 0, "%s: buffer offset %u is not a multiple of 16", fn, src_offset);
+    const uint64_t bytes = GPUX_BC6HMipBytes(dst, mip);
+    GPU_REQUIRE_V((uint64_t)src_offset + bytes <= src->size, "%s: buffer too small (%u bytes for %llu at offset %u)", fn, src->size, (unsigned long long)bytes, src_offset);
+    Op op; op.kind = Op_DecodeBC6H; op.name = "K19.bc6h_decode";
+    op.buf = (BufferImpl*)src; op.off_a = src_offset; op.tex = (TextureImpl*)dst; op.mip = mip; op.size = bytes;
+    g->ops.push_back(op);
+}
 
 GPU_API void GPU_OpGenerateMipmaps(GPU_Graph* g, GPU_Texture* tex) {
     REC_GUARD(g);
@@ -2201,6 +2216,18 @@ static void exec_bc6h(GPU_Graph* g, Op& op, size_t& ev_used) {
     });
 }
 
+// K19: one launch; the level was written, so the target's apron twin, cells and LUT cells are dropped like after any writer
+static void exec_bc6h_decode(GPU_Graph* g, Op& op, size_t& ev_used) {
+    const GPU_Texture& t = op.tex->base;
+    void* level = (char*)op.tex->dev + op.tex->mip_offset[op.mip];
+    timed(g, op.name, ev_used, [&] {
+        int rc = pbrk_bc6h_decode((const char*)op.buf->dev + op.off_a, (int)mip_dim(t.width, op.mip), (int)mip_dim(t.height, op.mip), (int)t.layer_count, level,
+                                  bc6h_source_format(t.format), g->cur);
+        if (rc != PBRK_OK) gpu_fail("%s launch failed (%d)", op.name.c_str(), rc);
+    });
+    op.tex->bordered_valid = false; op.tex->lut_cells_valid = false;
+}
+
 static void exec_blit(GPU_Graph* g, Op& op, size_t& ev_used) {
     hipStream_t st = g->cur;
     if (op.folded) { op.tex2->bordered_valid = false; op.tex2->lut_cells_valid = false; return; }   // its consumer reads the source (fold_blits)
@@ -2326,6 +2353,7 @@ static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
     case Op_CopyB2B: case Op_CopyB2T: case Op_CopyT2B: case Op_CopyDecodedT2B: exec_copy(g, op, ev_used); return;
     case Op_ProjectSH9: case Op_IrradianceSH9: exec_sh9(g, op, ev_used); return;
     case Op_EncodeBC6H: exec_bc6h(g, op, ev_used); return;
+    case Op_DecodeBC6H: exec_bc6h_decode(g, op, ev_used); return;
     }
 }
 
@@ -2347,6 +2375,7 @@ static bool op_replayable(const Op& op) {
     case Op_Raster: return false;                                             // its draw table is uploaded from pinned staging at submit
     case Op_ProjectSH9: case Op_IrradianceSH9: return true;                   // plain launches on device-visible pointers; the scratch exists since recording
     case Op_EncodeBC6H: return true;                                          // one plain launch, texture -> device-visible buffer
+    case Op_DecodeBC6H: return true;                                          // the same, buffer -> texture
     case Op_Clear: return fill_texel_ok(op.tex->texel_bytes);
     case Op_Shade: {
         if (is_post_kernel(op.gpipe->kernel)) return true;
@@ -2370,7 +2399,7 @@ static bool graph_replayable(GPU_Graph* g) {
     for (const Op& op : g->ops) {
         if (!op_replayable(op)) return false;
         switch (op.kind) {
-        case Op_Clear: case Op_MipGen: case Op_IrradianceSH9: written.push_back(op.tex); break;
+        case Op_Clear: case Op_MipGen: case Op_IrradianceSH9: case Op_DecodeBC6H: written.push_back(op.tex); break;
         case Op_Blit: if (op.tex2) written.push_back(op.tex2); break;          // tex = source, tex2 = destination
         case Op_Dispatch: { Slot* o = named_slot(op.set, "IMG0"); if (o && o->tex) written.push_back(o->tex); break; }
         case Op_Shade: {
@@ -2462,7 +2491,7 @@ static bool op_access(const Op& op, std::vector<TextureImpl*>& r, std::vector<Te
     case Op_Blit: r.push_back(op.tex); w.push_back(op.tex2); return true;
     case Op_Clear: w.push_back(op.tex); return true;
     case Op_ProjectSH9: case Op_EncodeBC6H: r.push_back(op.tex); return false; // their buffer is not followed: ends the walk like any buffer
-    case Op_IrradianceSH9: w.push_back(op.tex); return false;
+    case Op_IrradianceSH9: case Op_DecodeBC6H: w.push_back(op.tex); return false;   // the buffer they read is not followed either
     default: return false;
     }
 }

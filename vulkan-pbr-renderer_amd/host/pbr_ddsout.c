@@ -3,7 +3,7 @@
  * whole mip chain, the way cmft, IBLBaker and cmgen write theirs.  Float textures go out as they are (RGBA32F = DXGI 2, RGBA16F = 10,
  * RG16F = 34) or narrowed to RGBA16F on the host; BC6H_UF16 (DXGI 95) is encoded on the device by K18 (csrc/bc6h_core.h is the
  * contract, also of the host's fp32 -> fp16 conversion).  The float files load back (PBR_MakeTextureFromFloatDDS*), so a bake can be
- * saved and shaded later without the source environment; BC6H is write-only here.
+ * saved and shaded later without the source environment; BC6H files load through host/pbr_ddsin.c (K19).
  *
  * File layout (Microsoft's DDS programming guide): "DDS " magic, the 124-byte DDS_HEADER, the 20-byte DDS_HEADER_DXT10, then for a
  * cube the six faces in the order +X -X +Y -Y +Z -Z (the texture's layer order, face_texel_dir), each face with its levels largest

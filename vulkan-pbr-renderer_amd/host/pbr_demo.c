@@ -2,7 +2,7 @@
  * pbr_demo.c -- headless C driver of the hot path through the GPU_* boundary (what main.cpp:35-51 +
  * HotreloadShaders + BuildRenderCommands do for this path, without window / mesh import / raster passes).
  *
- *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster [gridview]]]]] [sh9 FILE] [dds PREFIX]
+ *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster [gridview]]]]] [sh9 FILE] [dds PREFIX] [ddsin PREFIX]
  *
  * Loads a vertical-strip HDR cube (asset_import.cpp:17-27), runs the IBL precompute (render.cpp:505-619),
  * shades a flat synthetic G-buffer (a metallic floor under the sky), then runs three frames of the per-frame chain
@@ -20,6 +20,9 @@
  * With `dds PREFIX` as the last two arguments (after `sh9 FILE` if both are given) the bake is saved as PREFIX_specular.dds (BC6H_UF16
  * through K18, the levels down to min_size), PREFIX_irradiance.dds and PREFIX_lut.dds (as they are), and the three file sizes are
  * printed as dds_bytes; the other lines stay as they are.
+ * With `ddsin PREFIX` as the last two arguments (after all of the above) nothing is baked: the three maps are loaded from
+ * PREFIX_specular.dds (a BC6H_UF16 file is decoded by K19 into an RGBA32F cube, a float file is loaded as it is), PREFIX_irradiance.dds
+ * and PREFIX_lut.dds -- the files `dds PREFIX` wrote -- and the run goes on unchanged from the irradiance_sum line.
  */
 #include "pbr_host.h"
 
@@ -84,9 +87,32 @@ static PBR_Mesh* demo_mesh(PBR_Material** material_out) {
     return m;
 }
 
+/* `ddsin PREFIX`: the bake's three maps from the files `dds PREFIX` wrote; the specular loader goes by the file's DXGI format */
+static PBR_IBLMaps load_maps(const char* prefix) {
+    PBR_IBLMaps maps;
+    memset(&maps, 0, sizeof maps);
+    const char* names[3] = {"specular", "irradiance", "lut"};
+    GPU_Texture** slots[3] = {&maps.tex_specular_env_map, &maps.irradiance_map, &maps.brdf_lut};
+    for (int i = 0; i < 3; ++i) {
+        char path[4096];
+        uint8_t head[148];
+        if (snprintf(path, sizeof path, "%s_%s.dds", prefix, names[i]) >= (int)sizeof path) { fprintf(stderr, "ddsin: path too long\n"); return maps; }
+        FILE* f = fopen(path, "rb");
+        const size_t got = f ? fread(head, 1, sizeof head, f) : 0;
+        if (f) fclose(f);
+        const uint32_t dxgi = got == sizeof head && head[84] == 'D' && head[85] == 'X' && head[86] == '1' && head[87] == '0'
+                                  ? (uint32_t)head[128] | ((uint32_t)head[129] << 8) | ((uint32_t)head[130] << 16) | ((uint32_t)head[131] << 24) : 0;
+        *slots[i] = i == 0 && dxgi == 95 ? PBR_MakeTextureFromBC6HDDSFile(path, GPU_Format_RGBA32F) : PBR_MakeTextureFromFloatDDSFile(path);
+        if (!*slots[i]) { fprintf(stderr, "ddsin: cannot load %s\n", path); return maps; }
+    }
+    return maps;
+}
+
 int main(int argc, char** argv) {
     const char* sh9_path = NULL;
     const char* dds_prefix = NULL;
+    const char* ddsin_prefix = NULL;
+    if (argc >= 4 && strcmp(argv[argc - 2], "ddsin") == 0) { ddsin_prefix = argv[argc - 1]; argc -= 2; }
     if (argc >= 4 && strcmp(argv[argc - 2], "dds") == 0) { dds_prefix = argv[argc - 1]; argc -= 2; }
     if (argc >= 4 && strcmp(argv[argc - 2], "sh9") == 0) { sh9_path = argv[argc - 1]; argc -= 2; }
     if (argc < 2) { fprintf(stderr, "usage: %s cube_strip.hdr [irr lut spec min_size [width height]]\n", argv[0]); return 2; }
@@ -107,10 +133,16 @@ int main(int argc, char** argv) {
     }
 
     PBR_IBLMaps maps;
-    PBR_MakeIBLMaps(&maps, irr, lut, spec);                                  /* render.cpp:794-796 */
-    PBR_GenIrradianceMap(tex_env_cube, maps.irradiance_map);                 /* render.cpp:505-540 */
-    PBR_GenPrefilteredEnvMap(tex_env_cube, maps.tex_specular_env_map, min_size);   /* render.cpp:542-589 */
-    PBR_GenBRDFIntegrationMap(maps.brdf_lut);                                /* render.cpp:591-619 */
+    if (ddsin_prefix) {
+        maps = load_maps(ddsin_prefix);
+        if (!maps.tex_specular_env_map || !maps.irradiance_map || !maps.brdf_lut) return 1;
+        spec = maps.tex_specular_env_map->width;
+    } else {
+        PBR_MakeIBLMaps(&maps, irr, lut, spec);                              /* render.cpp:794-796 */
+        PBR_GenIrradianceMap(tex_env_cube, maps.irradiance_map);             /* render.cpp:505-540 */
+        PBR_GenPrefilteredEnvMap(tex_env_cube, maps.tex_specular_env_map, min_size);   /* render.cpp:542-589 */
+        PBR_GenBRDFIntegrationMap(maps.brdf_lut);                            /* render.cpp:591-619 */
+    }
 
     printf("env_mip0_sum %.9e\n", checksum_texture_mip(tex_env_cube, 0, 1));
     printf("env_last_mip_sum %.9e\n", checksum_texture_mip(tex_env_cube, tex_env_cube->mip_level_count - 1, 1));

@@ -349,6 +349,11 @@ PROTOTYPES = {
     "PBR_EncodeTextureDDS": (VP, [TexP, U32, U32, C.c_int, C.POINTER(C.c_size_t)]),
     "PBR_WriteTextureDDS": (C.c_int, [C.c_char_p, TexP, U32, U32, C.c_int]),
     "PBR_MakeTextureFromFloatDDSMemory": (TexP, [VP, C.c_size_t]), "PBR_MakeTextureFromFloatDDSFile": (TexP, [C.c_char_p]),
+    # --- K19: BC6H decode, loading BC6H .dds files ---
+    "pbrk_bc6h_decode": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, VP, C.c_int, VP]),
+    "GPUX_OpDecodeBC6H": (None, [VP, BufP, U32, TexP, U32]),
+    "PBR_MakeTextureFromBC6HDDSMemory": (TexP, [VP, C.c_size_t, C.c_int]), "PBR_MakeTextureFromBC6HDDSFile": (TexP, [C.c_char_p, C.c_int]),
+    "PBR_DecodeBC6HBlocks": (None, [VP, U32, U32, C.POINTER(C.c_uint16)]),
 }
 
 _LIB = None
@@ -672,3 +677,41 @@ def make_texture_from_float_dds_file(path):
     if not t:
         raise RuntimeError("PBR_MakeTextureFromFloatDDSFile failed")
     return t
+
+
+def decode_bc6h(blocks, w, h, layers, fmt):
+    """BC6H_UF16 blocks of one level (uint8 [layers * bh * bw][16], layer after layer) decoded by K19 through GPUX_OpDecodeBC6H into a
+    fresh `fmt` (Format_RGBA32F / Format_RGBA16F) texture -> the level as read_mip gives it, always [layers][h][w][4]."""
+    L = lib()
+    blocks = np.ascontiguousarray(blocks, np.uint8)
+    if layers not in (1, 6) or blocks.size != ((w + 3) // 4) * ((h + 3) // 4) * 16 * layers:
+        raise ValueError("decode_bc6h: one 2-D level or six cube faces of ceil(w/4) x ceil(h/4) blocks each")
+    tex = make_texture(fmt, w, h, TextureFlag_Cubemap if layers == 6 else 0)
+    buf = L.GPU_MakeBuffer(blocks.size, BufferFlag_CPU, blocks.ctypes.data_as(VP))
+    g = L.GPU_MakeGraph()
+    try:
+        L.GPUX_OpDecodeBC6H(g, buf, 0, tex, 0)
+        L.GPU_GraphSubmit(g)
+        L.GPU_GraphWait(g)
+        out = read_mip(tex, 0)
+    finally:
+        L.GPU_DestroyGraph(g)
+        L.GPU_DestroyBuffer(buf)
+        L.GPU_DestroyTexture(tex)
+    return out if layers > 1 else out[None]
+
+
+def make_texture_from_bc6h_dds_file(path, fmt):
+    t = lib().PBR_MakeTextureFromBC6HDDSFile(os.fsencode(path), fmt)
+    if not t:
+        raise RuntimeError("PBR_MakeTextureFromBC6HDDSFile failed")
+    return t
+
+
+def decode_bc6h_blocks_host(blocks, w, h):
+    """PBR_DecodeBC6HBlocks: the contract's arithmetic on the host -> half bits uint16 [h][w][3]."""
+    blocks = np.ascontiguousarray(blocks, np.uint8)
+    assert blocks.size == ((w + 3) // 4) * ((h + 3) // 4) * 16
+    out = np.zeros((h, w, 3), np.uint16)
+    lib().PBR_DecodeBC6HBlocks(blocks.ctypes.data_as(VP), w, h, out.ctypes.data_as(C.POINTER(C.c_uint16)))
+    return out
