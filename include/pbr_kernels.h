@@ -178,6 +178,14 @@ void pbrk_mc_set_tile32(int mode);
 void pbrk_mc_set_fold(int on);
 /* 1 when the last region-kernel launch ran a folded instantiation, else 0 */
 int pbrk_mc_last_fold(void);
+/* levels of at most 16^2 texels with outputs of 256^2 and more, resident in LDS as a whole (k_mc_region.hip, 2k): the samples binning
+ * proves for a whole tile run test-free per face, every other sample once, each lane on its own face.  1 on, 0: the kernel such a level ran
+ * before, -1 (default) = the environment (PBR_MC_RESIDENT) or 1.  The two add a texel's samples in different orders: close, not the same bytes.  Tests and A-B runs. */
+void pbrk_mc_set_resident(int on);
+/* that kernel's counters (PBR_MC_STATS=1), since the last reset: {(lane, sample) pairs whose proof did not hold -- must stay 0 --,
+ * proved samples summed over tiles, pairs taken by the proved runs, pairs taken by the general pass}.  Its tiles also enter the flag
+ * and wave-slice counters; the window counter counts k_mc_region's proved samples alone. */
+int pbrk_mc_resident_stats(unsigned long long* out4);
 
 /* ---- K5: deferred shade pass (shaders/lighting_pass.glsl:432-716, in-scope sub-blocks). */
 typedef struct PbrkShadeArgs {

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Time pbrk_mc_filter (K4b) on synthetic levels: picoseconds per sample evaluation and clocks per wave-sample per CU for a
 given (n_src, out_size, roughness).  Kernel choice follows the library (env PBR_MC_LDS / PBR_MC_REGION / PBR_MC_BINNED); env
-PBR_MC_TILE32 = -1 | 0 | 1 goes to pbrk_mc_set_tile32 (the region kernel's 32 x 32 tile: by rule, never, wherever the shape allows).
+PBR_MC_TILE32 = -1 | 0 | 1 goes to pbrk_mc_set_tile32 (the region kernel's 32 x 32 tile: by rule, never, wherever the shape allows);
+PBR_MC_RESIDENT=0 keeps levels of at most 16^2 texels off k_mc_resident (the library reads it).
    python3 tools/mc_probe.py n_src out_size [roughness] [rows] [face0 face1]"""
 import ctypes as C
 import os
@@ -62,6 +63,11 @@ def main():
     print(f"n_src {n_src} out {out} rows {rows} faces {f0}-{f1} n_tab {n_tab}: {ms:.3f} ms  {ps:.3f} ps/eval  {clk:.1f} clk per wave-sample per CU @2.4GHz  "
           f"{65 * evals / ms * 1e-9:.1f} TFLOP/s alg  checksum {chk:.6e}", flush=True)
     if os.environ.get("PBR_MC_STATS") == "1":
+        rs = (C.c_uint64 * 4)()                                # k_mc_resident's own counters: read ahead of the reset below
+        if L.pbrk_mc_resident_stats(rs) == 0 and rs[2] + rs[3]:
+            pairs = rs[2] + rs[3]
+            print(f"   resident kernel: {rs[2] / pairs:.3f} of the (texel, sample) pairs taken by proved runs, {rs[3] / pairs:.3f} by the general pass, "
+                  f"{rs[1]} proved (tile, sample) pairs, {rs[0]} proof violations", flush=True)
         c = mc.counters(L, "flag", "window", "skip", "cut", "phase", "region", reset=True, missing_ok=True)
         if c.get("flag_samples"):
             tiles = c["flag_samples"] // n_tab

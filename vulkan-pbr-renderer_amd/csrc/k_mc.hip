@@ -291,6 +291,7 @@ extern "C" int pbrk_mc_filter(const void* src_bordered_level, const void* src_ce
     hipStream_t st = (hipStream_t)stream;
     a.snap = pbrk_get_cube_sampler_snap();                      // diagnostic convention: the direct kernel only
     // Kernel choice and the sample-split factor S depend on the LEVEL size only
+    if (!a.snap && launch_mc_resident(a, nfaces, st)) return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
     if (!a.snap && launch_mc_region(a, nfaces, st)) return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
     if (!a.snap && launch_mc_lds(a, nfaces, st)) return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
     // Sample-split factor S depends on the LEVEL size only (not on the dispatched sub-range), so that a

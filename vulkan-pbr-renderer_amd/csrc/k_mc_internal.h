@@ -117,4 +117,7 @@ __host__ __device__ inline int mc_launch_cut(const unsigned* wbits, int NW, cons
 // k_mc_region.hip: taps from LDS-staged regions of the source level.  Returns false when the kernel does not apply
 // (the caller then takes the direct kernel); the decision depends on the level's shape only, never on the dispatched range.
 bool launch_mc_region(McArgs a, int nfaces, hipStream_t st);
+// k_mc_region.hip, header 2k: levels up to 16^2 with outputs of 256^2 and more, resident in LDS as a whole; asked ahead of
+// launch_mc_region, same contract (pbrk_mc_set_resident)
+bool launch_mc_resident(McArgs a, int nfaces, hipStream_t st);
 extern int g_mc_region_mode, g_mc_lds_mode;         // pbrk_mc_set_kernels (k_mc_region.hip)

@@ -114,6 +114,34 @@
 //      texels alive with ONE statement (JOIN, MC_TAP_JOIN_G1): all four reads fly, one wait; same instructions and arithmetic.  Mip 2
 //      23.75 -> 22.99 ms, the job 48.94 -> 47.92 ms; the 34^2 shape (its loop already waits once) and the 18^2 shape lose with it, the
 //      quarter-face shape gains nothing: they keep the four statements.
+//   2k. (levels of at most 16^2 texels stay resident; k_mc_resident) the 18^2 shape staged one face at a time -- six barriers, a sample met
+//      once per flagged face (1.246 faces per sample on C4 mip 4), every visit the tested body with its two ballots, since only 78.5 % of the
+//      samples are proved and the run loop of 2i, cut into runs of three or four by the tested ones, lost there.  But the whole bordered
+//      level is 6 x 18^2 x 16 B = 31 KB.  k_mc_resident stages it once per tile and then (i) runs, face by face in index order, the samples
+//      binning proves for the tile (region_bin with PROOF and SOLE: one flagged face, every texel on it, taps inside its block) as
+//      certain_sample -- with the unproved samples gone from the face passes a word's proved bits of a face ARE one run, masks[f][w] &
+//      cmask[w], nothing splits it -- and (ii) takes every other sample ONCE in a general pass over ~cmask, each lane selecting the face of
+//      its own direction with v_cube* as the direct kernel does and tapping that face's block through tap_accumulate with a per-lane base
+//      (general_sample).  No pair is visited twice, there is no count-only body, the faces need not partition the directions consistently
+//      (a tie on a cube edge may go to either face: the apron makes both give the same tap up to rounding), and the completeness count and
+//      heal_slice have no role: the general pass takes all 64 lanes, and a proved sample is credited without a test in k_mc_region as well.
+//      In their place the PBR_MC_STATS instantiation re-evaluates, per proved (lane, sample), on_face and the tap bounds (proof_violation;
+//      pbrk_mc_resident_stats, slot 0: must stay 0) and counts the pairs each pass takes.  No absorb test, no head / tail phases, no launch
+//      cut: at roughness 0.6 every one of the 8192 weights is needed.  C2's 16 -> 256^2 level runs the 1389-sample table of roughness 0.03,
+//      most of which a launch cut could drop; that cut is left out of this kernel.
+//      Rule (launch_mc_resident, asked ahead of launch_mc_region): n_src <= 16, n_tab <= 8192 and an output of 256^2 or more take 16 x 16
+//      tiles x 4 slices, the work split, tree, divisor and alpha store of k_mc_region; outputs of 128^2 .. 255^2 take 8 x 8 tiles x 16
+//      slices (one wave holds a tile and a slice, a 16-way tree; MC_RESIDENT_TILE8), smaller ones stay on the level-in-LDS kernel of
+//      k_mc.hip.  FOLD where n_src is a power of two, the unfolded body elsewhere (n_src = 12).  The ORDER of a texel's sum now depends on
+//      what its tile proves, so the tiles are anchored at row 0 of the face, not at the dispatch's first row, and their frames, spread and
+//      centre are those of the whole tile whatever rows the dispatch holds: a texel has the same tile, proof and order in every dispatch,
+//      a row shard equals the full dispatch bit for bit, and a dispatch that starts or ends inside a tile computes the tile and stores its
+//      own rows.  A slice adds its proved samples by face and index, then the rest by index, and in both the samples of one mask word are
+//      summed on their own and enter the slice's sum as one term ("Word sums" at k_mc_resident: on a level of ones 6.6e-7 from the direct
+//      kernel where sums taken straight, and k_mc_region<18, ..>, stand at 2.6e-6): the levels this kernel takes move by a re-association
+//      (C4 mip 4: at most 4.9e-6 relative, 63 ulp); pbrk_mc_set_resident(0) / PBR_MC_RESIDENT=0 give the earlier kernels and bytes.  At
+//      most 47 VGPRs, no spill, no scratch; 36 VALU per proved sample, 43 per general one, six per word and pass; every k_mc_region
+//      instantiation keeps its opcode sequence.  Measured (profiles/resident_levels.md).
 // Each (texel, sample) pair is accumulated exactly once, in an order (66^2 shapes: head phase then tail phase; in each, own face's
 // regions, then the other regions in index order; else regions in index order; sample index inside a region) that depends on the
 // level's shape and the texel's face only, not on the tile: a row-sharded dispatch equals a full one bit for bit.
@@ -183,7 +211,10 @@ struct RegArgs {
     unsigned long long* stats;  // optional: [0] += healed wave-slices, [1] += all wave-slices, [2] += (region, sample) flags, [3] += samples per tile, [4] += regions visited,
                                 // [5] += proved samples (CERT), [6] += absorbed wave-words, [7] += their wave-samples, [8] += of those run through the
                                 // count-only body (a tile's region passes run 4 x [2] wave-samples in all: [2] .. [5] count per block of 256 texels, a 32 x 32 tile four times); PBR_MC_PHASE_STAMPS builds: [9..13] += clocks of
-                                // a workgroup's first lane in frames, clearing + binning, staging, region passes, reduction + store
+                                // a workgroup's first lane in frames, clearing + binning, staging, region passes, reduction + store;
+                                // k_mc_resident (2k): [1] .. [4] per tile as above ([0] and [5] stay: nothing is recomputed, and [5] counts k_mc_region's proved
+                                // samples alone), [16] += (lane, sample) pairs whose proof did not hold, [17] += proved samples per tile, [18] / [19] += pairs
+                                // taken by the proved runs / by the general pass
 };
 
 // direction -> (sc, tc, ma) of face f: the table of v_cubesc / v_cubetc / v_cubema (gen_prefiltered_env_map.glsl:12-23)
@@ -226,7 +257,8 @@ __device__ __forceinline__ void on_face(float sc, float tc, float ma, bool& c1, 
 // JOIN (header, 2j): the four texels are kept alive by ONE statement.  Each empty asm is a use of its read, and the compiler waits for a
 // read ahead of its first use: four statements split the reads into two groups with a wait behind each, one statement lets all four
 // fly and waits once.  Same instructions otherwise, same arithmetic; taken where it measured as a gain (MC_TAP_JOIN_G1).
-template <int RS, bool JOIN = false>
+// VBASE (header, 2k): the base differs per lane (each lane taps the face its own direction falls on) and rides in a vector register.
+template <int RS, bool JOIN = false, bool VBASE = false>
 __device__ __forceinline__ void tap_accumulate(float w, float u, float v, unsigned lds_base, float& ar, float& ag, float& ab) {
     const int il = (int)u, jl = (int)v;
     const float a = __builtin_amdgcn_fractf(u), b = __builtin_amdgcn_fractf(v);
@@ -234,7 +266,8 @@ __device__ __forceinline__ void tap_accumulate(float w, float u, float v, unsign
     // empty asm keeps the fourth component alive); LDS byte address = jl * row + (il << 4) + base (the region's origin
     // is folded into the base) in one shift-add and one 24-bit multiply-add
     unsigned t16, addr;
-    asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(t16) : "v"(il), "s"(lds_base));
+    if constexpr (VBASE) asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(t16) : "v"(il), "v"(lds_base));
+    else asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(t16) : "v"(il), "s"(lds_base));
     asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(addr) : "v"(jl), "s"(RS * 16), "v"(t16));
     lds_v4f_p tp = (lds_v4f_p)(unsigned long long)addr;
     v4f q00 = tp[0], q10 = tp[1], q01 = tp[RS], q11 = tp[RS + 1];
@@ -594,8 +627,8 @@ __device__ __forceinline__ void tile_of_block(const RegArgs& q, int& face, int& 
 // samples its lanes spread over two regions (PBR_MC_WAVE_SHAPE experiment: see DESIGN.md)
 template <int TILE>
 __device__ __forceinline__ void texel_of_thread(const McArgs& p, int tx, int ty, int t, int& x, int& y) {
-    constexpr int QW = TILE / 8, QSH = TILE == 32 ? 2 : 1;               // quadrants per tile edge (a power of two) and its log2: 2 x 2 (TILE 16), 4 x 4 (TILE 32)
-    static_assert(QW == 1 << QSH, "TILE is 16 or 32");
+    constexpr int QW = TILE / 8, QSH = TILE == 32 ? 2 : (TILE == 16 ? 1 : 0);   // quadrants per tile edge (a power of two) and its log2: 2 x 2 (TILE 16), 4 x 4 (TILE 32), 1 (TILE 8: k_mc_resident)
+    static_assert(QW == 1 << QSH, "TILE is 8, 16 or 32");
     const int q8 = t >> 6, l8 = t & 63;
     x = tx * TILE + (q8 & (QW - 1)) * 8 + (l8 & 7);
     y = p.y0 + ty * TILE + (q8 >> QSH) * 8 + (l8 >> 3);
@@ -912,6 +945,189 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 #endif
 }
 
+// ---- levels resident in LDS as a whole (header, 2k) ----
+// Every face is staged with the row pitch of the 18^2 shape, whatever n_src <= 16 is: face f's block starts RES_FACE_BYTES f behind the base.
+#define RES_RS 18
+#define RES_FACE_BYTES (RES_RS * RES_RS * 16)
+
+struct ResArgs {
+    RegArgs q;                  // a.y0, a.rows: the rows of the 16-row tiles that hold the dispatch's rows, counted from row 0 of the face;
+                                // G = 1, RC = n_src + 1, NR = 6; expect, tabmax, cut and absorb are not read
+    int ys, ye;                 // the dispatch's rows [ys, ye): what is stored
+};
+
+// A sample no proof covers: each lane selects the face its own direction falls on, as the direct kernel does (v_cube*; a tie on a cube
+// edge may go to either face: the apron makes both give the same tap up to rounding), and taps that face's block of the resident level.
+// rcp(|2 ma|) n is rcp(ma) n / 2 bit for bit (powers of two), and by the lemma of 2j the folded form rounds the same u, v: the tap
+// coordinates are those of certain_sample and of region_sample on the face chosen.  basef: the LDS byte address of face 0's block as a
+// float; with the face's offset (at most 5 x 5184) it stays an integer below 2^24, exact in fp32.
+__device__ __forceinline__ void general_sample(const v4f e, f3 R, f3 T, f3 B, float nf, float off, float basef, float& ar, float& ag, float& ab) {
+    const float Lx = fmaf(e.x, B.x, fmaf(e.y, T.x, e.z * R.x));
+    const float Ly = fmaf(e.x, B.y, fmaf(e.y, T.y, e.z * R.y));
+    const float Lz = fmaf(e.x, B.z, fmaf(e.y, T.z, e.z * R.z));
+    const float fid = __builtin_amdgcn_cubeid(Lx, Ly, Lz);
+    const float sc = __builtin_amdgcn_cubesc(Lx, Ly, Lz);
+    const float tc = __builtin_amdgcn_cubetc(Lx, Ly, Lz);
+    const float h = __builtin_amdgcn_rcpf(fabsf(__builtin_amdgcn_cubema(Lx, Ly, Lz))) * nf;
+    const unsigned vbase = (unsigned)fmaf(fid, (float)RES_FACE_BYTES, basef);
+    tap_accumulate<RES_RS, false, true>(e.w, fmaf(sc, h, off), fmaf(tc, h, off), vbase, ar, ag, ab);
+}
+
+// PBR_MC_STATS only: 1 when the proof binning gave for this sample does not hold in this lane -- the direction is not on the face
+// (on_face, the tie rule of the face's class) or its tap leaves the face's bordered block (0.5 <= u, v < n + 1.5).
+template <int CLS, bool FOLD>
+__device__ __forceinline__ unsigned proof_violation(const v4f e, const RegionView& V, float nf) {
+    float sc, tc, ma;
+    to_face(e, V, sc, tc, ma);
+    bool c1, c2;
+    on_face<CLS>(sc, tc, FOLD ? ma * V.half_n : ma, c1, c2);
+    const float h = FOLD ? __builtin_amdgcn_rcpf(ma) : __builtin_amdgcn_rcpf(ma) * V.half_n;
+    const float u = fmaf(sc, h, V.off), v = fmaf(tc, h, V.off);
+    return (c1 && c2 && u >= 0.5f && u < nf + 1.5f && v >= 0.5f && v < nf + 1.5f) ? 0u : 1u;
+}
+
+// The proved samples of face F in this wave's slice (words s, s + REG_S, ..; pm: the face's flags, already masked by the proof), as runs of
+// certain_sample: no test, no ballot, no exec mask, and nothing that splits a word's run.
+template <int F, int REG_S, bool FOLD, bool STATS>
+__device__ __forceinline__ void resident_face(const unsigned* __restrict__ pm, int NW, int s, ctab_t tab, unsigned lds_base, f3 R, f3 T, f3 B,
+                                              float nf, float& ar, float& ag, float& ab, unsigned& viol, unsigned& taken) {
+    RegionView V;
+    V.lds_base = lds_base + (unsigned)(F * RES_FACE_BYTES);
+    face_coords(F, B.x, B.y, B.z, V.Pb.x, V.Pb.y, V.Pb.z);
+    face_coords(F, T.x, T.y, T.z, V.Pt.x, V.Pt.y, V.Pt.z);
+    face_coords(F, R.x, R.y, R.z, V.Pr.x, V.Pr.y, V.Pr.z);
+    V.half_n = 0.5f * nf; V.off = 0.5f * nf + 0.5f;
+    if (FOLD) {
+        V.Pb.x *= V.half_n; V.Pt.x *= V.half_n; V.Pr.x *= V.half_n;
+        V.Pb.y *= V.half_n; V.Pt.y *= V.half_n; V.Pr.y *= V.half_n;
+    }
+    unsigned mnext = s < NW ? (unsigned)__builtin_amdgcn_readfirstlane((int)pm[s]) : 0u;
+    for (int w = s; w < NW; w += REG_S) {
+        const unsigned m = mnext;
+        mnext = w + REG_S < NW ? (unsigned)__builtin_amdgcn_readfirstlane((int)pm[w + REG_S]) : 0u;
+        if (STATS) taken += (unsigned)__builtin_popcount(m);
+        if (m == 0u) continue;
+        // a word's samples go to sums of their own, added to the slice's once per word ("Word sums" at k_mc_resident)
+        float wr = 0.0f, wg = 0.0f, wb = 0.0f;
+        each_sample(m, tab + (w << 5), [&](const v4f e) {
+            certain_sample<RES_RS, FOLD>(e, V, wr, wg, wb);
+            if (STATS) viol += proof_violation<(F >> 1), FOLD>(e, V, nf);
+        });
+        ar += wr; ag += wg; ab += wb;
+    }
+}
+
+// Header 2k.  The body reads: stage the level, frames, bin, split the flags into proved-per-face and the rest, the proved runs face by
+// face, the general pass, reduce / store.  STATS: the instantiation launched when the counters are on (PBR_MC_STATS=1); the product
+// kernel carries none of them.
+// TILE 16: 16 x 16 texels x 4 slices, a wave per 8 x 8 quadrant and slice; TILE 8 (128^2 outputs): 8 x 8 texels x 16 slices, one wave holds the
+// tile and one slice (slice s: words s, s + 16, ..), the tree is 16-way.
+// Word sums: the samples a pass takes from one mask word (at most 32, one FMA chain each, unchanged) are added up from zero and that sum
+// is added to the slice's, once per word and pass.  A slice of 2048 samples otherwise makes 8192 roundings at the size of its whole sum --
+// on a level of ones 2.6e-6 from the direct kernel, which adds each weight with one rounding, and as far as k_mc_region<18, ..> stands;
+// with word sums the roundings at that size are the few hundred word additions (16 -> 256^2, level of ones: see profiles/resident_levels.md).
+template <int TILE, bool FOLD, bool STATS>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_mc_resident(const ResArgs g) {
+    constexpr int REG_TX = TILE * TILE, REG_S = 1024 / REG_TX, RS = RES_RS;
+    // LDS layout: the level (6 RS^2 texels), then in words masks[6 NW] | any[6] | dmax[1] | cmask[NW]: region_bin's chain (launch_mc_resident)
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_v[];
+    float4* lvl = (float4*)smem_v;
+    const unsigned lds_base = (unsigned)(unsigned long long)smem_v;
+    const RegArgs& q = g.q;
+    const McArgs& p = q.a;
+    const int NW = q.NW;
+    unsigned* masks = (unsigned*)(smem_v + 6 * RES_FACE_BYTES);
+    unsigned* any = masks + 6 * NW;
+    unsigned* dmax = any + 6;
+    unsigned* cmask = dmax + 1;
+    const int tid = threadIdx.x;
+    const int s = __builtin_amdgcn_readfirstlane(tid / REG_TX);
+    const int t = tid % REG_TX;
+    const int n = p.n_src, nb = n + 2;
+    const float nf = (float)n;
+
+    // ---- 1. the whole bordered level, once: a plain strided copy (region_bin's barriers order it ahead of every tap) ----
+    for (int k = tid; k < 6 * RS * RS; k += 1024) {
+        const int f = k / (RS * RS), r = k - f * (RS * RS), ry = r / RS, rx = r - ry * RS;
+        if (rx < nb && ry < nb) lvl[k] = p.src[(f * nb + ry) * nb + rx];
+    }
+
+    int face, tx, ty, x, y;
+    tile_of_block(q, face, tx, ty);
+    texel_of_thread<TILE>(p, tx, ty, t, x, y);
+    // p.y0 + p.rows is the end of the last tile row or of the face, never of the dispatch: frames, binning and with them the order of
+    // every texel's sum depend on the tile alone
+    const int xc = min(x, p.size - 1), yc = min(y, p.y0 + p.rows - 1);
+    const f3 R = face_texel_dir(face, xc, yc, p.size);
+    const f3 T = tangent_of(R);
+    const f3 B = cross3(T, R);
+    const f3 Rc = face_texel_dir(face, min(tx * TILE + TILE / 2, p.size - 1), min(p.y0 + ty * TILE + TILE / 2, p.y0 + p.rows - 1), p.size);
+    const f3 Tc = tangent_of(Rc);
+    const f3 Bc = cross3(Tc, Rc);
+    ctab_t tab = (ctab_t)(unsigned long long)p.tab;
+
+    // ---- 2. binning, with the proof (one flagged face, every texel of the tile on it, taps inside its block) ----
+    region_bin<true, true, false, true, true>(masks, any, dmax, 6, NW, 1, n + 1, n, R, T, B, Rc, Tc, Bc, tab, p.n_tab, tid, cmask, nullptr, NW,
+                                              0x7fffffff, false, 32 * REG_S);
+    __syncthreads();
+    if (STATS) {                                                   // the counters of k_mc_region's binning, in its units
+        unsigned fl = 0;
+        for (int k = tid; k < 6 * NW; k += 1024) fl += __popc(masks[k]);
+        if (fl) atomicAdd(&q.stats[2], (unsigned long long)fl);
+        if (tid < NW) { const unsigned c = __popc(cmask[tid]); if (c) atomicAdd(&q.stats[17], (unsigned long long)c); }
+        if (tid == 0) { atomicAdd(&q.stats[3], (unsigned long long)p.n_tab); unsigned v = 0; for (int r = 0; r < 6; ++r) v += any[r] != 0u; atomicAdd(&q.stats[4], (unsigned long long)v); }
+    }
+    // masks[f][w] &= cmask[w]: the proved samples of face f (one face each: SOLE); cmask[w] = every other sample of the word.  Thread w
+    // alone touches word w of the seven arrays.
+    if (tid < NW) {
+        const unsigned c = cmask[tid];
+#pragma unroll
+        for (int f = 0; f < 6; ++f) masks[f * NW + tid] &= c;
+        const int left = p.n_tab - (tid << 5);
+        cmask[tid] = ~c & (left >= 32 ? ~0u : (1u << left) - 1u);
+    }
+    __syncthreads();
+
+    // ---- 3. proved runs, face by face in index order; 4. everything else once, each lane on its own face ----
+    float ar = 0.0f, ag = 0.0f, ab = 0.0f;
+    [[maybe_unused]] unsigned viol = 0u, taken = 0u, rest = 0u;
+    if (__builtin_amdgcn_readfirstlane((int)any[0])) resident_face<0, REG_S, FOLD, STATS>(masks, NW, s, tab, lds_base, R, T, B, nf, ar, ag, ab, viol, taken);
+    if (__builtin_amdgcn_readfirstlane((int)any[1])) resident_face<1, REG_S, FOLD, STATS>(masks + NW, NW, s, tab, lds_base, R, T, B, nf, ar, ag, ab, viol, taken);
+    if (__builtin_amdgcn_readfirstlane((int)any[2])) resident_face<2, REG_S, FOLD, STATS>(masks + 2 * NW, NW, s, tab, lds_base, R, T, B, nf, ar, ag, ab, viol, taken);
+    if (__builtin_amdgcn_readfirstlane((int)any[3])) resident_face<3, REG_S, FOLD, STATS>(masks + 3 * NW, NW, s, tab, lds_base, R, T, B, nf, ar, ag, ab, viol, taken);
+    if (__builtin_amdgcn_readfirstlane((int)any[4])) resident_face<4, REG_S, FOLD, STATS>(masks + 4 * NW, NW, s, tab, lds_base, R, T, B, nf, ar, ag, ab, viol, taken);
+    if (__builtin_amdgcn_readfirstlane((int)any[5])) resident_face<5, REG_S, FOLD, STATS>(masks + 5 * NW, NW, s, tab, lds_base, R, T, B, nf, ar, ag, ab, viol, taken);
+    {
+        const float off = 0.5f * nf + 0.5f, basef = (float)lds_base;
+        unsigned mnext = s < NW ? (unsigned)__builtin_amdgcn_readfirstlane((int)cmask[s]) : 0u;
+        for (int w = s; w < NW; w += REG_S) {
+            const unsigned m = mnext;
+            mnext = w + REG_S < NW ? (unsigned)__builtin_amdgcn_readfirstlane((int)cmask[w + REG_S]) : 0u;
+            if (STATS) rest += (unsigned)__builtin_popcount(m);
+            if (m == 0u) continue;
+            float wr = 0.0f, wg = 0.0f, wb = 0.0f;                 // word sums, as in resident_face
+            each_sample(m, tab + (w << 5), [&](const v4f e) { general_sample(e, R, T, B, nf, off, basef, wr, wg, wb); });
+            ar += wr; ag += wg; ab += wb;
+        }
+    }
+    if (STATS) {
+        // [1]: wave-slices (none is ever recomputed: [0] stays); [16]: (lane, sample) pairs whose proof did not hold; [18], [19]: pairs
+        // taken by the proved runs / by the general pass -- together n_tab per texel
+        if (viol) atomicAdd(&q.stats[16], (unsigned long long)viol);
+        if ((tid & 63) == 0) { atomicAdd(&q.stats[1], 1ull); atomicAdd(&q.stats[18], 64ull * taken); atomicAdd(&q.stats[19], 64ull * rest); }
+    }
+
+    // ---- 5. combine the slices and store: the tree, the divisor and the alpha of k_mc_region ----
+    __syncthreads();                                               // everybody is done with the level
+    float* red = (float*)smem_v;
+    reduce_slices<REG_TX, REG_S>(red, s, t, ar, ag, ab);
+    if (x < p.size && y >= g.ys && y < g.ye && s == 0) {
+        float4 o;
+        o.x = red[t * 3 + 0] / p.divisor; o.y = red[t * 3 + 1] / p.divisor; o.z = red[t * 3 + 2] / p.divisor; o.w = p.alpha;
+        p.out[((size_t)face * p.size + y) * p.size + x] = o;
+    }
+}
+
 // the visiting order of the region loops, for host-side checks: the k-th region a tile of `face` visits at G regions per face edge
 extern "C" int pbrk_mc_region_order(int face, int G, int k) {
     if (face < 0 || face > 5 || G < 1 || k < 0 || k >= 6 * G * G) return -1;
@@ -919,7 +1135,7 @@ extern "C" int pbrk_mc_region_order(int face, int G, int k) {
 }
 
 static unsigned long long* g_reg_stats = nullptr;      // device counters, enabled by PBR_MC_STATS=1
-#define REG_STATS_BYTES 128                            // 16 slots (RegArgs::stats)
+#define REG_STATS_BYTES 160                            // 20 slots (RegArgs::stats; [16..19]: k_mc_resident)
 
 // out[0 .. count) = the device counters RegArgs::stats[first_slot ..]
 static int read_stats(unsigned long long* out, int first_slot, int count) {
@@ -1136,6 +1352,28 @@ static void launch_shape(int RS, int tile, const RegArgs& q, unsigned grid, size
     else launch_runs<66, true, 16, LEAN>(q, grid, lds, st);
 }
 
+// The device counters (PBR_MC_STATS=1, read once), or null
+static unsigned long long* reg_stats() {
+    static int stats_on = -1;
+    if (stats_on < 0) {
+        const char* e = getenv("PBR_MC_STATS"); stats_on = e ? atoi(e) : 0;
+        if (stats_on) { if (hipMalloc(&g_reg_stats, REG_STATS_BYTES) != hipSuccess) g_reg_stats = nullptr; else (void)hipMemset(g_reg_stats, 0, REG_STATS_BYTES); }
+    }
+    return g_reg_stats;
+}
+
+// Tile row (relative to the tiles' first row y0, clamped) of the tangent frame's pole on faces +X (t = (1 - vy/vx)/2) and -X
+// (t = (1 + vy/vx)/2), v = the vector of tangent_of: tile_of_block deals the rows of these faces outwards from it
+static void pole_rows(int size, int y0, int tile, int tiles_y, int* pole_row) {
+    const double vy_vx = 6.11831989512 / 12.123825810901;
+    for (int f = 0; f < 2; ++f) {
+        int row = (int)((f == 0 ? 0.5 * (1.0 - vy_vx) : 0.5 * (1.0 + vy_vx)) * size);
+        int tr = (row - y0) / tile;
+        if (row < y0) tr = 0;
+        pole_row[f] = tr < 0 ? 0 : (tr > tiles_y - 1 ? tiles_y - 1 : tr);
+    }
+}
+
 // Which tile serves a level (header 2h): a function of the level alone -- n_src, n_tab, the output size -- never of the dispatch's faces
 // or rows, so a row shard equals the full dispatch bit for bit.  32 x 32 x 1 needs the quarter-face shape (its body is the shortest and
 // its prologue the largest share) and NW <= 64 (one ballot of region_pass_runs); the rule adds size >= MC_TILE32_MIN_SIZE: below it
@@ -1147,7 +1385,6 @@ static bool mc_tile32(int n_src, int n_tab, int size) {
 }
 
 bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
-    static int stats_on = -1;
     if (g_mc_region_mode < 0) { const char* e = getenv("PBR_MC_REGION"); g_mc_region_mode = e ? atoi(e) : 1; }
     if (!g_mc_region_mode) return false;
     // shape conditions (level only): source too big for LDS as a whole, enough 16x16 tiles to fill the chip twice over
@@ -1169,11 +1406,7 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
     if (lds > 80 * 1024) { q.absorb = 0; lds = lds_fixed; }
     if (lds < (size_t)1024 * 3 * 4) lds = (size_t)1024 * 3 * 4;      // the slices' partial sums (REG_S * REG_TX = 1024 texel-slices, whatever the tile)
     if (lds > 80 * 1024) return false;                             // two workgroups per CU or not at all
-    if (stats_on < 0) {
-        const char* e = getenv("PBR_MC_STATS"); stats_on = e ? atoi(e) : 0;
-        if (stats_on) { if (hipMalloc(&g_reg_stats, REG_STATS_BYTES) != hipSuccess) g_reg_stats = nullptr; else (void)hipMemset(g_reg_stats, 0, REG_STATS_BYTES); }
-    }
-    q.stats = g_reg_stats;
+    q.stats = reg_stats();
     // Tile size: 16 x 16 output texels x 4 slices of the sample table, but for the quarter-face level with a short table and a big
     // output (mc_tile32: header 2h), which takes 32 x 32 texels x 1 slice.  Measured and dropped: 8 x 8 tiles x 16
     // slices (halve the frame spread, pay four times the per-tile work: C4 mip 2 44.0 -> 53.5 ms), 32 x 16 tiles, and 32 x 32 tiles on
@@ -1184,15 +1417,7 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
     q.a.tiles_x = (a.size + tile - 1) / tile;
     const int tiles_y = (a.rows + tile - 1) / tile;
     q.a.tiles_per_face = q.a.tiles_x * tiles_y;                            // tiles start at the dispatch's first row, whatever it is
-    {   // output row of the tangent frame's pole on faces +X (t = (1 - vy/vx)/2) and -X (t = (1 + vy/vx)/2), v = the vector of tangent_of
-        const double vy_vx = 6.11831989512 / 12.123825810901;
-        for (int f = 0; f < 2; ++f) {
-            int row = (int)((f == 0 ? 0.5 * (1.0 - vy_vx) : 0.5 * (1.0 + vy_vx)) * a.size);
-            int tr = (row - a.y0) / tile;
-            if (row < a.y0) tr = 0;
-            q.pole_row[f] = tr < 0 ? 0 : (tr > tiles_y - 1 ? tiles_y - 1 : tr);
-        }
-    }
+    pole_rows(a.size, a.y0, tile, tiles_y, q.pole_row);
     const unsigned grid = (unsigned)(q.a.tiles_per_face * nfaces);
     // Lean prologue: the maxima of the absorbed-word test come from k_mc_prep, once per launch, instead of from every tile.  Without
     // a scratch slot (see prep_acquire) the launch takes the prologue that builds them itself: the same bytes.
@@ -1223,5 +1448,61 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
     }
     if (lean) launch_shape<true>(RS, tile, q, grid, lds, st);
     else launch_shape<false>(RS, tile, q, grid, lds, st);
+    return true;
+}
+
+// ---- header 2k: levels up to 16^2 with outputs of 256^2 and more stay resident in LDS ----
+// pbrk_mc_set_resident(0): such a level runs the kernel it ran before (n_src = 16: k_mc_region<18, ..>; smaller: the level-in-LDS kernel)
+// (-1: the environment variable PBR_MC_RESIDENT, else the default 1, as for pbrk_mc_set_kernels)
+#ifndef MC_RESIDENT_TILE8
+#define MC_RESIDENT_TILE8 1                            // outputs of 128^2 .. 255^2 take 8 x 8 tiles x 16 slices; 0: they keep the level-in-LDS kernel
+#endif
+static int g_mc_resident = -1;
+extern "C" void pbrk_mc_set_resident(int on) { g_mc_resident = on < 0 ? -1 : (on ? 1 : 0); }
+// PBR_MC_STATS=1, since the last reset: {(lane, sample) pairs whose proof did not hold (must stay 0), proved samples summed over
+// tiles, pairs taken by the proved runs, pairs taken by the general pass}
+extern "C" int pbrk_mc_resident_stats(unsigned long long* out4) { return read_stats(out4, 16, 4); }
+
+template <int TILE, bool FOLD, bool STATS>
+static void launch_resident_t(const ResArgs& g, unsigned grid, size_t lds, hipStream_t st) {
+    hipLaunchKernelGGL((k_mc_resident<TILE, FOLD, STATS>), dim3(grid), dim3(1024), lds, st, g);
+}
+template <int TILE>
+static void launch_resident_tile(const ResArgs& g, bool fold, unsigned grid, size_t lds, hipStream_t st) {
+    if (g.q.stats) { if (fold) launch_resident_t<TILE, true, true>(g, grid, lds, st); else launch_resident_t<TILE, false, true>(g, grid, lds, st); }
+    else { if (fold) launch_resident_t<TILE, true, false>(g, grid, lds, st); else launch_resident_t<TILE, false, false>(g, grid, lds, st); }
+}
+
+// The rule reads the level alone -- n_src, n_tab, the output size -- and the tiles are anchored at row 0 of the face, not at the
+// dispatch's first row: a texel sits in the same tile, with the same proof and the same order of its sum, in every dispatch that holds
+// it, so a row shard equals the full dispatch bit for bit.  A dispatch that starts or ends inside a tile computes the whole tile and
+// stores its own rows.
+bool launch_mc_resident(McArgs a, int nfaces, hipStream_t st) {
+    if (g_mc_region_mode < 0) { const char* e = getenv("PBR_MC_REGION"); g_mc_region_mode = e ? atoi(e) : 1; }
+    if (g_mc_resident < 0) { const char* e = getenv("PBR_MC_RESIDENT"); g_mc_resident = e ? (atoi(e) ? 1 : 0) : 1; }
+    if (!g_mc_region_mode || !g_mc_resident) return false;
+    if (a.n_src > 16 || a.size < (MC_RESIDENT_TILE8 ? 128 : 256) || a.n_tab < 1 || a.n_tab > 8192) return false;
+    ResArgs g;
+    RegArgs& q = g.q;
+    q.a = a;
+    q.G = 1; q.RC = a.n_src + 1; q.NR = 6;
+    q.NW = (a.n_tab + 31) / 32;
+    for (int s = 0; s < REG_MAX_S; ++s) q.expect[s] = 0;
+    q.tabmax = nullptr; q.cut = 0; q.absorb = 0;
+    q.stats = reg_stats();
+    // the LDS layout at the top of k_mc_resident; the slices' partial sums overlay the level (12 KB of its 30)
+    const size_t lds = (size_t)6 * RES_FACE_BYTES + ((size_t)6 * q.NW + 6 + 1 + q.NW) * 4;
+    const int tile = a.size >= 256 ? 16 : 8, ty0 = a.y0 / tile, ty1 = (a.y0 + a.rows - 1) / tile, tiles_y = ty1 - ty0 + 1;
+    g.ys = a.y0; g.ye = a.y0 + a.rows;
+    q.a.y0 = ty0 * tile;
+    q.a.rows = ((ty1 + 1) * tile < a.size ? (ty1 + 1) * tile : a.size) - q.a.y0;
+    q.a.tiles_x = (a.size + tile - 1) / tile;
+    q.a.tiles_per_face = q.a.tiles_x * tiles_y;
+    pole_rows(a.size, q.a.y0, tile, tiles_y, q.pole_row);
+    const unsigned grid = (unsigned)(q.a.tiles_per_face * nfaces);
+    // FOLD as in launch_runs: from n_src alone
+    const bool fold = g_mc_fold && (a.n_src & (a.n_src - 1)) == 0;
+    if (tile == 16) launch_resident_tile<16>(g, fold, grid, lds, st);
+    else launch_resident_tile<8>(g, fold, grid, lds, st);
     return true;
 }
