@@ -178,6 +178,16 @@ void pbrk_mc_set_tile32(int mode);
 void pbrk_mc_set_fold(int on);
 /* 1 when the last region-kernel launch ran a folded instantiation, else 0 */
 int pbrk_mc_last_fold(void);
+/* the completeness net of the region kernel (k_mc_region.hip, step 3 and 2l): every wave counts the (texel, sample) pairs it takes and
+ * recomputes its slice when the count is short.  -1 (default): on when the device counters are on (PBR_MC_STATS=1), off otherwise;
+ * 0: off wherever a net-less instantiation exists (the lean run loops); 1: always on.  Bit-identical either way.  Tests and A-B runs. */
+void pbrk_mc_set_net(int mode);
+/* 1 when the last region-kernel launch carried the net, 0 when it ran a net-less instantiation */
+int pbrk_mc_last_net(void);
+/* host twin of what k_mc_cut writes for the net-less kernel's early end of a pass (k_mc_region.hip, 2l): mono4[s], s < S (S = 1, 2 or 4
+ * slices; slice s owns the mask words s, s + S, ..), is the first word of slice s from which the slice's largest weights per word never
+ * rise again; a slice without words gets s.  n <= 8192 weights.  Returns 0, or -1 for bad arguments.  Needs no GPU. */
+int pbrk_mc_mono_slices(const float* weights, int n, int S, int* mono4);
 /* levels of at most 16^2 texels with outputs of 256^2 and more, resident in LDS as a whole (k_mc_region.hip, 2k): the samples binning
  * proves for a whole tile run test-free per face, every other sample once, each lane on its own face.  1 on, 0: the kernel such a level ran
  * before, -1 (default) = the environment (PBR_MC_RESIDENT) or 1.  The two add a texel's samples in different orders: close, not the same bytes.  Tests and A-B runs. */

@@ -2,6 +2,7 @@
 """Time pbrk_mc_filter (K4b) on synthetic levels: picoseconds per sample evaluation and clocks per wave-sample per CU for a
 given (n_src, out_size, roughness).  Kernel choice follows the library (env PBR_MC_LDS / PBR_MC_REGION / PBR_MC_BINNED); env
 PBR_MC_TILE32 = -1 | 0 | 1 goes to pbrk_mc_set_tile32 (the region kernel's 32 x 32 tile: by rule, never, wherever the shape allows);
+PBR_MC_NET = -1 | 0 | 1 goes to pbrk_mc_set_net (the region kernel's completeness net: by rule, off where it can be, always on);
 PBR_MC_RESIDENT=0 keeps levels of at most 16^2 texels off k_mc_resident (the library reads it).
    python3 tools/mc_probe.py n_src out_size [roughness] [rows] [face0 face1]"""
 import ctypes as C
@@ -27,6 +28,8 @@ def main():
     L = pbrhip.init(0)
     if os.environ.get("PBR_MC_TILE32"):
         L.pbrk_mc_set_tile32(int(os.environ["PBR_MC_TILE32"]))
+    if os.environ.get("PBR_MC_NET"):
+        L.pbrk_mc_set_net(int(os.environ["PBR_MC_NET"]))
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(1)
     lvl = rng.random((6, n_src, n_src, 4), dtype=np.float32) + 0.1

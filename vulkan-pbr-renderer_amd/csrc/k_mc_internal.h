@@ -114,6 +114,21 @@ __host__ __device__ inline int mc_launch_cut(const unsigned* wbits, int NW, cons
     return mc_launch_cut_s(wbits, NW, 4, H, min_bits, max_bits, cut4);
 }
 
+// k_mc_region.hip, header 2l: mono[s], s < S, is the first word of slice s (words s, s + S, .. below NW) from which the slice's word maxima
+// wbits[] never rise again -- compared as bit patterns, which for weights >= +0 is their order as floats; a slice without words gets s.
+// A pass of the net-less kernel that finds a word w >= mono[s] absorbed ends there: every later word of the slice has a maximum, hence a
+// threshold (absorb_threshold is monotone in the word maximum for one region maximum), no larger, and the sums have not moved.
+__host__ __device__ inline void mc_mono_from(const unsigned* wbits, int NW, int S, int* mono) {
+    for (int s = 0; s < S; ++s) {
+        int k = s;
+        if (s < NW) {
+            k = s + S * ((NW - 1 - s) / S);                            // the slice's last word: monotone on its own
+            while (k - S >= s && wbits[k - S] >= wbits[k]) k -= S;
+        }
+        mono[s] = k;
+    }
+}
+
 // k_mc_region.hip: taps from LDS-staged regions of the source level.  Returns false when the kernel does not apply
 // (the caller then takes the direct kernel); the decision depends on the level's shape only, never on the dispatched range.
 bool launch_mc_region(McArgs a, int nfaces, hipStream_t st);

@@ -142,6 +142,33 @@
 //      (C4 mip 4: at most 4.9e-6 relative, 63 ulp); pbrk_mc_set_resident(0) / PBR_MC_RESIDENT=0 give the earlier kernels and bytes.  At
 //      most 47 VGPRs, no spill, no scratch; 36 VALU per proved sample, 43 per general one, six per word and pass; every k_mc_region
 //      instantiation keeps its opcode sequence.  Measured (profiles/resident_levels.md).
+//   2l. (the completeness net out of the product kernel; NET) step 3 adds nothing to any sum.  It was there to catch a flag binning failed to
+//      set: every wave counts the pairs it takes (cnt += 1 under the exec mask of every tested sample, a popcount per word for the proved
+//      ones, cut_credit for the words of the launch cut), an absorbed word (2c) still walks its unproved samples through the count-only body
+//      -- frame transform, in-face and in-region tests, ballot, its own table load, no taps -- only so that the count stays complete, and a
+//      wave whose count is short of expect[s] recomputes its slice (heal_slice; seen once, the ulp case of 2i, which SOLE closed).  NET = false is the lean run loop (RUNS and LEAN, both FOLD values: <66, true, 32>,
+//      <66, true, 16>, <66, false, 16>, <34, false, 16>) without cnt, the credits, the read of expect[], the final ballot and heal_slice; an
+//      absorbed word ends at `continue` behind its threshold test.  Every test that decides what is accumulated stays (the wave-uniform
+//      early exit of SUB, every `in`): the samples accumulated, their order and arithmetic are the same, so are the bytes.  With heal_slice
+//      gone nothing behind the passes reads the frame, and B is formed again from T and R per staging (the same products and differences)
+//      instead of living across the passes: the quarter-face instantiations otherwise spill one VGPR.  At most 61 VGPRs, no VGPR spill, no scratch.
+//      The 34^2 shape has no absorbed words and loses only the count (MC_NET_OFF_34).  Every NET = true instantiation and k_mc_prep keep
+//      their opcode sequences; RegArgs keeps its layout.
+//      The early end of a pass (MC_MONO_EXIT): with no count-only bodies an absorbed word costs only its test -- two LDS reads through
+//      readfirstlane, a scalar load, three compares, a ballot -- and the tail of a pass is a run of such words.  If the slice's word maxima
+//      never rise from word k on, then once a word w >= k is absorbed in a pass every later word of that pass is absorbed too: the sums do
+//      not move over skipped words and absorb_threshold is monotone in the word maximum for one region maximum.  The pass ends there: same
+//      bytes.  k_mc_cut writes k per slice behind the regions' minima (mc_mono_from, k_mc_internal.h; pbrk_mc_mono_slices is its host twin;
+//      q.cut bit 1 says it is there: a launch without k_mc_cut walks every word as before); the reference's tables are monotone from their
+//      head words on (k = s).  Only NET = false takes the exit; under the counters the words it leaves are credited to stats[6] and [7].
+//      Where the net still runs: whenever the device counters are on (PBR_MC_STATS=1: the whole test suite, so every healed == 0 it asserts
+//      is the real check), under pbrk_mc_set_net(1), and in every instantiation that has no net-less form (the 18^2 shape, RUNS = false,
+//      LEAN = false: the yardsticks of pbrk_mc_set_runs / _prologue).  pbrk_mc_set_net(-1), the default, reads the counters' state and nothing
+//      of the dispatch, so a row shard equals the full dispatch; pbrk_mc_last_net tells what the last launch took.  With the net off and the
+//      counters on, stats[1] is still counted, [0] and [8] stay 0, [2] .. [7] keep their meaning.  What guards the product path: the byte
+//      comparison against the checked instantiation on every shape, table length, row shard, work unit and hostile level of
+//      tests/test_gpu_mc_net.py (C4 mips 1 - 3 at full size among them), and the every-texel cross-check against the direct kernel in
+//      tests/test_gpu_configs.py.  As k_mc_resident (2k), which never had a net in its product kernel.  Measured: profiles/net_off.md.
 // Each (texel, sample) pair is accumulated exactly once, in an order (66^2 shapes: head phase then tail phase; in each, own face's
 // regions, then the other regions in index order; else regions in index order; sample index inside a region) that depends on the
 // level's shape and the texel's face only, not on the tile: a row-sharded dispatch equals a full one bit for bit.
@@ -192,6 +219,14 @@ typedef const __attribute__((address_space(4))) unsigned* cu32_t;
 #ifndef MC_TILE32_SUB
 #define MC_TILE32_SUB 1
 #endif
+// Header 2l, decided by measurement: the 34^2 shape has no absorbed words and loses only the count with its net; 0 keeps its net always.
+#ifndef MC_NET_OFF_34
+#define MC_NET_OFF_34 1
+#endif
+// Header 2l, decided by measurement: the net-less kernel ends a pass at the first absorbed word behind which the slice's word maxima never rise.
+#ifndef MC_MONO_EXIT
+#define MC_MONO_EXIT 1
+#endif
 #ifndef MC_TILE32_MIN_SIZE
 #define MC_TILE32_MIN_SIZE 1024
 #endif
@@ -206,7 +241,8 @@ struct RegArgs {
     int pole_row[2];            // faces +X / -X: tile row (relative to the dispatch's first row, clamped) nearest to the pole of the tangent frame
     const unsigned* tabmax;     // lean prologue, absorb: [NW] largest weight bit pattern per mask word, then [NR] largest staged R, G, B bit pattern per
                                 // region (k_mc_prep, once per launch); null with the parent's prologue
-    int cut;                    // header 2g: tabmax holds, behind the maxima, the first cut word of each slice (k_mc_cut); 0: no word is dropped
+    int cut;                    // header 2g: tabmax holds, behind the maxima, the first cut word of each slice (k_mc_cut); 0: no word is dropped;
+                                // bit 1 (header 2l): and, behind the regions' minima, the first word of each slice with no rise behind it
     int absorb;                 // skip mask words whose samples are absorbed by every lane's sums (pbrk_mc_set_absorb; bit-identical)
     unsigned long long* stats;  // optional: [0] += healed wave-slices, [1] += all wave-slices, [2] += (region, sample) flags, [3] += samples per tile, [4] += regions visited,
                                 // [5] += proved samples (CERT), [6] += absorbed wave-words, [7] += their wave-samples, [8] += of those run through the
@@ -331,7 +367,8 @@ __device__ __forceinline__ void certain_sample(const v4f e, const RegionView& V,
 // s_bcnt1; only the wave-uniform early exit of SUB keeps a ballot.
 // FOLD (header, 2j): sc and tc arrive scaled by half_n; the in-face test compares them with ma half_n (exact: the same decisions), and
 // the multiply of the reciprocal has moved there.
-template <int RS, bool SUB, int CLS, bool ACC = true, bool FOLD = false, bool JOIN = false>
+// NET = false (header, 2l): the pair is not counted; every test that decides what is accumulated stays.
+template <int RS, bool SUB, int CLS, bool ACC = true, bool FOLD = false, bool JOIN = false, bool NET = true>
 __device__ __forceinline__ void lane_sample(const v4f e, const RegionView& V, float& ar, float& ag, float& ab, unsigned& cnt) {
     float sc, tc, ma;
     to_face(e, V, sc, tc, ma);
@@ -343,7 +380,7 @@ __device__ __forceinline__ void lane_sample(const v4f e, const RegionView& V, fl
     const float u = fmaf(sc, h, V.off), v = fmaf(tc, h, V.off);
     if (SUB) in = in && u >= V.ulo && u < V.uhi && v >= V.vlo && v < V.vhi;
     if (in) {
-        cnt += 1u;
+        if (NET) cnt += 1u;
         if (ACC) tap_accumulate<RS, JOIN>(e.w, u, v, V.lds_base, ar, ag, ab);
     }
 }
@@ -458,15 +495,17 @@ __device__ __forceinline__ void region_pass(const RegionView& V, const unsigned*
 //   * CERT: the proved samples below the next tested one run as a run of certain_sample (no per-sample proved-bit test, no exec
 //     join), then the tested one, in index order;
 //   * tested samples use lane_sample (one ballot chain), and every loop issues the next table entry's load ahead of the body.
-template <int RS, bool SUB, int CLS, int REG_S, bool CERT, bool LEAN, bool FOLD>
+// NET = false (header, 2l): nothing is counted and cnt is not touched.  An absorbed word ends behind its threshold test -- no credit, no
+// count-only walk, no read of cwords for the credit.
+template <int RS, bool SUB, int CLS, int REG_S, bool CERT, bool LEAN, bool FOLD, bool NET = true>
 __device__ __forceinline__ void region_pass_runs(const RegionView& V, const unsigned* __restrict__ mwords, const unsigned* __restrict__ cwords, cu32_t wmg,
                                                  unsigned rbits, unsigned* skc, int NW, int s, unsigned long long wsel, ctab_t tab,
-                                                 float& ar, float& ag, float& ab, unsigned& cnt) {
+                                                 float& ar, float& ag, float& ab, unsigned& cnt, const RegArgs& q) {
     const int wl = s + REG_S * (int)(threadIdx.x & 63);
     unsigned long long nz = __builtin_amdgcn_ballot_w64(wl < NW && mwords[wl] != 0u) & wsel;
     // header 2j: with the fold, the 66^2 whole-face shape also takes the tap whose four reads wait once (per shape, by measurement)
     constexpr bool JOIN = FOLD && RS == 66 && !SUB && MC_TAP_JOIN_G1 != 0;
-    auto tested = [&](const v4f e) { lane_sample<RS, SUB, CLS, true, FOLD, JOIN>(e, V, ar, ag, ab, cnt); };
+    auto tested = [&](const v4f e) { lane_sample<RS, SUB, CLS, true, FOLD, JOIN, NET>(e, V, ar, ag, ab, cnt); };
     while (nz) {
         const int w = s + REG_S * (int)__builtin_ctzll(nz);
         nz &= nz - 1ull;
@@ -477,6 +516,21 @@ __device__ __forceinline__ void region_pass_runs(const RegionView& V, const unsi
         if (wb < 0x7f800000u) {
             const float T = absorb_threshold(__uint_as_float(wb), __uint_as_float(rbits));
             if (__builtin_amdgcn_ballot_w64(!(ar >= T && ag >= T && ab >= T)) == 0ull) {
+                if (!NET) {                                                // absorbed for all 64 lanes: the sums do not change, the word ends here
+                    count_absorbed(skc, m, 0u);
+                    // Header 2l: the slice's word maxima do not rise from word mono on (mc_mono_from; k_mc_cut wrote it behind the regions' minima,
+                    // q.cut bit 1), so every later word of this pass has a threshold no larger and meets the same sums -- absorbed as well.  The
+                    // pass ends; under the counters the words it leaves are credited.  Read here, not ahead of the pass: it would live in a scalar
+                    // register across every sample of the pass, and the loop has none to spare.
+                    if (MC_MONO_EXIT == 0 || !(q.cut & 2) || w < (int)wmg[NW + 2 * q.NR + 4 + s]) continue;
+                    if (skc)
+                        while (nz) {
+                            const int wr = s + REG_S * (int)__builtin_ctzll(nz);
+                            nz &= nz - 1ull;
+                            count_absorbed(skc, (unsigned)__builtin_amdgcn_readfirstlane((int)mwords[wr]), 0u);
+                        }
+                    break;
+                }
                 if (!CERT) c = (unsigned)__builtin_amdgcn_readfirstlane((int)cwords[w]);
                 cnt += (unsigned)__builtin_popcount(m & c);                // every lane takes every proved sample
                 count_absorbed(skc, m, m & ~c);
@@ -485,7 +539,7 @@ __device__ __forceinline__ void region_pass_runs(const RegionView& V, const unsi
             }
         }
         if (!CERT) { each_sample(m, tw, tested); continue; }
-        cnt += (unsigned)__builtin_popcount(m & c);
+        if (NET) cnt += (unsigned)__builtin_popcount(m & c);
         unsigned mc = m & c, mu = m & ~c;
         for (;;) {
             const unsigned below = mu ? (mu & (0u - mu)) - 1u : ~0u;     // the samples before the next tested one (all: none left)
@@ -750,11 +804,14 @@ __device__ __forceinline__ void reduce_slices(float* red, int s, int t, float ar
 // RUNS (66^2 shapes and the 34^2 shape): the region loop visits the flagged regions only and runs region_pass_runs (round 5; cnt per lane)
 // LEAN: the prologue of header 2f (pbrk_mc_set_prologue); false: the one before it, kept as the yardstick
 // FOLD (header, 2j; power-of-two levels under RUNS and LEAN): half_n rides in the sc and tc rows of the permuted frame
+// NET (header, 2l): step 3, the completeness net -- the pair count, the credits, the count-only bodies, the check and heal_slice.  false:
+// none of it (the lean run loops only); expect[] is not read
 // The body reads: frames, bin, credit, the loop of (stage, pass) over the flagged regions, check / heal, reduce / store.
-template <int RS, bool SUB, int TILE, bool RUNS = false, bool LEAN = false, bool FOLD = false>
+template <int RS, bool SUB, int TILE, bool RUNS = false, bool LEAN = false, bool FOLD = false, bool NET = true>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_mc_region(const RegArgs q) {
     constexpr int REG_TX = TILE * TILE, REG_S = 1024 / REG_TX;
     static_assert(!FOLD || (RUNS && LEAN && RS != 18), "FOLD: the run loop of the lean 66^2 / 34^2 shapes only");
+    static_assert(NET || (RUNS && LEAN && RS != 18), "NET = false: the run loop of the lean 66^2 / 34^2 shapes only");
     // see the header, 2b and 2i: quarter faces always; whole faces only with the run loop, which pays no per-sample choice of body
     constexpr bool CERT = SUB || (RUNS && (RS != 66 || MC_CERT_G1 != 0));
     // see the header, 2c: compiled for the 66^2 region shapes only.  The 34^2 / 18^2 levels of C4 (mips 3, 4: weights fall to ~e^-6)
@@ -827,7 +884,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     float ar = 0.0f, ag = 0.0f, ab = 0.0f;
     // expect[s] less the samples of the slice's cut words, formed here as a credit: the count starts at what the cut took out, so
     // nothing of it stays alive across the passes
-    unsigned cnt = cut_on ? cut_credit<REG_S, RUNS>((int)wmg[NW + NR + s], NW, p.n_tab) : 0u;
+    unsigned cnt = (NET && cut_on) ? cut_credit<REG_S, RUNS>((int)wmg[NW + NR + s], NW, p.n_tab) : 0u;
     if (q.stats) {                                                 // diagnostics: (region, sample) flags of this tile, samples, regions visited
         __syncthreads();
         unsigned fl = 0, cfl = 0, cwd = 0;
@@ -866,7 +923,16 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         RegionView V;
         V.lds_base = lds_base - (unsigned)(oy * RS + ox) * 16u;
         // signed permutation of the frame for this face
-        face_coords(f, B.x, B.y, B.z, V.Pb.x, V.Pb.y, V.Pb.z);
+        // NET = false: nothing behind the passes reads the frame (no heal_slice), and B is formed again per staging from a copy of T that is
+        // opaque to the optimiser -- the same six products and three differences, the same bits -- instead of staying alive across the passes:
+        // at the 64-VGPR budget the quarter-face instantiations otherwise spill one of its components
+        f3 Bv = B;
+        if constexpr (!NET) {
+            f3 Tq = T;
+            asm volatile("" : "+v"(Tq.x), "+v"(Tq.y), "+v"(Tq.z));
+            Bv = cross3(Tq, R);
+        }
+        face_coords(f, Bv.x, Bv.y, Bv.z, V.Pb.x, V.Pb.y, V.Pb.z);
         face_coords(f, T.x, T.y, T.z, V.Pt.x, V.Pt.y, V.Pt.z);
         face_coords(f, R.x, R.y, R.z, V.Pr.x, V.Pr.y, V.Pr.z);
         V.half_n = half_n; V.off = off;
@@ -882,7 +948,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         const int w0 = (TWO && ph) ? s + REG_S : s, w1 = (TWO && !ph) ? min(NW, s + 1) : NW;
         auto pass = [&](auto cls) {                                // cls: the face's major axis as a compile-time constant
             constexpr int CLS = decltype(cls)::value;
-            if (RUNS) region_pass_runs<RS, SUB, CLS, REG_S, CERT, LEAN, FOLD>(V, mw, cmask, wmg, rbits, sc, NW, s, wsel, tab, ar, ag, ab, cnt);
+            if (RUNS) region_pass_runs<RS, SUB, CLS, REG_S, CERT, LEAN, FOLD, NET>(V, mw, cmask, wmg, rbits, sc, NW, s, wsel, tab, ar, ag, ab, cnt, q);
             else region_pass<RS, SUB, CLS, REG_S, CERT, LEAN>(V, mw, cmask, wmg, rbits, sc, NW, w0, w1, tab, ar, ag, ab, cnt);
         };
         switch (f >> 1) {
@@ -913,12 +979,15 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     // exactly -- so the total is right exactly when no lane missed a sample
     // RUNS: cnt per lane; a wave recomputes when any lane's count is off (a stronger test than the total)
     [[maybe_unused]] const unsigned long long st3 = STAMP();
-    const bool healed = RUNS ? __builtin_amdgcn_ballot_w64(cnt != (unsigned)q.expect[s]) != 0ull : cnt != 64u * (unsigned)q.expect[s];
-    if (healed) heal_slice<REG_S>(p, tab, NW, s, R, T, B, ar, ag, ab);
-    if (q.stats && (tid & 63) == 0) {
-        if (healed) atomicAdd(&q.stats[0], 1ull);
-        atomicAdd(&q.stats[1], 1ull);
-    }
+    // NET = false: no count, no check, nothing to heal; the wave-slices are still counted
+    if constexpr (NET) {
+        const bool healed = RUNS ? __builtin_amdgcn_ballot_w64(cnt != (unsigned)q.expect[s]) != 0ull : cnt != 64u * (unsigned)q.expect[s];
+        if (healed) heal_slice<REG_S>(p, tab, NW, s, R, T, B, ar, ag, ab);
+        if (q.stats && (tid & 63) == 0) {
+            if (healed) atomicAdd(&q.stats[0], 1ull);
+            atomicAdd(&q.stats[1], 1ull);
+        }
+    } else if (q.stats && (tid & 63) == 0) atomicAdd(&q.stats[1], 1ull);
 
     // ---- 4. combine the slices and store ----
     __syncthreads();                                               // everybody is done with the staged region
@@ -1153,12 +1222,14 @@ extern "C" int pbrk_mc_region_flag_stats(unsigned long long* out3) { return read
 extern "C" int pbrk_mc_region_phase_stats(unsigned long long* out5) { return read_stats(out5, 9, 5); }       // PBR_MC_PHASE_STAMPS builds; zeros otherwise (RegArgs::stats [9..13])
 
 static int g_last_fold = 0;                            // whether the last region launch took a FOLD instantiation (pbrk_mc_last_fold)
-template <int RS, bool SUB, int TILE, bool RUNS = false, bool LEAN = false, bool FOLD = false>
+static int g_last_net = 1;                             // whether the last region launch carried the completeness net (pbrk_mc_last_net)
+template <int RS, bool SUB, int TILE, bool RUNS = false, bool LEAN = false, bool FOLD = false, bool NET = true>
 static void launch_region_t(const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
     static bool attr_set = false;
-    if (!attr_set) { (void)hipFuncSetAttribute((const void*)k_mc_region<RS, SUB, TILE, RUNS, LEAN, FOLD>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
+    if (!attr_set) { (void)hipFuncSetAttribute((const void*)k_mc_region<RS, SUB, TILE, RUNS, LEAN, FOLD, NET>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
     g_last_fold = FOLD ? 1 : 0;
-    hipLaunchKernelGGL((k_mc_region<RS, SUB, TILE, RUNS, LEAN, FOLD>), dim3(grid), dim3(1024), lds, st, q);
+    g_last_net = NET ? 1 : 0;
+    hipLaunchKernelGGL((k_mc_region<RS, SUB, TILE, RUNS, LEAN, FOLD, NET>), dim3(grid), dim3(1024), lds, st, q);
 }
 
 // ---- the launch's maxima (header, 2f) ----
@@ -1204,6 +1275,8 @@ __global__ __launch_bounds__(256) void k_mc_prep(const float4* __restrict__ src,
 // One wave behind k_mc_prep on the same stream: lanes 0 .. S - 1 add up the weights of their slice's head word in double, in index order;
 // lane 0 folds the regions' extrema and writes the first cut word of each slice to out[NW + NR .. + 4) (mc_launch_cut_s, k_mc_internal.h).
 // S (1, 2 or 4) is the slice count of the region kernel behind it; all four slots are written, slot j with the cut of slice j % S.
+// Header 2l: out[NW + 2 NR + 4 .. + 4), behind the regions' minima: per slice the first word from which the word maxima never rise again
+// (mc_mono_from), slots as for the cut.
 __global__ __launch_bounds__(64) void k_mc_cut(const float4* __restrict__ tab, int n_tab, int NW, int NR, int S, unsigned* __restrict__ out) {
     __shared__ double H[4];
     const int tid = threadIdx.x;
@@ -1220,6 +1293,10 @@ __global__ __launch_bounds__(64) void k_mc_cut(const float4* __restrict__ tab, i
     int cut4[4];
     mc_launch_cut_s(out, NW, S, H, m, M, cut4);
     for (int s = 0; s < 4; ++s) out[NW + NR + s] = (unsigned)cut4[s % S];
+    // header 2l: per slice, the first word from which the word maxima never rise again, behind the regions' minima
+    int mono4[4];
+    mc_mono_from(out, NW, S, mono4);
+    for (int s = 0; s < 4; ++s) out[NW + 2 * NR + 4 + s] = (unsigned)mono4[s % S];
 }
 
 // The same cut on the host, from the table's weights and the level's extrema (bit patterns): what k_mc_cut writes for them.  Needs no GPU.
@@ -1246,6 +1323,24 @@ extern "C" int pbrk_mc_launch_cut_slices(const float* weights, int n, int S, uns
         for (int s = 0; s < S; ++s)
             for (int i = 0; i < 32; ++i) H[s] += (double)weights[(s << 5) + i];
     return mc_launch_cut_s(wbits, NW, S, H, min_bits, max_bits, cut4);
+}
+
+// mc_mono_from on the host, from a table's weights: mono4[s], s < S, as k_mc_cut writes it for a launch of S slices.  Needs no GPU.
+extern "C" int pbrk_mc_mono_slices(const float* weights, int n, int S, int* mono4) {
+    if (!weights || !mono4 || n < 1 || n > 8192 || (S != 1 && S != 2 && S != 4)) return -1;
+    const int NW = (n + 31) / 32;
+    unsigned wbits[256];
+    for (int w = 0; w < NW; ++w) {
+        unsigned m = 0u;
+        for (int i = w << 5; i < (w << 5) + 32 && i < n; ++i) {
+            union { float f; unsigned u; } c;
+            c.f = weights[i];
+            m = c.u > m ? c.u : m;
+        }
+        wbits[w] = m;
+    }
+    mc_mono_from(wbits, NW, S, mono4);
+    return 0;
 }
 
 // Scratch for those tables: a ring of slots in device memory, allocated once per device.  A slot is written by k_mc_prep and read
@@ -1306,6 +1401,13 @@ static int g_mc_fold = 1;
 extern "C" void pbrk_mc_set_fold(int on) { g_mc_fold = on ? 1 : 0; }
 // 1 when the last region-kernel launch ran a FOLD instantiation, else 0 (also before the first launch)
 extern "C" int pbrk_mc_last_fold(void) { return g_last_fold; }
+// The completeness net of the header's step 3 (2l; tests / A-B runs; the outputs are the same bit for bit either way): -1 the default rule --
+// on when the device counters are on (PBR_MC_STATS=1), off otherwise --, 0 off wherever a net-less instantiation exists (the lean run
+// loops), 1 always on.  The rule reads nothing of the dispatch.
+static int g_mc_net = -1;
+extern "C" void pbrk_mc_set_net(int mode) { g_mc_net = mode < 0 ? -1 : (mode ? 1 : 0); }
+// 1 when the last region-kernel launch carried the net, 0 when it ran a net-less instantiation (1 before the first launch)
+extern "C" int pbrk_mc_last_net(void) { return g_last_net; }
 // The cut of the last region-kernel launch, for tests and probes: out6 = the first cut word of slices 0 .. 3, NW, words cut.  A launch
 // without a cut reports 0 words.  A launch of S < 4 slices reports slice j % S in entry j (one slice: its first cut word four times);
 // the words cut are counted over the launch's S slices.  Waits for the device.
@@ -1332,9 +1434,18 @@ static void launch_runs(const RegArgs& q, unsigned grid, size_t lds, hipStream_t
     if constexpr (HAS_RUNS) {
         if (g_mc_runs && q.NW <= 64 * (1024 / (TILE * TILE))) {
             // header 2j: a rule of the level alone (n_src), so a row shard equals the full dispatch; only the lean run loop has the instantiation
+            // header 2l: the net is a rule of the process (the counters, pbrk_mc_set_net), never of the dispatch
             if constexpr (LEAN) {
                 const int n = q.a.n_src;
-                if (g_mc_fold && (n & (n - 1)) == 0) { launch_region_t<RS, SUB, TILE, true, true, true>(q, grid, lds, st); return; }
+                const bool fold = g_mc_fold && (n & (n - 1)) == 0;
+                if constexpr (RS != 34 || MC_NET_OFF_34 != 0) {
+                    if (!(g_mc_net < 0 ? q.stats != nullptr : g_mc_net != 0)) {
+                        if (fold) launch_region_t<RS, SUB, TILE, true, true, true, false>(q, grid, lds, st);
+                        else launch_region_t<RS, SUB, TILE, true, true, false, false>(q, grid, lds, st);
+                        return;
+                    }
+                }
+                if (fold) { launch_region_t<RS, SUB, TILE, true, true, true>(q, grid, lds, st); return; }
             }
             launch_region_t<RS, SUB, TILE, true, LEAN>(q, grid, lds, st);
             return;
@@ -1428,7 +1539,7 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
     if (lean && q.absorb) {
         std::lock_guard<std::mutex> hold(g_prep_lock);
         int slot = -1;
-        unsigned* scratch = q.NW + 2 * q.NR + 4 <= PREP_SLOT_WORDS ? prep_acquire(st, &slot) : nullptr;
+        unsigned* scratch = q.NW + 2 * q.NR + 8 <= PREP_SLOT_WORDS ? prep_acquire(st, &slot) : nullptr;
         if (!scratch) lean = false;
         else {
             int dev = 0; (void)hipGetDevice(&dev);
@@ -1438,7 +1549,7 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
             const bool head_first = RS == 66 && (q.G == 1 ? MC_HEAD_FIRST_G1 != 0 : MC_HEAD_FIRST_SUB != 0);
             if (head_first && g_mc_launch_cut && q.NW > nslices) {
                 hipLaunchKernelGGL(k_mc_cut, dim3(1), dim3(64), 0, st, a.tab, a.n_tab, q.NW, q.NR, nslices, scratch);
-                q.cut = 1;
+                q.cut = 3;
                 g_last_cut = scratch + q.NW + q.NR;
             }
             launch_shape<true>(RS, tile, q, grid, lds, st);

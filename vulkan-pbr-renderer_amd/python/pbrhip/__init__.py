@@ -320,6 +320,8 @@ PROTOTYPES = {
     "pbrk_mc_launch_cut_slices": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_uint, C.c_uint, C.POINTER(C.c_int)]),
     "pbrk_mc_set_tile32": (None, [C.c_int]),
     "pbrk_mc_set_fold": (None, [C.c_int]), "pbrk_mc_last_fold": (C.c_int, []),
+    "pbrk_mc_set_net": (None, [C.c_int]), "pbrk_mc_last_net": (C.c_int, []),
+    "pbrk_mc_mono_slices": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "pbrk_mc_set_resident": (None, [C.c_int]), "pbrk_mc_resident_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
     "pbrk_mc_region_phase_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
     "pbrk_lut_cells_build": (C.c_int, [VP, C.c_int, VP, VP]),
