@@ -261,7 +261,8 @@ void PBR_MeshSetPartMaterial(PBR_Mesh* mesh, uint32_t part, PBR_Material* materi
  * the material. */
 PBR_Material* PBR_MakeMaterialFromTextures(GPU_Texture* const tex[4]);
 
-/* ---- .dds material textures (N8 / K15): what asset_import.cpp:30-60 (LoadMeshTexture, through ddspp) accepts ---- */
+/* ---- .dds material textures (N8 / K15; the parser in host/pbr_dds.c, the loaders in host/pbr_ddsin.c): what asset_import.cpp:30-60
+ *      (LoadMeshTexture, through ddspp) accepts ---- */
 enum { PBR_DDS_MAX_LEVELS = 16 };
 typedef struct PBR_DDSInfo {
     GPU_Format format;            /* BC1_RGBA_UN (DXT1, DXGI 71), BC3_RGBA_UN (DXT5, 77), BC5_UN (ATI2 / BC5U, 83), RGBA8UN (DXGI 28, R G B A byte masks) */
@@ -281,7 +282,8 @@ enum { PBR_DDS_FILE_MIPS = 1 };   /* also upload the file's levels below 0, down
 GPU_Texture* PBR_MakeTextureFromDDSMemory(const void* bytes, size_t size, uint32_t flags);
 GPU_Texture* PBR_MakeTextureFromDDSFile(const char* filepath, uint32_t flags);
 
-/* ---- the bake's maps as .dds files (N11 / K18, host/pbr_ddsout.c): one DX10-header container per texture with its mip chain; cubes
+/* ---- the bake's maps as .dds files (N11 / K18; the container in host/pbr_dds.c, the writer in host/pbr_ddsout.c, the float loader in
+ *      host/pbr_ddsin.c): one DX10-header container per texture with its mip chain; cubes
  *      carry the TEXTURECUBE flag and all six faces, data face-major (+X -X +Y -Y +Z -Z, the layer order), each face's levels in order. ---- */
 typedef struct PBR_DDSInfoEx {
     uint32_t dxgi_format;         /* 2 RGBA32F, 10 RGBA16F, 34 RG16F, 95 BC6H_UF16, 28 RGBA8UN, 71 BC1, 77 BC3, 83 BC5 (legacy FourCCs map to these) */

@@ -1,15 +1,12 @@
 // sanitizer harness for the .dds header parser (host/pbr_dds.c, run on CPU only): the fixture header (argv[1], 128 bytes), synthesised
 // headers of every accepted kind, and a few thousand mutations of them (bit flips, truncations, huge extents, lying level counts).
-// Whatever PBR_ParseDDS accepts must describe levels that lie inside the buffer, which is an exact-size heap copy.
+// Whatever PBR_ParseDDS accepts must describe levels that lie inside the buffer, which is an exact-size heap copy.  Links against
+// pbr_dds.c alone: the container code calls nothing of the GPU layer.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <stdint.h>
 #include "pbr_host.h"
-
-/* what pbr_dds.c links against beside tests/sanitize/gpu_stubs.c; the harness never reaches the GPU entry points */
-void GPU_DestroyTexture(GPU_Texture* t) { (void)t; }
-void GPUX_OpCopyBufferToTextureMip(GPU_Graph* g, GPU_Buffer* b, uint32_t o, GPU_Texture* t, uint32_t m) { (void)g; (void)b; (void)o; (void)t; (void)m; }
 
 static uint32_t rs = 2463534242u;
 static uint32_t rnd(void) { rs ^= rs << 13; rs ^= rs >> 17; rs ^= rs << 5; return rs; }

@@ -1,4 +1,4 @@
-// sanitizer harness for the extended .dds parser and the header writer (host/pbr_ddsout.c, run on CPU only): every header
+// sanitizer harness for the extended .dds parser and the header writer (host/pbr_dds.c alone, run on CPU only): every header
 // PBR_BuildDDSHeader writes (eight formats, 2-D and cube, every level count) must parse back to the layout the writer used, one byte
 // short must be rejected, and a few thousand mutations (bit flips, truncations, huge extents, lying level counts, random layouts)
 // must either be rejected or describe (layer, level) ranges inside the buffer, which is an exact-size heap copy.
@@ -7,12 +7,6 @@
 #include <string.h>
 #include <stdint.h>
 #include "pbr_host.h"
-
-/* what pbr_ddsout.c and pbr_dds.c link against beside tests/sanitize/gpu_stubs.c; the harness never reaches the GPU entry points */
-void GPU_DestroyTexture(GPU_Texture* t) { (void)t; }
-void GPUX_OpCopyBufferToTextureMip(GPU_Graph* g, GPU_Buffer* b, uint32_t o, GPU_Texture* t, uint32_t m) { (void)g; (void)b; (void)o; (void)t; (void)m; }
-void GPUX_OpEncodeBC6H(GPU_Graph* g, GPU_Texture* t, uint32_t m, GPU_Buffer* b, uint32_t o) { (void)g; (void)t; (void)m; (void)b; (void)o; }
-uint64_t GPUX_BC6HMipBytes(const GPU_Texture* t, uint32_t m) { (void)t; (void)m; return 0; }
 
 static uint32_t rs = 2463534242u;
 static uint32_t rnd(void) { rs ^= rs << 13; rs ^= rs >> 17; rs ^= rs << 5; return rs; }

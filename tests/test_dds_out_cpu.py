@@ -1,6 +1,7 @@
-"""The .dds output layer (host/pbr_ddsout.c) on the CPU: the header writer and the extended parser built with ASan + UBSan into a
-stand-alone program (tests/sanitize/fuzz_ddsex.c), and through the library: PBR_ParseDDSEx on files laid out by PBR_BuildDDSHeader --
-what PBR_EncodeTextureDDS calls -- returns the offsets the writer used; PBR_ParseDDS stays as it was.  No GPU, no Pillow."""
+"""The .dds container (host/pbr_dds.c) and the loaders (host/pbr_ddsin.c) on the CPU: the header writer and the extended parser built
+with ASan + UBSan into a stand-alone program (tests/sanitize/fuzz_ddsex.c), the three loaders likewise over a recording fake of the GPU
+entry points (tests/sanitize/fuzz_ddsload.c), and through the library: PBR_ParseDDSEx on files laid out by PBR_BuildDDSHeader -- what
+PBR_EncodeTextureDDS calls -- returns the offsets the writer used; PBR_ParseDDS stays as it was.  No GPU, no Pillow."""
 import ctypes as C
 import os
 import shutil
@@ -24,14 +25,32 @@ def test_extended_dds_parser_under_sanitizers(tmp_path):
         pytest.skip("no gcc")
     exe = str(tmp_path / "fuzz_ddsex")
     cmd = ["gcc", "-std=c11", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-w",
-           "-I" + os.path.join(ROOT, "include"), os.path.join(HERE, "sanitize", "fuzz_ddsex.c"), os.path.join(HERE, "sanitize", "gpu_stubs.c"),
-           os.path.join(HOST, "pbr_ddsout.c"), os.path.join(HOST, "pbr_dds.c"), "-o", exe]
+           "-I" + os.path.join(ROOT, "include"), os.path.join(HERE, "sanitize", "fuzz_ddsex.c"),
+           os.path.join(HOST, "pbr_dds.c"), "-o", exe]
     b = subprocess.run(cmd, capture_output=True, text=True)
     assert b.returncode == 0, b.stderr[-3000:]
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.startswith("ok:"), (r.stdout[-500:], r.stderr[-3000:])
     acc, rej = int(r.stdout.split()[1]), int(r.stdout.split()[5])
     assert acc > 300 and rej > 300, r.stdout                       # the mutations reach both outcomes
+
+
+def test_dds_loaders_under_sanitizers(tmp_path):
+    """what each loader stages and records for files as the writer lays them out, and for mutated files: tests/sanitize/fuzz_ddsload.c"""
+    if not shutil.which("gcc"):
+        pytest.skip("no gcc")
+    exe = str(tmp_path / "fuzz_ddsload")
+    cmd = ["gcc", "-std=c11", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-w",
+           "-I" + os.path.join(ROOT, "include"), os.path.join(HERE, "sanitize", "fuzz_ddsload.c"),
+           os.path.join(HOST, "pbr_dds.c"), os.path.join(HOST, "pbr_ddsin.c"), "-o", exe]
+    b = subprocess.run(cmd, capture_output=True, text=True)
+    assert b.returncode == 0, b.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.startswith("ok:"), (r.stdout[-500:], r.stderr[-3000:])
+    words = r.stdout.replace(",", " ").replace(")", " ").split()
+    loaded, refused, laid_out_loaded, laid_out_refused = int(words[1]), int(words[4]), int(words[-2]), int(words[-1])
+    assert laid_out_loaded > 300 and laid_out_refused > 300, r.stdout        # the writer's files reach both outcomes ...
+    assert loaded - laid_out_loaded > 100 and refused - laid_out_refused > 300, r.stdout      # ... and so do the mutations
 
 
 def build(dxgi, w, h, layers, levels):

@@ -1,6 +1,8 @@
 """The .dds header parser (host/pbr_dds.c) on the CPU: built with ASan + UBSan into a stand-alone program (tests/sanitize/fuzz_dds.c)
 that parses the recorded header of a real file, synthesised headers of every accepted kind and a few thousand mutations; and, through
-the library, the same parser against the golden header.  No GPU."""
+the library, the same parser against the golden header, and both parsers against the return codes and filled structs recorded from
+structured random headers (tools/gen_dds_parse_golden.py).  No GPU."""
+import ctypes as C
 import os
 import shutil
 import subprocess
@@ -22,7 +24,7 @@ def test_dds_parser_under_sanitizers(tmp_path):
     np.load(os.path.join(HERE, "golden", "bc_crops.npz"))["header"].tofile(header)
     exe = str(tmp_path / "fuzz_dds")
     cmd = ["gcc", "-std=c11", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-w",
-           "-I" + os.path.join(ROOT, "include"), os.path.join(HERE, "sanitize", "fuzz_dds.c"), os.path.join(HERE, "sanitize", "gpu_stubs.c"),
+           "-I" + os.path.join(ROOT, "include"), os.path.join(HERE, "sanitize", "fuzz_dds.c"),
            os.path.join(ROOT, "vulkan-pbr-renderer_amd", "host", "pbr_dds.c"), "-o", exe]
     b = subprocess.run(cmd, capture_output=True, text=True)
     assert b.returncode == 0, b.stderr[-3000:]
@@ -43,3 +45,30 @@ def test_library_parser_reads_the_recorded_header():
         pbrhip.parse_dds(head + bytes(2796215))
     with pytest.raises(ValueError, match="not a DDS"):
         pbrhip.parse_dds(b"DDX " + head[4:] + bytes(64))
+
+
+def test_both_parsers_answer_the_recorded_cases_as_recorded():
+    """tests/golden/dds_parse_cases.npz: the code each parser returns pins the order of its checks, the struct bytes what it fills in
+    (and that a refusal leaves the struct zero)"""
+    import pbrhip
+    path = os.path.join(HERE, "golden", "dds_parse_cases.npz")
+    assert os.path.getsize(path) < 100 * 1024
+    z = np.load(path)
+    rc = z["rc"].astype(int)
+    for p in (0, 1):
+        for code in (0, -2, -3, -4, -5, -6, -7):
+            assert (rc[:, p] == code).sum() >= 20, (p, code)
+    assert (((rc[:, 0] == -4) | (rc[:, 0] == -5)) & (rc[:, 1] == 0)).sum() >= 20
+    L = pbrhip.lib()
+    taken = [0, 0]
+    for k, (head, size) in enumerate(zip(z["headers"], z["size"])):
+        head = head.tobytes()                                  # the parsers read the header only; `size` is what the file claims to be
+        for p, (fn, info, rec) in enumerate(((L.PBR_ParseDDS, pbrhip.PBR_DDSInfo(), z["narrow"]), (L.PBR_ParseDDSEx, pbrhip.PBR_DDSInfoEx(), z["wide"]))):
+            C.memset(C.byref(info), 0xAA, C.sizeof(info))
+            assert fn(head, int(size), C.byref(info)) == rc[k, p], (k, p)
+            if rc[k, p] == 0:
+                assert bytes(info) == rec[taken[p]].tobytes(), (k, p)
+                taken[p] += 1
+            else:
+                assert bytes(info) == bytes(C.sizeof(info)), (k, p)
+    assert taken == [len(z["narrow"]), len(z["wide"])]

@@ -272,6 +272,36 @@ def test_float_dds_round_trip_of_a_bake(gpu, bake, tmp_path):
             L.GPU_DestroyTexture(back)
 
 
+def test_float_dds_round_trip_of_a_flat_chain_and_no_partial_chain(gpu):
+    """a 2-D 24 x 12 RGBA16F texture with its chain (24 x 12, 12 x 6, 6 x 3, 3 x 1) written as it is and loaded back: every level's bytes;
+    the same texture written with two of its four levels is refused: the float loader takes a whole chain or one level"""
+    import pbrhip
+    L = gpu
+    tex = pbrhip.make_texture(pbrhip.Format_RGBA16F, 24, 12, pbrhip.TextureFlag_HasMipmaps)
+    back = None
+    try:
+        assert tex.contents.mip_level_count == 4
+        rng = np.random.default_rng(0x5EED2412)
+        for m in range(4):
+            pbrhip.upload_mip(tex, m, rng.integers(0, 0x7C00, (max(1, 12 >> m), 24 >> m, 4), dtype=np.uint16))
+        data = pbrhip.encode_dds(tex)
+        info = pbrhip.parse_dds_ex(data)
+        assert (info.dxgi_format, info.width, info.height, info.layers, info.level_count) == (10, 24, 12, 1, 4)
+        back = L.PBR_MakeTextureFromFloatDDSMemory(data, len(data))
+        assert back
+        b = back.contents
+        assert (b.format, b.width, b.height, b.layer_count, b.mip_level_count) == (pbrhip.Format_RGBA16F, 24, 12, 1, 4)
+        for m in range(4):
+            level = pbrhip.read_mip_bytes(tex, m)
+            assert len(level) == info.level_size[m] and data[info.level_offset[0][m]:][:len(level)] == level, m
+            assert pbrhip.read_mip_bytes(back, m) == level, m
+        part = pbrhip.encode_dds(tex, 0, 2)
+        assert pbrhip.parse_dds_ex(part).level_count == 2
+        assert not L.PBR_MakeTextureFromFloatDDSMemory(part, len(part))
+    finally:
+        L.GPU_DestroyTexture(tex); L.GPU_DestroyTexture(back)
+
+
 def test_rgba16f_dds_is_the_contract_conversion(gpu, bake):
     """RGBA32F narrowed on the host: round to nearest even, sign and Inf kept; a sub-range of the chain"""
     import pbrhip

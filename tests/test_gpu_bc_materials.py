@@ -166,6 +166,27 @@ def test_dds_file_loads_level_0_like_the_reference_and_all_levels_on_request(gpu
     assert not gpu.PBR_MakeTextureFromDDSFile(os.fsencode(str(tmp_path / "missing.dds")), 0)
 
 
+def test_dds_file_wider_than_high_uploads_the_levels_of_the_smaller_extent(gpu):
+    """a 64 x 16 DXT1 file holds the 7 levels of its larger extent; the texture's chain is counted from the smaller one: 5 levels, each
+    the file's; the same file cut below those 5 is refused"""
+    import pbrhip
+    levels = [R.random_blocks("bc1_rgba", max(1, 64 >> m), max(1, 16 >> m), 700 + m) for m in range(7)]
+    data = dds_file(b"DXT1", 64, 16, levels)
+    assert pbrhip.parse_dds(data).level_count == 7
+    t = gpu.PBR_MakeTextureFromDDSMemory(data, len(data), pbrhip.PBR_DDS_FILE_MIPS)
+    assert t
+    try:
+        assert (t.contents.format, t.contents.width, t.contents.height, t.contents.mip_level_count) == (pbrhip.Format_BC1_RGBA_UN, 64, 16, 5)
+        for m in range(5):
+            assert pbrhip.read_mip_bytes(t, m) == bytes(levels[m]), m
+            assert np.array_equal(pbrhip.read_decoded_mip(t, m), R.decode("bc1_rgba", levels[m], 64 >> m, max(1, 16 >> m))), m
+    finally:
+        gpu.GPU_DestroyTexture(t)
+    cut = dds_file(b"DXT1", 64, 16, levels[:4])
+    assert pbrhip.parse_dds(cut).level_count == 4
+    assert not gpu.PBR_MakeTextureFromDDSMemory(cut, len(cut), pbrhip.PBR_DDS_FILE_MIPS)
+
+
 def test_material_from_dds_files_draws_like_its_rgba8_twin(gpu, geo_scene, tmp_path):
     """base colour and emissive from .dds files with all their levels (the sampler walks the decoded chain), normal and ORM left NULL:
     the reference's 1 x 1 dummies.  The twin: RGBA8UN textures whose every level is uploaded from the restatement."""

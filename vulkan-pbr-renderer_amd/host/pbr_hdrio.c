@@ -4,6 +4,7 @@
  * cubemaps can be written in the very format MakeTextureFromHDRIFile reads.
  */
 #include "pbr_host.h"
+#include "pbr_file.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -21,16 +22,10 @@ GPU_Texture* PBR_MakeTextureFromEquirectHDRIMemory(const void* bytes, size_t siz
 }
 
 GPU_Texture* PBR_MakeTextureFromEquirectHDRIFile(const char* filepath, uint32_t face_size) {
-    FILE* f = fopen(filepath, "rb");
-    if (!f) { fprintf(stderr, "GPU-ERROR: PBR_MakeTextureFromEquirectHDRIFile: cannot open %s\n", filepath); return NULL; }
-    fseek(f, 0, SEEK_END);
-    long n = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    void* buf = malloc((size_t)n);
-    GPU_Texture* t = NULL;
-    if (buf && fread(buf, 1, (size_t)n, f) == (size_t)n) t = PBR_MakeTextureFromEquirectHDRIMemory(buf, (size_t)n, face_size);
+    size_t n;
+    void* buf = pbr_read_file("PBR_MakeTextureFromEquirectHDRIFile", filepath, &n);
+    GPU_Texture* t = buf ? PBR_MakeTextureFromEquirectHDRIMemory(buf, n, face_size) : NULL;
     free(buf);
-    fclose(f);
     return t;
 }
 

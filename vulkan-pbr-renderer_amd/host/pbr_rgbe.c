@@ -8,6 +8,7 @@
  * Written from the Radiance format description; stb_image is not used or copied.
  */
 #include "pbr_host.h"
+#include "pbr_file.h"
 
 #include <math.h>
 #include <stdio.h>
@@ -128,15 +129,9 @@ GPU_Texture* PBR_MakeTextureFromHDRIMemory(const void* bytes, size_t size) {
 }
 
 GPU_Texture* PBR_MakeTextureFromHDRIFile(const char* filepath) {
-    FILE* f = fopen(filepath, "rb");
-    if (!f) { fprintf(stderr, "GPU-ERROR: PBR_MakeTextureFromHDRIFile: cannot open %s\n", filepath); return NULL; }
-    fseek(f, 0, SEEK_END);
-    long n = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    void* buf = malloc((size_t)n);
-    GPU_Texture* t = NULL;
-    if (buf && fread(buf, 1, (size_t)n, f) == (size_t)n) t = PBR_MakeTextureFromHDRIMemory(buf, (size_t)n);
+    size_t n;
+    void* buf = pbr_read_file("PBR_MakeTextureFromHDRIFile", filepath, &n);
+    GPU_Texture* t = buf ? PBR_MakeTextureFromHDRIMemory(buf, n) : NULL;
     free(buf);
-    fclose(f);
     return t;
 }
