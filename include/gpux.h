@@ -40,9 +40,17 @@ GPU_API void GPUX_OpDispatchLines(GPU_Graph* graph, uint32_t y0, uint32_t y1, ui
 /* ---- shade pass controls ---- */
 enum { GPUX_Shade_IBL = 1 << 0, GPUX_Shade_LightShafts = 1 << 1,
        GPUX_Shade_SunShadows = 1 << 2, /* SUN_DEPTH_MAP: 4-tap PCF sun shadow + shaft visibility (lighting_pass.glsl:594-608, 646) */
-       GPUX_Shade_VoxelGI = 1 << 3     /* LIGHTGRID + PREV_FRAME_RESULT + GBUFFER_DEPTH: the live ambient / specular traces (:273-424, :685, :701);
-                                          with LightShafts | SunShadows | VoxelGI the pass is the reference's complete live shader */ };
+       GPUX_Shade_VoxelGI = 1 << 3,    /* LIGHTGRID + PREV_FRAME_RESULT + GBUFFER_DEPTH: the live ambient / specular traces (:273-424, :685, :701);
+                                          with LightShafts | SunShadows | VoxelGI the pass is the reference's complete live shader */
+       GPUX_Shade_SH9Irradiance = 1 << 4 /* with GPUX_Shade_IBL: the ambient term from the 27 SH9 coefficients of GPUX_SetShadeSH9 in place of
+                                          TEX_IRRADIANCE_MAP, which may stay unbound (csrc/sh_shade_core.h, DESIGN.md 4 "K5, SH9 ambient") */ };
 GPU_API void GPUX_SetShadeFlags(GPU_GraphicsPipeline* pipeline, int flags);    /* default GPUX_Shade_IBL */
+GPU_API int GPUX_GetShadeFlags(GPU_GraphicsPipeline* pipeline);
+/* The coefficients GPUX_Shade_SH9Irradiance shades from: 27 doubles (216 bytes, index 3 k + c: what GPUX_OpProjectSH9 writes) at `offset`
+ * (a multiple of 8) of `coef`; NULL unsets them.  A draw recorded with the flag keeps the buffer and offset it was recorded with; the
+ * numbers are read on the device when the draw executes, after every earlier op of its graph and of the graphs submitted before it.
+ * A device buffer (GPU_BufferFlag_GPU) keeps them in the cache: every workgroup of the draw reads them. */
+GPU_API void GPUX_SetShadeSH9(GPU_GraphicsPipeline* pipeline, GPU_Buffer* coef, uint32_t offset);
 /* full-screen draw restricted to rows [row0,row1) (screen-band sharding) */
 GPU_API void GPUX_OpDrawRows(GPU_Graph* graph, uint32_t row0, uint32_t row1);
 

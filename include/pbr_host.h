@@ -186,6 +186,11 @@ PBR_LightingPass* PBR_MakeLightingPassLive(const PBR_GBuffer* gb, const PBR_IBLM
 void PBR_DestroyLightingPass(PBR_LightingPass* lp);
 GPU_Buffer* PBR_LightingGlobalsBuffer(PBR_LightingPass* lp);           /* persistently mapped (render.cpp:675) */
 GPU_GraphicsPipeline* PBR_LightingPipeline(PBR_LightingPass* lp);
+/* Ambient term from SH9 coefficients in place of the irradiance cube (K5 with GPUX_Shade_SH9Irradiance): 27 doubles at `offset` (a
+ * multiple of 8) of `coef`, as GPUX_OpProjectSH9 writes them; they are read on the device when a recorded pass executes.  Sets the
+ * flag and the buffer on the pass's pipeline for the passes recorded from now on; NULL restores the cube path.  A pass made from maps
+ * whose irradiance_map is NULL can only be drawn this way.  (GPUX_SetShadeFlags replaces all flags: call it before this.) */
+void PBR_LightingUseSH9(PBR_LightingPass* lp, GPU_Buffer* coef, uint32_t offset);
 /* render.cpp:977-991 + 1119-1127: copies globals into the mapped buffer and records the pass; rows [row0,row1), row1 == 0 -> all */
 void PBR_RecordLightingPass(PBR_LightingPass* lp, GPU_Graph* graph, const PBR_Globals* globals, uint32_t row0, uint32_t row1);
 

@@ -45,7 +45,9 @@ enum {                      /* shade flags (reference lighting_pass.glsl sub-blo
     PBRK_SHADE_IBL = 1 << 0,     /* ambient = irradiance(N); spec = prefiltered(R, rough*4)  (:690, :699) */
     PBRK_SHADE_SHAFTS = 1 << 1,  /* light-shaft loop (:622-651); visibility == 1 unless PBRK_SHADE_SHADOWS */
     PBRK_SHADE_SHADOWS = 1 << 2, /* sun shadow: 4 PCF taps of the sun depth map (:594-608) + shaft visibility (:646) */
-    PBRK_SHADE_GI = 1 << 3       /* the live ambient / specular terms: SampleRadianceWithScreenSpaceTrace (:273-424, :685, :701) */
+    PBRK_SHADE_GI = 1 << 3,      /* the live ambient / specular terms: SampleRadianceWithScreenSpaceTrace (:273-424, :685, :701) */
+    PBRK_SHADE_SH9 = 1 << 4      /* with PBRK_SHADE_IBL only: ambient = the SH9 irradiance of sh9_coef at N (csrc/sh_shade_core.h) in place of the
+                                    irradiance cube, which is then neither required nor read; under PBRK_SHADE_GI the trace replaces it as always */
 };
 
 /* sizes / offsets of the pyramid layouts, in float4 texels */
@@ -229,6 +231,8 @@ typedef struct PbrkShadeArgs {
     int out_format;                     /* PBRK_FMT_RGBA16F / PBRK_FMT_RGBA32F */
     int flags;                          /* PBRK_SHADE_* */
     float globals[138];                 /* RendererGlobalsBuffer, render.h:122-136 (552 bytes) */
+    const double* sh9_coef;             /* PBRK_SHADE_SH9: 27 doubles on the device (index 3 k + c as pbrk_sh9_project writes them), 8-byte
+                                           aligned; read by the kernel when it runs, not by pbrk_shade */
 } PbrkShadeArgs;
 int pbrk_shade(const PbrkShadeArgs* args, void* stream);
 /* K5 has two instantiations: the general kernel k_shade (every mode; with PBRK_SHADE_GI k_shade<true>) and k_shade_fast (64 x 4

@@ -95,7 +95,8 @@ struct GPU_ComputePipeline { GPU_PipelineLayout* layout; KernelId kernel; };
 struct GPU_RenderPass { GPU_RenderPassDesc desc; std::vector<GPU_TextureView> targets; };
 struct GPU_GraphicsPipeline { GPU_PipelineLayout* layout; GPU_RenderPass* pass; KernelId kernel; int shade_flags; bool blend_additive = false;
                               uint32_t vertex_stride = 0; /* raster kinds: bytes per vertex (gpu_vulkan.c:1745-1762) */
-                              const struct RasterKind* raster = nullptr; /* K12 / K13 / K14: the row of its raster kind */ };
+                              const struct RasterKind* raster = nullptr; /* K12 / K13 / K14: the row of its raster kind */
+                              BufferImpl* sh9_buf = nullptr; uint32_t sh9_offset = 0; /* GPUX_SetShadeSH9 */ };
 
 enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster, Op_CopyDecodedT2B, Op_ProjectSH9, Op_IrradianceSH9, Op_EncodeBC6H, Op_DecodeBC6H };
 // one draw of a raster job: job triangles from first_tri on, matrices from the set's GLOBALS, the buffers and the target its kind
@@ -112,7 +113,7 @@ struct Op {
     uint32_t face0 = 0, face1 = 6, row0 = 0, row1 = 0;
     bool rows_explicit = false;
     uint32_t gx = 0, gy = 0, gz = 0;
-    // shade
+    // shade (a lighting draw recorded under GPUX_Shade_SH9Irradiance: buf / off_a = its 27 coefficients, else buf == nullptr)
     GPU_GraphicsPipeline* gpipe = nullptr;
     GPU_RenderPass* pass = nullptr;
     // transfers
@@ -1141,6 +1142,14 @@ GPU_API void GPUX_SetShadeFlags(GPU_GraphicsPipeline* p, int flags) {
     GPU_REQUIRE_V(p, "GPUX_SetShadeFlags: NULL pipeline");
     p->shade_flags = flags;
 }
+GPU_API int GPUX_GetShadeFlags(GPU_GraphicsPipeline* p) {
+    GPU_REQUIRE(p, 0, "GPUX_GetShadeFlags: NULL pipeline");
+    return p->shade_flags;
+}
+GPU_API void GPUX_SetShadeSH9(GPU_GraphicsPipeline* p, GPU_Buffer* coef, uint32_t offset) {
+    GPU_REQUIRE_V(p, "GPUX_SetShadeSH9: NULL pipeline");
+    p->sh9_buf = (BufferImpl*)coef; p->sh9_offset = coef ? offset : 0;
+}
 
 // ------------------------------------------------------------------------------------------
 // host tables -> device (cached)
@@ -1479,14 +1488,23 @@ static void record_shade(GPU_Graph* g, uint32_t row0, uint32_t row1, bool explic
         GPU_REQUIRE_V(lut && lut->tex && lut->tex->base.format == GPU_Format_RG16F && lut->tex->base.width == lut->tex->base.height,
                       "%s: \"BRDF_INTEGRATION_MAP\" must be a square RG16F texture", fn);
     }
+    Op op;
+    if (dp.pipeline->shade_flags & GPUX_Shade_SH9Irradiance) {                // the 27 coefficients in place of TEX_IRRADIANCE_MAP
+        BufferImpl* coef = dp.pipeline->sh9_buf;
+        const uint32_t off = dp.pipeline->sh9_offset;
+        GPU_REQUIRE_V(dp.pipeline->shade_flags & GPUX_Shade_IBL, "%s: GPUX_Shade_SH9Irradiance needs GPUX_Shade_IBL", fn);
+        GPU_REQUIRE_V(coef, "%s: GPUX_Shade_SH9Irradiance without a coefficient buffer (GPUX_SetShadeSH9)", fn);
+        GPU_REQUIRE_V((off % 8) == 0, "%s: SH9 coefficient offset %u is not a multiple of 8", fn, off);
+        GPU_REQUIRE_V((uint64_t)off + 27 * sizeof(double) <= coef->base.size, "%s: SH9 coefficient buffer too small (%u bytes for 216 at offset %u)", fn, coef->base.size, off);
+        op.buf = coef; op.off_a = off;
+    }
     if (dp.pipeline->shade_flags & GPUX_Shade_IBL) {
         Slot* irr = named_slot(s, "TEX_IRRADIANCE_MAP");
-        GPU_REQUIRE_V(irr && irr->tex && is_f4_cube(irr->tex), "%s: \"TEX_IRRADIANCE_MAP\" must be a square RGBA32F cubemap", fn);
+        GPU_REQUIRE_V(op.buf || (irr && irr->tex && is_f4_cube(irr->tex)), "%s: \"TEX_IRRADIANCE_MAP\" must be a square RGBA32F cubemap", fn);
         Slot* lut = named_slot(s, "BRDF_INTEGRATION_MAP");
         GPU_REQUIRE_V(lut && lut->tex && lut->tex->base.format == GPU_Format_RG16F && lut->tex->base.width == lut->tex->base.height,
                       "%s: \"BRDF_INTEGRATION_MAP\" must be a square RG16F texture", fn);
     }
-    Op op;
     push_shade_op(g, op, dp, row0, row1, explicit_rows, fn);
 }
 
@@ -2076,12 +2094,12 @@ static void exec_gridview(GPU_Graph* g, Op& op, size_t& ev_used, const float* gl
 // is, graph_replayable takes the sampled maps from them.
 enum TwinKind { Twin_Apron, Twin_SmallCells /* of every level of size <= 512 */, Twin_Cells0 /* of level 0 */, Twin_LutCells };
 struct ShadeTwin { TextureImpl* tex; TwinKind kind; const char* timed_name; /* of its build; NULL: not timed */ };
-static int shade_twins(GPU_DescriptorSet* s, int shade_flags, ShadeTwin tw[5]) {
+static int shade_twins(GPU_DescriptorSet* s, int shade_flags, ShadeTwin tw[5], bool sh9 = false /* the op shades from SH9 coefficients: no irradiance twin */) {
     auto tex = [&](const char* name) { Slot* sl = named_slot(s, name); return sl ? sl->tex : nullptr; };
     int n = 0;
     if (TextureImpl* pre = tex("PREFILTERED_ENV_MAP")) { tw[n++] = {pre, Twin_Apron, "apron.prefiltered"}; tw[n++] = {pre, Twin_SmallCells, "cells.prefiltered"}; }
     if (!(shade_flags & GPUX_Shade_IBL)) return n;
-    if (TextureImpl* irr = tex("TEX_IRRADIANCE_MAP")) { tw[n++] = {irr, Twin_Apron, "apron.irradiance"}; tw[n++] = {irr, Twin_Cells0, nullptr}; }
+    if (!sh9) if (TextureImpl* irr = tex("TEX_IRRADIANCE_MAP")) { tw[n++] = {irr, Twin_Apron, "apron.irradiance"}; tw[n++] = {irr, Twin_Cells0, nullptr}; }
     if (TextureImpl* lut = tex("BRDF_INTEGRATION_MAP")) tw[n++] = {lut, Twin_LutCells, nullptr};
     return n;
 }
@@ -2139,7 +2157,8 @@ static void exec_shade(GPU_Graph* g, Op& op, size_t& ev_used) {
     a.emissive = named_slot(s, "GBUFFER_EMISSIVE")->tex->dev;
     a.depth = named_slot(s, "GBUFFER_DEPTH")->tex->dev;
     ShadeTwin tw[5];
-    const int n_tw = shade_twins(s, op.gpipe->shade_flags, tw);
+    const bool sh9 = op.buf != nullptr;                                      // as recorded (record_shade)
+    const int n_tw = shade_twins(s, op.gpipe->shade_flags, tw, sh9);
     for (int i = 0; i < n_tw; ++i) if (!shade_twin_ready(tw[i]) && !build_shade_twin(g, tw[i], ev_used)) return;
     TextureImpl* pre = named_slot(s, "PREFILTERED_ENV_MAP")->tex;
     a.prefiltered_bordered = pre->bordered; a.prefiltered_size = (int)pre->base.width; a.prefiltered_levels = (int)pre->base.mip_level_count;
@@ -2147,9 +2166,14 @@ static void exec_shade(GPU_Graph* g, Op& op, size_t& ev_used) {
     a.flags = 0;
     if (op.gpipe->shade_flags & GPUX_Shade_IBL) {
         a.flags |= PBRK_SHADE_IBL;
-        TextureImpl* irr = named_slot(s, "TEX_IRRADIANCE_MAP")->tex;
-        a.irradiance_bordered = irr->bordered; a.irradiance_size = (int)irr->base.width;
-        a.irradiance_cells = cells_of(irr, 0);
+        if (sh9) {
+            a.flags |= PBRK_SHADE_SH9;
+            a.sh9_coef = (const double*)((const char*)op.buf->dev + op.off_a);
+        } else {
+            TextureImpl* irr = named_slot(s, "TEX_IRRADIANCE_MAP")->tex;
+            a.irradiance_bordered = irr->bordered; a.irradiance_size = (int)irr->base.width;
+            a.irradiance_cells = cells_of(irr, 0);
+        }
         TextureImpl* lut = named_slot(s, "BRDF_INTEGRATION_MAP")->tex;
         a.lut = lut->dev; a.lut_size = (int)lut->base.width;
         a.lut_cells = lut->lut_cells_valid ? lut->lut_cells : nullptr;
@@ -2380,7 +2404,7 @@ static bool op_replayable(const Op& op) {
     case Op_Shade: {
         if (is_post_kernel(op.gpipe->kernel)) return true;
         ShadeTwin tw[5];
-        const int n = shade_twins(op.set, op.gpipe->shade_flags, tw);
+        const int n = shade_twins(op.set, op.gpipe->shade_flags, tw, op.buf != nullptr);
         for (int i = 0; i < n; ++i) if (!shade_twin_ready(tw[i])) return false;
         return named_slot(op.set, "GLOBALS")->buf->pinned_host;
     }
@@ -2482,7 +2506,7 @@ static bool op_access(const Op& op, std::vector<TextureImpl*>& r, std::vector<Te
             if (sl.tex) { r.push_back(sl.tex); if (op.kind == Op_Dispatch) w.push_back(sl.tex); }
         }
         if (op.kind == Op_Shade) {
-            if (!op.pass) return false;
+            if (!op.pass || op.buf) return false;                            // op.buf: the SH9 coefficients a lighting draw reads -- a buffer, not followed
             for (const GPU_TextureView& tv : op.pass->targets) w.push_back((TextureImpl*)tv.texture);
             if (op.blend_tex) r.push_back(op.blend_tex);
         }

@@ -272,9 +272,13 @@ __device__ __forceinline__ f3 sample_radiance_ss(const ShadeParams& p, f3 V, con
 }
 
 // kGI: the voxel-GI traces need ~250 VGPRs; the common modes keep their own instantiation (54 VGPRs)
-template <bool kGI>
+// kSH (PBRK_SHADE_SH9 with PBRK_SHADE_IBL): :690 from the folded SH9 constants (sh_shade_core.h), no irradiance binding.  Its own
+// instantiations, so that the two without it keep their code.  Under kGI the trace overwrites `ambient` (:685): nothing is evaluated.
+template <bool kGI, bool kSH = false>
 __global__ __launch_bounds__(256) void k_shade(const ShadeParams p) {
     __shared__ int level_tab[32];
+    __shared__ __attribute__((aligned(16))) float sh_k[kSH && !kGI ? 28 : 1];
+    if (kSH && !kGI) sh9_fold_to_lds(p.sh9, sh_k);                        // published by fill_level_table's barrier
     fill_level_table(level_tab, p.pre_size, min(p.pre_levels, 16), p.pre_cells_first);
     {   // grid: x = 64-pixel column blocks, y = 4-row blocks (no integer division per pixel).  The GI instantiation takes 8 x 8 pixels
         // per wave (a 32 x 8 block): its traces diverge, and a square footprint has fewer waves that straddle a surface edge and
@@ -406,7 +410,13 @@ __global__ __launch_bounds__(256) void k_shade(const ShadeParams p) {
             if ((p.flags & PBRK_SHADE_IBL) || gi) {
                 float2 sb = lut_fetch(p.lut, p.lut_cells, p.lut_size, VdotN, fmaxf(roughness, 0.05f));  // :681
                 f3 ambient = mk3(0.0f, 0.0f, 0.0f);
-                if (p.flags & PBRK_SHADE_IBL) {                                            // :690 (commented line)
+                if (kSH) {
+                    if (!kGI && (p.flags & PBRK_SHADE_IBL)) {
+                        float e[3];
+                        sh_shade_eval(sh_k, N.x, N.y, N.z, e);
+                        ambient = mk3(e[0], e[1], e[2]);
+                    }
+                } else if (p.flags & PBRK_SHADE_IBL) {                                     // :690 (commented line)
                     CubeST cs = cube_select(N);
                     float si, ti;
                     if (kGI) cube_st_exact(cs, &si, &ti); else cube_st_shared(cs, &si, &ti);
@@ -521,8 +531,10 @@ extern "C" int pbrk_shade(const PbrkShadeArgs* a, void* stream) {
     if (a->out_format != PBRK_FMT_RGBA16F && a->out_format != PBRK_FMT_RGBA32F) return PBRK_E_FORMAT;
     if (!a->prefiltered_bordered || a->prefiltered_size < 1 || a->prefiltered_levels < 1 ||
         a->prefiltered_levels > pbrk_mip_count(a->prefiltered_size, a->prefiltered_size) || a->prefiltered_levels > 16) return PBRK_E_ARG;   // sky branch is live code; 16-entry level table
+    const bool sh9 = (a->flags & PBRK_SHADE_IBL) && (a->flags & PBRK_SHADE_SH9);      // the flag means nothing without IBL
     if (a->flags & PBRK_SHADE_IBL) {
-        if (!a->irradiance_bordered || a->irradiance_size < 1 || !a->lut || a->lut_size < 1) return PBRK_E_ARG;
+        if (!a->lut || a->lut_size < 1) return PBRK_E_ARG;
+        if (sh9 ? (!a->sh9_coef || ((size_t)a->sh9_coef & 7)) : (!a->irradiance_bordered || a->irradiance_size < 1)) return PBRK_E_ARG;
     }
     if (a->flags & PBRK_SHADE_GI) {
         if (!a->lightgrid || a->lightgrid_size < 1 || a->lightgrid_size > 1024 || !a->lut || a->lut_size < 1) return PBRK_E_ARG;
@@ -552,6 +564,8 @@ extern "C" int pbrk_shade(const PbrkShadeArgs* a, void* stream) {
     p.lightgrid_scale = a->globals[136];
     p.sun_depth = (const float*)a->sun_depth; p.sun_w = a->sun_depth_w; p.sun_h = a->sun_depth_h;
     p.rcp_width = 1.0f / (float)a->width; p.rcp_height = 1.0f / (float)a->height;
+    p.sh9 = sh9 ? a->sh9_coef : nullptr;
+    if (sh9) { p.irr = nullptr; p.irr_cells = nullptr; p.irr_size = 0; }   // neither required nor read
     // fast instantiation: no sun shadows / GI, power-of-two prefiltered cube with a complete cells twin (and, IBL, the two other twins)
     if (g_fast_mode < 0) { const char* e = getenv("PBR_SHADE_FAST"); g_fast_mode = e ? atoi(e) : 1; }
     const int fast_mode = g_fast_mode;
@@ -559,17 +573,21 @@ extern "C" int pbrk_shade(const PbrkShadeArgs* a, void* stream) {
     bool fast = fast_mode && !p.snap && !(a->flags & (PBRK_SHADE_GI | PBRK_SHADE_SHADOWS)) && p.pre_cells && p.pre_cells_first == 0 &&
                 (a->prefiltered_size & (a->prefiltered_size - 1)) == 0 && a->prefiltered_size <= 512 &&
                 (long long)a->width * a->height < (1ll << 29);
-    if (fast && (a->flags & PBRK_SHADE_IBL)) fast = p.irr_cells && p.lut_cells && a->irradiance_size <= 512;
+    if (fast && (a->flags & PBRK_SHADE_IBL)) fast = p.lut_cells && (sh9 || (p.irr_cells && a->irradiance_size <= 512));
     if (fast) {
         size_t cb = 0;
         for (int l = 0; l < a->prefiltered_levels; ++l) { int n = a->prefiltered_size >> l; if (n < 1) n = 1; cb += pbrk_cells_bytes(n); }
         p.pre_cells_bytes = (int)cb;
-        const int rc = launch_shade_fast(p, (a->flags & PBRK_SHADE_IBL) != 0, (a->flags & PBRK_SHADE_SHAFTS) != 0, (hipStream_t)stream);
+        const int rc = launch_shade_fast(p, (a->flags & PBRK_SHADE_IBL) != 0, (a->flags & PBRK_SHADE_SHAFTS) != 0, sh9, (hipStream_t)stream);
         if (rc == PBRK_OK) g_last_kernel = 1;
         return rc;
     }
-    if (a->flags & PBRK_SHADE_GI) hipLaunchKernelGGL(k_shade<true>, dim3((p.w + 31) / 32, (p.h + 7) / 8), dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(k_shade<false>, dim3((p.w + 63) / 64, (p.h + 3) / 4), dim3(256), 0, (hipStream_t)stream, p);
+    const dim3 grid_gi((p.w + 31) / 32, (p.h + 7) / 8), grid((p.w + 63) / 64, (p.h + 3) / 4);
+    if (a->flags & PBRK_SHADE_GI) {
+        if (sh9) hipLaunchKernelGGL((k_shade<true, true>), grid_gi, dim3(256), 0, (hipStream_t)stream, p);
+        else hipLaunchKernelGGL(k_shade<true>, grid_gi, dim3(256), 0, (hipStream_t)stream, p);
+    } else if (sh9) hipLaunchKernelGGL((k_shade<false, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(k_shade<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
     if (hipGetLastError() != hipSuccess) return PBRK_E_LAUNCH;
     g_last_kernel = (a->flags & PBRK_SHADE_GI) ? 2 : 0;
     return PBRK_OK;

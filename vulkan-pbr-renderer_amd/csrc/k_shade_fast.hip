@@ -32,10 +32,13 @@ __device__ __forceinline__ f3 pre_level_fetch(__amdgpu_buffer_rsrc_t rc, float f
     return cells_bilerp(bl4(rc, off), bl4(rc, off + 16), bl4(rc, off + 32), a, b);
 }
 
-template <bool kIBL, bool kShafts>
+// kSH (PBRK_SHADE_SH9, with kIBL): irradiance(N) from the folded SH9 constants in LDS instead of the three loads of the cells twin
+template <bool kIBL, bool kShafts, bool kSH = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_shade_fast(const ShadeParams p) {
     __shared__ int lv_off[16];        // byte offset of level l inside the prefiltered cells twin
+    __shared__ __attribute__((aligned(16))) float sh_k[kSH ? 28 : 1];
     if (threadIdx.x < 16) lv_off[threadIdx.x] = cells_level_off(p.pre_size, 0, min((int)threadIdx.x, p.pre_levels - 1)) * 16;
+    if (kSH) sh9_fold_to_lds(p.sh9, sh_k);
     __syncthreads();
     const int lx = blockIdx.x * 64 + (threadIdx.x & 63);
     const int ly = blockIdx.y * 4 + (threadIdx.x >> 6);
@@ -87,7 +90,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     // surface pixel at all (an all-sky wave -- most waves of a frame with sky -- skips them) and are consumed ~250 instructions later.
     // A smooth 32^2 map: one v_rcp projection.
     f3 amb = mk3(0.0f, 0.0f, 0.0f);
-    if (kIBL && __builtin_amdgcn_ballot_w64(!sky) != 0ull) {
+    if (kIBL && !kSH && __builtin_amdgcn_ballot_w64(!sky) != 0ull) {
         const float nf = (float)p.irr_size;
         float fid = __builtin_amdgcn_cubeid(N.x, N.y, N.z);
         float sc = __builtin_amdgcn_cubesc(N.x, N.y, N.z), tc = __builtin_amdgcn_cubetc(N.x, N.y, N.z);
@@ -188,6 +191,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                 sbx = lerp_fma(lerp_fma(t00.x, t10.x, a), lerp_fma(t01.x, t11.x, a), b);
                 sby = lerp_fma(lerp_fma(t00.y, t10.y, a), lerp_fma(t01.y, t11.y, a), b);
             }
+            if (kSH) {                                                                  // :690 from nine coefficients: no load, N as it is
+                float e[3];
+                sh_shade_eval(sh_k, N.x, N.y, N.z, e);
+                amb = mk3(e[0], e[1], e[2]);
+            }
             outl.x = fmaf(kdb.x, amb.x, outl.x); outl.y = fmaf(kdb.y, amb.y, outl.y); outl.z = fmaf(kdb.z, amb.z, outl.z);   // :687
             // :693-697 (exact: feeds the taps of the prefiltered fetch)
             const float dNI2 = 2.0f * -dNV;
@@ -222,9 +230,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     }
 }
 
-int launch_shade_fast(const ShadeParams& p, bool ibl, bool shafts, hipStream_t stream) {
+int launch_shade_fast(const ShadeParams& p, bool ibl, bool shafts, bool sh9, hipStream_t stream) {
     dim3 grid((p.w + 63) / 64, (p.h + 3) / 4);
-    if (ibl && shafts) hipLaunchKernelGGL((k_shade_fast<true, true>), grid, dim3(256), 0, stream, p);
+    if (ibl && sh9 && shafts) hipLaunchKernelGGL((k_shade_fast<true, true, true>), grid, dim3(256), 0, stream, p);
+    else if (ibl && sh9) hipLaunchKernelGGL((k_shade_fast<true, false, true>), grid, dim3(256), 0, stream, p);
+    else if (ibl && shafts) hipLaunchKernelGGL((k_shade_fast<true, true>), grid, dim3(256), 0, stream, p);
     else if (ibl) hipLaunchKernelGGL((k_shade_fast<true, false>), grid, dim3(256), 0, stream, p);
     else if (shafts) hipLaunchKernelGGL((k_shade_fast<false, true>), grid, dim3(256), 0, stream, p);
     else hipLaunchKernelGGL((k_shade_fast<false, false>), grid, dim3(256), 0, stream, p);

@@ -4,6 +4,7 @@
 #include "pbr_device.h"
 #include "pbr_kernels.h"
 #include <hip/hip_fp16.h>
+#include "sh_shade_core.h"
 
 struct ShadeParams {
     int width, height, x0, y0, w, h;
@@ -25,6 +26,7 @@ struct ShadeParams {
     const uint2* prev[8]; int prev_w, prev_h, prev_levels;
     float vfw[16], cfv[16], vfc[16], wfv[16];   // view_space_from_world, clip_space_from_view, view_space_from_clip, world_space_from_view
     float lightgrid_scale;
+    const double* sh9;             // PBRK_SHADE_SH9: 27 SH9 coefficients (device), read when the kernel runs
 };
 
 // EXACT b / 255.0f for b in 0..255 in 3 instructions: one Newton correction of b * fl(1/255) is the correctly
@@ -67,5 +69,11 @@ __device__ __forceinline__ float4 unpack_h4(uint2 v) {
     return make_float4(a.x, a.y, b.x, b.y);
 }
 
+// PBRK_SHADE_SH9: the 27 folded constants of sh_shade_core.h, one per lane of the workgroup's first wave, into LDS; the caller's
+// barrier publishes them.  Wave-uniform values from a uniform address, read where :690 needs them ("K5, SH9 ambient").
+__device__ __forceinline__ void sh9_fold_to_lds(const double* __restrict__ coef, float* k) {
+    if (threadIdx.x < 27) k[threadIdx.x] = sh_shade_fold_one(coef[threadIdx.x], (int)threadIdx.x);
+}
+
 // k_shade_fast.hip
-int launch_shade_fast(const ShadeParams& p, bool ibl, bool shafts, hipStream_t stream);
+int launch_shade_fast(const ShadeParams& p, bool ibl, bool shafts, bool sh9, hipStream_t stream);

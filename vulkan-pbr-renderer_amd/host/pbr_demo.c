@@ -2,7 +2,7 @@
  * pbr_demo.c -- headless C driver of the hot path through the GPU_* boundary (what main.cpp:35-51 +
  * HotreloadShaders + BuildRenderCommands do for this path, without window / mesh import / raster passes).
  *
- *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster [gridview]]]]] [sh9 FILE] [dds PREFIX] [ddsin PREFIX]
+ *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster [gridview]]]]] [sh9 FILE] [dds PREFIX] [ddsin PREFIX] [sh9shade]
  *
  * Loads a vertical-strip HDR cube (asset_import.cpp:17-27), runs the IBL precompute (render.cpp:505-619),
  * shades a flat synthetic G-buffer (a metallic floor under the sky), then runs three frames of the per-frame chain
@@ -23,6 +23,9 @@
  * With `ddsin PREFIX` as the last two arguments (after all of the above) nothing is baked: the three maps are loaded from
  * PREFIX_specular.dds (a BC6H_UF16 file is decoded by K19 into an RGBA32F cube, a float file is loaded as it is), PREFIX_irradiance.dds
  * and PREFIX_lut.dds -- the files `dds PREFIX` wrote -- and the run goes on unchanged from the irradiance_sum line.
+ * With `sh9shade` as the LAST argument (after all of the above) the first frame is rendered once more with the ambient term taken from
+ * the SH9 coefficients of level 0 of the environment instead of the irradiance cube (K17's projection and K5 in SH9 mode in one
+ * graph, PBR_LightingUseSH9), and its checksum is printed as frame_sh9_checksum; the other lines stay as they are.
  */
 #include "pbr_host.h"
 
@@ -112,6 +115,8 @@ int main(int argc, char** argv) {
     const char* sh9_path = NULL;
     const char* dds_prefix = NULL;
     const char* ddsin_prefix = NULL;
+    int sh9shade = 0;
+    if (argc >= 3 && strcmp(argv[argc - 1], "sh9shade") == 0) { sh9shade = 1; argc -= 1; }
     if (argc >= 4 && strcmp(argv[argc - 2], "ddsin") == 0) { ddsin_prefix = argv[argc - 1]; argc -= 2; }
     if (argc >= 4 && strcmp(argv[argc - 2], "dds") == 0) { dds_prefix = argv[argc - 1]; argc -= 2; }
     if (argc >= 4 && strcmp(argv[argc - 2], "sh9") == 0) { sh9_path = argv[argc - 1]; argc -= 2; }
@@ -309,6 +314,19 @@ int main(int argc, char** argv) {
         PBR_DestroyGeometryPass(gp); PBR_DestroyMesh(mesh); PBR_DestroyMaterial(material);
     }
     PBR_DestroyPostProcess(pp);
+    if (sh9shade) {                                                          /* the coefficients never leave the device */
+        GPU_Buffer* coef = GPU_MakeBuffer(27 * sizeof(double), GPU_BufferFlag_GPU, NULL);
+        GPU_Graph* g = GPU_MakeGraph();
+        if (!coef || !g) return 1;
+        PBR_FillGlobals(&globals, pos, NULL, 75.f, (float)width / (float)height, 0.02f, 10000.f, 56.5f, 97.f, 0);
+        GPUX_OpProjectSH9(g, tex_env_cube, 0, 0, 6, 0, tex_env_cube->width, coef, 0);
+        PBR_LightingUseSH9(lp, coef, 0);
+        PBR_RecordLightingPass(lp, g, &globals, 0, 0);
+        GPU_GraphSubmit(g); GPU_GraphWait(g);
+        PBR_LightingUseSH9(lp, NULL, 0);
+        printf("frame_sh9_checksum %.9e\n", checksum_texture_mip(gb.lighting_result, 0, 0));
+        GPU_DestroyGraph(g); GPU_DestroyBuffer(coef);
+    }
 
     GPU_DestroyGraph(graph);
     PBR_DestroyLightingPass(lp);

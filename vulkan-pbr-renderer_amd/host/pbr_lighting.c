@@ -264,7 +264,7 @@ PBR_LightingPass* PBR_MakeLightingPassLive(const PBR_GBuffer* gb, const PBR_IBLM
     GPU_SetTextureBinding(s, orm_b, gb->orm);
     GPU_SetTextureBinding(s, emissive_b, gb->emissive);
     GPU_SetTextureBinding(s, depth_b, gb->depth);
-    GPU_SetTextureBinding(s, irr_b, maps->irradiance_map);
+    GPU_SetTextureBinding(s, irr_b, maps->irradiance_map ? maps->irradiance_map : lp->dummy2d);  /* none: a pass for PBR_LightingUseSH9 only */
     GPU_SetTextureBinding(s, pre_b, maps->tex_specular_env_map);
     GPU_SetTextureBinding(s, lut_b, maps->brdf_lut);
     GPU_SetTextureBinding(s, grid_b, lightgrid ? lightgrid : lp->dummy3d);                      /* render.cpp:861 r->lightgrid */
@@ -292,6 +292,13 @@ void PBR_DestroyLightingPass(PBR_LightingPass* lp) {
 
 GPU_Buffer* PBR_LightingGlobalsBuffer(PBR_LightingPass* lp) { return lp->globals_buffer; }
 GPU_GraphicsPipeline* PBR_LightingPipeline(PBR_LightingPass* lp) { return lp->pipeline; }
+
+void PBR_LightingUseSH9(PBR_LightingPass* lp, GPU_Buffer* coef, uint32_t offset) {
+    if (!lp) return;
+    const int flags = GPUX_GetShadeFlags(lp->pipeline);
+    GPUX_SetShadeFlags(lp->pipeline, coef ? flags | GPUX_Shade_SH9Irradiance : flags & ~GPUX_Shade_SH9Irradiance);
+    GPUX_SetShadeSH9(lp->pipeline, coef, offset);
+}
 
 void PBR_RecordLightingPass(PBR_LightingPass* lp, GPU_Graph* graph, const PBR_Globals* globals, uint32_t row0, uint32_t row1) {
     if (globals) memcpy(lp->globals_buffer->data, globals, sizeof *globals);           /* render.cpp:991 */

@@ -110,6 +110,7 @@ class PbrkBloomArgs(C.Structure):
 
 
 Shade_IBL, Shade_LightShafts, Shade_SunShadows, Shade_VoxelGI = 1, 2, 4, 8
+Shade_SH9 = 16                          # GPUX_Shade_SH9Irradiance == PBRK_SHADE_SH9: with Shade_IBL, ambient from 27 SH9 coefficients
 PBRK_FMT_RG16F, PBRK_FMT_RG32F, PBRK_FMT_RGBA16F, PBRK_FMT_RGBA32F, PBRK_FMT_R32F, PBRK_FMT_RGBA8UN, PBRK_FMT_BGRA8UN = 1, 2, 3, 4, 5, 6, 7
 
 
@@ -124,7 +125,7 @@ class PbrkShadeArgs(C.Structure):
                 ("lightgrid", C.c_void_p), ("lightgrid_size", C.c_int), ("prev_frame", C.c_void_p * 8),
                 ("prev_frame_w", C.c_int), ("prev_frame_h", C.c_int), ("prev_frame_levels", C.c_int),
                 ("out", C.c_void_p), ("out_format", C.c_int), ("flags", C.c_int),
-                ("globals", C.c_float * 138)]
+                ("globals", C.c_float * 138), ("sh9_coef", C.c_void_p)]
 
 
 class PbrkGridViewArgs(C.Structure):
@@ -213,7 +214,8 @@ PROTOTYPES = {
     "GPUX_SetDevice": (None, [C.c_int]), "GPUX_GetDevice": (C.c_int, []), "GPUX_SetErrorHandler": (None, [VP, VP]),
     "GPUX_BackendName": (C.c_char_p, []), "GPUX_OpDispatchRows": (None, [VP, U32, U32, U32, U32]),
     "GPUX_OpDispatchLines": (None, [VP, U32, U32, U32, U32]),
-    "GPUX_SetShadeFlags": (None, [VP, C.c_int]), "GPUX_OpDrawRows": (None, [VP, U32, U32]),
+    "GPUX_SetShadeFlags": (None, [VP, C.c_int]), "GPUX_GetShadeFlags": (C.c_int, [VP]), "GPUX_SetShadeSH9": (None, [VP, BufP, U32]),
+    "GPUX_OpDrawRows": (None, [VP, U32, U32]),
     "GPUX_OpCopyTextureMipToBuffer": (None, [VP, TexP, U32, BufP, U32]), "GPUX_OpCopyBufferToTextureMip": (None, [VP, BufP, U32, TexP, U32]),
     "GPUX_OpCopyDecodedTextureMipToBuffer": (None, [VP, TexP, U32, BufP, U32]),
     "GPUX_FoldedBlitCount": (C.c_uint64, []), "GPUX_SetGraphOverlap": (None, [C.c_int]), "GPUX_OverlappedSubmitCount": (C.c_uint64, []), "GPUX_TextureMipBytes": (C.c_uint64, [TexP, U32]), "GPUX_TextureDevicePtr": (VP, [TexP, U32]), "GPUX_BufferDevicePtr": (VP, [BufP]),
@@ -256,7 +258,7 @@ PROTOTYPES = {
     "PBR_MakeLightingPassEx": (VP, [C.POINTER(PBR_GBuffer), C.POINTER(PBR_IBLMaps), U32, U32, TexP]),
     "PBR_MakeLightingPassLive": (VP, [C.POINTER(PBR_GBuffer), C.POINTER(PBR_IBLMaps), U32, U32, TexP, TexP, TexP]),
     "PBR_LightingGlobalsBuffer": (BufP, [VP]), "PBR_LightingPipeline": (VP, [VP]),
-    "PBR_RecordLightingPass": (None, [VP, VP, C.POINTER(PBR_Globals), U32, U32]),
+    "PBR_RecordLightingPass": (None, [VP, VP, C.POINTER(PBR_Globals), U32, U32]), "PBR_LightingUseSH9": (None, [VP, BufP, U32]),
     "PBR_MakePostProcess": (VP, [C.POINTER(PBR_GBuffer), U32, U32, C.c_int]), "PBR_DestroyPostProcess": (None, [VP]),
     "PBR_PostVelocity": (TexP, [VP, U32]), "PBR_PostTaaOutput": (TexP, [VP, U32]), "PBR_PostBackbuffer": (TexP, [VP]),
     "PBR_RecordBloom": (None, [VP, VP, U32]), "PBR_RecordFinalPostProcessBloom": (None, [VP, VP, U32]),
