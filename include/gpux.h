@@ -78,6 +78,12 @@ GPU_API void GPUX_OpIrradianceFromSH9(GPU_Graph* graph, GPU_Buffer* src, uint32_
  * under GPUX_SetGraphReplay(1). */
 GPU_API void GPUX_OpEncodeBC6H(GPU_Graph* graph, GPU_Texture* src, uint32_t mip_level, GPU_Buffer* dst, uint32_t dst_offset);
 GPU_API uint64_t GPUX_BC6HMipBytes(const GPU_Texture* texture, uint32_t mip_level);
+/* K18 with a quality level.  GPUX_BC6H_OneRegion records exactly what GPUX_OpEncodeBC6H records.  GPUX_BC6H_TwoRegions is an op of its
+ * own (K18.bc6h_encode2 in the per-op times): per block the one-region block or, where it has a strictly lower squared error, one of
+ * the two-region cases 0, 14, 1, 30 over the best of the 32 partitions (csrc/bc6h2_core.h, DESIGN.md "K18, two regions"); same
+ * layout, same size, several times the time.  Any other quality is one more error at record time with nothing recorded. */
+enum { GPUX_BC6H_OneRegion = 0, GPUX_BC6H_TwoRegions = 1 };
+GPU_API void GPUX_OpEncodeBC6HEx(GPU_Graph* graph, GPU_Texture* src, uint32_t mip_level, GPU_Buffer* dst, uint32_t dst_offset, uint32_t quality);
 /* K19: the way back: GPUX_BC6HMipBytes(dst, mip_level) bytes of BC6H_UF16 blocks (any of the 14 modes; csrc/bc6h_decode_core.h, DESIGN.md
  * K19) at src_offset (a multiple of 16), laid out as GPUX_OpEncodeBC6H writes them -> one level, every layer, of a 2-D or cube RGBA32F /
  * RGBA16F texture; alpha 1.  A texture writer like any other: the target's sampler twins are rebuilt before the next use.  Anything

@@ -307,7 +307,8 @@ uint64_t PBR_BuildDDSHeader(uint32_t dxgi_format, uint32_t width, uint32_t heigh
                             PBR_DDSInfoEx* layout);
 enum { PBR_DDS_OUT_SAME = 0,          /* RGBA32F -> DXGI 2, RGBA16F -> DXGI 10, RG16F -> DXGI 34 (the BRDF LUT) */
        PBR_DDS_OUT_RGBA16F = 1,       /* RGBA32F narrowed on the host: round to nearest even, sign and Inf kept (csrc/bc6h_core.h) */
-       PBR_DDS_OUT_BC6H_UF16 = 2 };   /* RGBA32F / RGBA16F -> DXGI 95 through GPUX_OpEncodeBC6H, every level in one graph */
+       PBR_DDS_OUT_BC6H_UF16 = 2,     /* RGBA32F / RGBA16F -> DXGI 95 through GPUX_OpEncodeBC6H, every level in one graph */
+       PBR_DDS_OUT_BC6H_UF16_2R = 3 };/* the same file with every level encoded at GPUX_BC6H_TwoRegions (csrc/bc6h2_core.h): slower, lower error */
 /* levels [first_mip, first_mip + mip_count) of a 2-D or cube texture (mip_count 0: to the end of the chain) as file bytes the caller
  * frees; blocking.  NULL (message on stderr) for a format / output pair outside the list, a bad range or a failed allocation. */
 void* PBR_EncodeTextureDDS(GPU_Texture* texture, uint32_t first_mip, uint32_t mip_count, int out_format, size_t* out_size);

@@ -419,6 +419,10 @@ int pbrk_sh9_irradiance(const double* coef27_device, void* out_level /* float4 [
 uint64_t pbrk_bc6h_level_bytes(int width, int height, int layers);      /* 0 for a non-positive argument */
 int pbrk_bc6h_encode(const void* level, int src_format /* PBRK_FMT_RGBA32F / PBRK_FMT_RGBA16F */, int width, int height, int layers,
                      void* blocks_out, void* stream);
+/* the two-region quality level: the same arguments, checks, error codes and layout; per block mode 11 or one of the two-region cases
+ * 0, 14, 1, 30, whichever has the lower squared half-code error (mode 11 on a tie).  Contract: csrc/bc6h2_core.h. */
+int pbrk_bc6h_encode2(const void* level, int src_format /* PBRK_FMT_RGBA32F / PBRK_FMT_RGBA16F */, int width, int height, int layers,
+                      void* blocks_out, void* stream);
 
 /* ---- K19: BC6H_UF16 decode of one level, all 14 modes (the input side, host/pbr_ddsin.c).  `layers` images of
  *      ceil(width / 4) x ceil(height / 4) blocks, laid out as pbrk_bc6h_encode writes them (16-byte aligned) -> width x height RGBA32F

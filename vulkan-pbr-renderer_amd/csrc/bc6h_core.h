@@ -106,8 +106,8 @@ BC6H_FN uint64_t bc6h_try(const uint32_t h[16][3], const uint32_t ea[3], const u
     return sum;
 }
 
-// 16 texels (row-major in the block, half codes r g b) -> the block's four little-endian words
-BC6H_FN void bc6h_encode_block(const uint32_t h[16][3], uint32_t out[4]) {
+// 16 texels (row-major in the block, half codes r g b) -> the block's four little-endian words; returns the block's squared error
+BC6H_FN uint64_t bc6h_encode_block_err(const uint32_t h[16][3], uint32_t out[4]) {
     uint32_t lo[3], hi[3], sum[3] = {0, 0, 0};
     uint64_t rg = 0, rb = 0;
     BC6H_UNROLL
@@ -162,4 +162,6 @@ BC6H_FN void bc6h_encode_block(const uint32_t h[16][3], uint32_t out[4]) {
     const uint64_t bits63 = (best_idx & 7u) | ((best_idx >> 4) << 3);         // 63 index bits
     const uint64_t high = (ends >> 59) | (bits63 << 1);
     out[0] = (uint32_t)low; out[1] = (uint32_t)(low >> 32); out[2] = (uint32_t)high; out[3] = (uint32_t)(high >> 32);
+    return best_err;
 }
+BC6H_FN void bc6h_encode_block(const uint32_t h[16][3], uint32_t out[4]) { (void)bc6h_encode_block_err(h, out); }

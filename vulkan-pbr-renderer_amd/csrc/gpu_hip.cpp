@@ -98,7 +98,7 @@ struct GPU_GraphicsPipeline { GPU_PipelineLayout* layout; GPU_RenderPass* pass; 
                               const struct RasterKind* raster = nullptr; /* K12 / K13 / K14: the row of its raster kind */
                               BufferImpl* sh9_buf = nullptr; uint32_t sh9_offset = 0; /* GPUX_SetShadeSH9 */ };
 
-enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster, Op_CopyDecodedT2B, Op_ProjectSH9, Op_IrradianceSH9, Op_EncodeBC6H, Op_DecodeBC6H };
+enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster, Op_CopyDecodedT2B, Op_ProjectSH9, Op_IrradianceSH9, Op_EncodeBC6H, Op_DecodeBC6H, Op_EncodeBC6H2 };
 // one draw of a raster job: job triangles from first_tri on, matrices from the set's GLOBALS, the buffers and the target its kind
 // names (K12 / K13: the buffers bound at the draw; K14: SSBO0 / SSBO1 of the set, first_index = its first vertex) and the pushed
 // constants (K13 reads them: the skybox rebinds both inside the pass)
@@ -1650,19 +1650,27 @@ GPU_API uint64_t GPUX_BC6HMipBytes(const GPU_Texture* t, uint32_t mip) {
     return pbrk_bc6h_level_bytes((int)mip_dim(t->width, mip), (int)mip_dim(t->height, mip), (int)t->layer_count);
 }
 // op.tex / op.mip = the source level (all layers), op.buf / op.off_b = the blocks, op.size = their bytes
-GPU_API void GPUX_OpEncodeBC6H(GPU_Graph* g, GPU_Texture* src, uint32_t mip, GPU_Buffer* dst, uint32_t dst_offset) {
-    REC_GUARD(g);
-    const char* fn = "GPUX_OpEncodeBC6H";
+static void record_bc6h_encode(GPU_Graph* g, GPU_Texture* src, uint32_t mip, GPU_Buffer* dst, uint32_t dst_offset, uint32_t quality, const char* fn) {
+    GPU_REQUIRE_V(g && !g->submitted, "%s: graph is NULL or already submitted (call GPU_GraphWait first)", fn);
     GPU_REQUIRE_V(g->in_pass == nullptr, "%s: inside a render pass", fn);
     GPU_REQUIRE_V(src && dst && mip < src->mip_level_count, "%s: bad arguments", fn);
+    GPU_REQUIRE_V(quality == GPUX_BC6H_OneRegion || quality == GPUX_BC6H_TwoRegions, "%s: quality %u is neither GPUX_BC6H_OneRegion (0) nor GPUX_BC6H_TwoRegions (1)", fn, quality);
     GPU_REQUIRE_V(bc6h_source_format(src->format) >= 0 && src->depth == 1, "%s: the source must be a 2-D or cube RGBA32F / RGBA16F texture", fn);
     GPU_REQUIRE_V(mip_dim(src->width, mip) <= 16384 && mip_dim(src->height, mip) <= 16384, "%s: levels above 16384 a side are not implemented", fn);
     GPU_REQUIRE_V((dst_offset % 16) == 0, "%s: buffer offset %u is not a multiple of 16", fn, dst_offset);
     const uint64_t bytes = GPUX_BC6HMipBytes(src, mip);
     GPU_REQUIRE_V((uint64_t)dst_offset + bytes <= dst->size, "%s: buffer too small (%u bytes for %llu at offset %u)", fn, dst->size, (unsigned long long)bytes, dst_offset);
-    Op op; op.kind = Op_EncodeBC6H; op.name = "K18.bc6h_encode";
+    Op op;
+    if (quality == GPUX_BC6H_TwoRegions) { op.kind = Op_EncodeBC6H2; op.name = "K18.bc6h_encode2"; }
+    else { op.kind = Op_EncodeBC6H; op.name = "K18.bc6h_encode"; }
     op.tex = (TextureImpl*)src; op.mip = mip; op.buf = (BufferImpl*)dst; op.off_b = dst_offset; op.size = bytes;
     g->ops.push_back(op);
+}
+GPU_API void GPUX_OpEncodeBC6H(GPU_Graph* g, GPU_Texture* src, uint32_t mip, GPU_Buffer* dst, uint32_t dst_offset) {
+    record_bc6h_encode(g, src, mip, dst, dst_offset, GPUX_BC6H_OneRegion, "GPUX_OpEncodeBC6H");
+}
+GPU_API void GPUX_OpEncodeBC6HEx(GPU_Graph* g, GPU_Texture* src, uint32_t mip, GPU_Buffer* dst, uint32_t dst_offset, uint32_t quality) {
+    record_bc6h_encode(g, src, mip, dst, dst_offset, quality, "GPUX_OpEncodeBC6HEx");
 }
 // K19: the way back.  op.buf / op.off_a = the blocks, op.tex / op.mip = the level written (all layers), op.size = the blocks' bytes
 GPU_API void GPUX_OpDecodeBC6H(GPU_Graph* g, GPU_Buffer* src, uint32_t src_offset, GPU_Texture* dst, uint32_t mip) {
@@ -2229,13 +2237,14 @@ static void exec_sh9(GPU_Graph* g, Op& op, size_t& ev_used) {
     if (op.kind == Op_IrradianceSH9) op.tex->bordered_valid = false;
 }
 
-// K18: one launch; nothing read back, nothing allocated
+// K18, either quality: one launch; nothing read back, nothing allocated
 static void exec_bc6h(GPU_Graph* g, Op& op, size_t& ev_used) {
     const GPU_Texture& t = op.tex->base;
     const void* level = (const char*)op.tex->dev + op.tex->mip_offset[op.mip];
+    const auto encode = op.kind == Op_EncodeBC6H2 ? pbrk_bc6h_encode2 : pbrk_bc6h_encode;
     timed(g, op.name, ev_used, [&] {
-        int rc = pbrk_bc6h_encode(level, bc6h_source_format(t.format), (int)mip_dim(t.width, op.mip), (int)mip_dim(t.height, op.mip), (int)t.layer_count,
-                                  (char*)op.buf->dev + op.off_b, g->cur);
+        int rc = encode(level, bc6h_source_format(t.format), (int)mip_dim(t.width, op.mip), (int)mip_dim(t.height, op.mip), (int)t.layer_count,
+                        (char*)op.buf->dev + op.off_b, g->cur);
         if (rc != PBRK_OK) gpu_fail("%s launch failed (%d)", op.name.c_str(), rc);
     });
 }
@@ -2376,7 +2385,7 @@ static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
     case Op_Clear: exec_clear(g, op, ev_used); return;
     case Op_CopyB2B: case Op_CopyB2T: case Op_CopyT2B: case Op_CopyDecodedT2B: exec_copy(g, op, ev_used); return;
     case Op_ProjectSH9: case Op_IrradianceSH9: exec_sh9(g, op, ev_used); return;
-    case Op_EncodeBC6H: exec_bc6h(g, op, ev_used); return;
+    case Op_EncodeBC6H: case Op_EncodeBC6H2: exec_bc6h(g, op, ev_used); return;
     case Op_DecodeBC6H: exec_bc6h_decode(g, op, ev_used); return;
     }
 }
@@ -2398,7 +2407,7 @@ static bool op_replayable(const Op& op) {
     case Op_CopyB2B: case Op_CopyB2T: case Op_CopyT2B: case Op_CopyDecodedT2B: return false;          // host pointers may be involved: keep them out of captures
     case Op_Raster: return false;                                             // its draw table is uploaded from pinned staging at submit
     case Op_ProjectSH9: case Op_IrradianceSH9: return true;                   // plain launches on device-visible pointers; the scratch exists since recording
-    case Op_EncodeBC6H: return true;                                          // one plain launch, texture -> device-visible buffer
+    case Op_EncodeBC6H: case Op_EncodeBC6H2: return true;                     // one plain launch, texture -> device-visible buffer
     case Op_DecodeBC6H: return true;                                          // the same, buffer -> texture
     case Op_Clear: return fill_texel_ok(op.tex->texel_bytes);
     case Op_Shade: {
@@ -2514,7 +2523,7 @@ static bool op_access(const Op& op, std::vector<TextureImpl*>& r, std::vector<Te
     case Op_MipGen: r.push_back(op.tex); w.push_back(op.tex); return true;
     case Op_Blit: r.push_back(op.tex); w.push_back(op.tex2); return true;
     case Op_Clear: w.push_back(op.tex); return true;
-    case Op_ProjectSH9: case Op_EncodeBC6H: r.push_back(op.tex); return false; // their buffer is not followed: ends the walk like any buffer
+    case Op_ProjectSH9: case Op_EncodeBC6H: case Op_EncodeBC6H2: r.push_back(op.tex); return false; // their buffer is not followed: ends the walk like any buffer
     case Op_IrradianceSH9: case Op_DecodeBC6H: w.push_back(op.tex); return false;   // the buffer they read is not followed either
     default: return false;
     }

@@ -3,7 +3,7 @@
  * whole mip chain, the way cmft, IBLBaker and cmgen write theirs, on top of PBR_BuildDDSHeader (host/pbr_dds.c: the header bytes and
  * where every layer's levels go).  Float textures go out as they are (RGBA32F = DXGI 2, RGBA16F = 10, RG16F = 34) or narrowed to
  * RGBA16F on the host; BC6H_UF16 (DXGI 95) is encoded on the device by K18 (csrc/bc6h_core.h is the contract, also of the host's
- * fp32 -> fp16 conversion).  The files load back through host/pbr_ddsin.c, so a bake can be saved and shaded later without the
+ * fp32 -> fp16 conversion), at its one-region or its two-region quality (csrc/bc6h2_core.h): the same container either way.  The files load back through host/pbr_ddsin.c, so a bake can be saved and shaded later without the
  * source environment.
  *
  * The file is face-major (each face with its levels), texture memory level-major: the writer reorders.
@@ -28,7 +28,7 @@ void* PBR_EncodeTextureDDS(GPU_Texture* texture, uint32_t first_mip, uint32_t mi
     uint32_t dxgi = 0;
     if (out_format == PBR_DDS_OUT_SAME) dxgi = src_dxgi;
     else if (out_format == PBR_DDS_OUT_RGBA16F && (src_dxgi == 2 || src_dxgi == 10)) dxgi = 10;
-    else if (out_format == PBR_DDS_OUT_BC6H_UF16 && (src_dxgi == 2 || src_dxgi == 10)) dxgi = 95;
+    else if ((out_format == PBR_DDS_OUT_BC6H_UF16 || out_format == PBR_DDS_OUT_BC6H_UF16_2R) && (src_dxgi == 2 || src_dxgi == 10)) dxgi = 95;
     if (!dxgi) { fprintf(stderr, "GPU-ERROR: %s: texture format %d cannot be written as output format %d\n", fn, (int)texture->format, out_format); return NULL; }
     const uint32_t layers = texture->layer_count, w0 = level_dim(texture->width, first_mip), h0 = level_dim(texture->height, first_mip);
     uint8_t header[148];
@@ -38,6 +38,7 @@ void* PBR_EncodeTextureDDS(GPU_Texture* texture, uint32_t first_mip, uint32_t mi
 
     /* every level, all layers, into one mapped buffer in texture order (level-major), by one graph */
     const int bc6h = dxgi == 95;
+    const uint32_t quality = out_format == PBR_DDS_OUT_BC6H_UF16_2R ? GPUX_BC6H_TwoRegions : GPUX_BC6H_OneRegion;
     uint64_t stage_off[PBR_DDS_MAX_LEVELS], stage_total = 0;
     for (uint32_t m = 0; m < mip_count; ++m) {
         stage_off[m] = stage_total;
@@ -49,7 +50,7 @@ void* PBR_EncodeTextureDDS(GPU_Texture* texture, uint32_t first_mip, uint32_t mi
     GPU_Graph* g = staging ? GPU_MakeGraph() : NULL;
     if (!g) { GPU_DestroyBuffer(staging); free(file); fprintf(stderr, "GPU-ERROR: %s: allocation failed\n", fn); return NULL; }
     for (uint32_t m = 0; m < mip_count; ++m) {
-        if (bc6h) GPUX_OpEncodeBC6H(g, texture, first_mip + m, staging, (uint32_t)stage_off[m]);
+        if (bc6h) GPUX_OpEncodeBC6HEx(g, texture, first_mip + m, staging, (uint32_t)stage_off[m], quality);
         else GPUX_OpCopyTextureMipToBuffer(g, texture, first_mip + m, staging, (uint32_t)stage_off[m]);
     }
     GPU_GraphSubmit(g);

@@ -2,7 +2,7 @@
  * pbr_demo.c -- headless C driver of the hot path through the GPU_* boundary (what main.cpp:35-51 +
  * HotreloadShaders + BuildRenderCommands do for this path, without window / mesh import / raster passes).
  *
- *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster [gridview]]]]] [sh9 FILE] [dds PREFIX] [ddsin PREFIX] [sh9shade]
+ *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster [gridview]]]]] [sh9 FILE] [dds|dds2 PREFIX] [ddsin PREFIX] [sh9shade]
  *
  * Loads a vertical-strip HDR cube (asset_import.cpp:17-27), runs the IBL precompute (render.cpp:505-619),
  * shades a flat synthetic G-buffer (a metallic floor under the sky), then runs three frames of the per-frame chain
@@ -19,7 +19,8 @@
  * environment (K17) are written to FILE and their sum is printed as sh9_sum; the other lines stay as they are.
  * With `dds PREFIX` as the last two arguments (after `sh9 FILE` if both are given) the bake is saved as PREFIX_specular.dds (BC6H_UF16
  * through K18, the levels down to min_size), PREFIX_irradiance.dds and PREFIX_lut.dds (as they are), and the three file sizes are
- * printed as dds_bytes; the other lines stay as they are.
+ * printed as dds_bytes; the other lines stay as they are.  `dds2 PREFIX` in the same place writes the same three files with the
+ * specular cube encoded at K18's two-region quality (PBR_DDS_OUT_BC6H_UF16_2R).
  * With `ddsin PREFIX` as the last two arguments (after all of the above) nothing is baked: the three maps are loaded from
  * PREFIX_specular.dds (a BC6H_UF16 file is decoded by K19 into an RGBA32F cube, a float file is loaded as it is), PREFIX_irradiance.dds
  * and PREFIX_lut.dds -- the files `dds PREFIX` wrote -- and the run goes on unchanged from the irradiance_sum line.
@@ -115,10 +116,11 @@ int main(int argc, char** argv) {
     const char* sh9_path = NULL;
     const char* dds_prefix = NULL;
     const char* ddsin_prefix = NULL;
-    int sh9shade = 0;
+    int sh9shade = 0, dds_format = PBR_DDS_OUT_BC6H_UF16;
     if (argc >= 3 && strcmp(argv[argc - 1], "sh9shade") == 0) { sh9shade = 1; argc -= 1; }
     if (argc >= 4 && strcmp(argv[argc - 2], "ddsin") == 0) { ddsin_prefix = argv[argc - 1]; argc -= 2; }
     if (argc >= 4 && strcmp(argv[argc - 2], "dds") == 0) { dds_prefix = argv[argc - 1]; argc -= 2; }
+    else if (argc >= 4 && strcmp(argv[argc - 2], "dds2") == 0) { dds_prefix = argv[argc - 1]; dds_format = PBR_DDS_OUT_BC6H_UF16_2R; argc -= 2; }
     if (argc >= 4 && strcmp(argv[argc - 2], "sh9") == 0) { sh9_path = argv[argc - 1]; argc -= 2; }
     if (argc < 2) { fprintf(stderr, "usage: %s cube_strip.hdr [irr lut spec min_size [width height]]\n", argv[0]); return 2; }
     uint32_t irr = argc > 2 ? (uint32_t)atoi(argv[2]) : 32, lut = argc > 3 ? (uint32_t)atoi(argv[3]) : 256;
@@ -160,7 +162,7 @@ int main(int argc, char** argv) {
         uint32_t filtered = 0;                                               /* the levels the prefilter wrote */
         for (uint32_t sz = spec; filtered < maps.tex_specular_env_map->mip_level_count && sz >= min_size; sz /= 2) filtered++;
         struct { const char* name; GPU_Texture* tex; uint32_t levels; int format; } files[3] = {
-            {"specular", maps.tex_specular_env_map, filtered, PBR_DDS_OUT_BC6H_UF16}, {"irradiance", maps.irradiance_map, 0, PBR_DDS_OUT_SAME},
+            {"specular", maps.tex_specular_env_map, filtered, dds_format}, {"irradiance", maps.irradiance_map, 0, PBR_DDS_OUT_SAME},
             {"lut", maps.brdf_lut, 0, PBR_DDS_OUT_SAME}};
         for (int i = 0; i < 3; ++i) {
             char path[4096];

@@ -23,7 +23,8 @@ BC_BLOCK_BYTES = {Format_BC1_RGB_UN: 8, Format_BC1_RGBA_UN: 8, Format_BC3_RGBA_U
 PBRK_BC1_RGB, PBRK_BC1_RGBA, PBRK_BC3, PBRK_BC5 = 0, 1, 2, 3
 PBR_DDS_FILE_MIPS = 1
 PBR_DDS_MAX_LEVELS = 16
-PBR_DDS_OUT_SAME, PBR_DDS_OUT_RGBA16F, PBR_DDS_OUT_BC6H_UF16 = 0, 1, 2
+PBR_DDS_OUT_SAME, PBR_DDS_OUT_RGBA16F, PBR_DDS_OUT_BC6H_UF16, PBR_DDS_OUT_BC6H_UF16_2R = 0, 1, 2, 3
+GPUX_BC6H_OneRegion, GPUX_BC6H_TwoRegions = 0, 1
 TextureFlag_StorageImage, TextureFlag_RenderTarget, TextureFlag_HasMipmaps, TextureFlag_Cubemap = 1, 2, 4, 8
 BufferFlag_CPU, BufferFlag_GPU, BufferFlag_StorageBuffer = 1, 2, 4
 Shade_IBL, Shade_LightShafts = 1, 2
@@ -349,6 +350,8 @@ PROTOTYPES = {
     "pbrk_bc6h_level_bytes": (C.c_uint64, [C.c_int, C.c_int, C.c_int]),
     "pbrk_bc6h_encode": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP]),
     "GPUX_OpEncodeBC6H": (None, [VP, TexP, U32, BufP, U32]), "GPUX_BC6HMipBytes": (C.c_uint64, [TexP, U32]),
+    "pbrk_bc6h_encode2": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, C.c_int, VP, VP]),
+    "GPUX_OpEncodeBC6HEx": (None, [VP, TexP, U32, BufP, U32, U32]),
     "PBR_ParseDDSEx": (C.c_int, [VP, C.c_size_t, C.POINTER(PBR_DDSInfoEx)]),
     "PBR_BuildDDSHeader": (C.c_uint64, [U32, U32, U32, U32, U32, C.POINTER(C.c_uint8), C.POINTER(PBR_DDSInfoEx)]),
     "PBR_EncodeTextureDDS": (VP, [TexP, U32, U32, C.c_int, C.POINTER(C.c_size_t)]),
@@ -642,13 +645,19 @@ def parse_dds_ex(data: bytes):
     return info
 
 
-def encode_bc6h(tex, mip=0):
-    """One level (every layer) of an RGBA32F / RGBA16F texture as BC6H_UF16 blocks (K18) -> uint8 [layers * bh * bw][16]."""
+def encode_bc6h(tex, mip=0, quality=GPUX_BC6H_OneRegion):
+    """One level (every layer) of an RGBA32F / RGBA16F texture as BC6H_UF16 blocks (K18) -> uint8 [layers * bh * bw][16].
+    quality: GPUX_BC6H_OneRegion (mode 11 only) or GPUX_BC6H_TwoRegions (GPUX_OpEncodeBC6HEx)."""
     L = lib()
     nbytes = L.GPUX_BC6HMipBytes(tex, mip)
     if nbytes == 0:
         raise ValueError("encode_bc6h: not a level of a 2-D or cube RGBA32F / RGBA16F texture")
-    raw = _read_back(lambda g, buf: L.GPUX_OpEncodeBC6H(g, tex, mip, buf, 0), nbytes)
+    if quality not in (GPUX_BC6H_OneRegion, GPUX_BC6H_TwoRegions):
+        raise ValueError("encode_bc6h: quality is GPUX_BC6H_OneRegion or GPUX_BC6H_TwoRegions")
+    if quality == GPUX_BC6H_OneRegion:
+        raw = _read_back(lambda g, buf: L.GPUX_OpEncodeBC6H(g, tex, mip, buf, 0), nbytes)
+    else:
+        raw = _read_back(lambda g, buf: L.GPUX_OpEncodeBC6HEx(g, tex, mip, buf, 0, quality), nbytes)
     return np.frombuffer(raw, np.uint8).reshape(-1, 16).copy()
 
 
