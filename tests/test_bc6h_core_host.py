@@ -1,5 +1,5 @@
-"""csrc/bc6h_core.h -- the encode rules the K18 kernel is made of -- compiled for the host (tests/bc6h_core_host.cpp), plain and with
-ASan + UBSan, against the numpy restatement (tests/bc6h_ref.py), byte for byte; the restatement's decoder against what an independent
+"""csrc/bc6h_core.h -- the encode rules the K18 kernel is made of -- compiled for the host (tests/bc6h_encode_host.cpp at quality 0), plain
+and with ASan + UBSan, against the numpy restatement (tests/bc6h_ref.py), byte for byte; the restatement's decoder against what an independent
 decoder (Pillow) recorded in tests/golden/bc6h_pillow.npz (tools/gen_bc6h_golden.py); and the properties of the contract.  No GPU."""
 import os
 import subprocess
@@ -9,20 +9,15 @@ import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
+import bc6h_host_build  # noqa: E402
 import bc6h_ref as R  # noqa: E402
+from bc6h_host_build import CSRC  # noqa: E402
 
-CSRC = os.path.join(ROOT, "vulkan-pbr-renderer_amd", "csrc")
 
-
-@pytest.fixture(scope="module", params=["plain", "sanitized"])
+@pytest.fixture(scope="module", params=bc6h_host_build.VARIANTS)
 def host(request, tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("bc6h_host") / ("bc6h_core_host_" + request.param))
-    extra = ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if request.param == "sanitized" else []
-    subprocess.run([os.environ.get("CXX", "c++"), "-O1", "-std=c++17", "-Wall", "-Werror", *extra, "-I" + CSRC, "-o", exe,
-                    os.path.join(HERE, "bc6h_core_host.cpp")], check=True)
-    return exe
+    return bc6h_host_build.build("bc6h_encode_host.cpp", request.param, tmp_path_factory)
 
 
 @pytest.fixture(scope="module")
@@ -40,13 +35,13 @@ def run_host(exe, tmp_path, level):
     layers, h, w, _ = level.shape
     src, dst = str(tmp_path / "texels.bin"), str(tmp_path / "blocks.bin")
     level.tofile(src)
-    r = subprocess.run([exe, "0" if level.dtype == np.float32 else "1", str(w), str(h), str(layers), src, dst], capture_output=True, text=True)
+    r = subprocess.run([exe, "0", "0" if level.dtype == np.float32 else "1", str(w), str(h), str(layers), src, dst], capture_output=True, text=True)
     assert r.returncode == 0, (r.stdout[-500:], r.stderr[-3000:])
     return np.fromfile(dst, np.uint8).reshape(-1, 16)
 
 
 def test_bc6h_core_header_exists():
-    assert os.path.isfile(os.path.join(CSRC, "bc6h_core.h"))
+    assert os.path.isfile(os.path.join(CSRC, "bc6h_core.h")) and os.path.isfile(os.path.join(CSRC, "bc6h_format.h"))
 
 
 def test_host_build_of_the_encode_core_equals_the_restatement(host, tmp_path, encoded):

@@ -14,9 +14,8 @@ ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(ROOT, "vulkan-pbr-renderer_amd", "python"))
 import bc6h_decode_ref as D  # noqa: E402
+import bc6h_host_build  # noqa: E402
 import bc6h_ref as R  # noqa: E402
-
-CSRC = os.path.join(ROOT, "vulkan-pbr-renderer_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -24,13 +23,9 @@ def golden():
     return np.load(os.path.join(HERE, "golden", "bc6h_modes_pillow.npz"))
 
 
-@pytest.fixture(scope="module", params=["plain", "sanitized"])
+@pytest.fixture(scope="module", params=bc6h_host_build.VARIANTS)
 def host(request, tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("bc6h_decode_host") / ("bc6h_decode_core_host_" + request.param))
-    extra = ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"] if request.param == "sanitized" else []
-    subprocess.run([os.environ.get("CXX", "c++"), "-O1", "-std=c++17", "-Wall", "-Werror", *extra, "-I" + CSRC, "-o", exe,
-                    os.path.join(HERE, "bc6h_decode_core_host.cpp")], check=True)
-    return exe
+    return bc6h_host_build.build("bc6h_decode_core_host.cpp", request.param, tmp_path_factory)
 
 
 def run_host(exe, tmp_path, blocks, w, h, layers):

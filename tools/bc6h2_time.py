@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""K18 at its two-region quality (pbrk_bc6h_encode2, csrc/bc6h2_core.h) next to the one-region kernel in the same session, on the
+"""K18 at its two-region quality (pbrk_bc6h_encode2: k_bc6h.hip, csrc/bc6h2_core.h) next to the one-region kernel in the same session, on the
 sizes a bake has: one RGBA32F cube level of 4096^2, 1024^2 and 256^2 with the content of tools/bc6h_time.py.  Per size, back to back
 on one stream with GPUX_SetLevelOverlap(0): host clock around `launches` launches that end in a device synchronise, per launch (median
 of `--repeats` windows after a warm-up window), for both kernels, and their ratio.  The yardstick is K18 in this session.

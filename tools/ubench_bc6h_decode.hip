@@ -1,5 +1,5 @@
 // Work splits of the K19 decode (development tool): row per lane, texel per lane and block per lane around the header of the
-// library's kernel, each with plain and with non-temporal stores, on cube levels of one mode (3) and of a random mode per block, into
+// library's kernel (bc6h_decode_core.h on bc6h_format.h), each with plain and with non-temporal stores, on cube levels of one mode (3) and of a random mode per block, into
 // RGBA32F and RGBA16F.  Prints the best of three windows per variant; at 256^2 every variant must write the bytes of the first.
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off tools/ubench_bc6h_decode.hip -o tools/ubench_bc6h_decode
 #include <hip/hip_runtime.h>

@@ -1,9 +1,9 @@
 // bc6h2_core.h -- the two-region quality level of the BC6H encode contract (K18, DESIGN.md "K18, two regions"), written once for the
-// device kernel of k_bc6h2.hip and for a host compiler (tests/bc6h2_core_host.cpp): integer arithmetic only, as bc6h_core.h.
+// device kernel of k_bc6h.hip and for a host compiler (tests/bc6h_encode_host.cpp): integer arithmetic only, as bc6h_core.h.
 // tests/bc6h2_ref.py restates it in numpy.
 //
 // Output: BC6H_UF16, per block either the one-region block of bc6h_core.h (mode 11, mode field 00011) or one of the four symmetric
-// two-region modes, named as the cases of bc6hd_header's switch:
+// two-region modes, named by their mode field as the lists of bc6h_format.h:
 //     case  0: endpoints of 10 bits, deltas of 5     case 14: 9 bits, deltas of 5
 //     case  1:  7 bits, deltas of 6                  case 30: 6 bits, no delta transform
 // 1. The one-region block and its squared error E1 are bc6h_encode_block_err's.  E1 = 0 ends the block there.
@@ -12,21 +12,21 @@
 //    with G resp. B run max -> min where n sum(r c) - sum(r) sum(c) < 0 over the subset (n its texel count): candidate 2 of the
 //    one-region rule per subset, without an inset.  Four endpoints a0, b0 (subset 0), a1, b1 (subset 1).
 // 3. The mode of the partition is the first of case 0, 14, 1, 30 that fits.  All four endpoints are quantised at the mode's width epb:
-//    the x whose bc6hd_unq(x, epb) is nearest, the lower x on a tie, among s >> (16 - epb) and its two neighbours clamped to
-//    0 .. 2^epb - 1.  A delta mode fits when in every channel max - min over the four quantised endpoints is <= 2^(d - 1) - 1 (15 resp.
-//    31): whichever endpoint becomes the base, every difference then fits d signed bits.  Case 30 always fits.
+//    the x whose bc6h_unq(x, epb) is nearest, the lower x on a tie (bc6h_quantize).  A delta mode fits when in every channel max - min
+//    over the four quantised endpoints is <= 2^(d - 1) - 1 (15 resp. 31): whichever endpoint becomes the base, every difference then
+//    fits d signed bits.  Case 30 always fits.
 // 4. Texel t gets the lowest i in 0 .. 7 that minimises sum_c (palette - h)^2, the palette being bc6h_palette(ua, ub, bc6hd_weight3(i))
 //    of its own subset's unquantised endpoints.  E2(p) is the sum of those minima (64-bit).  The partition with the lowest E2 wins, the
 //    lower p on a tie, and the two-region block replaces the one-region block only if E2 < E1.
 // 5. Anchors: texel 0 for subset 0, bc6hd_anchor(p) for subset 1.  If a subset's anchor index is 4 or more that subset's endpoints are
 //    swapped and every index of its texels becomes 7 - i (the weights are symmetric: the palette does not change).  Then e0, e1 = subset
 //    0's pair, e2, e3 = subset 1's; in the delta modes e1 .. e3 are stored as (e_k - e0) masked to d bits.
-// 6. Packing: the inverse of bc6hd_header's field lists, the partition at bits 77 .. 81, indices from bit 82 in texel order, 2 bits for
-//    the two anchors and 3 for every other texel.
+// 6. Packing: the mode's field list of bc6h_format.h expanded with the writer, the partition at bits 77 .. 81, indices from bit 82 in
+//    texel order, 2 bits for the two anchors and 3 for every other texel.
 // The partition loop is rolled (p and the subset mask are the same for every block in flight: scalars on the device), the loops over
 // texels and channels are unrolled, so no array is indexed by a run-time value.
 #pragma once
-#include "bc6h_decode_core.h"
+#include "bc6h_core.h"
 
 // what was chosen for a block; the tests read it, the kernel drops it
 typedef struct {
@@ -36,16 +36,6 @@ typedef struct {
 } Bc6h2Info;
 
 BC6H_FN uint32_t bc6h2_epb(uint32_t m) { return m == 0u ? 10u : m == 1u ? 9u : m == 2u ? 7u : 6u; }   // m: 0, 1, 2, 3 = case 0, 14, 1, 30
-// the x in 0 .. 2^epb - 1 whose bc6hd_unq(x, epb) is nearest to s (0 .. 65535), the lower x on a tie
-BC6H_FN uint32_t bc6h2_quantize(uint32_t s, uint32_t epb) {
-    const uint32_t top = (1u << epb) - 1u, x1 = s >> (16u - epb), x0 = x1 > 0u ? x1 - 1u : 0u, x2 = x1 < top ? x1 + 1u : top;
-    const int32_t d0 = (int32_t)bc6hd_unq(x0, epb) - (int32_t)s, d1 = (int32_t)bc6hd_unq(x1, epb) - (int32_t)s, d2 = (int32_t)bc6hd_unq(x2, epb) - (int32_t)s;
-    const uint32_t a0 = (uint32_t)(d0 < 0 ? -d0 : d0), a1 = (uint32_t)(d1 < 0 ? -d1 : d1), a2 = (uint32_t)(d2 < 0 ? -d2 : d2);
-    uint32_t x = x0, best = a0;
-    if (a1 < best) { best = a1; x = x1; }
-    if (a2 < best) { x = x2; }
-    return x;
-}
 
 // One partition (steps 2 .. 4).  hs[t][c] = half code | scaled value << 16; mask = bc6hd_subsets(p).  q[3 E + c] = the quantised
 // endpoints a0, b0, a1, b1; *m_out = the mode; idx = 16 indices, texel t at bit 4 t.  Returns E2.
@@ -94,7 +84,7 @@ BC6H_FN uint64_t bc6h2_try(const uint32_t hs[16][3], uint32_t mask, uint32_t q[1
     for (;; ++m) {                                                            // step 3: the first mode that fits
         epb = bc6h2_epb(m);
         BC6H_UNROLL
-        for (int i = 0; i < 12; ++i) q[i] = bc6h2_quantize(sp[i], epb);
+        for (int i = 0; i < 12; ++i) q[i] = bc6h_quantize(sp[i], epb);
         if (m == 3u) break;
         const uint32_t limit = m == 2u ? 31u : 15u;
         bool fit = true;
@@ -109,7 +99,7 @@ BC6H_FN uint64_t bc6h2_try(const uint32_t hs[16][3], uint32_t mask, uint32_t q[1
     }
     uint32_t u[12], err[16];
     BC6H_UNROLL
-    for (int i = 0; i < 12; ++i) u[i] = bc6hd_unq(q[i], epb);
+    for (int i = 0; i < 12; ++i) u[i] = bc6h_unq(q[i], epb);
     BC6H_UNROLL
     for (int t = 0; t < 16; ++t) err[t] = 0xFFFFFFFFu;
     uint64_t idx = 0;
@@ -140,47 +130,14 @@ BC6H_FN uint64_t bc6h2_try(const uint32_t hs[16][3], uint32_t mask, uint32_t q[1
     return total;
 }
 
-// v's low n bits at block bits pos .. pos + n - 1; pos and n are constants at every call, and no field is written twice
-BC6H_FN void bc6h2_put(uint32_t w[4], uint32_t pos, uint32_t n, uint32_t v) {
-    const uint32_t i = pos >> 5, s = pos & 31u;
-    v &= (1u << n) - 1u;
-    w[i] |= v << s;
-    if (s + n > 32u) w[i + 1u] |= v >> (32u - s);                             // pos + n <= 128: i + 1 <= 3 here
-}
-
-// step 6: e[3 E + c] as the decoder's switch names them (e1 .. e3 already deltas where the mode has them), indices after the anchor rule
+// step 6: e[3 E + c] as the field lists name them (e1 .. e3 already deltas where the mode has them), indices after the anchor rule
 BC6H_FN void bc6h2_pack(uint32_t m, const uint32_t e[12], uint32_t partition, uint64_t idx, uint32_t out[4]) {
     uint32_t w[4] = {0, 0, 0, 0};
-    if (m == 0u) {                                                            // case 0
-        bc6h2_put(w, 2, 1, e[7] >> 4); bc6h2_put(w, 3, 1, e[8] >> 4); bc6h2_put(w, 4, 1, e[11] >> 4); bc6h2_put(w, 5, 10, e[0]);
-        bc6h2_put(w, 15, 10, e[1]); bc6h2_put(w, 25, 10, e[2]);
-    } else if (m == 1u) {                                                     // case 14
-        w[0] = 14u;
-        bc6h2_put(w, 5, 9, e[0]); bc6h2_put(w, 14, 1, e[8] >> 4); bc6h2_put(w, 15, 9, e[1]); bc6h2_put(w, 24, 1, e[7] >> 4);
-        bc6h2_put(w, 25, 9, e[2]); bc6h2_put(w, 34, 1, e[11] >> 4);
-    } else if (m == 2u) {                                                     // case 1
-        w[0] = 1u;
-        bc6h2_put(w, 2, 1, e[7] >> 5); bc6h2_put(w, 3, 1, e[10] >> 4); bc6h2_put(w, 4, 1, e[10] >> 5); bc6h2_put(w, 5, 7, e[0]);
-        bc6h2_put(w, 12, 1, e[11]); bc6h2_put(w, 13, 1, e[11] >> 1); bc6h2_put(w, 14, 1, e[8] >> 4); bc6h2_put(w, 15, 7, e[1]);
-        bc6h2_put(w, 22, 1, e[8] >> 5); bc6h2_put(w, 23, 1, e[11] >> 2); bc6h2_put(w, 24, 1, e[7] >> 4); bc6h2_put(w, 25, 7, e[2]);
-        bc6h2_put(w, 32, 1, e[11] >> 3); bc6h2_put(w, 33, 1, e[11] >> 5); bc6h2_put(w, 34, 1, e[11] >> 4);
-    } else {                                                                  // case 30
-        w[0] = 30u;
-        bc6h2_put(w, 5, 6, e[0]); bc6h2_put(w, 11, 1, e[10] >> 4); bc6h2_put(w, 12, 1, e[11]); bc6h2_put(w, 13, 1, e[11] >> 1);
-        bc6h2_put(w, 14, 1, e[8] >> 4); bc6h2_put(w, 15, 6, e[1]); bc6h2_put(w, 21, 1, e[7] >> 5); bc6h2_put(w, 22, 1, e[8] >> 5);
-        bc6h2_put(w, 23, 1, e[11] >> 2); bc6h2_put(w, 24, 1, e[7] >> 4); bc6h2_put(w, 25, 6, e[2]); bc6h2_put(w, 31, 1, e[10] >> 5);
-        bc6h2_put(w, 32, 1, e[11] >> 3); bc6h2_put(w, 33, 1, e[11] >> 5); bc6h2_put(w, 34, 1, e[11] >> 4);
-    }
-    if (m < 2u) {                                                             // cases 0 and 14 share bits 35 .. 76
-        bc6h2_put(w, 35, 5, e[3]); bc6h2_put(w, 40, 1, e[10] >> 4); bc6h2_put(w, 41, 4, e[7]); bc6h2_put(w, 45, 5, e[4]);
-        bc6h2_put(w, 50, 1, e[11]); bc6h2_put(w, 51, 4, e[10]); bc6h2_put(w, 55, 5, e[5]); bc6h2_put(w, 60, 1, e[11] >> 1);
-        bc6h2_put(w, 61, 4, e[8]); bc6h2_put(w, 65, 5, e[6]); bc6h2_put(w, 70, 1, e[11] >> 2); bc6h2_put(w, 71, 5, e[9]);
-        bc6h2_put(w, 76, 1, e[11] >> 3);
-    } else {                                                                  // so do cases 1 and 30
-        bc6h2_put(w, 35, 6, e[3]); bc6h2_put(w, 41, 4, e[7]); bc6h2_put(w, 45, 6, e[4]); bc6h2_put(w, 51, 4, e[10]);
-        bc6h2_put(w, 55, 6, e[5]); bc6h2_put(w, 61, 4, e[8]); bc6h2_put(w, 65, 6, e[6]); bc6h2_put(w, 71, 6, e[9]);
-    }
-    bc6h2_put(w, 77, 5, partition);
+    if (m == 0u) { BC6H_MODE0(BC6H_PUT) }
+    else if (m == 1u) { w[0] = 14u; BC6H_MODE14(BC6H_PUT) }
+    else if (m == 2u) { w[0] = 1u; BC6H_MODE1(BC6H_PUT) }
+    else { w[0] = 30u; BC6H_MODE30(BC6H_PUT) }
+    bc6h_put_bits(w, 77, 5, partition);
     const uint32_t anchor = bc6hd_anchor(partition);
     uint64_t bits = 0;                                                        // the 46 index bits, block bit 82 at bit 0
     uint32_t pos = 0;

@@ -1,89 +1,42 @@
-// bc6h_core.h -- the BC6H encode contract (K18), written once for the device kernel of k_bc6h.hip and for a host compiler:
-// integer arithmetic only, so no rounding or denormal mode of either machine can change a bit.
+// bc6h_core.h -- the one-region search of the BC6H encode contract (K18), written once for the device kernel of k_bc6h.hip and
+// for a host compiler: integer arithmetic only, as bc6h_format.h, which holds everything the format fixes (half codes, the scaled
+// space, unq, weights, palette).
 //
 // Output: BC6H_UF16, mode 11 only (mode field 00011): one region, two RGB endpoints of 10 bits each without delta transform, 16 indices
 // (3 bits for texel 0, the anchor, 4 bits for every other).  Bits of the little-endian 128-bit block:
 //     0-4 mode = 3 | 5-34 r0 g0 b0 | 35-64 r1 g1 b1 | 65-67 index 0 | 68-127 indices 1 .. 15
-// Texel -> half code: round-to-nearest-even fp32 -> fp16 written out below; negative values, -0 and NaN give 0, +Inf and everything that
-// rounds above 65504 give 0x7BFF, half subnormals are kept, alpha is ignored.  Block texel (x, y) of a level of w x h is the source texel
-// (min(x, w - 1), min(y, h - 1)).
-// Decoder arithmetic (the format's): unq(x) = 0 for 0, 0xFFFF for 1023, else ((x << 16) + 0x8000) >> 10; weights {0, 4, 9, 13, 17, 21, 26,
-// 30, 34, 38, 43, 47, 51, 55, 60, 64}; palette entry ((a (64 - w) + b w + 32) >> 6) * 31 >> 6, a half code.
+// Alpha is ignored.  Block texel (x, y) of a level of w x h is the source texel (min(x, w - 1), min(y, h - 1)).
 // Endpoint candidates, per block in the scaled space s = (h * 64 + 30) / 31:
 //     1. the per-channel bounding box, min -> max on all three channels
 //     2. the same box with G resp. B run max -> min where 16 sum(r g) - sum(r) sum(g) resp. the same with b -- 256 times the covariance
 //        about the block mean -- is negative (horizon and sunset gradients: red rises as blue falls)
 //     3. candidate 2 with both ends of every channel pulled in by (max - min) >> 4
-// Each endpoint component is quantised to the x whose unq(x) is nearest, the lower x on a tie.  For each candidate texel t gets the
-// lowest i that minimises sum_c (palette[i][c] - h_t[c])^2 (at most 3 * 31743^2 < 2^32; the block sum is 64-bit); the candidate with
-// the lowest block sum is kept, the earlier one on a tie.  Anchor rule: if the index of texel 0 is 8 or more the endpoints are swapped
-// and every i becomes 15 - i (the weights are symmetric: the palette does not change).
+// Each endpoint component is quantised to the x whose bc6h_unq(x, 10) is nearest, the lower x on a tie.  For each candidate texel t
+// gets the lowest i that minimises sum_c (palette[i][c] - h_t[c])^2 (at most 3 * 31743^2 < 2^32; the block sum is 64-bit); the
+// candidate with the lowest block sum is kept, the earlier one on a tie.  Anchor rule: if the index of texel 0 is 8 or more the
+// endpoints are swapped and every i becomes 15 - i (the weights are symmetric: the palette does not change).
 #pragma once
-#include <stdint.h>
-#if !defined(__cplusplus)
-#include <stdbool.h>
-#endif
+#include "bc6h_format.h"
 
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define BC6H_FN __host__ __device__ __forceinline__
-#define BC6H_UNROLL _Pragma("unroll")
-#define BC6H_NO_UNROLL _Pragma("unroll 1")
-#else
-#define BC6H_FN static inline
-#define BC6H_UNROLL
-#define BC6H_NO_UNROLL
-#endif
-
-// fp32 bits -> fp16 bits, round to nearest even, sign, Inf and NaN kept (NaN becomes a quiet NaN): what the RGBA16F writer stores
-BC6H_FN uint32_t bc6h_f16_from_f32(uint32_t bits) {
-    const uint32_t sign = (bits >> 16) & 0x8000u, a = bits & 0x7FFFFFFFu;
-    if (a > 0x7F800000u) return sign | 0x7E00u;
-    if (a >= 0x47800000u) return sign | 0x7C00u;                              // 65536 and above, Inf included
-    const uint32_t e = a >> 23;
-    if (e >= 113u) {                                                          // a normal half: drop 13 mantissa bits
-        uint32_t h = (a - (112u << 23)) >> 13;
-        const uint32_t rem = a & 0x1FFFu;
-        h += (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) ? 1u : 0u;      // may carry into the exponent, up to 0x7C00 = Inf
-        return sign | h;
-    }
-    if (e < 102u) return sign;                                                // below half of the smallest half subnormal (fp32 subnormals too)
-    const uint32_t mant = (a & 0x7FFFFFu) | 0x800000u, shift = 126u - e;      // 14 .. 24: units of 2^-24
-    uint32_t h = mant >> shift;
-    const uint32_t rem = mant & ((1u << shift) - 1u), half = 1u << (shift - 1u);
-    h += (rem > half || (rem == half && (h & 1u))) ? 1u : 0u;
-    return sign | h;
-}
-// fp16 bits -> the unsigned half code 0 .. 0x7BFF the encoder works on
-BC6H_FN uint32_t bc6h_code_from_f16(uint32_t h) {
-    if (h & 0x8000u) return 0u;                                               // negative, -0, -Inf, NaN with the sign set
-    if (h > 0x7C00u) return 0u;                                               // NaN
-    return h == 0x7C00u ? 0x7BFFu : h;
-}
-BC6H_FN uint32_t bc6h_code_from_f32(uint32_t bits) { return bc6h_code_from_f16(bc6h_f16_from_f32(bits)); }
-
-BC6H_FN uint32_t bc6h_scale(uint32_t h) { return (h * 64u + 30u) / 31u; }     // half code -> the 16-bit space the endpoints live in
-BC6H_FN uint32_t bc6h_unq(uint32_t x) { return x == 0u ? 0u : x == 1023u ? 0xFFFFu : ((x << 16) + 0x8000u) >> 10; }
-// the x in 0 .. 1023 whose unq(x) is nearest to s (0 .. 65535), the lower x on a tie: one of s >> 6 and its two neighbours
-BC6H_FN uint32_t bc6h_quantize(uint32_t s) {
+// bc6h_quantize(s, 10) in the spelling this search was first compiled from: the values are equal for every s, but at a constant
+// width the compiler turns the shared function into other instructions, and the one-region kernels are held to theirs
+// (profiles/bc6h_one_format.md)
+BC6H_FN uint32_t bc6h_quantize10(uint32_t s) {
     const uint32_t x1 = s >> 6, x0 = x1 > 0u ? x1 - 1u : 0u, x2 = x1 < 1023u ? x1 + 1u : 1023u;
-    const int32_t d0 = (int32_t)bc6h_unq(x0) - (int32_t)s, d1 = (int32_t)bc6h_unq(x1) - (int32_t)s, d2 = (int32_t)bc6h_unq(x2) - (int32_t)s;
+    const int32_t d0 = (int32_t)bc6h_unq(x0, 10u) - (int32_t)s, d1 = (int32_t)bc6h_unq(x1, 10u) - (int32_t)s, d2 = (int32_t)bc6h_unq(x2, 10u) - (int32_t)s;
     const uint32_t a0 = (uint32_t)(d0 < 0 ? -d0 : d0), a1 = (uint32_t)(d1 < 0 ? -d1 : d1), a2 = (uint32_t)(d2 < 0 ? -d2 : d2);
     uint32_t x = x0, best = a0;
     if (a1 < best) { best = a1; x = x1; }
     if (a2 < best) { x = x2; }
     return x;
 }
-BC6H_FN uint32_t bc6h_weight(uint32_t i) { return (i * 64u + 7u) / 15u; }     // {0, 4, 9, 13, 17, 21, 26, 30, 34, 38, 43, 47, 51, 55, 60, 64}
-// palette entry of unquantised endpoints a, b at weight w, as a half code (at most 0x7BFF)
-BC6H_FN uint32_t bc6h_palette(uint32_t a, uint32_t b, uint32_t w) { return (((a * (64u - w) + b * w + 32u) >> 6) * 31u) >> 6; }
 
 // One candidate: quantise the endpoints ea / eb (scaled space), give every texel its index; returns the block's squared error.
 // q[0..2] = quantised a, q[3..5] = quantised b; idx = 16 indices of 4 bits, texel t at bit 4 t.
 BC6H_FN uint64_t bc6h_try(const uint32_t h[16][3], const uint32_t ea[3], const uint32_t eb[3], uint32_t q[6], uint64_t* idx_out) {
     uint32_t ua[3], ub[3];
     BC6H_UNROLL
-    for (int c = 0; c < 3; ++c) { q[c] = bc6h_quantize(ea[c]); q[3 + c] = bc6h_quantize(eb[c]); ua[c] = bc6h_unq(q[c]); ub[c] = bc6h_unq(q[3 + c]); }
+    for (int c = 0; c < 3; ++c) { q[c] = bc6h_quantize10(ea[c]); q[3 + c] = bc6h_quantize10(eb[c]); ua[c] = bc6h_unq(q[c], 10u); ub[c] = bc6h_unq(q[3 + c], 10u); }
     uint32_t err[16];
     BC6H_UNROLL
     for (int t = 0; t < 16; ++t) err[t] = 0xFFFFFFFFu;

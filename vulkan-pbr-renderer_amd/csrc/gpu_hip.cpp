@@ -98,7 +98,7 @@ struct GPU_GraphicsPipeline { GPU_PipelineLayout* layout; GPU_RenderPass* pass; 
                               const struct RasterKind* raster = nullptr; /* K12 / K13 / K14: the row of its raster kind */
                               BufferImpl* sh9_buf = nullptr; uint32_t sh9_offset = 0; /* GPUX_SetShadeSH9 */ };
 
-enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster, Op_CopyDecodedT2B, Op_ProjectSH9, Op_IrradianceSH9, Op_EncodeBC6H, Op_DecodeBC6H, Op_EncodeBC6H2 };
+enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster, Op_CopyDecodedT2B, Op_ProjectSH9, Op_IrradianceSH9, Op_EncodeBC6H, Op_DecodeBC6H };
 // one draw of a raster job: job triangles from first_tri on, matrices from the set's GLOBALS, the buffers and the target its kind
 // names (K12 / K13: the buffers bound at the draw; K14: SSBO0 / SSBO1 of the set, first_index = its first vertex) and the pushed
 // constants (K13 reads them: the skybox rebinds both inside the pass)
@@ -122,6 +122,7 @@ struct Op {
     uint32_t mip = 0, mip2 = 0, layer0 = 0, layer_count = 0, layer2 = 0;
     uint64_t off_a = 0, off_b = 0, size = 0;
     float clear[4]; uint32_t cleari[4]; int clear_mode = 0;
+    uint32_t quality = 0;                          // Op_EncodeBC6H: GPUX_BC6H_OneRegion / GPUX_BC6H_TwoRegions
     // submit-time folding (fold_blits): a 1:1 blit whose copy is consumed only by an additive bloom draw onto its target is not
     // executed; that draw takes the blend operand from the blit's source instead
     bool folded = false;
@@ -1649,7 +1650,7 @@ GPU_API uint64_t GPUX_BC6HMipBytes(const GPU_Texture* t, uint32_t mip) {
     if (!t || mip >= t->mip_level_count || t->depth != 1 || bc6h_source_format(t->format) < 0) return 0;
     return pbrk_bc6h_level_bytes((int)mip_dim(t->width, mip), (int)mip_dim(t->height, mip), (int)t->layer_count);
 }
-// op.tex / op.mip = the source level (all layers), op.buf / op.off_b = the blocks, op.size = their bytes
+// op.tex / op.mip = the source level (all layers), op.buf / op.off_b = the blocks, op.size = their bytes, op.quality = the level
 static void record_bc6h_encode(GPU_Graph* g, GPU_Texture* src, uint32_t mip, GPU_Buffer* dst, uint32_t dst_offset, uint32_t quality, const char* fn) {
     GPU_REQUIRE_V(g && !g->submitted, "%s: graph is NULL or already submitted (call GPU_GraphWait first)", fn);
     GPU_REQUIRE_V(g->in_pass == nullptr, "%s: inside a render pass", fn);
@@ -1660,10 +1661,8 @@ static void record_bc6h_encode(GPU_Graph* g, GPU_Texture* src, uint32_t mip, GPU
     GPU_REQUIRE_V((dst_offset % 16) == 0, "%s: buffer offset %u is not a multiple of 16", fn, dst_offset);
     const uint64_t bytes = GPUX_BC6HMipBytes(src, mip);
     GPU_REQUIRE_V((uint64_t)dst_offset + bytes <= dst->size, "%s: buffer too small (%u bytes for %llu at offset %u)", fn, dst->size, (unsigned long long)bytes, dst_offset);
-    Op op;
-    if (quality == GPUX_BC6H_TwoRegions) { op.kind = Op_EncodeBC6H2; op.name = "K18.bc6h_encode2"; }
-    else { op.kind = Op_EncodeBC6H; op.name = "K18.bc6h_encode"; }
-    op.tex = (TextureImpl*)src; op.mip = mip; op.buf = (BufferImpl*)dst; op.off_b = dst_offset; op.size = bytes;
+    Op op; op.kind = Op_EncodeBC6H; op.name = quality == GPUX_BC6H_TwoRegions ? "K18.bc6h_encode2" : "K18.bc6h_encode";
+    op.tex = (TextureImpl*)src; op.mip = mip; op.quality = quality; op.buf = (BufferImpl*)dst; op.off_b = dst_offset; op.size = bytes;
     g->ops.push_back(op);
 }
 GPU_API void GPUX_OpEncodeBC6H(GPU_Graph* g, GPU_Texture* src, uint32_t mip, GPU_Buffer* dst, uint32_t dst_offset) {
@@ -2241,7 +2240,7 @@ static void exec_sh9(GPU_Graph* g, Op& op, size_t& ev_used) {
 static void exec_bc6h(GPU_Graph* g, Op& op, size_t& ev_used) {
     const GPU_Texture& t = op.tex->base;
     const void* level = (const char*)op.tex->dev + op.tex->mip_offset[op.mip];
-    const auto encode = op.kind == Op_EncodeBC6H2 ? pbrk_bc6h_encode2 : pbrk_bc6h_encode;
+    const auto encode = op.quality == GPUX_BC6H_TwoRegions ? pbrk_bc6h_encode2 : pbrk_bc6h_encode;
     timed(g, op.name, ev_used, [&] {
         int rc = encode(level, bc6h_source_format(t.format), (int)mip_dim(t.width, op.mip), (int)mip_dim(t.height, op.mip), (int)t.layer_count,
                         (char*)op.buf->dev + op.off_b, g->cur);
@@ -2385,7 +2384,7 @@ static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
     case Op_Clear: exec_clear(g, op, ev_used); return;
     case Op_CopyB2B: case Op_CopyB2T: case Op_CopyT2B: case Op_CopyDecodedT2B: exec_copy(g, op, ev_used); return;
     case Op_ProjectSH9: case Op_IrradianceSH9: exec_sh9(g, op, ev_used); return;
-    case Op_EncodeBC6H: case Op_EncodeBC6H2: exec_bc6h(g, op, ev_used); return;
+    case Op_EncodeBC6H: exec_bc6h(g, op, ev_used); return;
     case Op_DecodeBC6H: exec_bc6h_decode(g, op, ev_used); return;
     }
 }
@@ -2407,7 +2406,7 @@ static bool op_replayable(const Op& op) {
     case Op_CopyB2B: case Op_CopyB2T: case Op_CopyT2B: case Op_CopyDecodedT2B: return false;          // host pointers may be involved: keep them out of captures
     case Op_Raster: return false;                                             // its draw table is uploaded from pinned staging at submit
     case Op_ProjectSH9: case Op_IrradianceSH9: return true;                   // plain launches on device-visible pointers; the scratch exists since recording
-    case Op_EncodeBC6H: case Op_EncodeBC6H2: return true;                     // one plain launch, texture -> device-visible buffer
+    case Op_EncodeBC6H: return true;                                          // one plain launch, texture -> device-visible buffer
     case Op_DecodeBC6H: return true;                                          // the same, buffer -> texture
     case Op_Clear: return fill_texel_ok(op.tex->texel_bytes);
     case Op_Shade: {
@@ -2523,7 +2522,7 @@ static bool op_access(const Op& op, std::vector<TextureImpl*>& r, std::vector<Te
     case Op_MipGen: r.push_back(op.tex); w.push_back(op.tex); return true;
     case Op_Blit: r.push_back(op.tex); w.push_back(op.tex2); return true;
     case Op_Clear: w.push_back(op.tex); return true;
-    case Op_ProjectSH9: case Op_EncodeBC6H: case Op_EncodeBC6H2: r.push_back(op.tex); return false; // their buffer is not followed: ends the walk like any buffer
+    case Op_ProjectSH9: case Op_EncodeBC6H: r.push_back(op.tex); return false; // their buffer is not followed: ends the walk like any buffer
     case Op_IrradianceSH9: case Op_DecodeBC6H: w.push_back(op.tex); return false;   // the buffer they read is not followed either
     default: return false;
     }

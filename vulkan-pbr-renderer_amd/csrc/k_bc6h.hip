@@ -1,4 +1,6 @@
-// k_bc6h.hip -- K18: one level of RGBA32F / RGBA16F layers -> BC6H_UF16 blocks (mode 11), by the contract of bc6h_core.h.
+// k_bc6h.hip -- K18: one level of RGBA32F / RGBA16F layers -> BC6H_UF16 blocks, at one of two quality levels: the
+// one-region block (mode 11) by the contract of bc6h_core.h, or per block that block or one of the two-region cases 0, 14, 1, 30 by
+// the contract of bc6h2_core.h.  One kernel template: the gather, the argument checks and the launch are the same for both.
 //
 // The output side of the bake: a prefiltered cube leaves the process as one .dds an engine loads (host/pbr_ddsout.c).  16 B (8 B) read
 // and 1 B written per texel, but the time goes to the palette search: 3 candidates x 16 entries x 16 texels x 3 channels of integer
@@ -10,10 +12,17 @@
 // registers as 48 half codes; the loops over candidates and palette entries are kept rolled (the entry index is wave-uniform, its
 // weight is scalar work), the loops over texels and channels are unrolled so that no array is indexed at run time.  Workgroups are
 // single waves: nothing is shared, and a 256^2 level (4096 blocks a face) spreads over every CU.
-#include "bc6h_core.h"
+//
+// Two regions, the opt-in second level for blocks with a hard edge (a sun disc, a horizon, a window): the loop over the 32 partitions
+// is rolled and wave-uniform: the subset mask is a scalar, every per-texel subset choice a select on a scalar bit, and the 16 texels
+// stay in registers as 48 words of half code | scaled value << 16.  Per block 32 partitions x 8 entries x 16 texels of palette search
+// on top of the one-region 3 x 16 x 16, about 5.3 times its palette work plus the per-subset statistics and the endpoint
+// quantisation -- measured 11 times its time (profiles/bc6h_encode2.json; 251 VGPRs, no scratch: profiles/bc6h_encode2.md); the mode
+// loop and the skip of blocks the one-region search already reproduces exactly are the only places where lanes of a wave part.
+#include "bc6h2_core.h"
 #include "pbr_kernels.h"
 
-template <bool F32>
+template <bool F32, bool TWO_REGIONS>
 __global__ __launch_bounds__(64) void k_bc6h_encode(const void* __restrict__ level, int w, int h, int bw, int nblocks, uint4* __restrict__ out) {
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= nblocks) return;
@@ -33,7 +42,12 @@ __global__ __launch_bounds__(64) void k_bc6h_encode(const void* __restrict__ lev
         }
     }
     uint32_t words[4];
-    bc6h_encode_block(codes, words);
+    if (TWO_REGIONS) {
+        Bc6h2Info info;
+        bc6h2_encode_block(codes, words, &info);
+    } else {
+        bc6h_encode_block(codes, words);
+    }
     out[layer * nblocks + b] = make_uint4(words[0], words[1], words[2], words[3]);
 }
 
@@ -42,7 +56,8 @@ extern "C" uint64_t pbrk_bc6h_level_bytes(int width, int height, int layers) {
     return (uint64_t)((width + 3) / 4) * (uint64_t)((height + 3) / 4) * 16u * (uint64_t)layers;
 }
 
-extern "C" int pbrk_bc6h_encode(const void* level, int src_format, int width, int height, int layers, void* blocks_out, void* stream) {
+template <bool TWO_REGIONS>
+static int bc6h_encode(const void* level, int src_format, int width, int height, int layers, void* blocks_out, void* stream) {
     // at most 16384 a side: 4096^2 blocks per layer, every index fits its type; layers ride in grid.y
     if (!level || !blocks_out || width < 1 || height < 1 || width > 16384 || height > 16384 || layers < 1 || layers > 65535) return PBRK_E_ARG;
     if (src_format != PBRK_FMT_RGBA32F && src_format != PBRK_FMT_RGBA16F) return PBRK_E_FORMAT;
@@ -50,7 +65,14 @@ extern "C" int pbrk_bc6h_encode(const void* level, int src_format, int width, in
     const int bw = (width + 3) / 4, bh = (height + 3) / 4, nblocks = bw * bh;
     const dim3 grid((unsigned)((nblocks + 63) / 64), (unsigned)layers), block(64);
     hipStream_t st = (hipStream_t)stream;
-    if (src_format == PBRK_FMT_RGBA32F) hipLaunchKernelGGL((k_bc6h_encode<true>), grid, block, 0, st, level, width, height, bw, nblocks, (uint4*)blocks_out);
-    else hipLaunchKernelGGL((k_bc6h_encode<false>), grid, block, 0, st, level, width, height, bw, nblocks, (uint4*)blocks_out);
+    if (src_format == PBRK_FMT_RGBA32F) hipLaunchKernelGGL((k_bc6h_encode<true, TWO_REGIONS>), grid, block, 0, st, level, width, height, bw, nblocks, (uint4*)blocks_out);
+    else hipLaunchKernelGGL((k_bc6h_encode<false, TWO_REGIONS>), grid, block, 0, st, level, width, height, bw, nblocks, (uint4*)blocks_out);
     return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
+}
+
+extern "C" int pbrk_bc6h_encode(const void* level, int src_format, int width, int height, int layers, void* blocks_out, void* stream) {
+    return bc6h_encode<false>(level, src_format, width, height, layers, blocks_out, stream);
+}
+extern "C" int pbrk_bc6h_encode2(const void* level, int src_format, int width, int height, int layers, void* blocks_out, void* stream) {
+    return bc6h_encode<true>(level, src_format, width, height, layers, blocks_out, stream);
 }

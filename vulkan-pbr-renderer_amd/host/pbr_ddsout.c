@@ -2,14 +2,14 @@
  * pbr_ddsout.c -- the bake's maps as .dds files an engine loads (C11): one DX10-header container per texture with the
  * whole mip chain, the way cmft, IBLBaker and cmgen write theirs, on top of PBR_BuildDDSHeader (host/pbr_dds.c: the header bytes and
  * where every layer's levels go).  Float textures go out as they are (RGBA32F = DXGI 2, RGBA16F = 10, RG16F = 34) or narrowed to
- * RGBA16F on the host; BC6H_UF16 (DXGI 95) is encoded on the device by K18 (csrc/bc6h_core.h is the contract, also of the host's
- * fp32 -> fp16 conversion), at its one-region or its two-region quality (csrc/bc6h2_core.h): the same container either way.  The files load back through host/pbr_ddsin.c, so a bake can be saved and shaded later without the
- * source environment.
+ * RGBA16F on the host (the fp32 -> fp16 conversion of csrc/bc6h_format.h); BC6H_UF16 (DXGI 95) is encoded on the device by K18, at its
+ * one-region or its two-region quality (csrc/bc6h_core.h, csrc/bc6h2_core.h are the contracts): the same container either way.  The
+ * files load back through host/pbr_ddsin.c, so a bake can be saved and shaded later without the source environment.
  *
  * The file is face-major (each face with its levels), texture memory level-major: the writer reorders.
  */
 #include "pbr_host.h"
-#include "../csrc/bc6h_core.h"
+#include "../csrc/bc6h_format.h"
 
 #include <stdio.h>
 #include <stdlib.h>
