@@ -198,6 +198,34 @@ void pbrk_mc_set_resident(int on);
  * proved samples summed over tiles, pairs taken by the proved runs, pairs taken by the general pass}.  Its tiles also enter the flag
  * and wave-slice counters; the window counter counts k_mc_region's proved samples alone. */
 int pbrk_mc_resident_stats(unsigned long long* out4);
+/* ---- the bin cache of the region and resident kernels (k_mc_region.hip, 2m).  What a tile's binning computes -- which regions its samples
+ * can reach, which samples are proved -- depends on the tile's geometry, the level's shape and the sample table, never on a texel.  The
+ * first whole-level launch (six faces, every row) of a (device, kernel shape, n_src, output size, n_entries, table) writes every tile's
+ * flags to device memory; every later launch whose tiles are tiles of that dispatch copies them instead of computing them.  Same samples,
+ * same order, same bytes.
+ * A table pointer says nothing about its contents, so only registered tables are served: pbrk_mc_table_register declares the
+ * n_entries x float4 table at table4 immutable until pbrk_mc_table_unregister (which also drops what was recorded with it).  Every
+ * registration is a new generation; a launch may use a prefix of a registered table (its own entry).  Return 0, or PBRK_E_ARG. */
+int pbrk_mc_table_register(const void* table4, int n_entries);
+int pbrk_mc_table_unregister(const void* table4);
+/* -1 (default): the environment (PBR_MC_BIN_CACHE=0|1), else on exactly when the device counters are off (the rule of pbrk_mc_set_net);
+ * 0: off; 1: on, with or without the counters.  Launches being captured into a graph, region-kernel launches without a k_mc_prep slot,
+ * the yardstick instantiations (pbrk_mc_set_runs(0), pbrk_mc_set_prologue(0), the 18^2 shape) and region-kernel row windows that do not
+ * start on a tile row and end on one or at the face's end always compute. */
+void pbrk_mc_set_bin_cache(int mode);
+/* bytes the cache may hold per device (default 512 MiB).  No eviction: an entry that would pass the budget is not created. */
+void pbrk_mc_set_bin_cache_budget(size_t bytes);
+/* frees every entry (waits for the device); the next whole-level launch records again */
+void pbrk_mc_bin_cache_clear(void);
+/* since the library was loaded: {recording launches, replaying launches, launches that computed though the cache was on (a launch declined
+ * for the budget among them), launches declined for the budget}, and the bytes held now */
+void pbrk_mc_bin_cache_stats(unsigned long long out[5]);
+/* host twin of the kernels' block -> tile map (mc_tile_of_block, k_mc_internal.h) for a dispatch of faces [face0, face0 + nfaces) and rows
+ * [y0, y1) of a size^2 output with tile x tile tiles (8, 16 or 32): out4 = {face, tile column, tile row counted from the dispatch's first,
+ * the tile's index in the cache: (face * tiles_per_edge + y0 / tile + row) * tiles_per_edge + column}.  Needs no GPU. */
+int pbrk_mc_tile_of_block(int block, int size, int tile, int face0, int nfaces, int y0, int y1, int* out4);
+/* 1 when a region-kernel dispatch of rows [y0, y1) may record or replay: y0 a multiple of the tile, y1 one or the face's end.  Needs no GPU. */
+int pbrk_mc_bin_window_eligible(int size, int tile, int y0, int y1);
 
 /* ---- K5: deferred shade pass (shaders/lighting_pass.glsl:432-716, in-scope sub-blocks). */
 typedef struct PbrkShadeArgs {

@@ -3,7 +3,9 @@
 given (n_src, out_size, roughness).  Kernel choice follows the library (env PBR_MC_LDS / PBR_MC_REGION / PBR_MC_BINNED); env
 PBR_MC_TILE32 = -1 | 0 | 1 goes to pbrk_mc_set_tile32 (the region kernel's 32 x 32 tile: by rule, never, wherever the shape allows);
 PBR_MC_NET = -1 | 0 | 1 goes to pbrk_mc_set_net (the region kernel's completeness net: by rule, off where it can be, always on);
-PBR_MC_RESIDENT=0 keeps levels of at most 16^2 texels off k_mc_resident (the library reads it).
+PBR_MC_RESIDENT=0 keeps levels of at most 16^2 texels off k_mc_resident (the library reads it).  The table is registered
+(pbrk_mc_table_register), so the bin cache serves it by its default rule: the untimed first launch records, the timed ones replay;
+PBR_MC_BIN_CACHE=0 keeps it off (the library reads it).
    python3 tools/mc_probe.py n_src out_size [roughness] [rows] [face0 face1]"""
 import ctypes as C
 import os
@@ -44,6 +46,7 @@ def main():
     alpha = C.c_float()
     n_tab = L.pbrk_host_prefilter_table(8192, rough, tab.ctypes.data_as(C.c_void_p), C.byref(alpha))
     dtab = torch.from_numpy(tab).to(dev)
+    assert L.pbrk_mc_table_register(dtab.data_ptr(), n_tab) == 0
     outt = torch.zeros((6, out, out, 4), dtype=torch.float32, device=dev)
     torch.cuda.synchronize()
 
@@ -85,7 +88,9 @@ def main():
                   + ", ".join(f"{v / tiles:.0f}" for v in c["phase"]), flush=True)
         if "healed" in c:
             print(f"   region kernel: {c['healed']} of {c['slices']} wave-slices recomputed with direct loads", flush=True)
-    L.GPU_WaitUntilIdle(); L.GPU_Deinit()
+    bc = mc.bin_cache_stats(L)
+    print(f"   bin cache: {bc['recorded']} recording, {bc['replayed']} replaying, {bc['computed']} computing launches, {bc['bytes']} bytes held", flush=True)
+    L.GPU_WaitUntilIdle(); L.pbrk_mc_table_unregister(dtab.data_ptr()); L.GPU_Deinit()
 
 
 if __name__ == "__main__":

@@ -296,7 +296,8 @@ GPU_API void GPU_Init(GPU_WindowHandle window) {
 GPU_API void GPU_Deinit(void) {
     if (!G.init) return;
     (void)hipDeviceSynchronize();
-    for (auto& kv : G.tables) (void)hipFree(kv.second.dev);
+    pbrk_mc_bin_cache_clear();                                  // the bin cache's buffers go with the tables they were recorded from
+    for (auto& kv : G.tables) { (void)pbrk_mc_table_unregister(kv.second.dev); (void)hipFree(kv.second.dev); }
     G.tables.clear();
     if (G.raster_rejected) {
         unsigned long long d = 0;
@@ -1189,6 +1190,8 @@ static DeviceTable* get_table(int kind, int n, float roughness, int aux) {
     hipError_t e = hipMalloc(&t.dev, bytes);
     if (e != hipSuccess) { gpu_fail("table allocation failed: %s", hipGetErrorString(e)); return nullptr; }
     HIP_OK(hipMemcpy(t.dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    // written once, never again: the Monte-Carlo kernels may keep what they derive from it (the bin cache, k_mc_region.hip 2m)
+    if (kind <= 1 && t.count > 0) (void)pbrk_mc_table_register(t.dev, t.count);
     auto ins = G.tables.insert({key, t});
     return &ins.first->second;
 }

@@ -129,6 +129,48 @@ __host__ __device__ inline void mc_mono_from(const unsigned* wbits, int NW, int 
     }
 }
 
+// k_mc_region.hip, tile_of_block: block -> (face, tx, ty) of a dispatch of tiles_per_face = tiles_x * tiles_y tiles per face that starts
+// at face0; ty counts from the dispatch's first tile row.  Tiles in plain block order but for the faces +X / -X, whose rows are dealt
+// outwards from pole_row[face] (the comment at tile_of_block says why).  A bijection of the dispatch's blocks onto its tiles.
+__host__ __device__ __forceinline__ void mc_tile_of_block(unsigned block, int face0, int tiles_x, int tiles_per_face, const int* pole_row,
+                                                          int& face, int& tx, int& ty) {
+    face = face0 + (int)(block / (unsigned)tiles_per_face);
+    const int tf = (int)(block % (unsigned)tiles_per_face);
+    ty = tf / tiles_x;
+    tx = tf % tiles_x;
+    if (face < 2) {
+        const int ny = tiles_per_face / tiles_x, pr = pole_row[face];
+        const int a = pr < ny - 1 - pr ? pr : ny - 1 - pr;
+        if (ty <= 2 * a) { const int h = (ty + 1) >> 1; ty = (ty & 1) ? pr + h : pr - h; }
+        else { const int rest = ty - 2 * a; ty = (pr > ny - 1 - pr) ? pr - a - rest : pr + a + rest; }
+    }
+}
+
+// Tile row (relative to the tiles' first row y0, clamped) of the tangent frame's pole on faces +X (t = (1 - vy/vx)/2) and -X
+// (t = (1 + vy/vx)/2), v = the vector of tangent_of: mc_tile_of_block deals the rows of these faces outwards from it
+inline void mc_pole_rows(int size, int y0, int tile, int tiles_y, int* pole_row) {
+    const double vy_vx = 6.11831989512 / 12.123825810901;
+    for (int f = 0; f < 2; ++f) {
+        int row = (int)((f == 0 ? 0.5 * (1.0 - vy_vx) : 0.5 * (1.0 + vy_vx)) * size);
+        int tr = (row - y0) / tile;
+        if (row < y0) tr = 0;
+        pole_row[f] = tr < 0 ? 0 : (tr > tiles_y - 1 ? tiles_y - 1 : tr);
+    }
+}
+
+// k_mc_region.hip, header 2m: the bin cache.  A tile's flags are masks[NR][NW], then cmask[NW]; tiles lie [face][tile row from row 0 of
+// the face][tile column], each on a stride of whole 16-byte groups so that a lane's 16-byte load never straddles two tiles.
+__host__ __device__ __forceinline__ unsigned mc_bin_tile_words(int NR, int NW) { return ((unsigned)(NR + 1) * (unsigned)NW + 3u) & ~3u; }
+// the index of tile (face, first_row + ty, tx): first_row = the dispatch's first tile row, counted from row 0 of the face
+__host__ __device__ __forceinline__ unsigned mc_bin_tile_index(int face, int first_row, int ty, int tx, int tiles_x, int tiles_y_face) {
+    return (unsigned)((face * tiles_y_face + first_row + ty) * tiles_x + tx);
+}
+// Which row windows [y0, y1) of the region kernel may use the cache: its tiles start at the dispatch's first row and their frames clamp at
+// its last, so the window must start on a tile row of the whole-face dispatch and end on one or at the face's end.
+__host__ __device__ __forceinline__ bool mc_bin_window_ok(int size, int tile, int y0, int y1) {
+    return y0 >= 0 && y0 < y1 && y1 <= size && y0 % tile == 0 && (y1 % tile == 0 || y1 == size);
+}
+
 // k_mc_region.hip: taps from LDS-staged regions of the source level.  Returns false when the kernel does not apply
 // (the caller then takes the direct kernel); the decision depends on the level's shape only, never on the dispatched range.
 bool launch_mc_region(McArgs a, int nfaces, hipStream_t st);

@@ -169,6 +169,31 @@
 //      comparison against the checked instantiation on every shape, table length, row shard, work unit and hostile level of
 //      tests/test_gpu_mc_net.py (C4 mips 1 - 3 at full size among them), and the every-texel cross-check against the direct kernel in
 //      tests/test_gpu_configs.py.  As k_mc_resident (2k), which never had a net in its product kernel.  Measured: profiles/net_off.md.
+//   2m. (binning once per process; the bin cache) region_bin reads the tile's geometry, the level's shape and the sample table, and no texel:
+//      for one (kernel shape, n_src, output size, table) every call recomputes the same masks[] and cmask[] in every tile -- a hot reload, a new
+//      environment at the same sizes, a probe refreshed each frame -- and the tile-centre frame with its correctly rounded divisions and roots
+//      exists only to feed it.  With the sample loops at a quarter of their first length that is 3 - 6 % of a tile's VALU instructions on C4's
+//      big levels and 13 % on mip 5.  RegArgs carries two pointers: bins_out (record) -- the first whole-level launch (six faces, every row) bins
+//      as ever, but EVERY sample (region_bin's keep_cut: the launch cut depends on the level's texels and moves from call to call; a cut sample sets
+//      its mask bit and flags no region), stores the tile's words to device memory (region_bin_record), then clears the cut words as the counters'
+//      block does -- and bins (replay) -- every later launch whose tiles are tiles of that dispatch copies them, 16 bytes per lane, zeroes the
+//      words at or behind its slice's cut, and rebuilds any[] from the words that are left (region_bin_replay); no centre frame, no dmax, no
+//      sample touched.  The flags are the recorded launch's bit for bit, so the samples taken, their order, the absorb decisions and every
+//      output byte are what they were; under PBR_MC_STATS the uncut words are loaded and the counters' block counts and clears them: every
+//      counter keeps its value.  The branch is workgroup-uniform and sits in the prologue; the sample loops have no new parameter (BINS = RUNS
+//      && LEAN is a name for existing ones).  Who takes part: the lean run loops (both FOLD and NET values) and the four forms of
+//      k_mc_resident.  Everything else bins as ever: the yardsticks (RUNS = false, LEAN = false, the 18^2 shape), a 66^2 launch without a
+//      k_mc_prep slot, stream capture, an unregistered table (pbrk_mc_table_register: a pointer says nothing about its contents; each
+//      registration is a generation), and region-kernel row windows that do not start on a tile row of the whole-level dispatch and end on one
+//      or at the face's end (mc_bin_window_ok: the tiles start at the dispatch's first row and their frames clamp at its last; ragged shards,
+//      the partitions of a multi-GPU job among them).  k_mc_resident's tiles are anchored at row 0 of the face: every dispatch of it may
+//      replay.  Tiles lie [face][tile row from row 0][tile column] (mc_bin_tile_index; pbrk_mc_tile_of_block is the host twin of the block ->
+//      tile map), (NR + 1) NW words each on a stride of whole 16-byte groups (mc_bin_tile_words).  Host: one entry per {device, kernel shape,
+//      n_src, output size, n_entries, table, generation}, an event behind the recording launch that a replay on any stream waits for, one lock,
+//      no eviction, a budget (512 MiB per device by default; C4 holds 345 MB beside 2.1 GB of outputs) past which an entry is not created.
+//      pbrk_mc_set_bin_cache(-1), the default, is on exactly when the device counters are off -- the rule of pbrk_mc_set_net -- so the suite
+//      keeps its paths and tests/test_gpu_mc_bin_cache.py asks for both states by name.  At most 64 VGPRs, no spill, no scratch (the net-carrying
+//      instantiations form the texel index again ahead of the reduction to stay there).  Measured: profiles/bin_cache.md.
 // Each (texel, sample) pair is accumulated exactly once, in an order (66^2 shapes: head phase then tail phase; in each, own face's
 // regions, then the other regions in index order; else regions in index order; sample index inside a region) that depends on the
 // level's shape and the texel's face only, not on the tile: a row-sharded dispatch equals a full one bit for bit.
@@ -179,6 +204,7 @@
 #include <stdlib.h>
 #include <mutex>
 #include <type_traits>
+#include <vector>
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 // The sample table is read-only for the whole launch: a pointer into the constant address space makes every wave-uniform
@@ -251,6 +277,9 @@ struct RegArgs {
                                 // k_mc_resident (2k): [1] .. [4] per tile as above ([0] and [5] stay: nothing is recomputed, and [5] counts k_mc_region's proved
                                 // samples alone), [16] += (lane, sample) pairs whose proof did not hold, [17] += proved samples per tile, [18] / [19] += pairs
                                 // taken by the proved runs / by the general pass
+    const unsigned* bins;       // header 2m, replay: every tile's flags as an earlier launch of this (kernel shape, level shape, table) recorded them
+                                // (mc_bin_tile_index, mc_bin_tile_words); the tile copies its words instead of binning.  null: bin
+    unsigned* bins_out;         // header 2m, record: bin every sample (the cut ones too) and store the tile's flags there.  null: do not
 };
 
 // direction -> (sc, tc, ma) of face f: the table of v_cubesc / v_cubetc / v_cubema (gen_prefiltered_env_map.glsl:12-23)
@@ -654,27 +683,58 @@ __device__ __forceinline__ void region_bin(unsigned* masks, unsigned* any, unsig
     }
 }
 
+// Header 2m, replay: region_bin's result for this tile as an earlier launch recorded it at src -- masks[NR][NW], then cmask[NW], every
+// sample's bits, the cut ones too (the cut moves with the level's texels, the flags do not).  Coalesced 16-byte loads, a lane's four words
+// written to LDS one by one (cmask sits behind any[] and dmax: no 16-byte alignment).  cutw (the launch has a cut): the first cut word of
+// each of the S slices; a word at or behind its slice's cut flags no region, as a cut sample flags none in region_bin, and is zeroed --
+// unless keep_cut (the counters are on): then it stays for the caller's block to count and clear, as region_bin's keep_cut leaves it.
+// any[] is rebuilt as binning sets it: a word that is not zero flags its region; TWO: byte 0 for the head words (below S), byte 1 for
+// the rest.  dmax stays 0: nothing reads it.  Leaves with a barrier pending, as region_bin does.
+template <bool TWO, int S>
+__device__ __forceinline__ void region_bin_replay(unsigned* masks, unsigned* any, int NR, int NW, const unsigned* __restrict__ src, int tid,
+                                                  const unsigned* __restrict__ cutw, bool keep_cut) {
+    if (tid < NR + 1) masks[NR * NW + tid] = 0u;                    // any[], dmax
+    __syncthreads();                                               // also orders the caller's clearing of skc
+    const int nflag = NR * NW, nw = nflag + NW;
+    for (int k = tid * 4; k < nw; k += 4096) {
+        const uint4 v = *(const uint4*)(src + k);
+        const unsigned wv[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int kk = k + j;
+            if (kk < nw) {
+                const int r = kk / NW, w = kk - r * NW;            // r == NR: cmask
+                unsigned m = wv[j];
+                const bool cut = cutw && w >= (int)cutw[w % S];
+                if (cut && !keep_cut) m = 0u;
+                masks[kk < nflag ? kk : kk + NR + 1] = m;
+                if (kk < nflag && m != 0u && !cut) {
+                    if (TWO) ((unsigned char*)any)[4 * r + (w >= S ? 1 : 0)] = 1;
+                    else any[r] = 1u;
+                }
+            }
+        }
+    }
+}
+
+// Header 2m, record: the tile's flags as region_bin left them (every sample binned: keep_cut) go to dst in replay's layout.  The caller
+// has synchronised behind region_bin; it synchronises again before it changes a word.
+__device__ __forceinline__ void region_bin_record(const unsigned* masks, int NR, int NW, unsigned* __restrict__ dst, int tid) {
+    const int nflag = NR * NW, nw = nflag + NW;
+    for (int k = tid; k < nw; k += 1024) dst[k] = masks[k < nflag ? k : k + NR + 1];
+}
+
 // Block -> (face, tx, ty).  Tiles in plain block order: consecutive tiles go round-robin over the 8 XCDs.  An XCD-contiguous remap (one
 // eighth of the grid per XCD) put all tiles around the pole of the tangent frame -- where every sample is flagged for several regions and
 // a tile takes up to 3x as long -- on ONE XCD, and the launch waited for it (a single-face dispatch of a +-X face: 10.2 vs 7.6 ms).
 // The whole level fits every XCD's L2, so locality has nothing to lose.
 __device__ __forceinline__ void tile_of_block(const RegArgs& q, int& face, int& tx, int& ty) {
-    const McArgs& p = q.a;
-    const unsigned tile = blockIdx.x;
-    face = p.face0 + (int)(tile / (unsigned)p.tiles_per_face);
-    const int tf = (int)(tile % (unsigned)p.tiles_per_face);
-    ty = tf / p.tiles_x;
-    tx = tf % p.tiles_x;
     // Longest tiles first: around the pole of the tangent frame (tangent_of: inside the +X face, its antipode inside -X) the frames
     // of a tile twist against each other, a sample lands in several regions and a tile takes up to 3x as long.  In row order those
     // tiles came last on the -X face (pole at 3/4 of its height) and the launch ended in their tail; here the rows of these two
-    // faces are dealt outwards from the pole row, so the long tiles start first and the short ones fill in behind them.
-    if (face < 2) {
-        const int ny = p.tiles_per_face / p.tiles_x, pr = q.pole_row[face];
-        const int a = min(pr, ny - 1 - pr);
-        if (ty <= 2 * a) { const int h = (ty + 1) >> 1; ty = (ty & 1) ? pr + h : pr - h; }
-        else { const int rest = ty - 2 * a; ty = (pr > ny - 1 - pr) ? pr - a - rest : pr + a + rest; }
-    }
+    // faces are dealt outwards from the pole row, so the long tiles start first and the short ones fill in behind them
+    // (mc_tile_of_block, k_mc_internal.h: the host's twin is pbrk_mc_tile_of_block).
+    mc_tile_of_block(blockIdx.x, q.a.face0, q.a.tiles_x, q.a.tiles_per_face, q.pole_row, face, tx, ty);
 }
 
 // Output texel of thread t of a slice.  A wave covers an 8 x 8 quadrant of the tile (not 16 x 4): the smaller its extent, the fewer
@@ -822,6 +882,8 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     // index order and their bytes: there the reordered sums bought nothing and moved C4 mip 3 to 2.5e-5 from the direct kernel,
     // past the 2e-5 of the every-texel cross-check (test_gpu_configs.py)
     constexpr bool OWN_FIRST = ABS;
+    // see the header, 2m: the product instantiations (the lean run loops, both FOLD and NET values) can record and replay their binning
+    constexpr bool BINS = RUNS && LEAN;
     // see the header, 2g: head words first, then the tail words; decided per 66^2 shape (MC_HEAD_FIRST_SUB / MC_HEAD_FIRST_G1)
     constexpr bool TWO = RS == 66 && (SUB ? MC_HEAD_FIRST_SUB != 0 : MC_HEAD_FIRST_G1 != 0);
     const bool cut_on = TWO && LEAN && q.cut != 0;                       // workgroup-uniform: the launch's cut words are not binned
@@ -854,10 +916,6 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     const f3 R = face_texel_dir(face, xc, yc, p.size);
     const f3 T = tangent_of(R);
     const f3 B = cross3(T, R);
-    // tile-centre frame (evaluated redundantly per lane: wave-uniform values)
-    const f3 Rc = face_texel_dir(face, min(tx * TILE + TILE / 2, p.size - 1), min(p.y0 + ty * TILE + TILE / 2, p.y0 + p.rows - 1), p.size);
-    const f3 Tc = tangent_of(Rc);
-    const f3 Bc = cross3(Tc, Rc);
 
     const int n = p.n_src, nb = n + 2;
     const float nf = (float)n;
@@ -871,9 +929,33 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     [[maybe_unused]] const unsigned long long st1 = STAMP();
     // the first cut word of this thread's slice (a vector load of one of the REG_S words behind the maxima): samples tid + 1024 k lie
     // in word (tid >> 5) + 32 k, that is in slice (tid >> 5) % REG_S
-    const int lim = cut_on ? (int)q.tabmax[NW + NR + ((tid >> 5) % REG_S)] << 5 : 0x7fffffff;
-    region_bin<LEAN, !SUB, TWO, CERT || ABS, CERT && !SUB>(masks, any, dmax, NR, NW, G, RC, n, R, T, B, Rc, Tc, Bc, tab, p.n_tab, tid, (CERT || ABS) ? cmask : nullptr,
-                                (absorb_on && !LEAN) ? wmax : nullptr, ntail, lim, cut_on && q.stats != nullptr, 32 * REG_S);
+    // header 2m: this tile's place in the bin cache -- its (face, row from row 0 of the face, column) in the whole-level dispatch
+    [[maybe_unused]] const size_t bin_at = (size_t)mc_bin_tile_index(face, p.y0 / TILE, ty, tx, p.tiles_x, (p.size + TILE - 1) / TILE) * mc_bin_tile_words(NR, NW);
+    if (BINS && q.bins) {                                                // workgroup-uniform: no centre frame, no dmax, no sample is looked at
+        region_bin_replay<TWO, REG_S>(masks, any, NR, NW, q.bins + bin_at, tid, cut_on ? q.tabmax + NW + NR : nullptr, q.stats != nullptr);
+    } else {
+        // tile-centre frame (evaluated redundantly per lane: wave-uniform values)
+        const f3 Rc = face_texel_dir(face, min(tx * TILE + TILE / 2, p.size - 1), min(p.y0 + ty * TILE + TILE / 2, p.y0 + p.rows - 1), p.size);
+        const f3 Tc = tangent_of(Rc);
+        const f3 Bc = cross3(Tc, Rc);
+        const bool rec = BINS && q.bins_out != nullptr;                  // workgroup-uniform
+        const int lim = cut_on ? (int)q.tabmax[NW + NR + ((tid >> 5) % REG_S)] << 5 : 0x7fffffff;
+        region_bin<LEAN, !SUB, TWO, CERT || ABS, CERT && !SUB>(masks, any, dmax, NR, NW, G, RC, n, R, T, B, Rc, Tc, Bc, tab, p.n_tab, tid, (CERT || ABS) ? cmask : nullptr,
+                                    (absorb_on && !LEAN) ? wmax : nullptr, ntail, lim, cut_on && (q.stats != nullptr || rec), 32 * REG_S);
+        if (rec) {
+            // the cache holds the flags of EVERY sample: the launch cut depends on the level's texels and moves from call to call.  The cut
+            // words then go, as in the counters' block below, which keeps doing it (and counting them) when the counters are on.
+            __syncthreads();
+            region_bin_record(masks, NR, NW, q.bins_out + bin_at, tid);
+            if (cut_on && !q.stats) {
+                __syncthreads();
+                for (int k = tid; k < NR * NW; k += 1024) {
+                    const int w = k % NW;
+                    if (w >= (int)q.tabmax[NW + NR + (w % REG_S)]) masks[k] = 0u;
+                }
+            }
+        }
+    }
     [[maybe_unused]] unsigned long long st_stage = 0ull;
 #ifdef PBR_MC_PHASE_STAMPS
     __syncthreads();                                               // the wait for the slowest thread's binning is charged to binning
@@ -993,13 +1075,13 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     __syncthreads();                                               // everybody is done with the staged region
     if (absorb_on && q.stats && tid < 3 && skc[tid]) atomicAdd(&q.stats[6 + tid], (unsigned long long)skc[tid]);
     float* red = (float*)smem_r;
-    reduce_slices<REG_TX, REG_S>(red, s, t, ar, ag, ab);
-    // The texel's coordinates are formed AGAIN from the thread index (opaque to the optimiser) instead of being kept alive across
+    // The texel's index and coordinates are formed AGAIN from the thread index (opaque to the optimiser) instead of being kept alive across
     // the passes: at the 64-VGPR budget the quarter-face instantiation otherwise spills them (4 VGPRs, 16 bytes of scratch per lane
     // and tile: harmless in time, but rocprofv3's WRITE_SIZE of C4 mip 1 read 853 MB against 403 MB of output).
     int tid_o = tid, x_o, y_o;
     asm volatile("" : "+v"(tid_o));
     const int t_o = tid_o % REG_TX;
+    reduce_slices<REG_TX, REG_S>(red, s, NET ? t_o : t, ar, ag, ab);         // t_o: the net-carrying instantiations have no register to keep t in across the passes
     texel_of_thread<TILE>(p, tx, ty, t_o, x_o, y_o);
     if (x_o < p.size && y_o < p.y0 + p.rows && s == 0) {
         float4 o;
@@ -1130,15 +1212,26 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     const f3 R = face_texel_dir(face, xc, yc, p.size);
     const f3 T = tangent_of(R);
     const f3 B = cross3(T, R);
-    const f3 Rc = face_texel_dir(face, min(tx * TILE + TILE / 2, p.size - 1), min(p.y0 + ty * TILE + TILE / 2, p.y0 + p.rows - 1), p.size);
-    const f3 Tc = tangent_of(Rc);
-    const f3 Bc = cross3(Tc, Rc);
     ctab_t tab = (ctab_t)(unsigned long long)p.tab;
 
     // ---- 2. binning, with the proof (one flagged face, every texel of the tile on it, taps inside its block) ----
-    region_bin<true, true, false, true, true>(masks, any, dmax, 6, NW, 1, n + 1, n, R, T, B, Rc, Tc, Bc, tab, p.n_tab, tid, cmask, nullptr, NW,
-                                              0x7fffffff, false, 32 * REG_S);
-    __syncthreads();
+    // header 2m: recorded once per (tile size, level shape, table), copied from then on; p.y0 is a tile row of the face here
+    const size_t bin_at = (size_t)mc_bin_tile_index(face, p.y0 / TILE, ty, tx, p.tiles_x, (p.size + TILE - 1) / TILE) * mc_bin_tile_words(6, NW);
+    if (q.bins) {                                                  // workgroup-uniform
+        region_bin_replay<false, REG_S>(masks, any, 6, NW, q.bins + bin_at, tid, nullptr, false);
+        __syncthreads();
+    } else {
+        const f3 Rc = face_texel_dir(face, min(tx * TILE + TILE / 2, p.size - 1), min(p.y0 + ty * TILE + TILE / 2, p.y0 + p.rows - 1), p.size);
+        const f3 Tc = tangent_of(Rc);
+        const f3 Bc = cross3(Tc, Rc);
+        region_bin<true, true, false, true, true>(masks, any, dmax, 6, NW, 1, n + 1, n, R, T, B, Rc, Tc, Bc, tab, p.n_tab, tid, cmask, nullptr, NW,
+                                                  0x7fffffff, false, 32 * REG_S);
+        __syncthreads();
+        if (q.bins_out) {
+            region_bin_record(masks, 6, NW, q.bins_out + bin_at, tid);
+            __syncthreads();                                       // the words change below
+        }
+    }
     if (STATS) {                                                   // the counters of k_mc_region's binning, in its units
         unsigned fl = 0;
         for (int k = tid; k < 6 * NW; k += 1024) fl += __popc(masks[k]);
@@ -1473,18 +1566,6 @@ static unsigned long long* reg_stats() {
     return g_reg_stats;
 }
 
-// Tile row (relative to the tiles' first row y0, clamped) of the tangent frame's pole on faces +X (t = (1 - vy/vx)/2) and -X
-// (t = (1 + vy/vx)/2), v = the vector of tangent_of: tile_of_block deals the rows of these faces outwards from it
-static void pole_rows(int size, int y0, int tile, int tiles_y, int* pole_row) {
-    const double vy_vx = 6.11831989512 / 12.123825810901;
-    for (int f = 0; f < 2; ++f) {
-        int row = (int)((f == 0 ? 0.5 * (1.0 - vy_vx) : 0.5 * (1.0 + vy_vx)) * size);
-        int tr = (row - y0) / tile;
-        if (row < y0) tr = 0;
-        pole_row[f] = tr < 0 ? 0 : (tr > tiles_y - 1 ? tiles_y - 1 : tr);
-    }
-}
-
 // Which tile serves a level (header 2h): a function of the level alone -- n_src, n_tab, the output size -- never of the dispatch's faces
 // or rows, so a row shard equals the full dispatch bit for bit.  32 x 32 x 1 needs the quarter-face shape (its body is the shortest and
 // its prologue the largest share) and NW <= 64 (one ballot of region_pass_runs); the rule adds size >= MC_TILE32_MIN_SIZE: below it
@@ -1493,6 +1574,127 @@ static bool mc_tile32(int n_src, int n_tab, int size) {
     if (n_src <= 64 || (n_tab + 31) / 32 > 64) return false;
     const int mode = g_mc_tile32 < 0 ? (MC_TILE32_SUB ? -1 : 0) : g_mc_tile32;
     return mode > 0 || (mode < 0 && size >= MC_TILE32_MIN_SIZE);
+}
+
+// ---- header 2m: the bin cache ----
+// What binning computes depends on the tile's geometry, the level's shape and the sample table, never on a texel: one buffer per
+// (device, kernel shape, n_src, output size, n_entries, table, generation) holds every tile's flags, written by the first whole-level
+// launch and read by every eligible launch after it.  A raw table pointer says nothing about its contents, so only tables registered as
+// immutable (pbrk_mc_table_register) are served; each registration is a new generation.  No eviction: an entry that would pass the budget
+// is not created.  One lock orders lookup, creation and the event behind the recording launch; a replay on any stream waits for that event.
+struct BinTable { const void* ptr; int n; unsigned long long gen; };
+struct BinEntry {
+    int dev, flavour, n_src, size, n_tab; const void* tab; unsigned long long gen;
+    unsigned* buf; size_t bytes; hipEvent_t ready; bool done;
+};
+static std::vector<BinTable> g_bin_tables;
+static std::vector<BinEntry> g_bin_entries;
+static std::mutex g_bin_lock;
+static int g_bin_mode = -1;
+static size_t g_bin_budget = (size_t)512 << 20;
+static unsigned long long g_bin_gen = 0;
+static unsigned long long g_bin_count[4];               // recording launches, replaying launches, computed though the cache was on, declined for the budget
+
+static void bin_entry_free(BinEntry& e) { (void)hipFree(e.buf); (void)hipEventDestroy(e.ready); }   // hipFree waits for the device
+
+extern "C" void pbrk_mc_set_bin_cache(int mode) { g_bin_mode = mode < 0 ? -1 : (mode ? 1 : 0); }
+extern "C" void pbrk_mc_set_bin_cache_budget(size_t bytes) { std::lock_guard<std::mutex> hold(g_bin_lock); g_bin_budget = bytes; }
+extern "C" void pbrk_mc_bin_cache_clear(void) {
+    std::lock_guard<std::mutex> hold(g_bin_lock);
+    for (BinEntry& e : g_bin_entries) bin_entry_free(e);
+    g_bin_entries.clear();
+}
+extern "C" void pbrk_mc_bin_cache_stats(unsigned long long out[5]) {
+    if (!out) return;
+    std::lock_guard<std::mutex> hold(g_bin_lock);
+    for (int i = 0; i < 4; ++i) out[i] = g_bin_count[i];
+    out[4] = 0;
+    for (const BinEntry& e : g_bin_entries) out[4] += e.bytes;
+}
+extern "C" int pbrk_mc_table_unregister(const void* table4) {
+    if (!table4) return PBRK_E_ARG;
+    std::lock_guard<std::mutex> hold(g_bin_lock);
+    for (size_t i = 0; i < g_bin_tables.size(); ++i)
+        if (g_bin_tables[i].ptr == table4) {
+            g_bin_tables.erase(g_bin_tables.begin() + (long)i);
+            // the entries recorded with this registration can never be asked for again
+            for (size_t k = g_bin_entries.size(); k-- > 0;)
+                if (g_bin_entries[k].tab == table4) { bin_entry_free(g_bin_entries[k]); g_bin_entries.erase(g_bin_entries.begin() + (long)k); }
+            return PBRK_OK;
+        }
+    return PBRK_E_ARG;
+}
+extern "C" int pbrk_mc_table_register(const void* table4, int n_entries) {
+    if (!table4 || n_entries < 1) return PBRK_E_ARG;
+    (void)pbrk_mc_table_unregister(table4);                         // registered again: a new generation
+    std::lock_guard<std::mutex> hold(g_bin_lock);
+    g_bin_tables.push_back({table4, n_entries, ++g_bin_gen});
+    return PBRK_OK;
+}
+extern "C" int pbrk_mc_tile_of_block(int block, int size, int tile, int face0, int nfaces, int y0, int y1, int* out4) {
+    if (!out4 || size < 1 || (tile != 8 && tile != 16 && tile != 32) || face0 < 0 || nfaces < 1 || face0 + nfaces > 6 || y0 < 0 || y0 >= y1 || y1 > size) return PBRK_E_ARG;
+    const int tiles_x = (size + tile - 1) / tile, tiles_y = (y1 - y0 + tile - 1) / tile;
+    if (block < 0 || block >= tiles_x * tiles_y * nfaces) return PBRK_E_ARG;
+    int pole_row[2];
+    mc_pole_rows(size, y0, tile, tiles_y, pole_row);
+    mc_tile_of_block((unsigned)block, face0, tiles_x, tiles_x * tiles_y, pole_row, out4[0], out4[1], out4[2]);
+    out4[3] = (int)mc_bin_tile_index(out4[0], y0 / tile, out4[2], out4[1], tiles_x, tiles_x);
+    return PBRK_OK;
+}
+extern "C" int pbrk_mc_bin_window_eligible(int size, int tile, int y0, int y1) { return mc_bin_window_ok(size, tile, y0, y1) ? 1 : 0; }
+
+// The cache's part in one launch; g_bin_lock is held from here until the launch (and, for a recording one, its event) is enqueued.
+// eligible: a participating kernel shape and a row window whose tiles are those of the whole-level dispatch; whole: all six faces, all rows.
+// Sets q.bins (replay) or q.bins_out (record; returns the entry's index for bin_recorded) or neither (compute as ever).
+static int bin_plan(RegArgs& q, int flavour, bool eligible, bool whole, int tile, hipStream_t st) {
+    q.bins = nullptr; q.bins_out = nullptr;
+    int mode = g_bin_mode;
+    if (mode < 0) { static int env = -2; if (env == -2) { const char* e = getenv("PBR_MC_BIN_CACHE"); env = e ? (atoi(e) ? 1 : 0) : -1; } mode = env; }
+    if (!(mode < 0 ? q.stats == nullptr : mode != 0)) return -1;
+    const McArgs& a = q.a;
+    int dev = 0;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const BinTable* bt = nullptr;
+    for (const BinTable& t : g_bin_tables) if (t.ptr == (const void*)a.tab && a.n_tab <= t.n) bt = &t;
+    if (!eligible || !bt || hipGetDevice(&dev) != hipSuccess || hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        ++g_bin_count[2];
+        return -1;
+    }
+    size_t held = 0;
+    for (BinEntry& e : g_bin_entries) {
+        if (e.dev != dev) continue;
+        held += e.bytes;
+        if (e.flavour == flavour && e.n_src == a.n_src && e.size == a.size && e.n_tab == a.n_tab && e.tab == bt->ptr && e.gen == bt->gen) {
+            if (!e.done) {
+                if (hipEventQuery(e.ready) == hipSuccess) e.done = true;
+                else { (void)hipGetLastError(); if (hipStreamWaitEvent(st, e.ready, 0) != hipSuccess) { (void)hipGetLastError(); ++g_bin_count[2]; return -1; } }
+            }
+            q.bins = e.buf;
+            ++g_bin_count[1];
+            return -1;
+        }
+    }
+    if (!whole) { ++g_bin_count[2]; return -1; }                  // entries are recorded by whole-level launches only
+    const size_t tiles_e = (size_t)((a.size + tile - 1) / tile);
+    BinEntry e = {dev, flavour, a.n_src, a.size, a.n_tab, bt->ptr, bt->gen, nullptr, 6 * tiles_e * tiles_e * mc_bin_tile_words(q.NR, q.NW) * 4, nullptr, false};
+    if (held + e.bytes > g_bin_budget) { ++g_bin_count[3]; ++g_bin_count[2]; return -1; }
+    if (hipMalloc(&e.buf, e.bytes) != hipSuccess) { (void)hipGetLastError(); ++g_bin_count[3]; ++g_bin_count[2]; return -1; }
+    if (hipEventCreateWithFlags(&e.ready, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(e.buf); ++g_bin_count[2]; return -1; }
+    g_bin_entries.push_back(e);
+    q.bins_out = e.buf;
+    ++g_bin_count[0];
+    return (int)g_bin_entries.size() - 1;
+}
+// behind the recording launch: what a replay on another stream waits for.  Without the event the entry cannot be trusted: it goes.
+static void bin_recorded(int entry, hipStream_t st) {
+    if (entry < 0) return;
+    if (hipEventRecord(g_bin_entries[(size_t)entry].ready, st) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(st);
+        bin_entry_free(g_bin_entries[(size_t)entry]);
+        g_bin_entries.erase(g_bin_entries.begin() + entry);
+    }
 }
 
 bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
@@ -1528,7 +1730,7 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
     q.a.tiles_x = (a.size + tile - 1) / tile;
     const int tiles_y = (a.rows + tile - 1) / tile;
     q.a.tiles_per_face = q.a.tiles_x * tiles_y;                            // tiles start at the dispatch's first row, whatever it is
-    pole_rows(a.size, a.y0, tile, tiles_y, q.pole_row);
+    mc_pole_rows(a.size, a.y0, tile, tiles_y, q.pole_row);
     const unsigned grid = (unsigned)(q.a.tiles_per_face * nfaces);
     // Lean prologue: the maxima of the absorbed-word test come from k_mc_prep, once per launch, instead of from every tile.  Without
     // a scratch slot (see prep_acquire) the launch takes the prologue that builds them itself: the same bytes.
@@ -1536,6 +1738,12 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
     q.tabmax = nullptr;
     q.cut = 0;
     g_last_cut = nullptr; g_last_cut_nw = q.NW; g_last_cut_s = nslices;
+    // header 2m: the launches that take a lean run loop (launch_runs) may record or replay their binning
+    const bool bin_shape = RS != 18 && g_mc_runs && q.NW <= 64 * nslices;
+    const bool bin_window = mc_bin_window_ok(a.size, tile, a.y0, a.y0 + a.rows);
+    const bool bin_whole = a.face0 == 0 && nfaces == 6 && a.y0 == 0 && a.rows == a.size;
+    const int bin_flavour = (RS << 8) | tile;
+    std::lock_guard<std::mutex> hold_bins(g_bin_lock);
     if (lean && q.absorb) {
         std::lock_guard<std::mutex> hold(g_prep_lock);
         int slot = -1;
@@ -1552,13 +1760,18 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
                 q.cut = 3;
                 g_last_cut = scratch + q.NW + q.NR;
             }
+            const int rec = bin_plan(q, bin_flavour, bin_shape && bin_window, bin_whole, tile, st);
             launch_shape<true>(RS, tile, q, grid, lds, st);
+            bin_recorded(rec, st);
             if (hipEventRecord(g_prep[dev].ev[slot], st) == hipSuccess) g_prep[dev].used[slot] = true;
             return true;
         }
     }
+    // the 66^2 shapes without a k_mc_prep slot bin as ever; the 34^2 shape never takes one
+    const int rec = bin_plan(q, bin_flavour, lean && RS == 34 && bin_shape && bin_window, bin_whole, tile, st);
     if (lean) launch_shape<true>(RS, tile, q, grid, lds, st);
     else launch_shape<false>(RS, tile, q, grid, lds, st);
+    bin_recorded(rec, st);
     return true;
 }
 
@@ -1609,11 +1822,15 @@ bool launch_mc_resident(McArgs a, int nfaces, hipStream_t st) {
     q.a.rows = ((ty1 + 1) * tile < a.size ? (ty1 + 1) * tile : a.size) - q.a.y0;
     q.a.tiles_x = (a.size + tile - 1) / tile;
     q.a.tiles_per_face = q.a.tiles_x * tiles_y;
-    pole_rows(a.size, q.a.y0, tile, tiles_y, q.pole_row);
+    mc_pole_rows(a.size, q.a.y0, tile, tiles_y, q.pole_row);
     const unsigned grid = (unsigned)(q.a.tiles_per_face * nfaces);
     // FOLD as in launch_runs: from n_src alone
     const bool fold = g_mc_fold && (a.n_src & (a.n_src - 1)) == 0;
+    // header 2m: the tiles are anchored at row 0 of the face, so every dispatch may replay; a whole-level one records
+    std::lock_guard<std::mutex> hold_bins(g_bin_lock);
+    const int rec = bin_plan(q, (1 << 16) | tile, true, a.face0 == 0 && nfaces == 6 && a.y0 == 0 && a.rows == a.size, tile, st);
     if (tile == 16) launch_resident_tile<16>(g, fold, grid, lds, st);
     else launch_resident_tile<8>(g, fold, grid, lds, st);
+    bin_recorded(rec, st);
     return true;
 }

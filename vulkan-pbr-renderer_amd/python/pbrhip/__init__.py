@@ -327,6 +327,11 @@ PROTOTYPES = {
     "pbrk_mc_mono_slices": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "pbrk_mc_set_resident": (None, [C.c_int]), "pbrk_mc_resident_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
     "pbrk_mc_region_phase_stats": (C.c_int, [C.POINTER(C.c_uint64)]),
+    "pbrk_mc_table_register": (C.c_int, [VP, C.c_int]), "pbrk_mc_table_unregister": (C.c_int, [VP]),
+    "pbrk_mc_set_bin_cache": (None, [C.c_int]), "pbrk_mc_set_bin_cache_budget": (None, [C.c_size_t]), "pbrk_mc_bin_cache_clear": (None, []),
+    "pbrk_mc_bin_cache_stats": (None, [C.POINTER(C.c_uint64)]),
+    "pbrk_mc_tile_of_block": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "pbrk_mc_bin_window_eligible": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "pbrk_lut_cells_build": (C.c_int, [VP, C.c_int, VP, VP]),
     "pbrk_equirect_to_cube": (C.c_int, [VP, C.c_int, C.c_int, VP, C.c_int, VP]),
     "pbrk_raster_scratch_bytes": (C.c_size_t, [U32, C.c_int, C.c_int]),
