@@ -226,6 +226,23 @@ void pbrk_mc_bin_cache_stats(unsigned long long out[5]);
 int pbrk_mc_tile_of_block(int block, int size, int tile, int face0, int nfaces, int y0, int y1, int* out4);
 /* 1 when a region-kernel dispatch of rows [y0, y1) may record or replay: y0 a multiple of the tile, y1 one or the face's end.  Needs no GPU. */
 int pbrk_mc_bin_window_eligible(int size, int tile, int y0, int y1);
+/* ---- exact flags in the bin cache (k_mc_region.hip, 2n).  The flags a recording launch stores are a bound: a superset of what the tile's
+ * texels reach.  Behind the recording launch, ahead of the event replays wait for, k_mc_refine_bins rewrites the entry in place: a flag
+ * stays exactly where some lane of the tile takes the sample, a proof bit is set exactly where all lanes take it in one region, both
+ * decided by the sample bodies' own arithmetic.  The recording launch itself ran on the bound's flags; replays read the refined words
+ * in the same layout.  Same samples accumulated, same order, same bytes.  k_mc_region entries only: in k_mc_resident the order of a
+ * texel's sum depends on what its tile proves, so its bytes would move; its entries stay as recorded.
+ * -1 (default): the environment (PBR_MC_EXACT_BINS=0|1), else on exactly when the device counters are off (the rule of pbrk_mc_set_net
+ * and pbrk_mc_set_bin_cache) and only for the kernel shapes whose replaying kernel measured as a gain (today the 34^2 shape: levels of
+ * 17 .. 32 texels per edge; profiles/exact_bins.md); 0: off; 1: on for every k_mc_region entry, with or without the counters. */
+void pbrk_mc_set_exact_bins(int mode);
+/* 1 when the last recording launch was followed by the refinement, else 0 */
+int pbrk_mc_last_exact_bins(void);
+/* summed over the refined entries since the last reset: {(region, sample) flags before, after; proved samples before, after; stagings the
+ * tiles' words ask for (regions with a flag, head and tail words counted apart where a tile runs two phases) before, after; hits on a
+ * bit the bound had not set; (lane, sample) pairs that found no region}.  The last two must stay 0: the bound is rigorous.  Waits for the
+ * device.  Returns 0, PBRK_E_ARG or PBRK_E_LAUNCH. */
+int pbrk_mc_exact_bins_stats(unsigned long long* out8, int reset);
 
 /* ---- K5: deferred shade pass (shaders/lighting_pass.glsl:432-716, in-scope sub-blocks). */
 typedef struct PbrkShadeArgs {

@@ -18,6 +18,8 @@ L = pbrhip.init()
 env_tex = pbrhip.make_texture(pbrhip.Format_RGBA32F, W, W, pbrhip.TextureFlag_Cubemap | pbrhip.TextureFlag_HasMipmaps, env)
 maps = pbrhip.PBR_IBLMaps(); L.PBR_MakeIBLMaps(C.byref(maps), irr_size, 256, spec_size)
 pipes = L.PBR_MakeIBLPipelines(); arena = L.GPU_MakeDescriptorArena(); graph = L.GPU_MakeGraph()
+# one whole-level job first: single faces never record a bin-cache entry (k_mc_region.hip 2m, 2n), behind it they replay as in real use
+L.PBR_GenPrefilteredEnvMap(env_tex, maps.tex_specular_env_map, 1); L.GPU_WaitUntilIdle()
 for mip in [int(a) for a in sys.argv[1:]] or [1, 2, 3, 4, 5]:
     size = spec_size >> mip
     out = []

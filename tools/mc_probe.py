@@ -5,7 +5,7 @@ PBR_MC_TILE32 = -1 | 0 | 1 goes to pbrk_mc_set_tile32 (the region kernel's 32 x 
 PBR_MC_NET = -1 | 0 | 1 goes to pbrk_mc_set_net (the region kernel's completeness net: by rule, off where it can be, always on);
 PBR_MC_RESIDENT=0 keeps levels of at most 16^2 texels off k_mc_resident (the library reads it).  The table is registered
 (pbrk_mc_table_register), so the bin cache serves it by its default rule: the untimed first launch records, the timed ones replay;
-PBR_MC_BIN_CACHE=0 keeps it off (the library reads it).
+PBR_MC_BIN_CACHE=0 keeps it off, PBR_MC_EXACT_BINS=0 keeps the recorded flags the bound's (the library reads both).
    python3 tools/mc_probe.py n_src out_size [roughness] [rows] [face0 face1]"""
 import ctypes as C
 import os
@@ -90,6 +90,12 @@ def main():
             print(f"   region kernel: {c['healed']} of {c['slices']} wave-slices recomputed with direct loads", flush=True)
     bc = mc.bin_cache_stats(L)
     print(f"   bin cache: {bc['recorded']} recording, {bc['replayed']} replaying, {bc['computed']} computing launches, {bc['bytes']} bytes held", flush=True)
+    if hasattr(mc, "exact_bins_stats"):
+        xb = mc.exact_bins_stats(L)
+        if xb["flags_before"]:
+            print(f"   exact bins (summed over the tiles of the recorded entry, {n_tab} samples each): flags {xb['flags_before']} -> {xb['flags_after']}, "
+                  f"proved {xb['proved_before']} -> {xb['proved_after']}, stagings asked for {xb['any_before']} -> {xb['any_after']}, "
+                  f"unset hits {xb['unset_hits']}, lost lanes {xb['lost_lanes']}", flush=True)
     L.GPU_WaitUntilIdle(); L.pbrk_mc_table_unregister(dtab.data_ptr()); L.GPU_Deinit()
 
 

@@ -194,12 +194,38 @@
 //      pbrk_mc_set_bin_cache(-1), the default, is on exactly when the device counters are off -- the rule of pbrk_mc_set_net -- so the suite
 //      keeps its paths and tests/test_gpu_mc_bin_cache.py asks for both states by name.  At most 64 VGPRs, no spill, no scratch (the net-carrying
 //      instantiations form the texel index again ahead of the reduction to stay there).  Measured: profiles/bin_cache.md.
+//   2n. (exact flags in the bin cache; k_mc_refine_bins) the flags of 2m are still region_bin's: one ball around the tile-centre direction,
+//      inflated, six face tests with sqrt(2) delta of slack -- a superset of what any texel reaches.  A sample flagged for a region no lane
+//      takes it in still runs there (frame transform, in-face test, exec join, on SUB an early exit); a sample every lane takes in one
+//      region but the bound cannot prove runs the tested body and cuts a proved run in two; a region with one spurious flag is staged.
+//      Since 2m binning is paid once per (kernel shape, level shape, table), so it may cost far more than a bound: behind the recording
+//      launch, on its stream and ahead of the event replays wait for, k_mc_refine_bins rewrites the entry's words in place.  One workgroup
+//      per recorded tile holds the frames every replaying thread of that tile will hold (texel_of_thread, the clamps of the whole-level
+//      dispatch), and for each sample the bound left unproved or flagged for more than one region every lane runs lane_sample's count-only
+//      form -- the tested body's own to_face, on_face, reciprocal, tap coordinates and cell comparisons under the view REGION_VIEW_FRAME
+//      sets up for visit, with the FOLD the replays will take -- against the regions the bound flagged for it (and, in a wave where a lane
+//      finds none of them, against all the others).  The ballots become words
+//      (mc_refine_core.h): a flag stays exactly where some lane of the slice's waves takes the sample, a proof bit is set exactly where
+//      one region is hit and every lane is in it (SOLE for free; on SUB the cell test then holds for all lanes, which is what
+//      certain_sample assumes).  A bit the bound had not set is never set; such hits and lanes that find no region are counted
+//      (pbrk_mc_exact_bins_stats: both must stay 0 -- the bound is rigorous).  Cut words are refined like the rest: the cache holds every
+//      sample.  The replaying kernels read the same words in the same layout: no instruction of k_mc_region changes, RegArgs, the cache's
+//      layout, key and budget stay.  Bytes: a pair is accumulated in the pass of the region the lane's own test puts it in, in index
+//      order, whichever body it takes; a flag no lane answers to added nothing; a tested sample all 64 lanes take runs the same twelve
+//      FMAs on the same taps as a proved one; an absorbed-word test that no longer happens decided nothing that was accumulated.  The
+//      recording launch itself ran on the bound's flags.  k_mc_resident's entries are NOT refined: there the order of a texel's sum depends
+//      on what its tile proves, so its bytes would move.  pbrk_mc_set_exact_bins(-1), the default, is on exactly when the device counters
+//      are off (the rule of pbrk_mc_set_net and pbrk_mc_set_bin_cache; PBR_MC_EXACT_BINS=0|1) and, per shape by measurement (exact_shape),
+//      today for the 34^2 shape alone: C4 mip 3 10.77 -> 10.13 ms.  The quarter-face level gained 0.45 ms of 7.15 and the 66^2 whole-face
+//      level 0.07 of 21.3, both inside five sigma of their launches: they keep the bound's flags unless pbrk_mc_set_exact_bins(1) asks.
+//      pbrk_mc_last_exact_bins tells what the last recording did.  48 VGPRs, no scratch; no texel is staged.  Measured: profiles/exact_bins.md.
 // Each (texel, sample) pair is accumulated exactly once, in an order (66^2 shapes: head phase then tail phase; in each, own face's
 // regions, then the other regions in index order; else regions in index order; sample index inside a region) that depends on the
 // level's shape and the texel's face only, not on the tile: a row-sharded dispatch equals a full one bit for bit.
 #include "pbr_device.h"
 #include "pbr_kernels.h"
 #include "k_mc_internal.h"
+#include "mc_refine_core.h"
 
 #include <stdlib.h>
 #include <mutex>
@@ -308,6 +334,24 @@ __device__ __forceinline__ void to_face(const v4f e, const RegionView& V, float&
     tc = fmaf(e.x, V.Pb.y, fmaf(e.y, V.Pt.y, e.z * V.Pr.y));
     ma = fmaf(e.x, V.Pb.z, fmaf(e.y, V.Pt.z, e.z * V.Pr.z));
 }
+
+// The frame's part of a RegionView for face f and the region's cells [ox, ox + rcx) x [oy, oy + rcy): the signed permutation of the
+// frame, FOLD (header, 2j) six exact multiplies per staging for one per sample.  k_mc_region's visit and k_mc_refine_bins (2n) both
+// set their views up with these statements, so the lanes of the second decide with the numbers the first will hold.  A macro, not a
+// function: behind a call boundary the compiler orders two moves of the folded net-carrying instantiations differently, and every
+// k_mc_region instantiation is to keep its opcode sequence.
+#define REGION_VIEW_FRAME(V, FOLD, f, B, T, R, half_n, off, ox, oy, rcx, rcy)                                                   \
+    do {                                                                                                                        \
+        face_coords(f, B.x, B.y, B.z, V.Pb.x, V.Pb.y, V.Pb.z);                                                                  \
+        face_coords(f, T.x, T.y, T.z, V.Pt.x, V.Pt.y, V.Pt.z);                                                                  \
+        face_coords(f, R.x, R.y, R.z, V.Pr.x, V.Pr.y, V.Pr.z);                                                                  \
+        V.half_n = half_n; V.off = off;                                                                                         \
+        if (FOLD) {                                                                                                             \
+            V.Pb.x *= half_n; V.Pt.x *= half_n; V.Pr.x *= half_n;                                                               \
+            V.Pb.y *= half_n; V.Pt.y *= half_n; V.Pr.y *= half_n;                                                               \
+        }                                                                                                                       \
+        V.ulo = (float)ox; V.uhi = (float)(ox + rcx); V.vlo = (float)oy; V.vhi = (float)(oy + rcy);                             \
+    } while (0)
 
 // In-face test.  CLS = major axis of the region's face (0: x, 1: y, 2: z): the hardware's tie rule (z >= y >= x) in two comparisons.
 template <int CLS>
@@ -1014,15 +1058,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
             asm volatile("" : "+v"(Tq.x), "+v"(Tq.y), "+v"(Tq.z));
             Bv = cross3(Tq, R);
         }
-        face_coords(f, Bv.x, Bv.y, Bv.z, V.Pb.x, V.Pb.y, V.Pb.z);
-        face_coords(f, T.x, T.y, T.z, V.Pt.x, V.Pt.y, V.Pt.z);
-        face_coords(f, R.x, R.y, R.z, V.Pr.x, V.Pr.y, V.Pr.z);
-        V.half_n = half_n; V.off = off;
-        if (FOLD) {                                                // header 2j: six exact multiplies per staging for one per sample
-            V.Pb.x *= half_n; V.Pt.x *= half_n; V.Pr.x *= half_n;
-            V.Pb.y *= half_n; V.Pt.y *= half_n; V.Pr.y *= half_n;
-        }
-        V.ulo = (float)ox; V.uhi = (float)(ox + rcx); V.vlo = (float)oy; V.vhi = (float)(oy + rcy);
+        REGION_VIEW_FRAME(V, FOLD, f, Bv, T, R, half_n, off, ox, oy, rcx, rcy);
         const unsigned* mw = masks + r * NW;
         unsigned* const sc = (ABS && q.stats) ? skc : nullptr;
         // the words of this pass: the whole slice, or (TWO) its head word s / its tail words s + REG_S, ..
@@ -1094,6 +1130,136 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
         atomicAdd(&q.stats[12], (st3 - st2b) - st_stage); atomicAdd(&q.stats[13], STAMP() - st3);
     }
 #endif
+}
+
+// ---- header 2n: exact flags in the bin cache ----
+struct RefineArgs {
+    McArgs a;                   // size, n_src, tab, n_tab, tiles_x of the whole-level dispatch that recorded: y0 = 0, rows = size
+    int G, RC, NR, NW;          // as RegArgs
+    unsigned* bins;             // the recorded words of every tile (mc_bin_tile_index, mc_bin_tile_words), rewritten in place
+    unsigned long long* out;    // [8] += (region, sample) flags before, after; proved samples before, after; stagings a tile's words ask for
+                                // ((region, phase) pairs with a flag) before, after; hits on a bit the bound had not set; (lane, sample)
+                                // pairs that found no region.  The last two must stay 0
+};
+
+// One workgroup per recorded tile, a thread per texel and slice as in k_mc_region<RS, SUB, TILE>: the frames are those every replaying
+// thread of the tile will hold.  For every sample of its slice that the bound left unproved or flagged for more than one region, a wave
+// runs the count-only form of lane_sample -- the tested body's own frame transform, in-face test, reciprocal, tap coordinates and cell
+// comparisons, FOLD as the entry's flavour has it -- against the regions flagged for the sample, and the words of mc_refine_core.h are
+// built from the ballots.  No texel is staged or read.  At most 64 VGPRs, no scratch.
+template <int RS, bool SUB, int TILE, bool FOLD>
+__global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_mc_refine_bins(const RefineArgs g) {
+    constexpr int REG_TX = TILE * TILE, REG_S = 1024 / REG_TX;
+    constexpr bool TWO = RS == 66 && (SUB ? MC_HEAD_FIRST_SUB != 0 : MC_HEAD_FIRST_G1 != 0);
+    extern __shared__ __attribute__((aligned(16))) unsigned smem_f[];
+    const McArgs& p = g.a;
+    const int NR = g.NR, NW = g.NW, G = g.G, RC = g.RC, tid = threadIdx.x;
+    const int nflag = NR * NW;
+    unsigned* old = smem_f;                                        // [NR][NW] the bound's masks, then [NW] its proof words
+    unsigned* need = old + nflag + NW;                             // [NW] mc_refine_need; at the end the new proof words
+    unsigned* hit = need + NW;                                     // [NR][NW]; at the end the new masks
+    unsigned* part = hit + nflag;                                  // [NR][NW]
+    unsigned* tot = part + nflag;                                  // [8] this tile's share of g.out
+    const int te = p.tiles_x, face = (int)blockIdx.x / (te * te), tf = (int)blockIdx.x % (te * te), ty = tf / te, tx = tf % te;
+    unsigned* words = g.bins + (size_t)mc_bin_tile_index(face, 0, ty, tx, te, te) * mc_bin_tile_words(NR, NW);
+    for (int k = tid; k < nflag + NW; k += 1024) old[k] = words[k];
+    for (int k = tid; k < 2 * nflag + 8; k += 1024) hit[k] = 0u;
+    __syncthreads();
+    for (int w = tid; w < NW; w += 1024) {
+        unsigned nd = mc_refine_need(old + w, NW, NR, old[nflag + w]);
+        if (w == NW - 1 && (p.n_tab & 31)) nd &= (1u << (p.n_tab & 31)) - 1u;      // no sample behind the table's end (the bound sets none)
+        need[w] = nd;
+    }
+    __syncthreads();
+
+    const int s = __builtin_amdgcn_readfirstlane(tid / REG_TX), t = tid % REG_TX;
+    int x, y;
+    texel_of_thread<TILE>(p, tx, ty, t, x, y);
+    const int xc = min(x, p.size - 1), yc = min(y, p.y0 + p.rows - 1);
+    const f3 R = face_texel_dir(face, xc, yc, p.size);
+    const f3 T = tangent_of(R);
+    const f3 B = cross3(T, R);
+    const int n = p.n_src;
+    const float half_n = 0.5f * (float)n, off = 0.5f * (float)n + 0.5f;
+    ctab_t tab = (ctab_t)(unsigned long long)p.tab;
+
+    unsigned cnt = 0u;                                             // per lane: the (region, sample) pairs that took it -- one per sample looked at
+    float ar = 0.0f, ag = 0.0f, ab = 0.0f;                         // the count-only body accumulates nothing
+    unsigned want = 0u;                                            // wave-uniform: the samples this slice looks at
+    for (int w = s; w < NW; w += REG_S) want += (unsigned)__builtin_popcount((unsigned)__builtin_amdgcn_readfirstlane((int)need[w]));
+    // Sweep 0: each sample against the regions the bound flagged for it.  The bound is rigorous, so every lane finds its region there;
+    // a wave with a lane that did not (counted: tot[7]) goes on to sweep 1, the same samples against the regions the bound did NOT flag,
+    // where every hit is a bit the bound had not set (counted by mc_refine_word, never written).
+    for (int sweep = 0; sweep < 2; ++sweep) {
+        for (int r = 0; r < NR; ++r) {
+            const int f = r / (G * G), gy = (r / G) % G, gx = r % G;
+            const int ox = gx * RC, oy = gy * RC;
+            const int rcx = min(RC, n + 1 - ox), rcy = min(RC, n + 1 - oy);
+            RegionView V;
+            V.lds_base = 0u;
+            REGION_VIEW_FRAME(V, FOLD, f, B, T, R, half_n, off, ox, oy, rcx, rcy);
+            auto pass = [&](auto cls) {
+                constexpr int CLS = decltype(cls)::value;
+                for (int w = s; w < NW; w += REG_S) {
+                    const unsigned o = (unsigned)__builtin_amdgcn_readfirstlane((int)old[r * NW + w]);
+                    unsigned m = (unsigned)__builtin_amdgcn_readfirstlane((int)need[w]) & (sweep ? ~o : o);
+                    if (m == 0u) continue;
+                    ctab_t tw = tab + (w << 5);
+                    unsigned h = 0u, pt = 0u;
+                    while (m) {
+                        const int i = __builtin_ctz(m);
+                        m &= m - 1u;
+                        const unsigned c0 = cnt;
+                        lane_sample<RS, SUB, CLS, false, FOLD, false, true>(tw[i], V, ar, ag, ab, cnt);
+                        mc_refine_ballot(__builtin_amdgcn_ballot_w64(cnt != c0), i, h, pt);
+                    }
+                    if ((tid & 63) == 0) {
+                        if (h) atomicOr(&hit[r * NW + w], h);
+                        if (pt) atomicOr(&part[r * NW + w], pt);
+                    }
+                }
+            };
+            switch (f >> 1) {
+            case 0: pass(std::integral_constant<int, 0>()); break;
+            case 1: pass(std::integral_constant<int, 1>()); break;
+            default: pass(std::integral_constant<int, 2>()); break;
+            }
+        }
+        if (sweep == 0) {
+            const unsigned long long lost = __builtin_amdgcn_ballot_w64(cnt != want);
+            if (lost == 0ull) break;
+            if ((tid & 63) == 0) atomicAdd(&tot[7], (unsigned)__builtin_popcountll(lost));
+        }
+    }
+    __syncthreads();
+
+    for (int w = tid; w < NW; w += 1024) {
+        unsigned long long unset = 0ull;
+        need[w] = mc_refine_word(old + w, NW, NR, old[nflag + w], need[w], hit + w, part + w, NW, hit + w, NW, &unset);
+        if (unset) atomicAdd(&tot[6], (unsigned)unset);
+    }
+    __syncthreads();
+    {
+        unsigned fb = 0u, fa = 0u, pb = 0u, pa = 0u;
+        for (int k = tid; k < nflag; k += 1024) { fb += __popc(old[k]); fa += __popc(hit[k]); words[k] = hit[k]; }
+        for (int k = tid; k < NW; k += 1024) { pb += __popc(old[nflag + k]); pa += __popc(need[k]); words[nflag + k] = need[k]; }
+        if (fb) atomicAdd(&tot[0], fb);
+        if (fa) atomicAdd(&tot[1], fa);
+        if (pb) atomicAdd(&tot[2], pb);
+        if (pa) atomicAdd(&tot[3], pa);
+        if (tid < NR) {
+            // the stagings these words ask for: a region with a flag; TWO: once for the head words (below REG_S), once for the tail
+            unsigned bh = 0u, bt = 0u, ah = 0u, at = 0u;
+            for (int w = 0; w < NW; ++w) {
+                const unsigned o = old[tid * NW + w], a2 = hit[tid * NW + w];
+                if (TWO && w >= REG_S) { bt |= o; at |= a2; } else { bh |= o; ah |= a2; }
+            }
+            atomicAdd(&tot[4], (bh != 0u) + (bt != 0u));
+            atomicAdd(&tot[5], (ah != 0u) + (at != 0u));
+        }
+    }
+    __syncthreads();
+    if (tid < 8 && tot[tid]) atomicAdd(&g.out[tid], (unsigned long long)tot[tid]);
 }
 
 // ---- levels resident in LDS as a whole (header, 2k) ----
@@ -1697,6 +1863,75 @@ static void bin_recorded(int entry, hipStream_t st) {
     }
 }
 
+// ---- header 2n: the recorded flags made exact, once, behind the recording launch ----
+static int g_exact_mode = -1;
+static int g_last_exact = 0;                                    // whether the last recording launch was followed by k_mc_refine_bins
+static unsigned long long* g_exact_stats[PREP_MAX_DEVICES];     // RefineArgs::out, one per device
+extern "C" void pbrk_mc_set_exact_bins(int mode) { g_exact_mode = mode < 0 ? -1 : (mode ? 1 : 0); }
+extern "C" int pbrk_mc_last_exact_bins(void) { return g_last_exact; }
+extern "C" int pbrk_mc_exact_bins_stats(unsigned long long* out8, int reset) {
+    if (!out8) return PBRK_E_ARG;
+    std::lock_guard<std::mutex> hold(g_bin_lock);
+    for (int i = 0; i < 8; ++i) out8[i] = 0;
+    for (int d = 0; d < PREP_MAX_DEVICES; ++d) {
+        if (!g_exact_stats[d]) continue;
+        unsigned long long v[8];
+        if (hipMemcpy(v, g_exact_stats[d], sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return PBRK_E_LAUNCH;
+        for (int i = 0; i < 8; ++i) out8[i] += v[i];
+        if (reset && hipMemset(g_exact_stats[d], 0, sizeof v) != hipSuccess) return PBRK_E_LAUNCH;
+    }
+    return PBRK_OK;
+}
+
+template <int RS, bool SUB, int TILE>
+static void launch_refine_t(const RefineArgs& g, bool fold, unsigned grid, size_t lds, hipStream_t st) {
+    if (fold) hipLaunchKernelGGL((k_mc_refine_bins<RS, SUB, TILE, true>), dim3(grid), dim3(1024), lds, st, g);
+    else hipLaunchKernelGGL((k_mc_refine_bins<RS, SUB, TILE, false>), dim3(grid), dim3(1024), lds, st, g);
+}
+
+// Which kernel shapes have their recorded flags refined under the default rule: decided per shape by measurement (profiles/exact_bins.md;
+// a shape is in when its replaying kernel, levels one after another, falls by more than five times the larger sigma of its two rows).
+//   <34, false, 16> (C4 mip 3): 10.77 -> 10.13 ms, sigma 0.09: in.
+//   <66, true, 32>  (C4 mip 1):  7.15 ->  6.70 ms, sigma 0.17: a fall of 2.6 sigma, out.
+//   <66, false, 16> (C4 mip 2): 21.32 -> 21.25 ms, sigma 0.29: out.
+//   <66, true, 16>: on no level of the measured job; out.
+// pbrk_mc_set_exact_bins(1) refines every shape (tests, A-B runs).
+static bool exact_shape(int RS, int G, int tile) {
+    (void)G; (void)tile;
+    return RS == 34;
+}
+
+// Behind the recording launch of entry `entry` (bin_plan's return; < 0: this launch records nothing) on its stream, ahead of the event
+// replays wait for.  g_bin_lock is held.  q: the recording launch's arguments -- a whole-level dispatch.
+static void bin_refine(int entry, const RegArgs& q, int RS, int tile, hipStream_t st) {
+    if (entry < 0) return;
+    g_last_exact = 0;
+    int mode = g_exact_mode;
+    if (mode < 0) { static int env = -2; if (env == -2) { const char* e = getenv("PBR_MC_EXACT_BINS"); env = e ? (atoi(e) ? 1 : 0) : -1; } mode = env; }
+    if (!(mode < 0 ? q.stats == nullptr && exact_shape(RS, q.G, tile) : mode != 0)) return;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PREP_MAX_DEVICES) { (void)hipGetLastError(); return; }
+    if (!g_exact_stats[dev]) {
+        if (hipMalloc(&g_exact_stats[dev], 64) != hipSuccess) { (void)hipGetLastError(); g_exact_stats[dev] = nullptr; return; }
+        (void)hipMemset(g_exact_stats[dev], 0, 64);
+    }
+    RefineArgs g;
+    g.a = q.a;
+    g.G = q.G; g.RC = q.RC; g.NR = q.NR; g.NW = q.NW;
+    g.bins = g_bin_entries[(size_t)entry].buf;
+    g.out = g_exact_stats[dev];
+    const size_t lds = ((size_t)3 * q.NR * q.NW + 2 * (size_t)q.NW + 8) * 4;
+    if (lds > 64 * 1024) return;
+    const unsigned grid = (unsigned)(6 * q.a.tiles_x * q.a.tiles_x);
+    const int n = q.a.n_src;
+    const bool fold = g_mc_fold && (n & (n - 1)) == 0;              // launch_runs' rule: the flavour the replays will take
+    if (tile == 32) launch_refine_t<66, true, 32>(g, fold, grid, lds, st);
+    else if (RS == 34) launch_refine_t<34, false, 16>(g, fold, grid, lds, st);
+    else if (q.G == 1) launch_refine_t<66, false, 16>(g, fold, grid, lds, st);
+    else launch_refine_t<66, true, 16>(g, fold, grid, lds, st);
+    g_last_exact = 1;
+}
+
 bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
     if (g_mc_region_mode < 0) { const char* e = getenv("PBR_MC_REGION"); g_mc_region_mode = e ? atoi(e) : 1; }
     if (!g_mc_region_mode) return false;
@@ -1762,6 +1997,7 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
             }
             const int rec = bin_plan(q, bin_flavour, bin_shape && bin_window, bin_whole, tile, st);
             launch_shape<true>(RS, tile, q, grid, lds, st);
+            bin_refine(rec, q, RS, tile, st);
             bin_recorded(rec, st);
             if (hipEventRecord(g_prep[dev].ev[slot], st) == hipSuccess) g_prep[dev].used[slot] = true;
             return true;
@@ -1771,6 +2007,7 @@ bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
     const int rec = bin_plan(q, bin_flavour, lean && RS == 34 && bin_shape && bin_window, bin_whole, tile, st);
     if (lean) launch_shape<true>(RS, tile, q, grid, lds, st);
     else launch_shape<false>(RS, tile, q, grid, lds, st);
+    bin_refine(rec, q, RS, tile, st);
     bin_recorded(rec, st);
     return true;
 }

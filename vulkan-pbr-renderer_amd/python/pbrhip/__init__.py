@@ -330,6 +330,8 @@ PROTOTYPES = {
     "pbrk_mc_table_register": (C.c_int, [VP, C.c_int]), "pbrk_mc_table_unregister": (C.c_int, [VP]),
     "pbrk_mc_set_bin_cache": (None, [C.c_int]), "pbrk_mc_set_bin_cache_budget": (None, [C.c_size_t]), "pbrk_mc_bin_cache_clear": (None, []),
     "pbrk_mc_bin_cache_stats": (None, [C.POINTER(C.c_uint64)]),
+    "pbrk_mc_set_exact_bins": (None, [C.c_int]), "pbrk_mc_last_exact_bins": (C.c_int, []),
+    "pbrk_mc_exact_bins_stats": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
     "pbrk_mc_tile_of_block": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "pbrk_mc_bin_window_eligible": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "pbrk_lut_cells_build": (C.c_int, [VP, C.c_int, VP, VP]),

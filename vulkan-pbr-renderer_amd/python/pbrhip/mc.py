@@ -1,4 +1,4 @@
-"""Harness of the K4b region kernel (k_mc_region.hip) for the tests and the probes under tools/: its nine switches, its counters
+"""Harness of the K4b region kernel (k_mc_region.hip) for the tests and the probes under tools/: its switches, its counters
 by name, device buffers, bordered levels, prefilter tables, and the two ways it is driven (row windows through pbrk_mc_filter,
 work units through PBR_RecordUnits).  Importing this loads no library and touches no GPU; every function takes the loaded
 library `L` (pbrhip.lib() / pbrhip.init())."""
@@ -12,12 +12,12 @@ import pbrhip
 
 # switch -> the library's default: pbrk_mc_set_<switch>(*default)
 SWITCH_DEFAULTS = {"absorb": (1,), "runs": (1,), "prologue": (1,), "launch_cut": (1,), "tile32": (-1,), "fold": (1,), "net": (-1,),
-                   "kernels": (-1, -1), "bin_cache": (-1,)}
+                   "kernels": (-1, -1), "bin_cache": (-1,), "exact_bins": (-1,)}
 
 
 @contextlib.contextmanager
 def switches(L, **named):
-    """Set the named switches (absorb, runs, prologue, launch_cut, tile32, fold, net, bin_cache, kernels=(lds, region)) for the body and no others.
+    """Set the named switches (absorb, runs, prologue, launch_cut, tile32, fold, net, bin_cache, exact_bins, kernels=(lds, region)) for the body and no others.
     On exit, also on an exception, exactly those go back to the library's DEFAULTS, not to their previous values: the library
     has no getters."""
     unknown = set(named) - set(SWITCH_DEFAULTS)
@@ -67,6 +67,16 @@ def bin_cache_stats(L):
     buf = (C.c_uint64 * 5)()
     L.pbrk_mc_bin_cache_stats(buf)
     return dict(zip(BIN_CACHE_KEYS, (int(v) for v in buf)))
+
+
+EXACT_BINS_KEYS = ("flags_before", "flags_after", "proved_before", "proved_after", "any_before", "any_after", "unset_hits", "lost_lanes")
+
+
+def exact_bins_stats(L, reset=False):
+    """pbrk_mc_exact_bins_stats by name, summed over the entries refined since the last reset; unset_hits and lost_lanes must be 0."""
+    buf = (C.c_uint64 * 8)()
+    assert L.pbrk_mc_exact_bins_stats(buf, int(reset)) == 0
+    return dict(zip(EXACT_BINS_KEYS, (int(v) for v in buf)))
 
 
 def reset_counters(L):
