@@ -243,6 +243,27 @@ int pbrk_mc_last_exact_bins(void);
  * bit the bound had not set; (lane, sample) pairs that found no region}.  The last two must stay 0: the bound is rigorous.  Waits for the
  * device.  Returns 0, PBRK_E_ARG or PBRK_E_LAUNCH. */
 int pbrk_mc_exact_bins_stats(unsigned long long* out8, int reset);
+/* ---- the launch plan (mc_plan.h): everything the host decides about one pbrk_mc_filter dispatch, from the level (n_src, n_tab,
+ * size), the dispatch (face0, nfaces, y0, rows), the process switches as they stand (pbrk_mc_set_*, environment), whether the device
+ * counters are on (PBR_MC_STATS) and whether a k_mc_prep scratch slot is to be had (0: stream capture, no device memory).  Needs no GPU. */
+typedef struct PbrkMcPlan {
+    int family;                     /* 0: declined (the level-in-LDS or the direct kernel runs), 1: k_mc_region, 2: k_mc_resident */
+    int RS, G, RC, NR, NW;          /* staged edge, regions per face edge, cells per region edge, regions, mask words per region */
+    int tile, nslices;              /* TILE x TILE output texels x nslices slices of the sample table per workgroup */
+    int runs, lean, fold, net;      /* the template arguments RUNS, LEAN, FOLD, NET of k_mc_region (fold: also of k_mc_resident) */
+    int absorb;                     /* absorbed words are skipped (2c) */
+    int head_first;                 /* the shape runs its head words first (2g) */
+    int prep, cut;                  /* k_mc_prep / k_mc_cut run ahead of the kernel */
+    int stats;                      /* the counters are on: k_mc_resident's STATS */
+    int bin_cache, bin_eligible;    /* the bin cache is on; this dispatch may replay (and, whole, record) its binning (2m) */
+    int whole;                      /* all six faces, every row */
+    int refine;                     /* if this launch records, k_mc_refine_bins follows it (2n) */
+    int bin_flavour;                /* the kernel shape in the cache's key */
+    int lds;                        /* dynamic LDS bytes of the kernel */
+    int lds_slices, direct_slices;  /* declined: k_mc_filter_lds<lds_slices> runs, or with lds_slices == 0 k_mc_filter<direct_slices, ..> */
+    int expect[16];                 /* k_mc_region: samples per slice */
+} PbrkMcPlan;
+int pbrk_mc_plan(int n_src, int n_tab, int size, int face0, int nfaces, int y0, int rows, int counters, int have_prep, PbrkMcPlan* out);
 
 /* ---- K5: deferred shade pass (shaders/lighting_pass.glsl:432-716, in-scope sub-blocks). */
 typedef struct PbrkShadeArgs {

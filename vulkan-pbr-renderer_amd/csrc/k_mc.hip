@@ -201,22 +201,11 @@ static void launch_mc_lds_s(McArgs a, int nfaces, size_t lds, hipStream_t st) {
     hipLaunchKernelGGL(k_mc_filter_lds<S>, dim3((unsigned)(a.tiles_per_face * nfaces)), dim3(1024), lds, st, a);
 }
 
-// returns false when the level does not fit in LDS
+// returns false when the level does not fit in LDS, or loses there (mc_lds_slices, mc_plan.h)
 static bool launch_mc_lds(McArgs a, int nfaces, hipStream_t st) {
-    if (g_mc_lds_mode < 0) { const char* e = getenv("PBR_MC_LDS"); g_mc_lds_mode = e ? atoi(e) : 1; }
-    const int mode = g_mc_lds_mode;
-    int nb = a.n_src + 2;
-    size_t lvl_bytes = (size_t)6 * nb * nb * 16;
-    if (!mode || lvl_bytes > 112 * 1024) return false;
-    // Measured (C4 / C2 on MI355X): with a 111 KB level only one 1024-thread workgroup fits per CU (16 waves) and the
-    // VALU-bound loop runs at ~4.4 clk/instruction; the direct kernel (32 waves/CU, 3 loads/sample) then wins on big
-    // outputs.  Small levels (several workgroups per CU) and small outputs (launch-limited) win with LDS.
-    if (lvl_bytes > 48 * 1024 && (size_t)6 * a.size * a.size > ((size_t)1 << 19)) return false;
-    // S from the level size only (deterministic under sharding): at least 512 workgroups of 1024 threads
-    size_t texels = (size_t)6 * a.size * a.size;
-    int S = 1;
-    while (S < 1024 && texels * (size_t)S < (size_t)512 * 1024) S <<= 1;
-    size_t lds = lvl_bytes + (S > 1 ? (size_t)1024 * 3 * 4 : 0);
+    const int S = mc_lds_slices(mc_switches().lds, a.n_src, a.size);            // pbrk_mc_set_kernels / PBR_MC_LDS
+    if (!S) return false;
+    size_t lds = (size_t)6 * (a.n_src + 2) * (a.n_src + 2) * 16 + (S > 1 ? (size_t)1024 * 3 * 4 : 0);
     switch (S) {
     case 1: launch_mc_lds_s<1>(a, nfaces, lds, st); break;
     case 2: launch_mc_lds_s<2>(a, nfaces, lds, st); break;
@@ -296,14 +285,7 @@ extern "C" int pbrk_mc_filter(const void* src_bordered_level, const void* src_ce
     if (!a.snap && launch_mc_lds(a, nfaces, st)) return hipGetLastError() == hipSuccess ? PBRK_OK : PBRK_E_LAUNCH;
     // Sample-split factor S depends on the LEVEL size only (not on the dispatched sub-range), so that a
     // sharded dispatch sums in exactly the same order as a full one (bit-identical results).
-    size_t texels = (size_t)6 * out_size * out_size;
-    // Enough workgroups to fill 256 CUs several times over: split the sample table when texels are few.  Never fewer than 4
-    // slices: a 256-texel workgroup walking all 8192 samples runs for ~5.6 ms, and a share of the level (one rank's tiles)
-    // that is only a few such rounds long loses up to a round in its tail; 4 slices of 64 texels (one wave each, table
-    // entries still wave-uniform scalar loads) cost nothing and cut that tail by four (8-way share: 18.1 -> 17.3 ms mean).
-    size_t want_blocks = 2048;
-    int S = 4;
-    while (S < 256 && texels * (size_t)S < want_blocks * 256) S <<= 1;
+    const int S = mc_direct_slices(out_size);
     switch (S) {
     case 4: launch_mc<4>(a, nfaces, st); break;
     case 8: launch_mc<8>(a, nfaces, st); break;

@@ -1,7 +1,9 @@
-// k_mc_internal.h -- argument block shared by the Monte-Carlo filter kernels (k_mc.hip, k_mc_region.hip).
+// k_mc_internal.h -- argument block shared by the Monte-Carlo filter kernels (k_mc.hip, k_mc_region.hip, k_mc_prep.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <mutex>
 #include "pbr_device.h"
+#include "mc_plan.h"
 
 struct McArgs {
     const float4* src; int n_src; unsigned src_bytes;
@@ -172,9 +174,15 @@ __host__ __device__ __forceinline__ bool mc_bin_window_ok(int size, int tile, in
 }
 
 // k_mc_region.hip: taps from LDS-staged regions of the source level.  Returns false when the kernel does not apply
-// (the caller then takes the direct kernel); the decision depends on the level's shape only, never on the dispatched range.
+// (the caller then takes the direct kernel); the decision (mc_plan) depends on the level's shape only, never on the dispatched range.
 bool launch_mc_region(McArgs a, int nfaces, hipStream_t st);
-// k_mc_region.hip, header 2k: levels up to 16^2 with outputs of 256^2 and more, resident in LDS as a whole; asked ahead of
+// k_mc_region.hip, header 2k: levels up to 16^2 with outputs of 128^2 and more, resident in LDS as a whole; asked ahead of
 // launch_mc_region, same contract (pbrk_mc_set_resident)
 bool launch_mc_resident(McArgs a, int nfaces, hipStream_t st);
-extern int g_mc_region_mode, g_mc_lds_mode;         // pbrk_mc_set_kernels (k_mc_region.hip)
+
+#define MC_MAX_DEVICES 16                           // per-device host state: the k_mc_prep ring, the counters of k_mc_refine_bins
+// k_mc_prep.hip: a slot of the scratch ring for one region launch.  words == null: none to be had (mc_plan's have_prep = false).
+struct McPrepSlot { unsigned* words = nullptr; int dev = 0, slot = -1; std::unique_lock<std::mutex> hold; };
+McPrepSlot mc_prep_acquire(hipStream_t st);
+void mc_prep_launch(const McPrepSlot& s, const McArgs& a, const McPlan& p, hipStream_t st);
+void mc_prep_release(McPrepSlot& s, hipStream_t st);

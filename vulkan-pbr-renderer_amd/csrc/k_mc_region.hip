@@ -1,4 +1,6 @@
 // k_mc_region.hip -- K4b / K3 for source levels too big for LDS as a whole: taps served from LDS-staged REGIONS.
+// The device code of k_mc_region, k_mc_refine_bins and k_mc_resident and their thin launchers.  Which kernel serves a level: mc_plan.cpp;
+// k_mc_prep, k_mc_cut and their scratch ring: k_mc_prep.hip; the bin cache's host side: mc_bins.cpp.
 //
 // Same sum as k_mc.hip (gen_prefiltered_env_map.glsl:115-146, gen_irradiance_map.glsl:81-97):
 //   out.rgb(texel) = ( sum_i w_i * bilinear(src, frame(texel) * l_i) ) / divisor
@@ -72,7 +74,7 @@
 //      S = 1, weighs the heaviest head word H_0 against the whole table).  The wider tile spreads its frames further: more samples are
 //      flagged for two regions and fewer are proved (2b).  A texel's sum is added in one chain instead of four partial ones: close to
 //      the 16 x 16 x 4 bytes, not equal.  One ballot of region_pass_runs covers 64 words here, so the tile serves tables of at most
-//      2048 samples.  Which levels take it is mc_tile32's rule (level shape and output size only; pbrk_mc_set_tile32; MC_TILE32_SUB);
+//      2048 samples.  Which levels take it is mc_tile32's rule (mc_plan.cpp; level shape and output size only; pbrk_mc_set_tile32; MC_TILE32_SUB);
 //      every other level keeps 16 x 16 x 4 and its bytes.  DESIGN.md 4, "K4b, round 9"; profiles/r09_tile32.md.
 //   2i. (round 10, proved runs on the whole-face shapes) the run loop of 2d walks the proved samples below the next tested one as a
 //      tight loop found with bit operations per run, so the proof of 2b costs no choice per sample.  It was only ever compiled for
@@ -86,7 +88,7 @@
 //      The quarter-face shape keeps its binning (one region per sample there as well, and the same ulp could meet it; not seen, and step
 //      3 catches it).  Measured (profiles/r10_certain_g1.md): C4 mip 2 24.45 -> 23.65 ms, mip 3 11.67 -> 11.09 ms, the job 50.2 -> 48.9 ms.
 //      The 18^2 shape (mip 4) LOSES with the run loop (3.71 -> 4.11 ms: 78 % proved, runs of three or four samples): it keeps the
-//      round-3 pass and has no RUNS instantiation.  A table of more than 64 words per slice would take the round-3 pass (launch_runs).
+//      round-3 pass and has no RUNS instantiation.  A table of more than 64 words per slice would take the round-3 pass (mc_plan).
 //   2j. (round 11, half_n folded into the frame rows; FOLD) a sample body forms (sc, tc, ma) = Pframe e, h = rcp(ma) half_n and the tap
 //      coordinates u = fma(sc, h, off), v = fma(tc, h, off).  Lemma: when half_n = 2^k (n_src a power of two), multiplying the six
 //      entries of the sc and tc rows of Pframe by half_n, once per (region, pass), gives sc' = 2^k sc and tc' = 2^k tc bit for bit --
@@ -103,7 +105,7 @@
 //      three numbers, permuted: their in-face tests would stop being one partition of the directions, and step 3 would heal
 //      wave-slices.  Such levels keep the multiply: the fold is a compile-time flag of k_mc_region, instantiated for the four lean run
 //      loops (RUNS and LEAN: <66, true, 32>, <66, true, 16>, <66, false, 16>, <34, false, 16>) and chosen by the host from n_src alone
-//      (launch_runs: a row shard equals the full dispatch), under pbrk_mc_set_fold (default 1; pbrk_mc_last_fold tells what the last
+//      (mc_plan: a row shard equals the full dispatch), under pbrk_mc_set_fold (default 1; pbrk_mc_last_fold tells what the last
 //      launch took).  FOLD = false is the machine code the instantiation had before.  heal_slice, binning and the direct kernel
 //      are untouched; the 18^2 shape has no proved body and no folded instantiation.  Measured (profiles/r11_fold.md): C4 mip 2 falls
 //      by 0.2 ms, mip 3 by 0.13, mip 1 by 0.05, the job by 0.4 ms (48.94 -> 48.53), in four sessions: under the 0.5 ms the round asked of a gain.
@@ -129,7 +131,7 @@
 //      pbrk_mc_resident_stats, slot 0: must stay 0) and counts the pairs each pass takes.  No absorb test, no head / tail phases, no launch
 //      cut: at roughness 0.6 every one of the 8192 weights is needed.  C2's 16 -> 256^2 level runs the 1389-sample table of roughness 0.03,
 //      most of which a launch cut could drop; that cut is left out of this kernel.
-//      Rule (launch_mc_resident, asked ahead of launch_mc_region): n_src <= 16, n_tab <= 8192 and an output of 256^2 or more take 16 x 16
+//      Rule (mc_plan, resident asked ahead of region): n_src <= 16, n_tab <= 8192 and an output of 256^2 or more take 16 x 16
 //      tiles x 4 slices, the work split, tree, divisor and alpha store of k_mc_region; outputs of 128^2 .. 255^2 take 8 x 8 tiles x 16
 //      slices (one wave holds a tile and a slice, a 16-way tree; MC_RESIDENT_TILE8), smaller ones stay on the level-in-LDS kernel of
 //      k_mc.hip.  FOLD where n_src is a power of two, the unfolded body elsewhere (n_src = 12).  The ORDER of a texel's sum now depends on
@@ -215,7 +217,7 @@
 //      FMAs on the same taps as a proved one; an absorbed-word test that no longer happens decided nothing that was accumulated.  The
 //      recording launch itself ran on the bound's flags.  k_mc_resident's entries are NOT refined: there the order of a texel's sum depends
 //      on what its tile proves, so its bytes would move.  pbrk_mc_set_exact_bins(-1), the default, is on exactly when the device counters
-//      are off (the rule of pbrk_mc_set_net and pbrk_mc_set_bin_cache; PBR_MC_EXACT_BINS=0|1) and, per shape by measurement (exact_shape),
+//      are off (the rule of pbrk_mc_set_net and pbrk_mc_set_bin_cache; PBR_MC_EXACT_BINS=0|1) and, per shape by measurement (McShape::EXACT_DEFAULT),
 //      today for the 34^2 shape alone: C4 mip 3 10.77 -> 10.13 ms.  The quarter-face level gained 0.45 ms of 7.15 and the 66^2 whole-face
 //      level 0.07 of 21.3, both inside five sigma of their launches: they keep the bound's flags unless pbrk_mc_set_exact_bins(1) asks.
 //      pbrk_mc_last_exact_bins tells what the last recording did.  48 VGPRs, no scratch; no texel is staged.  Measured: profiles/exact_bins.md.
@@ -225,12 +227,10 @@
 #include "pbr_device.h"
 #include "pbr_kernels.h"
 #include "k_mc_internal.h"
+#include "mc_bins.h"
 #include "mc_refine_core.h"
 
-#include <stdlib.h>
-#include <mutex>
 #include <type_traits>
-#include <vector>
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 // The sample table is read-only for the whole launch: a pointer into the constant address space makes every wave-uniform
@@ -245,43 +245,7 @@ typedef const __attribute__((address_space(4))) unsigned* cu32_t;
 //   TILE 16: 256 texels x 4 slices (waves 4s .. 4s+3 own slice s);  TILE 32 (header 2h): 1024 texels x 1 slice.
 // The smaller tile halves the frame spread delta the region flags are built from (fewer samples flagged for two regions) and
 // pays four times the binning / staging per texel: it wins where regions are small next to that spread (n_src <= 32).
-#define REG_MAX_S 16
-// Header 2g, decided per 66^2 shape by measurement: head words first (and with it the launch-level cut) on the quarter-face shape
-// (SUB) / on the whole-face shape (G == 1).  0 keeps the shape's earlier order and bytes.
-#ifndef MC_HEAD_FIRST_SUB
-#define MC_HEAD_FIRST_SUB 1
-#endif
-#ifndef MC_HEAD_FIRST_G1
-#define MC_HEAD_FIRST_G1 1
-#endif
-// Header 2i, decided per whole-face shape by measurement: under RUNS the samples binning proves for the whole tile run as test-free runs
-// (CERT in k_mc_region).  The 34^2 shape takes them; MC_CERT_G1 is the 66^2 whole-face shape: 0 keeps the machine code it had without.
-#ifndef MC_CERT_G1
-#define MC_CERT_G1 1
-#endif
-
-// Header 2j, decided per shape by measurement: the folded instantiation of the 66^2 whole-face shape keeps a tap's four texels alive with
-// one statement, so that their LDS reads wait once (tap_accumulate, JOIN).  0 keeps the two waits; the other shapes lose or gain nothing with it.
-#ifndef MC_TAP_JOIN_G1
-#define MC_TAP_JOIN_G1 1
-#endif
-
-// Header 2h: 32 x 32 tiles x 1 slice on the quarter-face shape where mc_tile32's rule holds.  0 keeps 16 x 16 x 4 and the parent's bytes
-// (pbrk_mc_set_tile32(1) still selects the tile).
-#ifndef MC_TILE32_SUB
-#define MC_TILE32_SUB 1
-#endif
-// Header 2l, decided by measurement: the 34^2 shape has no absorbed words and loses only the count with its net; 0 keeps its net always.
-#ifndef MC_NET_OFF_34
-#define MC_NET_OFF_34 1
-#endif
-// Header 2l, decided by measurement: the net-less kernel ends a pass at the first absorbed word behind which the slice's word maxima never rise.
-#ifndef MC_MONO_EXIT
-#define MC_MONO_EXIT 1
-#endif
-#ifndef MC_TILE32_MIN_SIZE
-#define MC_TILE32_MIN_SIZE 1024
-#endif
+// The shapes' compile-time facts (McShape) and the MC_* switches of the measurements behind them: mc_plan.h.
 
 struct RegArgs {
     McArgs a;
@@ -563,7 +527,7 @@ __device__ __forceinline__ void region_pass(const RegionView& V, const unsigned*
 // region_pass with less scalar work per word and per sample (round 5, 66^2 shapes; RUNS in k_mc_region).  Same words, samples,
 // bodies, absorb decisions and FMA order; cnt counts per LANE (every lane of a complete wave ends at expect[s]):
 //   * only the non-empty words of the slice are visited: one LDS read per lane (lane k: word s + REG_S k; one ballot covers 64 REG_S
-//     words -- NW <= 256 with four slices, NW <= 64 with one: launch_mc_region keeps longer tables off the one-slice tile) and a ballot,
+//     words -- NW <= 256 with four slices, NW <= 64 with one: mc_tile32 keeps longer tables off the one-slice tile) and a ballot,
 //     masked by wsel (bit k: word s + REG_S k belongs to this pass -- all, the head word alone, or the tail words: header 2g);
 //   * CERT: the proved samples below the next tested one run as a run of certain_sample (no per-sample proved-bit test, no exec
 //     join), then the tested one, in index order;
@@ -918,21 +882,16 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
     static_assert(NET || (RUNS && LEAN && RS != 18), "NET = false: the run loop of the lean 66^2 / 34^2 shapes only");
     // see the header, 2b and 2i: quarter faces always; whole faces only with the run loop, which pays no per-sample choice of body
     constexpr bool CERT = SUB || (RUNS && (RS != 66 || MC_CERT_G1 != 0));
-    // see the header, 2c: compiled for the 66^2 region shapes only.  The 34^2 / 18^2 levels of C4 (mips 3, 4: weights fall to ~e^-6)
-    // never absorb a word, and the test alone cost them 7 % (measured); without it their code is that of round 3
-    constexpr bool ABS = RS == 66;
+    using SH = McShape<RS, SUB, TILE>;                                  // ABS (2c), OWN_FIRST (2e), TWO (2g): mc_plan.h
+    constexpr bool ABS = SH::ABS;
     const bool absorb_on = ABS && q.absorb;                              // workgroup-uniform
-    // see the header, 2e: the order pays through the absorbed words, so it is taken where they are compiled.  The 34^2 / 18^2 shapes keep
-    // index order and their bytes: there the reordered sums bought nothing and moved C4 mip 3 to 2.5e-5 from the direct kernel,
-    // past the 2e-5 of the every-texel cross-check (test_gpu_configs.py)
-    constexpr bool OWN_FIRST = ABS;
+    constexpr bool OWN_FIRST = SH::OWN_FIRST;
     // see the header, 2m: the product instantiations (the lean run loops, both FOLD and NET values) can record and replay their binning
     constexpr bool BINS = RUNS && LEAN;
-    // see the header, 2g: head words first, then the tail words; decided per 66^2 shape (MC_HEAD_FIRST_SUB / MC_HEAD_FIRST_G1)
-    constexpr bool TWO = RS == 66 && (SUB ? MC_HEAD_FIRST_SUB != 0 : MC_HEAD_FIRST_G1 != 0);
+    constexpr bool TWO = SH::TWO;
     const bool cut_on = TWO && LEAN && q.cut != 0;                       // workgroup-uniform: the launch's cut words are not binned
     // LDS layout: the staged region (RS^2 texels), then in words skc[4] | masks[NR NW] | any[NR] | dmax[1] | cmask[NW] | wmax[NW] | rmax[NR].
-    // launch_mc_region's lds_fixed is this chain up to cmask, its absorb term the last two.  region_bin clears masks .. dmax and the
+    // mc_region_lds (mc_plan.h) is this chain up to cmask, its absorb term the last two.  region_bin clears masks .. dmax and the
     // ntail words behind dmax: the arrays this launch reads.  All three move together.
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_r[];
     float4* region = (float4*)smem_r;
@@ -1150,7 +1109,7 @@ struct RefineArgs {
 template <int RS, bool SUB, int TILE, bool FOLD>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_mc_refine_bins(const RefineArgs g) {
     constexpr int REG_TX = TILE * TILE, REG_S = 1024 / REG_TX;
-    constexpr bool TWO = RS == 66 && (SUB ? MC_HEAD_FIRST_SUB != 0 : MC_HEAD_FIRST_G1 != 0);
+    constexpr bool TWO = McShape<RS, SUB, TILE>::TWO;
     extern __shared__ __attribute__((aligned(16))) unsigned smem_f[];
     const McArgs& p = g.a;
     const int NR = g.NR, NW = g.NW, G = g.G, RC = g.RC, tid = threadIdx.x;
@@ -1263,9 +1222,7 @@ __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) vo
 }
 
 // ---- levels resident in LDS as a whole (header, 2k) ----
-// Every face is staged with the row pitch of the 18^2 shape, whatever n_src <= 16 is: face f's block starts RES_FACE_BYTES f behind the base.
-#define RES_RS 18
-#define RES_FACE_BYTES (RES_RS * RES_RS * 16)
+// Every face is staged with the row pitch of the 18^2 shape, whatever n_src <= 16 is (RES_RS, RES_FACE_BYTES: mc_plan.h).
 
 struct ResArgs {
     RegArgs q;                  // a.y0, a.rows: the rows of the 16-row tiles that hold the dispatch's rows, counted from row 0 of the face;
@@ -1346,7 +1303,7 @@ __device__ __forceinline__ void resident_face(const unsigned* __restrict__ pm, i
 template <int TILE, bool FOLD, bool STATS>
 __global__ __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_mc_resident(const ResArgs g) {
     constexpr int REG_TX = TILE * TILE, REG_S = 1024 / REG_TX, RS = RES_RS;
-    // LDS layout: the level (6 RS^2 texels), then in words masks[6 NW] | any[6] | dmax[1] | cmask[NW]: region_bin's chain (launch_mc_resident)
+    // LDS layout: the level (6 RS^2 texels), then in words masks[6 NW] | any[6] | dmax[1] | cmask[NW]: region_bin's chain (mc_resident_lds, mc_plan.h)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_v[];
     float4* lvl = (float4*)smem_v;
     const unsigned lds_base = (unsigned)(unsigned long long)smem_v;
@@ -1479,550 +1436,120 @@ extern "C" int pbrk_mc_region_skip_stats(unsigned long long* out3) { return read
 extern "C" int pbrk_mc_region_window_stats(unsigned long long* out1) { return read_stats(out1, 5, 1); }      // samples run through the test-free body (sum over tiles)
 extern "C" int pbrk_mc_region_flag_stats(unsigned long long* out3) { return read_stats(out3, 2, 3); }
 extern "C" int pbrk_mc_region_phase_stats(unsigned long long* out5) { return read_stats(out5, 9, 5); }       // PBR_MC_PHASE_STAMPS builds; zeros otherwise (RegArgs::stats [9..13])
+// PBR_MC_STATS=1, since the last reset: {(lane, sample) pairs whose proof did not hold (must stay 0), proved samples summed over
+// tiles, pairs taken by the proved runs, pairs taken by the general pass}
+extern "C" int pbrk_mc_resident_stats(unsigned long long* out4) { return read_stats(out4, 16, 4); }
 
-static int g_last_fold = 0;                            // whether the last region launch took a FOLD instantiation (pbrk_mc_last_fold)
-static int g_last_net = 1;                             // whether the last region launch carried the completeness net (pbrk_mc_last_net)
-template <int RS, bool SUB, int TILE, bool RUNS = false, bool LEAN = false, bool FOLD = false, bool NET = true>
-static void launch_region_t(const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
-    static bool attr_set = false;
-    if (!attr_set) { (void)hipFuncSetAttribute((const void*)k_mc_region<RS, SUB, TILE, RUNS, LEAN, FOLD, NET>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
-    g_last_fold = FOLD ? 1 : 0;
-    g_last_net = NET ? 1 : 0;
-    hipLaunchKernelGGL((k_mc_region<RS, SUB, TILE, RUNS, LEAN, FOLD, NET>), dim3(grid), dim3(1024), lds, st, q);
-}
-
-// ---- the launch's maxima (header, 2f) ----
-// out[0 .. NW): per mask word, the largest bit pattern of its samples' weights; out[NW .. NW + NR): per region, the largest bit
-// pattern of the R, G, B of exactly the texels the region kernel stages for it (rx <= rcx, ry <= rcy: apron included).  Compared as
-// unsigned integers, as the lemma at absorb_threshold wants: a negative, -0, inf or NaN orders at or above +inf's pattern.
-// Block b < NR reduces region b; the blocks behind take 256 words each, one per thread.
-// Header 2g: out[NW + NR + 4 .. + NR): per region, the SMALLEST such bit pattern (k_mc_cut's m; a negative or -0 texel hides from it but
-// not from the largest pattern, which then switches the cut off).
-__global__ __launch_bounds__(256) void k_mc_prep(const float4* __restrict__ src, int n, int G, int RC, int NR,
-                                                 const float4* __restrict__ tab, int n_tab, int NW, unsigned* __restrict__ out) {
-    const int tid = threadIdx.x;
-    if ((int)blockIdx.x >= NR) {
-        const int w = ((int)blockIdx.x - NR) * 256 + tid;
-        if (w >= NW) return;
-        unsigned m = 0u;
-        for (int i = w << 5; i < min((w << 5) + 32, n_tab); ++i) m = max(m, __float_as_uint(tab[i].w));
-        out[w] = m;
-        return;
-    }
-    __shared__ unsigned red, redlo;
-    if (tid == 0) { red = 0u; redlo = 0xffffffffu; }
-    __syncthreads();
-    const int r = (int)blockIdx.x, nb = n + 2;
-    const int f = r / (G * G), gy = (r / G) % G, gx = r % G;
-    const int ox = gx * RC, oy = gy * RC;
-    const int cols = min(RC, n + 1 - ox) + 1, rows = min(RC, n + 1 - oy) + 1;
-    const float4* __restrict__ fsrc = src + ((size_t)f * nb + oy) * nb + ox;
-    unsigned m = 0u, lo = 0xffffffffu;
-    for (int k = tid; k < rows * cols; k += 256) {
-        const int ry = k / cols, rx = k - ry * cols;
-        const float4 v = fsrc[ry * nb + rx];
-        m = max(m, max(__float_as_uint(v.x), max(__float_as_uint(v.y), __float_as_uint(v.z))));
-        lo = min(lo, min(__float_as_uint(v.x), min(__float_as_uint(v.y), __float_as_uint(v.z))));
-    }
-    atomicMax(&red, m);
-    atomicMin(&redlo, lo);
-    __syncthreads();
-    if (tid == 0) { out[NW + r] = red; out[NW + NR + 4 + r] = redlo; }
-}
-
-// ---- the launch's cut (header, 2g) ----
-// One wave behind k_mc_prep on the same stream: lanes 0 .. S - 1 add up the weights of their slice's head word in double, in index order;
-// lane 0 folds the regions' extrema and writes the first cut word of each slice to out[NW + NR .. + 4) (mc_launch_cut_s, k_mc_internal.h).
-// S (1, 2 or 4) is the slice count of the region kernel behind it; all four slots are written, slot j with the cut of slice j % S.
-// Header 2l: out[NW + 2 NR + 4 .. + 4), behind the regions' minima: per slice the first word from which the word maxima never rise again
-// (mc_mono_from), slots as for the cut.
-__global__ __launch_bounds__(64) void k_mc_cut(const float4* __restrict__ tab, int n_tab, int NW, int NR, int S, unsigned* __restrict__ out) {
-    __shared__ double H[4];
-    const int tid = threadIdx.x;
-    if (tid < 4) {
-        double h = 0.0;
-        if (tid < S && NW > S)
-            for (int i = 0; i < 32; ++i) h += (double)tab[(tid << 5) + i].w;
-        H[tid] = h;
-    }
-    __syncthreads();
-    if (tid != 0) return;
-    unsigned M = 0u, m = 0xffffffffu;
-    for (int r = 0; r < NR; ++r) { M = max(M, out[NW + r]); m = min(m, out[NW + NR + 4 + r]); }
-    int cut4[4];
-    mc_launch_cut_s(out, NW, S, H, m, M, cut4);
-    for (int s = 0; s < 4; ++s) out[NW + NR + s] = (unsigned)cut4[s % S];
-    // header 2l: per slice, the first word from which the word maxima never rise again, behind the regions' minima
-    int mono4[4];
-    mc_mono_from(out, NW, S, mono4);
-    for (int s = 0; s < 4; ++s) out[NW + 2 * NR + 4 + s] = (unsigned)mono4[s % S];
-}
-
-// The same cut on the host, from the table's weights and the level's extrema (bit patterns): what k_mc_cut writes for them.  Needs no GPU.
-// cut4[s]: the first cut word of slice s (see mc_launch_cut).  Returns the number of words cut, or -1 for bad arguments.
-extern "C" int pbrk_mc_launch_cut(const float* weights, int n, unsigned min_bits, unsigned max_bits, int* cut4) {
-    return pbrk_mc_launch_cut_slices(weights, n, 4, min_bits, max_bits, cut4);
-}
-// The same for a launch of S slices per workgroup (S = 1, 2 or 4; mc_launch_cut_s): cut[s], s < S.
-extern "C" int pbrk_mc_launch_cut_slices(const float* weights, int n, int S, unsigned min_bits, unsigned max_bits, int* cut4) {
-    if (!weights || !cut4 || n < 1 || n > 8192 || (S != 1 && S != 2 && S != 4)) return -1;
-    const int NW = (n + 31) / 32;
-    unsigned wbits[256];
-    for (int w = 0; w < NW; ++w) {
-        unsigned m = 0u;
-        for (int i = w << 5; i < (w << 5) + 32 && i < n; ++i) {
-            union { float f; unsigned u; } c;
-            c.f = weights[i];
-            m = c.u > m ? c.u : m;
-        }
-        wbits[w] = m;
-    }
-    double H[4] = {0.0, 0.0, 0.0, 0.0};
-    if (NW > S)
-        for (int s = 0; s < S; ++s)
-            for (int i = 0; i < 32; ++i) H[s] += (double)weights[(s << 5) + i];
-    return mc_launch_cut_s(wbits, NW, S, H, min_bits, max_bits, cut4);
-}
-
-// mc_mono_from on the host, from a table's weights: mono4[s], s < S, as k_mc_cut writes it for a launch of S slices.  Needs no GPU.
-extern "C" int pbrk_mc_mono_slices(const float* weights, int n, int S, int* mono4) {
-    if (!weights || !mono4 || n < 1 || n > 8192 || (S != 1 && S != 2 && S != 4)) return -1;
-    const int NW = (n + 31) / 32;
-    unsigned wbits[256];
-    for (int w = 0; w < NW; ++w) {
-        unsigned m = 0u;
-        for (int i = w << 5; i < (w << 5) + 32 && i < n; ++i) {
-            union { float f; unsigned u; } c;
-            c.f = weights[i];
-            m = c.u > m ? c.u : m;
-        }
-        wbits[w] = m;
-    }
-    mc_mono_from(wbits, NW, S, mono4);
-    return 0;
-}
-
-// Scratch for those tables: a ring of slots in device memory, allocated once per device.  A slot is written by k_mc_prep and read
-// by the region kernel behind it on the same stream; an event recorded behind that reader is waited for, in-stream, by the next
-// launch that takes the slot, so launches in flight on different streams (the tile streams of GPU_GraphSubmit) never share one.
-#define PREP_SLOTS 32
-#define PREP_SLOT_WORDS 4096                                    // NW <= 256; NR (NW + 1) words of masks fit 80 KB of LDS behind the region
-#define PREP_MAX_DEVICES 16
-struct PrepRing { unsigned* dev; hipEvent_t ev[PREP_SLOTS]; bool used[PREP_SLOTS]; unsigned next; };
-static PrepRing g_prep[PREP_MAX_DEVICES];
-static std::mutex g_prep_lock;
-
-// The slot for one launch on `st` (its previous reader waited for), or null: no device memory, or `st` is being captured into a
-// graph -- a replayed graph keeps the slot it was recorded with, and nothing would order its replays against later launches.
-static unsigned* prep_acquire(hipStream_t st, int* slot_out) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    if (cs != hipStreamCaptureStatusNone) return nullptr;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PREP_MAX_DEVICES) return nullptr;
-    PrepRing& R = g_prep[dev];
-    if (!R.dev) {
-        if (hipMalloc(&R.dev, (size_t)PREP_SLOTS * PREP_SLOT_WORDS * 4) != hipSuccess) { (void)hipGetLastError(); R.dev = nullptr; return nullptr; }
-        for (int i = 0; i < PREP_SLOTS; ++i) {
-            R.used[i] = false;
-            if (hipEventCreateWithFlags(&R.ev[i], hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(R.dev); R.dev = nullptr; return nullptr; }
-        }
-        R.next = 0;
-    }
-    const int slot = (int)(R.next++ % PREP_SLOTS);
-    if (R.used[slot] && hipStreamWaitEvent(st, R.ev[slot], 0) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    *slot_out = slot;
-    return R.dev + (size_t)slot * PREP_SLOT_WORDS;
-}
-
-// Which kernel serves a level (tests / A-B runs; -1 = the environment variable PBR_MC_REGION / PBR_MC_LDS, else the default 1)
-int g_mc_region_mode = -1, g_mc_lds_mode = -1;
-extern "C" void pbrk_mc_set_kernels(int region, int lds) { g_mc_region_mode = region; g_mc_lds_mode = lds; }
-// Skipping of absorbed words (tests / A-B runs; the outputs are the same bit for bit either way)
-static int g_mc_absorb = 1;
-extern "C" void pbrk_mc_set_absorb(int on) { g_mc_absorb = on ? 1 : 0; }
-// The round-5 loop of the 66^2 shapes (k_mc_region RUNS; tests / A-B runs; the outputs are the same bit for bit either way)
-static int g_mc_runs = 1;
-extern "C" void pbrk_mc_set_runs(int on) { g_mc_runs = on ? 1 : 0; }
-// The prologue of header 2f (k_mc_region LEAN; tests / A-B runs; 0: the prologue before it; the outputs are the same bit for bit either way)
-static int g_mc_lean = 1;
-extern "C" void pbrk_mc_set_prologue(int lean) { g_mc_lean = lean ? 1 : 0; }
-
-// The launch-level cut of header 2g (tests / A-B runs; the outputs are the same bit for bit either way)
-static int g_mc_launch_cut = 1;
-extern "C" void pbrk_mc_set_launch_cut(int on) { g_mc_launch_cut = on ? 1 : 0; }
-// The 32 x 32 tile of header 2h (tests / A-B runs): -1 the rule of mc_tile32 (default), 0 never, 1 wherever the shape allows it
-// (quarter faces, NW <= 64) whatever the output size.  The tile changes the order of a texel's sum: not the same bytes as 16 x 16 x 4.
-static int g_mc_tile32 = -1;
-extern "C" void pbrk_mc_set_tile32(int mode) { g_mc_tile32 = mode < 0 ? -1 : (mode ? 1 : 0); }
-// half_n folded into the frame rows on power-of-two levels (header 2j; tests / A-B runs; the outputs are the same bit for bit either way)
-static int g_mc_fold = 1;
-extern "C" void pbrk_mc_set_fold(int on) { g_mc_fold = on ? 1 : 0; }
-// 1 when the last region-kernel launch ran a FOLD instantiation, else 0 (also before the first launch)
-extern "C" int pbrk_mc_last_fold(void) { return g_last_fold; }
-// The completeness net of the header's step 3 (2l; tests / A-B runs; the outputs are the same bit for bit either way): -1 the default rule --
-// on when the device counters are on (PBR_MC_STATS=1), off otherwise --, 0 off wherever a net-less instantiation exists (the lean run
-// loops), 1 always on.  The rule reads nothing of the dispatch.
-static int g_mc_net = -1;
-extern "C" void pbrk_mc_set_net(int mode) { g_mc_net = mode < 0 ? -1 : (mode ? 1 : 0); }
-// 1 when the last region-kernel launch carried the net, 0 when it ran a net-less instantiation (1 before the first launch)
-extern "C" int pbrk_mc_last_net(void) { return g_last_net; }
-// The cut of the last region-kernel launch, for tests and probes: out6 = the first cut word of slices 0 .. 3, NW, words cut.  A launch
-// without a cut reports 0 words.  A launch of S < 4 slices reports slice j % S in entry j (one slice: its first cut word four times);
-// the words cut are counted over the launch's S slices.  Waits for the device.
-static const unsigned* g_last_cut = nullptr;
-static int g_last_cut_nw = 0, g_last_cut_s = 4;
-extern "C" int pbrk_mc_launch_cut_stats(int* out6) {
-    if (!out6) return PBRK_E_ARG;
-    const int NW = g_last_cut_nw, S = g_last_cut_s;
-    for (int j = 0; j < 4; ++j) { const int s = j % S; out6[j] = s >= NW ? s : s + S * ((NW - s + S - 1) / S); }
-    out6[4] = NW; out6[5] = 0;
-    if (!g_last_cut) return PBRK_OK;
-    if (hipDeviceSynchronize() != hipSuccess) return PBRK_E_LAUNCH;
-    int c[4];
-    if (hipMemcpy(c, g_last_cut, 16, hipMemcpyDeviceToHost) != hipSuccess) return PBRK_E_LAUNCH;
-    for (int s = 0; s < 4; ++s) { if (s < S) out6[5] += (out6[s] - c[s]) / S; out6[s] = c[s]; }
-    return PBRK_OK;
-}
-
-// The round-5 loop (pbrk_mc_set_runs) on the shapes that have it (HAS_RUNS), or the pass before it.  One ballot of region_pass_runs
-// covers 64 words per slice: a longer table takes the pass before it as well (launch_mc_region admits at most 8192 samples, 256 words,
-// and mc_tile32 at most 64 words on the one-slice tile, so today that never happens).
-template <int RS, bool SUB, int TILE, bool LEAN, bool HAS_RUNS = true>
-static void launch_runs(const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
-    if constexpr (HAS_RUNS) {
-        if (g_mc_runs && q.NW <= 64 * (1024 / (TILE * TILE))) {
-            // header 2j: a rule of the level alone (n_src), so a row shard equals the full dispatch; only the lean run loop has the instantiation
-            // header 2l: the net is a rule of the process (the counters, pbrk_mc_set_net), never of the dispatch
-            if constexpr (LEAN) {
-                const int n = q.a.n_src;
-                const bool fold = g_mc_fold && (n & (n - 1)) == 0;
-                if constexpr (RS != 34 || MC_NET_OFF_34 != 0) {
-                    if (!(g_mc_net < 0 ? q.stats != nullptr : g_mc_net != 0)) {
-                        if (fold) launch_region_t<RS, SUB, TILE, true, true, true, false>(q, grid, lds, st);
-                        else launch_region_t<RS, SUB, TILE, true, true, false, false>(q, grid, lds, st);
-                        return;
-                    }
-                }
-                if (fold) { launch_region_t<RS, SUB, TILE, true, true, true>(q, grid, lds, st); return; }
-            }
-            launch_region_t<RS, SUB, TILE, true, LEAN>(q, grid, lds, st);
-            return;
-        }
-    }
-    launch_region_t<RS, SUB, TILE, false, LEAN>(q, grid, lds, st);
-}
-
-template <bool LEAN>
-static void launch_shape(int RS, int tile, const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
-    if (tile == 32) launch_runs<66, true, 32, LEAN>(q, grid, lds, st);
-    else if (RS == 18) launch_runs<18, false, 16, LEAN, false>(q, grid, lds, st);    // header 2i: the run loop loses on this shape
-    else if (RS == 34) launch_runs<34, false, 16, LEAN>(q, grid, lds, st);
-    else if (q.G == 1) launch_runs<66, false, 16, LEAN>(q, grid, lds, st);
-    else launch_runs<66, true, 16, LEAN>(q, grid, lds, st);
-}
-
-// The device counters (PBR_MC_STATS=1, read once), or null
+// The device counters (PBR_MC_STATS=1), or null
 static unsigned long long* reg_stats() {
     static int stats_on = -1;
     if (stats_on < 0) {
-        const char* e = getenv("PBR_MC_STATS"); stats_on = e ? atoi(e) : 0;
+        stats_on = mc_counters_wanted() ? 1 : 0;
         if (stats_on) { if (hipMalloc(&g_reg_stats, REG_STATS_BYTES) != hipSuccess) g_reg_stats = nullptr; else (void)hipMemset(g_reg_stats, 0, REG_STATS_BYTES); }
     }
     return g_reg_stats;
 }
 
-// Which tile serves a level (header 2h): a function of the level alone -- n_src, n_tab, the output size -- never of the dispatch's faces
-// or rows, so a row shard equals the full dispatch bit for bit.  32 x 32 x 1 needs the quarter-face shape (its body is the shortest and
-// its prologue the largest share) and NW <= 64 (one ballot of region_pass_runs); the rule adds size >= MC_TILE32_MIN_SIZE: below it
-// the level has too few 32 x 32 tiles to fill the chip (profiles/r09_tile32.md).
-static bool mc_tile32(int n_src, int n_tab, int size) {
-    if (n_src <= 64 || (n_tab + 31) / 32 > 64) return false;
-    const int mode = g_mc_tile32 < 0 ? (MC_TILE32_SUB ? -1 : 0) : g_mc_tile32;
-    return mode > 0 || (mode < 0 && size >= MC_TILE32_MIN_SIZE);
+// ---- plan -> launch: the thin launchers of the three kernel families.  Every decision is mc_plan's (mc_plan.cpp) ----
+template <int RS, bool SUB, int TILE, bool RUNS = false, bool LEAN = false, bool FOLD = false, bool NET = true>
+static void launch_region_t(const RegArgs& q, unsigned grid, size_t lds, hipStream_t st) {
+    static bool attr_set = false;
+    if (!attr_set) { (void)hipFuncSetAttribute((const void*)k_mc_region<RS, SUB, TILE, RUNS, LEAN, FOLD, NET>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
+    hipLaunchKernelGGL((k_mc_region<RS, SUB, TILE, RUNS, LEAN, FOLD, NET>), dim3(grid), dim3(1024), lds, st, q);
 }
 
-// ---- header 2m: the bin cache ----
-// What binning computes depends on the tile's geometry, the level's shape and the sample table, never on a texel: one buffer per
-// (device, kernel shape, n_src, output size, n_entries, table, generation) holds every tile's flags, written by the first whole-level
-// launch and read by every eligible launch after it.  A raw table pointer says nothing about its contents, so only tables registered as
-// immutable (pbrk_mc_table_register) are served; each registration is a new generation.  No eviction: an entry that would pass the budget
-// is not created.  One lock orders lookup, creation and the event behind the recording launch; a replay on any stream waits for that event.
-struct BinTable { const void* ptr; int n; unsigned long long gen; };
-struct BinEntry {
-    int dev, flavour, n_src, size, n_tab; const void* tab; unsigned long long gen;
-    unsigned* buf; size_t bytes; hipEvent_t ready; bool done;
-};
-static std::vector<BinTable> g_bin_tables;
-static std::vector<BinEntry> g_bin_entries;
-static std::mutex g_bin_lock;
-static int g_bin_mode = -1;
-static size_t g_bin_budget = (size_t)512 << 20;
-static unsigned long long g_bin_gen = 0;
-static unsigned long long g_bin_count[4];               // recording launches, replaying launches, computed though the cache was on, declined for the budget
-
-static void bin_entry_free(BinEntry& e) { (void)hipFree(e.buf); (void)hipEventDestroy(e.ready); }   // hipFree waits for the device
-
-extern "C" void pbrk_mc_set_bin_cache(int mode) { g_bin_mode = mode < 0 ? -1 : (mode ? 1 : 0); }
-extern "C" void pbrk_mc_set_bin_cache_budget(size_t bytes) { std::lock_guard<std::mutex> hold(g_bin_lock); g_bin_budget = bytes; }
-extern "C" void pbrk_mc_bin_cache_clear(void) {
-    std::lock_guard<std::mutex> hold(g_bin_lock);
-    for (BinEntry& e : g_bin_entries) bin_entry_free(e);
-    g_bin_entries.clear();
-}
-extern "C" void pbrk_mc_bin_cache_stats(unsigned long long out[5]) {
-    if (!out) return;
-    std::lock_guard<std::mutex> hold(g_bin_lock);
-    for (int i = 0; i < 4; ++i) out[i] = g_bin_count[i];
-    out[4] = 0;
-    for (const BinEntry& e : g_bin_entries) out[4] += e.bytes;
-}
-extern "C" int pbrk_mc_table_unregister(const void* table4) {
-    if (!table4) return PBRK_E_ARG;
-    std::lock_guard<std::mutex> hold(g_bin_lock);
-    for (size_t i = 0; i < g_bin_tables.size(); ++i)
-        if (g_bin_tables[i].ptr == table4) {
-            g_bin_tables.erase(g_bin_tables.begin() + (long)i);
-            // the entries recorded with this registration can never be asked for again
-            for (size_t k = g_bin_entries.size(); k-- > 0;)
-                if (g_bin_entries[k].tab == table4) { bin_entry_free(g_bin_entries[k]); g_bin_entries.erase(g_bin_entries.begin() + (long)k); }
-            return PBRK_OK;
-        }
-    return PBRK_E_ARG;
-}
-extern "C" int pbrk_mc_table_register(const void* table4, int n_entries) {
-    if (!table4 || n_entries < 1) return PBRK_E_ARG;
-    (void)pbrk_mc_table_unregister(table4);                         // registered again: a new generation
-    std::lock_guard<std::mutex> hold(g_bin_lock);
-    g_bin_tables.push_back({table4, n_entries, ++g_bin_gen});
-    return PBRK_OK;
-}
-extern "C" int pbrk_mc_tile_of_block(int block, int size, int tile, int face0, int nfaces, int y0, int y1, int* out4) {
-    if (!out4 || size < 1 || (tile != 8 && tile != 16 && tile != 32) || face0 < 0 || nfaces < 1 || face0 + nfaces > 6 || y0 < 0 || y0 >= y1 || y1 > size) return PBRK_E_ARG;
-    const int tiles_x = (size + tile - 1) / tile, tiles_y = (y1 - y0 + tile - 1) / tile;
-    if (block < 0 || block >= tiles_x * tiles_y * nfaces) return PBRK_E_ARG;
-    int pole_row[2];
-    mc_pole_rows(size, y0, tile, tiles_y, pole_row);
-    mc_tile_of_block((unsigned)block, face0, tiles_x, tiles_x * tiles_y, pole_row, out4[0], out4[1], out4[2]);
-    out4[3] = (int)mc_bin_tile_index(out4[0], y0 / tile, out4[2], out4[1], tiles_x, tiles_x);
-    return PBRK_OK;
-}
-extern "C" int pbrk_mc_bin_window_eligible(int size, int tile, int y0, int y1) { return mc_bin_window_ok(size, tile, y0, y1) ? 1 : 0; }
-
-// The cache's part in one launch; g_bin_lock is held from here until the launch (and, for a recording one, its event) is enqueued.
-// eligible: a participating kernel shape and a row window whose tiles are those of the whole-level dispatch; whole: all six faces, all rows.
-// Sets q.bins (replay) or q.bins_out (record; returns the entry's index for bin_recorded) or neither (compute as ever).
-static int bin_plan(RegArgs& q, int flavour, bool eligible, bool whole, int tile, hipStream_t st) {
-    q.bins = nullptr; q.bins_out = nullptr;
-    int mode = g_bin_mode;
-    if (mode < 0) { static int env = -2; if (env == -2) { const char* e = getenv("PBR_MC_BIN_CACHE"); env = e ? (atoi(e) ? 1 : 0) : -1; } mode = env; }
-    if (!(mode < 0 ? q.stats == nullptr : mode != 0)) return -1;
-    const McArgs& a = q.a;
-    int dev = 0;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    const BinTable* bt = nullptr;
-    for (const BinTable& t : g_bin_tables) if (t.ptr == (const void*)a.tab && a.n_tab <= t.n) bt = &t;
-    if (!eligible || !bt || hipGetDevice(&dev) != hipSuccess || hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-        (void)hipGetLastError();
-        ++g_bin_count[2];
-        return -1;
-    }
-    size_t held = 0;
-    for (BinEntry& e : g_bin_entries) {
-        if (e.dev != dev) continue;
-        held += e.bytes;
-        if (e.flavour == flavour && e.n_src == a.n_src && e.size == a.size && e.n_tab == a.n_tab && e.tab == bt->ptr && e.gen == bt->gen) {
-            if (!e.done) {
-                if (hipEventQuery(e.ready) == hipSuccess) e.done = true;
-                else { (void)hipGetLastError(); if (hipStreamWaitEvent(st, e.ready, 0) != hipSuccess) { (void)hipGetLastError(); ++g_bin_count[2]; return -1; } }
+// The instantiation of shape SH that the plan's (runs, lean, fold, net) name.  FOLD and NET = false exist for the lean run loops only
+// (header 2j, 2l), the run loop on the shapes that have it (2i).
+template <class SH>
+static void launch_region_shape(const McPlan& p, const RegArgs& q, unsigned grid, hipStream_t st) {
+    constexpr int RS = SH::RS, TILE = SH::TILE;
+    constexpr bool SUB = SH::SUB;
+    const size_t lds = (size_t)p.lds;
+    if constexpr (SH::HAS_RUNS) {
+        if (p.runs && p.lean) {
+            if constexpr (SH::NET_OFF) {
+                if (!p.net) {
+                    if (p.fold) launch_region_t<RS, SUB, TILE, true, true, true, false>(q, grid, lds, st);
+                    else launch_region_t<RS, SUB, TILE, true, true, false, false>(q, grid, lds, st);
+                    return;
+                }
             }
-            q.bins = e.buf;
-            ++g_bin_count[1];
-            return -1;
+            if (p.fold) launch_region_t<RS, SUB, TILE, true, true, true>(q, grid, lds, st);
+            else launch_region_t<RS, SUB, TILE, true, true>(q, grid, lds, st);
+            return;
         }
+        if (p.runs) { launch_region_t<RS, SUB, TILE, true, false>(q, grid, lds, st); return; }
     }
-    if (!whole) { ++g_bin_count[2]; return -1; }                  // entries are recorded by whole-level launches only
-    const size_t tiles_e = (size_t)((a.size + tile - 1) / tile);
-    BinEntry e = {dev, flavour, a.n_src, a.size, a.n_tab, bt->ptr, bt->gen, nullptr, 6 * tiles_e * tiles_e * mc_bin_tile_words(q.NR, q.NW) * 4, nullptr, false};
-    if (held + e.bytes > g_bin_budget) { ++g_bin_count[3]; ++g_bin_count[2]; return -1; }
-    if (hipMalloc(&e.buf, e.bytes) != hipSuccess) { (void)hipGetLastError(); ++g_bin_count[3]; ++g_bin_count[2]; return -1; }
-    if (hipEventCreateWithFlags(&e.ready, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(e.buf); ++g_bin_count[2]; return -1; }
-    g_bin_entries.push_back(e);
-    q.bins_out = e.buf;
-    ++g_bin_count[0];
-    return (int)g_bin_entries.size() - 1;
-}
-// behind the recording launch: what a replay on another stream waits for.  Without the event the entry cannot be trusted: it goes.
-static void bin_recorded(int entry, hipStream_t st) {
-    if (entry < 0) return;
-    if (hipEventRecord(g_bin_entries[(size_t)entry].ready, st) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(st);
-        bin_entry_free(g_bin_entries[(size_t)entry]);
-        g_bin_entries.erase(g_bin_entries.begin() + entry);
-    }
+    if (p.lean) launch_region_t<RS, SUB, TILE, false, true>(q, grid, lds, st);
+    else launch_region_t<RS, SUB, TILE, false, false>(q, grid, lds, st);
 }
 
-// ---- header 2n: the recorded flags made exact, once, behind the recording launch ----
-static int g_exact_mode = -1;
-static int g_last_exact = 0;                                    // whether the last recording launch was followed by k_mc_refine_bins
-static unsigned long long* g_exact_stats[PREP_MAX_DEVICES];     // RefineArgs::out, one per device
-extern "C" void pbrk_mc_set_exact_bins(int mode) { g_exact_mode = mode < 0 ? -1 : (mode ? 1 : 0); }
-extern "C" int pbrk_mc_last_exact_bins(void) { return g_last_exact; }
-extern "C" int pbrk_mc_exact_bins_stats(unsigned long long* out8, int reset) {
-    if (!out8) return PBRK_E_ARG;
-    std::lock_guard<std::mutex> hold(g_bin_lock);
-    for (int i = 0; i < 8; ++i) out8[i] = 0;
-    for (int d = 0; d < PREP_MAX_DEVICES; ++d) {
-        if (!g_exact_stats[d]) continue;
-        unsigned long long v[8];
-        if (hipMemcpy(v, g_exact_stats[d], sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return PBRK_E_LAUNCH;
-        for (int i = 0; i < 8; ++i) out8[i] += v[i];
-        if (reset && hipMemset(g_exact_stats[d], 0, sizeof v) != hipSuccess) return PBRK_E_LAUNCH;
-    }
-    return PBRK_OK;
-}
-
-template <int RS, bool SUB, int TILE>
-static void launch_refine_t(const RefineArgs& g, bool fold, unsigned grid, size_t lds, hipStream_t st) {
-    if (fold) hipLaunchKernelGGL((k_mc_refine_bins<RS, SUB, TILE, true>), dim3(grid), dim3(1024), lds, st, g);
-    else hipLaunchKernelGGL((k_mc_refine_bins<RS, SUB, TILE, false>), dim3(grid), dim3(1024), lds, st, g);
-}
-
-// Which kernel shapes have their recorded flags refined under the default rule: decided per shape by measurement (profiles/exact_bins.md;
-// a shape is in when its replaying kernel, levels one after another, falls by more than five times the larger sigma of its two rows).
-//   <34, false, 16> (C4 mip 3): 10.77 -> 10.13 ms, sigma 0.09: in.
-//   <66, true, 32>  (C4 mip 1):  7.15 ->  6.70 ms, sigma 0.17: a fall of 2.6 sigma, out.
-//   <66, false, 16> (C4 mip 2): 21.32 -> 21.25 ms, sigma 0.29: out.
-//   <66, true, 16>: on no level of the measured job; out.
-// pbrk_mc_set_exact_bins(1) refines every shape (tests, A-B runs).
-static bool exact_shape(int RS, int G, int tile) {
-    (void)G; (void)tile;
-    return RS == 34;
-}
-
-// Behind the recording launch of entry `entry` (bin_plan's return; < 0: this launch records nothing) on its stream, ahead of the event
-// replays wait for.  g_bin_lock is held.  q: the recording launch's arguments -- a whole-level dispatch.
-static void bin_refine(int entry, const RegArgs& q, int RS, int tile, hipStream_t st) {
-    if (entry < 0) return;
-    g_last_exact = 0;
-    int mode = g_exact_mode;
-    if (mode < 0) { static int env = -2; if (env == -2) { const char* e = getenv("PBR_MC_EXACT_BINS"); env = e ? (atoi(e) ? 1 : 0) : -1; } mode = env; }
-    if (!(mode < 0 ? q.stats == nullptr && exact_shape(RS, q.G, tile) : mode != 0)) return;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= PREP_MAX_DEVICES) { (void)hipGetLastError(); return; }
-    if (!g_exact_stats[dev]) {
-        if (hipMalloc(&g_exact_stats[dev], 64) != hipSuccess) { (void)hipGetLastError(); g_exact_stats[dev] = nullptr; return; }
-        (void)hipMemset(g_exact_stats[dev], 0, 64);
-    }
+// Behind a recording launch (t.entry >= 0) on its stream, ahead of the event replays wait for; the token holds the cache's lock.
+// q: the recording launch's arguments -- a whole-level dispatch.  FOLD: the flavour the replays will take.  Returns whether it ran.
+static bool launch_refine(const McPlan& p, const RegArgs& q, const McBinToken& t, hipStream_t st) {
+    if (t.entry < 0 || !p.refine) return false;
     RefineArgs g;
     g.a = q.a;
     g.G = q.G; g.RC = q.RC; g.NR = q.NR; g.NW = q.NW;
-    g.bins = g_bin_entries[(size_t)entry].buf;
-    g.out = g_exact_stats[dev];
-    const size_t lds = ((size_t)3 * q.NR * q.NW + 2 * (size_t)q.NW + 8) * 4;
-    if (lds > 64 * 1024) return;
+    g.bins = t.record;
+    g.out = mc_bins_refine_stats(t);
+    if (!g.out) return false;
     const unsigned grid = (unsigned)(6 * q.a.tiles_x * q.a.tiles_x);
-    const int n = q.a.n_src;
-    const bool fold = g_mc_fold && (n & (n - 1)) == 0;              // launch_runs' rule: the flavour the replays will take
-    if (tile == 32) launch_refine_t<66, true, 32>(g, fold, grid, lds, st);
-    else if (RS == 34) launch_refine_t<34, false, 16>(g, fold, grid, lds, st);
-    else if (q.G == 1) launch_refine_t<66, false, 16>(g, fold, grid, lds, st);
-    else launch_refine_t<66, true, 16>(g, fold, grid, lds, st);
-    g_last_exact = 1;
-}
-
-bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
-    if (g_mc_region_mode < 0) { const char* e = getenv("PBR_MC_REGION"); g_mc_region_mode = e ? atoi(e) : 1; }
-    if (!g_mc_region_mode) return false;
-    // shape conditions (level only): source too big for LDS as a whole, enough 16x16 tiles to fill the chip twice over
-    if (a.n_src < 16 || a.size < 256 || a.n_tab < 1 || a.n_tab > 8192) return false;
-    RegArgs q;
-    q.a = a;
-    int RS;
-    if (a.n_src <= 16) { RS = 18; q.G = 1; q.RC = a.n_src + 1; }
-    else if (a.n_src <= 32) { RS = 34; q.G = 1; q.RC = a.n_src + 1; }
-    else if (a.n_src <= 64) { RS = 66; q.G = 1; q.RC = a.n_src + 1; }
-    else { RS = 66; q.RC = 65; q.G = (a.n_src + 1 + 64) / 65; }
-    q.NR = 6 * q.G * q.G;
-    q.NW = (a.n_tab + 31) / 32;
-    // the LDS layout at the top of k_mc_region: counters, region flags, any[], dmax, proved-sample flags, (absorb) wmax[], rmax[]; where the last two do not fit, the level runs
-    // without them.  The absorbed-word skip is compiled for the 66^2 shapes only (k_mc_region, ABS).
-    q.absorb = RS == 66 ? g_mc_absorb : 0;
-    const size_t lds_fixed = (size_t)RS * RS * 16 + (4 + (size_t)q.NR * q.NW + q.NR + 1 + q.NW) * 4;
-    size_t lds = lds_fixed + (q.absorb ? (size_t)(q.NW + q.NR) * 4 : 0);
-    if (lds > 80 * 1024) { q.absorb = 0; lds = lds_fixed; }
-    if (lds < (size_t)1024 * 3 * 4) lds = (size_t)1024 * 3 * 4;      // the slices' partial sums (REG_S * REG_TX = 1024 texel-slices, whatever the tile)
-    if (lds > 80 * 1024) return false;                             // two workgroups per CU or not at all
-    q.stats = reg_stats();
-    // Tile size: 16 x 16 output texels x 4 slices of the sample table, but for the quarter-face level with a short table and a big
-    // output (mc_tile32: header 2h), which takes 32 x 32 texels x 1 slice.  Measured and dropped: 8 x 8 tiles x 16
-    // slices (halve the frame spread, pay four times the per-tile work: C4 mip 2 44.0 -> 53.5 ms), 32 x 16 tiles, and 32 x 32 tiles on
-    // the whole-face and the small shapes (no gain on the big levels, losses on the small ones).
-    const int tile = mc_tile32(a.n_src, a.n_tab, a.size) ? 32 : 16, nslices = 1024 / (tile * tile);
-    for (int s = 0; s < REG_MAX_S; ++s) q.expect[s] = 0;
-    for (int w = 0; w < q.NW; ++w) { int c = a.n_tab - w * 32; q.expect[w % nslices] += c > 32 ? 32 : c; }
-    q.a.tiles_x = (a.size + tile - 1) / tile;
-    const int tiles_y = (a.rows + tile - 1) / tile;
-    q.a.tiles_per_face = q.a.tiles_x * tiles_y;                            // tiles start at the dispatch's first row, whatever it is
-    mc_pole_rows(a.size, a.y0, tile, tiles_y, q.pole_row);
-    const unsigned grid = (unsigned)(q.a.tiles_per_face * nfaces);
-    // Lean prologue: the maxima of the absorbed-word test come from k_mc_prep, once per launch, instead of from every tile.  Without
-    // a scratch slot (see prep_acquire) the launch takes the prologue that builds them itself: the same bytes.
-    bool lean = g_mc_lean != 0;
-    q.tabmax = nullptr;
-    q.cut = 0;
-    g_last_cut = nullptr; g_last_cut_nw = q.NW; g_last_cut_s = nslices;
-    // header 2m: the launches that take a lean run loop (launch_runs) may record or replay their binning
-    const bool bin_shape = RS != 18 && g_mc_runs && q.NW <= 64 * nslices;
-    const bool bin_window = mc_bin_window_ok(a.size, tile, a.y0, a.y0 + a.rows);
-    const bool bin_whole = a.face0 == 0 && nfaces == 6 && a.y0 == 0 && a.rows == a.size;
-    const int bin_flavour = (RS << 8) | tile;
-    std::lock_guard<std::mutex> hold_bins(g_bin_lock);
-    if (lean && q.absorb) {
-        std::lock_guard<std::mutex> hold(g_prep_lock);
-        int slot = -1;
-        unsigned* scratch = q.NW + 2 * q.NR + 8 <= PREP_SLOT_WORDS ? prep_acquire(st, &slot) : nullptr;
-        if (!scratch) lean = false;
-        else {
-            int dev = 0; (void)hipGetDevice(&dev);
-            q.tabmax = scratch;
-            hipLaunchKernelGGL(k_mc_prep, dim3((unsigned)(q.NR + (q.NW + 255) / 256)), dim3(256), 0, st, a.src, a.n_src, q.G, q.RC, q.NR, a.tab, a.n_tab, q.NW, scratch);
-            // header 2g: the shapes that run their head words first drop the words k_mc_cut proves to be no-ops for the whole launch
-            const bool head_first = RS == 66 && (q.G == 1 ? MC_HEAD_FIRST_G1 != 0 : MC_HEAD_FIRST_SUB != 0);
-            if (head_first && g_mc_launch_cut && q.NW > nslices) {
-                hipLaunchKernelGGL(k_mc_cut, dim3(1), dim3(64), 0, st, a.tab, a.n_tab, q.NW, q.NR, nslices, scratch);
-                q.cut = 3;
-                g_last_cut = scratch + q.NW + q.NR;
-            }
-            const int rec = bin_plan(q, bin_flavour, bin_shape && bin_window, bin_whole, tile, st);
-            launch_shape<true>(RS, tile, q, grid, lds, st);
-            bin_refine(rec, q, RS, tile, st);
-            bin_recorded(rec, st);
-            if (hipEventRecord(g_prep[dev].ev[slot], st) == hipSuccess) g_prep[dev].used[slot] = true;
-            return true;
+    const size_t lds = mc_refine_lds(p.NR, p.NW);
+    mc_for_shape(p.RS, p.G, p.tile, [&](auto sh) {
+        using SH = decltype(sh);
+        if constexpr (SH::HAS_RUNS) {                               // the 18^2 shape never records
+            if (p.fold) hipLaunchKernelGGL((k_mc_refine_bins<SH::RS, SH::SUB, SH::TILE, true>), dim3(grid), dim3(1024), lds, st, g);
+            else hipLaunchKernelGGL((k_mc_refine_bins<SH::RS, SH::SUB, SH::TILE, false>), dim3(grid), dim3(1024), lds, st, g);
         }
-    }
-    // the 66^2 shapes without a k_mc_prep slot bin as ever; the 34^2 shape never takes one
-    const int rec = bin_plan(q, bin_flavour, lean && RS == 34 && bin_shape && bin_window, bin_whole, tile, st);
-    if (lean) launch_shape<true>(RS, tile, q, grid, lds, st);
-    else launch_shape<false>(RS, tile, q, grid, lds, st);
-    bin_refine(rec, q, RS, tile, st);
-    bin_recorded(rec, st);
+    });
     return true;
 }
 
-// ---- header 2k: levels up to 16^2 with outputs of 256^2 and more stay resident in LDS ----
-// pbrk_mc_set_resident(0): such a level runs the kernel it ran before (n_src = 16: k_mc_region<18, ..>; smaller: the level-in-LDS kernel)
-// (-1: the environment variable PBR_MC_RESIDENT, else the default 1, as for pbrk_mc_set_kernels)
-#ifndef MC_RESIDENT_TILE8
-#define MC_RESIDENT_TILE8 1                            // outputs of 128^2 .. 255^2 take 8 x 8 tiles x 16 slices; 0: they keep the level-in-LDS kernel
-#endif
-static int g_mc_resident = -1;
-extern "C" void pbrk_mc_set_resident(int on) { g_mc_resident = on < 0 ? -1 : (on ? 1 : 0); }
-// PBR_MC_STATS=1, since the last reset: {(lane, sample) pairs whose proof did not hold (must stay 0), proved samples summed over
-// tiles, pairs taken by the proved runs, pairs taken by the general pass}
-extern "C" int pbrk_mc_resident_stats(unsigned long long* out4) { return read_stats(out4, 16, 4); }
+// RegArgs from the plan: the fields both families fill.  tiles_y tile rows from row y0 of the face.
+static void fill_args(RegArgs& q, const McArgs& a, const McPlan& p, int y0, int rows, int tiles_y) {
+    q.a = a;
+    q.G = p.G; q.RC = p.RC; q.NR = p.NR; q.NW = p.NW;
+    for (int s = 0; s < REG_MAX_S; ++s) q.expect[s] = p.expect[s];
+    q.tabmax = nullptr; q.cut = 0; q.absorb = p.absorb;
+    q.stats = reg_stats();
+    q.a.y0 = y0; q.a.rows = rows;
+    q.a.tiles_x = (a.size + p.tile - 1) / p.tile;
+    q.a.tiles_per_face = q.a.tiles_x * tiles_y;
+    mc_pole_rows(a.size, y0, p.tile, tiles_y, q.pole_row);
+}
+
+// plan; prep and bin resources; arguments; launch.  The cache's lock is held from ahead of k_mc_prep until the launch, its refine pass and
+// its event are enqueued; the prep ring's from the slot's acquisition until the event behind its reader.
+bool launch_mc_region(McArgs a, int nfaces, hipStream_t st) {
+    const McSwitches sw = mc_switches();
+    const bool counters = reg_stats() != nullptr;
+    McPlan p = mc_plan(sw, a.n_src, a.n_tab, a.size, a.face0, nfaces, a.y0, a.rows, counters, true);
+    if (p.family != MC_REGION) return false;
+    McBinToken bins = mc_bins_begin();
+    McPrepSlot prep;
+    if (p.prep) {
+        prep = mc_prep_acquire(st);
+        // no slot (see prep_acquire): the launch takes the prologue that builds the maxima itself -- the same bytes
+        if (!prep.words) p = mc_plan(sw, a.n_src, a.n_tab, a.size, a.face0, nfaces, a.y0, a.rows, counters, false);
+    }
+    RegArgs q;
+    fill_args(q, a, p, a.y0, a.rows, (a.rows + p.tile - 1) / p.tile);         // tiles start at the dispatch's first row, whatever it is
+    g_mc_last.plan = p; g_mc_last.cut = nullptr;
+    if (p.prep) {
+        mc_prep_launch(prep, a, p, st);
+        q.tabmax = prep.words;
+        if (p.cut) { q.cut = 3; g_mc_last.cut = prep.words + p.NW + p.NR; }
+    }
+    mc_bins_plan(bins, a, p, st);
+    q.bins = bins.replay; q.bins_out = bins.record;
+    const unsigned grid = (unsigned)(q.a.tiles_per_face * nfaces);
+    mc_for_shape(p.RS, p.G, p.tile, [&](auto sh) { launch_region_shape<decltype(sh)>(p, q, grid, st); });
+    if (bins.entry >= 0) g_mc_last.refined = launch_refine(p, q, bins, st) ? 1 : 0;
+    mc_bins_end(bins, st);
+    mc_prep_release(prep, st);
+    return true;
+}
 
 template <int TILE, bool FOLD, bool STATS>
 static void launch_resident_t(const ResArgs& g, unsigned grid, size_t lds, hipStream_t st) {
@@ -2034,40 +1561,24 @@ static void launch_resident_tile(const ResArgs& g, bool fold, unsigned grid, siz
     else { if (fold) launch_resident_t<TILE, true, false>(g, grid, lds, st); else launch_resident_t<TILE, false, false>(g, grid, lds, st); }
 }
 
-// The rule reads the level alone -- n_src, n_tab, the output size -- and the tiles are anchored at row 0 of the face, not at the
-// dispatch's first row: a texel sits in the same tile, with the same proof and the same order of its sum, in every dispatch that holds
-// it, so a row shard equals the full dispatch bit for bit.  A dispatch that starts or ends inside a tile computes the whole tile and
-// stores its own rows.
+// The tiles are anchored at row 0 of the face, not at the dispatch's first row: a texel sits in the same tile, with the same proof and the
+// same order of its sum, in every dispatch that holds it, so a row shard equals the full dispatch bit for bit.  A dispatch that starts or
+// ends inside a tile computes the whole tile and stores its own rows.
 bool launch_mc_resident(McArgs a, int nfaces, hipStream_t st) {
-    if (g_mc_region_mode < 0) { const char* e = getenv("PBR_MC_REGION"); g_mc_region_mode = e ? atoi(e) : 1; }
-    if (g_mc_resident < 0) { const char* e = getenv("PBR_MC_RESIDENT"); g_mc_resident = e ? (atoi(e) ? 1 : 0) : 1; }
-    if (!g_mc_region_mode || !g_mc_resident) return false;
-    if (a.n_src > 16 || a.size < (MC_RESIDENT_TILE8 ? 128 : 256) || a.n_tab < 1 || a.n_tab > 8192) return false;
+    const McPlan p = mc_plan(mc_switches(), a.n_src, a.n_tab, a.size, a.face0, nfaces, a.y0, a.rows, reg_stats() != nullptr, true);
+    if (p.family != MC_RESIDENT) return false;
+    McBinToken bins = mc_bins_begin();
     ResArgs g;
     RegArgs& q = g.q;
-    q.a = a;
-    q.G = 1; q.RC = a.n_src + 1; q.NR = 6;
-    q.NW = (a.n_tab + 31) / 32;
-    for (int s = 0; s < REG_MAX_S; ++s) q.expect[s] = 0;
-    q.tabmax = nullptr; q.cut = 0; q.absorb = 0;
-    q.stats = reg_stats();
-    // the LDS layout at the top of k_mc_resident; the slices' partial sums overlay the level (12 KB of its 30)
-    const size_t lds = (size_t)6 * RES_FACE_BYTES + ((size_t)6 * q.NW + 6 + 1 + q.NW) * 4;
-    const int tile = a.size >= 256 ? 16 : 8, ty0 = a.y0 / tile, ty1 = (a.y0 + a.rows - 1) / tile, tiles_y = ty1 - ty0 + 1;
+    const int tile = p.tile, ty0 = a.y0 / tile, ty1 = (a.y0 + a.rows - 1) / tile;
     g.ys = a.y0; g.ye = a.y0 + a.rows;
-    q.a.y0 = ty0 * tile;
-    q.a.rows = ((ty1 + 1) * tile < a.size ? (ty1 + 1) * tile : a.size) - q.a.y0;
-    q.a.tiles_x = (a.size + tile - 1) / tile;
-    q.a.tiles_per_face = q.a.tiles_x * tiles_y;
-    mc_pole_rows(a.size, q.a.y0, tile, tiles_y, q.pole_row);
+    fill_args(q, a, p, ty0 * tile, ((ty1 + 1) * tile < a.size ? (ty1 + 1) * tile : a.size) - ty0 * tile, ty1 - ty0 + 1);
+    // header 2m: every dispatch may replay; a whole-level one records
+    mc_bins_plan(bins, a, p, st);
+    q.bins = bins.replay; q.bins_out = bins.record;
     const unsigned grid = (unsigned)(q.a.tiles_per_face * nfaces);
-    // FOLD as in launch_runs: from n_src alone
-    const bool fold = g_mc_fold && (a.n_src & (a.n_src - 1)) == 0;
-    // header 2m: the tiles are anchored at row 0 of the face, so every dispatch may replay; a whole-level one records
-    std::lock_guard<std::mutex> hold_bins(g_bin_lock);
-    const int rec = bin_plan(q, (1 << 16) | tile, true, a.face0 == 0 && nfaces == 6 && a.y0 == 0 && a.rows == a.size, tile, st);
-    if (tile == 16) launch_resident_tile<16>(g, fold, grid, lds, st);
-    else launch_resident_tile<8>(g, fold, grid, lds, st);
-    bin_recorded(rec, st);
+    if (tile == 16) launch_resident_tile<16>(g, p.fold != 0, grid, (size_t)p.lds, st);
+    else launch_resident_tile<8>(g, p.fold != 0, grid, (size_t)p.lds, st);
+    mc_bins_end(bins, st);
     return true;
 }

@@ -332,6 +332,7 @@ PROTOTYPES = {
     "pbrk_mc_bin_cache_stats": (None, [C.POINTER(C.c_uint64)]),
     "pbrk_mc_set_exact_bins": (None, [C.c_int]), "pbrk_mc_last_exact_bins": (C.c_int, []),
     "pbrk_mc_exact_bins_stats": (C.c_int, [C.POINTER(C.c_uint64), C.c_int]),
+    "pbrk_mc_plan": (C.c_int, [C.c_int] * 9 + [VP]),
     "pbrk_mc_tile_of_block": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "pbrk_mc_bin_window_eligible": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "pbrk_lut_cells_build": (C.c_int, [VP, C.c_int, VP, VP]),

@@ -79,6 +79,42 @@ def exact_bins_stats(L, reset=False):
     return dict(zip(EXACT_BINS_KEYS, (int(v) for v in buf)))
 
 
+PLAN_FIELDS = ("family", "RS", "G", "RC", "NR", "NW", "tile", "nslices", "runs", "lean", "fold", "net", "absorb", "head_first", "prep", "cut",
+               "stats", "bin_cache", "bin_eligible", "whole", "refine", "bin_flavour", "lds", "lds_slices", "direct_slices")
+PLAN_FAMILIES = ("declined", "region", "resident")
+
+
+class PbrkMcPlan(C.Structure):
+    _fields_ = [(name, C.c_int) for name in PLAN_FIELDS] + [("expect", C.c_int * 16)]
+
+
+def _targs(*values):
+    return "<" + ", ".join(str(v).lower() if isinstance(v, bool) else str(v) for v in values) + ">"
+
+
+def plan(L, n_src, n_tab, size, window=None, counters=False, have_prep=True):
+    """pbrk_mc_plan by name, for the library's switches as they stand: what one pbrk_mc_filter dispatch of the window (face0, face1, y0,
+    rows; default: the whole level) would decide.  Touches no GPU.  Besides the struct's fields: "family" by name, "kernel" -- the region,
+    resident, level-in-LDS or direct instantiation (without cells, sampler snap off) as a demangled kernel name spells it --, and
+    "refine_kernel", the k_mc_refine_bins instantiation that follows the launch IF it records (plan["refine"])."""
+    f0, f1, y0, rows = window or (0, 6, 0, size)
+    raw = PbrkMcPlan()
+    rc = L.pbrk_mc_plan(n_src, n_tab, size, f0, f1 - f0, y0, rows, int(counters), int(have_prep), C.byref(raw))
+    assert rc == 0, f"pbrk_mc_plan returned {rc}"
+    p = {name: getattr(raw, name) for name in PLAN_FIELDS}
+    p["expect"] = list(raw.expect)
+    p["family"] = PLAN_FAMILIES[raw.family]
+    sub = raw.tile == 32 or raw.G > 1
+    p["refine_kernel"] = None
+    p["kernel"] = "k_mc_filter_lds" + _targs(raw.lds_slices) if raw.lds_slices else "k_mc_filter" + _targs(raw.direct_slices, 4, False, False)
+    if p["family"] == "region":
+        p["kernel"] = "k_mc_region" + _targs(raw.RS, sub, raw.tile, bool(raw.runs), bool(raw.lean), bool(raw.fold), bool(raw.net))
+        p["refine_kernel"] = "k_mc_refine_bins" + _targs(raw.RS, sub, raw.tile, bool(raw.fold))
+    elif p["family"] == "resident":
+        p["kernel"] = "k_mc_resident" + _targs(raw.tile, bool(raw.fold), bool(raw.stats))
+    return p
+
+
 def reset_counters(L):
     """Zero every counter.  The return code is ignored: the counters exist only after the kernel's first launch."""
     L.pbrk_mc_region_stats((C.c_uint64 * 2)(), 1)
