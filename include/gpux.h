@@ -98,7 +98,8 @@ GPU_API void* GPUX_GraphStream(GPU_Graph* graph);                               
 GPU_API GPU_Texture* GPUX_MakeTextureExternal(GPU_Format format, uint32_t width, uint32_t height, uint32_t depth, GPU_TextureFlags flags,
                                               void* device_memory, uint64_t device_bytes);
 /* Tell the backend that the texture's memory was written behind its back (RCCL receive, torch, any other library working on
- * GPUX_TextureDevicePtr / external memory): the lazily built sampler twins (apron, cells) are rebuilt before the next use. */
+ * GPUX_TextureDevicePtr / external memory): everything built lazily from the texture (apron, cells of every level, LUT cells, the
+ * per-level range of GPUX_SetPrefilterTolerance) is dropped, exactly as after an op that writes it, and rebuilt before the next use. */
 GPU_API void GPUX_InvalidateTexture(GPU_Texture* texture);
 GPU_API uint64_t GPUX_TextureTotalBytes(const GPU_Texture* texture);
 GPU_API uint64_t GPUX_TextureMipOffset(const GPU_Texture* texture, uint32_t mip_level);

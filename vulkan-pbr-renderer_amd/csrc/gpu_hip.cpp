@@ -66,20 +66,30 @@ struct TextureImpl {
     size_t bytes = 0;
     std::vector<size_t> mip_offset;   // bytes
     uint32_t texel_bytes = 0;
-    void* bordered = nullptr;         // bordered pyramid twin (RGBA32F cubes only), built on demand
-    size_t bordered_bytes = 0;
-    bool bordered_valid = false;                   // apron twin valid for levels >= bordered_from
-    int bordered_from = 0;
     bool owns_memory = true;          // false: GPUX_MakeTextureExternal (caller-owned HBM, e.g. a torch tensor)
     // BC1 / BC3 / BC5 2-D textures (K15): `dev` keeps the compressed blocks; `decoded` is what the draws sample -- RGBA8UN, all levels
-    // back to back like an RGBA8UN texture of the same extents; a level is decoded when it is written
+    // back to back like an RGBA8UN texture of the same extents.  Not lazily invalidated: exec_copy decodes a level when it is written
     void* decoded = nullptr; std::vector<size_t> decoded_offset;
-    // 2x2-footprint "cells" twin of the levels with n <= 512 (levels cells_first.., back to back), built per level on demand
-    void* cells = nullptr; int cells_first = 0; std::vector<size_t> cells_off; std::vector<char> cells_valid;
-    void* lut_cells = nullptr; bool lut_cells_valid = false;      // RG16F 2-D textures sampled by the shade pass
-    // {min, max} of a level's RGB values (GPUX_SetPrefilterTolerance), measured on demand; dropped with the cells twin
-    std::vector<char> range_valid; std::vector<float> range_min, range_max; void* range_dev = nullptr;
+    // What the hot kernels sample in place of `dev`: built on demand (ensure_*, level_range), each part by its own flag alone;
+    // marked stale by texture_written() only -- all of it, after every op that writes the texture (exec_op); freed by free_derived()
+    struct Derived {
+        // bordered pyramid twin (RGBA32F cubes only), the seamless-filter apron: valid for levels >= bordered_from
+        void* bordered = nullptr; bool bordered_valid{}; int bordered_from = 0;
+        // 2x2-footprint "cells" twin of the levels with n <= 512 (levels cells_first.., back to back), built per level from the apron
+        void* cells = nullptr; int cells_first = 0; std::vector<size_t> cells_off; std::vector<char> cells_valid;
+        void* lut_cells = nullptr; bool lut_cells_valid{};          // RG16F 2-D textures sampled by the shade pass
+        std::vector<char> range_valid; std::vector<float> range_min, range_max; void* range_dev = nullptr;   // {min, max} of a level's RGB values (level_range)
+    } derived;
 };
+static void texture_written(TextureImpl* t) {
+    TextureImpl::Derived& d = t->derived;
+    d.bordered_valid = false; d.lut_cells_valid = false;
+    std::fill(d.cells_valid.begin(), d.cells_valid.end(), 0); std::fill(d.range_valid.begin(), d.range_valid.end(), 0);
+}
+static void free_derived(TextureImpl* t) {
+    for (void* p : {t->derived.bordered, t->derived.cells, t->derived.lut_cells, t->derived.range_dev}) (void)hipFree(p);   // NULL: a no-op
+    t->derived = TextureImpl::Derived();
+}
 struct BufferImpl {
     GPU_Buffer base;
     void* dev = nullptr;              // device-visible pointer (== base.data for CPU buffers)
@@ -572,10 +582,7 @@ GPU_API void GPU_DestroyTexture(GPU_Texture* tex) {
     if (!tex) return;
     TextureImpl* t = (TextureImpl*)tex;
     if (t->owns_memory) (void)hipFree(t->dev);
-    if (t->bordered) (void)hipFree(t->bordered);
-    if (t->cells) (void)hipFree(t->cells);
-    if (t->range_dev) (void)hipFree(t->range_dev);
-    if (t->lut_cells) (void)hipFree(t->lut_cells);
+    free_derived(t);
     if (t->decoded) (void)hipFree(t->decoded);
     delete t;
 }
@@ -615,9 +622,7 @@ GPU_API void* GPUX_TextureDevicePtr(GPU_Texture* tex, uint32_t mip) {
 }
 GPU_API void GPUX_InvalidateTexture(GPU_Texture* tex) {
     GPU_REQUIRE_V(tex, "GPUX_InvalidateTexture: NULL texture");
-    TextureImpl* t = (TextureImpl*)tex;
-    t->bordered_valid = false; t->lut_cells_valid = false;          // ensure_bordered() drops the cells twin with the apron
-    for (char& v : t->cells_valid) v = 0;
+    texture_written((TextureImpl*)tex);
 }
 GPU_API void* GPUX_BufferDevicePtr(GPU_Buffer* buf) { return buf ? ((BufferImpl*)buf)->dev : nullptr; }
 
@@ -1102,8 +1107,6 @@ static void exec_raster(GPU_Graph* g, Op& op, size_t& ev_used) {
             int rc = rk.launch(op, rs, g->cur, stage);
             if (rc != PBRK_OK) gpu_fail("%s %s launch failed (%d)", rk.tag, stage == 0 ? "setup" : "tile", rc);
         });
-    for (const GPU_TextureView& tv : op.pass->targets) { ((TextureImpl*)tv.texture)->bordered_valid = false; ((TextureImpl*)tv.texture)->lut_cells_valid = false; }
-    op.tex->bordered_valid = false;
 }
 
 GPU_API GPU_GraphicsPipeline* GPU_MakeGraphicsPipeline(const GPU_GraphicsPipelineDesc* desc) {
@@ -1764,38 +1767,39 @@ static bool ensure_bordered(TextureImpl* t, hipStream_t st, int first_level = 0)
     int W = (int)t->base.width, levels = (int)t->base.mip_level_count;
     if (first_level < 0) first_level = 0;
     if (first_level > levels - 1) first_level = levels - 1;
-    if (t->bordered_valid && t->bordered_from <= first_level) return true;
-    if (!t->bordered) {
-        t->bordered_bytes = pbrk_bordered_pyramid_texels(W, levels) * 16;
-        hipError_t e = hipMalloc(&t->bordered, t->bordered_bytes);
-        if (e != hipSuccess) { gpu_fail("bordered twin allocation (%zu bytes) failed: %s", t->bordered_bytes, hipGetErrorString(e)); return false; }
+    TextureImpl::Derived& d = t->derived;
+    if (d.bordered_valid && d.bordered_from <= first_level) return true;
+    if (!d.bordered) {
+        const size_t bytes = pbrk_bordered_pyramid_texels(W, levels) * 16;
+        hipError_t e = hipMalloc(&d.bordered, bytes);
+        if (e != hipSuccess) { gpu_fail("bordered twin allocation (%zu bytes) failed: %s", bytes, hipGetErrorString(e)); return false; }
     }
-    // only the levels somebody samples get an apron: the precompute never touches level 0 of its source (400 MB at 2048^2)
-    int end = t->bordered_valid ? t->bordered_from : levels;
-    if (!t->bordered_valid) { for (char& v : t->cells_valid) v = 0; for (char& v : t->range_valid) v = 0; }
-    int rc = pbrk_border_build_range(t->dev, t->bordered, W, levels, first_level, end, st);
+    // only the levels somebody samples get an apron (the precompute never touches level 0 of its source: 400 MB at 2048^2); a valid one is only extended
+    int end = d.bordered_valid ? d.bordered_from : levels;
+    int rc = pbrk_border_build_range(t->dev, d.bordered, W, levels, first_level, end, st);
     if (rc != PBRK_OK) { gpu_fail("border build failed (%d)", rc); return false; }
-    t->bordered_valid = true; t->bordered_from = first_level;
+    d.bordered_valid = true; d.bordered_from = first_level;
     return true;
 }
 
 // {min, max} of the RGB values of level l (blocking: one reduction + an 8-byte read-back per level and content change)
 static bool level_range(TextureImpl* t, int l, hipStream_t st, float* mn, float* mx) {
     const int levels = (int)t->base.mip_level_count;
-    if (t->range_valid.empty()) { t->range_valid.assign((size_t)levels, 0); t->range_min.assign((size_t)levels, 0.0f); t->range_max.assign((size_t)levels, 0.0f); }
-    if (!t->range_valid[(size_t)l]) {
-        if (!t->range_dev && hipMalloc(&t->range_dev, 8) != hipSuccess) { t->range_dev = nullptr; return false; }
+    TextureImpl::Derived& d = t->derived;
+    if (d.range_valid.empty()) { d.range_valid.assign((size_t)levels, 0); d.range_min.assign((size_t)levels, 0.0f); d.range_max.assign((size_t)levels, 0.0f); }
+    if (!d.range_valid[(size_t)l]) {
+        if (!d.range_dev && hipMalloc(&d.range_dev, 8) != hipSuccess) { d.range_dev = nullptr; return false; }
         const unsigned init[2] = {0x7F800000u, 0u};
         unsigned got[2] = {0, 0};
-        HIP_OK(hipMemcpyAsync(t->range_dev, init, 8, hipMemcpyHostToDevice, st));
+        HIP_OK(hipMemcpyAsync(d.range_dev, init, 8, hipMemcpyHostToDevice, st));
         const size_t n = mip_dim(t->base.width, (uint32_t)l);
-        if (pbrk_level_minmax((const char*)t->dev + t->mip_offset[(size_t)l], 6 * n * n, t->range_dev, st) != PBRK_OK) return false;
-        HIP_OK(hipMemcpyAsync(got, t->range_dev, 8, hipMemcpyDeviceToHost, st));
+        if (pbrk_level_minmax((const char*)t->dev + t->mip_offset[(size_t)l], 6 * n * n, d.range_dev, st) != PBRK_OK) return false;
+        HIP_OK(hipMemcpyAsync(got, d.range_dev, 8, hipMemcpyDeviceToHost, st));
         HIP_OK(hipStreamSynchronize(st));
-        memcpy(&t->range_min[(size_t)l], &got[0], 4); memcpy(&t->range_max[(size_t)l], &got[1], 4);
-        t->range_valid[(size_t)l] = 1;
+        memcpy(&d.range_min[(size_t)l], &got[0], 4); memcpy(&d.range_max[(size_t)l], &got[1], 4);
+        d.range_valid[(size_t)l] = 1;
     }
-    *mn = t->range_min[(size_t)l]; *mx = t->range_max[(size_t)l];
+    *mn = d.range_min[(size_t)l]; *mx = d.range_max[(size_t)l];
     return true;
 }
 // Samples a prefilter dispatch keeps under GPUX_SetPrefilterTolerance(rel): the smallest prefix K of the weight table (weights fall
@@ -1821,33 +1825,36 @@ static int bounded_sample_count(const DeviceTable* tab, float mn, float mx, floa
 // cells twin of one level (needs a valid bordered twin); NULL when the level is too big to be worth it (n > 512)
 static void* ensure_cells(TextureImpl* t, int level, hipStream_t st) {
     int W = (int)t->base.width, levels = (int)t->base.mip_level_count;
-    if (t->cells_off.empty()) {
+    TextureImpl::Derived& d = t->derived;
+    if (d.cells_off.empty()) {
         int first = 0;
         while (first < levels && (W >> first) > 512) ++first;
-        t->cells_first = first;
+        d.cells_first = first;
         size_t off = 0;
-        for (int l = first; l < levels; ++l) { t->cells_off.push_back(off); int n = W >> l; if (n < 1) n = 1; off += pbrk_cells_bytes(n); }
-        t->cells_off.push_back(off);
-        t->cells_valid.assign(levels > first ? levels - first : 0, 0);
+        for (int l = first; l < levels; ++l) { d.cells_off.push_back(off); int n = W >> l; if (n < 1) n = 1; off += pbrk_cells_bytes(n); }
+        d.cells_off.push_back(off);
+        d.cells_valid.assign(levels > first ? levels - first : 0, 0);
         if (off) {
-            hipError_t e = hipMalloc(&t->cells, off);
-            if (e != hipSuccess) { t->cells = nullptr; gpu_fail("cells twin allocation (%zu bytes) failed: %s", off, hipGetErrorString(e)); }
+            hipError_t e = hipMalloc(&d.cells, off);
+            if (e != hipSuccess) { d.cells = nullptr; gpu_fail("cells twin allocation (%zu bytes) failed: %s", off, hipGetErrorString(e)); }
         }
     }
-    if (!t->cells || level < t->cells_first || level >= levels) return nullptr;
-    int li = level - t->cells_first;
-    void* c = (char*)t->cells + t->cells_off[li];
-    if (t->cells_valid[li]) return c;
+    if (!d.cells || level < d.cells_first || level >= levels) return nullptr;
+    int li = level - d.cells_first;
+    void* c = (char*)d.cells + d.cells_off[li];
+    if (d.cells_valid[li]) return c;
     int n = W >> level; if (n < 1) n = 1;
-    const void* src = (const char*)t->bordered + pbrk_bordered_level_offset(W, level) * 16;
+    const void* src = (const char*)d.bordered + pbrk_bordered_level_offset(W, level) * 16;
     if (pbrk_cells_build(src, n, c, st) != PBRK_OK) return nullptr;
-    t->cells_valid[li] = 1;
+    d.cells_valid[li] = 1;
     return c;
 }
-static bool cells_ready(TextureImpl* t, int level) {
-    return t->cells && level >= t->cells_first && level - t->cells_first < (int)t->cells_valid.size() && t->cells_valid[level - t->cells_first];
+static bool cells_ready(const TextureImpl* t, int level) {
+    const int li = level - t->derived.cells_first;
+    return t->derived.cells && li >= 0 && li < (int)t->derived.cells_valid.size() && t->derived.cells_valid[li];
 }
 
+static bool apron_ready(const TextureImpl* t, int first_level) { return t->derived.bordered_valid && t->derived.bordered_from <= first_level; }
 static float reference_roughness(int mip) {                      // gen_prefiltered_env_map.glsl:117 + SURVEY 8d extension
     static const float tab[5] = {0.0f, 0.03f, 0.15f, 0.4f, 0.6f};
     if (mip < 5) return tab[mip < 0 ? 0 : mip];
@@ -1904,7 +1911,6 @@ static void exec_brdf_lut(GPU_Graph* g, Op& op, size_t& ev_used) {
         int rc = pbrk_brdf_lut(out_ptr, fmt, (int)size, n, ang->dev, vcs->dev, (int)op.row0, (int)op.row1, g->cur);
         if (rc != PBRK_OK) gpu_fail("K1 launch failed (%d)", rc);
     });
-    ot->bordered_valid = false; ot->lut_cells_valid = false;
 }
 
 // What an irradiance (K3) or prefilter (K4a: the copy of mip 0, K4b: Monte Carlo) dispatch asks for, decoded once from its push
@@ -1962,9 +1968,9 @@ static int ibl_source_level(const TextureImpl* et, const IblPlan& p) {
 // g->cur where they are missing, and published.  False: the apron could not be built (reported).
 static bool ensure_ibl_twins(GPU_Graph* g, TextureImpl* et, int l, bool want_cells, size_t& ev_used) {
     hipStream_t st = g->cur;
-    if (!et->bordered_valid || et->bordered_from > l) {
+    if (!apron_ready(et, l)) {
         timed(g, "apron.env", ev_used, [&] { ensure_bordered(et, st, l); });
-        if (!et->bordered_valid || et->bordered_from > l) return false;
+        if (!apron_ready(et, l)) return false;
         publish_side_work(g);
     }
     if (want_cells && !cells_ready(et, l)) {
@@ -1991,7 +1997,7 @@ static void exec_ibl_filter(GPU_Graph* g, Op& op, size_t& ev_used) {
     if (l < 0) { gpu_fail("%s: fractional source LOD %g is not supported by the precompute kernels", p.name, p.lod); return; }
     if (!ensure_ibl_twins(g, et, l, !p.copy, ev_used)) return;
     int n_src = W >> l; if (n_src < 1) n_src = 1;
-    const void* src = (const char*)et->bordered + pbrk_bordered_level_offset(W, l) * 16;
+    const void* src = (const char*)et->derived.bordered + pbrk_bordered_level_offset(W, l) * 16;
     const void* cells = p.copy ? nullptr : ensure_cells(et, l, st);          // built by now: the pointer (NULL: the level has no cells twin)
     int n_keep = p.tab ? p.tab->count : 0;
     if (mc_prefilter && G.prefilter_tol > 0.0f) {            // opt-in: tolerance-budgeted sample cut (gpux.h)
@@ -2006,7 +2012,6 @@ static void exec_ibl_filter(GPU_Graph* g, Op& op, size_t& ev_used) {
                                          (int)op.face0, (int)op.face1, (int)op.row0, (int)op.row1, st);
         if (rc != PBRK_OK) gpu_fail("%s launch failed (%d)", p.name, rc);
     });
-    ot->bordered_valid = false;
 }
 
 // sample evaluations per output texel of a precompute dispatch
@@ -2095,7 +2100,6 @@ static void exec_gridview(GPU_Graph* g, Op& op, size_t& ev_used, const float* gl
         int rc = pbrk_lightgrid_view(&v, g->cur);
         if (rc != PBRK_OK) gpu_fail("K16 launch failed (%d)", rc);
     });
-    target->bordered_valid = false;
 }
 
 // The sampler twins that the lighting op (K5) reads and that are built lazily, in the order exec_shade builds them: the apron of the
@@ -2116,12 +2120,12 @@ static int shade_twins(GPU_DescriptorSet* s, int shade_flags, ShadeTwin tw[5], b
 static bool shade_twin_ready(const ShadeTwin& tw) {
     TextureImpl* t = tw.tex;
     switch (tw.kind) {
-    case Twin_Apron: return t->bordered_valid && t->bordered_from <= 0;
+    case Twin_Apron: return apron_ready(t, 0);
     case Twin_SmallCells:
         for (int l = 0; l < (int)t->base.mip_level_count; ++l) if (((int)t->base.width >> l) <= 512 && !cells_ready(t, l)) return false;
         return true;
     case Twin_Cells0: return cells_ready(t, 0);
-    case Twin_LutCells: return t->lut_cells_valid;
+    case Twin_LutCells: return t->derived.lut_cells_valid;
     }
     return false;
 }
@@ -2131,21 +2135,22 @@ static bool build_shade_twin(GPU_Graph* g, const ShadeTwin& tw, size_t& ev_used)
     switch (tw.kind) {
     case Twin_Apron:
         timed(g, tw.timed_name, ev_used, [&] { ensure_bordered(t, g->stream); });
-        return t->bordered_valid;
+        return apron_ready(t, 0);
     case Twin_SmallCells:
         timed(g, tw.timed_name, ev_used, [&] { for (int l = 0; l < (int)t->base.mip_level_count; ++l) if (((int)t->base.width >> l) <= 512) ensure_cells(t, l, g->stream); });
         return true;
     case Twin_Cells0: ensure_cells(t, 0, g->stream); return true;
     case Twin_LutCells: {
         const int n = (int)t->base.width;
-        if (!t->lut_cells && hipMalloc(&t->lut_cells, (size_t)(n + 1) * (n + 1) * 16) != hipSuccess) t->lut_cells = nullptr;
-        if (t->lut_cells && pbrk_lut_cells_build(t->dev, n, t->lut_cells, g->stream) == PBRK_OK) t->lut_cells_valid = true;
+        TextureImpl::Derived& d = t->derived;
+        if (!d.lut_cells && hipMalloc(&d.lut_cells, (size_t)(n + 1) * (n + 1) * 16) != hipSuccess) d.lut_cells = nullptr;
+        if (d.lut_cells && pbrk_lut_cells_build(t->dev, n, d.lut_cells, g->stream) == PBRK_OK) d.lut_cells_valid = true;
         return true;
     }
     }
     return false;
 }
-static void* cells_of(TextureImpl* t, int level) { return cells_ready(t, level) ? (char*)t->cells + t->cells_off[(size_t)(level - t->cells_first)] : nullptr; }
+static void* cells_of(TextureImpl* t, int level) { return cells_ready(t, level) ? (char*)t->derived.cells + t->derived.cells_off[(size_t)(level - t->derived.cells_first)] : nullptr; }
 
 static void exec_shade(GPU_Graph* g, Op& op, size_t& ev_used) {
     GPU_DescriptorSet* s = op.set;
@@ -2171,8 +2176,8 @@ static void exec_shade(GPU_Graph* g, Op& op, size_t& ev_used) {
     const int n_tw = shade_twins(s, op.gpipe->shade_flags, tw, sh9);
     for (int i = 0; i < n_tw; ++i) if (!shade_twin_ready(tw[i]) && !build_shade_twin(g, tw[i], ev_used)) return;
     TextureImpl* pre = named_slot(s, "PREFILTERED_ENV_MAP")->tex;
-    a.prefiltered_bordered = pre->bordered; a.prefiltered_size = (int)pre->base.width; a.prefiltered_levels = (int)pre->base.mip_level_count;
-    a.prefiltered_cells = pre->cells; a.prefiltered_cells_first = pre->cells_first;
+    a.prefiltered_bordered = pre->derived.bordered; a.prefiltered_size = (int)pre->base.width; a.prefiltered_levels = (int)pre->base.mip_level_count;
+    a.prefiltered_cells = pre->derived.cells; a.prefiltered_cells_first = pre->derived.cells_first;
     a.flags = 0;
     if (op.gpipe->shade_flags & GPUX_Shade_IBL) {
         a.flags |= PBRK_SHADE_IBL;
@@ -2181,12 +2186,12 @@ static void exec_shade(GPU_Graph* g, Op& op, size_t& ev_used) {
             a.sh9_coef = (const double*)((const char*)op.buf->dev + op.off_a);
         } else {
             TextureImpl* irr = named_slot(s, "TEX_IRRADIANCE_MAP")->tex;
-            a.irradiance_bordered = irr->bordered; a.irradiance_size = (int)irr->base.width;
+            a.irradiance_bordered = irr->derived.bordered; a.irradiance_size = (int)irr->base.width;
             a.irradiance_cells = cells_of(irr, 0);
         }
         TextureImpl* lut = named_slot(s, "BRDF_INTEGRATION_MAP")->tex;
         a.lut = lut->dev; a.lut_size = (int)lut->base.width;
-        a.lut_cells = lut->lut_cells_valid ? lut->lut_cells : nullptr;
+        a.lut_cells = lut->derived.lut_cells_valid ? lut->derived.lut_cells : nullptr;
     }
     if (op.gpipe->shade_flags & GPUX_Shade_VoxelGI) {
         a.flags |= PBRK_SHADE_GI;
@@ -2213,7 +2218,6 @@ static void exec_shade(GPU_Graph* g, Op& op, size_t& ev_used) {
         int rc = pbrk_shade(&a, g->cur);
         if (rc != PBRK_OK) gpu_fail("K5 launch failed (%d)", rc);
     });
-    target->bordered_valid = false;
 }
 
 static void exec_mipgen(GPU_Graph* g, Op& op, size_t& ev_used) {
@@ -2222,7 +2226,6 @@ static void exec_mipgen(GPU_Graph* g, Op& op, size_t& ev_used) {
                                        : pbrk_mip_chain(op.tex->dev, (int)op.tex->base.width, (int)op.tex->base.mip_level_count, g->cur);
         if (rc != PBRK_OK) gpu_fail("K2 launch failed (%d)", rc);
     });
-    op.tex->bordered_valid = false;
 }
 
 // K17: two launches (partials, then their sum in index order) resp. one; no read-back, nothing allocated
@@ -2236,7 +2239,6 @@ static void exec_sh9(GPU_Graph* g, Op& op, size_t& ev_used) {
                      : pbrk_sh9_irradiance(coef, level, n, (int)op.face0, (int)op.face1, (int)op.row0, (int)op.row1, g->cur);
         if (rc != PBRK_OK) gpu_fail("%s launch failed (%d)", op.name.c_str(), rc);
     });
-    if (op.kind == Op_IrradianceSH9) op.tex->bordered_valid = false;
 }
 
 // K18, either quality: one launch; nothing read back, nothing allocated
@@ -2251,7 +2253,7 @@ static void exec_bc6h(GPU_Graph* g, Op& op, size_t& ev_used) {
     });
 }
 
-// K19: one launch; the level was written, so the target's apron twin, cells and LUT cells are dropped like after any writer
+// K19: one launch
 static void exec_bc6h_decode(GPU_Graph* g, Op& op, size_t& ev_used) {
     const GPU_Texture& t = op.tex->base;
     void* level = (char*)op.tex->dev + op.tex->mip_offset[op.mip];
@@ -2260,30 +2262,23 @@ static void exec_bc6h_decode(GPU_Graph* g, Op& op, size_t& ev_used) {
                                   bc6h_source_format(t.format), g->cur);
         if (rc != PBRK_OK) gpu_fail("%s launch failed (%d)", op.name.c_str(), rc);
     });
-    op.tex->bordered_valid = false; op.tex->lut_cells_valid = false;
 }
 
 static void exec_blit(GPU_Graph* g, Op& op, size_t& ev_used) {
     hipStream_t st = g->cur;
-    if (op.folded) { op.tex2->bordered_valid = false; op.tex2->lut_cells_valid = false; return; }   // its consumer reads the source (fold_blits)
-    if (op.size) {                                                         // 1:1 copy of one layer
-        const void* src = (const char*)op.tex->dev + op.tex->mip_offset[op.mip] + op.size * op.layer0;
-        void* dst = (char*)op.tex2->dev + op.tex2->mip_offset[op.mip2] + op.size * op.layer2;
-        timed(g, op.name, ev_used, [&] { HIP_OK(hipMemcpyAsync(dst, src, op.size, hipMemcpyDeviceToDevice, st)); });
-        op.tex2->bordered_valid = false; op.tex2->lut_cells_valid = false;
-        return;
-    }
+    if (op.folded) return;                                                 // its consumer reads the source (fold_blits)
     uint32_t nsw = mip_dim(op.tex->base.width, op.mip), nsh = mip_dim(op.tex->base.height, op.mip);
     uint32_t ndw = mip_dim(op.tex2->base.width, op.mip2), ndh = mip_dim(op.tex2->base.height, op.mip2);
-    size_t layer_bytes_s = (size_t)nsw * nsh * 16, layer_bytes_d = (size_t)ndw * ndh * 16;
+    // op.size: a 1:1 copy of one layer of that many bytes; 0: a scaled blit between RGBA32F layers
+    size_t layer_bytes_s = op.size ? op.size : (size_t)nsw * nsh * 16, layer_bytes_d = op.size ? op.size : (size_t)ndw * ndh * 16;
     const void* src = (const char*)op.tex->dev + op.tex->mip_offset[op.mip] + layer_bytes_s * op.layer0;
     void* dst = (char*)op.tex2->dev + op.tex2->mip_offset[op.mip2] + layer_bytes_d * op.layer2;
     timed(g, op.name, ev_used, [&] {
+        if (op.size) { HIP_OK(hipMemcpyAsync(dst, src, op.size, hipMemcpyDeviceToDevice, st)); return; }
         int rc = (nsw == nsh && ndw == ndh && nsw == 2 * ndw) ? pbrk_box_downsample(src, (int)nsw, dst, 1, st)
                                                               : pbrk_blit_linear(src, (int)nsw, (int)nsh, dst, (int)ndw, (int)ndh, 1, st);
         if (rc != PBRK_OK) gpu_fail("blit launch failed (%d)", rc);
     });
-    op.tex2->bordered_valid = false;
 }
 
 // the four memcpy ops
@@ -2299,7 +2294,6 @@ static void exec_copy(GPU_Graph* g, Op& op, size_t& ev_used) {
             HIP_OK(hipMemcpyAsync((char*)op.tex->dev + op.tex->mip_offset[op.mip] + per_layer * op.layer0, (const char*)op.buf->dev + op.off_a,
                                   per_layer * op.layer_count, hipMemcpyDefault, st));
         });
-        op.tex->bordered_valid = false; op.tex->lut_cells_valid = false;
         if (op.tex->decoded) {                                                 // K15: the level that was written, and only it
             timed(g, "K15.bc_decode", ev_used, [&] {
                 int rc = decode_bc_level(op.tex, op.mip, st);
@@ -2330,66 +2324,97 @@ static void exec_clear(GPU_Graph* g, Op& op, size_t& ev_used) {
     (void)ev_used;                                                             // clears are not timed
     hipStream_t st = g->cur;
     TextureImpl* t = op.tex;
-    uint32_t m0 = op.mip == GPU_MIP_LEVEL_ALL ? 0 : op.mip, m1 = op.mip == GPU_MIP_LEVEL_ALL ? t->base.mip_level_count : op.mip + 1;
     // Levels are back to back in the allocation ([mip][layer][y][x], tight), so GPU_MIP_LEVEL_ALL is ONE fill of the whole
     // texture instead of one per level: the reference clears bloom_upscale_rt this way every frame (render.cpp:1156; 11 levels at
     // 1080p = 11 fill kernels of ~5 us each in rocprofv3's trace, a quarter of the post-process tail, before round 3).
     const bool whole = op.mip == GPU_MIP_LEVEL_ALL;
-    for (uint32_t m = m0; m < (whole ? m0 + 1 : m1); ++m) {
-        size_t bytes = whole ? t->bytes : (size_t)GPUX_TextureMipBytes(&t->base, m);
-        void* p = (char*)t->dev + t->mip_offset[m];
-        if (whole && op.skip_level0) { p = (char*)t->dev + t->mip_offset[1]; bytes = t->bytes - t->mip_offset[1]; }   // fold_blits
-        // build one texel pattern on the host and replicate it (clears are rare: upload a staging row)
-        uint32_t tb = t->texel_bytes;
-        std::vector<uint8_t> texel(tb, 0);
-        if (op.clear_mode == 2 || t->base.format == GPU_Format_R32F) { memcpy(texel.data(), &op.clear[0], 4 < tb ? 4 : tb); }
-        else if (op.clear_mode == 1) { for (uint32_t k = 0; k * 4 < tb && k < 4; ++k) memcpy(texel.data() + 4 * k, &op.cleari[k], 4); }
-        else if (t->base.format == GPU_Format_RGBA32F || t->base.format == GPU_Format_RG32F) { memcpy(texel.data(), op.clear, tb); }
-        else if (t->base.format == GPU_Format_RGBA8UN || t->base.format == GPU_Format_BGRA8UN) {
-            int order[4] = {0, 1, 2, 3};
-            if (t->base.format == GPU_Format_BGRA8UN) { order[0] = 2; order[2] = 0; }
-            for (int k = 0; k < 4; ++k) { float v = op.clear[order[k]]; v = v < 0 ? 0 : (v > 1 ? 1 : v); texel[k] = (uint8_t)(v * 255.0f + 0.5f); }
-        } else {
-            bool zero = op.clear[0] == 0 && op.clear[1] == 0 && op.clear[2] == 0 && op.clear[3] == 0;
-            if (!zero) { gpu_fail("GPU_OpClearColorF: non-zero clears of format %d are not implemented", (int)t->base.format); return; }
-        }
-        if (fill_texel_ok(tb)) {
-            int rc = pbrk_fill_pattern(p, bytes, texel.data(), (int)tb, st);
-            if (rc != PBRK_OK) gpu_fail("clear launch failed (%d)", rc);
-        } else {
-            std::vector<uint8_t> host(bytes);
-            for (size_t o = 0; o < bytes; o += tb) memcpy(host.data() + o, texel.data(), tb);
-            HIP_OK(hipMemcpyAsync(p, host.data(), bytes, hipMemcpyHostToDevice, st));
-            HIP_OK(hipStreamSynchronize(st));      // the staging vector dies at scope exit
-        }
+    const uint32_t m = whole ? 0 : op.mip;
+    size_t bytes = whole ? t->bytes : (size_t)GPUX_TextureMipBytes(&t->base, m);
+    void* p = (char*)t->dev + t->mip_offset[m];
+    if (whole && op.skip_level0) { p = (char*)t->dev + t->mip_offset[1]; bytes = t->bytes - t->mip_offset[1]; }   // fold_blits
+    // build one texel pattern on the host and replicate it (clears are rare: upload a staging row)
+    uint32_t tb = t->texel_bytes;
+    std::vector<uint8_t> texel(tb, 0);
+    if (op.clear_mode == 2 || t->base.format == GPU_Format_R32F) { memcpy(texel.data(), &op.clear[0], 4 < tb ? 4 : tb); }
+    else if (op.clear_mode == 1) { for (uint32_t k = 0; k * 4 < tb && k < 4; ++k) memcpy(texel.data() + 4 * k, &op.cleari[k], 4); }
+    else if (t->base.format == GPU_Format_RGBA32F || t->base.format == GPU_Format_RG32F) { memcpy(texel.data(), op.clear, tb); }
+    else if (t->base.format == GPU_Format_RGBA8UN || t->base.format == GPU_Format_BGRA8UN) {
+        int order[4] = {0, 1, 2, 3};
+        if (t->base.format == GPU_Format_BGRA8UN) { order[0] = 2; order[2] = 0; }
+        for (int k = 0; k < 4; ++k) { float v = op.clear[order[k]]; v = v < 0 ? 0 : (v > 1 ? 1 : v); texel[k] = (uint8_t)(v * 255.0f + 0.5f); }
+    } else {
+        bool zero = op.clear[0] == 0 && op.clear[1] == 0 && op.clear[2] == 0 && op.clear[3] == 0;
+        if (!zero) { gpu_fail("GPU_OpClearColorF: non-zero clears of format %d are not implemented", (int)t->base.format); return; }
     }
-    t->bordered_valid = false; t->lut_cells_valid = false;
+    if (fill_texel_ok(tb)) {
+        int rc = pbrk_fill_pattern(p, bytes, texel.data(), (int)tb, st);
+        if (rc != PBRK_OK) gpu_fail("clear launch failed (%d)", rc);
+    } else {
+        std::vector<uint8_t> host(bytes);
+        for (size_t o = 0; o < bytes; o += tb) memcpy(host.data() + o, texel.data(), tb);
+        HIP_OK(hipMemcpyAsync(p, host.data(), bytes, hipMemcpyHostToDevice, st));
+        HIP_OK(hipStreamSynchronize(st));      // the staging vector dies at scope exit
+    }
+}
+
+// What an op reads and writes, at whole-texture granularity: the one switch over op kind and kernel that names textures.  A new op
+// kind gets one case here; exec_op (what goes stale), graph_replayable (a shade op that would rebuild twins inside a capture) and
+// op_access (frames in flight) follow.  Every texture bound in a set counts as read, a bound buffer as memory not followed here.
+struct OpEffects {
+    TextureImpl* reads[16]; TextureImpl* writes[8]; int n_reads = 0, n_writes = 0;   // writes: a geometry job has five colour targets and its depth
+    bool unfollowed = false;                                                  // also touches memory not followed here: buffers, host pointers
+    void read(TextureImpl* t) { if (t && n_reads < 16) reads[n_reads++] = t; else if (t) unfollowed = true; }   // more reads than fit: as good as not followed
+    void write(TextureImpl* t) { if (t && n_writes < 8) writes[n_writes++] = t; else if (t) gpu_fail("an op writes more than 8 textures"); }
+    void bound(const GPU_DescriptorSet* set) { if (set) for (const Slot& sl : set->slots) { if (sl.buf) unfollowed = true; read(sl.tex); } else unfollowed = true; }
+};
+static OpEffects op_effects(const Op& op) {
+    OpEffects e;
+    switch (op.kind) {
+    case Op_Dispatch:                                                          // stores to one storage image: the sweep's grid, the output of K1 / K3 / K4
+        e.bound(op.set);
+        if (Slot* out = op.set ? named_slot(op.set, op.cpipe->kernel == Kernel_LightgridSweep ? "IMG0" : "OUTPUT") : nullptr) e.write(out->tex);
+        break;
+    case Op_Shade: case Op_Raster:
+        if (op.kind == Op_Shade) e.bound(op.set); else for (const RasterDraw& d : op.draws) e.bound(d.set);
+        e.read(op.blend_tex);                                                  // a folded blit's source (fold_blits)
+        if (op.pass) for (const GPU_TextureView& tv : op.pass->targets) e.write((TextureImpl*)tv.texture); else e.unfollowed = true;
+        if (op.kind == Op_Raster) e.write(op.tex);                             // the depth target (K14: the light grid)
+        if (op.buf) e.unfollowed = true;                                       // SH9 coefficients of a lighting draw; a raster job's vertices
+        break;
+    case Op_MipGen: e.read(op.tex); e.write(op.tex); break;
+    case Op_Blit: e.read(op.tex); e.write(op.tex2); break;                     // folded too: its consumer stores the sum to tex2
+    case Op_Clear: e.write(op.tex); break;
+    case Op_CopyB2T: case Op_IrradianceSH9: case Op_DecodeBC6H: e.write(op.tex); e.unfollowed = true; break;   // from a buffer
+    case Op_CopyT2B: case Op_CopyDecodedT2B: case Op_ProjectSH9: case Op_EncodeBC6H: e.read(op.tex); e.unfollowed = true; break;   // into one
+    case Op_CopyB2B: e.unfollowed = true; break;
+    }
+    return e;
 }
 
 static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
     switch (op.kind) {
     case Op_Dispatch:
-        switch (op.cpipe->kernel) {
-        case Kernel_LightgridSweep: exec_sweep(g, op, ev_used); return;
-        case Kernel_BrdfLut: exec_brdf_lut(g, op, ev_used); return;
-        default: exec_ibl_filter(g, op, ev_used); return;                    // K3, K4a, K4b
-        }
+        if (op.cpipe->kernel == Kernel_LightgridSweep) exec_sweep(g, op, ev_used);
+        else if (op.cpipe->kernel == Kernel_BrdfLut) exec_brdf_lut(g, op, ev_used);
+        else exec_ibl_filter(g, op, ev_used);                                // K3, K4a, K4b
+        break;
     case Op_Shade:
-        switch (op.gpipe->kernel) {
-        case Kernel_BloomDown: case Kernel_BloomUp: exec_bloom(g, op, ev_used); return;
-        case Kernel_TaaResolve: exec_taa(g, op, ev_used); return;
-        case Kernel_FinalPost: exec_final(g, op, ev_used); return;
-        default: exec_shade(g, op, ev_used); return;                         // K5, or K16 when the Globals ask for it
-        }
-    case Op_Raster: exec_raster(g, op, ev_used); return;
-    case Op_MipGen: exec_mipgen(g, op, ev_used); return;
-    case Op_Blit: exec_blit(g, op, ev_used); return;
-    case Op_Clear: exec_clear(g, op, ev_used); return;
-    case Op_CopyB2B: case Op_CopyB2T: case Op_CopyT2B: case Op_CopyDecodedT2B: exec_copy(g, op, ev_used); return;
-    case Op_ProjectSH9: case Op_IrradianceSH9: exec_sh9(g, op, ev_used); return;
-    case Op_EncodeBC6H: exec_bc6h(g, op, ev_used); return;
-    case Op_DecodeBC6H: exec_bc6h_decode(g, op, ev_used); return;
+        if (is_bloom_kernel(op.gpipe->kernel)) exec_bloom(g, op, ev_used);
+        else if (op.gpipe->kernel == Kernel_TaaResolve) exec_taa(g, op, ev_used);
+        else if (op.gpipe->kernel == Kernel_FinalPost) exec_final(g, op, ev_used);
+        else exec_shade(g, op, ev_used);                                     // K5, or K16 when the Globals ask for it
+        break;
+    case Op_Raster: exec_raster(g, op, ev_used); break;
+    case Op_MipGen: exec_mipgen(g, op, ev_used); break;
+    case Op_Blit: exec_blit(g, op, ev_used); break;
+    case Op_Clear: exec_clear(g, op, ev_used); break;
+    case Op_CopyB2B: case Op_CopyB2T: case Op_CopyT2B: case Op_CopyDecodedT2B: exec_copy(g, op, ev_used); break;
+    case Op_ProjectSH9: case Op_IrradianceSH9: exec_sh9(g, op, ev_used); break;
+    case Op_EncodeBC6H: exec_bc6h(g, op, ev_used); break;
+    case Op_DecodeBC6H: exec_bc6h_decode(g, op, ev_used); break;
     }
+    const OpEffects e = op_effects(op);                                        // whatever was built from the old bytes is stale now
+    for (int i = 0; i < e.n_writes; ++i) texture_written(e.writes[i]);
 }
 
 // ---- hipGraph replay of the per-frame chain --------------------------------------------------------------------------
@@ -2423,29 +2448,22 @@ static bool op_replayable(const Op& op) {
     return false;
 }
 
+static bool contains(const std::vector<TextureImpl*>& v, const TextureImpl* t) { for (const TextureImpl* x : v) if (x == t) return true; return false; }
 // Graph-level eligibility.  op_replayable() looks at the sampler twins as they are NOW; an earlier op of the same graph that writes
-// one of the maps a later shade op samples (Op_Clear / Op_MipGen / Op_Blit / a storage-image dispatch drop the apron, cells and LUT
-// twins when they execute) would have that shade op rebuild its twins -- allocation + synchronisation -- inside the capture.
-// Such a graph takes the plain path: the textures written by the ops seen so far are tracked and compared with what each shade
-// op samples.
+// one of the maps a later shade op samples (exec_op drops the twins of every texture an op writes) would have that shade op rebuild
+// its twins -- allocation + synchronisation -- inside the capture.  Such a graph takes the plain path: the textures
+// written by the ops seen so far (op_effects) are compared with what each shade op samples.
 static bool graph_replayable(GPU_Graph* g) {
-    std::vector<const TextureImpl*> written;
-    auto is_written = [&](const TextureImpl* t) { for (const TextureImpl* w : written) if (w == t) return true; return false; };
+    std::vector<TextureImpl*> written;
     for (const Op& op : g->ops) {
         if (!op_replayable(op)) return false;
-        switch (op.kind) {
-        case Op_Clear: case Op_MipGen: case Op_IrradianceSH9: case Op_DecodeBC6H: written.push_back(op.tex); break;
-        case Op_Blit: if (op.tex2) written.push_back(op.tex2); break;          // tex = source, tex2 = destination
-        case Op_Dispatch: { Slot* o = named_slot(op.set, "IMG0"); if (o && o->tex) written.push_back(o->tex); break; }
-        case Op_Shade: {
-            if (is_post_kernel(op.gpipe->kernel)) break;
+        if (op.kind == Op_Shade && !is_post_kernel(op.gpipe->kernel)) {
             ShadeTwin tw[5];                                                   // all three maps, whatever the op's flags: a bound map counts even when it is not sampled
             const int n = shade_twins(op.set, GPUX_Shade_IBL, tw);
-            for (int i = 0; i < n; ++i) if (is_written(tw[i].tex)) return false;
-            break;
+            for (int i = 0; i < n; ++i) if (contains(written, tw[i].tex)) return false;
         }
-        default: break;
-        }
+        const OpEffects e = op_effects(op);
+        written.insert(written.end(), e.writes, e.writes + e.n_writes);
     }
     return true;
 }
@@ -2505,35 +2523,17 @@ static void fold_blits(GPU_Graph* g) {
     }
 }
 
-// Textures an op reads / writes, at whole-texture granularity; false when the op touches memory this analysis does not follow (buffers,
-// host pointers).  Draws and dispatches: every texture bound in their descriptor set counts as read, a dispatch's also as written
-// (storage images), a draw's render targets as written.
+// op_effects for the frames-in-flight analysis: appends what the op reads and writes; false (ends the walk): not all of it is followed
 static bool op_access(const Op& op, std::vector<TextureImpl*>& r, std::vector<TextureImpl*>& w) {
-    switch (op.kind) {
-    case Op_Dispatch: case Op_Shade:
-        if (!op.set) return false;
-        for (const Slot& sl : op.set->slots) {
-            if (sl.buf) return false;
-            if (sl.tex) { r.push_back(sl.tex); if (op.kind == Op_Dispatch) w.push_back(sl.tex); }
-        }
-        if (op.kind == Op_Shade) {
-            if (!op.pass || op.buf) return false;                            // op.buf: the SH9 coefficients a lighting draw reads -- a buffer, not followed
-            for (const GPU_TextureView& tv : op.pass->targets) w.push_back((TextureImpl*)tv.texture);
-            if (op.blend_tex) r.push_back(op.blend_tex);
-        }
-        return true;
-    case Op_MipGen: r.push_back(op.tex); w.push_back(op.tex); return true;
-    case Op_Blit: r.push_back(op.tex); w.push_back(op.tex2); return true;
-    case Op_Clear: w.push_back(op.tex); return true;
-    case Op_ProjectSH9: case Op_EncodeBC6H: r.push_back(op.tex); return false; // their buffer is not followed: ends the walk like any buffer
-    case Op_IrradianceSH9: case Op_DecodeBC6H: w.push_back(op.tex); return false;   // the buffer they read is not followed either
-    default: return false;
-    }
+    const OpEffects e = op_effects(op);
+    r.insert(r.end(), e.reads, e.reads + e.n_reads);
+    w.insert(w.end(), e.writes, e.writes + e.n_writes);
+    if (op.kind == Op_Dispatch) w.insert(w.end(), e.reads, e.reads + e.n_reads);   // more cautious than the facts: any texture bound to a dispatch may be a storage image
+    return !e.unfollowed;
 }
 static uint64_t g_overlapped_submits = 0;
 GPU_API void GPUX_SetGraphOverlap(int on) { G.overlap = on; }
 GPU_API uint64_t GPUX_OverlappedSubmitCount(void) { return g_overlapped_submits; }
-static bool contains(const std::vector<TextureImpl*>& v, const TextureImpl* t) { for (const TextureImpl* x : v) if (x == t) return true; return false; }
 
 // ---- GPU_GraphSubmit, step by step ----
 // Submission order is execution order, as on the reference's single queue (vkQueueSubmit, gpu_vulkan.c:2481-2530): a graph
