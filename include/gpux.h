@@ -89,6 +89,21 @@ GPU_API void GPUX_OpEncodeBC6HEx(GPU_Graph* graph, GPU_Texture* src, uint32_t mi
  * RGBA16F texture; alpha 1.  A texture writer like any other: the target's sampler twins are rebuilt before the next use.  Anything
  * else is one error at record time with nothing recorded.  A plain launch; may be captured under GPUX_SetGraphReplay(1). */
 GPU_API void GPUX_OpDecodeBC6H(GPU_Graph* graph, GPU_Buffer* src, uint32_t src_offset, GPU_Texture* dst, uint32_t mip_level);
+/* K20: level src_mip of an RGBA32F cubemap (any face size) -> level dst_mip of a 2-D RGBA32F or RGBA16F texture as a lat-long panorama;
+ * that level's extent (1 .. 16384 a side, nothing has to be a multiple of anything) is the panorama's.  Pixel (x, y) is the seamless
+ * bilinear sample of the cube level along d = (sin t cos p, sin t sin p, cos t), p = ((2 x + 1) / w - 1) pi, t = (2 y + 1) / (2 h) pi:
+ * Z-up, row 0 next to +Z, the inverse of K6 (csrc/panorama_core.h).  No minification filter: a panorama far narrower
+ * than 4 n aliases, and the choice of level is the caller's.  The column / row tables are built and uploaded when the op is recorded
+ * and belong to the graph; the apron of the cube is ensured from src_mip when the op executes (its own timed entry, apron.panorama,
+ * in front of K20.cube_to_panorama).  Reads the cube and writes dst, both followed: a later sampler of dst sees the new bytes, a later
+ * write to the cube has the next submission rebuild the apron.  Never captured: a graph holding this op submits the plain way under
+ * GPUX_SetGraphReplay(1).  Any bad argument (NULL, formats, a cube or 3-D target, a mip out of range, inside a render pass, an extent
+ * above 16384) is one error at record time with nothing recorded. */
+GPU_API void GPUX_OpCubeToPanorama(GPU_Graph* graph, GPU_Texture* cube, uint32_t src_mip, GPU_Texture* dst, uint32_t dst_mip);
+/* The width * height * 3 fp32 directions K20 samples along, row-major: the arithmetic of the op's tables (the same translation unit),
+ * pure host code, callable without GPU_Init.  For tools that must find the pixel of a direction, and for tests.  0 on success, 1 for a
+ * NULL pointer or an extent outside 1 .. 16384. */
+GPU_API int GPUX_PanoramaDirections(uint32_t width, uint32_t height, float* xyz);
 GPU_API void* GPUX_TextureDevicePtr(GPU_Texture* texture, uint32_t mip_level);            /* for RCCL / interop */
 GPU_API void* GPUX_BufferDevicePtr(GPU_Buffer* buffer);
 GPU_API void* GPUX_GraphStream(GPU_Graph* graph);                                         /* hipStream_t */

@@ -33,6 +33,15 @@ void* PBR_EncodeHDR(const float* rgba, int w, int h, size_t* out_size);
 int   PBR_WriteHDRFile(const char* filepath, const float* rgba, int w, int h);
 /* One mip of a cubemap as a vertical-strip .hdr (the layout MakeTextureFromHDRIFile reads back). Returns 0 on success. */
 int   PBR_WriteCubeStripHDR(const char* filepath, GPU_Texture* cube, uint32_t mip_level);
+/* One level of an RGBA32F cubemap as a lat-long panorama (K20, GPUX_OpCubeToPanorama: Z-up, row 0 next to +Z, the inverse of the
+ * equirectangular loader above; host/pbr_panorama.c): a new 2-D texture of `format` (GPU_Format_RGBA32F or GPU_Format_RGBA16F) that the
+ * caller destroys.  width 0 means 4 n and height 0 means width / 2 (at least 1), n the level's face size; either may be anything from 1
+ * to 16384.  Blocking (own graph).  NULL on any error.  The level is the caller's choice and is sampled bilinearly with no minification
+ * filter: on the specular map the levels are roughness levels, not a filter chain, so a width far below 4 n aliases instead of moving
+ * to a smaller level.  A panorama as .dds, BC6H included, needs nothing more: it is PBR_WriteTextureDDS of the texture returned. */
+GPU_Texture* PBR_MakePanoramaFromCube(GPU_Texture* cube, uint32_t mip_level, uint32_t width, uint32_t height, GPU_Format format);
+/* The RGBA32F panorama of PBR_MakePanoramaFromCube, read back and written with PBR_WriteHDRFile (RGBE).  Returns 0 on success. */
+int   PBR_WritePanoramaHDR(const char* filepath, GPU_Texture* cube, uint32_t mip_level, uint32_t width, uint32_t height);
 
 /* ---- IBL precompute, render.cpp:505-619 ---- */
 typedef struct PBR_IBLMaps {

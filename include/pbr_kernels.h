@@ -499,6 +499,15 @@ int pbrk_bc6h_encode2(const void* level, int src_format /* PBRK_FMT_RGBA32F / PB
 int pbrk_bc6h_decode(const void* blocks, int width, int height, int layers, void* level_out,
                      int dst_format /* PBRK_FMT_RGBA32F / PBRK_FMT_RGBA16F */, void* stream);
 
+/* ---- K20: one level of an RGBA32F cube -> a w x h lat-long panorama (the inverse of K6).  bordered_level: the n^2
+ *      level inside the bordered twin ([6][n+2][n+2] float4, pbrk_border_build).  table: device double[2 w + 2 h] as pano_fill_table
+ *      (csrc/panorama_core.h) writes it -- {cos phi, sin phi} per column, then {sin theta, cos theta} per row.  out: w x h RGBA32F
+ *      (16-byte aligned) or RGBA16F (8-byte aligned) texels, tight rows; fp16 by v_cvt_f16_f32 (round to nearest even).  n, w and h:
+ *      any value from 1 to 16384.  Another target format is PBRK_E_FORMAT, anything else PBRK_E_ARG, with nothing launched.
+ *      Contract: csrc/panorama_core.h, DESIGN.md K20. ---- */
+int pbrk_cube_to_panorama(const void* bordered_level, int n, const void* table, void* out,
+                          int out_format /* PBRK_FMT_RGBA32F / PBRK_FMT_RGBA16F */, int w, int h, void* stream);
+
 /* ---- diagnostics: the device samplers of the widened passes evaluated at caller-supplied coordinates, so that tests can feed them
  *      NaN / inf / 1e30 / boundary values directly (a ray that has marched far away must never become an out-of-bounds read).
  *      which: 0 = LIGHTGRID (RGBA16F n^3, coords xyz), 1 = sampler2DShadow (R32F w x h, coords u, v, ref; result in out[0]),

@@ -23,6 +23,7 @@
 
 #include "gpux.h"
 #include "pbr_kernels.h"
+#include "panorama_core.h"
 
 // ------------------------------------------------------------------------------------------
 // errors
@@ -108,7 +109,7 @@ struct GPU_GraphicsPipeline { GPU_PipelineLayout* layout; GPU_RenderPass* pass; 
                               const struct RasterKind* raster = nullptr; /* K12 / K13 / K14: the row of its raster kind */
                               BufferImpl* sh9_buf = nullptr; uint32_t sh9_offset = 0; /* GPUX_SetShadeSH9 */ };
 
-enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster, Op_CopyDecodedT2B, Op_ProjectSH9, Op_IrradianceSH9, Op_EncodeBC6H, Op_DecodeBC6H };
+enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster, Op_CopyDecodedT2B, Op_ProjectSH9, Op_IrradianceSH9, Op_EncodeBC6H, Op_DecodeBC6H, Op_CubeToPanorama };
 // one draw of a raster job: job triangles from first_tri on, matrices from the set's GLOBALS, the buffers and the target its kind
 // names (K12 / K13: the buffers bound at the draw; K14: SSBO0 / SSBO1 of the set, first_index = its first vertex) and the pushed
 // constants (K13 reads them: the skybox rebinds both inside the pass)
@@ -133,6 +134,7 @@ struct Op {
     uint64_t off_a = 0, off_b = 0, size = 0;
     float clear[4]; uint32_t cleari[4]; int clear_mode = 0;
     uint32_t quality = 0;                          // Op_EncodeBC6H: GPUX_BC6H_OneRegion / GPUX_BC6H_TwoRegions
+    const void* pano_table = nullptr;              // Op_CubeToPanorama: the op's column / row table (GPU_Graph::pano)
     // submit-time folding (fold_blits): a 1:1 blit whose copy is consumed only by an additive bloom draw onto its target is not
     // executed; that draw takes the blend operand from the blit's source instead
     bool folded = false;
@@ -172,6 +174,10 @@ struct GPU_Graph {
     int raster_op = -1;                            // index in ops of the raster job of the open render pass (-1: none yet)
     std::vector<RasterScratch> raster; size_t raster_used = 0;
     void* sh_scratch = nullptr; size_t sh_scratch_bytes = 0;   // K17 partials (GPUX_OpProjectSH9): sized at record time, kept across submissions
+    // K20 tables (GPUX_OpCubeToPanorama), one per recorded op: allocated and filled at record time, handed out again after a reset
+    // (a table that is big enough is kept), freed with the graph
+    struct PanoTable { void* dev = nullptr; size_t bytes = 0; };
+    std::vector<PanoTable> pano; size_t pano_used = 0;
     // hipGraph replay (GPUX_SetGraphReplay): the executable graph of the previous submission, updated in place when the
     // next one has the same shape
     hipGraphExec_t exec = nullptr;
@@ -1220,6 +1226,7 @@ static void reset_graph(GPU_Graph* g) {
     g->bound_cpipe = nullptr; g->bound_cset = nullptr; g->push_size = 0;
     g->preparing = nullptr; g->in_pass = nullptr; g->draw_params.clear(); g->bound_draw = -1;
     g->vertex_buffer = nullptr; g->index_buffer = nullptr; g->raster_op = -1; g->raster_used = 0;
+    g->pano_used = 0;
 }
 GPU_API void GPU_DestroyGraph(GPU_Graph* g) {
     GPU_REQUIRE_V(g, "GPU_DestroyGraph: NULL graph");            // the reference does not accept NULL here (gpu_vulkan.c:2393-2404)
@@ -1234,6 +1241,7 @@ GPU_API void GPU_DestroyGraph(GPU_Graph* g) {
     if (g->exec) (void)hipGraphExecDestroy(g->exec);
     for (RasterScratch& r : g->raster) { (void)hipFree(r.dev); (void)hipFree(r.draws_dev); (void)hipHostFree(r.draws_host); }
     (void)hipFree(g->sh_scratch);
+    for (GPU_Graph::PanoTable& t : g->pano) (void)hipFree(t.dev);
     if (G.last_submitted == g) G.last_submitted = nullptr;        // idle by contract (gpu.h:453): nothing left to order against
     (void)hipStreamDestroy(g->stream);
     delete g;
@@ -1690,6 +1698,50 @@ GPU_API void GPUX_OpDecodeBC6H(GPU_Graph* g, GPU_Buffer* src, uint32_t src_offse
     GPU_REQUIRE_V((uint64_t)src_offset + bytes <= src->size, "%s: buffer too small (%u bytes for %llu at offset %u)", fn, src->size, (unsigned long long)bytes, src_offset);
     Op op; op.kind = Op_DecodeBC6H; op.name = "K19.bc6h_decode";
     op.buf = (BufferImpl*)src; op.off_a = src_offset; op.tex = (TextureImpl*)dst; op.mip = mip; op.size = bytes;
+    g->ops.push_back(op);
+}
+
+// ---- K20: one level of an RGBA32F cube -> one level of a 2-D RGBA32F / RGBA16F texture as a lat-long panorama ----
+// The directions of a w x h panorama, from the entries pano_fill_table writes: what the kernel forms from the uploaded table
+static void pano_directions(const double* table, int w, int h, float* xyz) {
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) pano_dir(table + 2 * x, table + 2 * (w + y), xyz + 3 * ((size_t)y * w + x));
+}
+GPU_API int GPUX_PanoramaDirections(uint32_t width, uint32_t height, float* xyz) {
+    if (!xyz || width < 1 || height < 1 || width > PANO_MAX_EXTENT || height > PANO_MAX_EXTENT) return 1;
+    std::vector<double> table(2 * ((size_t)width + height));
+    pano_fill_table((int)width, (int)height, table.data());
+    pano_directions(table.data(), (int)width, (int)height, xyz);
+    return 0;
+}
+// op.tex / op.mip = the cube level, op.tex2 / op.mip2 = the panorama, op.pano_table = its table on the device
+GPU_API void GPUX_OpCubeToPanorama(GPU_Graph* g, GPU_Texture* cube, uint32_t src_mip, GPU_Texture* dst, uint32_t dst_mip) {
+    REC_GUARD(g);
+    const char* fn = "GPUX_OpCubeToPanorama";
+    GPU_REQUIRE_V(g->in_pass == nullptr, "%s: inside a render pass", fn);
+    GPU_REQUIRE_V(cube && dst && src_mip < cube->mip_level_count && dst_mip < dst->mip_level_count, "%s: bad arguments", fn);
+    GPU_REQUIRE_V(is_f4_cube((TextureImpl*)cube), "%s: the source must be a square RGBA32F cubemap", fn);
+    GPU_REQUIRE_V((dst->format == GPU_Format_RGBA32F || dst->format == GPU_Format_RGBA16F) && dst->depth == 1 && dst->layer_count == 1,
+                  "%s: the target must be a 2-D RGBA32F / RGBA16F texture", fn);
+    const uint32_t n = mip_dim(cube->width, src_mip), w = mip_dim(dst->width, dst_mip), h = mip_dim(dst->height, dst_mip);
+    GPU_REQUIRE_V(n <= PANO_MAX_EXTENT && w <= PANO_MAX_EXTENT && h <= PANO_MAX_EXTENT, "%s: levels above 16384 a side are not implemented", fn);
+    // the table is built, allocated and uploaded here, not at submit: nothing allocates inside a submission, and the graph is idle while
+    // it records.  A slot of an earlier recording is used again; a slot in use is never touched, so the ops recorded so far keep theirs
+    std::vector<double> table(2 * ((size_t)w + h));
+    pano_fill_table((int)w, (int)h, table.data());
+    const size_t bytes = table.size() * sizeof(double);
+    if (g->pano_used == g->pano.size()) g->pano.push_back(GPU_Graph::PanoTable());
+    GPU_Graph::PanoTable& slot = g->pano[g->pano_used];
+    if (slot.bytes < bytes) {
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); gpu_fail("%s: allocation of the direction table (%zu bytes) failed", fn, bytes); return; }
+        (void)hipFree(slot.dev);
+        slot.dev = p; slot.bytes = bytes;
+    }
+    if (hipMemcpy(slot.dev, table.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); gpu_fail("%s: upload of the direction table failed", fn); return; }
+    ++g->pano_used;
+    Op op; op.kind = Op_CubeToPanorama; op.name = "K20.cube_to_panorama";
+    op.tex = (TextureImpl*)cube; op.mip = src_mip; op.tex2 = (TextureImpl*)dst; op.mip2 = dst_mip; op.pano_table = slot.dev;
     g->ops.push_back(op);
 }
 
@@ -2264,6 +2316,24 @@ static void exec_bc6h_decode(GPU_Graph* g, Op& op, size_t& ev_used) {
     });
 }
 
+// K20: the apron of the cube from the source level on where it is missing (its own timed entry), then one launch; nothing allocated
+static void exec_panorama(GPU_Graph* g, Op& op, size_t& ev_used) {
+    TextureImpl* cube = op.tex;
+    const GPU_Texture& d = op.tex2->base;
+    const int W = (int)cube->base.width;
+    if (!apron_ready(cube, (int)op.mip)) {
+        timed(g, "apron.panorama", ev_used, [&] { ensure_bordered(cube, g->cur, (int)op.mip); });
+        if (!apron_ready(cube, (int)op.mip)) return;
+    }
+    const void* level = (const char*)cube->derived.bordered + pbrk_bordered_level_offset(W, (int)op.mip) * 16;
+    void* out = (char*)op.tex2->dev + op.tex2->mip_offset[op.mip2];
+    timed(g, op.name, ev_used, [&] {
+        int rc = pbrk_cube_to_panorama(level, (int)mip_dim(cube->base.width, op.mip), op.pano_table, out, bc6h_source_format(d.format),
+                                       (int)mip_dim(d.width, op.mip2), (int)mip_dim(d.height, op.mip2), g->cur);
+        if (rc != PBRK_OK) gpu_fail("%s launch failed (%d)", op.name.c_str(), rc);
+    });
+}
+
 static void exec_blit(GPU_Graph* g, Op& op, size_t& ev_used) {
     hipStream_t st = g->cur;
     if (op.folded) return;                                                 // its consumer reads the source (fold_blits)
@@ -2387,6 +2457,7 @@ static OpEffects op_effects(const Op& op) {
     case Op_CopyB2T: case Op_IrradianceSH9: case Op_DecodeBC6H: e.write(op.tex); e.unfollowed = true; break;   // from a buffer
     case Op_CopyT2B: case Op_CopyDecodedT2B: case Op_ProjectSH9: case Op_EncodeBC6H: e.read(op.tex); e.unfollowed = true; break;   // into one
     case Op_CopyB2B: e.unfollowed = true; break;
+    case Op_CubeToPanorama: e.read(op.tex); e.write(op.tex2); break;          // its table belongs to the graph and is written at record time only
     }
     return e;
 }
@@ -2412,6 +2483,7 @@ static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
     case Op_ProjectSH9: case Op_IrradianceSH9: exec_sh9(g, op, ev_used); break;
     case Op_EncodeBC6H: exec_bc6h(g, op, ev_used); break;
     case Op_DecodeBC6H: exec_bc6h_decode(g, op, ev_used); break;
+    case Op_CubeToPanorama: exec_panorama(g, op, ev_used); break;
     }
     const OpEffects e = op_effects(op);                                        // whatever was built from the old bytes is stale now
     for (int i = 0; i < e.n_writes; ++i) texture_written(e.writes[i]);
@@ -2436,6 +2508,7 @@ static bool op_replayable(const Op& op) {
     case Op_ProjectSH9: case Op_IrradianceSH9: return true;                   // plain launches on device-visible pointers; the scratch exists since recording
     case Op_EncodeBC6H: return true;                                          // one plain launch, texture -> device-visible buffer
     case Op_DecodeBC6H: return true;                                          // the same, buffer -> texture
+    case Op_CubeToPanorama: return false;                                     // may build the cube's apron (allocation) when it executes
     case Op_Clear: return fill_texel_ok(op.tex->texel_bytes);
     case Op_Shade: {
         if (is_post_kernel(op.gpipe->kernel)) return true;

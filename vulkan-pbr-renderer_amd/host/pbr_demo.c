@@ -2,7 +2,7 @@
  * pbr_demo.c -- headless C driver of the hot path through the GPU_* boundary (what main.cpp:35-51 +
  * HotreloadShaders + BuildRenderCommands do for this path, without window / mesh import / raster passes).
  *
- *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster [gridview]]]]] [sh9 FILE] [dds|dds2 PREFIX] [ddsin PREFIX] [sh9shade]
+ *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster [gridview]]]]] [sh9 FILE] [dds|dds2 PREFIX] [ddsin PREFIX] [sh9shade] [pano PREFIX]
  *
  * Loads a vertical-strip HDR cube (asset_import.cpp:17-27), runs the IBL precompute (render.cpp:505-619),
  * shades a flat synthetic G-buffer (a metallic floor under the sky), then runs three frames of the per-frame chain
@@ -27,6 +27,9 @@
  * With `sh9shade` as the LAST argument (after all of the above) the first frame is rendered once more with the ambient term taken from
  * the SH9 coefficients of level 0 of the environment instead of the irradiance cube (K17's projection and K5 in SH9 mode in one
  * graph, PBR_LightingUseSH9), and its checksum is printed as frame_sh9_checksum; the other lines stay as they are.
+ * With `pano PREFIX` as the LAST two arguments (after all of the above, `sh9shade` included) the baked maps are also written as lat-long
+ * panoramas one can look at (K20, PBR_WritePanoramaHDR at the default extent 4 n x 2 n): PREFIX_irradiance.hdr and PREFIX_specular_mipN.hdr
+ * for every level that has a specular_mipN_sum line, and each file's extent is printed as pano_extent; the other lines stay as they are.
  */
 #include "pbr_host.h"
 
@@ -116,7 +119,9 @@ int main(int argc, char** argv) {
     const char* sh9_path = NULL;
     const char* dds_prefix = NULL;
     const char* ddsin_prefix = NULL;
+    const char* pano_prefix = NULL;
     int sh9shade = 0, dds_format = PBR_DDS_OUT_BC6H_UF16;
+    if (argc >= 4 && strcmp(argv[argc - 2], "pano") == 0) { pano_prefix = argv[argc - 1]; argc -= 2; }
     if (argc >= 3 && strcmp(argv[argc - 1], "sh9shade") == 0) { sh9shade = 1; argc -= 1; }
     if (argc >= 4 && strcmp(argv[argc - 2], "ddsin") == 0) { ddsin_prefix = argv[argc - 1]; argc -= 2; }
     if (argc >= 4 && strcmp(argv[argc - 2], "dds") == 0) { dds_prefix = argv[argc - 1]; argc -= 2; }
@@ -173,6 +178,19 @@ int main(int argc, char** argv) {
                 fwrite(data, 1, bytes, f) != bytes || fclose(f) != 0) { fprintf(stderr, "dds: cannot write %s_%s.dds\n", dds_prefix, files[i].name); return 1; }
             free(data);
             printf("dds_bytes %s %zu\n", files[i].name, bytes);
+        }
+    }
+    if (pano_prefix) {
+        uint32_t sz = spec, levels = 0;                                      /* the levels the prefilter wrote (or the file held) */
+        for (; levels < maps.tex_specular_env_map->mip_level_count && sz >= min_size; sz /= 2) levels++;
+        for (uint32_t i = 0; i <= levels; ++i) {                             /* the irradiance map, then specular level i - 1 */
+            GPU_Texture* cube = i == 0 ? maps.irradiance_map : maps.tex_specular_env_map;
+            const uint32_t mip = i == 0 ? 0 : i - 1;
+            uint32_t n = cube->width >> mip; if (n < 1) n = 1;
+            char path[4096];
+            const int len = i == 0 ? snprintf(path, sizeof path, "%s_irradiance.hdr", pano_prefix) : snprintf(path, sizeof path, "%s_specular_mip%u.hdr", pano_prefix, mip);
+            if (len >= (int)sizeof path || PBR_WritePanoramaHDR(path, cube, mip, 0, 0) != 0) { fprintf(stderr, "pano: cannot write a panorama under %s\n", pano_prefix); return 1; }
+            if (i == 0) printf("pano_extent irradiance %u %u\n", 4 * n, 2 * n); else printf("pano_extent specular_mip%u %u %u\n", mip, 4 * n, 2 * n);
         }
     }
 

@@ -370,6 +370,12 @@ PROTOTYPES = {
     "GPUX_OpDecodeBC6H": (None, [VP, BufP, U32, TexP, U32]),
     "PBR_MakeTextureFromBC6HDDSMemory": (TexP, [VP, C.c_size_t, C.c_int]), "PBR_MakeTextureFromBC6HDDSFile": (TexP, [C.c_char_p, C.c_int]),
     "PBR_DecodeBC6HBlocks": (None, [VP, U32, U32, C.POINTER(C.c_uint16)]),
+    # --- K20: cube level -> lat-long panorama ---
+    "pbrk_cube_to_panorama": (C.c_int, [VP, C.c_int, VP, VP, C.c_int, C.c_int, C.c_int, VP]),
+    "GPUX_OpCubeToPanorama": (None, [VP, TexP, U32, TexP, U32]),
+    "GPUX_PanoramaDirections": (C.c_int, [U32, U32, C.POINTER(C.c_float)]),
+    "PBR_MakePanoramaFromCube": (TexP, [TexP, U32, U32, U32, C.c_int]),
+    "PBR_WritePanoramaHDR": (C.c_int, [C.c_char_p, TexP, U32, U32, U32]),
 }
 
 _LIB = None
@@ -737,3 +743,25 @@ def decode_bc6h_blocks_host(blocks, w, h):
     out = np.zeros((h, w, 3), np.uint16)
     lib().PBR_DecodeBC6HBlocks(blocks.ctypes.data_as(VP), w, h, out.ctypes.data_as(C.POINTER(C.c_uint16)))
     return out
+
+
+def panorama_directions(w, h):
+    """GPUX_PanoramaDirections: the fp32 directions K20 samples along -> float32 [h][w][3] (host code, needs no GPU)."""
+    out = np.zeros((int(h), int(w), 3), np.float32)
+    if int(w) < 1 or int(h) < 1 or lib().GPUX_PanoramaDirections(int(w), int(h), out.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise ValueError("panorama_directions: extents are 1 .. 16384")
+    return out
+
+
+def cube_to_panorama(cube, mip=0, width=0, height=0, fmt=Format_RGBA32F):
+    """Level `mip` of an RGBA32F cube as a lat-long panorama (K20 through PBR_MakePanoramaFromCube; width 0: 4 n, height 0: width / 2)
+    -> float32 [h][w][4], or for fmt=Format_RGBA16F the half bit patterns as uint16 [h][w][4]."""
+    L = lib()
+    pano = L.PBR_MakePanoramaFromCube(cube, mip, width, height, fmt)
+    if not pano:
+        raise RuntimeError("PBR_MakePanoramaFromCube failed")
+    try:
+        out = read_mip(pano, 0)
+    finally:
+        L.GPU_DestroyTexture(pano)
+    return out.view(np.uint16) if fmt == Format_RGBA16F else out
