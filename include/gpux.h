@@ -104,6 +104,27 @@ GPU_API void GPUX_OpCubeToPanorama(GPU_Graph* graph, GPU_Texture* cube, uint32_t
  * pure host code, callable without GPU_Init.  For tools that must find the pixel of a direction, and for tests.  0 on success, 1 for a
  * NULL pointer or an extent outside 1 .. 16384. */
 GPU_API int GPUX_PanoramaDirections(uint32_t width, uint32_t height, float* xyz);
+/* K21: faces [face0, face1) x rows [row0, row1) of level dst_mip of an RGBA32F cubemap from ANOTHER RGBA32F cubemap and its mip chain
+ * by GGX importance sampling with filtered lookups (csrc/prefilter_ggx_core.h): sample_count (1 .. 4096) GGX-distributed
+ * light directions for V = N = the texel's direction at `roughness` (0 < r <= 1), each a trilinear seamless sample of env_cube at the
+ * level whose texel solid angle matches the sample's, plus lod_bias (finite; 1 is the usual choice), weighted by N.L and divided by
+ * the weight sum; alpha 1.  Any face size, any number of source levels.  The sample table is built and uploaded when the op is
+ * recorded and belongs to the graph; the whole apron of env_cube is ensured when the op executes (its own timed entry,
+ * apron.prefilter_ggx, in front of K21.prefilter_ggx.mip<dst_mip>).  Reads env_cube and writes dst_cube, both followed.  A texel's
+ * bytes depend on neither the range it was dispatched in nor the run; texels outside the range are not touched.  Never captured:
+ * a graph holding this op submits the plain way under GPUX_SetGraphReplay(1).  Not part of the level-overlap regions of K3 / K4.
+ * With an odd sample_count at roughness 1 the middle sample has weight 0 and is dropped; sample_count 1 then keeps none and the
+ * level is 0 / 0.  Any bad argument (NULL, formats, not a cube, the same texture twice, a mip out of range, roughness outside (0, 1]
+ * or NaN, a count outside 1 .. 4096, a bias that is not finite, an empty or out-of-range face / row range, inside a render pass) is
+ * one error at record time with nothing recorded. */
+GPU_API void GPUX_OpPrefilterGGX(GPU_Graph* graph, GPU_Texture* env_cube, GPU_Texture* dst_cube, uint32_t dst_mip,
+                                 float roughness, uint32_t sample_count, float lod_bias,
+                                 uint32_t face0, uint32_t face1, uint32_t row0, uint32_t row1);
+/* The sample table K21 uses for a source of src_levels levels (1 .. the full chain) below a src_size^2 level 0: *kept entries
+ * {l.x, l.y, l.z, lod} in xyz_lod (room for 4 * sample_count floats) and the weight sum.  The arithmetic of the op's table (the same
+ * translation unit), pure host code, callable without GPU_Init.  0 on success, 1 for a NULL pointer or an argument the op refuses. */
+GPU_API int  GPUX_PrefilterGGXSamples(float roughness, uint32_t sample_count, uint32_t src_size, uint32_t src_levels,
+                                      float lod_bias, float* xyz_lod /* 4 * sample_count */, uint32_t* kept, float* wsum);
 GPU_API void* GPUX_TextureDevicePtr(GPU_Texture* texture, uint32_t mip_level);            /* for RCCL / interop */
 GPU_API void* GPUX_BufferDevicePtr(GPU_Buffer* buffer);
 GPU_API void* GPUX_GraphStream(GPU_Graph* graph);                                         /* hipStream_t */

@@ -66,6 +66,11 @@ typedef struct PBR_WorkUnit {
 void PBR_GenIrradianceMap(GPU_Texture* tex_env_cube, GPU_Texture* irradiance_map);           /* render.cpp:505-540 */
 /* render.cpp:542-589; min_size = 16 reproduces the reference's `if (size < 16) break;`, 1 runs the whole chain */
 void PBR_GenPrefilteredEnvMap(GPU_Texture* tex_env_cube, GPU_Texture* tex_specular_env_map, uint32_t min_size);
+/* The same map baked the way the lighting pass reads it (K21, GPUX_OpPrefilterGGX; no reference counterpart): level 0 is the same
+ * copy, recorded the same way; level i >= 1 down to min_size is the GGX importance-sampled prefilter of the environment at roughness
+ * min(1, i / 4) -- lighting_pass.glsl:699 fetches lod = roughness * 4 -- with sample_count (1 .. 4096) samples per texel and lod bias 1,
+ * one op per whole level, all in one graph.  Blocking.  Until a GGX split-sum LUT exists the map is paired with K1's Beckmann LUT. */
+void PBR_GenPrefilteredEnvMapGGX(GPU_Texture* tex_env_cube, GPU_Texture* tex_specular_env_map, uint32_t min_size, uint32_t sample_count);
 void PBR_GenBRDFIntegrationMap(GPU_Texture* brdf_lut);                                       /* render.cpp:591-619 */
 
 /* ---- K17 (no reference counterpart): the nine-coefficient spherical-harmonic form of the environment's diffuse
@@ -89,6 +94,10 @@ PBR_IBLPipelines* PBR_MakeIBLPipelines(void);
 void PBR_DestroyIBLPipelines(PBR_IBLPipelines* p);
 void PBR_RecordUnits(PBR_IBLPipelines* p, GPU_Graph* graph, GPU_DescriptorArena* arena, GPU_Texture* tex_env_cube,
                      const PBR_IBLMaps* maps, const PBR_WorkUnit* units, uint32_t unit_count);
+/* One level of PBR_GenPrefilteredEnvMap's graph: the descriptor set from `arena`, the prefilter pipeline, the level as push constant and
+ * the reference's size / 8 dispatch.  For host code that records the bake's levels itself (PBR_GenPrefilteredEnvMapGGX). */
+void PBR_RecordPrefilterLevel(PBR_IBLPipelines* p, GPU_Graph* graph, GPU_DescriptorArena* arena, GPU_Texture* tex_env_cube,
+                              GPU_Texture* tex_specular_env_map, uint32_t mip_level);
 
 /* Splits the precompute (prefilter mips down to min_size, optionally irradiance) over `world` ranks: the rows of
  * the big levels, laid end to end and weighted with the measured time per sample evaluation of their level, are cut into

@@ -508,6 +508,16 @@ int pbrk_bc6h_decode(const void* blocks, int width, int height, int layers, void
 int pbrk_cube_to_panorama(const void* bordered_level, int n, const void* table, void* out,
                           int out_format /* PBRK_FMT_RGBA32F / PBRK_FMT_RGBA16F */, int w, int h, void* stream);
 
+/* ---- K21: faces [face0, face1) x rows [y0, y1) of one out_size^2 level of the specular cube by GGX importance sampling with filtered
+ *      lookups.  src_bordered: the bordered twin of the whole source cube, level 0 first (pbrk_border_build; the
+ *      levels the table names must hold their apron).  table: device uint4[2 * kept], per kept sample {l.x, l.y, l.z, f} as fp32 bits
+ *      and {pbrk_bordered_level_offset and size of level l0, the same of level l1}, f the blend towards l1; wsum: the fp32 sum of
+ *      the l.z.  out: the whole level, [6][out_size][out_size] RGBA32F; alpha 1; texels outside the range are not touched.  A
+ *      texel's bytes do not depend on the range.  kept 0 .. 4096 (0: 0 / 0), out_size 1 .. 16384; anything else is PBRK_E_ARG with
+ *      nothing launched.  Contract: csrc/prefilter_ggx_core.h, DESIGN.md K21. ---- */
+int pbrk_prefilter_ggx(const void* src_bordered, const void* table, int kept, float wsum, void* out, int out_size,
+                       int face0, int face1, int y0, int y1, void* stream);
+
 /* ---- diagnostics: the device samplers of the widened passes evaluated at caller-supplied coordinates, so that tests can feed them
  *      NaN / inf / 1e30 / boundary values directly (a ray that has marched far away must never become an out-of-bounds read).
  *      which: 0 = LIGHTGRID (RGBA16F n^3, coords xyz), 1 = sampler2DShadow (R32F w x h, coords u, v, ref; result in out[0]),

@@ -24,6 +24,7 @@
 #include "gpux.h"
 #include "pbr_kernels.h"
 #include "panorama_core.h"
+#include "prefilter_ggx_core.h"
 
 // ------------------------------------------------------------------------------------------
 // errors
@@ -109,7 +110,7 @@ struct GPU_GraphicsPipeline { GPU_PipelineLayout* layout; GPU_RenderPass* pass; 
                               const struct RasterKind* raster = nullptr; /* K12 / K13 / K14: the row of its raster kind */
                               BufferImpl* sh9_buf = nullptr; uint32_t sh9_offset = 0; /* GPUX_SetShadeSH9 */ };
 
-enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster, Op_CopyDecodedT2B, Op_ProjectSH9, Op_IrradianceSH9, Op_EncodeBC6H, Op_DecodeBC6H, Op_CubeToPanorama };
+enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster, Op_CopyDecodedT2B, Op_ProjectSH9, Op_IrradianceSH9, Op_EncodeBC6H, Op_DecodeBC6H, Op_CubeToPanorama, Op_PrefilterGGX };
 // one draw of a raster job: job triangles from first_tri on, matrices from the set's GLOBALS, the buffers and the target its kind
 // names (K12 / K13: the buffers bound at the draw; K14: SSBO0 / SSBO1 of the set, first_index = its first vertex) and the pushed
 // constants (K13 reads them: the skybox rebinds both inside the pass)
@@ -135,6 +136,7 @@ struct Op {
     float clear[4]; uint32_t cleari[4]; int clear_mode = 0;
     uint32_t quality = 0;                          // Op_EncodeBC6H: GPUX_BC6H_OneRegion / GPUX_BC6H_TwoRegions
     const void* pano_table = nullptr;              // Op_CubeToPanorama: the op's column / row table (GPU_Graph::pano)
+    const void* ggx_table = nullptr; uint32_t ggx_kept = 0; float ggx_wsum = 0.0f;   // Op_PrefilterGGX: its sample table (GPU_Graph::pano too)
     // submit-time folding (fold_blits): a 1:1 blit whose copy is consumed only by an additive bloom draw onto its target is not
     // executed; that draw takes the blend operand from the blit's source instead
     bool folded = false;
@@ -174,7 +176,7 @@ struct GPU_Graph {
     int raster_op = -1;                            // index in ops of the raster job of the open render pass (-1: none yet)
     std::vector<RasterScratch> raster; size_t raster_used = 0;
     void* sh_scratch = nullptr; size_t sh_scratch_bytes = 0;   // K17 partials (GPUX_OpProjectSH9): sized at record time, kept across submissions
-    // K20 tables (GPUX_OpCubeToPanorama), one per recorded op: allocated and filled at record time, handed out again after a reset
+    // K20 / K21 tables (GPUX_OpCubeToPanorama, GPUX_OpPrefilterGGX), one per recorded op: allocated and filled at record time, handed out again after a reset
     // (a table that is big enough is kept), freed with the graph
     struct PanoTable { void* dev = nullptr; size_t bytes = 0; };
     std::vector<PanoTable> pano; size_t pano_used = 0;
@@ -1701,6 +1703,23 @@ GPU_API void GPUX_OpDecodeBC6H(GPU_Graph* g, GPU_Buffer* src, uint32_t src_offse
     g->ops.push_back(op);
 }
 
+// The table of an op that brings one (K20, K21) is allocated and uploaded when the op is recorded, not at submit: nothing allocates
+// inside a submission, and the graph is idle while it records.  A slot of an earlier recording is used again; a slot in use is never
+// touched, so the ops recorded so far keep theirs.  NULL after one error.
+static const void* upload_op_table(GPU_Graph* g, const void* data, size_t bytes, const char* fn) {
+    if (g->pano_used == g->pano.size()) g->pano.push_back(GPU_Graph::PanoTable());
+    GPU_Graph::PanoTable& slot = g->pano[g->pano_used];
+    if (slot.bytes < bytes) {
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); gpu_fail("%s: allocation of the op's table (%zu bytes) failed", fn, bytes); return nullptr; }
+        (void)hipFree(slot.dev);
+        slot.dev = p; slot.bytes = bytes;
+    }
+    if (hipMemcpy(slot.dev, data, bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); gpu_fail("%s: upload of the op's table failed", fn); return nullptr; }
+    ++g->pano_used;
+    return slot.dev;
+}
+
 // ---- K20: one level of an RGBA32F cube -> one level of a 2-D RGBA32F / RGBA16F texture as a lat-long panorama ----
 // The directions of a w x h panorama, from the entries pano_fill_table writes: what the kernel forms from the uploaded table
 static void pano_directions(const double* table, int w, int h, float* xyz) {
@@ -1725,23 +1744,60 @@ GPU_API void GPUX_OpCubeToPanorama(GPU_Graph* g, GPU_Texture* cube, uint32_t src
                   "%s: the target must be a 2-D RGBA32F / RGBA16F texture", fn);
     const uint32_t n = mip_dim(cube->width, src_mip), w = mip_dim(dst->width, dst_mip), h = mip_dim(dst->height, dst_mip);
     GPU_REQUIRE_V(n <= PANO_MAX_EXTENT && w <= PANO_MAX_EXTENT && h <= PANO_MAX_EXTENT, "%s: levels above 16384 a side are not implemented", fn);
-    // the table is built, allocated and uploaded here, not at submit: nothing allocates inside a submission, and the graph is idle while
-    // it records.  A slot of an earlier recording is used again; a slot in use is never touched, so the ops recorded so far keep theirs
     std::vector<double> table(2 * ((size_t)w + h));
     pano_fill_table((int)w, (int)h, table.data());
-    const size_t bytes = table.size() * sizeof(double);
-    if (g->pano_used == g->pano.size()) g->pano.push_back(GPU_Graph::PanoTable());
-    GPU_Graph::PanoTable& slot = g->pano[g->pano_used];
-    if (slot.bytes < bytes) {
-        void* p = nullptr;
-        if (hipMalloc(&p, bytes) != hipSuccess) { (void)hipGetLastError(); gpu_fail("%s: allocation of the direction table (%zu bytes) failed", fn, bytes); return; }
-        (void)hipFree(slot.dev);
-        slot.dev = p; slot.bytes = bytes;
-    }
-    if (hipMemcpy(slot.dev, table.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); gpu_fail("%s: upload of the direction table failed", fn); return; }
-    ++g->pano_used;
+    const void* dev = upload_op_table(g, table.data(), table.size() * sizeof(double), fn);
+    if (!dev) return;
     Op op; op.kind = Op_CubeToPanorama; op.name = "K20.cube_to_panorama";
-    op.tex = (TextureImpl*)cube; op.mip = src_mip; op.tex2 = (TextureImpl*)dst; op.mip2 = dst_mip; op.pano_table = slot.dev;
+    op.tex = (TextureImpl*)cube; op.mip = src_mip; op.tex2 = (TextureImpl*)dst; op.mip2 = dst_mip; op.pano_table = dev;
+    g->ops.push_back(op);
+}
+
+// ---- K21: one level of an RGBA32F cube from another RGBA32F cube by GGX importance sampling with filtered lookups ----
+static bool ggx_args_ok(float roughness, uint32_t sample_count, float lod_bias) {
+    return roughness > 0.0f && roughness <= 1.0f && sample_count >= 1 && sample_count <= PGGX_MAX_SAMPLES && isfinite(lod_bias);
+}
+GPU_API int GPUX_PrefilterGGXSamples(float roughness, uint32_t sample_count, uint32_t src_size, uint32_t src_levels, float lod_bias,
+                                     float* xyz_lod, uint32_t* kept, float* wsum) {
+    if (!xyz_lod || !kept || !wsum || !ggx_args_ok(roughness, sample_count, lod_bias) || src_size < 1 || src_size > 16384 ||
+        src_levels < 1 || src_levels > (uint32_t)pbrk_mip_count((int)src_size, (int)src_size)) return 1;
+    *kept = pggx_fill_table(roughness, sample_count, src_size, src_levels, lod_bias, xyz_lod, wsum);
+    return 0;
+}
+// op.tex = the source cube, op.tex2 / op.mip2 = the target level, faces [face0, face1) x rows [row0, row1), op.ggx_* = its table
+GPU_API void GPUX_OpPrefilterGGX(GPU_Graph* g, GPU_Texture* env_cube, GPU_Texture* dst_cube, uint32_t dst_mip, float roughness,
+                                 uint32_t sample_count, float lod_bias, uint32_t face0, uint32_t face1, uint32_t row0, uint32_t row1) {
+    REC_GUARD(g);
+    const char* fn = "GPUX_OpPrefilterGGX";
+    GPU_REQUIRE_V(g->in_pass == nullptr, "%s: inside a render pass", fn);
+    GPU_REQUIRE_V(env_cube && dst_cube && env_cube != dst_cube && dst_mip < dst_cube->mip_level_count, "%s: bad arguments (NULL, the source as its own target, or a mip out of range)", fn);
+    GPU_REQUIRE_V(is_f4_cube((TextureImpl*)env_cube) && is_f4_cube((TextureImpl*)dst_cube), "%s: source and target must be square RGBA32F cubemaps", fn);
+    GPU_REQUIRE_V(ggx_args_ok(roughness, sample_count, lod_bias), "%s: roughness %g outside (0, 1], %u samples outside 1 .. %d, or lod_bias %g not finite", fn,
+                  (double)roughness, sample_count, PGGX_MAX_SAMPLES, (double)lod_bias);
+    const uint32_t size = mip_dim(dst_cube->width, dst_mip), W = env_cube->width, levels = env_cube->mip_level_count;
+    GPU_REQUIRE_V(face0 < face1 && face1 <= 6 && row0 < row1 && row1 <= size, "%s: empty or out-of-range faces [%u, %u) x rows [%u, %u) of a %u^2 level", fn,
+                  face0, face1, row0, row1, size);
+    GPU_REQUIRE_V(W <= 16384 && size <= 16384, "%s: levels above 16384 a side are not implemented", fn);
+    // the kernel's form of the table: per kept sample {l.x, l.y, l.z, f} and the two levels it blends, as offset and size inside the
+    // bordered twin.  floorf and the difference are exact, so f is the contract's lod - floorf(lod)
+    std::vector<float> e(4 * (size_t)sample_count);
+    float wsum = 0.0f;
+    const uint32_t kept = pggx_fill_table(roughness, sample_count, W, levels, lod_bias, e.data(), &wsum);
+    std::vector<uint32_t> table(8 * (size_t)kept + 8);                        // never empty: a table of no entries still has a slot
+    for (uint32_t i = 0; i < kept; ++i) {
+        const float lod = e[4 * i + 3], fl = floorf(lod), f = lod - fl;
+        const uint32_t l0 = (uint32_t)fl, l1 = l0 + 1 < levels ? l0 + 1 : levels - 1;
+        uint32_t* t = &table[8 * (size_t)i];
+        memcpy(t, &e[4 * i], 12); memcpy(t + 3, &f, 4);
+        t[4] = (uint32_t)pbrk_bordered_level_offset((int)W, (int)l0); t[5] = mip_dim(W, l0);
+        t[6] = (uint32_t)pbrk_bordered_level_offset((int)W, (int)l1); t[7] = mip_dim(W, l1);
+    }
+    const void* dev = upload_op_table(g, table.data(), table.size() * sizeof(uint32_t), fn);
+    if (!dev) return;
+    Op op; op.kind = Op_PrefilterGGX; op.name = "K21.prefilter_ggx.mip" + std::to_string(dst_mip);
+    op.tex = (TextureImpl*)env_cube; op.tex2 = (TextureImpl*)dst_cube; op.mip2 = dst_mip;
+    op.face0 = face0; op.face1 = face1; op.row0 = row0; op.row1 = row1;
+    op.ggx_table = dev; op.ggx_kept = kept; op.ggx_wsum = wsum;
     g->ops.push_back(op);
 }
 
@@ -2334,6 +2390,21 @@ static void exec_panorama(GPU_Graph* g, Op& op, size_t& ev_used) {
     });
 }
 
+// K21: the whole apron of the source where it is missing (its own timed entry: a sample may name any level), then one launch
+static void exec_prefilter_ggx(GPU_Graph* g, Op& op, size_t& ev_used) {
+    TextureImpl* env = op.tex;
+    if (!apron_ready(env, 0)) {
+        timed(g, "apron.prefilter_ggx", ev_used, [&] { ensure_bordered(env, g->cur, 0); });
+        if (!apron_ready(env, 0)) return;
+    }
+    void* out = (char*)op.tex2->dev + op.tex2->mip_offset[op.mip2];
+    timed(g, op.name, ev_used, [&] {
+        int rc = pbrk_prefilter_ggx(env->derived.bordered, op.ggx_table, (int)op.ggx_kept, op.ggx_wsum, out, (int)mip_dim(op.tex2->base.width, op.mip2),
+                                    (int)op.face0, (int)op.face1, (int)op.row0, (int)op.row1, g->cur);
+        if (rc != PBRK_OK) gpu_fail("%s launch failed (%d)", op.name.c_str(), rc);
+    });
+}
+
 static void exec_blit(GPU_Graph* g, Op& op, size_t& ev_used) {
     hipStream_t st = g->cur;
     if (op.folded) return;                                                 // its consumer reads the source (fold_blits)
@@ -2457,7 +2528,7 @@ static OpEffects op_effects(const Op& op) {
     case Op_CopyB2T: case Op_IrradianceSH9: case Op_DecodeBC6H: e.write(op.tex); e.unfollowed = true; break;   // from a buffer
     case Op_CopyT2B: case Op_CopyDecodedT2B: case Op_ProjectSH9: case Op_EncodeBC6H: e.read(op.tex); e.unfollowed = true; break;   // into one
     case Op_CopyB2B: e.unfollowed = true; break;
-    case Op_CubeToPanorama: e.read(op.tex); e.write(op.tex2); break;          // its table belongs to the graph and is written at record time only
+    case Op_CubeToPanorama: case Op_PrefilterGGX: e.read(op.tex); e.write(op.tex2); break;   // their tables belong to the graph and are written at record time only
     }
     return e;
 }
@@ -2484,6 +2555,7 @@ static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
     case Op_EncodeBC6H: exec_bc6h(g, op, ev_used); break;
     case Op_DecodeBC6H: exec_bc6h_decode(g, op, ev_used); break;
     case Op_CubeToPanorama: exec_panorama(g, op, ev_used); break;
+    case Op_PrefilterGGX: exec_prefilter_ggx(g, op, ev_used); break;
     }
     const OpEffects e = op_effects(op);                                        // whatever was built from the old bytes is stale now
     for (int i = 0; i < e.n_writes; ++i) texture_written(e.writes[i]);
@@ -2508,7 +2580,7 @@ static bool op_replayable(const Op& op) {
     case Op_ProjectSH9: case Op_IrradianceSH9: return true;                   // plain launches on device-visible pointers; the scratch exists since recording
     case Op_EncodeBC6H: return true;                                          // one plain launch, texture -> device-visible buffer
     case Op_DecodeBC6H: return true;                                          // the same, buffer -> texture
-    case Op_CubeToPanorama: return false;                                     // may build the cube's apron (allocation) when it executes
+    case Op_CubeToPanorama: case Op_PrefilterGGX: return false;               // may build the cube's apron (allocation) when they execute
     case Op_Clear: return fill_texel_ok(op.tex->texel_bytes);
     case Op_Shade: {
         if (is_post_kernel(op.gpipe->kernel)) return true;

@@ -2,7 +2,7 @@
  * pbr_demo.c -- headless C driver of the hot path through the GPU_* boundary (what main.cpp:35-51 +
  * HotreloadShaders + BuildRenderCommands do for this path, without window / mesh import / raster passes).
  *
- *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster [gridview]]]]] [sh9 FILE] [dds|dds2 PREFIX] [ddsin PREFIX] [sh9shade] [pano PREFIX]
+ *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster [gridview]]]]] [sh9 FILE] [dds|dds2 PREFIX] [ddsin PREFIX] [sh9shade] [pano PREFIX] [ggx N]
  *
  * Loads a vertical-strip HDR cube (asset_import.cpp:17-27), runs the IBL precompute (render.cpp:505-619),
  * shades a flat synthetic G-buffer (a metallic floor under the sky), then runs three frames of the per-frame chain
@@ -30,6 +30,9 @@
  * With `pano PREFIX` as the LAST two arguments (after all of the above, `sh9shade` included) the baked maps are also written as lat-long
  * panoramas one can look at (K20, PBR_WritePanoramaHDR at the default extent 4 n x 2 n): PREFIX_irradiance.hdr and PREFIX_specular_mipN.hdr
  * for every level that has a specular_mipN_sum line, and each file's extent is printed as pano_extent; the other lines stay as they are.
+ * With `ggx N` as the LAST two arguments (after all of the above, `pano PREFIX` included) the specular map is baked by K21
+ * (PBR_GenPrefilteredEnvMapGGX, N samples per texel): level 0 is the same copy, the levels below it are the GGX prefilter at the
+ * roughness the lighting pass reads them at.  Every line keeps its name; specular_mip0_sum keeps its value.
  */
 #include "pbr_host.h"
 
@@ -120,7 +123,11 @@ int main(int argc, char** argv) {
     const char* dds_prefix = NULL;
     const char* ddsin_prefix = NULL;
     const char* pano_prefix = NULL;
-    int sh9shade = 0, dds_format = PBR_DDS_OUT_BC6H_UF16;
+    int sh9shade = 0, dds_format = PBR_DDS_OUT_BC6H_UF16, ggx_samples = 0;
+    if (argc >= 4 && strcmp(argv[argc - 2], "ggx") == 0) {
+        ggx_samples = atoi(argv[argc - 1]); argc -= 2;
+        if (ggx_samples < 1 || ggx_samples > 4096) { fprintf(stderr, "ggx: the sample count is 1 .. 4096\n"); return 2; }
+    }
     if (argc >= 4 && strcmp(argv[argc - 2], "pano") == 0) { pano_prefix = argv[argc - 1]; argc -= 2; }
     if (argc >= 3 && strcmp(argv[argc - 1], "sh9shade") == 0) { sh9shade = 1; argc -= 1; }
     if (argc >= 4 && strcmp(argv[argc - 2], "ddsin") == 0) { ddsin_prefix = argv[argc - 1]; argc -= 2; }
@@ -152,7 +159,8 @@ int main(int argc, char** argv) {
     } else {
         PBR_MakeIBLMaps(&maps, irr, lut, spec);                              /* render.cpp:794-796 */
         PBR_GenIrradianceMap(tex_env_cube, maps.irradiance_map);             /* render.cpp:505-540 */
-        PBR_GenPrefilteredEnvMap(tex_env_cube, maps.tex_specular_env_map, min_size);   /* render.cpp:542-589 */
+        if (ggx_samples) PBR_GenPrefilteredEnvMapGGX(tex_env_cube, maps.tex_specular_env_map, min_size, (uint32_t)ggx_samples);
+        else PBR_GenPrefilteredEnvMap(tex_env_cube, maps.tex_specular_env_map, min_size);   /* render.cpp:542-589 */
         PBR_GenBRDFIntegrationMap(maps.brdf_lut);                            /* render.cpp:591-619 */
     }
 

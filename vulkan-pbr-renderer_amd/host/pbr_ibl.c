@@ -99,6 +99,22 @@ void PBR_GenIrradianceMap(GPU_Texture* tex_env_cube, GPU_Texture* irradiance_map
     PBR_DestroyIBLPipelines(p);
 }
 
+/* one level of render.cpp:564-580 */
+void PBR_RecordPrefilterLevel(PBR_IBLPipelines* p, GPU_Graph* graph, GPU_DescriptorArena* descriptor_arena, GPU_Texture* tex_env_cube,
+                              GPU_Texture* spec, uint32_t i) {
+    uint32_t size = spec->width >> i; if (size < 1) size = 1;
+    GPU_DescriptorSet* desc_set = GPU_InitDescriptorSet(descriptor_arena, p->cube_layout);
+    GPU_SetSamplerBinding(desc_set, p->sampler_binding, GPU_SamplerLinearClamp());
+    GPU_SetTextureBinding(desc_set, p->tex_env_cube_binding, tex_env_cube);
+    GPU_SetStorageImageBinding(desc_set, p->output_binding, spec, i);
+    GPU_FinalizeDescriptorSet(desc_set);
+
+    GPU_OpBindComputePipeline(graph, p->prefilter);
+    GPU_OpBindComputeDescriptorSet(graph, desc_set);
+    GPU_OpPushComputeConstants(graph, p->cube_layout, &i, sizeof(i));
+    GPU_OpDispatch(graph, group_count(size), group_count(size), 1);
+}
+
 /* render.cpp:542-589 */
 void PBR_GenPrefilteredEnvMap(GPU_Texture* tex_env_cube, GPU_Texture* spec, uint32_t min_size) {
     PBR_IBLPipelines* p = PBR_MakeIBLPipelines();
@@ -109,17 +125,7 @@ void PBR_GenPrefilteredEnvMap(GPU_Texture* tex_env_cube, GPU_Texture* spec, uint
     uint32_t size = spec->width;
     for (uint32_t i = 0; i < spec->mip_level_count; i++) {
         if (size < min_size) break;                        /* reference: `if (size < 16) break;` */
-
-        GPU_DescriptorSet* desc_set = GPU_InitDescriptorSet(descriptor_arena, p->cube_layout);
-        GPU_SetSamplerBinding(desc_set, p->sampler_binding, GPU_SamplerLinearClamp());
-        GPU_SetTextureBinding(desc_set, p->tex_env_cube_binding, tex_env_cube);
-        GPU_SetStorageImageBinding(desc_set, p->output_binding, spec, i);
-        GPU_FinalizeDescriptorSet(desc_set);
-
-        GPU_OpBindComputePipeline(graph, p->prefilter);
-        GPU_OpBindComputeDescriptorSet(graph, desc_set);
-        GPU_OpPushComputeConstants(graph, p->cube_layout, &i, sizeof(i));
-        GPU_OpDispatch(graph, group_count(size), group_count(size), 1);
+        PBR_RecordPrefilterLevel(p, graph, descriptor_arena, tex_env_cube, spec, i);
         size /= 2;
     }
     GPU_GraphSubmit(graph);

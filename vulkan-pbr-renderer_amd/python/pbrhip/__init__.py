@@ -376,6 +376,12 @@ PROTOTYPES = {
     "GPUX_PanoramaDirections": (C.c_int, [U32, U32, C.POINTER(C.c_float)]),
     "PBR_MakePanoramaFromCube": (TexP, [TexP, U32, U32, U32, C.c_int]),
     "PBR_WritePanoramaHDR": (C.c_int, [C.c_char_p, TexP, U32, U32, U32]),
+    # --- K21: GGX importance-sampled prefilter ---
+    "pbrk_prefilter_ggx": (C.c_int, [VP, VP, C.c_int, C.c_float, VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP]),
+    "GPUX_OpPrefilterGGX": (None, [VP, TexP, TexP, U32, C.c_float, U32, C.c_float, U32, U32, U32, U32]),
+    "GPUX_PrefilterGGXSamples": (C.c_int, [C.c_float, U32, U32, U32, C.c_float, C.POINTER(C.c_float), C.POINTER(U32), C.POINTER(C.c_float)]),
+    "PBR_GenPrefilteredEnvMapGGX": (None, [TexP, TexP, U32, U32]),
+    "PBR_RecordPrefilterLevel": (None, [VP, VP, VP, TexP, TexP, U32]),
 }
 
 _LIB = None
@@ -765,3 +771,30 @@ def cube_to_panorama(cube, mip=0, width=0, height=0, fmt=Format_RGBA32F):
     finally:
         L.GPU_DestroyTexture(pano)
     return out.view(np.uint16) if fmt == Format_RGBA16F else out
+
+
+def prefilter_ggx_samples(roughness, samples, src_size, src_levels, lod_bias=1.0):
+    """GPUX_PrefilterGGXSamples: the table K21 uses -> (float32 [kept][4] of {l.x, l.y, l.z, lod}, wsum as np.float32); host code,
+    needs no GPU"""
+    n = int(samples)
+    out = np.zeros((max(n, 1), 4), np.float32)
+    kept, wsum = U32(0), C.c_float(0.0)
+    if n < 1 or n > 4096 or lib().GPUX_PrefilterGGXSamples(float(roughness), n, int(src_size), int(src_levels), float(lod_bias),
+                                                          out.ctypes.data_as(C.POINTER(C.c_float)), C.byref(kept), C.byref(wsum)) != 0:
+        raise ValueError("prefilter_ggx_samples: bad arguments")
+    return out[:kept.value].copy(), np.float32(wsum.value)
+
+
+def prefilter_ggx(env, dst, mip, roughness, samples, lod_bias=1.0, faces=(0, 6), rows=None):
+    """Level `mip` of the RGBA32F cube `dst` from the RGBA32F cube `env` by K21 (GPUX_OpPrefilterGGX in a graph of its own, blocking);
+    rows=None: the whole level."""
+    L = lib()
+    if rows is None:
+        rows = (0, max(1, dst.contents.width >> mip))
+    g = L.GPU_MakeGraph()
+    try:
+        L.GPUX_OpPrefilterGGX(g, env, dst, mip, float(roughness), int(samples), float(lod_bias), int(faces[0]), int(faces[1]), int(rows[0]), int(rows[1]))
+        L.GPU_GraphSubmit(g)
+        L.GPU_GraphWait(g)
+    finally:
+        L.GPU_DestroyGraph(g)
