@@ -125,6 +125,25 @@ GPU_API void GPUX_OpPrefilterGGX(GPU_Graph* graph, GPU_Texture* env_cube, GPU_Te
  * translation unit), pure host code, callable without GPU_Init.  0 on success, 1 for a NULL pointer or an argument the op refuses. */
 GPU_API int  GPUX_PrefilterGGXSamples(float roughness, uint32_t sample_count, uint32_t src_size, uint32_t src_levels,
                                       float lod_bias, float* xyz_lod /* 4 * sample_count */, uint32_t* kept, float* wsum);
+/* K22: rows [row0, row1) of level 0 of a 2-D RG16F / RG32F / RGBA32F texture as the split-sum BRDF LUT of the GGX lobe by importance
+ * sampling (Karis' IntegrateBRDF; csrc/brdf_lut_ggx_core.h), the LUT that goes with K21's specular cube: texel (x, y)
+ * holds (A, B) -- specular = prefiltered * (F0 * A + B) -- at N.V = (x + .5) / width and roughness (y + .5) / height, from sample_count
+ * (1 .. 4096) GGX-distributed half vectors; RGBA32F stores (A, B, 0, 1).  Any extent from 1 to 4096 on each axis, square or not.
+ * `visibility` selects the geometry term.  The sample table is built and uploaded when the op is recorded and belongs to the graph;
+ * nothing is allocated when the op executes, so the op may be captured under GPUX_SetGraphReplay(1).  Writes lut_tex, followed: the
+ * sampler twin the lighting pass built from the old bytes is dropped.  Timed as K22.brdf_lut_ggx.  A texel's bytes depend on neither
+ * the rows it was dispatched with nor the run; texels outside the rows are not touched.  Any bad argument (NULL, another format, a cube,
+ * layered or 3-D texture, an extent above 4096, a count outside 1 .. 4096, an unknown visibility, an empty or out-of-range row range,
+ * inside a render pass) is one error at record time with nothing recorded. */
+typedef enum GPUX_BrdfLutVisibility {
+    GPUX_BrdfLut_SmithSchlick = 0,      /* G1(N.V) G1(N.L), G1(c) = c / (c (1 - k) + k), k = roughness^2 / 2: lighting_pass.glsl's GeometrySmithIBL */
+    GPUX_BrdfLut_SmithCorrelated = 1    /* the height-correlated Smith term (Heitz), as in Filament's DFG */
+} GPUX_BrdfLutVisibility;
+GPU_API void GPUX_OpBrdfLutGGX(GPU_Graph* graph, GPU_Texture* lut_tex, uint32_t sample_count, uint32_t visibility, uint32_t row0, uint32_t row1);
+/* The sample table K22 uses: {xi1, cos phi, sin phi} per sample into xi_cos_sin (room for 3 * sample_count floats).  The arithmetic of
+ * the op's table (the same translation unit), pure host code, callable without GPU_Init.  0 on success, 1 for a NULL pointer or a count
+ * outside 1 .. 4096. */
+GPU_API int  GPUX_BrdfLutGGXSamples(uint32_t sample_count, float* xi_cos_sin /* 3 * sample_count */);
 GPU_API void* GPUX_TextureDevicePtr(GPU_Texture* texture, uint32_t mip_level);            /* for RCCL / interop */
 GPU_API void* GPUX_BufferDevicePtr(GPU_Buffer* buffer);
 GPU_API void* GPUX_GraphStream(GPU_Graph* graph);                                         /* hipStream_t */

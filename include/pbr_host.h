@@ -69,9 +69,14 @@ void PBR_GenPrefilteredEnvMap(GPU_Texture* tex_env_cube, GPU_Texture* tex_specul
 /* The same map baked the way the lighting pass reads it (K21, GPUX_OpPrefilterGGX; no reference counterpart): level 0 is the same
  * copy, recorded the same way; level i >= 1 down to min_size is the GGX importance-sampled prefilter of the environment at roughness
  * min(1, i / 4) -- lighting_pass.glsl:699 fetches lod = roughness * 4 -- with sample_count (1 .. 4096) samples per texel and lod bias 1,
- * one op per whole level, all in one graph.  Blocking.  Until a GGX split-sum LUT exists the map is paired with K1's Beckmann LUT. */
+ * one op per whole level, all in one graph.  Blocking.  Its split-sum partner is the LUT of PBR_GenBRDFIntegrationMapGGX (K22); PBR_GenBRDFIntegrationMap is K1's Beckmann LUT. */
 void PBR_GenPrefilteredEnvMapGGX(GPU_Texture* tex_env_cube, GPU_Texture* tex_specular_env_map, uint32_t min_size, uint32_t sample_count);
 void PBR_GenBRDFIntegrationMap(GPU_Texture* brdf_lut);                                       /* render.cpp:591-619 */
+/* The split-sum LUT of the GGX lobe by importance sampling (K22, GPUX_OpBrdfLutGGX; no reference counterpart): the partner of
+ * PBR_GenPrefilteredEnvMapGGX's map, sample_count (1 .. 4096) samples per texel, visibility a GPUX_BrdfLutVisibility
+ * (GPUX_BrdfLut_SmithSchlick is the term lighting_pass.glsl:56-61 evaluates).  Any 2-D RG16F / RG32F / RGBA32F texture up to 4096 a
+ * side; one op over all rows.  Blocking. */
+void PBR_GenBRDFIntegrationMapGGX(GPU_Texture* brdf_lut, uint32_t sample_count, uint32_t visibility);
 
 /* ---- K17 (no reference counterpart): the nine-coefficient spherical-harmonic form of the environment's diffuse
  * lighting -- the 27 numbers other IBL bakers emit and engines consume in place of an irradiance cube.  Contract (csrc/sh_core.h):

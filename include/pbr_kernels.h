@@ -518,6 +518,14 @@ int pbrk_cube_to_panorama(const void* bordered_level, int n, const void* table, 
 int pbrk_prefilter_ggx(const void* src_bordered, const void* table, int kept, float wsum, void* out, int out_size,
                        int face0, int face1, int y0, int y1, void* stream);
 
+/* ---- K22: rows [y0, y1) of a w x h split-sum BRDF LUT by GGX importance sampling: texel (x, y) is (A, B) at
+ *      N.V = (x + .5) / w and roughness (y + .5) / h, RGBA32F stores (A, B, 0, 1).  table: device float[3 * nsamples], {xi1, cos phi,
+ *      sin phi} per sample (GPUX_BrdfLutGGXSamples).  visibility: 0 Smith-Schlick with k = a / 2, 1 height-correlated Smith.  Texels
+ *      outside the rows are not touched; a texel's bytes do not depend on the rows.  w, h 1 .. 4096, nsamples 1 .. 4096; anything else
+ *      is PBRK_E_ARG / PBRK_E_FORMAT with nothing launched.  Contract: csrc/brdf_lut_ggx_core.h, DESIGN.md K22. ---- */
+int pbrk_brdf_lut_ggx(void* out, int out_format /* PBRK_FMT_RG16F / RG32F / RGBA32F */, int w, int h, int nsamples, int visibility,
+                      const void* table, int y0, int y1, void* stream);
+
 /* ---- diagnostics: the device samplers of the widened passes evaluated at caller-supplied coordinates, so that tests can feed them
  *      NaN / inf / 1e30 / boundary values directly (a ray that has marched far away must never become an out-of-bounds read).
  *      which: 0 = LIGHTGRID (RGBA16F n^3, coords xyz), 1 = sampler2DShadow (R32F w x h, coords u, v, ref; result in out[0]),

@@ -25,6 +25,7 @@
 #include "pbr_kernels.h"
 #include "panorama_core.h"
 #include "prefilter_ggx_core.h"
+#include "brdf_lut_ggx_core.h"
 
 // ------------------------------------------------------------------------------------------
 // errors
@@ -110,7 +111,7 @@ struct GPU_GraphicsPipeline { GPU_PipelineLayout* layout; GPU_RenderPass* pass; 
                               const struct RasterKind* raster = nullptr; /* K12 / K13 / K14: the row of its raster kind */
                               BufferImpl* sh9_buf = nullptr; uint32_t sh9_offset = 0; /* GPUX_SetShadeSH9 */ };
 
-enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster, Op_CopyDecodedT2B, Op_ProjectSH9, Op_IrradianceSH9, Op_EncodeBC6H, Op_DecodeBC6H, Op_CubeToPanorama, Op_PrefilterGGX };
+enum OpKind { Op_Dispatch, Op_Shade, Op_MipGen, Op_CopyB2T, Op_CopyT2B, Op_CopyB2B, Op_Blit, Op_Clear, Op_Raster, Op_CopyDecodedT2B, Op_ProjectSH9, Op_IrradianceSH9, Op_EncodeBC6H, Op_DecodeBC6H, Op_CubeToPanorama, Op_PrefilterGGX, Op_BrdfLutGGX };
 // one draw of a raster job: job triangles from first_tri on, matrices from the set's GLOBALS, the buffers and the target its kind
 // names (K12 / K13: the buffers bound at the draw; K14: SSBO0 / SSBO1 of the set, first_index = its first vertex) and the pushed
 // constants (K13 reads them: the skybox rebinds both inside the pass)
@@ -137,6 +138,7 @@ struct Op {
     uint32_t quality = 0;                          // Op_EncodeBC6H: GPUX_BC6H_OneRegion / GPUX_BC6H_TwoRegions
     const void* pano_table = nullptr;              // Op_CubeToPanorama: the op's column / row table (GPU_Graph::pano)
     const void* ggx_table = nullptr; uint32_t ggx_kept = 0; float ggx_wsum = 0.0f;   // Op_PrefilterGGX: its sample table (GPU_Graph::pano too)
+    const void* lut_table = nullptr; uint32_t lut_samples = 0, lut_visibility = 0;   // Op_BrdfLutGGX: its sample table (the same), count and term
     // submit-time folding (fold_blits): a 1:1 blit whose copy is consumed only by an additive bloom draw onto its target is not
     // executed; that draw takes the blend operand from the blit's source instead
     bool folded = false;
@@ -176,7 +178,7 @@ struct GPU_Graph {
     int raster_op = -1;                            // index in ops of the raster job of the open render pass (-1: none yet)
     std::vector<RasterScratch> raster; size_t raster_used = 0;
     void* sh_scratch = nullptr; size_t sh_scratch_bytes = 0;   // K17 partials (GPUX_OpProjectSH9): sized at record time, kept across submissions
-    // K20 / K21 tables (GPUX_OpCubeToPanorama, GPUX_OpPrefilterGGX), one per recorded op: allocated and filled at record time, handed out again after a reset
+    // K20 / K21 / K22 tables (GPUX_OpCubeToPanorama, GPUX_OpPrefilterGGX, GPUX_OpBrdfLutGGX), one per recorded op: allocated and filled at record time, handed out again after a reset
     // (a table that is big enough is kept), freed with the graph
     struct PanoTable { void* dev = nullptr; size_t bytes = 0; };
     std::vector<PanoTable> pano; size_t pano_used = 0;
@@ -1703,7 +1705,7 @@ GPU_API void GPUX_OpDecodeBC6H(GPU_Graph* g, GPU_Buffer* src, uint32_t src_offse
     g->ops.push_back(op);
 }
 
-// The table of an op that brings one (K20, K21) is allocated and uploaded when the op is recorded, not at submit: nothing allocates
+// The table of an op that brings one (K20, K21, K22) is allocated and uploaded when the op is recorded, not at submit: nothing allocates
 // inside a submission, and the graph is idle while it records.  A slot of an earlier recording is used again; a slot in use is never
 // touched, so the ops recorded so far keep theirs.  NULL after one error.
 static const void* upload_op_table(GPU_Graph* g, const void* data, size_t bytes, const char* fn) {
@@ -1798,6 +1800,37 @@ GPU_API void GPUX_OpPrefilterGGX(GPU_Graph* g, GPU_Texture* env_cube, GPU_Textur
     op.tex = (TextureImpl*)env_cube; op.tex2 = (TextureImpl*)dst_cube; op.mip2 = dst_mip;
     op.face0 = face0; op.face1 = face1; op.row0 = row0; op.row1 = row1;
     op.ggx_table = dev; op.ggx_kept = kept; op.ggx_wsum = wsum;
+    g->ops.push_back(op);
+}
+
+// ---- K22: rows of a 2-D RG16F / RG32F / RGBA32F texture as the GGX split-sum BRDF LUT ----
+GPU_API int GPUX_BrdfLutGGXSamples(uint32_t sample_count, float* xi_cos_sin) {
+    if (!xi_cos_sin || sample_count < 1 || sample_count > BLG_MAX_SAMPLES) return 1;
+    blg_fill_table(sample_count, xi_cos_sin);
+    return 0;
+}
+// op.tex = the map, rows [row0, row1), op.lut_* = its table, count and visibility term
+GPU_API void GPUX_OpBrdfLutGGX(GPU_Graph* g, GPU_Texture* lut_tex, uint32_t sample_count, uint32_t visibility, uint32_t row0, uint32_t row1) {
+    REC_GUARD(g);
+    const char* fn = "GPUX_OpBrdfLutGGX";
+    GPU_REQUIRE_V(g->in_pass == nullptr, "%s: inside a render pass", fn);
+    GPU_REQUIRE_V(lut_tex, "%s: the texture is NULL", fn);
+    GPU_REQUIRE_V((lut_tex->format == GPU_Format_RG16F || lut_tex->format == GPU_Format_RG32F || lut_tex->format == GPU_Format_RGBA32F) &&
+                  !(lut_tex->flags & GPU_TextureFlag_Cubemap) && lut_tex->layer_count == 1 && lut_tex->depth == 1,
+                  "%s: the target must be a 2-D RG16F / RG32F / RGBA32F texture", fn);
+    GPU_REQUIRE_V(lut_tex->width <= BLG_MAX_EXTENT && lut_tex->height <= BLG_MAX_EXTENT, "%s: a %u x %u map is above %d a side", fn,
+                  lut_tex->width, lut_tex->height, BLG_MAX_EXTENT);
+    GPU_REQUIRE_V(sample_count >= 1 && sample_count <= BLG_MAX_SAMPLES, "%s: %u samples outside 1 .. %d", fn, sample_count, BLG_MAX_SAMPLES);
+    GPU_REQUIRE_V(visibility == GPUX_BrdfLut_SmithSchlick || visibility == GPUX_BrdfLut_SmithCorrelated, "%s: unknown visibility term %u", fn, visibility);
+    GPU_REQUIRE_V(row0 < row1 && row1 <= lut_tex->height, "%s: empty or out-of-range rows [%u, %u) of a %u x %u map", fn, row0, row1,
+                  lut_tex->width, lut_tex->height);
+    std::vector<float> table(3 * (size_t)sample_count);
+    blg_fill_table(sample_count, table.data());
+    const void* dev = upload_op_table(g, table.data(), table.size() * sizeof(float), fn);
+    if (!dev) return;
+    Op op; op.kind = Op_BrdfLutGGX; op.name = "K22.brdf_lut_ggx";
+    op.tex = (TextureImpl*)lut_tex; op.row0 = row0; op.row1 = row1;
+    op.lut_table = dev; op.lut_samples = sample_count; op.lut_visibility = visibility;
     g->ops.push_back(op);
 }
 
@@ -2405,6 +2438,17 @@ static void exec_prefilter_ggx(GPU_Graph* g, Op& op, size_t& ev_used) {
     });
 }
 
+// K22: one launch on level 0; the table exists since recording, nothing is allocated
+static void exec_brdf_lut_ggx(GPU_Graph* g, Op& op, size_t& ev_used) {
+    const GPU_Texture& t = op.tex->base;
+    const int fmt = t.format == GPU_Format_RG16F ? PBRK_FMT_RG16F : (t.format == GPU_Format_RG32F ? PBRK_FMT_RG32F : PBRK_FMT_RGBA32F);
+    timed(g, op.name, ev_used, [&] {
+        int rc = pbrk_brdf_lut_ggx(op.tex->dev, fmt, (int)t.width, (int)t.height, (int)op.lut_samples, (int)op.lut_visibility, op.lut_table,
+                                   (int)op.row0, (int)op.row1, g->cur);
+        if (rc != PBRK_OK) gpu_fail("%s launch failed (%d)", op.name.c_str(), rc);
+    });
+}
+
 static void exec_blit(GPU_Graph* g, Op& op, size_t& ev_used) {
     hipStream_t st = g->cur;
     if (op.folded) return;                                                 // its consumer reads the source (fold_blits)
@@ -2524,7 +2568,7 @@ static OpEffects op_effects(const Op& op) {
         break;
     case Op_MipGen: e.read(op.tex); e.write(op.tex); break;
     case Op_Blit: e.read(op.tex); e.write(op.tex2); break;                     // folded too: its consumer stores the sum to tex2
-    case Op_Clear: e.write(op.tex); break;
+    case Op_Clear: case Op_BrdfLutGGX: e.write(op.tex); break;                 // K22 reads its table only: the graph's, written at record time
     case Op_CopyB2T: case Op_IrradianceSH9: case Op_DecodeBC6H: e.write(op.tex); e.unfollowed = true; break;   // from a buffer
     case Op_CopyT2B: case Op_CopyDecodedT2B: case Op_ProjectSH9: case Op_EncodeBC6H: e.read(op.tex); e.unfollowed = true; break;   // into one
     case Op_CopyB2B: e.unfollowed = true; break;
@@ -2556,6 +2600,7 @@ static void exec_op(GPU_Graph* g, Op& op, size_t& ev_used) {
     case Op_DecodeBC6H: exec_bc6h_decode(g, op, ev_used); break;
     case Op_CubeToPanorama: exec_panorama(g, op, ev_used); break;
     case Op_PrefilterGGX: exec_prefilter_ggx(g, op, ev_used); break;
+    case Op_BrdfLutGGX: exec_brdf_lut_ggx(g, op, ev_used); break;
     }
     const OpEffects e = op_effects(op);                                        // whatever was built from the old bytes is stale now
     for (int i = 0; i < e.n_writes; ++i) texture_written(e.writes[i]);
@@ -2580,6 +2625,7 @@ static bool op_replayable(const Op& op) {
     case Op_ProjectSH9: case Op_IrradianceSH9: return true;                   // plain launches on device-visible pointers; the scratch exists since recording
     case Op_EncodeBC6H: return true;                                          // one plain launch, texture -> device-visible buffer
     case Op_DecodeBC6H: return true;                                          // the same, buffer -> texture
+    case Op_BrdfLutGGX: return true;                                          // one plain launch; its table exists since recording
     case Op_CubeToPanorama: case Op_PrefilterGGX: return false;               // may build the cube's apron (allocation) when they execute
     case Op_Clear: return fill_texel_ok(op.tex->texel_bytes);
     case Op_Shade: {

@@ -2,7 +2,7 @@
  * pbr_demo.c -- headless C driver of the hot path through the GPU_* boundary (what main.cpp:35-51 +
  * HotreloadShaders + BuildRenderCommands do for this path, without window / mesh import / raster passes).
  *
- *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster [gridview]]]]] [sh9 FILE] [dds|dds2 PREFIX] [ddsin PREFIX] [sh9shade] [pano PREFIX] [ggx N]
+ *   pbr_demo <cube_strip.hdr> [irradiance_size lut_size specular_size min_size [width height [frame.ppm [raster [gridview]]]]] [sh9 FILE] [dds|dds2 PREFIX] [ddsin PREFIX] [sh9shade] [pano PREFIX] [ggx N | ggxpair N]
  *
  * Loads a vertical-strip HDR cube (asset_import.cpp:17-27), runs the IBL precompute (render.cpp:505-619),
  * shades a flat synthetic G-buffer (a metallic floor under the sky), then runs three frames of the per-frame chain
@@ -33,6 +33,9 @@
  * With `ggx N` as the LAST two arguments (after all of the above, `pano PREFIX` included) the specular map is baked by K21
  * (PBR_GenPrefilteredEnvMapGGX, N samples per texel): level 0 is the same copy, the levels below it are the GGX prefilter at the
  * roughness the lighting pass reads them at.  Every line keeps its name; specular_mip0_sum keeps its value.
+ * With `ggxpair N` in the same place the specular map is baked the same way and the BRDF LUT is its split-sum partner, K22's GGX LUT
+ * (PBR_GenBRDFIntegrationMapGGX, N samples per texel, the Smith-Schlick term the lighting pass evaluates), in place of K1's Beckmann
+ * LUT: against `ggx N` only lut_bits_sum and what is shaded with the LUT change.
  */
 #include "pbr_host.h"
 
@@ -123,10 +126,13 @@ int main(int argc, char** argv) {
     const char* dds_prefix = NULL;
     const char* ddsin_prefix = NULL;
     const char* pano_prefix = NULL;
-    int sh9shade = 0, dds_format = PBR_DDS_OUT_BC6H_UF16, ggx_samples = 0;
+    int sh9shade = 0, dds_format = PBR_DDS_OUT_BC6H_UF16, ggx_samples = 0, ggx_lut = 0;
     if (argc >= 4 && strcmp(argv[argc - 2], "ggx") == 0) {
         ggx_samples = atoi(argv[argc - 1]); argc -= 2;
         if (ggx_samples < 1 || ggx_samples > 4096) { fprintf(stderr, "ggx: the sample count is 1 .. 4096\n"); return 2; }
+    } else if (argc >= 4 && strcmp(argv[argc - 2], "ggxpair") == 0) {
+        ggx_samples = atoi(argv[argc - 1]); ggx_lut = 1; argc -= 2;
+        if (ggx_samples < 1 || ggx_samples > 4096) { fprintf(stderr, "ggxpair: the sample count is 1 .. 4096\n"); return 2; }
     }
     if (argc >= 4 && strcmp(argv[argc - 2], "pano") == 0) { pano_prefix = argv[argc - 1]; argc -= 2; }
     if (argc >= 3 && strcmp(argv[argc - 1], "sh9shade") == 0) { sh9shade = 1; argc -= 1; }
@@ -161,7 +167,8 @@ int main(int argc, char** argv) {
         PBR_GenIrradianceMap(tex_env_cube, maps.irradiance_map);             /* render.cpp:505-540 */
         if (ggx_samples) PBR_GenPrefilteredEnvMapGGX(tex_env_cube, maps.tex_specular_env_map, min_size, (uint32_t)ggx_samples);
         else PBR_GenPrefilteredEnvMap(tex_env_cube, maps.tex_specular_env_map, min_size);   /* render.cpp:542-589 */
-        PBR_GenBRDFIntegrationMap(maps.brdf_lut);                            /* render.cpp:591-619 */
+        if (ggx_lut) PBR_GenBRDFIntegrationMapGGX(maps.brdf_lut, (uint32_t)ggx_samples, GPUX_BrdfLut_SmithSchlick);
+        else PBR_GenBRDFIntegrationMap(maps.brdf_lut);                       /* render.cpp:591-619 */
     }
 
     printf("env_mip0_sum %.9e\n", checksum_texture_mip(tex_env_cube, 0, 1));

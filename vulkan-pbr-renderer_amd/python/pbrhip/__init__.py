@@ -382,6 +382,11 @@ PROTOTYPES = {
     "GPUX_PrefilterGGXSamples": (C.c_int, [C.c_float, U32, U32, U32, C.c_float, C.POINTER(C.c_float), C.POINTER(U32), C.POINTER(C.c_float)]),
     "PBR_GenPrefilteredEnvMapGGX": (None, [TexP, TexP, U32, U32]),
     "PBR_RecordPrefilterLevel": (None, [VP, VP, VP, TexP, TexP, U32]),
+    # --- K22: GGX split-sum BRDF LUT ---
+    "pbrk_brdf_lut_ggx": (C.c_int, [VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, VP, C.c_int, C.c_int, VP]),
+    "GPUX_OpBrdfLutGGX": (None, [VP, TexP, U32, U32, U32, U32]),
+    "GPUX_BrdfLutGGXSamples": (C.c_int, [U32, C.POINTER(C.c_float)]),
+    "PBR_GenBRDFIntegrationMapGGX": (None, [TexP, U32, U32]),
 }
 
 _LIB = None
@@ -794,6 +799,33 @@ def prefilter_ggx(env, dst, mip, roughness, samples, lod_bias=1.0, faces=(0, 6),
     g = L.GPU_MakeGraph()
     try:
         L.GPUX_OpPrefilterGGX(g, env, dst, mip, float(roughness), int(samples), float(lod_bias), int(faces[0]), int(faces[1]), int(rows[0]), int(rows[1]))
+        L.GPU_GraphSubmit(g)
+        L.GPU_GraphWait(g)
+    finally:
+        L.GPU_DestroyGraph(g)
+
+
+BrdfLut_SmithSchlick, BrdfLut_SmithCorrelated = 0, 1
+
+
+def brdf_lut_ggx_samples(count):
+    """GPUX_BrdfLutGGXSamples: the table K22 uses -> float32 [count][3] of {xi1, cos phi, sin phi}; host code, needs no GPU"""
+    n = int(count)
+    out = np.zeros((max(n, 1), 3), np.float32)
+    if n < 1 or n > 4096 or lib().GPUX_BrdfLutGGXSamples(n, out.ctypes.data_as(C.POINTER(C.c_float))) != 0:
+        raise ValueError("brdf_lut_ggx_samples: bad arguments")
+    return out
+
+
+def brdf_lut_ggx(tex, count, visibility=0, rows=None):
+    """Rows `rows` of the 2-D texture `tex` as the GGX split-sum LUT by K22 (GPUX_OpBrdfLutGGX in a graph of its own, blocking);
+    rows=None: the whole map."""
+    L = lib()
+    if rows is None:
+        rows = (0, tex.contents.height)
+    g = L.GPU_MakeGraph()
+    try:
+        L.GPUX_OpBrdfLutGGX(g, tex, int(count), int(visibility), int(rows[0]), int(rows[1]))
         L.GPU_GraphSubmit(g)
         L.GPU_GraphWait(g)
     finally:
